@@ -5,6 +5,7 @@ L=100, 224x224, batch 8 per GPU, bf16 inference) on N MI355X, one process per GP
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --mode train --workload rny008_b16          # BASELINE configs[2]: one optimisation step
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   # + the last timed step's output, DIR/head_out.npy
 
 A step = one pass of the whole hot path (uint8 clips resident in HBM -> per-frame logits) over one batch
 of B synthetic clips per GPU.  Clips shard over ranks with no data-path collective (inference), so
@@ -360,7 +361,7 @@ def infer_sub_record(workload, steps, repeats, depth, rank, dev, traffic_file, s
     T = cfg["clip_len"]
     sd = synth.make_state(state_layout.model_state_shapes(cfg), 0)
     # the headline's own streams when the caller has them: new streams created next to the (idle) ones of the headline and the
-    # feed measurement can land on a hardware queue one of them already holds (GPU_MAX_HW_QUEUES = 8), and two of the three
+    # feed measurement can land on a hardware queue one of them already holds, and two of the three
     # batches in flight then serialise -- measured 9.16-9.29 vs 8.82 ms per 800MF step
     streams = list(streams[:depth]) if streams is not None and len(streams) >= depth else [torch.cuda.Stream() for _ in range(depth)]
     with torch.cuda.stream(streams[0]):
@@ -485,6 +486,24 @@ def emit(out, full):
     except OSError:
         out["full_record"] = None
     print(json.dumps(out if full else compact_line(out)))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every tensor of `arrays` (device tensors of the timed path) as d/<name>.npy in float32 (float64 stays
+    float64).  The headline's outputs are a few KB; the limit only guards the option against a much larger workload."""
+    import numpy as np
+    host = {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32).numpy()
+            for k, v in arrays.items()}
+    total = sum(x.nbytes for x in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"bench: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(d, exist_ok=True)
+    for k, x in host.items():
+        np.save(os.path.join(d, k + ".npy"), x)
+
 
 def _cpu_model():
     try:
@@ -948,7 +967,15 @@ def main():
     ap.add_argument("--mode", default="infer", choices=["infer", "train"],
                     help="infer (default, the BASELINE metric): forward of configs[1]; train: one optimisation step "
                          "(train-mode forward + loss + backward + fused AdamW, gradient all-reduce over RCCL when N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0: the head output a caller "
+                         "of ForwardEngine.forward receives, fp32) as DIR/<name>.npy; the inputs depend on the arguments "
+                         "only, so two builds run with the same arguments can be compared output for output")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs is not None and a.mode != "infer":
+        ap.error("--dump-outputs is implemented for --mode infer (the headline forward)")
     if a.mode == "train":
         return main_train(a)
 
@@ -978,6 +1005,9 @@ def main():
     run(max(a.warmup, depth))
     walls, evs = timed_regions(run, a.steps, a.repeats, dev, streams)
     el = statistics.median(walls)
+    if a.dump_outputs is not None and rank == 0:
+        # step i of a timed region runs plans[i % depth]; read before any later measurement reuses the buffers
+        dump_outputs(a.dump_outputs, dict(head_out=plans[(a.steps - 1) % depth].head_out.view(B, T, -1)))
     if a.pmc_pass:
         if rank == 0:
             print(json.dumps({"pmc_pass": True, "workload": a.workload, "steps": a.steps, "ms_per_step": round(el / a.steps * 1e3, 4),

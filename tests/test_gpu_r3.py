@@ -301,7 +301,7 @@ def test_one_launch_bottleneck_equals_the_launch_per_layer_chain(h, w, C, gw, R,
     assert float(err) < 2e-2, float(err)
 
 
-def test_debug_flavour_runs_the_hot_path_without_a_trap():
+def test_debug_flavour_runs_the_hot_path_without_a_trap(tmp_path):
     """The asserting build (TDEED_LIB_FLAVOUR=debug: LDS offsets and table indices checked on the device) runs a small
     forward through the one-launch bottleneck, the SGP stage and the heads in a child process, and agrees with the release
     library on the logits."""
@@ -333,7 +333,7 @@ def test_debug_flavour_runs_the_hot_path_without_a_trap():
         "torch.save(out.cpu(), sys.argv[2])\n" % root)
     outs = []
     for flav, suffix in (("debug", "libtdeed_hip_dbg.so"), ("release", "libtdeed_hip.so")):
-        path = os.path.join("/tmp", f"tdeed_flavour_{flav}.pt")
+        path = str(tmp_path / f"tdeed_flavour_{flav}.pt")
         env = dict(os.environ, TDEED_LIB_FLAVOUR=flav)
         r = subprocess.run([sys.executable, "-c", code, suffix, path], env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, (flav, r.stdout[-2000:], r.stderr[-2000:])
