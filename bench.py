@@ -1,7 +1,8 @@
 """Headline benchmark: clips/s of the T-DEED forward (BASELINE.json configs[1]: RegNetY-200MF + GSF + SGP,
 L=100, 224x224, batch 8 per GPU, bf16 inference) on N MI355X, one process per GPU.
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10             # the headline alone: set up, warm up, time, print the line
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full      # + every side measurement and check (see --full)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --mode train --workload rny008_b16          # BASELINE configs[2]: one optimisation step
@@ -403,9 +404,9 @@ def infer_sub_record(workload, steps, repeats, depth, rank, dev, traffic_file, s
 
 
 # ---------------------------------------------------------------------------------------------- the printed line
-# The driver keeps 8 KB of head and 2 KB of tail of a line: the default line is therefore COMPACT (< 7 KB) with the numbers
-# a reader looks for hoisted as scalars right behind the contract's fields; `--full` prints every table (what
-# tools/prof_r05.sh stores under profiles/), and the full record is also left in gpurun_out/bench_full.json.
+# The driver keeps 8 KB of head and 2 KB of tail of a line: the printed line is therefore COMPACT (< 7 KB) with the numbers
+# a reader looks for hoisted as scalars right behind the contract's fields; `--tables` prints every table (what
+# tools/prof_r06.sh stores under profiles/), and emit() also leaves the whole record in a file of its own.
 _DROP_KEYS = {"note", "kernels", "ms_per_step_repeats", "by_processes", "by_threads", "families_ms", "traffic_source",
               "cpu_model", "measured", "workload", "thread_sweep", "sweep", "repeats", "hip_graph", "steps", "unit_note",
               "bn_bwd_family", "gemm_family", "narrow_bwd_family", "kernel_name", "slots", "algorithmic_bytes_per_launch", "host_cores"}
@@ -946,11 +947,18 @@ def main():
     ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; the median is reported")
     ap.add_argument("--workload", default="rny002_b8", choices=list(CONFIGS))
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the training-step sub-records of the default line")
-    ap.add_argument("--no-feed", action="store_true", help="skip the fed-from-pinned-host-memory measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full / --mode train: skip the CPU baselines")
+    ap.add_argument("--no-train", action="store_true",
+                    help="--full: skip the other configurations' forwards and the training-step sub-records")
+    ap.add_argument("--no-feed", action="store_true", help="--full: skip the fed-from-pinned-host-memory measurement")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every side measurement and check (--mode infer): the timed outputs "
+                         "against a fresh forward, single-batch latency, the fed-from-host rate, per-kernel times and rooflines, "
+                         "the CPU baseline and the logits against the oracle in fp32 / bf16, the forwards of the other "
+                         "configurations, the training-step records (--no-cpu-baseline / --no-train / --no-feed leave single "
+                         "ones out).  Off by default: a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--tables", action="store_true",
                     help="print every table (per-kernel tables, sweeps, notes); the default line is compact (< 7 KB: the driver "
                          "keeps 8 KB of a line's head) with the sub-records' headline numbers hoisted as scalars")
     ap.add_argument("--pmc-pass", action="store_true",
@@ -1012,6 +1020,27 @@ def main():
         if rank == 0:
             print(json.dumps({"pmc_pass": True, "workload": a.workload, "steps": a.steps, "ms_per_step": round(el / a.steps * 1e3, 4),
                               "hip_graph": not a.no_graph, "git_head": git_head()}))
+        return
+    out = None
+    if rank == 0:
+        # the headline record: everything in it comes from the timed regions above
+        ms = el / a.steps * 1e3
+        value = world * B * a.steps / el
+        out = dict(metric=f"clips/sec (L={T}, 224^2, {a.dtype}) forward, per-frame logits", value=round(value, 2),
+                   unit="clips/s", n_gpus=world, steps=a.steps, warmup=a.warmup, ms_per_step=round(ms, 4),
+                   higher_is_better=True, scaling="weak", vs_baseline=None, dtype=a.dtype, data="synthetic",
+                   config=dict(workload=f"{a.workload}: {cfg['feature_arch']} + ed_sgp_mixer n_layers={cfg['n_layers']} "
+                                        f"ks={cfg['sgp_ks']}, L={T}, {H}x{W}, batch {B}/GPU, inference forward, "
+                                        "random-init weights", clips_per_gpu=B, parallelism=f"dp{world} (clip-sharded, no collective)",
+                               hip_graph=not a.no_graph, batches_in_flight=depth,
+                               sub_batches_per_batch=len(plan.subs), **_dist_fields()),
+                   repeats=a.repeats, ms_per_step_repeats=[round(w / a.steps * 1e3, 4) for w in walls],
+                   ms_per_step_hip_events=round(statistics.median(evs) / a.steps, 4), git_head=git_head())
+    if not a.full:
+        # a plain run ends here: the side measurements and checks below belong to --full
+        if rank == 0:
+            emit(out, a.tables)
+        _leave(world)
         return
     out_check = check_timed_outputs(eng, plans, B, T, H, W, rank, dev)
     # latency of ONE batch with nothing else in flight (graph replay + sync per step)
@@ -1095,25 +1124,13 @@ def main():
         sgp_direct = sgp_stage_time(plan) if rank == 0 else None
 
     if rank == 0:
-        ms = el / a.steps * 1e3
-        value = world * B * a.steps / el
         roof = dominant_roofline(prof, dt, TRAFFIC_FILE if (a.workload == "rny002_b8" and a.dtype == "bf16") else None)
         sgp_roof = sgp_roofline(cfg, B, T, eng, plan, sgp_direct, sgp_stage_ms, dt,
                                 TRAFFIC_FILE if (a.workload == "rny002_b8" and a.dtype == "bf16") else None)
         kernels = kernels_table(prof)
         step_bytes, _ = forward_layer_bytes(cfg, B, H, W, dt, dev)     # layer-granular (fusion-independent), as in round 1 / 2
         step_flops = sum(s.flops for s in plan.steps)
-        out = dict(metric=f"clips/sec (L={T}, 224^2, {a.dtype}) forward, per-frame logits", value=round(value, 2),
-                   unit="clips/s", n_gpus=world, steps=a.steps, warmup=a.warmup, ms_per_step=round(ms, 4),
-                   higher_is_better=True, scaling="weak", vs_baseline=None, dtype=a.dtype, data="synthetic",
-                   config=dict(workload=f"{a.workload}: {cfg['feature_arch']} + ed_sgp_mixer n_layers={cfg['n_layers']} "
-                                        f"ks={cfg['sgp_ks']}, L={T}, {H}x{W}, batch {B}/GPU, inference forward, "
-                                        "random-init weights", clips_per_gpu=B, parallelism=f"dp{world} (clip-sharded, no collective)",
-                               hip_graph=not a.no_graph, batches_in_flight=depth,
-                               sub_batches_per_batch=len(plan.subs), **_dist_fields()),
-                   repeats=a.repeats, ms_per_step_repeats=[round(w / a.steps * 1e3, 4) for w in walls],
-                   ms_per_step_hip_events=round(statistics.median(evs) / a.steps, 4),
-                   latency_ms_inflight1=round(statistics.median(lat), 4),
+        out.update(latency_ms_inflight1=round(statistics.median(lat), 4),
                    roofline=roof,
                    roofline_step=dict(bound="hbm", note="whole forward, layer-granular algorithmic bytes (every fused layer "
                                       "reads its inputs and writes its output once) / ms_per_step",
@@ -1122,7 +1139,7 @@ def main():
                                       tflops=round(step_flops / (ms * 1e-3) / 1e12, 1)),
                    kernels=kernels,
                    roofline_sgp=sgp_roof, timed_output_check=out_check,
-                   fed_from_host=feed, cpu_baseline=None, git_head=git_head())
+                   fed_from_host=feed, cpu_baseline=None)
     del plans, plan, eng
     torch.cuda.empty_cache()
     if rank == 0:
@@ -1156,7 +1173,11 @@ def main():
                 tr[wk] = dict(error=f"{type(e).__name__}: {e}"[:300])
         out["train"] = tr
     if rank == 0:
-        emit(out, a.full)
+        emit(out, a.tables)
+    _leave(world)
+
+
+def _leave(world):
     if world > 1:
         import torch.distributed as dist
         tdist.barrier()                                          # rank 0's side measurements are over: leave together

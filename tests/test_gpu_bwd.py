@@ -218,20 +218,24 @@ def test_temporal_stack_loss_and_grads_match_autograd(dtype, geom):
 @pytest.mark.parametrize("M,C,relu,res", [(3000, 24, True, False), (5001, 152, True, True), (700, 368, False, False),
                                           (40000, 32, True, True)])
 def test_bn_train_fwd_bwd(bops, dtype, M, C, relu, res):
+    """The reference is autograd in float64 on the same (fp32 / bf16) inputs: the ReLU gate of an element is the sign of
+    z_hat * w + b + r, and the (40000, 32) case holds one element at -1.1e-7, where a float32 reference on the CPU takes
+    either sign depending on how many threads fold its batch statistics (8 or 16 threads: +4.8e-7, a gradient off by 0.19 of
+    the largest entry).  Same bounds as before."""
     z = (rnd(231, "z", (M, C), 1.5) + rnd(232, "mu", (C,), 0.5)).to(dtype)
     dy = rnd(233, "dy", (M, C)).to(dtype)
     r = rnd(234, "r", (M, C)).to(dtype) if res else None
     w, b = rnd(235, "w", (C,)) * 0.3 + 1.0, rnd(236, "b", (C,), 0.2)
     rm, rv = rnd(237, "rm", (C,), 0.1), rnd(238, "rv", (C,)).abs() + 0.5
-    zr, wr, br = z.float().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
-    rr = r.float().requires_grad_(True) if res else None
-    rm_ref, rv_ref = rm.clone(), rv.clone()
+    zr, wr, br = z.double().requires_grad_(True), w.double().requires_grad_(True), b.double().requires_grad_(True)
+    rr = r.double().requires_grad_(True) if res else None
+    rm_ref, rv_ref = rm.double(), rv.double()
     y = F.batch_norm(zr, rm_ref, rv_ref, wr, br, True, 0.1, 1e-5)
     if res:
         y = y + rr
     if relu:
         y = torch.relu(y)
-    y.backward(dy.float())
+    y.backward(dy.double())
     rm_d, rv_d = rm.clone().to(DEV), rv.clone().to(DEV)
     out, ctx = bops.bn_train(z.to(DEV), w.to(DEV), b.to(DEV), run_mean=rm_d, run_var=rv_d, res=None if r is None else r.to(DEV),
                              relu=relu)

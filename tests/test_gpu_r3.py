@@ -414,13 +414,13 @@ def test_s1_front_forms_agree(env):
 
 @pytest.mark.parametrize("flags", [[], ["--cu-mask", "interleave", "--inflight", "4"]])
 def test_bench_line_contract(flags):
-    """`bench.py` prints ONE JSON line with the contract's fields (short run, side measurements off); the same with every
-    in-flight batch's stream confined to its own XCDs (`--cu-mask`)."""
+    """`bench.py --full` prints ONE JSON line with the contract's fields and the roofline (short run, the long side
+    measurements off); the same with every in-flight batch's stream confined to its own XCDs (`--cu-mask`)."""
     import json
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--repeats", "1", "--no-train",
-                        "--no-feed", "--no-cpu-baseline", *flags], capture_output=True, text=True, timeout=900, cwd=root)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--repeats", "1", "--full",
+                        "--no-train", "--no-feed", "--no-cpu-baseline", *flags], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-1000:]
@@ -435,3 +435,38 @@ def test_bench_line_contract(flags):
         assert k in rf, k
     assert abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-3
     assert abs(d["value"] - d["config"]["clips_per_gpu"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-3
+    assert d["timed_output_check"]["finite"] is True and d["latency_ms_inflight1"] > 0
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` without `--full`: ONE JSON line with the contract's fields, computed from the
+    timed regions alone -- none of the side measurements or checks of `--full` has run -- and `--dump-outputs` still writes
+    the last timed step's logits.  The run spends at most 30 s outside its steps."""
+    import json
+    import subprocess
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=root)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-1000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config"):
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 2 and d["value"] > 0 and d["higher_is_better"] is True
+    assert d["unit"] == "clips/s" and d["dtype"] == "bf16" and d["config"]["workload"].startswith("rny002_b8")
+    assert abs(d["value"] - d["config"]["clips_per_gpu"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-3
+    for k in ("timed_output_check", "latency_ms_inflight1", "fed_from_host", "roofline_step", "roofline_sgp", "infer_800mf",
+              "infer_snb_t250", "train", "logit_max_abs_err_bf16"):
+        assert k not in d, k
+    assert d.get("roofline") is None and d.get("cpu_baseline") is None
+    # the whole process, start to exit, less its warm-up and timed steps: at most 30 s (measured: under 3 s)
+    outside = wall - (4 + 2) * d["ms_per_step"] * 1e-3
+    print(f"plain bench run: {wall:.2f} s in all, {outside:.2f} s outside its steps")
+    assert outside <= 30.0, outside
+    h = np.load(os.path.join(str(tmp_path), "head_out.npy"))
+    assert h.shape[:2] == (8, 100) and h.dtype == np.float32 and np.isfinite(h).all()
