@@ -387,6 +387,22 @@ int tdeed_multi_cast_transpose(const void* tab, int n, long tiles, int dtype, vo
 int tdeed_gather_cast(const float* src, const int* idx, long n, void* out, int dtype, void* stream);
 int tdeed_fill_u8_hash(uint8_t* dst, long n, uint64_t seed, void* stream); /* synthetic clips */
 
+/* ---- whole-video scoring (video.hip) ---------------------------------------------------------
+ * video: uint8 [L][frame_bytes] resident on the device; starts: DEVICE int32[B] (first video frame of each clip, may be
+ * negative or hang over the end).  clips_out[b][t] = video[starts[b] + t] when 0 <= starts[b] + t < L, else a zero frame
+ * (dataset/frame.py:580-626 with pad=True).  16-byte accesses when frame_bytes % 16 == 0 and both buffers are 16-byte
+ * aligned, a byte path otherwise.  B * T <= 65535. */
+int tdeed_clip_gather_u8(const uint8_t* video, int L, long frame_bytes, const int* starts, int B, int T,
+                         uint8_t* clips_out, void* stream);
+/* clip_scores fp32 [V][n][T][K1] (V views of n clips), starts: DEVICE int32[n].  Per video frame f, over the clips i in the
+ * order given with 0 <= f - starts[i] < T, view after view: track_sum[f] += clip_scores[v][i][f - starts[i]] and
+ * support[f] += 1 (count_all = 1: always; count_all = 0: only when the added row has a non-zero entry).  track_sum [L][K1]
+ * and support int32[L] are accumulated onto (the caller zeroes them); mean_out [L][K1] (or NULL) = track_sum /
+ * float(max(support, 1)).  One thread per frame, fixed order, no atomics: bit-identical to the host loop of
+ * util/eval.py:284-349. */
+int tdeed_stitch_scores(const float* clip_scores, int V, int n, int T, int K1, const int* starts, int count_all, int L,
+                        float* track_sum, int* support, float* mean_out, void* stream);
+
 /* ---- backward of the SGP encoder-decoder (training path; sgp_bwd.hip) ------------------------------------------
  * Activations and activation gradients share the forward dtype; parameter gradients are fp32.  Every parameter
  * gradient is produced as caller-owned per-workgroup partials (`part*`) folded in a fixed order: no float atomics,

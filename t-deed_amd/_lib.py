@@ -172,6 +172,8 @@ _SIGS = {
     "tdeed_cast_f32_to_bf16": ([P, P, c_long, P], c_int),
     "tdeed_multi_cast_transpose": ([P, c_int, c_long, c_int, P], c_int),
     "tdeed_fill_u8_hash": ([P, c_long, c_uint64, P], c_int),
+    "tdeed_clip_gather_u8": ([P, c_int, c_long, P, c_int, c_int, P, P], c_int),
+    "tdeed_stitch_scores": ([P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P], c_int),
     "tdeed_comm_unique_id": ([P], c_int),
     "tdeed_comm_init": ([POINTER(c_void_p), P, c_int, c_int], c_int),
     "tdeed_comm_info": ([P, POINTER(c_int), POINTER(c_int)], c_int),

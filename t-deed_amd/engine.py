@@ -1304,6 +1304,25 @@ class ForwardEngine:
         self.run_plan(plan)
         return plan.head_out, plan
 
+    def forward_from_video(self, video_u8, starts_dev, augment_inference=False, slot=0):
+        """forward() over clip windows of a frame buffer that is resident on the device: video_u8 uint8 (L,3,H,W), starts_dev
+        int32 (B,) on the device (first frame of each clip; windows that hang over either end are zero padded like the
+        evaluation reader's).  The windows are gathered straight into the plan's input buffers (ops.clip_gather, one launch
+        per sub-batch) in place of set_frames' copy of a materialised batch; same plan keys and graphs as forward(), so the
+        result carries the same bits as forward() on the materialised windows."""
+        if video_u8.dtype != torch.uint8 or video_u8.dim() != 4 or not video_u8.is_cuda:
+            raise TypeError("video frames must be a uint8 (L,3,H,W) tensor on the device")
+        if starts_dev.dtype != torch.int32 or starts_dev.dim() != 1 or not starts_dev.is_cuda:
+            raise TypeError("clip starts must be an int32 (B,) tensor on the device")
+        B = starts_dev.numel()
+        _, _, H, W = video_u8.shape
+        plan = self.plan(B, H, W, augment_inference, (), slot=slot)
+        Bs = B // len(plan.subs)
+        for i, sb in enumerate(plan.subs):
+            ops.clip_gather(video_u8, starts_dev[i * Bs:(i + 1) * Bs], self.pw.clip_len, sb.frames)
+        self.run_plan(plan)
+        return plan.head_out, plan
+
     def forward_augmented(self, frames, flip_frames=None):
         """Eval-mode forward (running-statistics BatchNorm) of frames that the caller has already cropped / augmented:
         frames (B,T,3,h,w) uint8 or fp32 0..255 on the GPU, flip_frames: optional uint8 (B*T,) per-frame h-flip flags.

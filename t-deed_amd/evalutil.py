@@ -77,6 +77,73 @@ def stitch_predictions(model, loader, videos, n_cols, augment=False):
     return st
 
 
+def video_clip_starts(num_frames, clip_len, overlap_len, stride=1, pad_len=5):
+    """First frame of every evaluation clip of one video, in sampled-frame units and in dataset order: the loop of
+    `ActionSpotVideoDataset.__init__` (dataset/frame.py:410-422) with the `start // stride` of its `__getitem__`
+    (frame.py:451).  On the sampled frames (L = ceil(num_frames / stride) of them) this is the same list as
+    video_clip_starts(L, clip_len, overlap_len, 1, pad_len): an integer is below num_frames / stride exactly when it is
+    below its ceiling."""
+    return [i // stride for i in range(-pad_len * stride, max(0, num_frames - overlap_len * stride),
+                                       (clip_len - overlap_len) * stride)]
+
+
+def stitch_clip_scores(scores, starts, L, flip_scores=None):
+    """numpy twin of the stitch kernel (ops.stitch_scores), and the statement of its order: per video frame, over the clips
+    in the order given, the plain view's row and then the flipped view's row are added one after the other.
+    scores (n,T,K+1) fp32, starts: n first frames (may be negative / hang over L).  Without flip_scores support counts
+    the added rows that are not all zero (`ScoreStitcher.add`); with flip_scores (n,T,K+1) it counts every added row
+    (`ScoreStitcher.add_views`, once per view).  Returns (sums (L,K+1) float32, support (L,) int32) -- equal, bit for bit,
+    to what ScoreStitcher's clip-major loop leaves in its track."""
+    scores = np.asarray(scores, np.float32)
+    views = [scores] if flip_scores is None else [scores, np.asarray(flip_scores, np.float32)]
+    n, T, K1 = scores.shape
+    sums = np.zeros((L, K1), np.float32)
+    support = np.zeros(L, np.int32)
+    for f in range(L):
+        for i in range(n):
+            t = f - int(starts[i])
+            if 0 <= t < T:
+                for p in views:
+                    sums[f] += p[i, t]
+                    support[f] += 1 if (flip_scores is not None or np.any(p[i, t] != 0)) else 0
+    return sums, support
+
+
+def stitch_videos(model, videos, n_cols, augment=False, batch_size=8, overlap_len=None, decode_ahead=1):
+    """Whole-video counterpart of `stitch_predictions`: `videos` yields (name, length, fps, frames) with frames a uint8
+    (length,3,H,W) tensor of the sampled frames or a callable returning one (e.g. a `feeder.load_video` closure); every
+    video goes through `model.predict_video` once and its (sums, support) become the video's track of the returned
+    ScoreStitcher, so `normalised()`, `frame_events`, both NMS functions and `mean_average_precisions` work on it
+    unchanged.  Callables run up to `decode_ahead` videos ahead on a worker thread: decoding video v+1 overlaps scoring
+    video v."""
+    from concurrent.futures import ThreadPoolExecutor
+    videos = list(videos)
+    st = ScoreStitcher([(v, n, f) for v, n, f, _ in videos], n_cols)
+    ahead = max(int(decode_ahead), 0)
+    with ThreadPoolExecutor(max_workers=1, thread_name_prefix="tdeed-video") as ex:
+        pending = {}
+
+        def fetch(j):
+            if j < len(videos) and j not in pending:
+                src = videos[j][3]
+                pending[j] = ex.submit(src) if callable(src) else None
+
+        for j, (name, length, _, src) in enumerate(videos):
+            for k in range(j, j + ahead + 1):
+                fetch(k)
+            fut = pending.pop(j)
+            frames = src if fut is None else fut.result()
+            if int(frames.shape[0]) != int(length):
+                raise ValueError(f"video {name}: {int(frames.shape[0])} frames delivered, {int(length)} announced")
+            sums, support = model.predict_video(frames, overlap_len=overlap_len, batch_size=batch_size, augment=augment)
+            if sums.shape[1] != n_cols:
+                raise ValueError(f"video {name}: the model scores {sums.shape[1]} columns, the stitcher holds {n_cols}")
+            track, sup = st.tracks[name]
+            track[...] = sums
+            sup[...] = support
+    return st
+
+
 def frame_events(norm_scores, classes, fps, high_recall_score_threshold=0.01, labels=None):
     """`process_frame_predictions[_challenge]` (util/eval.py:86-192): per video the arg-max events and the high-recall
     events (every class whose score passes the threshold).  classes: name -> index (1-based, 0 = background).

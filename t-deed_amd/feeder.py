@@ -46,6 +46,48 @@ def load_clip_video(frame_dir, dataset, video_name, start, end, pad=False, strid
     return load_clip(path_fn, start, end, stride=stride, pad=pad, out=out)
 
 
+def load_video(frame_dir, dataset, video_name, num_frames, stride=1, source_info=None, out=None, pool=None):
+    """All sampled frames of one video, each decoded ONCE: uint8 (L,3,H,W) with L = ceil(num_frames / stride), row j =
+    frame j*stride of the video (`frame_locator` file naming) -- the buffer `TDEEDModel.predict_video` keeps resident, from
+    which every overlapping clip window of the evaluation reader (`load_clip_video(..., pad=True)`) is a gather.
+    out: optional uint8 (>= L,3,H,W) tensor to decode into; otherwise a new one, page-locked when a GPU runtime is there.
+    pool: a DecodePool to decode the frames concurrently.
+    Trailing missing files (a video shorter than its label says) become zero frames, as the reference's end padding makes
+    them.  A missing file FOLLOWED by an existing one raises FileNotFoundError: the reference's reader appends the frames it
+    can read and pads the end (dataset/frame.py:609-626), which silently shifts every later frame of the clip forward;
+    that is not reproduced here."""
+    _, _, _, path_fn = frame_locator(frame_dir, dataset, video_name, source_info)
+    L = (int(num_frames) + stride - 1) // stride
+    names = [path_fn(j * stride) for j in range(L)]
+    have = [os.path.exists(p) for p in names]
+    n_real = L
+    while n_real > 0 and not have[n_real - 1]:
+        n_real -= 1
+    if n_real == 0:
+        raise FileNotFoundError(f"video {video_name}: no frame found (looked for {names[0] if names else frame_dir})")
+    if not all(have[:n_real]):
+        raise FileNotFoundError(f"video {video_name}: {names[have.index(False)]} is missing although later frames exist")
+    if out is None:
+        first = read_frame(names[0])
+        out = torch.zeros((L,) + tuple(first.shape), dtype=torch.uint8)
+        if torch.cuda.is_available():
+            out = out.pin_memory()
+        out[0].copy_(first)
+        jobs = [(names[j], out[j]) for j in range(1, n_real)]
+    else:
+        if out.shape[0] < L:
+            raise ValueError(f"the buffer holds {out.shape[0]} frames, the video has {L}")
+        if n_real < L:
+            out[n_real:L].zero_()
+        jobs = [(names[j], out[j]) for j in range(n_real)]
+    if pool is not None:
+        pool.decode(jobs)
+    else:
+        for nm, dst in jobs:
+            read_frame(nm, out=dst)
+    return out[:L]
+
+
 def load_clip(frame_path_fn, start, end, stride=1, pad=False, out=None):
     """`FrameReaderVideo.load_frames` (frame.py:558-626) for one clip: frames start, start+stride, ... < end through
     `frame_path_fn(frame_num) -> path`; frames before 0 pad the start with zeros, missing files pad the end (kept only

@@ -350,16 +350,153 @@ class TDEEDModel:
             pred, _ = self._model(seq.to(self.device), inference=True, augment_inference=augment_inference,
                                   act_dtype=dt)
             B, T = seq.shape[:2]
-            if isinstance(pred, dict):
-                head = pred["_head_out"].reshape(B * T, -1)
-                pw = self._model.engine(dt).pw
-                k1 = (self._args.num_classes + 1) if self._model._double_head else pw.n_cls
-                cls, scores = ops.process_prediction(head, B, T, k1, pw.displ_col)
-            else:
-                head = pred.reshape(B * T, -1).contiguous()
-                cls, scores = ops.process_prediction(head, B, T, head.shape[-1], -1)
+            cls, scores = self._process_pred(pred, B, T, dt)
             self._stream.synchronize()
         return cls.cpu().numpy(), scores.cpu().numpy()
+
+    def _score_cols(self, dt):
+        """number of score columns predict() / predict_video() deliver for the current head layout"""
+        pw = self._model.engine(dt).pw
+        if self._model._radi_displacement > 0 and self._model._double_head:
+            return self._args.num_classes + 1
+        return pw.n_cls
+
+    def _process_pred(self, pred, B, T, dt, out=None):
+        """model.py:351-367 on what Impl.forward returned (displacement column, no displacement, double head): softmax +
+        displacement scatter-max on the current stream -> (cls (B,T) int64, scores (B,T,K+1) fp32) on the device.
+        out: where to write the scores."""
+        if isinstance(pred, dict):
+            head = pred["_head_out"].reshape(B * T, -1)
+            pw = self._model.engine(dt).pw
+            return ops.process_prediction(head, B, T, self._score_cols(dt), pw.displ_col, out=out)
+        head = pred.reshape(B * T, -1).contiguous()
+        return ops.process_prediction(head, B, T, head.shape[-1], -1, out=out)
+
+    video_chunk_bytes = 64 << 20        # upload granularity of predict_video (one arrival event per chunk)
+
+    def predict_video(self, frames, clip_starts=None, overlap_len=None, pad_len=5, batch_size=8, augment=False, use_amp=True,
+                      max_resident_bytes=16 << 30):
+        """Score a whole video from one resident frame buffer: what the prediction loop of `evaluate` (util/eval.py:284-349)
+        leaves in its per-video track, -> (scores_sum (L,K+1) float32, support (L,) int32) numpy, i.e.
+        `ScoreStitcher.tracks[video]`.
+
+        frames: uint8 (L,3,H,W) sampled frames (frame j = original frame j*stride), a host tensor (pinned or not) or a
+        device tensor.  clip_starts: first sampled frame of every clip, in the order they are to be scored; default
+        `evalutil.video_clip_starts(L, clip_len, overlap_len, pad_len=pad_len)` with overlap_len = clip_len // 4 * 3.
+        Clips go through the forward in batches of `batch_size` in list order (the last one may be smaller, like a
+        DataLoader's); augment=True scores every batch a second time horizontally flipped.
+
+        Host frames are uploaded ONCE, in chunks of `video_chunk_bytes` on a copy stream; a batch waits only for the chunk
+        that holds its last frame.  Clip windows are gathered on the device into the engine's input buffers, consecutive
+        batches alternate over two engine slots / streams like epoch()'s validation loop, the clip scores stay on the
+        device and one stitch launch (ops.stitch_scores) adds them per frame in ScoreStitcher's order.  Apart from the
+        warm-up of a geometry seen for the first time (graph capture) the host synchronises once per video.
+        Raises ValueError when the video does not fit `max_resident_bytes`."""
+        from . import evalutil
+        from .streams import new_stream
+        if not isinstance(frames, torch.Tensor):
+            frames = torch.as_tensor(np.asarray(frames))
+        if frames.dtype != torch.uint8 or frames.dim() != 4:
+            raise TypeError("predict_video: frames must be a uint8 (L,3,H,W) tensor")
+        L = int(frames.shape[0])
+        fb = int(frames[0].numel()) if L else 0
+        if L == 0:
+            raise ValueError("predict_video: empty video")
+        if L * fb > max_resident_bytes:
+            raise ValueError(f"predict_video: the video needs {L * fb} bytes on the device, more than max_resident_bytes="
+                             f"{max_resident_bytes} (a ring buffer for longer videos is not implemented)")
+        T = self._args.clip_len
+        if clip_starts is None:
+            ov = T // 4 * 3 if overlap_len is None else int(overlap_len)
+            clip_starts = evalutil.video_clip_starts(L, T, ov, pad_len=pad_len)
+        starts = [int(s) for s in clip_starts]
+        n = len(starts)
+        if n == 0:
+            raise ValueError("predict_video: no clips")
+        if batch_size < 1:
+            raise ValueError("predict_video: batch_size must be positive")
+        V = 2 if augment else 1
+        self._model.eval()
+        dt = torch.bfloat16 if use_amp else torch.float32
+        eng = self._model.engine(dt)
+        pw = eng.pw
+        K1 = self._score_cols(dt)
+        dev = self.device
+        if self._stream is None:
+            self._stream = new_stream()
+        if getattr(self, "_stream2", None) is None:
+            self._stream2 = new_stream(avoid=[self._stream])
+        if getattr(self, "_copy_stream", None) is None:
+            self._copy_stream = new_stream(avoid=[self._stream, self._stream2])
+        streams, cp = [self._stream, self._stream2], self._copy_stream
+        cur = torch.cuda.current_stream()
+        for st in streams + [cp]:
+            st.wait_stream(cur)
+        # ---- the resident buffers (kept alive until the one synchronisation at the end)
+        starts_host = torch.tensor(starts, dtype=torch.int32).pin_memory()
+        starts_dev = torch.empty((n,), dtype=torch.int32, device=dev)
+        clip_scores = torch.empty((V, n, T, K1), dtype=torch.float32, device=dev)
+        with torch.cuda.stream(cp):
+            starts_dev.copy_(starts_host, non_blocking=True)
+            ev_starts = torch.cuda.Event()
+            ev_starts.record(cp)
+        h2d = 0
+        on_host = not frames.is_cuda
+        frames = frames.contiguous()
+        if on_host:
+            video = torch.empty(frames.shape, dtype=torch.uint8, device=dev)
+            per = max(1, int(self.video_chunk_bytes) // fb)
+            bounds = [(lo, min(lo + per, L)) for lo in range(0, L, per)]
+            arrived = []
+
+            def upload_through(c):
+                nonlocal h2d
+                with torch.cuda.stream(cp):
+                    while len(arrived) <= min(c, len(bounds) - 1):
+                        lo, hi = bounds[len(arrived)]
+                        video[lo:hi].copy_(frames[lo:hi], non_blocking=True)
+                        h2d += (hi - lo) * fb
+                        ev = torch.cuda.Event()
+                        ev.record(cp)
+                        arrived.append(ev)
+            if frames.is_pinned():
+                upload_through(len(bounds) - 1)       # asynchronous copies: queue the whole video behind the first chunk
+        else:
+            video = frames.to(dev)
+        # ---- the batches: gather -> forward -> post-processing, two in flight
+        n_batches = 0
+        for bi, lo in enumerate(range(0, n, batch_size)):
+            B = min(batch_size, n - lo)
+            slot = bi % 2
+            st = streams[slot]
+            need = ev_starts
+            if on_host:
+                last = min(L - 1, max(starts[lo:lo + B]) + T - 1)
+                if last >= 0:
+                    c = last // per
+                    upload_through(c + 1)             # pageable frames: the copy call stages on the host, keep one chunk ahead
+                    need = arrived[c]
+            with torch.cuda.stream(st):
+                st.wait_event(need)
+                for v in range(V):
+                    head, _ = eng.forward_from_video(video, starts_dev[lo:lo + B], augment_inference=bool(v), slot=slot)
+                    pred, _ = self._model._pack_head(head, B, T, pw.n_cls, pw.displ_col, None)
+                    # head is a view of the slot's buffer: consumed here, on the launching stream, before the slot runs again
+                    self._process_pred(pred, B, T, dt, out=clip_scores[v, lo:lo + B])
+            n_batches += 1
+        # ---- one stitch launch, one synchronisation
+        s0 = streams[0]
+        s0.wait_stream(streams[1])
+        s0.wait_stream(cp)
+        with torch.cuda.stream(s0):
+            track, support, _ = ops.stitch_scores(clip_scores, starts_dev, L, count_all=augment)
+            out_sum = torch.empty((L, K1), dtype=torch.float32).pin_memory()
+            out_sup = torch.empty((L,), dtype=torch.int32).pin_memory()
+            out_sum.copy_(track, non_blocking=True)
+            out_sup.copy_(support, non_blocking=True)
+            s0.synchronize()
+        self.last_video_stats = dict(frames=L, clips=n, batches=n_batches, views=V, frames_h2d_bytes=h2d)
+        return out_sum.numpy().copy(), out_sup.numpy().copy()
 
     def epoch(self, loader, optimizer=None, scaler=None, lr_scheduler=None, acc_grad_iter=1, fg_weight=5,
               valMAP=False):

@@ -611,12 +611,57 @@ def adamw_step(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), e
     return param
 
 
-def process_prediction(head_out, B, T, K1, displ_col):
+def process_prediction(head_out, B, T, K1, displ_col, out=None):
+    """out: optional contiguous fp32 (B,T,K1) tensor (e.g. a slice of a per-video score buffer) to write the scores into."""
     ld = head_out.shape[-1]
-    scores = torch.empty((B, T, K1), dtype=torch.float32, device=head_out.device)
+    if out is None:
+        scores = torch.empty((B, T, K1), dtype=torch.float32, device=head_out.device)
+    else:
+        if out.dtype != torch.float32 or tuple(out.shape) != (B, T, K1) or not out.is_contiguous():
+            raise ValueError(f"process_prediction: out must be a contiguous float32 {(B, T, K1)} tensor")
+        scores = out
     cls = torch.empty((B, T), dtype=torch.int64, device=head_out.device)
     call("tdeed_process_prediction", ptr(head_out), B, T, ld, K1, displ_col, ptr(scores), ptr(cls), stream_ptr())
     return cls, scores
+
+
+def clip_gather(video_u8, starts_dev, T, out):
+    """out[b*T + t] = video_u8[starts[b] + t], zero frames outside [0, L) (the evaluation reader's padding).
+    video_u8: uint8 (L, ...) on the device; starts_dev: int32 (B,) on the device; out: uint8 buffer of B*T frames."""
+    if video_u8.dtype != torch.uint8 or out.dtype != torch.uint8 or starts_dev.dtype != torch.int32:
+        raise TypeError("clip_gather: uint8 frames and int32 starts")
+    if not (video_u8.is_contiguous() and out.is_contiguous() and starts_dev.is_contiguous()):
+        raise ValueError("clip_gather: contiguous tensors only")
+    L, B = video_u8.shape[0], starts_dev.numel()
+    fb = video_u8[0].numel()
+    if out.numel() != B * T * fb:
+        raise ValueError(f"clip_gather: out holds {out.numel()} bytes, {B} clips of {T} frames need {B * T * fb}")
+    call("tdeed_clip_gather_u8", ptr(video_u8), L, fb, ptr(starts_dev), B, T, ptr(out), stream_ptr())
+    return out
+
+
+def stitch_scores(clip_scores, starts_dev, L, count_all=None, track_sum=None, support=None, mean=False):
+    """clip_scores fp32 (V,n,T,K1), starts_dev int32 (n,) on the device -> (track_sum (L,K1), support (L,) int32, mean
+    (L,K1) | None): the device twin of evalutil.ScoreStitcher (add per clip for count_all=False, add_views per view for
+    count_all=True; default: True when V > 1).  track_sum / support: accumulate onto these instead of fresh zeros."""
+    V, n, T, K1 = clip_scores.shape
+    if clip_scores.dtype != torch.float32 or starts_dev.dtype != torch.int32 or not clip_scores.is_contiguous():
+        raise TypeError("stitch_scores: contiguous float32 scores and int32 starts")
+    if starts_dev.numel() != n:
+        raise ValueError(f"stitch_scores: {starts_dev.numel()} starts for {n} clips")
+    dev = clip_scores.device
+    if track_sum is None:
+        track_sum = torch.zeros((L, K1), dtype=torch.float32, device=dev)
+    if support is None:
+        support = torch.zeros((L,), dtype=torch.int32, device=dev)
+    if tuple(track_sum.shape) != (L, K1) or tuple(support.shape) != (L,) or track_sum.dtype != torch.float32 \
+            or support.dtype != torch.int32 or not (track_sum.is_contiguous() and support.is_contiguous()):
+        raise ValueError("stitch_scores: track_sum float32 (L,K1) and support int32 (L,), contiguous")
+    mean_out = torch.empty((L, K1), dtype=torch.float32, device=dev) if mean else None
+    ca = (V > 1) if count_all is None else bool(count_all)
+    call("tdeed_stitch_scores", ptr(clip_scores), V, n, T, K1, ptr(starts_dev), int(ca), L, ptr(track_sum), ptr(support),
+         ptr(mean_out), stream_ptr())
+    return track_sum, support, mean_out
 
 
 def cast_bf16(src_f32):

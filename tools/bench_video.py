@@ -1,0 +1,160 @@
+"""Whole-video scoring against the clip-batch route, in ONE process, alternating the routes.
+
+    python tools/bench_video.py [--frames 2030] [--repeats 5]          one JSON line
+    python tools/bench_video.py --gather-only                           the gather launch alone (run it under
+                                                                        `rocprofv3 --kernel-trace --stats -- python ...`)
+    python tools/bench_video.py --decode [--decode-frames 400]          host only: load_video vs clip_batches, JPEG decode
+
+Routes (RegNetY-200MF, T = 100, 224 x 224, bf16; 3/4 overlap like the evaluation datasets):
+  A  the clip route: `evalutil.stitch_predictions` over host-resident PINNED uint8 clip batches of the video, at loader
+     batch size 4 (the reference's INFERENCE_BATCH_SIZE) and 8; with augment=True at batch size 1, the only batch size the
+     route (like the reference's) supports there.
+  B  `TDEEDModel.predict_video(batch_size=8)` from the pinned frames of the video.
+Every shape is warmed up once (plan build, graph capture); then the routes alternate, `--repeats` timed passes each."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import tdeed_amd  # noqa: E402,F401
+from tdeed_amd import synth, state_layout, ops, feeder  # noqa: E402
+from tdeed_amd import evalutil as E  # noqa: E402
+
+CFG = dict(feature_arch="rny002_gsf", clip_len=100, crop_dim=224, n_layers=2, sgp_ks=7, sgp_r=4, num_classes=4,
+           radi_displacement=2)
+H = W = 224
+COPY_GBPS = 6290.0        # measured HBM3E copy bandwidth of the MI355X (16-byte copy kernel, read + write; 8 TB/s spec), GB/s
+
+
+def _stat(times, frames, clips):
+    t = np.asarray(times)
+    med = float(np.median(t))
+    return dict(ms_median=round(med * 1e3, 2), ms_min=round(float(t.min()) * 1e3, 2), ms_max=round(float(t.max()) * 1e3, 2),
+                frames_per_s=round(frames / med, 1), clips_per_s=round(clips / med, 1),
+                clips_per_s_min=round(clips / float(t.max()), 1), clips_per_s_max=round(clips / float(t.min()), 1))
+
+
+def bench(a):
+    from tdeed_amd.model import TDEEDModel
+    from types import SimpleNamespace
+    T, L = CFG["clip_len"], a.frames
+    m = TDEEDModel(device="cuda", args=SimpleNamespace(modality="rgb", temporal_arch="ed_sgp_mixer", pretrain=None, **CFG))
+    m.load({k: torch.from_numpy(v) for k, v in synth.make_state(state_layout.model_state_shapes(CFG), 0).items()})
+    video = ops.fill_u8_hash((L, 3, H, W), 9, "cuda").cpu().pin_memory()
+    starts = E.video_clip_starts(L, T, T // 4 * 3)
+    n = len(starts)
+    fb = 3 * H * W
+    # route A's input: every clip window materialised on the host, pinned
+    clips = torch.zeros((n, T, 3, H, W), dtype=torch.uint8).pin_memory()
+    for i, s in enumerate(starts):
+        lo, hi = max(s, 0), min(s + T, L)
+        clips[i, lo - s:hi - s] = video[lo:hi]
+    videos = [("v", L, 25.0)]
+
+    def loader(bs):
+        return [dict(frame=clips[lo:lo + bs], video=["v"] * len(starts[lo:lo + bs]), start=np.array(starts[lo:lo + bs]))
+                for lo in range(0, n, bs)]
+
+    out = dict(kind="video_scoring", cfg=CFG, frames=L, clips=n, repeats=a.repeats, settings={})
+    for augment in (False, True):
+        routes = {}
+        if augment:
+            routes["A_bs1"] = lambda: E.stitch_predictions(m, loader(1), videos, 5, augment=True).tracks["v"]
+        else:
+            routes["A_bs4"] = lambda: E.stitch_predictions(m, loader(4), videos, 5).tracks["v"]
+            routes["A_bs8"] = lambda: E.stitch_predictions(m, loader(8), videos, 5).tracks["v"]
+        routes["B_bs8"] = lambda: m.predict_video(video, batch_size=8, augment=augment)
+        res = {k: fn() for k, fn in routes.items()}                     # warm-up of every shape
+        times = {k: [] for k in routes}
+        for _ in range(a.repeats):
+            for k, fn in routes.items():                                # alternating
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                times[k].append(time.perf_counter() - t0)
+        V = 2 if augment else 1
+        st = {k: _stat(v, L, n * V) for k, v in times.items()}
+        for k in st:
+            st[k]["frame_bytes_h2d"] = m.last_video_stats["frames_h2d_bytes"] if k.startswith("B") else n * V * T * fb
+        ref = "A_bs1" if augment else "A_bs8"
+        eq = dict(reference=ref, sums_equal=bool(np.array_equal(res[ref][0], res["B_bs8"][0])),
+                  support_equal=bool(np.array_equal(res[ref][1], res["B_bs8"][1])),
+                  max_abs_diff=float(np.abs(res[ref][0] - res["B_bs8"][0]).max()))
+        acc = {}
+        for k in st:
+            if k.startswith("A"):
+                spread = st[k]["clips_per_s_max"] - st[k]["clips_per_s_min"]
+                acc[k] = dict(ratio_B_over_A=round(st["B_bs8"]["clips_per_s"] / st[k]["clips_per_s"], 3),
+                              B_not_below_A_minus_spread=bool(st["B_bs8"]["clips_per_s"] >= st[k]["clips_per_s"] - spread))
+        out["settings"]["augment" if augment else "plain"] = dict(routes=st, equality=eq, acceptance=acc)
+    if not out["settings"]["plain"]["equality"]["sums_equal"]:
+        out["error"] = "predict_video differs from the clip route at batch size 8 without augmentation"
+    print(json.dumps(out))
+    return 0 if "error" not in out else 1
+
+
+def gather_only(a):
+    T, B, L = 100, 8, 400
+    video = ops.fill_u8_hash((L, 3, H, W), 9, "cuda")
+    sd = torch.tensor([-5, 20, 45, 70, 95, 120, 145, 170], dtype=torch.int32, device="cuda")
+    out = torch.empty((B * T, 3, H, W), dtype=torch.uint8, device="cuda")
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for _ in range(5):
+        ops.clip_gather(video, sd, T, out)
+    ev[0].record()
+    for _ in range(a.repeats * 10):
+        ops.clip_gather(video, sd, T, out)
+    ev[1].record()
+    torch.cuda.synchronize()
+    us = ev[0].elapsed_time(ev[1]) * 1e3 / (a.repeats * 10)
+    moved = 2 * B * T * 3 * H * W
+    print(json.dumps(dict(kind="clip_gather", B=B, T=T, frame_bytes=3 * H * W, us_per_launch_events=round(us, 2),
+                          bytes_moved=moved, bound_us_at_copy_bandwidth=round(moved / (COPY_GBPS * 1e3), 2),
+                          copy_bandwidth_GBps=COPY_GBPS)))
+    return 0
+
+
+def decode(a):
+    """host only, measured on whichever host runs it: every sampled frame once (load_video) against the clip reader at 3/4
+    overlap (clip_batches), same JPEG tree, same thread pool"""
+    import tempfile
+    from PIL import Image
+    n, T = a.decode_frames, 100
+    with tempfile.TemporaryDirectory() as tmp:
+        d = os.path.join(tmp, "vid")
+        os.makedirs(d)
+        for i in range(n):
+            Image.fromarray(synth.uint8_clip(700 + i % 16, (H, W, 3))).save(os.path.join(d, f"frame{i}.jpg"), quality=92)
+        pool = feeder.DecodePool(a.threads)
+        t0 = time.perf_counter()
+        feeder.load_video(tmp, "soccernetball", "vid", n, pool=pool)
+        t_video = time.perf_counter() - t0
+        starts = [s for s in E.video_clip_starts(n, T, 75) if s + T > 0]
+        descs = [dict(paths=feeder.load_paths(tmp, "soccernetball", "vid", s, s + T)) for s in starts]
+        t0 = time.perf_counter()
+        nb = sum(1 for _ in feeder.clip_batches(descs, 1, (3, H, W), T, pool=pool))
+        t_clips = time.perf_counter() - t0
+        pool.close()
+    print(json.dumps(dict(kind="video_decode_host_only", frames=n, clips=nb, threads=pool.threads,
+                          load_video_frames_per_s=round(n / t_video, 1), load_video_s=round(t_video, 3),
+                          clip_batches_video_frames_per_s=round(n / t_clips, 1), clip_batches_s=round(t_clips, 3),
+                          ratio=round(t_clips / t_video, 2))))
+    return 0
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=2030)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--gather-only", action="store_true")
+    ap.add_argument("--decode", action="store_true")
+    ap.add_argument("--decode-frames", type=int, default=400)
+    ap.add_argument("--threads", type=int, default=8)
+    a = ap.parse_args()
+    sys.exit(decode(a) if a.decode else gather_only(a) if a.gather_only else bench(a))

@@ -436,6 +436,39 @@ def frame_reader(name="frame_reader"):
                     layouts={k: [v[0], v[1]] for k, v in layouts.items()}), **arrays)
 
 
+def video_clips(name="video_clips"):
+    """The clip lists of the reference's evaluation dataset (dataset/frame.py:385-452 ActionSpotVideoDataset): per case the
+    (video, start) list of `_clips` in dataset order and the (name, length, fps) triples of `.videos`, from a temporary
+    label file.  Dataset names other than soccernet / soccernetball (those read label paths at construction).  Covers
+    strides 1, 2, 12, videos shorter than a clip, videos no longer than overlap_len * stride (the range's end collapses
+    to 0) and lengths that are no multiple of the stride."""
+    import tempfile
+    import dataset.frame as rframe
+    lengths = [3, 6, 7, 8, 37, 75, 100, 101, 430, 899, 1201]
+    settings = [  # (clip_len, overlap_len, stride, dataset)
+        (8, 6, 1, "finediving"), (8, 6, 2, "finediving"), (8, 6, 12, "fs_comp"), (8, 4, 1, "tennis"), (8, 0, 2, "fs_perf"),
+        (100, 75, 1, "finediving"), (100, 75, 2, "fs_comp"), (100, 50, 12, "tennis"), (100, 75, 12, "fs_perf"),
+    ]
+    arrays, cases = {}, []
+    with tempfile.TemporaryDirectory() as tmp:
+        labels = [dict(video=f"v{n:05d}", num_frames=n, fps=25.0, events=[]) for n in lengths]
+        lf = os.path.join(tmp, "labels.json")
+        with open(lf, "w") as fh:
+            json.dump(labels, fh)
+        for ci, (clip_len, overlap, stride, ds) in enumerate(settings):
+            d = rframe.ActionSpotVideoDataset({}, lf, tmp, "rgb", clip_len, overlap_len=overlap, stride=stride, dataset=ds)
+            vids = [v for v, _ in d._clips]
+            arrays[f"clip_video__{ci}"] = np.array([lengths.index(int(v[1:])) for v in vids], np.int32)
+            arrays[f"clip_start__{ci}"] = np.array([s for _, s in d._clips], np.int64)
+            arrays[f"clip_start_sampled__{ci}"] = np.array([s // stride for _, s in d._clips], np.int64)   # frame.py:451
+            vv = d.videos
+            arrays[f"videos_len__{ci}"] = np.array([n for _, n, _ in vv], np.int64)
+            arrays[f"videos_fps__{ci}"] = np.array([f for _, _, f in vv], np.float64)
+            cases.append(dict(clip_len=clip_len, overlap_len=overlap, stride=stride, dataset=ds, pad_len=rframe.DEFAULT_PAD_LEN,
+                              videos=[v for v, _, _ in vv]))
+    save(name, dict(kind="video_clips", lengths=lengths, names=[f"v{n:05d}" for n in lengths], cases=cases), **arrays)
+
+
 # ----------------------------------------------------------------------------- training (VERDICT r4 item 3; SURVEY 8c)
 TRAIN_KEYS = [
     "_features.stem.conv.weight", "_features.stem.bn.weight", "_features.s1.b1.downsample.conv.weight",
@@ -604,6 +637,7 @@ CASES = {
     "init_stats": lambda: init_stats(),
     "timm_keymap": lambda: timm_keymap(),
     "frame_reader": lambda: frame_reader(),
+    "video_clips": lambda: video_clips(),
     "misc_ops": lambda: mod_misc(),
     "loss_postproc": lambda: mod_loss(),
     "eval_utils": lambda: mod_eval_utils(),
