@@ -403,6 +403,29 @@ int tdeed_clip_gather_u8(const uint8_t* video, int L, long frame_bytes, const in
 int tdeed_stitch_scores(const float* clip_scores, int V, int n, int T, int K1, const int* starts, int count_all, int L,
                         float* track_sum, int* support, float* mean_out, void* stream);
 
+/* ---- event spotting on the resident track (spot.hip) --------------------------------------------------------------
+ * mean fp32 [L][K1] (tdeed_stitch_scores' mean_out).  pred int32[L]: first maximum of each row (np.argmax), pred_score
+ * fp32[L] that entry.  Per class c >= 1 the frames with mean[f][c] >= hr_threshold (fp32 comparison, util/eval.py:160):
+ * count[c] += their number, first_frame[c] = min(first_frame[c], the first of them).  pred_u8 (or NULL; K1 <= 256): pred in
+ * one byte per frame, the form in which it is copied to the host.  The caller fills first_frame
+ * int32[K1] with L and count int32[K1] with 0. */
+int tdeed_frame_events(const float* mean, int L, int K1, float hr_threshold, int* pred, unsigned char* pred_u8, float* pred_score,
+                       int* first_frame, int* count, void* stream);
+/* bytes of workspace tdeed_nms_track needs for this track (0: the suppression state fits the LDS of a workgroup) */
+long tdeed_nms_track_workspace(int L, int K1);
+/* Exact hard (soft = 0, util/eval.py:195-226) or soft (soft = 1, util/eval.py:228-261) non-maximum suppression of the
+ * high-recall candidates of every class c >= 1 (frames with mean[f][c] >= hr_threshold, score (double)mean[f][c]), one
+ * workgroup per class, in rounds (evalutil.nms_rounds states the rule); events are kept while their score is >= threshold
+ * (double comparison).  windows: HOST int32[n_windows], n_windows = 1 (every class) or >= K1 - 1 (indexed by the rank of
+ * (first_frame[c], c) among the classes that have a candidate: the order in which labels appear in the host's list); soft
+ * needs windows >= 1.  first_frame: DEVICE int32[K1] as tdeed_frame_events leaves it.  emitted uint8 [K1][L] and kept_score
+ * double [K1][L] are scratch.  Output: out_count[0] events in out_frame / out_class (int32) / out_score (double), each with
+ * room for L * (K1 - 1) entries (out_class_u8, or NULL: the classes once more in one byte each, for the copy to the host), ordered by ascending frame and within a frame by that rank (the host's stable sort);
+ * rounds int32[K1]: rounds taken per class (<= its candidates).  Deterministic; K1 - 1 <= 64. */
+int tdeed_nms_track(const float* mean, int L, int K1, float hr_threshold, double threshold, int soft, const int* windows,
+                    int n_windows, const int* first_frame, void* workspace, unsigned char* emitted, double* kept_score,
+                    int* out_frame, int* out_class, unsigned char* out_class_u8, double* out_score, int* out_count, int* rounds, void* stream);
+
 /* ---- backward of the SGP encoder-decoder (training path; sgp_bwd.hip) ------------------------------------------
  * Activations and activation gradients share the forward dtype; parameter gradients are fp32.  Every parameter
  * gradient is produced as caller-owned per-workgroup partials (`part*`) folded in a fixed order: no float atomics,

@@ -6,7 +6,7 @@ PyTorch-ROCm already loaded (same SONAME) and streams / device pointers are inte
 """
 import ctypes
 import os
-from ctypes import c_int, c_long, c_float, c_void_p, c_char_p, c_uint64, POINTER
+from ctypes import c_int, c_long, c_float, c_double, c_void_p, c_char_p, c_uint64, POINTER
 
 import torch  # noqa: F401  (must precede CDLL: see module docstring)
 
@@ -174,6 +174,9 @@ _SIGS = {
     "tdeed_fill_u8_hash": ([P, c_long, c_uint64, P], c_int),
     "tdeed_clip_gather_u8": ([P, c_int, c_long, P, c_int, c_int, P, P], c_int),
     "tdeed_stitch_scores": ([P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P], c_int),
+    "tdeed_frame_events": ([P, c_int, c_int, c_float, P, P, P, P, P, P], c_int),
+    "tdeed_nms_track_workspace": ([c_int, c_int], c_long),
+    "tdeed_nms_track": ([P, c_int, c_int, c_float, c_double, c_int, P, c_int, P, P, P, P, P, P, P, P, P, P, P], c_int),
     "tdeed_comm_unique_id": ([P], c_int),
     "tdeed_comm_init": ([POINTER(c_void_p), P, c_int, c_int], c_int),
     "tdeed_comm_info": ([P, POINTER(c_int), POINTER(c_int)], c_int),

@@ -258,6 +258,110 @@ def soft_non_maximum_suppression(pred, window, threshold=0.01):
     return out
 
 
+def label_order(first_frame, L):
+    """Classes (>= 1) that have a high-recall candidate, in the order in which their labels first appear in the high-recall
+    list (`_by_label`'s insertion order): by (first candidate frame, class).  first_frame: (K+1,), L where a class has none."""
+    return sorted((c for c in range(1, len(first_frame)) if first_frame[c] < L), key=lambda c: (int(first_frame[c]), c))
+
+
+def nms_rounds(mean, window, threshold, soft, hr_threshold=0.01):
+    """numpy twin of the suppression kernel (ops.nms_track), and the statement of its order.  mean (L,K+1) fp32 (a
+    normalised track); the candidates of class c >= 1 are the frames with mean[f,c] >= float32(hr_threshold), their score is
+    float64(mean[f,c]) -- the high-recall list of `frame_events`.  The greedy loop of `non_maximum_suppression` /
+    `soft_non_maximum_suppression` is replaced by rounds: in each round every live candidate with score >= threshold wins
+    when no live candidate within +-R frames beats it in (score descending, frame ascending) order, and all winners of the
+    round are kept at once.  Hard (R = w): a winner removes every candidate within +-w; scores never change.  Soft
+    (R = 2w, so the winners of one round share no neighbour): a winner at p sets s[g] = s[g] * (p-g)^2 / w^2 for every live
+    g within +-w, then only the winner is removed.  window: an int, or a list indexed by the label's appearance rank
+    (`label_order`).  Returns (frames int32, classes int32, scores float64, rounds (K+1,) int32), events in the host's
+    order: ascending frame, within a frame by appearance rank -- equal, bit for bit, to the two host functions applied to
+    `frame_events(...)[1]`."""
+    mean = np.asarray(mean, np.float32)
+    L, K1 = mean.shape
+    cand = mean >= np.float32(hr_threshold)
+    cand[:, 0] = False
+    first = np.where(cand.any(axis=0), cand.argmax(axis=0), L)
+    rounds = np.zeros(K1, np.int32)
+    kept = []                                                   # (frame, rank, class, score)
+    for rank, c in enumerate(label_order(first, L)):
+        w = int(_class_window(window, rank))
+        if w < (1 if soft else 0):
+            raise ValueError(f"nms_rounds: window {w}")
+        reach = min(2 * w if soft else w, L - 1)
+        alive = cand[:, c].copy()
+        s = mean[:, c].astype(np.float64)
+        for _ in range(int(alive.sum())):                       # every round keeps at least the best live candidate
+            elig = alive & (s >= threshold)
+            if not elig.any():
+                break
+            rounds[c] += 1
+            win = elig.copy()
+            for d in range(1, reach + 1):
+                win[d:] &= ~(alive[:-d] & (s[:-d] >= s[d:]))    # an earlier frame wins ties
+                win[:-d] &= ~(alive[d:] & (s[d:] > s[:-d]))
+            for p in np.nonzero(win)[0]:
+                kept.append((int(p), rank, c, float(s[p])))
+            for p in np.nonzero(win)[0]:
+                lo, hi = max(p - w, 0), min(p + w, L - 1)
+                if soft:
+                    g = np.arange(lo, hi + 1)
+                    g = g[alive[g]]
+                    s[g] = s[g] * np.abs(p - g) ** 2 / (w ** 2)
+                    alive[p] = False
+                else:
+                    alive[lo:hi + 1] = False
+    kept.sort(key=lambda e: (e[0], e[1]))
+    return (np.array([e[0] for e in kept], np.int32), np.array([e[2] for e in kept], np.int32),
+            np.array([e[3] for e in kept], np.float64), rounds)
+
+
+def event_dicts(frames, classes_idx, scores, inv):
+    """(frames, class indices, scores) arrays -> the reference's event dicts; inv: class index -> label."""
+    return [{"label": inv[int(c)], "frame": int(f), "score": float(s)} for f, c, s in zip(frames, classes_idx, scores)]
+
+
+def spot_videos(model, videos, classes, suppress, high_recall_score_threshold=0.01, augment=False, batch_size=8,
+                overlap_len=None, decode_ahead=1):
+    """Whole-video counterpart of `stitch_videos` + `frame_events` + the two NMS functions with the tail on the device:
+    `videos` as in `stitch_videos`; every video goes through `model.spot_video` once.  suppress: entries (kind, window,
+    threshold) with kind "nms" | "snms".  Returns (pred_events, [one list of video records per suppress entry],
+    {video: pred (L,) int32}), videos in sorted order, records as `frame_events` / `non_maximum_suppression` /
+    `soft_non_maximum_suppression` build them ('num_events' included), so `mean_average_precisions` works on them
+    unchanged.  The label-dependent error / F1 counters of `frame_events` follow from the returned pred on the host."""
+    from concurrent.futures import ThreadPoolExecutor
+    videos = list(videos)
+    suppress = [tuple(e) for e in suppress]
+    inv = {v: k for k, v in classes.items()}
+    ahead = max(int(decode_ahead), 0)
+    done = {}
+    with ThreadPoolExecutor(max_workers=1, thread_name_prefix="tdeed-video") as ex:
+        pending = {}
+
+        def fetch(j):
+            if j < len(videos) and j not in pending:
+                src = videos[j][3]
+                pending[j] = ex.submit(src) if callable(src) else None
+
+        for j, (name, length, fps, src) in enumerate(videos):
+            for k in range(j, j + ahead + 1):
+                fetch(k)
+            fut = pending.pop(j)
+            frames = src if fut is None else fut.result()
+            if int(frames.shape[0]) != int(length):
+                raise ValueError(f"video {name}: {int(frames.shape[0])} frames delivered, {int(length)} announced")
+            done[name] = (fps, model.spot_video(frames, classes, suppress=suppress,
+                                                high_recall_score_threshold=high_recall_score_threshold,
+                                                overlap_len=overlap_len, batch_size=batch_size, augment=augment))
+    pred_events, lists, preds = [], [[] for _ in suppress], {}
+    for name in sorted(done):
+        fps, r = done[name]
+        pred_events.append({"video": name, "events": r["events"], "fps": fps})
+        for i, evs in enumerate(r["suppressed"]):
+            lists[i].append({"video": name, "events": evs, "fps": fps, "num_events": len(evs)})
+        preds[name] = r["pred"]
+    return pred_events, lists, preds
+
+
 def average_precision(pred, truth, tolerance=0):
     """util/score.py:45-96.  pred: [(video, frame, score)] sorted by descending score; truth: video -> [frames].
     Greedy matching: every prediction takes the closest not-yet-recalled ground-truth frame of its video (first one wins

@@ -392,6 +392,92 @@ class TDEEDModel:
         device and one stitch launch (ops.stitch_scores) adds them per frame in ScoreStitcher's order.  Apart from the
         warm-up of a geometry seen for the first time (graph capture) the host synchronises once per video.
         Raises ValueError when the video does not fit `max_resident_bytes`."""
+        track, support, _, s0, stats, keep = self._video_track(frames, clip_starts, overlap_len, pad_len, batch_size, augment,
+                                                               use_amp, max_resident_bytes, want_mean=False)
+        L, K1 = track.shape
+        with torch.cuda.stream(s0):
+            out_sum = torch.empty((L, K1), dtype=torch.float32).pin_memory()
+            out_sup = torch.empty((L,), dtype=torch.int32).pin_memory()
+            out_sum.copy_(track, non_blocking=True)
+            out_sup.copy_(support, non_blocking=True)
+            s0.synchronize()
+        del keep
+        self.last_video_stats = stats
+        return out_sum.numpy().copy(), out_sup.numpy().copy()
+
+    def spot_video(self, frames, classes, suppress=(("nms", 1, 0.01), ("snms", 3, 0.01)), high_recall_score_threshold=0.01,
+                   clip_starts=None, overlap_len=None, pad_len=5, batch_size=8, augment=False, use_amp=True,
+                   max_resident_bytes=16 << 30):
+        """Score a whole video like predict_video and spot its events on the device: the tail of `evaluate`
+        (util/eval.py:87-261, 386-391) -- `frame_events` and (soft) non-maximum suppression of the high-recall list -- without
+        the (L,K+1) track ever leaving the device.  classes: name -> index (1-based); suppress: entries (kind, window,
+        threshold), kind "nms" | "snms", window an int or a list indexed by label appearance like the reference's (defaults:
+        the reference's thresholds with WINDOWS['default']); the other keyword arguments are predict_video's.
+        -> dict(pred (L,) int32 numpy: arg-max class per frame; events: the arg-max events; suppressed: one event list per
+        entry of suppress), events being the reference's dicts {'label','frame','score'}, equal to what
+        `evalutil.frame_events` / `non_maximum_suppression` / `soft_non_maximum_suppression` give on the normalised track.
+        The host synchronises twice: once for pred, pred_score and the event counts, once for the first `count` entries of
+        every event list.  Class indices travel as one byte (pred: 1 + 4 bytes per frame with its score; an event: frame
+        int32, class uint8, score float64 = 13 bytes), which limits K+1 to 256 columns here.  last_video_stats gains events_d2h_bytes and nms_rounds (per suppress entry, the maximum over
+        the classes)."""
+        from . import evalutil
+        suppress = [tuple(e) for e in suppress]
+        for kind, window, _ in suppress:
+            if kind not in ("nms", "snms"):
+                raise ValueError(f"spot_video: suppression kind {kind!r} (nms | snms)")
+        inv = {v: k for k, v in classes.items()}
+        K1 = self._score_cols(torch.bfloat16 if use_amp else torch.float32)
+        if K1 > 256:
+            raise ValueError(f"spot_video: {K1} score columns, at most 256")
+        if sorted(inv) != list(range(1, K1)):
+            raise ValueError(f"spot_video: classes must name the indices 1..{K1 - 1} of the model's score columns")
+        track, _, mean, s0, stats, keep = self._video_track(frames, clip_starts, overlap_len, pad_len, batch_size, augment,
+                                                            use_amp, max_resident_bytes, want_mean=True)
+        L = track.shape[0]
+        hr = float(high_recall_score_threshold)
+        n = len(suppress)
+        with torch.cuda.stream(s0):
+            pred8 = torch.empty((L,), dtype=torch.uint8, device=mean.device)
+            _, pred_score, first, _ = ops.frame_events(mean, hr, pred_u8=pred8)
+            cls8 = [torch.empty((L * (K1 - 1),), dtype=torch.uint8, device=mean.device) for _ in suppress]
+            lists = [ops.nms_track(mean, window, thr, kind == "snms", hr, first_frame=first, classes_u8=c8)
+                     for (kind, window, thr), c8 in zip(suppress, cls8)]
+            h_pred = torch.empty((L,), dtype=torch.uint8).pin_memory()
+            h_score = torch.empty((L,), dtype=torch.float32).pin_memory()
+            h_small = torch.empty((n, 1 + K1), dtype=torch.int32).pin_memory()       # count, rounds per class
+            h_pred.copy_(pred8, non_blocking=True)
+            h_score.copy_(pred_score, non_blocking=True)
+            for i, (_, _, _, count, rounds) in enumerate(lists):
+                h_small[i, :1].copy_(count, non_blocking=True)
+                h_small[i, 1:].copy_(rounds, non_blocking=True)
+            s0.synchronize()
+            counts = [int(h_small[i, 0]) for i in range(n)]
+            host = []
+            for (fr, _, sc, _, _), c8, m in zip(lists, cls8, counts):
+                bufs = (torch.empty((m,), dtype=torch.int32).pin_memory(), torch.empty((m,), dtype=torch.uint8).pin_memory(),
+                        torch.empty((m,), dtype=torch.float64).pin_memory())
+                if m:
+                    for dst, src in zip(bufs, (fr, c8, sc)):
+                        dst.copy_(src[:m], non_blocking=True)
+                host.append(bufs)
+            if any(counts):
+                s0.synchronize()
+        del keep
+        pred_np = h_pred.numpy().astype(np.int32)
+        score_np = h_score.numpy()
+        fg = np.nonzero(pred_np != 0)[0]
+        events = [{"label": inv[int(pred_np[i])], "frame": int(i), "score": float(score_np[i])} for i in fg]
+        suppressed = [evalutil.event_dicts(f.numpy(), c.numpy(), s.numpy(), inv) for f, c, s in host]
+        stats["events_d2h_bytes"] = L * 5 + n * (1 + K1) * 4 + 13 * sum(counts)
+        stats["nms_rounds"] = [int(h_small[i, 1:].max()) for i in range(n)]
+        self.last_video_stats = stats
+        return dict(pred=pred_np, events=events, suppressed=suppressed)
+
+    def _video_track(self, frames, clip_starts, overlap_len, pad_len, batch_size, augment, use_amp, max_resident_bytes,
+                     want_mean):
+        """The body of predict_video up to and including the stitch launch, nothing synchronised: -> (track (L,K+1) fp32,
+        support (L,) int32, mean (L,K+1) fp32 | None: device tensors written on stream s0; s0; the last_video_stats dict; the
+        resident buffers, to be kept alive until s0 has been synchronised)."""
         from . import evalutil
         from .streams import new_stream
         if not isinstance(frames, torch.Tensor):
@@ -484,19 +570,14 @@ class TDEEDModel:
                     # head is a view of the slot's buffer: consumed here, on the launching stream, before the slot runs again
                     self._process_pred(pred, B, T, dt, out=clip_scores[v, lo:lo + B])
             n_batches += 1
-        # ---- one stitch launch, one synchronisation
+        # ---- one stitch launch
         s0 = streams[0]
         s0.wait_stream(streams[1])
         s0.wait_stream(cp)
         with torch.cuda.stream(s0):
-            track, support, _ = ops.stitch_scores(clip_scores, starts_dev, L, count_all=augment)
-            out_sum = torch.empty((L, K1), dtype=torch.float32).pin_memory()
-            out_sup = torch.empty((L,), dtype=torch.int32).pin_memory()
-            out_sum.copy_(track, non_blocking=True)
-            out_sup.copy_(support, non_blocking=True)
-            s0.synchronize()
-        self.last_video_stats = dict(frames=L, clips=n, batches=n_batches, views=V, frames_h2d_bytes=h2d)
-        return out_sum.numpy().copy(), out_sup.numpy().copy()
+            track, support, mean = ops.stitch_scores(clip_scores, starts_dev, L, count_all=augment, mean=want_mean)
+        stats = dict(frames=L, clips=n, batches=n_batches, views=V, frames_h2d_bytes=h2d)
+        return track, support, mean, s0, stats, (video, frames, clip_scores, starts_dev, starts_host)
 
     def epoch(self, loader, optimizer=None, scaler=None, lr_scheduler=None, acc_grad_iter=1, fg_weight=5,
               valMAP=False):

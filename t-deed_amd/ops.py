@@ -5,6 +5,8 @@ channels-last (NHWC images, NTC sequences).  Nothing here computes on the host: 
 function validates shapes, allocates the output with torch (device memory plumbing) and
 launches the HIP kernel on the current stream.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -662,6 +664,87 @@ def stitch_scores(clip_scores, starts_dev, L, count_all=None, track_sum=None, su
     call("tdeed_stitch_scores", ptr(clip_scores), V, n, T, K1, ptr(starts_dev), int(ca), L, ptr(track_sum), ptr(support),
          ptr(mean_out), stream_ptr())
     return track_sum, support, mean_out
+
+
+def _chk_track(mean, who):
+    if not isinstance(mean, torch.Tensor) or mean.dtype != torch.float32:
+        raise TypeError(f"{who}: the track must be a float32 tensor")
+    if mean.dim() != 2 or mean.shape[0] < 1 or mean.shape[1] < 2 or not mean.is_contiguous():
+        raise ValueError(f"{who}: the track must be a contiguous (L, K+1) tensor with L >= 1 and K >= 1")
+    return int(mean.shape[0]), int(mean.shape[1])
+
+
+def frame_events(mean, hr_threshold=0.01, pred_u8=None):
+    """mean fp32 (L,K1) on the device (stitch_scores(..., mean=True)) -> (pred (L,) int32: arg-max column, first maximum
+    like np.argmax; pred_score (L,) fp32 = mean[f, pred[f]]; first_frame (K1,) int32: per class c >= 1 the first frame with
+    mean[f,c] >= float32(hr_threshold), L when there is none (and at index 0); count (K1,) int32: the number of such
+    frames).  The comparison is in fp32, as numpy compares an fp32 array with a python float.
+    pred_u8: optional uint8 (L,) tensor that receives pred once more, one byte per frame (K1 <= 256): what spot_video copies
+    to the host."""
+    L, K1 = _chk_track(mean, "frame_events")
+    dev = mean.device
+    if pred_u8 is not None:
+        if K1 > 256:
+            raise ValueError(f"frame_events: {K1} columns do not fit a one-byte prediction")
+        if pred_u8.dtype != torch.uint8 or tuple(pred_u8.shape) != (L,) or not pred_u8.is_contiguous() or pred_u8.device != dev:
+            raise ValueError("frame_events: pred_u8 must be a contiguous uint8 (L,) tensor on the track's device")
+    pred = torch.empty((L,), dtype=torch.int32, device=dev)
+    pred_score = torch.empty((L,), dtype=torch.float32, device=dev)
+    first = torch.full((K1,), L, dtype=torch.int32, device=dev)
+    count = torch.zeros((K1,), dtype=torch.int32, device=dev)
+    call("tdeed_frame_events", ptr(mean), L, K1, float(hr_threshold), ptr(pred), ptr(pred_u8), ptr(pred_score), ptr(first),
+         ptr(count), stream_ptr())
+    return pred, pred_score, first, count
+
+
+def nms_track(mean, window, threshold, soft, hr_threshold=0.01, first_frame=None, classes_u8=None):
+    """Exact (soft) non-maximum suppression of a track's high-recall events on the device: what
+    evalutil.non_maximum_suppression (soft=False) / soft_non_maximum_suppression (soft=True) keep of
+    `evalutil.frame_events(...)[1]`, bit for bit (evalutil.nms_rounds states the kernel's order).
+    mean fp32 (L,K1) on the device; window: an int for every class, or a list indexed like the reference's -- by the order in
+    which labels first appear in the high-recall list; first_frame: frame_events(mean, hr_threshold)[2] when the caller has
+    it already.  Returns device tensors (frames int32, classes int32, scores float64, count int32 (1,), rounds int32 (K1,)):
+    the first `count` entries are the events, ascending frame and within a frame by label appearance; rounds[c] is the number
+    of rounds class c took.  classes_u8: optional uint8 tensor of L*(K1-1) entries that receives the classes once more, one
+    byte each: what spot_video copies to the host.
+    Raises ValueError for a soft window below 1, a negative window, or a window list with fewer than K1-1 entries -- the host
+    only fails (IndexError) once more labels appear than the list has entries; this wrapper refuses the list up front."""
+    L, K1 = _chk_track(mean, "nms_track")
+    soft = bool(soft)
+    is_list = isinstance(window, (list, tuple))
+    wins = [int(w) for w in window] if is_list else [int(window)]
+    if is_list and len(wins) < K1 - 1:
+        raise ValueError(f"nms_track: a window list of {len(wins)} entries for {K1 - 1} classes")
+    if is_list and len(wins) == 1:
+        is_list = False                                 # K1 == 2: one class, the entry is its window
+    if any(w < (1 if soft else 0) or w > 1 << 30 for w in wins):
+        raise ValueError(f"nms_track: windows {wins}: soft suppression needs windows >= 1, hard suppression >= 0 (and at most 2^30)")
+    wins = wins[:K1 - 1] if is_list else wins[:1]
+    dev = mean.device
+    if first_frame is None:
+        first_frame = frame_events(mean, hr_threshold)[2]
+    if first_frame.dtype != torch.int32 or tuple(first_frame.shape) != (K1,) or not first_frame.is_contiguous() \
+            or first_frame.device != dev:
+        raise ValueError("nms_track: first_frame must be a contiguous int32 (K1,) tensor on the track's device")
+    cap = L * (K1 - 1)
+    if classes_u8 is not None and (classes_u8.dtype != torch.uint8 or classes_u8.numel() != cap or not classes_u8.is_contiguous()
+                                   or classes_u8.device != dev):
+        raise ValueError(f"nms_track: classes_u8 must be a contiguous uint8 tensor of {cap} entries on the track's device")
+    ws_bytes = int(_lib.load().tdeed_nms_track_workspace(L, K1))
+    ws = torch.empty((ws_bytes // 8 + 1,), dtype=torch.float64, device=dev) if ws_bytes else None
+    emitted = torch.empty((K1, L), dtype=torch.uint8, device=dev)
+    kept = torch.empty((K1, L), dtype=torch.float64, device=dev)
+    frames = torch.empty((cap,), dtype=torch.int32, device=dev)
+    classes = torch.empty((cap,), dtype=torch.int32, device=dev)
+    scores = torch.empty((cap,), dtype=torch.float64, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    rounds = torch.empty((K1,), dtype=torch.int32, device=dev)
+    warr = (ctypes.c_int * len(wins))(*wins)
+    call("tdeed_nms_track", ptr(mean), L, K1, float(hr_threshold), float(threshold), int(soft), warr, len(wins),
+         ptr(first_frame), ptr(ws), ptr(emitted), ptr(kept), ptr(frames), ptr(classes), ptr(classes_u8), ptr(scores), ptr(count),
+         ptr(rounds),
+         stream_ptr())
+    return frames, classes, scores, count, rounds
 
 
 def cast_bf16(src_f32):

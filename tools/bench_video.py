@@ -4,6 +4,8 @@
     python tools/bench_video.py --gather-only                           the gather launch alone (run it under
                                                                         `rocprofv3 --kernel-trace --stats -- python ...`)
     python tools/bench_video.py --decode [--decode-frames 400]          host only: load_video vs clip_batches, JPEG decode
+    python tools/bench_video.py --spot [--frames 5625]                  events: predict_video + the host chain against
+                                                                        spot_video, one JSON line
 
 Routes (RegNetY-200MF, T = 100, 224 x 224, bf16; 3/4 overlap like the evaluation datasets):
   A  the clip route: `evalutil.stitch_predictions` over host-resident PINNED uint8 clip batches of the video, at loader
@@ -99,6 +101,117 @@ def bench(a):
     return 0 if "error" not in out else 1
 
 
+def _peaky_track(L, K1, seed=3):
+    """a synthetic normalised track like a trained model's: narrow bumps per class on a low noise floor"""
+    rng = np.random.RandomState(seed)
+    x = (rng.rand(L, K1) ** 48 * 0.2).astype(np.float32)
+    f = np.arange(L, dtype=np.float32)[:, None]
+    for c in range(1, K1):
+        centres = rng.choice(L, size=max(1, L // 150), replace=False).astype(np.float32)[None]
+        amp = rng.uniform(0.3, 0.95, size=centres.shape).astype(np.float32)
+        x[:, c] += (amp * np.exp(-0.5 * ((f - centres) / 2.0) ** 2)).max(axis=1)
+    x[:, 0] = np.maximum(1.0 - x[:, 1:].sum(axis=1), 0.0)
+    x /= x.sum(axis=1, keepdims=True)
+    return np.ascontiguousarray(x, np.float32)
+
+
+def _host_chain(norm, classes, fps, suppress, hr):
+    pe, recall, _ = E.frame_events(norm, classes, fps, high_recall_score_threshold=hr)
+    lists = [(E.soft_non_maximum_suppression if kind == "snms" else E.non_maximum_suppression)(recall, w, thr)
+             for kind, w, thr in suppress]
+    return pe, recall, lists
+
+
+def _median_ms(fn, repeats):
+    times = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        times.append(time.perf_counter() - t0)
+    return round(float(np.median(times)) * 1e3, 3)
+
+
+def spot(a):
+    """Two routes on the same video, alternating: (1) predict_video -> ScoreStitcher.normalised -> frame_events -> NMS ->
+    soft-NMS on the host, (2) spot_video.  Then the tail alone on a synthetic peaky track of the same length with K+1 = 13
+    columns: the host chain against ops.frame_events + ops.nms_track (+ the copies of the event lists)."""
+    from tdeed_amd.model import TDEEDModel
+    from types import SimpleNamespace
+    L = a.frames
+    hr = 0.01
+    suppress = (("nms", a.window, 0.01), ("snms", a.window, 0.01))
+    m = TDEEDModel(device="cuda", args=SimpleNamespace(modality="rgb", temporal_arch="ed_sgp_mixer", pretrain=None, **CFG))
+    m.load({k: torch.from_numpy(v) for k, v in synth.make_state(state_layout.model_state_shapes(CFG), 0).items()})
+    video = ops.fill_u8_hash((L, 3, H, W), 9, "cuda").cpu().pin_memory()
+    classes = {f"c{k}": k for k in range(1, CFG["num_classes"] + 1)}
+
+    def route_host():
+        sums, sup = m.predict_video(video, batch_size=8)
+        st = E.ScoreStitcher([("v", L, 25.0)], sums.shape[1])
+        st.tracks["v"][0][...] = sums
+        st.tracks["v"][1][...] = sup
+        pe, _, lists = _host_chain(st.normalised(), classes, st.fps, suppress, hr)
+        return pe[0]["events"], [x[0]["events"] for x in lists]
+
+    def route_device():
+        r = m.spot_video(video, classes, suppress=suppress, high_recall_score_threshold=hr, batch_size=8)
+        return r["events"], r["suppressed"]
+
+    routes = dict(host=route_host, device=route_device)
+    res = {k: fn() for k, fn in routes.items()}                         # warm-up
+    stats = dict(m.last_video_stats)
+    times = {k: [] for k in routes}
+    for _ in range(a.repeats):
+        for k, fn in routes.items():                                    # alternating
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            times[k].append(time.perf_counter() - t0)
+    out = dict(kind="video_spotting", cfg=CFG, frames=L, clips=stats["clips"], repeats=a.repeats, window=a.window,
+               predict_video_plus_host_chain_ms=round(float(np.median(times["host"])) * 1e3, 2),
+               spot_video_ms=round(float(np.median(times["device"])) * 1e3, 2),
+               events=dict(argmax=len(res["device"][0]), nms=len(res["device"][1][0]), snms=len(res["device"][1][1])),
+               nms_rounds=stats["nms_rounds"], events_d2h_bytes=stats["events_d2h_bytes"], track_bytes=L * 5 * 4,
+               equal=bool(res["host"] == res["device"]))
+    # ---- the tail alone, peaky track
+    K1 = 13
+    mean = _peaky_track(L, K1)
+    pk_classes = {f"c{k}": k for k in range(1, K1)}
+    inv = {v: k for k, v in pk_classes.items()}
+    dmean = torch.from_numpy(mean).cuda()
+
+    def tail_host():
+        return [x[0]["events"] for x in _host_chain({"v": mean}, pk_classes, {"v": 25.0}, suppress, hr)[2]]
+
+    last = {}
+
+    def tail_device():
+        _, _, first, cnt = ops.frame_events(dmean, hr)
+        lists = [ops.nms_track(dmean, w, thr, kind == "snms", hr, first_frame=first) for kind, w, thr in suppress]
+        counts = [int(x[3].cpu()[0]) for x in lists]                    # synchronises
+        host = [[t[:n].cpu().numpy() for t in x[:3]] for x, n in zip(lists, counts)]
+        last["rounds"] = [int(x[4].max().cpu()) for x in lists]
+        last["recall"] = int(cnt.sum().cpu())
+        return [E.event_dicts(f, c, s, inv) for f, c, s in host]
+
+    def tail_device_kernels():
+        _, _, first, _ = ops.frame_events(dmean, hr)
+        for kind, w, thr in suppress:
+            ops.nms_track(dmean, w, thr, kind == "snms", hr, first_frame=first)
+        torch.cuda.synchronize()
+
+    th, td = tail_host(), tail_device()
+    tail_device_kernels()
+    out["tail_peaky"] = dict(K1=K1, high_recall_events=last["recall"], events=[len(x) for x in td], rounds=last["rounds"],
+                             host_chain_ms=_median_ms(tail_host, a.repeats), device_ms=_median_ms(tail_device, a.repeats),
+                             device_kernels_only_ms=_median_ms(tail_device_kernels, a.repeats), equal=bool(th == td))
+    if not (out["equal"] and out["tail_peaky"]["equal"]):
+        out["error"] = "the device route differs from the host chain"
+    print(json.dumps(out))
+    return 0 if "error" not in out else 1
+
+
 def gather_only(a):
     T, B, L = 100, 8, 400
     video = ops.fill_u8_hash((L, 3, H, W), 9, "cuda")
@@ -150,11 +263,15 @@ def decode(a):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=2030)
+    ap.add_argument("--frames", type=int, default=None, help="default 2030, with --spot 5625")
+    ap.add_argument("--spot", action="store_true")
+    ap.add_argument("--window", type=int, default=12, help="--spot: NMS / soft-NMS window")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--gather-only", action="store_true")
     ap.add_argument("--decode", action="store_true")
     ap.add_argument("--decode-frames", type=int, default=400)
     ap.add_argument("--threads", type=int, default=8)
     a = ap.parse_args()
-    sys.exit(decode(a) if a.decode else gather_only(a) if a.gather_only else bench(a))
+    if a.frames is None:
+        a.frames = 5625 if a.spot else 2030
+    sys.exit(decode(a) if a.decode else gather_only(a) if a.gather_only else spot(a) if a.spot else bench(a))
