@@ -61,7 +61,7 @@ int tdeed_stem_mfma_fwd(const void* frames, int frames_f32, int N, int H, int W,
  * maps stay in LDS / MFMA accumulators (front.hip: a workgroup walks a strip of output rows over rings of input and
  * conv1 rows; parts = strips per frame, a function of the shape and of TDEED_FRONT_ROLL / TDEED_FRONT_PIPE only, never of
  * the frames' alignment).  Weight fragments are pre-packed by
- * tdeed_amd.engine.pack_front_weights; scale/shift are the folded eval BatchNorms (fp32). */
+ * tdeed_amd.packing.pack_front_weights; scale/shift are the folded eval BatchNorms (fp32). */
 int tdeed_s1_front_parts(int crop_h, int crop_w, int C1);
 int tdeed_s1_front_fwd(const uint8_t* frames, int N, int H, int W, int crop_top, int crop_left, int crop_h,
                        int crop_w, int flip, const void* stem_wf, const float* stem_sc, const float* stem_sh,
@@ -102,7 +102,7 @@ int tdeed_gemm_fwd(const void* A, long lda, const void* A0, long lda0, int k0,
 /* Weight-stationary variant of the same contraction for narrow layers (whole W in LDS, activations
  * streamed global->registers in MFMA fragment shape, persistent blocks; see gemm.hip).  Same
  * semantics and arguments as tdeed_gemm_fwd except that the weights arrive pre-packed:
- * Wfrag = tdeed_amd.engine.pack_ws_weights(W): [2*ceil(N/32)][ceil(K/(4*epc))][64 lanes][16 B], rows
+ * Wfrag = tdeed_amd.packing.pack_ws_weights(W): [2*ceil(N/32)][ceil(K/(4*epc))][64 lanes][16 B], rows
  * permuted so that each lane owns 8 consecutive output channels.  tdeed_gemm_ws_fits() tells whether
  * (K, N, dtype) fits (LDS budget 64 KB). */
 int tdeed_gemm_ws_fits(int K, int N, int dtype);
@@ -117,7 +117,7 @@ int tdeed_gemm_ws_fwd(const void* A, long lda, const void* A0, long lda0, int k0
  * squeeze (sum over H,W) of its output.  x: [N][Hi][Wi][C], y: [N][Ho][Wo][C], gw in {8,16}.
  *   w      fp32 [G][9][gw_in][gw_out] (tap-major repack of Conv2d.weight [C][gw][3][3]); used by the
  *          VALU kernel (TDEED_F32, or bf16 when wfrag is NULL).
- *   wfrag  bf16 MFMA operand fragments [ceil4(C/16)][5][64][8] (see tdeed_amd.engine.pack_gconv_frags);
+ *   wfrag  bf16 MFMA operand fragments [ceil4(C/16)][5][64][8] (see tdeed_amd.packing.pack_gconv_frags);
  *          TDEED_BF16 only: implicit GEMM on v_mfma_f32_16x16x32_bf16 from an LDS-staged halo band.
  *   pooled fp32 [N][parts][C]: per-band partial SUMS of y over pixels, parts =
  *          tdeed_gconv3x3_parts(Hi, Wi, C, stride, dtype) (1 on the VALU path).
@@ -145,7 +145,7 @@ int tdeed_gemm_splitk_fwd(const void* A, long lda, int M, int K, int N, const vo
                           float* workspace, void* stream);
 
 /* SE excitation on the MFMA pipe (bf16 weights as A-operand fragments [ceil(R/16)][ceil(C/32)][64][8] and
- * [ceil(C/16)][ceil(R/32)][64][8], tdeed_amd.engine.pack_se_mfma); 16 frames per workgroup; same contract as
+ * [ceil(C/16)][ceil(R/32)][64][8], tdeed_amd.packing.pack_se_mfma); 16 frames per workgroup; same contract as
  * tdeed_se_gate_bf16_fwd.  tdeed_se_gate_mfma_fits(C, R) != 0 tells whether the shape is covered (C <= 384, R <= 96). */
 int tdeed_se_gate_mfma_fits(int C, int R);
 int tdeed_se_gate_mfma_fwd(const float* pooled, int n_parts, float inv_cnt, int N, int C, int R, const void* w1f,
@@ -187,7 +187,7 @@ int tdeed_c1_gconv_fwd(const void* x, const void* G, int Fp, int N, int Hi, int 
  * SURVEY §8 a2 / a3): the frames of a workgroup stay in LDS, only x and the output cross HBM.  bf16.
  *   x [N][h][w][C]; G optional [N*h*w][Fp] compact gate-shift output replacing channels [0, Fp) of conv1's operand (the
  *   residual is x itself); w1f / w3f: conv weights [C][C] as MFMA A-operand fragments [ceil(C/16)][ceil(C/32)][64][8]
- *   (tdeed_amd.engine.pack_mfma_frags); w2f as for tdeed_gconv3x3_fwd (pack_gconv_frags, group width 8 or 16); se_w1f /
+ *   (tdeed_amd.packing.pack_mfma_frags); w2f as for tdeed_gconv3x3_fwd (pack_gconv_frags, group width 8 or 16); se_w1f /
  *   se_w2f / R as for tdeed_se_gate_mfma_fwd; s*, h*: folded BatchNorm scale / shift; out [N][h][w][C]; out2 optional
  *   [N*h*w][n2] compact copy of channels [0, n2) (the next block's gate-shift slice).
  * Bit-identical to tdeed_gemm_fwd -> tdeed_gconv3x3_fwd -> tdeed_se_gate_mfma_fwd -> tdeed_gemm_fwd on the same operands.
@@ -199,7 +199,7 @@ int tdeed_bneck_fwd(const void* x, const void* G, int Fp, int N, int h, int w, i
                     const float* h1, const void* w2f, const float* s2, const float* h2, const void* se_w1f,
                     const float* se_b1, const void* se_w2f, const float* se_b2, int R, const void* w3f, const float* s3,
                     const float* h3, void* out, void* out2, int n2,
-                    int w2_tap_major /* k-slot order of w2f: 1 = engine.pack_gconv_frags(tap_major=True), the conflict-free
+                    int w2_tap_major /* k-slot order of w2f: 1 = packing.pack_gconv_frags(tap_major=True), the conflict-free
                                         order of this launch (group width 8); 0 = the order tdeed_gconv3x3_fwd reads */,
                     void* stream);
 /* The same block behind a gate-shift-fuse site (impl/gsf.py:74-93) with the site's last launch -- fusion weights + blend,
@@ -210,7 +210,7 @@ int tdeed_bneck_fwd(const void* x, const void* G, int Fp, int N, int h, int w, i
  * conv3d as three 2-D convs per frame), made from this block's output rows while they are in LDS -- what the first launch of
  * tdeed_gsf_gate_fwd computes from `out`, as a 1x1 contraction to per-tap sums plus nine fp32 adds (same products, another
  * summation order: equal to fp32 rounding); the site then runs tdeed_gsf_gate_sums_fwd only.  q_wqf: the site's weights as
- * engine.pack_gsf_p_frags lays them out; q_bn [2][8 * ceil(q_F / 8)]: its folded BatchNorm3d scale | shift, zeros behind
+ * packing.pack_gsf_p_frags lays them out; q_bn [2][8 * ceil(q_F / 8)]: its folded BatchNorm3d scale | shift, zeros behind
  * channel q_F. */
 int tdeed_bneck_qtail_fits(int h, int w, int C, int F);
 int tdeed_bneck_gs_fwd(const void* x, const void* gx, int ldx, const float* gate, const float* ysum, const float* xsum,
@@ -229,7 +229,7 @@ int tdeed_se_gate_fwd(const float* pooled, int n_parts, float inv_cnt, int N, in
                       float* gate, void* stream);
 
 /* Same excitation with bf16 weights (throughput mode): w1p bf16 [C][ceil8(R)] (fc1.weight^T zero padded),
- * w2p bf16 [R][C] (fc2.weight^T) = tdeed_amd.engine.pack_se_bf16. */
+ * w2p bf16 [R][C] (fc2.weight^T) = tdeed_amd.packing.pack_se_bf16. */
 int tdeed_se_gate_bf16_fwd(const float* pooled, int n_parts, float inv_cnt, int N, int C, int R,
                            const void* w1p, const float* b1, const void* w2p, const float* b2,
                            float* gate, void* stream);
@@ -246,7 +246,7 @@ int tdeed_se_gate_bf16_fwd(const float* pooled, int n_parts, float inv_cnt, int 
 int tdeed_gsf_gate_fwd(const void* x, int B, int T, int h, int w, int C, int F,
                        const float* bn_scale, const float* bn_shift,
                        const float* wq /*[27][F] tap-major conv3D weight (VALU path)*/,
-                       const void* wqf /*bf16 MFMA fragments, engine.pack_gsf_q_frags; NULL => VALU*/,
+                       const void* wqf /*bf16 MFMA fragments, packing.pack_gsf_q_frags; NULL => VALU*/,
                        const float* b3d /*[2]*/,
                        float* Q /*scratch fp32 [B*T][h][w][6]*/, float* gate, float* ysum, float* xsum,
                        int dtype, void* stream);
@@ -599,7 +599,7 @@ int tdeed_gemm_dgrad(const void* A, long lda, int M, int K, int N, const void* W
                      long ldbz, const float* bmean, const void* bzd, long ldbzd, const float* bmean_d, float* bpart, int dtype,
                      void* stream);
 /* tdeed_gemm_dgrad for K = N = 320 over many rows on the register-stationary contraction (Wfrag = the packed [N][K] matrix,
- * engine.pack_ws_weights): residual and mask required, no stride-2 residual, no second statistics map;
+ * packing.pack_ws_weights): residual and mask required, no stride-2 residual, no second statistics map;
  * bpart fp32 [tdeed_gemm_rs_grid(M)][3][N]. */
 int tdeed_gemm_dgrad_rs(const void* A, long lda, int M, int K, int N, const void* Wfrag, const void* R, long ldr, void* C,
                         long ldc, void* C2, long ldc2, int n2, const void* mask, long ldmask, const void* bz, long ldbz,

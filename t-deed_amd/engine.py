@@ -8,7 +8,6 @@ compiler, no per-op host work in the steady state.
 
 Mirrors ``TDEEDModel.Impl.forward(x, inference=True)`` (/root/reference/model/model.py:105-149).
 """
-import math
 import os
 from types import SimpleNamespace
 
@@ -18,14 +17,13 @@ import torch
 from . import ops, _lib
 from .streams import new_stream
 from .regnet_spec import regnet_spec, sgp_up_size, pyramid_lengths
+# the weight layouts (also importable from here, where they used to live)
+from .packing import (_np, _f32, _dense, pack_ws_weights, pack_se_bf16, pack_mfma_frags, pack_se_mfma,  # noqa: F401
+                      pack_front_weights, _stem_frags_np, gs_source_order_columns, _gsf_q_frags_np, pack_gsf_q_frags,
+                      _gsf_p_frags_np, pack_gsf_p_frags, pack_gconv_frags, _gconv_frags_np, stem_frags_on_device,
+                      gsf_q_frags_on_device, gconv_frag_index, gconv_frags_on_device)
 
 BN_EPS = 1e-5
-
-
-def _np(v):
-    if isinstance(v, torch.Tensor):
-        return v.detach().cpu().numpy()
-    return np.asarray(v)
 
 
 class _Pool:
@@ -58,14 +56,6 @@ class _Pool:
 
     def total_bytes(self):
         return sum(b.numel() for b in self.all)
-
-
-def _f32(a, device):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
-
-
-def _dense(a, act_dtype, device):
-    return _f32(a, device).to(act_dtype).contiguous()
 
 
 def _dwpack(sd, pre, names, C, device):
@@ -101,63 +91,6 @@ def _pack_mlp(sd, pre, C, o, act_dtype, device):
         # sgp_gemm.hip: plain MFMA fragments of the whole weight, k-steps padded to its chunk ring
         o.w1g = pack_mfma_frags(_np(sd[pre + ".mlp.0.weight"]).reshape(4 * C, C), device, ks_mult=12)
         o.w2g = pack_mfma_frags(_np(sd[pre + ".mlp.2.weight"]).reshape(C, 4 * C), device, ks_mult=12)
-
-
-def pack_ws_weights(W, act_dtype, device):
-    """[N][K] dense weight -> fragments for gemm_ws_kernel: [NT][KS][64][epc] with NT = 2*ceil(N/32),
-    KS = ceil(K/(4*epc)); MFMA row n of tile 2t+h holds logical channel 32t + 8(n//4) + 4h + n%4 so that a
-    lane's accumulators of a tile pair are 8 consecutive output channels."""
-    W = _np(W).astype(np.float32)
-    N, K = W.shape
-    epc = 8 if act_dtype == torch.bfloat16 else 4
-    KS = (K + 4 * epc - 1) // (4 * epc)
-    NT = (N + 31) // 32 * 2
-    Wp = np.zeros((NT * 16, KS * 4 * epc), np.float32)
-    n = np.arange(16)
-    for nt in range(NT):
-        t, h = divmod(nt, 2)
-        L = 32 * t + 8 * (n // 4) + 4 * h + (n % 4)
-        ok = L < N
-        Wp[nt * 16 + n[ok], :K] = W[L[ok]]
-    fr = Wp.reshape(NT, 16, KS, 4, epc).transpose(0, 2, 3, 1, 4)          # [NT][KS][q][n][epc]
-    fr = np.ascontiguousarray(fr).reshape(NT, KS, 64, epc)
-    return torch.from_numpy(fr).to(device).to(act_dtype).contiguous()
-
-
-def pack_se_bf16(fc1_w, fc2_w, device):
-    """SE weights for the bf16 excitation kernel: fc1.weight [R][C][1][1] -> bf16 [C][ceil8(R)] (transposed, zero padded);
-    fc2.weight [C][R][1][1] -> bf16 [R][C] (transposed)."""
-    w1 = _np(fc1_w).astype(np.float32)
-    w1 = w1.reshape(w1.shape[0], -1)
-    w2 = _np(fc2_w).astype(np.float32)
-    w2 = w2.reshape(w2.shape[0], -1)
-    R, C = w1.shape
-    R8 = (R + 7) // 8 * 8
-    p1 = np.zeros((C, R8), np.float32)
-    p1[:, :R] = w1.T
-    bf = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device).to(torch.bfloat16).contiguous()   # noqa: E731
-    return dict(se_w1p=bf(p1), se_w2p=bf(w2.T))
-
-
-def pack_mfma_frags(W, device, rows=None, ks_mult=1):
-    """A dense [N][K] weight as MFMA A-operand fragments [ceil(N/16)][ceil(K/32)][64][8] (bf16, zero padded; lane l holds row
-    l&15, k = 8*(l>>4)+j of the 16 x 32 tile).  rows: pad N up to this many rows (whole channel slabs); ks_mult: pad the
-    k-steps to a multiple of this (sgp_gemm: whole super-iterations of its chunk ring, 12)."""
-    W = _np(W).astype(np.float32)
-    W = W.reshape(W.shape[0], -1)
-    N, K = W.shape
-    NT, KS = (max(N, rows or 0) + 15) // 16, (K + 31) // 32
-    KS = (KS + ks_mult - 1) // ks_mult * ks_mult
-    Wp = np.zeros((NT * 16, KS * 32), np.float32)
-    Wp[:N, :K] = W
-    fr = Wp.reshape(NT, 16, KS, 4, 8).transpose(0, 2, 3, 1, 4)
-    return torch.from_numpy(np.ascontiguousarray(fr).reshape(NT, KS, 64, 8)).to(device).to(torch.bfloat16).contiguous()
-
-
-def pack_se_mfma(fc1_w, fc2_w, device):
-    """SE weights as MFMA A-operand fragments: fc1.weight [R][C] -> [ceil(R/16)][ceil(C/32)][64][8],
-    fc2.weight [C][R] -> [ceil(C/16)][ceil(R/32)][64][8] (pack_mfma_frags)."""
-    return dict(w1f=pack_mfma_frags(fc1_w, device), w2f=pack_mfma_frags(fc2_w, device))
 
 
 GS_SLICE = True
@@ -221,209 +154,6 @@ class DenseW:
         if self._use_wide(kw.get("M")):
             return ops.gemm_ws(A, self.w_wide, self.K, self.N, scale, shift, act, **kw)
         return ops.gemm(A, self.w, scale, shift, act, **kw)
-
-
-def pack_front_weights(stem_w, stem_sc, stem_sh, w1, sc1, sh1, wd, scd, shd, w2, gw, sc2, sh2, device):
-    """Weight fragments of s1_front_kernel (front.hip).  stem_w [32][3][3][3]; w1/wd [C1][32]; w2 [C1][gw][3][3].
-    Stem k-slot s = 4ks+q -> (ky = s>>1, half = s&1), element j -> (kx = 2half + j//4, c = j%4 (3 = pad));
-    conv1/downsample k-slot q element j -> stem channel 4q+j (j<4) / 16+4q+j-4: the order in which the stem's
-    MFMA accumulators hand the 32 channels over."""
-    stem_w, w1, wd = _np(stem_w).astype(np.float32), _np(w1).astype(np.float32), _np(wd).astype(np.float32)
-    C1 = w1.shape[0]
-    sw = _stem_frags_np(stem_w)
-    nt = (C1 + 15) // 16
-
-    def kperm(W):
-        fr = np.zeros((nt, 64, 8), np.float32)
-        for t in range(nt):
-            for q in range(4):
-                for j in range(8):
-                    chn = 4 * q + j if j < 4 else 16 + 4 * q + j - 4
-                    for n in range(16):
-                        if t * 16 + n < C1:
-                            fr[t, q * 16 + n, j] = W[t * 16 + n, chn]
-        return fr
-    bf = lambda a: torch.from_numpy(a).to(device).to(torch.bfloat16).contiguous()      # noqa: E731
-    f32 = lambda a: _f32(_np(a), device)                                              # noqa: E731
-    return SimpleNamespace(C1=C1, stem_wf=bf(sw), stem_sc=f32(stem_sc), stem_sh=f32(stem_sh), w1f=bf(kperm(w1)),
-                           sc1=f32(sc1), sh1=f32(sh1), wdf=bf(kperm(wd)), scd=f32(scd), shd=f32(shd),
-                           w2f=pack_gconv_frags(w2, gw, device), sc2=f32(sc2), sh2=f32(sh2))
-
-
-def _stem_frags_np(stem_w):
-    """stem conv weight [32][3][3][3] -> MFMA A fragments [2 channel tiles][2 k-steps][64 lanes][8] (front.hip: k-slot
-    s = 4ks+q -> (ky = s>>1, half = s&1), element j -> (kx = 2half + j//4, c = j%4, 3 = pad))."""
-    sw = np.zeros((2, 2, 64, 8), stem_w.dtype)
-    for t in range(2):
-        for ks in range(2):
-            for q in range(4):
-                s_ = 4 * ks + q
-                if s_ >= 6:
-                    continue
-                ky, half = s_ >> 1, s_ & 1
-                for j in range(8):
-                    kx, c = 2 * half + j // 4, j % 4
-                    if kx > 2 or c > 2:
-                        continue
-                    sw[t, ks, q * 16:(q + 1) * 16, j] = stem_w[t * 16:(t + 1) * 16, c, ky, kx]
-    return sw
-
-
-_STEM_IDX = {}
-
-
-def stem_frags_on_device(w):
-    """_features.stem.conv.weight (32,3,3,3) fp32 on the device -> the fragments of _stem_frags_np (kept in fp32: the training
-    stem splits them into bf16 head + tail itself) by one gather through a cached index map (the training step re-packs the
-    updated weight without a host round trip)."""
-    key = str(w.device)
-    if key not in _STEM_IDX:
-        ids = (np.arange(32 * 27, dtype=np.float32) + 1).reshape(32, 3, 3, 3)              # exact in fp32
-        _STEM_IDX[key] = torch.from_numpy(_stem_frags_np(ids).astype(np.int64)).to(w.device)
-    ext = torch.cat([torch.zeros(1, dtype=w.dtype, device=w.device), w.reshape(-1)])
-    return ext[_STEM_IDX[key]].contiguous()
-
-
-_GSFQ_IDX = {}
-
-
-def gs_source_order_columns(w1, F):
-    """conv1 weight (cout, cin) of a gate-shift-fuse site -> the same weight for a slice left in SOURCE channel order:
-    out[:, ci] = w1[:, co] for the output channel co that source channel ci is interleaved to (impl/gsf.py:88-91);
-    columns >= F unchanged."""
-    w = np.array(w1, copy=True)
-    src = ops.gs_source_order(F)                  # src[co] = ci
-    w[:, src] = w1[:, :F]
-    return w
-
-
-def gsf_q_frags_on_device(w3d):
-    """conv3D.weight (2,F/2,3,3,3) fp32 on the device -> the bf16 MFMA fragments of pack_gsf_q_frags, by one gather
-    through a cached index map (a training step re-packs the updated weight without a host round trip)."""
-    Fh = w3d.shape[1]
-    key = (Fh, str(w3d.device))
-    if key not in _GSFQ_IDX:
-        ids = (np.arange(2 * Fh * 27, dtype=np.float32) + 1).reshape(2, Fh, 3, 3, 3)       # exact in fp32
-        _GSFQ_IDX[key] = torch.from_numpy(_gsf_q_frags_np(ids).astype(np.int64)).to(w3d.device)
-    from . import repack as R
-    ext = torch.cat([torch.zeros(1, dtype=w3d.dtype, device=w3d.device), w3d.reshape(-1)])
-    return R.to_bf16(ext[_GSFQ_IDX[key]]).contiguous()
-
-
-def _gsf_q_frags_np(w3d):
-    Fh = w3d.shape[1]
-    F = 2 * Fh
-    nch = (F + 7) // 8
-    KS = (9 * nch + 3) // 4
-    fr = np.zeros((KS, 64, 8), np.float32)
-    for ks in range(KS):
-        for q in range(4):
-            s_ = 4 * ks + q
-            tap, ck = divmod(s_, nch)
-            if tap >= 9:
-                continue
-            dy, dx = divmod(tap, 3)
-            for n in range(6):
-                jt, g = divmod(n, 2)
-                for e in range(8):
-                    c = ck * 8 + e
-                    if c < F and c // Fh == g:
-                        fr[ks, q * 16 + n, e] = w3d[g, c - g * Fh, jt, dy, dx]
-    return fr
-
-
-def pack_gsf_q_frags(w3d, device):
-    """conv3D.weight [2][F/2][3][3][3] -> bf16 MFMA A fragments [KS][64][8] for gsf_q_mfma_kernel:
-    row n = jg = 2*j_t + g (rows 6..15 zero); k-slot s = 4ks+q = tap*nch + chunk, element e = channel 8*chunk+e,
-    non-zero only for channels of gate group g."""
-    return torch.from_numpy(_gsf_q_frags_np(_np(w3d).astype(np.float32))).to(device).to(torch.bfloat16).contiguous()
-
-
-def _gsf_p_frags_np(w3d):
-    Fh = w3d.shape[1]
-    F = 2 * Fh
-    nch = (F + 7) // 8
-    KSc = (nch + 3) // 4
-    fr = np.zeros((4, KSc, 64, 8), np.float32)
-    for rt in range(4):
-        for n in range(16):
-            r = rt * 16 + n
-            if r >= 54:
-                continue
-            tap, jg = divmod(r, 6)
-            dy, dx = divmod(tap, 3)
-            jt, g = divmod(jg, 2)
-            for ks in range(KSc):
-                for q in range(4):
-                    for e in range(8):
-                        c = (4 * ks + q) * 8 + e
-                        if c < F and c // Fh == g:
-                            fr[rt, ks, q * 16 + n, e] = w3d[g, c - g * Fh, jt, dy, dx]
-    return fr
-
-
-def pack_gsf_p_frags(w3d, device):
-    """conv3D.weight [2][F/2][3][3][3] -> bf16 MFMA A fragments [4][ceil(nch/4)][64][8] for the tap-map tail of
-    tdeed_bneck_gs_fwd: row r = tap*6 + jg (jg = 2*j_t + g as in pack_gsf_q_frags; rows 54..63 zero), k = channel,
-    non-zero only for channels of gate group g -- the 3x3x3 conv as ONE 1x1 contraction to per-tap sums."""
-    return torch.from_numpy(_gsf_p_frags_np(_np(w3d).astype(np.float32))).to(device).to(torch.bfloat16).contiguous()
-
-
-def pack_gconv_frags(w, gw, device, tap_major=False):
-    """Conv2d.weight [C][gw][3][3] -> bf16 MFMA A-operand fragments [ceil4(C/16)][5][64][8] for
-    gconv3x3_mfma_kernel: unit u = output channels [16u,16u+16); lane l holds Wt[n=l&15][k=8(l>>4)+j];
-    k-slot s = 4*ks + (l>>4) = half*9 + tap; for gw=8 'half' selects which of the unit's two groups
-    the 8 input channels belong to (block-diagonal), for gw=16 which half of the group's 16 inputs.
-    tap_major (tdeed_bneck_fwd): s = 2*tap + half -- the two k-slots of a ds_read_b128 lane group then differ by 16 bytes
-    at the SAME tap pixel, which is conflict-free at the one-launch bottleneck's even row stride (bneck.hip)."""
-    return torch.from_numpy(_gconv_frags_np(_np(w).astype(np.float32), gw, tap_major)).to(device).to(torch.bfloat16).contiguous()
-
-
-def _gconv_frags_np(w, gw, tap_major=False):
-    C = w.shape[0]
-    nu = (C + 15) // 16
-    nu4 = (nu + 3) // 4 * 4
-    fr = np.zeros((nu4, 5, 64, 8), np.float32)
-    for u in range(nu):
-        for ks in range(5):
-            for q in range(4):
-                s_ = 4 * ks + q
-                if s_ >= 18:
-                    continue
-                half, tap = (s_ & 1, s_ >> 1) if tap_major else divmod(s_, 9)
-                ky, kx = divmod(tap, 3)
-                for n in range(16):
-                    co = u * 16 + n
-                    if co >= C:
-                        continue
-                    lane = q * 16 + n
-                    if gw == 16:
-                        fr[u, ks, lane, :] = w[co, half * 8:half * 8 + 8, ky, kx]
-                    elif n // 8 == half:
-                        fr[u, ks, lane, :] = w[co, :, ky, kx]
-    return fr
-
-
-_GCONV_IDX = {}
-
-
-def gconv_frag_index(C, gw, device):
-    """Index map of pack_gconv_frags: frags = cat([0, w.reshape(-1)])[idx], so a training step can re-pack the MFMA
-    fragments of an updated weight on the device (one gather) instead of through numpy."""
-    key = (C, gw, str(device))
-    if key not in _GCONV_IDX:
-        ids = (np.arange(C * gw * 9, dtype=np.float32) + 1).reshape(C, gw, 3, 3)     # exact in fp32 (< 2^24)
-        fr = _gconv_frags_np(ids, gw)
-        _GCONV_IDX[key] = torch.from_numpy(fr.astype(np.int64)).to(device)
-    return _GCONV_IDX[key]
-
-
-def gconv_frags_on_device(w, gw):
-    """Conv2d.weight (C,gw,3,3) fp32 on the device -> bf16 MFMA fragments (same layout as pack_gconv_frags)."""
-    idx = gconv_frag_index(w.shape[0], gw, w.device)
-    from . import repack as R
-    ext = torch.cat([torch.zeros(1, dtype=w.dtype, device=w.device), w.reshape(-1)])
-    return R.to_bf16(ext[idx]).contiguous()
 
 
 def pack_sgp_block(sd, pre, C, act_dtype, device):
@@ -549,7 +279,7 @@ class SgpBuilder:
         kernel: a tiled contraction would be ~40 workgroups each walking K in 20+ dependent round trips."""
         N, K = Wt.shape
         es = _esz(self.dt)
-        if (self.dt == torch.bfloat16 and R <= self.splitk_rows and str(A.device) != "cpu"
+        if (self.dt == torch.bfloat16 and R <= self.splitk_rows
                 and ops.gemm_splitk_splits(K) >= 4):      # K = 4C / 6C; for K = C the tiled kernel is faster (11 vs 15 us)
             ws = self.pool.take((ops.gemm_splitk_splits(K), R, N), torch.float32)
             self.steps.append(Step(name, "gemm_splitk", lambda: ops.gemm_splitk(A, Wt, None, bias, act, residual=residual,
@@ -573,51 +303,43 @@ class SgpBuilder:
         pool.give(gn)
         pool.give(hid)
 
+    def _tap(self, name, outb):
+        if name in self.taps:
+            self.keep[name] = outb
+        return outb
+
     def block(self, xin, Tn, o, name, pool_to=None):
         """One SGPBlock.  pool_to: length of the AdaptiveMaxPool1d that follows (encoder half); when the MLP launch can
         carry it, `self.last_pooled` holds the pooled tensor afterwards (else None: the caller adds a max-pool launch)."""
         pool, steps, B, C, dt = self.pool, self.steps, self.B, o.C, self.dt
         self.last_pooled = None
-        if self.gemm and self.fused and str(xin.device) != "cpu" and getattr(o, "w1g", None) is not None:
-            adt = xin.dtype
-            es, R = _esz(adt), B * Tn
-            wl = 2 * o.ks + o.up + 2
+        R, wl = B * Tn, 2 * o.ks + o.up + 2
+        if self.fused:
+            gemm = self.gemm and getattr(o, "w1g", None) is not None      # the MLP on sgp_gemm.hip, over the stream's own type
+            adt = xin.dtype if gemm else dt
+            es = _esz(adt)
             y = pool.take((B, Tn, C), adt)
-            y16 = pool.take((B, Tn, C), torch.bfloat16) if (adt == torch.float32 and C > SGP_BF16_OPERAND_MIN_C) else None
-            chs = pool.take((B, C, 2), torch.float32)
-            rs_in = getattr(xin, "_td_rowstat", None)
+            y16 = pool.take((B, Tn, C), torch.bfloat16) if (gemm and adt == torch.float32 and C > SGP_BF16_OPERAND_MIN_C) else None
+            chs = pool.take((B, C, 2), torch.float32) if gemm else None
+            outb = None if gemm else pool.take((B, Tn, C), dt)            # (_mlp_gemm takes its own)
+            rs_in = getattr(xin, "_td_rowstat", None)          # LayerNorm statistics left by the producer of xin (avgpool_posenc)
             steps.append(Step(name + ".front", "sgp_front", lambda: ops.sgp_front(xin, o.ks, o.up, o.ln_w, o.ln_b, o.dw, o.db,
                                                                                  out=y, chsum=chs, rowstat=rs_in, out16=y16),
                               2 * R * C * es + C * (wl + 7) * 4 + (0 if y16 is None else R * C * 2), 2 * R * C * (wl + 3)))
-            outb = self._mlp_gemm(name, y, o, Tn, chs, pool_to=pool_to, y16=y16)
-            pool.give(y)
-            if y16 is not None:
-                pool.give(y16)
-            pool.give(chs)
-            if name in self.taps:
-                self.keep[name] = outb
-            return outb
-        if self.fused and str(xin.device) != "cpu":
-            y = pool.take((B, Tn, C), dt)
-            outb = pool.take((B, Tn, C), dt)
-            es, R = _esz(dt), B * Tn
-            wl = 2 * o.ks + o.up + 2
-            rs_in = getattr(xin, "_td_rowstat", None)          # LayerNorm statistics left by the producer of xin (avgpool_posenc)
-            steps.append(Step(name + ".front", "sgp_front", lambda: ops.sgp_front(xin, o.ks, o.up, o.ln_w, o.ln_b, o.dw, o.db,
-                                                                                 out=y, rowstat=rs_in),
-                              2 * R * C * es + C * (wl + 7) * 4, 2 * R * C * (wl + 3)))
-            self._mlp(name, y, o, outb, Tn)
-            pool.give(y)
-            if name in self.taps:
-                self.keep[name] = outb
-            return outb
+            if gemm:
+                outb = self._mlp_gemm(name, y, o, Tn, chs, pool_to=pool_to, y16=y16)
+            else:
+                self._mlp(name, y, o, outb, Tn)
+            for t_ in (y, y16, chs):
+                if t_ is not None:
+                    pool.give(t_)
+            return self._tap(name, outb)
         ln = pool.take((B, Tn, C), dt)
         y = pool.take((B, Tn, C), dt)
         gn = pool.take((B, Tn, C), dt)
         hid = pool.take((B, Tn, 4 * C), dt)
         outb = pool.take((B, Tn, C), dt)
-        es, R = _esz(dt), B * Tn
-        wl = 2 * o.ks + o.up + 2
+        es = _esz(dt)
         steps.append(Step(name + ".ln", "layernorm", lambda: ops.layernorm(xin, o.ln_w, o.ln_b, out=ln), 2 * R * C * es))
         steps.append(Step(name + ".branch", "sgp_branch", lambda: ops.sgp_branch(ln, xin, o.ks, o.up, o.dw, o.db, out=y),
                           3 * R * C * es + C * (wl + 5) * 4, 2 * R * C * (wl + 3)))
@@ -626,24 +348,32 @@ class SgpBuilder:
         self.dense(name + ".fc2", hid, o.w_fc2, o.b_fc2, ops.ACT_NONE, outb, R, residual=y)
         for t_ in (ln, y, gn, hid):
             pool.give(t_)
-        if name in self.taps:
-            self.keep[name] = outb
-        return outb
+        return self._tap(name, outb)
 
     def mixer(self, xlo, T_lo, z, T_hi, o, name):
         pool, steps, B, C, dt = self.pool, self.steps, self.B, o.C, self.dt
-        if self.gemm and self.fused and str(z.device) != "cpu" and getattr(o, "wcg", None) is not None:
-            adt = z.dtype
-            if xlo.dtype != adt:
+        R, Rl, wl = B * T_hi, B * T_lo, 2 * o.ks + o.up + 2
+        if self.fused:
+            gemm = self.gemm and getattr(o, "wcg", None) is not None      # concat_fc and the MLP on sgp_gemm.hip
+            adt = z.dtype if gemm else dt
+            if gemm and xlo.dtype != adt:
                 raise TypeError("SgpBuilder.mixer: z and x_lo must share the residual stream's type")
-            es, R, Rl = _esz(adt), B * T_hi, B * T_lo
-            wl = 2 * o.ks + o.up + 2
-            cat = pool.take((B, T_hi, 6 * C), torch.bfloat16)
+            es = _esz(adt)
+            cat = pool.take((B, T_hi, 6 * C), torch.bfloat16 if gemm else dt)
+            if not gemm:
+                mo = pool.take((B, T_hi, C), dt)
+                outb = pool.take((B, T_hi, C), dt)
             rs_z, rs_x = getattr(z, "_td_rowstat", None), getattr(xlo, "_td_rowstat", None)
             steps.append(Step(name + ".front", "mixer_front",
                               lambda: ops.mixer_front(z, xlo, cat, o.ks, o.up, o.ln1_w, o.ln1_b, o.ln2_w, o.ln2_b, o.dw1,
                                                       o.db1, o.dw2, o.db2, rowstat_z=rs_z, rowstat_x=rs_x),
-                              (R + Rl) * C * es + 6 * R * C * 2 + 2 * C * (wl + 7) * 4, 4 * R * C * (wl + 3)))
+                              (R + Rl) * C * es + 6 * R * C * _esz(cat.dtype) + 2 * C * (wl + 7) * 4, 4 * R * C * (wl + 3)))
+            if not gemm:
+                self.dense(name + ".cat", cat, o.w_cat, o.b_cat, ops.ACT_GELU, mo, R)
+                self._mlp(name, mo, o, outb, T_hi)
+                pool.give(cat)
+                pool.give(mo)
+                return self._tap(name, outb)
             fc = ops.sgp_gemm_form(2, B, T_hi, C, 6 * C)
             NJ = ops.sgp_gemm_tiles(T_hi, C, fc)[0]
             mo = pool.take((B, T_hi, C), adt)
@@ -658,27 +388,7 @@ class SgpBuilder:
             if mo16 is not None:
                 pool.give(mo16)
             pool.give(chs)
-            if name in self.taps:
-                self.keep[name] = outb
-            return outb
-        if self.fused and str(z.device) != "cpu":
-            cat = pool.take((B, T_hi, 6 * C), dt)
-            mo = pool.take((B, T_hi, C), dt)
-            outb = pool.take((B, T_hi, C), dt)
-            es, R, Rl = _esz(dt), B * T_hi, B * T_lo
-            wl = 2 * o.ks + o.up + 2
-            rs_z, rs_x = getattr(z, "_td_rowstat", None), getattr(xlo, "_td_rowstat", None)
-            steps.append(Step(name + ".front", "mixer_front",
-                              lambda: ops.mixer_front(z, xlo, cat, o.ks, o.up, o.ln1_w, o.ln1_b, o.ln2_w, o.ln2_b, o.dw1,
-                                                      o.db1, o.dw2, o.db2, rowstat_z=rs_z, rowstat_x=rs_x),
-                              (7 * R + Rl) * C * es + 2 * C * (wl + 7) * 4, 4 * R * C * (wl + 3)))
-            self.dense(name + ".cat", cat, o.w_cat, o.b_cat, ops.ACT_GELU, mo, R)
-            self._mlp(name, mo, o, outb, T_hi)
-            pool.give(cat)
-            pool.give(mo)
-            if name in self.taps:
-                self.keep[name] = outb
-            return outb
+            return self._tap(name, outb)
         cat = pool.take((B, T_hi, 6 * C), dt)
         xn = pool.take((B, T_lo, C), dt)
         mo = pool.take((B, T_hi, C), dt)
@@ -686,8 +396,7 @@ class SgpBuilder:
         hid = pool.take((B, T_hi, 4 * C), dt)
         outb = pool.take((B, T_hi, C), dt)
         zslab = cat.view(-1)[4 * C:]
-        es, R, Rl = _esz(dt), B * T_hi, B * T_lo
-        wl = 2 * o.ks + o.up + 2
+        es = _esz(dt)
         steps.append(Step(name + ".ln1", "layernorm", lambda: ops.layernorm(z, o.ln1_w, o.ln1_b, out=zslab, ldy=6 * C,
                                                                             rows=R, C=C), 2 * R * C * es))
         steps.append(Step(name + ".ln2", "layernorm", lambda: ops.layernorm(xlo, o.ln2_w, o.ln2_b, out=xn), 2 * Rl * C * es))
@@ -700,9 +409,7 @@ class SgpBuilder:
         self.dense(name + ".fc2", hid, o.w_fc2, o.b_fc2, ops.ACT_NONE, outb, R, residual=mo)
         for t_ in (cat, xn, mo, gn, hid):
             pool.give(t_)
-        if name in self.taps:
-            self.keep[name] = outb
-        return outb
+        return self._tap(name, outb)
 
     def pyramid(self, feat, T, n, sgp, mixers, pre="_temp_fine."):
         """EDSGPMIXERLayers.forward (modules.py:69-87) on an NTC tensor."""
@@ -717,7 +424,7 @@ class SgpBuilder:
             pooled = self.last_pooled
             if pooled is None:
                 pooled = pool.take((B, lens[i + 1], C), cur.dtype)
-                if self.gemm and self.fused and str(cur.device) != "cpu":
+                if self.gemm and self.fused:
                     # lengths that do not halve: a pooling launch that also leaves the pooled rows' LayerNorm statistics
                     prs = torch.empty((B * lens[i + 1], 2), dtype=torch.float32, device=cur.device)
                     pooled._td_rowstat = prs
@@ -752,8 +459,8 @@ class PackedWeights:
         self.device = device
         sd = {k: _np(v) for k, v in state.items()}
         self.double_head = "_pred_fine._fc1._fc_out.weight" in sd
-        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)   # noqa: E731
-        dense = lambda a: f32(a).to(act_dtype).contiguous()                                       # noqa: E731
+        f32 = lambda a: _f32(a, device)                                                          # noqa: E731
+        bf16_gpu = act_dtype == torch.bfloat16 and str(device) != "cpu"       # the MFMA forms exist on the card only
 
         def bn_fold(pre):
             w, b = sd[pre + ".weight"].astype(np.float64), sd[pre + ".bias"].astype(np.float64)
@@ -774,8 +481,7 @@ class PackedWeights:
             # gate-shift-fuse sites of the bf16 engine: the module's channel interleave is folded into conv1's columns (the
             # blend launch leaves its slice in source channel order, ops.gate_shift(src_order=True)): column ci of the
             # packed weight is the column of the output channel that source channel ci is interleaved to
-            bw.gs_src = bool(blk.gsf_fold and GS_SRC_ORDER and self.mode == "gsf" and act_dtype == torch.bfloat16
-                             and str(device) != "cpu")
+            bw.gs_src = bool(blk.gsf_fold and GS_SRC_ORDER and self.mode == "gsf" and bf16_gpu)
             if bw.gs_src:
                 w1_mat = gs_source_order_columns(w1_mat, blk.gsf_fold)
             bw.w1 = DenseW(w1_mat, act_dtype, device)
@@ -795,10 +501,9 @@ class PackedWeights:
             bw.se_w2t = f32(sd[bp + ".se.fc2.weight"].reshape(blk.cout, blk.se_rd).T)
             bw.se_b2 = f32(sd[bp + ".se.fc2.bias"])
             bw.se_bf = (SimpleNamespace(**pack_se_bf16(sd[bp + ".se.fc1.weight"], sd[bp + ".se.fc2.weight"], device))
-                        if act_dtype == torch.bfloat16 and str(device) != "cpu" else None)
+                        if bf16_gpu else None)
             bw.se_mf = (SimpleNamespace(**pack_se_mfma(sd[bp + ".se.fc1.weight"], sd[bp + ".se.fc2.weight"], device))
-                        if (bw.se_bf is not None and True
-                            and ops.se_gate_mfma_fits(blk.cout, blk.se_rd)) else None)
+                        if (bf16_gpu and ops.se_gate_mfma_fits(blk.cout, blk.se_rd)) else None)
             bw.w3 = DenseW(sd[bp + ".conv3.conv.weight"].reshape(blk.cout, blk.cout), act_dtype, device, gated=True)
             # MFMA-fragment copies of conv1 / conv3 for the one-launch bottleneck (stride-1 identity blocks up to 384 wide)
             bw.fused = (SimpleNamespace(w1f=pack_mfma_frags(w1_mat, device),
@@ -818,7 +523,7 @@ class PackedWeights:
                 w3d = sd[gp + ".conv3D.weight"]                       # [2][F/2][3][3][3]
                 bw.gs_wq = f32(w3d.reshape(F, 27).T)                  # [27][F], c = g*F/2 + cl
                 bw.gs_b3d = f32(sd[gp + ".conv3D.bias"])
-                bw.gs_wqf = pack_gsf_q_frags(w3d, device) if (act_dtype == torch.bfloat16 and str(device) != "cpu") else None
+                bw.gs_wqf = pack_gsf_q_frags(w3d, device) if bf16_gpu else None
                 bw.gs_bnq = ops.gsq_bn_table(bw.gs_scale, bw.gs_shift) if bw.gs_wqf is not None else None
                 bw.gs_wpf = pack_gsf_p_frags(w3d, device) if bw.gs_wqf is not None else None
                 if self.mode == "gsf":
@@ -831,8 +536,7 @@ class PackedWeights:
             W.blocks.append(bw)
         W.front = None
         b0 = self.spec.blocks[0]
-        if act_dtype == torch.bfloat16 and b0.stride == 2 and b0.has_downsample and b0.cout <= 64 and not b0.gsf_fold \
-                and str(device) != "cpu":
+        if bf16_gpu and b0.stride == 2 and b0.has_downsample and b0.cout <= 64 and not b0.gsf_fold:
             bw0, bp0 = W.blocks[0], p + b0.name
             W.front = pack_front_weights(
                 sd[p + "stem.conv.weight"], W.stem_scale, W.stem_shift,
@@ -896,6 +600,50 @@ class ForwardEngine:
         self._plans = {}
 
     # ------------------------------------------------------------------ plan construction
+    def _se_conv3(self, bw, N, h2, w2, y2, pooled, gate, sc, out, out2=None):
+        """The last two steps of a bottleneck that is not one launch: the SE excitation from the grouped conv's pooled sums,
+        and conv3 with the gate on its operand + shortcut `sc` + ReLU (out2: the next block's gate-shift slice beside `out`)."""
+        blk, es, M2 = bw.spec, _esz(self.act_dtype), N * h2 * w2
+        return (Step(blk.name + ".se", "se_gate", lambda: _se(pooled, 1.0 / (h2 * w2), bw, gate),
+                     2 * N * blk.cout * 4 + 2 * blk.cout * blk.se_rd * 4, 4 * N * blk.cout * blk.se_rd),
+                Step(blk.name + ".conv3", bw.w3.kern(M2), lambda: bw.w3.run(
+                    y2, bw.s3, bw.h3, ops.ACT_RELU, residual=sc, a_scale=gate, a_scale_rows=h2 * w2, out=out, M=M2, out2=out2),
+                    *gemm_cost(M2, blk.cout, blk.cout, es, True)))
+
+    @staticmethod
+    def _block_done(pool, keep, taps, blk, dead, x, x_kept, out):
+        """A bottleneck's epilogue: its temporaries `dead` and its input x (unless a tap keeps it, or it is not the pool's) go
+        back to the pool, its output is recorded when it is a tap.  Returns whether the output must be kept."""
+        for t_ in dead:
+            pool.give(t_)
+        if not x_kept and hasattr(x, "_td_raw"):
+            pool.give(x)
+        tapname = "_features." + blk.name
+        if tapname in taps:
+            keep[tapname] = out
+        return tapname in taps
+
+    def _avgpool(self, steps, B, x, h, w, feat, frs=None):
+        """Appends avg-pool + positional encoding of the trunk's map x into feat, with the LayerNorm statistics of the feature
+        rows for the first SGP block's front kernel (frs: the caller's slice of a shared buffer)."""
+        pw, Wt = self.pw, self.pw.W
+        N, C = B * pw.clip_len, pw.spec.feat_dim
+        if frs is None:
+            frs = torch.empty((N, 2), dtype=torch.float32, device=self.device)
+        feat._td_rowstat = frs
+        steps.append(Step("avgpool", "avgpool_posenc", lambda: ops.avgpool_posenc(x, B, pw.clip_len, Wt.temp_enc, out=feat,
+                                                                                 rowstat=frs),
+                          (N * h * w + N) * C * _esz(self.act_dtype)))
+
+    def _sgp_heads(self, pool, steps, keep, taps, B, feat, head_out):
+        """Appends the SGP encoder-decoder over feat and the heads; returns the encoder-decoder's output."""
+        pw, Wt = self.pw, self.pw.W
+        N, C = B * pw.clip_len, pw.spec.feat_dim
+        cur = SgpBuilder(pool, steps, keep, taps, B, self.act_dtype).pyramid(feat, pw.clip_len, pw.n_layers, Wt.sgp, Wt.mixer)
+        steps.append(Step("heads", "heads", lambda: ops.heads(cur, Wt.head_w, Wt.head_b, out=head_out),
+                          N * C * _esz(self.act_dtype) + N * pw.n_out * 4, 2 * N * C * pw.n_out))
+        return cur
+
     def _blocks(self, pool, steps, keep, taps, B, x, h, w, blocks, x_kept, out_last=None):
         """Appends the launches of a run of bottlenecks for B clips (N = B*T frames) to `steps`; x (N,h,w,Cin) is the input
         map (owned by `pool` unless x_kept).  out_last: where the last block writes its output (a slice of a buffer shared
@@ -989,16 +737,8 @@ class ForwardEngine:
                                   + (24 * M if (blend_in and qt is not None) else 0)
                                   + (2 * blk.cout * blk.cout + blk.cout * blk.gw * 9) * es,
                                   2 * M * blk.cout * (2 * blk.cout + blk.gw * 9)))
-                for t_ in gs_bufs:
-                    pool.give(t_)
-                xs = xs_next
-                if not x_kept and hasattr(x, "_td_raw"):
-                    pool.give(x)
-                tapname = "_features." + blk.name
-                x_kept = tapname in taps
-                if x_kept:
-                    keep[tapname] = out
-                x = out
+                x_kept = self._block_done(pool, keep, taps, blk, gs_bufs, x, x_kept, out)
+                xs, x = xs_next, out
                 continue
             s = blk.stride
             h2, w2 = (h - 1) // s + 1, (w - 1) // s + 1
@@ -1017,56 +757,35 @@ class ForwardEngine:
                 steps.append(Step(blk.name + ".conv2", "gconv3x3", lambda y1=y1, bw=bw, blk=blk, y2=y2, pooled=pooled: ops.gconv3x3(
                     y1, bw.w2, bw.s2, bw.h2, blk.gw, blk.stride, wfrag=bw.w2frag, out=y2, pooled=pooled),
                     (M + M2) * blk.cout * es + blk.cout * blk.gw * 9 * 4, 2 * M2 * blk.cout * blk.gw * 9))
-            steps.append(Step(blk.name + ".se", "se_gate", lambda pooled=pooled, bw=bw, gate=gate, ic=1.0 / (h2 * w2): _se(pooled, ic, bw, gate),
-                2 * N * blk.cout * 4 + 2 * blk.cout * blk.se_rd * 4, 4 * N * blk.cout * blk.se_rd))
+            sc, shortcut = x, []
             if blk.has_downsample:
                 sc = pool.take((N, h2, w2, blk.cout), dt)
                 gather = (s, h, w, h2, w2) if s > 1 else None
-                steps.append(Step(blk.name + ".downsample", bw.wd.kern(M2), lambda x=x, bw=bw, sc=sc, gather=gather, M2=M2: bw.wd.run(
+                shortcut = [Step(blk.name + ".downsample", bw.wd.kern(M2), lambda x=x, bw=bw, sc=sc, gather=gather, M2=M2: bw.wd.run(
                     x, bw.sd, bw.hd, ops.ACT_NONE, gather=gather, out=sc, M=M2),
-                    *gemm_cost(M2, blk.cin, blk.cout, es)))
-            else:
-                sc = x
+                    *gemm_cost(M2, blk.cin, blk.cout, es))]
             out = (out_last if (out_last is not None and bw is blocks[-1]) else pool.take((N, h2, w2, blk.cout), dt))
             nxt = blocks[bi + 1].spec if bi + 1 < len(blocks) else None
             xs_next = None
             if nxt is not None and nxt.gsf_fold and GS_SLICE:
                 xs_next = pool.take((N, h2, w2, (nxt.gsf_fold + 7) // 8 * 8), dt)
-            steps.append(Step(blk.name + ".conv3", bw.w3.kern(M2), lambda y2=y2, bw=bw, gate=gate, sc=sc, out=out, M2=M2, hw2=h2 * w2, xs_next=xs_next: bw.w3.run(
-                y2, bw.s3, bw.h3, ops.ACT_RELU, residual=sc, a_scale=gate, a_scale_rows=hw2, out=out, M=M2, out2=xs_next),
-                *gemm_cost(M2, blk.cout, blk.cout, es, True)))
+            se, conv3 = self._se_conv3(bw, N, h2, w2, y2, pooled, gate, sc, out, out2=xs_next)
+            steps += [se, *shortcut, conv3]                     # (the shortcut conv launches between the two)
             # liveness: everything but `out` (and the next block's slice) dies here
-            for t_ in ([y1] if y1 is not None else []) + [y2, pooled, gate] + gs_bufs + ([sc] if blk.has_downsample else []):
-                pool.give(t_)
-            xs = xs_next
-            if not x_kept and hasattr(x, "_td_raw"):
-                pool.give(x)
-            tapname = "_features." + blk.name
-            x_kept = tapname in taps
-            if x_kept:
-                keep[tapname] = out
-            x, h, w = out, h2, w2
+            dead = ([y1] if y1 is not None else []) + [y2, pooled, gate] + gs_bufs + ([sc] if blk.has_downsample else [])
+            x_kept = self._block_done(pool, keep, taps, blk, dead, x, x_kept, out)
+            xs, x, h, w = xs_next, out, h2, w2
         return x, h, w, x_kept
 
     def _build_tail(self, B, feat, head_out, trunk_in=None, start=None):
         """The launches behind the sub-batch join, over all B clips: optionally the rest of the trunk (blocks[start:] on the
         map `trunk_in` = (x, h, w) that the sub-batch plans wrote) + avg-pool, then SGP encoder-decoder + heads."""
-        pw, Wt = self.pw, self.pw.W
-        T, C, dt = pw.clip_len, pw.spec.feat_dim, self.act_dtype
         pool, steps, keep = _Pool(self.device), [], {}
-        N = B * T
         if trunk_in is not None:
             x, h, w = trunk_in
-            x, h, w, _ = self._blocks(pool, steps, keep, set(), B, x, h, w, list(Wt.blocks[start:]), True)
-            frs = torch.empty((N, 2), dtype=torch.float32, device=self.device)
-            feat._td_rowstat = frs
-            steps.append(Step("avgpool", "avgpool_posenc", lambda x=x: ops.avgpool_posenc(x, B, T, Wt.temp_enc, out=feat,
-                                                                                       rowstat=frs),
-                              (N * h * w + N) * C * _esz(dt)))
-        sb = SgpBuilder(pool, steps, keep, set(), B, dt)
-        cur = sb.pyramid(feat, T, pw.n_layers, Wt.sgp, Wt.mixer)
-        steps.append(Step("heads", "heads", lambda cur=cur: ops.heads(cur, Wt.head_w, Wt.head_b, out=head_out),
-                          N * C * _esz(dt) + N * pw.n_out * 4, 2 * N * C * pw.n_out))
+            x, h, w, _ = self._blocks(pool, steps, keep, set(), B, x, h, w, list(self.pw.W.blocks[start:]), True)
+            self._avgpool(steps, B, x, h, w, feat)
+        cur = self._sgp_heads(pool, steps, keep, set(), B, feat, head_out)
         return SimpleNamespace(steps=steps, pool_bytes=pool.total_bytes(), sgp_out=cur)
 
     def _build(self, B, H, W, flip, taps, head_out=None, feat_out=None, stop_at=None, trunk_out=None, feat_rs=None,
@@ -1107,24 +826,14 @@ class ForwardEngine:
                 frames, Wt.front, crop, flip, y2=y2, shortcut=sc, pooled=pooled),
                               N * 3 * ch * cw + 2 * M2 * blk.cout * es,
                               2 * N * Ho * Wo * 32 * (27 + 2 * blk.cout) // 1 + 2 * M2 * blk.cout * blk.gw * 9))
-            steps.append(Step(blk.name + ".se", "se_gate", lambda bw=bw, pooled=pooled, gate=gate, ic=1.0 / (h2 * w2): _se(pooled, ic, bw, gate),
-                2 * N * blk.cout * 4 + 2 * blk.cout * blk.se_rd * 4, 4 * N * blk.cout * blk.se_rd))
-            steps.append(Step(blk.name + ".conv3", bw.w3.kern(M2), lambda bw=bw, y2=y2, sc=sc, gate=gate, out=out, M2=M2, hw2=h2 * w2: bw.w3.run(
-                y2, bw.s3, bw.h3, ops.ACT_RELU, residual=sc, a_scale=gate, a_scale_rows=hw2, out=out, M=M2),
-                *gemm_cost(M2, blk.cout, blk.cout, es, True)))
-            for t_ in (y2, sc, pooled, gate):
-                pool.give(t_)
+            steps += self._se_conv3(bw, N, h2, w2, y2, pooled, gate, sc, out)
+            x_kept = self._block_done(pool, keep, taps, blk, (y2, sc, pooled, gate), None, True, out)
             x, h, w = out, h2, w2
-            x_kept = ("_features." + blk.name) in taps
-            if x_kept:
-                keep["_features." + blk.name] = out
         else:
             x = pool.take((N, Ho, Wo, 32), dt)
-        if not fused_front:
             steps.append(Step("stem", "stem", lambda x=x: ops.stem(frames, Wt.stem_w, Wt.stem_scale, Wt.stem_shift, dt, crop,
                                                                    flip, out=x),
                               N * 3 * ch * cw + N * Ho * Wo * 32 * es, 2 * N * Ho * Wo * 32 * 27))
-        if not fused_front:
             h, w = Ho, Wo
             x_kept = "_features.stem" in taps
             if x_kept:
@@ -1137,28 +846,17 @@ class ForwardEngine:
         if stop_at is not None:          # trunk head only: the rest of the trunk runs once for all sub-batches (plan.tail)
             return SimpleNamespace(frames=frames, steps=steps, keep=keep, head_out=None, pool_bytes=pool.total_bytes(), B=B, T=T,
                                    h=h, w=w)
-        C = pw.spec.feat_dim
-        feat = pool.take((B, T, C), sgp_stream_dtype(dt, dev)) if feat_out is None else feat_out
-        # LayerNorm statistics of the feature rows for the first SGP block's front kernel (the caller's slice of the shared
-        # buffer when the temporal stage runs once for all sub-batches)
-        frs = feat_rs if feat_rs is not None else torch.empty((N, 2), dtype=torch.float32, device=dev)
-        feat._td_rowstat = frs
-        steps.append(Step("avgpool", "avgpool_posenc", lambda x=x, feat=feat, frs=frs: ops.avgpool_posenc(
-            x, B, T, Wt.temp_enc, out=feat, rowstat=frs), (N * h * w + N) * C * es))
+        feat = pool.take((B, T, pw.spec.feat_dim), sgp_stream_dtype(dt, dev)) if feat_out is None else feat_out
+        self._avgpool(steps, B, x, h, w, feat, feat_rs)
         keep["feat"] = feat
         if not x_kept:
             pool.give(x)
         if feat_out is not None:         # trunk only: the temporal stage runs once for all sub-batches (plan.tail)
             return SimpleNamespace(frames=frames, steps=steps, keep=keep, head_out=None, pool_bytes=pool.total_bytes(), B=B, T=T)
 
-        # ---------------- SGP encoder-decoder
-        sb = SgpBuilder(pool, steps, keep, taps, B, dt)
-        cur = sb.pyramid(feat, T, pw.n_layers, Wt.sgp, Wt.mixer)
-        keep["sgp_out"] = cur
         if head_out is None:
             head_out = torch.empty((N, pw.n_out), dtype=torch.float32, device=dev)
-        steps.append(Step("heads", "heads", lambda cur=cur: ops.heads(cur, Wt.head_w, Wt.head_b, out=head_out),
-                          N * C * es + N * pw.n_out * 4, 2 * N * C * pw.n_out))
+        keep["sgp_out"] = self._sgp_heads(pool, steps, keep, taps, B, feat, head_out)
         return SimpleNamespace(frames=frames, steps=steps, keep=keep, head_out=head_out,
                                pool_bytes=pool.total_bytes(), B=B, T=T)
 

@@ -77,7 +77,7 @@ def s1_front_parts(ch, cw, C1):
 
 
 def s1_front(frames_u8, fw, crop=None, flip=False, y2=None, shortcut=None, pooled=None):
-    """Fused pre-proc + stem + s1.b1.{conv1, conv2, downsample} (bf16).  fw: engine.pack_front_weights(...).
+    """Fused pre-proc + stem + s1.b1.{conv1, conv2, downsample} (bf16).  fw: packing.pack_front_weights(...).
     frames (N,3,H,W) uint8 -> y2 (N,Ho,Wo,C1), shortcut (N,Ho,Wo,C1), pooled (N,parts,C1) fp32 sums."""
     _chk(frames_u8, "frames", torch.uint8)
     N, _, H, W = frames_u8.shape
@@ -166,7 +166,7 @@ def bneck(x, w1f, s1, h1, w2f, s2, h2, se_w1f, se_b1, se_w2f, se_b2, R, w3f, s3,
           w2_tap_major=True):
     """Whole stride-1 bottleneck in one launch (tdeed_bneck_fwd): x (N,h,w,C) bf16 -> (N,h,w,C); G (N*h*w, Fp): gate-shift
     output spliced into conv1's operand; out2 (N*h*w, n2): compact copy of the first n2 output channels.
-    w2f: engine.pack_gconv_frags(..., tap_major=w2_tap_major) -- tap-major k-slots are the conflict-free order of this launch
+    w2f: packing.pack_gconv_frags(..., tap_major=w2_tap_major) -- tap-major k-slots are the conflict-free order of this launch
     (group width 8: bit-identical to the chain either way); False: the order tdeed_gconv3x3_fwd reads (16-wide groups)."""
     _chk(x, "x", torch.bfloat16); _chk(G, "G", torch.bfloat16); _chk(out2, "out2", torch.bfloat16)
     N, h, w, C = x.shape
@@ -183,7 +183,7 @@ def bneck_gs(x, gx, gate, ysum, xsum, cw1, cb1, cw2, cb2, T, F, Fp, w1f, s1, h1,
     """The one-launch bottleneck behind a gate-shift-fuse site with the site's blend inside its frame load
     (tdeed_bneck_gs_fwd): gx (N,h,w,ldx >= Fp) the slice's source, gate / ysum / xsum from gate_shift(gates_only=True).
     == bneck(x, G=gate_shift(gx, ..., src_order=True)), bit for bit.
-    qtail = (wpf, bn, F, Q): also the tap maps Q (N,h,w,6) of the NEXT block's site (fold F, wpf = engine.pack_gsf_p_frags,
+    qtail = (wpf, bn, F, Q): also the tap maps Q (N,h,w,6) of the NEXT block's site (fold F, wpf = packing.pack_gsf_p_frags,
     bn = gsq_bn_table) -- what gate_shift's first launch computes from `out`, in another fp32 summation order; that site then
     runs gate_shift(q_given=True)."""
     _chk(x, "x", torch.bfloat16); _chk(gx, "gx", torch.bfloat16); _chk(out2, "out2", torch.bfloat16)
@@ -223,7 +223,7 @@ def gemm_ws_fits(K, N, act_dtype):
 
 def gemm_ws(A, Wfrag, K, N, scale=None, shift=None, act=ACT_NONE, residual=None, a_scale=None, a_scale_rows=0,
             A0=None, k0=0, gather=None, out=None, M=None, lda=None, ldc=None, out2=None):
-    """Weight-stationary streaming form of gemm(); Wfrag from engine.pack_ws_weights."""
+    """Weight-stationary streaming form of gemm(); Wfrag from packing.pack_ws_weights."""
     _chk(A, "A")
     if M is None:
         M = A.numel() // A.shape[-1]
@@ -248,7 +248,7 @@ def gemm_rs_fits(M, K, N):
 
 def gemm_rs(A, Wfrag, K, N, scale=None, shift=None, act=ACT_NONE, residual=None, a_scale=None, a_scale_rows=0, A0=None, k0=0,
             out=None, M=None, out2=None):
-    """Register-stationary form of gemm_ws() for K = N = 320 (tdeed_gemm_rs_fwd); Wfrag from engine.pack_ws_weights."""
+    """Register-stationary form of gemm_ws() for K = N = 320 (tdeed_gemm_rs_fwd); Wfrag from packing.pack_ws_weights."""
     _chk(A, "A", torch.bfloat16)
     if M is None:
         M = A.numel() // A.shape[-1]
@@ -315,7 +315,7 @@ def se_gate_mfma(pooled, inv_cnt, w1f, b1, w2f, b2, R, out=None):
 
 
 def se_gate_bf16(pooled, inv_cnt, w1p, b1, w2p, b2, R, out=None):
-    """SE excitation with bf16 packed weights (engine.pack_se_bf16): pooled (N,parts,C) sums -> gate (N,C)."""
+    """SE excitation with bf16 packed weights (packing.pack_se_bf16): pooled (N,parts,C) sums -> gate (N,C)."""
     N, parts, C = pooled.shape
     if out is None:
         out = torch.empty((N, C), dtype=torch.float32, device=pooled.device)
@@ -785,7 +785,7 @@ def sgp_gemm_tiles(T, N, form):
 
 def sgp_gemm_gn_gelu(y, chsum, gn_w, gn_b, Wp, bias, N, out=None, form=None, G=16, eps=1e-5):
     """H (B,T,N) bf16 = GELU(GroupNorm(y) @ W^T + b).  y (B,T,K) bf16 | fp32; chsum fp32 (parts,B,K,2) or (B,K,2): per-channel
-    (sum, sum of squares) of y over each clip's rows; Wp: engine.pack_mfma_frags(W, ks_mult=12)."""
+    (sum, sum of squares) of y over each clip's rows; Wp: packing.pack_mfma_frags(W, ks_mult=12)."""
     B, T, K = y.shape
     parts = 1 if chsum.dim() == 3 else chsum.shape[0]
     form = form or sgp_gemm_form(0 if y.dtype == torch.bfloat16 else 3, B, T, N, K)

@@ -10,6 +10,7 @@ from types import SimpleNamespace
 import torch
 
 from . import ops, ops_bwd as B_, repack as R
+from .packing import gconv_frags_on_device, gsf_q_frags_on_device, stem_frags_on_device
 
 BN_EPS = 1e-5
 # ReLU masks of the BatchNorm backward recomputed from z (fa * z + fb > 0) instead of read from the stored activation
@@ -71,8 +72,7 @@ class GateShiftTrain:
         self.wq = w3.t().contiguous()                  # [27][F]: forward (VALU tap kernel)
         self.wqf = None                                # bf16: the tap convolution runs on the MFMA kernel of the inference path
         if self.dt == torch.bfloat16:
-            from .engine import gsf_q_frags_on_device
-            self.wqf = gsf_q_frags_on_device(sd[pre + ".conv3D.weight"])
+            self.wqf = gsf_q_frags_on_device(sd[pre + ".conv3D.weight"], R.to_bf16)
         self.b3 = sd[pre + ".conv3D.bias"]
         self.w_pad = R.pad1d(sd[pre + ".bn.weight"], self.Fp)      # BatchNorm3d affine, zero in the pad columns
         self.b_pad = R.pad1d(sd[pre + ".bn.bias"], self.Fp)
@@ -155,7 +155,6 @@ class StemTrain:
     def repack(self):
         self.wf = None
         if self.dt == torch.bfloat16:
-            from .engine import stem_frags_on_device
             self.wf = stem_frags_on_device(self.sd["_features.stem.conv.weight"])
 
 
@@ -215,12 +214,11 @@ class BottleneckTrain:
         # a grouped conv of dy with the weights flipped in space and transposed inside each group
         self.w2frag = self.w2frag_t = None
         if dt == torch.bfloat16:
-            from .engine import gconv_frags_on_device
             w2 = sd[pre + ".conv2.conv.weight"]
-            self.w2frag = gconv_frags_on_device(w2, gw)
+            self.w2frag = gconv_frags_on_device(w2, gw, R.to_bf16)
             if blk.stride == 1:
                 wt = w2.reshape(G, gw, gw, 3, 3).transpose(1, 2).flip(3, 4).reshape(blk.cout, gw, 3, 3)
-                self.w2frag_t = gconv_frags_on_device(wt, gw)
+                self.w2frag_t = gconv_frags_on_device(wt, gw, R.to_bf16)
         Rd, C = blk.se_rd, blk.cout
         self.se_w1 = sd[pre + ".se.fc1.weight"].reshape(Rd, C).contiguous()
         self.se_w2 = sd[pre + ".se.fc2.weight"].reshape(C, Rd).contiguous()

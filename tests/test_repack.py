@@ -181,3 +181,16 @@ def test_tap_map_fragments_of_both_forms_restate_the_conv3d():
             q2 += Pp[dy:dy + h, dx:dx + w, tap * 6:tap * 6 + 6]
         assert np.allclose(q1, ref, rtol=0, atol=1e-9 * max(1.0, np.abs(ref).max()))
         assert np.allclose(q2, ref, rtol=0, atol=1e-9 * max(1.0, np.abs(ref).max()))
+
+
+def test_on_device_forms_and_pack_ws_restate_the_numpy_layouts():
+    """The gather through the cached index map against the layout functions themselves (CPU tensors): the stem fragments, and
+    repack.pack_ws against pack_ws_weights at the smallest shapes with more than one tile in each direction."""
+    from tdeed_amd.engine import _stem_frags_np, pack_ws_weights, stem_frags_on_device
+    rng = np.random.default_rng(7)
+    w = rng.standard_normal((32, 3, 3, 3)).astype(np.float32)
+    assert torch.equal(stem_frags_on_device(torch.from_numpy(w)), torch.from_numpy(_stem_frags_np(w)))
+    for N, K in ((32, 32), (64, 96)):
+        W = torch.from_numpy(rng.standard_normal((N, K)).astype(np.float32))
+        assert torch.equal(repack.pack_ws(W).to(torch.bfloat16), pack_ws_weights(W, torch.bfloat16, "cpu"))
+        assert torch.equal(repack.pack_ws(W.t()).to(torch.bfloat16), pack_ws_weights(W.t(), torch.bfloat16, "cpu"))
