@@ -112,6 +112,21 @@ int tdeed_gemm_ws_fwd(const void* A, long lda, const void* A0, long lda0, int k0
                       void* C, long ldc, int gather_stride, int gather_hi, int gather_wi,
                       int gather_ho, int gather_wo, void* C2, long ldc2, int n2, int dtype, void* stream);
 
+/* conv3 of a bottleneck whose shortcut is a 1x1 conv (stride 1|2), the two launches
+ *   sc = bf16((gather(As) @ Ws^T) * sscale + sshift);  C = act((A' @ W^T) * scale + shift + sc)
+ * as one: the shortcut product goes into a second accumulator set, is scaled, shifted and rounded to bf16 in registers and
+ * takes the residual's place -- bit-identical to tdeed_gemm_ws_fwd twice, and the shortcut map never exists.  Arguments of
+ * tdeed_gemm_ws_fwd without R / ldr; As [rows of the block's input][ldas], Ks its channels, Wsfrag = pack_ws_weights(Ws)
+ * (same N); the gather geometry applies to As only (A is not gathered).  bf16; both weights sit in LDS (up to 80 KB =
+ * two workgroups per CU).  tdeed_gemm_ws_sc_fits: (ceil(K/32), ceil(Ks/32)) is (2, 1) or (5, 2) and the weights fit. */
+int tdeed_gemm_ws_sc_fits(int K, int Ks, int N, int dtype);
+int tdeed_gemm_ws_sc_fwd(const void* A, long lda, const void* A0, long lda0, int k0, const float* a_scale,
+                         int a_scale_rows, int M, int K, int N, const void* Wfrag, const float* scale,
+                         const float* shift, const void* As, long ldas, int Ks, const void* Wsfrag,
+                         const float* sscale, const float* sshift, int act, void* C, long ldc, int gather_stride,
+                         int gather_hi, int gather_wi, int gather_ho, int gather_wo, void* C2, long ldc2, int n2,
+                         int dtype, void* stream);
+
 /* ---- grouped 3x3 conv + BN + ReLU + SE squeeze ---------------------------------------------
  * timm Bottleneck.conv2 (groups = C/gw, stride 1|2, pad 1) + BN(eval) + ReLU, and the SE
  * squeeze (sum over H,W) of its output.  x: [N][Hi][Wi][C], y: [N][Ho][Wo][C], gw in {8,16}.

@@ -47,6 +47,9 @@ _SIGS = {
     "tdeed_gemm_ws_fits": ([c_int, c_int, c_int], c_int),
     "tdeed_gemm_ws_fwd": ([P, c_long, P, c_long, c_int, P, c_int, c_int, c_int, c_int, P, P, P, P, c_long,
                            c_int, P, c_long, c_int, c_int, c_int, c_int, c_int, P, c_long, c_int, c_int, P], c_int),
+    "tdeed_gemm_ws_sc_fits": ([c_int, c_int, c_int, c_int], c_int),
+    "tdeed_gemm_ws_sc_fwd": ([P, c_long, P, c_long, c_int, P, c_int, c_int, c_int, c_int, P, P, P, P, c_long, c_int, P, P, P,
+                              c_int, P, c_long, c_int, c_int, c_int, c_int, c_int, P, c_long, c_int, c_int, P], c_int),
     "tdeed_gconv3x3_parts": ([c_int, c_int, c_int, c_int, c_int], c_int),
     "tdeed_gconv3x3_mfma_fits": ([c_int, c_int, c_int, c_int], c_int),
     "tdeed_gconv3x3_fwd": ([P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, c_int, c_int, P], c_int),

@@ -603,13 +603,38 @@ struct GemmWsP {
   int NTS;                        // n-tiles per block slice (blockIdx.y selects the slice; == NT when W fits LDS)
   void* C2; long ldc2; int n2;    // optional second, compact copy of columns [0, n2) of C
   float* colpart;                 // gemm_rs STATS: [gridDim.x][2][N] per-workgroup column sums / sums of squares of the stored C
+  // gemm_ws KS2 > 0: the block's shortcut conv as a second contraction (rows of As through the g_* gather, Ks channels)
+  const void* As; long ldas; int Ks;
+  const void* Wsf;                // [NT][KS2][64] x 16 B
+  const float* sscale; const float* sshift;
 };
+
+// global -> LDS copy of nfr packed fragments, 8 per thread in flight (round 6: `wdst[i] = src[i]` per trip was one
+// `global_load; s_waitcnt vmcnt(0)` per 16 bytes -- a 152 x 152 weight cost every workgroup 13 dependent L2 round trips
+// before its first row)
+template <typename frag_t, int NTHR>
+__device__ __forceinline__ void ws_fill_frags(frag_t* wdst, const frag_t* src, int nfr, int tid) {
+  constexpr int WB = 8;
+  for (int i0 = tid; i0 < nfr; i0 += NTHR * WB) {
+    frag_t v[WB];
+#pragma unroll
+    for (int b_ = 0; b_ < WB; ++b_) v[b_] = src[min(i0 + b_ * NTHR, nfr - 1)];
+    TD_ISSUE_FENCE();
+#pragma unroll
+    for (int b_ = 0; b_ < WB; ++b_)
+      if (i0 + b_ * NTHR < nfr) wdst[i0 + b_ * NTHR] = v[b_];
+  }
+}
 
 // WLDS = false: the weights do not fit LDS (K = N = 368): fragments are read straight from global memory
 // (1-KiB coalesced wave loads of the pre-packed array; L1/L2 resident, all waves of a CU walk it in step).
 // NW: waves per workgroup (4; 8 for the sliced form, where the LDS budget leaves one workgroup per CU and two waves per
 // SIMD are needed for one wave's loads to travel while the other one computes).
-template <typename T, int KS, bool WLDS, int NW = 4>
+// KS2 > 0 (whole W in LDS only): conv3 of a block with a shortcut conv.  The residual is not read: it is computed here, as
+// a second contraction over KS2 k-steps of the rows of As (the block's input, through the stride-2 gather, which then
+// applies to As alone) into a second accumulator set, scaled, shifted and rounded to T exactly as the shortcut launch
+// stores it -- the bits of the two launches, without the shortcut map's round trip.
+template <typename T, int KS, bool WLDS, int NW = 4, int KS2 = 0>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_ws_kernel(const GemmWsP p) {
   constexpr int NTHR = NW * 64, CR = NW * 32;        // threads, rows per chunk
   constexpr int EPC = Chunk<T>::N;
@@ -622,30 +647,29 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_ws_kernel(const
   const frag_t* wl = WLDS ? reinterpret_cast<const frag_t*>(smem) : reinterpret_cast<const frag_t*>(p.Wf);
   float* ssc = reinterpret_cast<float*>(smem + wbytes);               // [nts*16] scale (logical order)
   float* ssh = ssc + (WLDS ? p.NTS : p.NT) * 16;
+  // KS2: behind them the shortcut's fragments [NT][KS2][64] and its scale / shift (the tables above are 128 B per tile)
+  const frag_t* wl2 = reinterpret_cast<const frag_t*>(ssh + p.NTS * 16);
+  float* ssc2 = reinterpret_cast<float*>(smem + wbytes + (size_t)p.NTS * 128 + (size_t)p.NTS * KS2 * 64 * 16);
+  float* ssh2 = ssc2 + p.NTS * 16;
+  static_assert(KS2 == 0 || WLDS, "the two-operand form keeps both weights in LDS");
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   {
     if (WLDS) {
       frag_t* wdst = reinterpret_cast<frag_t*>(smem);
       const frag_t* src = reinterpret_cast<const frag_t*>(p.Wf) + (size_t)nt0 * KS * 64;
       TD_DEV_ASSERT(nts <= p.NTS && nt0 + nts <= p.NT);
-      // 8 fragments per thread in flight (round 6: `wdst[i] = src[i]` per trip was one `global_load; s_waitcnt vmcnt(0)` per
-      // 16 bytes -- a 152 x 152 weight cost every workgroup 13 dependent L2 round trips before its first row)
-      const int nfr = nts * KS * 64;
-      constexpr int WB = 8;
-      for (int i0 = tid; i0 < nfr; i0 += NTHR * WB) {
-        frag_t v[WB];
-#pragma unroll
-        for (int b_ = 0; b_ < WB; ++b_) v[b_] = src[min(i0 + b_ * NTHR, nfr - 1)];
-        TD_ISSUE_FENCE();
-#pragma unroll
-        for (int b_ = 0; b_ < WB; ++b_)
-          if (i0 + b_ * NTHR < nfr) wdst[i0 + b_ * NTHR] = v[b_];
-      }
+      ws_fill_frags<frag_t, NTHR>(wdst, src, nts * KS * 64, tid);
+      if constexpr (KS2 > 0)
+        ws_fill_frags<frag_t, NTHR>(const_cast<frag_t*>(wl2), reinterpret_cast<const frag_t*>(p.Wsf), nts * KS2 * 64, tid);
     }
     for (int i = tid; i < nts * 16; i += NTHR) {
       const int n = nt0 * 16 + i;
       ssc[i] = (p.scale && n < p.N) ? p.scale[n] : 1.0f;
       ssh[i] = (p.shift && n < p.N) ? p.shift[n] : 0.0f;
+      if constexpr (KS2 > 0) {
+        ssc2[i] = (p.sscale && n < p.N) ? p.sscale[n] : 1.0f;
+        ssh2[i] = (p.sshift && n < p.N) ? p.sshift[n] : 0.0f;
+      }
     }
   }
   __syncthreads();
@@ -654,6 +678,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_ws_kernel(const
   for (long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
     const long mbase = chunk * CR + wv * 32;
     frag_t xf[2][KS];
+    frag_t xs[2][KS2 > 0 ? KS2 : 1];
     bool mok[2];
     long mrow[2];
 #pragma unroll
@@ -669,6 +694,17 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_ws_kernel(const
         const unsigned f = mu / per, rem = mu - f * per;
         const unsigned yo = rem / (unsigned)p.g_wo, xo = rem - yo * (unsigned)p.g_wo;
         src = ((long)f * p.g_hi + (long)yo * p.g_stride) * p.g_wi + (long)xo * p.g_stride;
+      }
+      if constexpr (KS2 > 0) {                   // the gathered rows are the shortcut's; conv3's own operand is row m
+        const T* srow2 = reinterpret_cast<const T*>(p.As) + src * p.ldas;
+#pragma unroll
+        for (int ks = 0; ks < KS2; ++ks) {
+          const int k = (ks * 4 + q) * EPC;
+          u32x4 v = {0u, 0u, 0u, 0u};
+          if (mok[mt] && k < p.Ks) v = *reinterpret_cast<const u32x4*>(srow2 + k);
+          xs[mt][ks] = *reinterpret_cast<frag_t*>(&v);
+        }
+        src = mm;
       }
       const T* arow = reinterpret_cast<const T*>(p.A) + src * p.lda;
       const T* a0row = p.A0 ? reinterpret_cast<const T*>(p.A0) + src * p.lda0 : nullptr;
@@ -698,7 +734,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_ws_kernel(const
     for (int tp = 0; tp < nts; tp += 2) {            // 32 output channels per pass (tp: tile within the slice)
       const int chp = (nt0 + tp) * 16 + q * 8;
       u32x4 rpre[2][8 / EPC];
-      if (p.R && chp < p.N) {                          // residual chunks: issued now, consumed after the MFMAs
+      if (KS2 == 0 && p.R && chp < p.N) {                          // residual chunks: issued now, consumed after the MFMAs
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -720,6 +756,23 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_ws_kernel(const
           acc[1][mt] = mma<T>(w1, xf[mt][ks], acc[1][mt]);
         }
       }
+      f32x4 accs[2][2];
+      if constexpr (KS2 > 0) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int mt = 0; mt < 2; ++mt) accs[t][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KS2; ++ks) {
+          const frag_t w0 = wl2[((tp + 0) * KS2 + ks) * 64 + lane];
+          const frag_t w1 = wl2[((tp + 1) * KS2 + ks) * 64 + lane];
+#pragma unroll
+          for (int mt = 0; mt < 2; ++mt) {
+            accs[0][mt] = mma<T>(w0, xs[mt][ks], accs[0][mt]);
+            accs[1][mt] = mma<T>(w1, xs[mt][ks], accs[1][mt]);
+          }
+        }
+      }
       const int ch = (nt0 + tp) * 16 + q * 8;         // first of this lane's 8 logical channels
       if (ch < p.N) {
         float sc[8], sh[8];
@@ -735,7 +788,26 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_ws_kernel(const
             v[4 + r] = acc[1][mt][r] * sc[4 + r] + sh[4 + r];
           }
           const long m = mrow[mt];
-          if (p.R) {
+          if constexpr (KS2 > 0) {
+            // the shortcut launch's epilogue (no activation) and its store's rounding, then conv3's residual add
+            float sv[8];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              sv[r] = accs[0][mt][r] * ssc2[tp * 16 + q * 8 + r] + ssh2[tp * 16 + q * 8 + r];
+              sv[4 + r] = accs[1][mt][r] * ssc2[tp * 16 + q * 8 + 4 + r] + ssh2[tp * 16 + q * 8 + 4 + r];
+            }
+#pragma unroll
+            for (int h = 0; h < 8 / EPC; ++h) {
+              u32x4 rb;
+              float rv[EPC];
+#pragma unroll
+              for (int e = 0; e < EPC; ++e) rv[e] = sv[h * EPC + e];
+              Chunk<T>::store(reinterpret_cast<T*>(&rb), rv);
+              Chunk<T>::load(reinterpret_cast<const T*>(&rb), rv);
+#pragma unroll
+              for (int e = 0; e < EPC; ++e) v[h * EPC + e] += rv[e];
+            }
+          } else if (p.R) {
             float rv[EPC];
 #pragma unroll
             for (int h = 0; h < 8 / EPC; ++h) {
@@ -891,6 +963,80 @@ extern "C" int tdeed_gemm_ws_fwd(const void* A, long lda, const void* A0, long l
   p.C2 = C2; p.ldc2 = ldc2; p.n2 = C2 ? n2 : 0;
   hipStream_t st = (hipStream_t)stream;
   return dtype == TDEED_F32 ? launch_gemm_ws<float>(p, st) : launch_gemm_ws<bf16_t>(p, st);
+}
+
+// ---- conv3 with the block's shortcut conv as a second contraction (gemm_ws_kernel KS2 > 0) ----
+// Both weights whole in LDS: up to 80 KB, which still leaves two workgroups per CU (s3.b1 of RegNetY-200MF: 50 + 20 KB of
+// fragments).  bf16 only; the instances are the (k-steps, shortcut k-steps) pairs of the stride-2 blocks the narrow kernel
+// serves: (2, 1) = 56 <- 24 channels, (5, 2) = 152 <- 56 and 144 <- 64.
+static constexpr size_t WS_SC_LDS_MAX = 80 * 1024;
+static size_t ws_sc_smem(int NT, int KS, int KS2) {
+  return (size_t)NT * (KS + KS2) * 64 * 16 + (size_t)NT * 16 * 4 * sizeof(float);
+}
+extern "C" int tdeed_gemm_ws_sc_fits(int K, int Ks, int N, int dtype) {
+  if (dtype != TDEED_BF16 || K <= 0 || Ks <= 0 || N <= 0) return 0;
+  const int KS = (K + 31) / 32, KS2 = (Ks + 31) / 32, NT = (N + 31) / 32 * 2;
+  if (!((KS == 2 && KS2 == 1) || (KS == 5 && KS2 == 2))) return 0;
+  return ws_sc_smem(NT, KS, KS2) <= WS_SC_LDS_MAX;
+}
+
+template <int KS, int KS2>
+static int launch_gemm_ws_sc(const GemmWsP& p, hipStream_t st) {
+  const size_t smem = ws_sc_smem(p.NT, KS, KS2);
+  static TdDevOnce attr_set;
+  if (smem > 64 * 1024 && !attr_set.get()) {
+    if (hipFuncSetAttribute((const void*)gemm_ws_kernel<bf16_t, KS, true, 4, KS2>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)WS_SC_LDS_MAX) != hipSuccess) {
+      tdeed_set_error("gemm_ws_sc: hipFuncSetAttribute failed");
+      return TDEED_ERR_RUNTIME;
+    }
+    attr_set.set();
+  }
+  // persistent workgroups, all resident (launch_gemm_ws): as many per CU as the two weights' LDS allows, at most 4
+  const long nchunks = ((long)p.M + 127) / 128;
+  long per_cu = (long)((160 * 1024) / smem);
+  if (per_cu > 4) per_cu = 4;
+  long gx = 256 * per_cu;
+  if (gx > nchunks) gx = nchunks;
+  hipLaunchKernelGGL((gemm_ws_kernel<bf16_t, KS, true, 4, KS2>), dim3((unsigned)gx, 1), dim3(256), smem, st, p);
+  TD_LAUNCH_CHECK("gemm_ws_sc");
+  return TDEED_OK;
+}
+
+extern "C" int tdeed_gemm_ws_sc_fwd(const void* A, long lda, const void* A0, long lda0, int k0, const float* a_scale,
+                                    int a_scale_rows, int M, int K, int N, const void* Wfrag, const float* scale,
+                                    const float* shift, const void* As, long ldas, int Ks, const void* Wsfrag,
+                                    const float* sscale, const float* sshift, int act, void* C, long ldc, int gather_stride,
+                                    int gather_hi, int gather_wi, int gather_ho, int gather_wo, void* C2, long ldc2, int n2,
+                                    int dtype, void* stream) {
+  TD_CHECK(A && Wfrag && C && As && Wsfrag, "gemm_ws_sc: null pointer");
+  TD_CHECK(!C2 || (n2 > 0 && n2 % 8 == 0 && n2 <= N && ldc2 % 8 == 0 && ldc2 >= n2),
+           "gemm_ws_sc: bad second output n2=%d ldc2=%ld", n2, ldc2);
+  TD_CHECK(M > 0 && K > 0 && N > 0 && Ks > 0, "gemm_ws_sc: bad sizes M=%d K=%d N=%d Ks=%d", M, K, N, Ks);
+  TD_CHECK(dtype == TDEED_BF16, "gemm_ws_sc: bf16 only (dtype %d)", dtype);
+  TD_CHECK(K % 8 == 0 && N % 8 == 0 && Ks % 8 == 0 && lda % 8 == 0 && ldc % 8 == 0 && ldas % 8 == 0 && lda >= K && ldas >= Ks &&
+               ldc >= N,
+           "gemm_ws_sc: K, N, Ks, lda, ldc, ldas must be multiples of 8 and the strides cover the rows");
+  TD_CHECK(!A0 || (k0 % 8 == 0 && lda0 % 8 == 0 && k0 <= K && lda0 >= k0), "gemm_ws_sc: bad splice");
+  TD_CHECK(act >= 0 && act <= 2, "gemm_ws_sc: bad act %d", act);
+  TD_CHECK(tdeed_gemm_ws_sc_fits(K, Ks, N, dtype), "gemm_ws_sc: K=%d Ks=%d N=%d is not one of the two-operand forms", K, Ks, N);
+  if (gather_stride > 1)
+    TD_CHECK(gather_hi > 0 && gather_wi > 0 && gather_ho > 0 && gather_wo > 0 && M % (gather_ho * gather_wo) == 0 &&
+                 (long)(gather_ho - 1) * gather_stride < gather_hi && (long)(gather_wo - 1) * gather_stride < gather_wi,
+             "gemm_ws_sc: bad gather geometry");
+  GemmWsP p{};
+  p.A = A; p.lda = lda; p.A0 = A0; p.lda0 = lda0; p.k0 = A0 ? k0 : 0;
+  p.a_scale = a_scale; p.a_scale_rows = a_scale_rows > 0 ? a_scale_rows : 1;
+  p.M = M; p.K = K; p.N = N; p.Wf = Wfrag; p.scale = scale; p.shift = shift;
+  p.act = act; p.C = C; p.ldc = ldc;
+  p.g_stride = gather_stride > 1 ? gather_stride : 1;
+  p.g_hi = gather_hi; p.g_wi = gather_wi; p.g_ho = gather_ho; p.g_wo = gather_wo;
+  p.NT = (N + 31) / 32 * 2;
+  p.NTS = p.NT;
+  p.C2 = C2; p.ldc2 = ldc2; p.n2 = C2 ? n2 : 0;
+  p.As = As; p.ldas = ldas; p.Ks = Ks; p.Wsf = Wsfrag; p.sscale = sscale; p.sshift = sshift;
+  hipStream_t st = (hipStream_t)stream;
+  return (K + 31) / 32 == 2 ? launch_gemm_ws_sc<2, 1>(p, st) : launch_gemm_ws_sc<5, 2>(p, st);
 }
 
 // =============================================================================================

@@ -203,6 +203,9 @@ BNECK_BLEND = True
 BNECK_QTAIL = True
 C1_GCONV = os.environ.get("TDEED_C1_GCONV", "1") == "1"           # conv1 (+ downsample) computed inside the grouped conv's launch
 C1_GCONV_MAX_CIN = 160
+# the shortcut conv of a strided block as a second contraction inside conv3's launch (tdeed_gemm_ws_sc_fwd): no `.downsample`
+# launch, and the shortcut map is neither written nor read back
+SC_IN_CONV3 = True
 
 
 def _bneck_fused(bw, h, w, out_is_slice):
@@ -600,15 +603,24 @@ class ForwardEngine:
         self._plans = {}
 
     # ------------------------------------------------------------------ plan construction
-    def _se_conv3(self, bw, N, h2, w2, y2, pooled, gate, sc, out, out2=None):
+    def _se_conv3(self, bw, N, h2, w2, y2, pooled, gate, sc, out, out2=None, sc_from=None):
         """The last two steps of a bottleneck that is not one launch: the SE excitation from the grouped conv's pooled sums,
-        and conv3 with the gate on its operand + shortcut `sc` + ReLU (out2: the next block's gate-shift slice beside `out`)."""
+        and conv3 with the gate on its operand + shortcut `sc` + ReLU (out2: the next block's gate-shift slice beside `out`).
+        sc_from = (x, gather): no `sc` map -- conv3's launch computes the shortcut conv from the block's input x itself."""
         blk, es, M2 = bw.spec, _esz(self.act_dtype), N * h2 * w2
-        return (Step(blk.name + ".se", "se_gate", lambda: _se(pooled, 1.0 / (h2 * w2), bw, gate),
-                     2 * N * blk.cout * 4 + 2 * blk.cout * blk.se_rd * 4, 4 * N * blk.cout * blk.se_rd),
-                Step(blk.name + ".conv3", bw.w3.kern(M2), lambda: bw.w3.run(
-                    y2, bw.s3, bw.h3, ops.ACT_RELU, residual=sc, a_scale=gate, a_scale_rows=h2 * w2, out=out, M=M2, out2=out2),
-                    *gemm_cost(M2, blk.cout, blk.cout, es, True)))
+        se = Step(blk.name + ".se", "se_gate", lambda: _se(pooled, 1.0 / (h2 * w2), bw, gate),
+                  2 * N * blk.cout * 4 + 2 * blk.cout * blk.se_rd * 4, 4 * N * blk.cout * blk.se_rd)
+        if sc_from is not None:
+            x, gather = sc_from
+            return (se, Step(blk.name + ".conv3", "gemm_ws", lambda: ops.gemm_ws_sc(
+                y2, bw.w3.w, blk.cout, blk.cout, bw.s3, bw.h3, x, bw.wd.w, blk.cin, bw.sd, bw.hd, ops.ACT_RELU, a_scale=gate,
+                a_scale_rows=h2 * w2, gather=gather, out=out, M=M2, out2=out2),
+                # y2, the gathered rows of x, out, both weights
+                (M2 * (2 * blk.cout + blk.cin) + blk.cout * (blk.cout + blk.cin)) * es,
+                2 * M2 * blk.cout * (blk.cout + blk.cin)))
+        return (se, Step(blk.name + ".conv3", bw.w3.kern(M2), lambda: bw.w3.run(
+            y2, bw.s3, bw.h3, ops.ACT_RELU, residual=sc, a_scale=gate, a_scale_rows=h2 * w2, out=out, M=M2, out2=out2),
+            *gemm_cost(M2, blk.cout, blk.cout, es, True)))
 
     @staticmethod
     def _block_done(pool, keep, taps, blk, dead, x, x_kept, out):
@@ -757,10 +769,13 @@ class ForwardEngine:
                 steps.append(Step(blk.name + ".conv2", "gconv3x3", lambda y1=y1, bw=bw, blk=blk, y2=y2, pooled=pooled: ops.gconv3x3(
                     y1, bw.w2, bw.s2, bw.h2, blk.gw, blk.stride, wfrag=bw.w2frag, out=y2, pooled=pooled),
                     (M + M2) * blk.cout * es + blk.cout * blk.gw * 9 * 4, 2 * M2 * blk.cout * blk.gw * 9))
-            sc, shortcut = x, []
-            if blk.has_downsample:
+            sc, shortcut, sc_from = x, [], None
+            gather = (s, h, w, h2, w2) if s > 1 else None
+            if (SC_IN_CONV3 and blk.has_downsample and dt == torch.bfloat16 and bw.w3.ws and bw.wd.ws
+                    and ops.gemm_ws_sc_fits(blk.cout, blk.cin, blk.cout, dt)):
+                sc, sc_from = None, (x, gather)
+            elif blk.has_downsample:
                 sc = pool.take((N, h2, w2, blk.cout), dt)
-                gather = (s, h, w, h2, w2) if s > 1 else None
                 shortcut = [Step(blk.name + ".downsample", bw.wd.kern(M2), lambda x=x, bw=bw, sc=sc, gather=gather, M2=M2: bw.wd.run(
                     x, bw.sd, bw.hd, ops.ACT_NONE, gather=gather, out=sc, M=M2),
                     *gemm_cost(M2, blk.cin, blk.cout, es))]
@@ -769,10 +784,10 @@ class ForwardEngine:
             xs_next = None
             if nxt is not None and nxt.gsf_fold and GS_SLICE:
                 xs_next = pool.take((N, h2, w2, (nxt.gsf_fold + 7) // 8 * 8), dt)
-            se, conv3 = self._se_conv3(bw, N, h2, w2, y2, pooled, gate, sc, out, out2=xs_next)
+            se, conv3 = self._se_conv3(bw, N, h2, w2, y2, pooled, gate, sc, out, out2=xs_next, sc_from=sc_from)
             steps += [se, *shortcut, conv3]                     # (the shortcut conv launches between the two)
             # liveness: everything but `out` (and the next block's slice) dies here
-            dead = ([y1] if y1 is not None else []) + [y2, pooled, gate] + gs_bufs + ([sc] if blk.has_downsample else [])
+            dead = ([y1] if y1 is not None else []) + [y2, pooled, gate] + gs_bufs + ([sc] if shortcut else [])
             x_kept = self._block_done(pool, keep, taps, blk, dead, x, x_kept, out)
             xs, x, h, w = xs_next, out, h2, w2
         return x, h, w, x_kept

@@ -242,6 +242,36 @@ def gemm_ws(A, Wfrag, K, N, scale=None, shift=None, act=ACT_NONE, residual=None,
     return out
 
 
+def gemm_ws_sc_fits(K, Ks, N, act_dtype):
+    """True when gemm_ws_sc() serves a conv3 of K -> N channels with a shortcut conv of Ks -> N."""
+    lib = _lib.load()
+    if not hasattr(lib, "tdeed_gemm_ws_sc_fits"):       # an A/B flavour of the library built from an older revision
+        return False
+    return lib.tdeed_gemm_ws_sc_fits(K, Ks, N, dtype_code(act_dtype)) != 0
+
+
+def gemm_ws_sc(A, Wfrag, K, N, scale, shift, As, Wsfrag, Ks, sscale, sshift, act=ACT_NONE, a_scale=None, a_scale_rows=0,
+               A0=None, k0=0, gather=None, out=None, M=None, out2=None):
+    """gemm_ws(A, ..., residual=gemm_ws(As, Wsfrag, Ks, N, sscale, sshift, ACT_NONE, gather=gather)) in one launch
+    (tdeed_gemm_ws_sc_fwd): the shortcut conv of a bottleneck inside its conv3, bit for bit.  A (M, K) bf16; As the block's
+    input rows (.., Ks), gathered with gather = (stride, hi, wi, ho, wo) when the block is strided."""
+    _chk(A, "A", torch.bfloat16); _chk(As, "As", torch.bfloat16)
+    if M is None:
+        M = A.numel() // A.shape[-1]
+    rows_s = As.numel() // As.shape[-1]
+    g = gather if gather is not None else (1, 0, 0, 0, 0)
+    need = (M // (g[3] * g[4])) * g[1] * g[2] if gather is not None else M
+    if rows_s < need or A.numel() // A.shape[-1] < M:
+        raise ValueError(f"gemm_ws_sc: operands hold {A.numel() // A.shape[-1]} / {rows_s} rows, {M} / {need} needed")
+    if out is None:
+        out = torch.empty((M, N), dtype=A.dtype, device=A.device)
+    call("tdeed_gemm_ws_sc_fwd", ptr(A), A.shape[-1], ptr(A0), (A0.shape[-1] if A0 is not None else 0), k0,
+         ptr(a_scale), a_scale_rows, M, K, N, ptr(Wfrag), ptr(scale), ptr(shift), ptr(As), As.shape[-1], Ks, ptr(Wsfrag),
+         ptr(sscale), ptr(sshift), act, ptr(out), N, g[0], g[1], g[2], g[3], g[4], *_out2(out2, A), dtype_code(A.dtype),
+         stream_ptr())
+    return out
+
+
 def gemm_rs_fits(M, K, N):
     return _lib.load().tdeed_gemm_rs_fits(M, K, N) != 0
 

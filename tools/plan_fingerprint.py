@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 VARIANTS = [{}, {"TDEED_BNECK": "0"}, {"TDEED_C1_GCONV": "0"}, {"TDEED_GS_SRC_ORDER": "0"}, {"TDEED_SGP_GEMM": "0"},
-            {"TDEED_SGP_FUSED": "0"}, {"TDEED_SGP_F32_STREAM": "0"}, ["BNECK_BLEND=False"], ["BNECK_QTAIL=False"],
+            {"TDEED_SGP_FUSED": "0"}, {"TDEED_SGP_F32_STREAM": "0"}, ["BNECK_BLEND=False"], ["BNECK_QTAIL=False"], ["SC_IN_CONV3=False"],
             ["BNECK_ONE_LAUNCH=False", "C1_GCONV=False"]]
 GEOMETRIES = [("rny002_gsf", 2, 100, 8, 224), ("rny008_gsf", 3, 100, 16, 224), ("rny008_gsf", 3, 250, 4, 224),
               ("rny002_gsm", 2, 16, 2, 224), ("rny002", 2, 16, 2, 224), ("rny002_gsf", 2, 16, 2, 112), ("rny002_gsf", 2, 16, 2, 96)]
