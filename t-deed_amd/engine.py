@@ -9,6 +9,7 @@ compiler, no per-op host work in the steady state.
 Mirrors ``TDEEDModel.Impl.forward(x, inference=True)`` (/root/reference/model/model.py:105-149).
 """
 import os
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
@@ -93,10 +94,8 @@ def _pack_mlp(sd, pre, C, o, act_dtype, device):
         o.w2g = pack_mfma_frags(_np(sd[pre + ".mlp.2.weight"]).reshape(C, 4 * C), device, ks_mult=12)
 
 
-GS_SLICE = True
 # gate-shift-fuse slice left in source channel order, the module's interleave folded into conv1's weight columns
 GS_SRC_ORDER = os.environ.get("TDEED_GS_SRC_ORDER", "1") == "1"
-WS_NARROW_ONLY = True
 WS_WIDE_MIN_ROWS = 250000     # 0: never the sliced form
 RS_MIN_ROWS = int(os.environ.get("TDEED_RS_MIN_ROWS", "60000"))                # 0: never the register-stationary kernel
 
@@ -115,7 +114,7 @@ class DenseW:
         # The weight-stationary kernel was built for the narrow RegNetY-200MF layers (24 .. 152 channels), where it wins by
         # 20-35 %; on the 64- and 128-wide layers of the 800MF trunk the tiled kernel is the faster one
         # (tools/bench_ws_vs_gemm.py, us: 64x64 conv1 135 vs 152, conv3 190 vs 221; 128x128 conv3 101 vs 123; conv1 a tie)
-        if self.ws and WS_NARROW_ONLY and ((self.K == 64 and self.N == 64) or (gated and self.K >= 64 and self.K % 64 == 0)):
+        if self.ws and ((self.K == 64 and self.N == 64) or (gated and self.K >= 64 and self.K % 64 == 0)):
             self.ws = False
         self.w = pack_ws_weights(W, act_dtype, device) if self.ws else _dense(W, act_dtype, device)
         # wide layers over MANY rows (the 320-wide s3 layers of RegNetY-800MF at 3 * 10^5 rows): the sliced form reads the
@@ -208,13 +207,55 @@ C1_GCONV_MAX_CIN = 160
 SC_IN_CONV3 = True
 
 
-def _bneck_fused(bw, h, w, out_is_slice):
-    """True when the whole block runs as ONE launch (tdeed_bneck_fwd): bf16, stride 1, identity shortcut, a map small enough
-    for a workgroup's frames to stay in LDS (s3.b2-b4 and s4.b2-b7 of RegNetY-200MF), contiguous output."""
-    blk = bw.spec
-    return bool(BNECK_ONE_LAUNCH and getattr(bw, "fused", None) is not None and bw.se_mf is not None and blk.stride == 1
-                and not blk.has_downsample and blk.cin == blk.cout and not out_is_slice
-                and ops.bneck_fits(h, w, blk.cout, blk.se_rd))
+# The launch form of one bottleneck of a run (block_forms):
+# h, w, h2, w2    input and output map size
+# one_launch      the whole block is ONE launch (tdeed_bneck_fwd / tdeed_bneck_gs_fwd)
+# c1g             conv1 runs inside the grouped conv's launch (tdeed_c1_gconv_fwd): the y1 map never exists
+# site, Fp        the block has a gate-shift site; its fold padded to whole 8-channel groups (0 without a site)
+# slice_in        the gate-shift launches read the compact slice that the producer of the input wrote beside it
+# q_given         the launch in front of the block already wrote the site's tap maps
+# blend_in        the site's blend runs inside the one-launch bottleneck's frame load
+# qtail           the launch's tail writes the NEXT site's tap maps
+# slice_next      channels of the compact slice written for the next block's site (0: none)
+# sc_in_conv3     the shortcut conv is a second contraction inside conv3's launch (tdeed_gemm_ws_sc_fwd)
+BlockForm = namedtuple("BlockForm", "h w h2 w2 one_launch c1g site Fp slice_in q_given blend_in qtail slice_next sc_in_conv3")
+
+
+def block_forms(blocks, h, w, act_dtype, taps, last_out_is_slice):
+    """The launch form of every bottleneck of a run over an (h, w) input map: one BlockForm per block.  Pure: decided from the
+    block specs, from which packed forms the weights have, from the module switches (read now) and from the library's host
+    predicates; nothing is allocated, packed or written.  last_out_is_slice: the last block writes into a slice of a shared
+    buffer (no one-launch form: its output is not contiguous)."""
+    forms = []
+    for bi, bw in enumerate(blocks):
+        blk = bw.spec
+        nbw = blocks[bi + 1] if bi + 1 < len(blocks) else None
+        # bf16, stride 1, identity shortcut, a map small enough for a workgroup's frames to stay in LDS (s3.b2-b4 and s4.b2-b7
+        # of RegNetY-200MF), contiguous output
+        one_launch = bool(BNECK_ONE_LAUNCH and getattr(bw, "fused", None) is not None and bw.se_mf is not None
+                          and blk.stride == 1 and not blk.has_downsample and blk.cin == blk.cout
+                          and not (last_out_is_slice and nbw is None) and ops.bneck_fits(h, w, blk.cout, blk.se_rd))
+        # narrow block inputs, bf16 (block inputs up to 160 channels = 5 k-steps of conv1 fragments per wave; s4.b1 of
+        # RegNetY-200MF, 152 -> 368: 4072 vs 4002 clips/s with it on the same box)
+        c1g = bool(C1_GCONV and not one_launch and act_dtype == torch.bfloat16 and bw.w2frag is not None
+                   and blk.cin <= C1_GCONV_MAX_CIN and ops.c1_gconv_fits(h, w, blk.cin, blk.cout, blk.stride))
+        site = blk.gsf_fold > 0
+        Fp = (blk.gsf_fold + 7) // 8 * 8 if site else 0
+        blend_in = bool(site and one_launch and BNECK_BLEND and bw.gs_src and bw.gs_cw1 is not None and h * w >= 14
+                        and 2 * Fp <= blk.cin and ("_features." + blk.name + ".gs_out") not in taps)
+        # the gate-shift launches read only channels [0, Fp) of their input: every producer writes them once more as a compact
+        # slice beside its output (a slice of the channels-last map drags whole cache lines)
+        slice_next = (nbw.spec.gsf_fold + 7) // 8 * 8 if (nbw is not None and nbw.spec.gsf_fold) else 0
+        # (the tail's input slice is the block's own output rows)
+        qtail = bool(blend_in and BNECK_QTAIL and slice_next and getattr(nbw, "gs_wqf", None) is not None
+                     and ops.bneck_qtail_fits(h, w, blk.cout, nbw.spec.gsf_fold))
+        sc_in_conv3 = bool(SC_IN_CONV3 and blk.has_downsample and act_dtype == torch.bfloat16 and bw.w3.ws and bw.wd.ws
+                           and ops.gemm_ws_sc_fits(blk.cout, blk.cin, blk.cout, act_dtype))
+        h2, w2 = (h - 1) // blk.stride + 1, (w - 1) // blk.stride + 1
+        slice_in, q_given = bool(site and forms and forms[-1].slice_next == Fp), bool(forms and forms[-1].qtail)
+        forms.append(BlockForm(h, w, h2, w2, one_launch, c1g, site, Fp, slice_in, q_given, blend_in, qtail, slice_next, sc_in_conv3))
+        h, w = h2, w2
+    return forms
 
 
 class Step:
@@ -656,140 +697,132 @@ class ForwardEngine:
                           N * C * _esz(self.act_dtype) + N * pw.n_out * 4, 2 * N * C * pw.n_out))
         return cur
 
+    def _gs_site(self, pool, steps, keep, taps, B, bw, f, xg, q):
+        """Appends the gate-shift launch of a block's site over xg (the block's input, or its compact slice) and returns the
+        site's buffers.  q: the site's tap maps where the launch in front of the block wrote them (f.q_given).  Under
+        f.blend_in the launch leaves only the gates and the sums (the blend runs inside the bottleneck's launch); otherwise
+        gb["out"] is the blended slice that conv1 splices in."""
+        blk, T = bw.spec, self.pw.clip_len
+        N, F, Fp = B * T, blk.gsf_fold, f.Fp
+        M = N * f.h * f.w
+        gb = dict(gate=pool.take((N, f.h, f.w, 2), torch.float32),
+                  q=(q if f.q_given else pool.take((N, f.h, f.w, 6), torch.float32)),
+                  ysum=pool.take((N, F), torch.float32),
+                  xsum=pool.take((N, F), torch.float32))
+        if not f.blend_in:
+            gb["out"] = pool.take((M, Fp), self.act_dtype)
+            if bw.gs_cw1 is not None:
+                gb["fw"] = pool.take((B, F, T), torch.float32)
+        steps.append(Step(blk.name + ".gate_shift", "gate_shift", lambda: ops.gate_shift(
+            xg, B, T, F, Fp, bw.gs_scale, bw.gs_shift, bw.gs_wq, bw.gs_b3d, bw.gs_cw1, bw.gs_cb1,
+            bw.gs_cw2, bw.gs_cb2, bufs=gb, wqf=bw.gs_wqf, src_order=bw.gs_src, gates_only=f.blend_in, q_given=f.q_given),
+            M * ((1 if f.blend_in else 2) * F + (0 if f.blend_in else Fp)) * _esz(self.act_dtype) + M * 16, 2 * M * F * 27))
+        tap = "_features." + blk.name + ".gs_out"
+        if tap in taps:
+            if bw.gs_src:
+                raise ValueError("the gs_out tap is in module channel order: build the engine with TDEED_GS_SRC_ORDER=0")
+            keep[tap] = gb["out"]
+        return gb
+
+    def _one_launch(self, pool, steps, B, bw, f, x, xg, gb, nbw):
+        """Appends a bottleneck as ONE launch, conv1 (+ splice) -> conv2 -> SE -> conv3 + shortcut: only x and the output cross
+        HBM.  gb: the buffers of the block's site ({} without one), xg: what the site read, nbw: the next block's weights.
+        Returns the output, the next site's compact slice and the next site's tap maps (None where the form has none)."""
+        blk, T, dt = bw.spec, self.pw.clip_len, self.act_dtype
+        N, es = B * T, _esz(dt)
+        M = N * f.h * f.w
+        out = pool.take((N, f.h, f.w, blk.cout), dt)
+        xs_next = pool.take((N, f.h, f.w, f.slice_next), dt) if f.slice_next else None
+        o2 = xs_next.view(-1, f.slice_next) if f.slice_next else None
+        q_next = None
+        if f.blend_in:
+            qt = None
+            if f.qtail:
+                q_next = pool.take((N, f.h, f.w, 6), torch.float32)
+                qt = (nbw.gs_wpf, nbw.gs_bnq, nbw.spec.gsf_fold, q_next)
+            run = lambda: ops.bneck_gs(                                                                       # noqa: E731
+                x, xg, gb["gate"], gb["ysum"], gb["xsum"], bw.gs_cw1, bw.gs_cb1, bw.gs_cw2, bw.gs_cb2, T, blk.gsf_fold, f.Fp,
+                bw.fused.w1f, bw.s1, bw.h1, bw.fused.w2f, bw.s2, bw.h2, bw.se_mf.w1f, bw.se_b1, bw.se_mf.w2f, bw.se_b2,
+                blk.se_rd, bw.fused.w3f, bw.s3, bw.h3, out=out, out2=o2, w2_tap_major=bw.fused.w2_tap_major, qtail=qt)
+        else:
+            G = gb.get("out")
+            run = lambda: ops.bneck(                                                                          # noqa: E731
+                x, bw.fused.w1f, bw.s1, bw.h1, bw.fused.w2f, bw.s2, bw.h2, bw.se_mf.w1f, bw.se_b1, bw.se_mf.w2f, bw.se_b2,
+                blk.se_rd, bw.fused.w3f, bw.s3, bw.h3, G=G, out=out, out2=o2, w2_tap_major=bw.fused.w2_tap_major)
+        steps.append(Step(blk.name + ".bneck", "bneck", run,
+                          # x in, out; with the blend: each slice piece's temporal neighbour and the gate maps; the tail's Q
+                          (2 * M * blk.cout + (M * f.Fp if f.blend_in else 0)) * es + (8 * M if f.blend_in else 0)
+                          + (24 * M if f.qtail else 0)
+                          + (2 * blk.cout * blk.cout + blk.cout * blk.gw * 9) * es,
+                          2 * M * blk.cout * (2 * blk.cout + blk.gw * 9)))
+        return out, xs_next, q_next
+
+    def _chain(self, pool, steps, B, bw, f, x, y1, G, out, dead_site):
+        """Appends a bottleneck as a chain of launches: conv1 into y1 and the grouped conv, or both in one launch (f.c1g, no
+        y1); SE; the shortcut conv, unless conv3's launch computes it (f.sc_in_conv3); conv3.  G: the blended slice of the
+        block's site that conv1 splices in (None without a site), out: where the block writes instead of a pool buffer,
+        dead_site: the site's buffers.  Returns the output, the next site's compact slice and everything that dies here."""
+        blk, dt = bw.spec, self.act_dtype
+        N, es, s = B * self.pw.clip_len, _esz(dt), blk.stride
+        h, w, h2, w2 = f.h, f.w, f.h2, f.w2
+        M, M2 = N * h * w, N * h2 * w2
+        if y1 is not None:
+            splice = dict(A0=G, k0=f.Fp) if f.site else {}
+            steps.append(Step(blk.name + ".conv1", bw.w1.kern(M), lambda: bw.w1.run(
+                x, bw.s1, bw.h1, ops.ACT_RELU, out=y1, M=M, **splice), *gemm_cost(M, blk.cin, blk.cout, es)))
+        y2 = pool.take((N, h2, w2, blk.cout), dt)
+        parts = ops.gconv3x3_parts(h, w, blk.cout, s, dt) if bw.w2frag is not None else 1
+        pooled = pool.take((N, parts, blk.cout), torch.float32)
+        gate = pool.take((N, blk.cout), torch.float32)
+        if f.c1g:
+            if bw.c1g_w1f is None:
+                bw.c1g_w1f = pack_mfma_frags(bw.w1_raw, self.device, rows=16 * ops.c1_gconv_slab_tiles(h, w, blk.cout, s))
+            steps.append(Step(blk.name + ".conv1_conv2", "c1_gconv", lambda: ops.c1_gconv(
+                x, bw.c1g_w1f, bw.s1, bw.h1, bw.w2frag, bw.s2, bw.h2, blk.gw, s, blk.cout, G=G, out=y2, pooled=pooled),
+                (M * blk.cin + M2 * blk.cout) * es + blk.cout * (blk.cin + blk.gw * 9) * es,
+                2 * M * blk.cin * blk.cout + 2 * M2 * blk.cout * blk.gw * 9))
+        else:
+            steps.append(Step(blk.name + ".conv2", "gconv3x3", lambda: ops.gconv3x3(
+                y1, bw.w2, bw.s2, bw.h2, blk.gw, s, wfrag=bw.w2frag, out=y2, pooled=pooled),
+                (M + M2) * blk.cout * es + blk.cout * blk.gw * 9 * 4, 2 * M2 * blk.cout * blk.gw * 9))
+        sc, shortcut, sc_from = x, [], None
+        gather = (s, h, w, h2, w2) if s > 1 else None
+        if f.sc_in_conv3:
+            sc, sc_from = None, (x, gather)
+        elif blk.has_downsample:
+            sc = pool.take((N, h2, w2, blk.cout), dt)
+            shortcut = [Step(blk.name + ".downsample", bw.wd.kern(M2), lambda: bw.wd.run(
+                x, bw.sd, bw.hd, ops.ACT_NONE, gather=gather, out=sc, M=M2), *gemm_cost(M2, blk.cin, blk.cout, es))]
+        if out is None:
+            out = pool.take((N, h2, w2, blk.cout), dt)
+        xs_next = pool.take((N, h2, w2, f.slice_next), dt) if f.slice_next else None
+        se, conv3 = self._se_conv3(bw, N, h2, w2, y2, pooled, gate, sc, out, out2=xs_next, sc_from=sc_from)
+        steps += [se, *shortcut, conv3]                     # (the shortcut conv launches between the two)
+        # liveness: everything but `out` (and the next block's slice) dies here
+        return out, xs_next, ([y1] if y1 is not None else []) + [y2, pooled, gate] + dead_site + ([sc] if shortcut else [])
+
     def _blocks(self, pool, steps, keep, taps, B, x, h, w, blocks, x_kept, out_last=None):
-        """Appends the launches of a run of bottlenecks for B clips (N = B*T frames) to `steps`; x (N,h,w,Cin) is the input
-        map (owned by `pool` unless x_kept).  out_last: where the last block writes its output (a slice of a buffer shared
-        with the plan that continues the trunk) instead of a pool buffer.  Returns (x, h, w, x_kept)."""
-        pw, Wt = self.pw, self.pw.W
-        T = pw.clip_len
-        N = B * T
-        dt = self.act_dtype
-        es = _esz(dt)
-        xs = None           # compact copy of the first Fp channels of x, written by the producer of x (see below)
-        q_carry = None      # tap maps of this block's gate-shift site, made in the tail of the bottleneck launch in front of it
-        for bi, bw in enumerate(blocks):
-            blk = bw.spec
-            M = N * h * w
-            one_launch = _bneck_fused(bw, h, w, out_last is not None and bw is blocks[-1])
-            # conv1 inside the grouped conv's launch (the y1 map never exists): narrow block inputs, bf16
-            # (block inputs up to 160 channels = 5 k-steps of conv1 fragments per wave; s4.b1 of RegNetY-200MF, 152 -> 368: 4072 vs
-            # 4002 clips/s with it on the same box)
-            c1g = bool(C1_GCONV and not one_launch and dt == torch.bfloat16 and bw.w2frag is not None and blk.cin <= C1_GCONV_MAX_CIN
-                       and ops.c1_gconv_fits(h, w, blk.cin, blk.cout, blk.stride))
-            if c1g and bw.c1g_w1f is None:
-                rows_ = 16 * ops.c1_gconv_slab_tiles(h, w, blk.cout, blk.stride)
-                bw.c1g_w1f = pack_mfma_frags(bw.w1_raw, self.device, rows=rows_)
-            # conv1 (optionally behind the gate-shift splice)
-            y1 = None if (one_launch or c1g) else pool.take((N, h, w, blk.cout), dt)
-            if blk.gsf_fold:
-                F = blk.gsf_fold
-                Fp = (F + 7) // 8 * 8
-                # the gate-shift launches read only channels [0, Fp): from the compact slice the previous block's conv3 wrote
-                # beside its output when there is one (a slice of the channels-last map drags whole cache lines)
-                xg = xs if (xs is not None and xs.shape[-1] == Fp) else x
-                q_given = q_carry is not None
-                gb = dict(gate=pool.take((N, h, w, 2), torch.float32),
-                          q=(q_carry if q_given else pool.take((N, h, w, 6), torch.float32)),
-                          ysum=pool.take((N, F), torch.float32),
-                          xsum=pool.take((N, F), torch.float32))
-                q_carry = None
-                # the blend itself runs inside the one-launch bottleneck's frame load when it can (tdeed_bneck_gs_fwd)
-                blend_in = bool(one_launch and BNECK_BLEND and bw.gs_src and bw.gs_cw1 is not None and h * w >= 14
-                                and 2 * Fp <= blk.cin and ("_features." + blk.name + ".gs_out") not in taps)
-                if not blend_in:
-                    gb["out"] = pool.take((M, Fp), dt)
-                if bw.gs_cw1 is not None and not blend_in:
-                    gb["fw"] = pool.take((B, F, T), torch.float32)
-                steps.append(Step(blk.name + ".gate_shift", "gate_shift", lambda x=xg, bw=bw, gb=gb, F=F, Fp=Fp, go=blend_in, qg=q_given: ops.gate_shift(
-                    x, B, T, F, Fp, bw.gs_scale, bw.gs_shift, bw.gs_wq, bw.gs_b3d, bw.gs_cw1, bw.gs_cb1,
-                    bw.gs_cw2, bw.gs_cb2, bufs=gb, wqf=bw.gs_wqf, src_order=bw.gs_src, gates_only=go, q_given=qg),
-                    M * ((1 if blend_in else 2) * F + (0 if blend_in else Fp)) * es + M * 16, 2 * M * F * 27))
-                if not (one_launch or c1g):
-                    steps.append(Step(blk.name + ".conv1", bw.w1.kern(M), lambda x=x, bw=bw, gb=gb, Fp=Fp, y1=y1, M=M: bw.w1.run(
-                        x, bw.s1, bw.h1, ops.ACT_RELU, A0=gb["out"], k0=Fp, out=y1, M=M),
-                        *gemm_cost(M, blk.cin, blk.cout, es)))
-                if blk.name and ("_features." + blk.name + ".gs_out") in taps:
-                    if bw.gs_src:
-                        raise ValueError("the gs_out tap is in module channel order: build the engine with TDEED_GS_SRC_ORDER=0")
-                    keep["_features." + blk.name + ".gs_out"] = gb["out"]
-                gs_bufs = list(gb.values()) + ([xs] if xs is not None else [])
+        """Appends the launches of a run of bottlenecks for B clips (N = B*T frames) to `steps`, each in the form that
+        block_forms chose; x (N,h,w,Cin) is the input map (owned by `pool` unless x_kept).  out_last: where the last block
+        writes its output (a slice of a buffer shared with the plan that continues the trunk) instead of a pool buffer.
+        Returns (x, h, w, x_kept)."""
+        N, dt = B * self.pw.clip_len, self.act_dtype
+        xs = q = None       # the compact slice and the tap maps of the coming block's site, where the launch in front wrote them
+        for bi, f in enumerate(block_forms(blocks, h, w, dt, taps, out_last is not None)):
+            bw, last = blocks[bi], bi + 1 == len(blocks)
+            # (conv1's map is taken in front of the site's buffers: the pool is best-fit, so the order of takes decides which
+            # buffer a tensor lands in)
+            y1 = None if (f.one_launch or f.c1g) else pool.take((N, f.h, f.w, bw.spec.cout), dt)
+            xg = xs if f.slice_in else x
+            gb = self._gs_site(pool, steps, keep, taps, B, bw, f, xg, q) if f.site else {}
+            dead = list(gb.values()) + ([xs] if f.slice_in else [])
+            if f.one_launch:
+                out, xs, q = self._one_launch(pool, steps, B, bw, f, x, xg, gb, None if last else blocks[bi + 1])
             else:
-                blend_in = False
-                if not (one_launch or c1g):
-                    steps.append(Step(blk.name + ".conv1", bw.w1.kern(M), lambda x=x, bw=bw, y1=y1, M=M: bw.w1.run(
-                        x, bw.s1, bw.h1, ops.ACT_RELU, out=y1, M=M), *gemm_cost(M, blk.cin, blk.cout, es)))
-                gs_bufs = []
-            if one_launch:
-                # conv1 (+ splice) -> conv2 -> SE -> conv3 + shortcut in one launch: only x and the output cross HBM
-                out = pool.take((N, h, w, blk.cout), dt)
-                nxt = blocks[bi + 1].spec if bi + 1 < len(blocks) else None
-                xs_next = (pool.take((N, h, w, (nxt.gsf_fold + 7) // 8 * 8), dt)
-                           if (nxt is not None and nxt.gsf_fold and GS_SLICE) else None)
-                G = gb["out"] if (blk.gsf_fold and not blend_in) else None
-                o2 = xs_next.view(-1, xs_next.shape[-1]) if xs_next is not None else None
-                if blend_in:
-                    # the next site's tap maps in this launch's tail (its input slice is this block's output rows)
-                    qt = None
-                    nbw = blocks[bi + 1] if bi + 1 < len(blocks) else None
-                    if (BNECK_QTAIL and nbw is not None and nxt.gsf_fold and getattr(nbw, "gs_wqf", None) is not None
-                            and xs_next is not None and ops.bneck_qtail_fits(h, w, blk.cout, nxt.gsf_fold)):
-                        q_carry = pool.take((N, h, w, 6), torch.float32)
-                        qt = (nbw.gs_wpf, nbw.gs_bnq, nxt.gsf_fold, q_carry)
-                    run = lambda x=x, xg=xg, bw=bw, gb=gb, out=out, o2=o2, F=F, Fp=Fp, qt=qt: ops.bneck_gs(           # noqa: E731
-                        x, xg, gb["gate"], gb["ysum"], gb["xsum"], bw.gs_cw1, bw.gs_cb1, bw.gs_cw2, bw.gs_cb2, T, F, Fp,
-                        bw.fused.w1f, bw.s1, bw.h1, bw.fused.w2f, bw.s2, bw.h2, bw.se_mf.w1f, bw.se_b1, bw.se_mf.w2f, bw.se_b2,
-                        bw.spec.se_rd, bw.fused.w3f, bw.s3, bw.h3, out=out, out2=o2, w2_tap_major=bw.fused.w2_tap_major, qtail=qt)
-                else:
-                    run = lambda x=x, bw=bw, G=G, out=out, o2=o2: ops.bneck(                                    # noqa: E731
-                        x, bw.fused.w1f, bw.s1, bw.h1, bw.fused.w2f, bw.s2, bw.h2, bw.se_mf.w1f, bw.se_b1, bw.se_mf.w2f, bw.se_b2,
-                        bw.spec.se_rd, bw.fused.w3f, bw.s3, bw.h3, G=G, out=out, out2=o2, w2_tap_major=bw.fused.w2_tap_major)
-                steps.append(Step(blk.name + ".bneck", "bneck", run,
-                                  # x in, out; with the blend: each slice piece's temporal neighbour and the gate maps; the tail's Q
-                                  (2 * M * blk.cout + (M * Fp if blend_in else 0)) * es + (8 * M if blend_in else 0)
-                                  + (24 * M if (blend_in and qt is not None) else 0)
-                                  + (2 * blk.cout * blk.cout + blk.cout * blk.gw * 9) * es,
-                                  2 * M * blk.cout * (2 * blk.cout + blk.gw * 9)))
-                x_kept = self._block_done(pool, keep, taps, blk, gs_bufs, x, x_kept, out)
-                xs, x = xs_next, out
-                continue
-            s = blk.stride
-            h2, w2 = (h - 1) // s + 1, (w - 1) // s + 1
-            M2 = N * h2 * w2
-            y2 = pool.take((N, h2, w2, blk.cout), dt)
-            parts = ops.gconv3x3_parts(h, w, blk.cout, s, dt) if bw.w2frag is not None else 1
-            pooled = pool.take((N, parts, blk.cout), torch.float32)
-            gate = pool.take((N, blk.cout), torch.float32)
-            if c1g:
-                G = gb["out"] if blk.gsf_fold else None
-                steps.append(Step(blk.name + ".conv1_conv2", "c1_gconv", lambda x=x, bw=bw, blk=blk, G=G, y2=y2, pooled=pooled: ops.c1_gconv(
-                    x, bw.c1g_w1f, bw.s1, bw.h1, bw.w2frag, bw.s2, bw.h2, blk.gw, blk.stride, blk.cout, G=G, out=y2, pooled=pooled),
-                    (M * blk.cin + M2 * blk.cout) * es + blk.cout * (blk.cin + blk.gw * 9) * es,
-                    2 * M * blk.cin * blk.cout + 2 * M2 * blk.cout * blk.gw * 9))
-            else:
-                steps.append(Step(blk.name + ".conv2", "gconv3x3", lambda y1=y1, bw=bw, blk=blk, y2=y2, pooled=pooled: ops.gconv3x3(
-                    y1, bw.w2, bw.s2, bw.h2, blk.gw, blk.stride, wfrag=bw.w2frag, out=y2, pooled=pooled),
-                    (M + M2) * blk.cout * es + blk.cout * blk.gw * 9 * 4, 2 * M2 * blk.cout * blk.gw * 9))
-            sc, shortcut, sc_from = x, [], None
-            gather = (s, h, w, h2, w2) if s > 1 else None
-            if (SC_IN_CONV3 and blk.has_downsample and dt == torch.bfloat16 and bw.w3.ws and bw.wd.ws
-                    and ops.gemm_ws_sc_fits(blk.cout, blk.cin, blk.cout, dt)):
-                sc, sc_from = None, (x, gather)
-            elif blk.has_downsample:
-                sc = pool.take((N, h2, w2, blk.cout), dt)
-                shortcut = [Step(blk.name + ".downsample", bw.wd.kern(M2), lambda x=x, bw=bw, sc=sc, gather=gather, M2=M2: bw.wd.run(
-                    x, bw.sd, bw.hd, ops.ACT_NONE, gather=gather, out=sc, M=M2),
-                    *gemm_cost(M2, blk.cin, blk.cout, es))]
-            out = (out_last if (out_last is not None and bw is blocks[-1]) else pool.take((N, h2, w2, blk.cout), dt))
-            nxt = blocks[bi + 1].spec if bi + 1 < len(blocks) else None
-            xs_next = None
-            if nxt is not None and nxt.gsf_fold and GS_SLICE:
-                xs_next = pool.take((N, h2, w2, (nxt.gsf_fold + 7) // 8 * 8), dt)
-            se, conv3 = self._se_conv3(bw, N, h2, w2, y2, pooled, gate, sc, out, out2=xs_next, sc_from=sc_from)
-            steps += [se, *shortcut, conv3]                     # (the shortcut conv launches between the two)
-            # liveness: everything but `out` (and the next block's slice) dies here
-            dead = ([y1] if y1 is not None else []) + [y2, pooled, gate] + gs_bufs + ([sc] if shortcut else [])
-            x_kept = self._block_done(pool, keep, taps, blk, dead, x, x_kept, out)
-            xs, x, h, w = xs_next, out, h2, w2
+                out, xs, dead = self._chain(pool, steps, B, bw, f, x, y1, gb.get("out"), out_last if last else None, dead)
+                q = None
+            x_kept = self._block_done(pool, keep, taps, bw.spec, dead, x, x_kept, out)
+            x, h, w = out, f.h2, f.w2
         return x, h, w, x_kept
 
     def _build_tail(self, B, feat, head_out, trunk_in=None, start=None):

@@ -18,6 +18,15 @@ from tdeed_amd.regnet_spec import regnet_spec, sgp_up_size  # noqa: E402
 GOLD = os.path.join(ROOT, "tests", "golden")
 
 
+def plan_tool():
+    """tools/plan_fingerprint.py as a module: its patch_meta / meta_engine build launch plans on torch's "meta" device"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("plan_fingerprint", os.path.join(ROOT, "tools", "plan_fingerprint.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
 def load_golden(name):
     z = np.load(os.path.join(GOLD, name + ".npz"))
     meta = json.loads(str(z["meta"]))

@@ -4,11 +4,10 @@ the two-operand instances of gemm_ws_kernel that serve it do not spill."""
 import os
 import re
 
-import numpy as np
 import pytest
 import torch
 
-from helpers import ROOT  # noqa: F401  (puts the package on sys.path)
+from helpers import plan_tool, model_state
 from test_isa_guards import HIPCC, _resource_usage
 
 
@@ -21,21 +20,12 @@ def lib():
 
 
 def _cfg2_plan(monkeypatch, on):
-    from tdeed_amd import engine as E, packing, state_layout, synth
+    from tdeed_amd import engine as E
+    tool = plan_tool()
     monkeypatch.setattr(E, "SC_IN_CONV3", on)
-    monkeypatch.setattr(E, "new_stream", lambda *a, **k: None)
-    for mod in (E, packing):      # the folded-BN vectors of the front are read back on the host
-        monkeypatch.setattr(mod, "_np", (lambda real: lambda v: np.zeros(tuple(v.shape), np.float32)
-                                         if getattr(v, "is_meta", False) else real(v))(mod._np))
-    cfg = dict(feature_arch="rny002_gsf", clip_len=100, crop_dim=None, n_layers=2, sgp_ks=5, sgp_r=2, num_classes=3,
-               radi_displacement=2)
-    sd = synth.make_state(state_layout.model_state_shapes(cfg), 3)
-    eng = object.__new__(E.ForwardEngine)
-    eng.cfg, eng.crop_dim, eng.act_dtype, eng.device = cfg, None, torch.bfloat16, "meta"
-    eng.pw = E.PackedWeights(cfg, sd, torch.bfloat16, "meta")
-    eng.use_graph, eng.fuse_front, eng.n_split, eng.merge_tail, eng.join_at = False, True, 1, True, None
-    eng._plans = {}
-    return eng.plan(8, 224, 224)
+    tool.patch_meta(E, monkeypatch.setattr)
+    cfg = tool.config("rny002_gsf", 2, 100)
+    return tool.meta_engine(E, cfg, E.PackedWeights(cfg, model_state(cfg, 3), torch.bfloat16, "meta")).plan(8, 224, 224)
 
 
 def test_cfg2_plan_drops_two_launches_and_their_maps(lib, monkeypatch):

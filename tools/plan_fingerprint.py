@@ -1,6 +1,6 @@
 """Fingerprints of the forward engine's launch plans and packed weights, computed without a GPU.
 
-    python tools/plan_fingerprint.py [TREE] --plans | --weights [--set NAME=VALUE ...] | --variants
+    python tools/plan_fingerprint.py [TREE] --plans [--forms] | --weights [--set NAME=VALUE ...] | --variants
 
 Two trees (two commits) whose outputs are byte-identical build the same plans -- the same launches with the same costs over
 the same buffer assignment -- and pack the same weights.  What the fingerprint cannot see are the arguments captured in the
@@ -9,7 +9,8 @@ Step closures; the GPU suite checks those.
 --plans builds the plans on torch's "meta" device: the engine is made without its constructor, its weights are packed for
 "meta" (every GPU-only form is chosen as on the card, the *_fits / *_parts / *_form predicates are host functions of the built
 library), no Step is ever called.  --weights packs on the CPU.  --set flips a module attribute of `engine` after import;
---variants runs --plans once per plan switch, each in a process of its own (some switches are read at import).
+--variants runs --plans once per plan switch, each in a process of its own (some switches are read at import).  --forms adds,
+under each plan's line, one line per bottleneck of each of its runs with the launch form that engine.block_forms chose.
 """
 import argparse
 import hashlib
@@ -39,8 +40,26 @@ def config(arch, n_layers, T):
                 radi_displacement=2)
 
 
-def plans(E, synth, state_layout):
+def patch_meta(E, set_attr=setattr):
+    """What planning on "meta" replaces in the engine module (set_attr: setattr, or a pytest monkeypatch's)."""
+    set_attr(E, "new_stream", lambda *a, **k: None)
+    for mod in {E, sys.modules.get("tdeed_amd.packing", E)}:      # the folded-BN vectors of the front are read back on the host
+        set_attr(mod, "_np", (lambda real: lambda v: np.zeros(tuple(v.shape), np.float32)
+                              if getattr(v, "is_meta", False) else real(v))(mod._np))
+
+
+def meta_engine(E, cfg, pw, n_split=1, merge_tail=True, join_at=None, fuse_front=True):
+    """A ForwardEngine over the weights pw = E.PackedWeights(cfg, state, dtype, "meta"), made without its constructor."""
+    eng = object.__new__(E.ForwardEngine)
+    eng.cfg, eng.crop_dim, eng.pw, eng.act_dtype, eng.device = cfg, None, pw, pw.act_dtype, "meta"
+    eng.use_graph, eng.fuse_front, eng.n_split, eng.merge_tail, eng.join_at = False, fuse_front, n_split, merge_tail, join_at
+    eng._plans = {}
+    return eng
+
+
+def plans(E, synth, state_layout, show_forms=False):
     log = []                                                      # pool events of the plan being built
+    runs = []                                                     # (blocks, forms) of every run of bottlenecks in it
     take, give = E._Pool.take, E._Pool.give
     raw_index = lambda pool, t: next(i for i, b in enumerate(pool.all) if b is t._td_raw)   # noqa: E731
 
@@ -54,29 +73,34 @@ def plans(E, synth, state_layout):
         give(pool, t)
 
     E._Pool.take, E._Pool.give = logged_take, logged_give
-    E.new_stream = lambda *a, **k: None
-    for mod in {E, sys.modules.get("tdeed_amd.packing", E)}:      # the folded-BN vectors of the front are read back on the host
-        mod._np = (lambda real: lambda v: np.zeros(tuple(v.shape), np.float32) if getattr(v, "is_meta", False) else real(v))(mod._np)
+    patch_meta(E)
+    if show_forms:
+        block_forms = E.block_forms
+
+        def logged_forms(blocks, *a):
+            runs.append((blocks, block_forms(blocks, *a)))
+            return runs[-1][1]
+        E.block_forms = logged_forms
 
     weights = {}
 
-    def engine(arch, n_layers, T, dt, n_split=1, merge_tail=True, join_at=None, fuse_front=True):
+    def engine(arch, n_layers, T, dt, **opt):
         cfg = config(arch, n_layers, T)
         if (arch, n_layers, T, dt) not in weights:
             sd = synth.make_state(state_layout.model_state_shapes(cfg), 3)
             weights[arch, n_layers, T, dt] = E.PackedWeights(cfg, sd, dt, "meta")
-        eng = object.__new__(E.ForwardEngine)
-        eng.cfg, eng.crop_dim, eng.pw, eng.act_dtype, eng.device = cfg, None, weights[arch, n_layers, T, dt], dt, "meta"
-        eng.use_graph, eng.fuse_front, eng.n_split, eng.merge_tail, eng.join_at = False, fuse_front, n_split, merge_tail, join_at
-        eng._plans = {}
-        return eng
+        return meta_engine(E, cfg, weights[arch, n_layers, T, dt], **opt)
 
     def show(label, dt, build):
-        del log[:]
+        del log[:], runs[:]
         p = build()
         steps = [(s.name, s.kernel, s.bytes, s.flops) for s in p.steps]
         print(f"{label} {str(dt)[6:]}: steps {len(steps)} takes {sum(e[0] == 'take' for e in log)} "
               f"pool_bytes {p.pool_bytes} digest {digest((steps, log))}")
+        if show_forms:
+            for blocks, forms in runs:
+                for bw, f in zip(blocks, forms):
+                    print(f"    {bw.spec.name} " + " ".join(f"{k}={int(v)}" for k, v in f._asdict().items()))
 
     for (arch, n, T, B, S), opt, dt in itertools.product(GEOMETRIES, OPTIONS, DTYPES):
         show(f"{arch} n{n} T{T} B{B} {S}x{S} {opt}", dt, lambda: engine(arch, n, T, dt, **opt).plan(B, S, S))
@@ -150,6 +174,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("tree", nargs="?", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--plans", action="store_true")
+    ap.add_argument("--forms", action="store_true", help="with --plans: every bottleneck's launch form under its plan's line")
     ap.add_argument("--weights", action="store_true")
     ap.add_argument("--variants", action="store_true", help="--plans once per plan switch, each in its own process")
     ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE", help="engine attribute set after import")
@@ -169,7 +194,7 @@ def main():
         name, value = s.split("=")
         setattr(E, name, {"True": True, "False": False}[value])
     if a.plans:
-        plans(E, synth, state_layout)
+        plans(E, synth, state_layout, a.forms)
     if a.weights:
         weights(E, synth, state_layout, repack, regnet_spec)
 
