@@ -441,6 +441,43 @@ int tdeed_nms_track(const float* mean, int L, int K1, float hr_threshold, double
                     int n_windows, const int* first_frame, void* workspace, unsigned char* emitted, double* kept_score,
                     int* out_frame, int* out_class, unsigned char* out_class_u8, double* out_score, int* out_count, int* rounds, void* stream);
 
+/* ---- a group of videos scored as one packed job (video.hip, spot.hip) ------------------------------------------------
+ * The videos' frames sit one after the other in one buffer of L_total frames, their clips one after the other (video-major)
+ * in one clip list; evalutil.group_clip_table builds the tables, all DEVICE int32: seg_off[nv+1] first packed frame of
+ * every video (seg_off[nv] = L_total), clip_off[nv+1] first clip of every video, starts[n] video-local first frame of
+ * every clip, clip_base[n] / clip_len_v[n] = seg_off / length of the clip's video.  nv <= 65535.  max_len: the longest
+ * video of the group (sizes grids, workgroups and LDS; a video longer than max_len is left out).  A table entry that
+ * points outside the buffers it indexes is skipped, never followed. */
+/* clips_out[b][t] = video[clip_base[b] + starts[b] + t] when 0 <= starts[b] + t < clip_len_v[b], else a zero frame: the
+ * window is cut at the ends of the clip's OWN video.  Forms and limits of tdeed_clip_gather_u8. */
+int tdeed_clip_gather_seg_u8(const uint8_t* video, int L_total, long frame_bytes, const int* starts, const int* clip_base,
+                             const int* clip_len_v, int B, int T, uint8_t* clips_out, void* stream);
+/* tdeed_stitch_scores per video: one thread per packed frame walks only the clips clip_off[v] .. clip_off[v+1]-1 of its
+ * video, in the order given, views inner -- per frame the additions of tdeed_stitch_scores on that video alone (same bits).
+ * track_sum [L_total][K1], support [L_total] (accumulated onto), mean_out [L_total][K1] or NULL. */
+int tdeed_stitch_scores_seg(const float* clip_scores, int V, int n, int T, int K1, const int* starts, const int* seg_off,
+                            const int* clip_off, int nv, int count_all, int L_total, float* track_sum, int* support,
+                            float* mean_out, void* stream);
+/* tdeed_frame_events per video: pred / pred_u8 / pred_score per packed frame; first_frame int32 [nv][K1] in video-local
+ * frames (the caller fills row v with the video's length), count int32 [nv][K1] (the caller zeroes it). */
+int tdeed_frame_events_seg(const float* mean, const int* seg_off, int nv, int L_total, int max_len, int K1, float hr_threshold,
+                           int* pred, unsigned char* pred_u8, float* pred_score, int* first_frame, int* count, void* stream);
+/* bytes of workspace tdeed_nms_track_seg needs (0: max_len frames of suppression state fit the LDS of a workgroup) */
+long tdeed_nms_track_seg_workspace(int L_total, int max_len, int K1);
+/* threads of the suppression / compaction workgroups tdeed_nms_track_seg launches for this max_len */
+int tdeed_nms_track_seg_threads(int max_len);
+/* tdeed_nms_track per video, one workgroup per (class, video), same rule and arithmetic, video-local frames / windows /
+ * ranks from first_frame [nv][K1] (tdeed_frame_events_seg).  emitted uint8 [K1][L_total], kept_score double [K1][L_total],
+ * st_frame / st_class_u8 / st_score (L_total * (K1-1) entries each) and st_count int32[nv] are scratch.  Output: the kept
+ * events of video v, in tdeed_nms_track's order with video-local frames, are entries event_off[v] .. event_off[v+1]-1 of
+ * out_frame (int32) / out_class_u8 / out_score (double), each with room for L_total * (K1-1) entries: the videos' lists
+ * follow each other densely in video order, event_off int32[nv+1].  rounds int32 [nv][K1].  Deterministic. */
+int tdeed_nms_track_seg(const float* mean, const int* seg_off, int nv, int L_total, int max_len, int K1, float hr_threshold,
+                        double threshold, int soft, const int* windows, int n_windows, const int* first_frame, void* workspace,
+                        unsigned char* emitted, double* kept_score, int* st_frame, unsigned char* st_class_u8, double* st_score,
+                        int* st_count, int* out_frame, unsigned char* out_class_u8, double* out_score, int* event_off, int* rounds,
+                        void* stream);
+
 /* ---- backward of the SGP encoder-decoder (training path; sgp_bwd.hip) ------------------------------------------
  * Activations and activation gradients share the forward dtype; parameter gradients are fp32.  Every parameter
  * gradient is produced as caller-owned per-workgroup partials (`part*`) folded in a fixed order: no float atomics,

@@ -5,13 +5,29 @@
 // clips_out[b][t] = video[starts[b] + t], a zero frame where the window hangs over either end of the video (the padding
 // of the reference's FrameReaderVideo.load_frames(pad=True)).  blockIdx.y = frame slot b*T + t: one 32-bit division per
 // workgroup, none per element.  A workgroup walks its share of the frame in 16-byte chunks.
-__global__ __launch_bounds__(256) void clip_gather_v16_kernel(const u32x4* __restrict__ video, int L, long chunks,
-                                                              const int* __restrict__ starts, int T,
-                                                              u32x4* __restrict__ out) {
-  const int slot = blockIdx.y;
+// SEG: `video` packs several videos one after the other; clip b belongs to the video whose first packed frame is
+// clip_base[b] and whose length is clip_len_v[b], starts[b] is local to it, and the window is cut at THAT video's ends (a
+// window hanging over the end of video v must not read the first frames of video v+1).  L is then the packed total, and a
+// table entry that points outside it yields a zero frame.
+template <bool SEG>
+__device__ __forceinline__ long clip_gather_source(int L, const int* __restrict__ starts, const int* __restrict__ clip_base,
+                                                   const int* __restrict__ clip_len_v, int T, int slot) {
   const int b = slot / T;
   const long f = (long)starts[b] + (slot - b * T);
-  const bool real = f >= 0 && f < L;
+  if (!SEG) return f >= 0 && f < L ? f : -1;
+  const long base = clip_base[b];
+  const long p = base + f;
+  return f >= 0 && f < clip_len_v[b] && base >= 0 && p < L ? p : -1;
+}
+
+template <bool SEG>
+__global__ __launch_bounds__(256) void clip_gather_v16_kernel(const u32x4* __restrict__ video, int L, long chunks,
+                                                              const int* __restrict__ starts, const int* __restrict__ clip_base,
+                                                              const int* __restrict__ clip_len_v, int T,
+                                                              u32x4* __restrict__ out) {
+  const int slot = blockIdx.y;
+  const long f = clip_gather_source<SEG>(L, starts, clip_base, clip_len_v, T, slot);
+  const bool real = f >= 0;
   const u32x4* src = video + (real ? f : 0) * chunks;
   u32x4* dst = out + (long)slot * chunks;
   const u32x4 zero = {0u, 0u, 0u, 0u};
@@ -20,17 +36,37 @@ __global__ __launch_bounds__(256) void clip_gather_v16_kernel(const u32x4* __res
 }
 
 // frame sizes that are no multiple of 16 bytes (or unaligned buffers)
+template <bool SEG>
 __global__ __launch_bounds__(256) void clip_gather_u8_kernel(const uint8_t* __restrict__ video, int L, long frame_bytes,
-                                                             const int* __restrict__ starts, int T,
+                                                             const int* __restrict__ starts, const int* __restrict__ clip_base,
+                                                             const int* __restrict__ clip_len_v, int T,
                                                              uint8_t* __restrict__ out) {
   const int slot = blockIdx.y;
-  const int b = slot / T;
-  const long f = (long)starts[b] + (slot - b * T);
-  const bool real = f >= 0 && f < L;
+  const long f = clip_gather_source<SEG>(L, starts, clip_base, clip_len_v, T, slot);
+  const bool real = f >= 0;
   const uint8_t* src = video + (real ? f : 0) * frame_bytes;
   uint8_t* dst = out + (long)slot * frame_bytes;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < frame_bytes; i += (long)gridDim.x * 256)
     dst[i] = real ? src[i] : (uint8_t)0;
+}
+
+template <bool SEG>
+static int clip_gather_launch(const uint8_t* video, int L, long frame_bytes, const int* starts, const int* clip_base,
+                              const int* clip_len_v, int B, int T, uint8_t* clips_out, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const bool v16 = frame_bytes % 16 == 0 && (((uintptr_t)video | (uintptr_t)clips_out) & 15) == 0;
+  if (v16) {
+    const long chunks = frame_bytes / 16;
+    const int gx = (int)(cdiv(chunks, 256 * 4) < 64 ? cdiv(chunks, 256 * 4) : 64);     // 4+ chunks per thread
+    hipLaunchKernelGGL(clip_gather_v16_kernel<SEG>, dim3(gx, B * T), dim3(256), 0, st, (const u32x4*)video, L, chunks, starts,
+                       clip_base, clip_len_v, T, (u32x4*)clips_out);
+  } else {
+    const int gx = (int)(cdiv(frame_bytes, 256 * 4) < 64 ? cdiv(frame_bytes, 256 * 4) : 64);
+    hipLaunchKernelGGL(clip_gather_u8_kernel<SEG>, dim3(gx, B * T), dim3(256), 0, st, video, L, frame_bytes, starts, clip_base,
+                       clip_len_v, T, clips_out);
+  }
+  TD_LAUNCH_CHECK("clip_gather");
+  return TDEED_OK;
 }
 
 extern "C" int tdeed_clip_gather_u8(const uint8_t* video, int L, long frame_bytes, const int* starts, int B, int T,
@@ -38,34 +74,28 @@ extern "C" int tdeed_clip_gather_u8(const uint8_t* video, int L, long frame_byte
   TD_CHECK(video && starts && clips_out, "clip_gather: null pointer");
   TD_CHECK(L > 0 && frame_bytes > 0 && B > 0 && T > 0, "clip_gather: bad sizes");
   TD_CHECK((long)B * T <= 65535, "clip_gather: B*T=%ld frame slots exceed the grid's 65535", (long)B * T);
-  hipStream_t st = (hipStream_t)stream;
-  const bool v16 = frame_bytes % 16 == 0 && (((uintptr_t)video | (uintptr_t)clips_out) & 15) == 0;
-  if (v16) {
-    const long chunks = frame_bytes / 16;
-    const int gx = (int)(cdiv(chunks, 256 * 4) < 64 ? cdiv(chunks, 256 * 4) : 64);     // 4+ chunks per thread
-    hipLaunchKernelGGL(clip_gather_v16_kernel, dim3(gx, B * T), dim3(256), 0, st, (const u32x4*)video, L, chunks, starts, T,
-                       (u32x4*)clips_out);
-  } else {
-    const int gx = (int)(cdiv(frame_bytes, 256 * 4) < 64 ? cdiv(frame_bytes, 256 * 4) : 64);
-    hipLaunchKernelGGL(clip_gather_u8_kernel, dim3(gx, B * T), dim3(256), 0, st, video, L, frame_bytes, starts, T, clips_out);
-  }
-  TD_LAUNCH_CHECK("clip_gather");
-  return TDEED_OK;
+  return clip_gather_launch<false>(video, L, frame_bytes, starts, nullptr, nullptr, B, T, clips_out, stream);
+}
+
+extern "C" int tdeed_clip_gather_seg_u8(const uint8_t* video, int L_total, long frame_bytes, const int* starts,
+                                        const int* clip_base, const int* clip_len_v, int B, int T, uint8_t* clips_out,
+                                        void* stream) {
+  TD_CHECK(video && starts && clip_base && clip_len_v && clips_out, "clip_gather_seg: null pointer");
+  TD_CHECK(L_total > 0 && frame_bytes > 0 && B > 0 && T > 0, "clip_gather_seg: bad sizes");
+  TD_CHECK((long)B * T <= 65535, "clip_gather_seg: B*T=%ld frame slots exceed the grid's 65535", (long)B * T);
+  return clip_gather_launch<true>(video, L_total, frame_bytes, starts, clip_base, clip_len_v, B, T, clips_out, stream);
 }
 
 // =========================================================================== score stitching
 // Device twin of evalutil.ScoreStitcher (add / add_views / normalised).  One thread owns one video frame: it walks the
 // clips in the order given and, per covering clip, adds the views one after the other -- the same sequence of fp32
 // additions per frame as the host's clip-major loop, so sums, support and mean carry the same bits.  No atomics.
-__global__ __launch_bounds__(256) void stitch_scores_kernel(const float* __restrict__ clip_scores, int V, int n, int T, int K1,
-                                                            const int* __restrict__ starts, int count_all, int L,
-                                                            float* __restrict__ track_sum, int* __restrict__ support,
-                                                            float* __restrict__ mean_out) {
-  const int f = blockIdx.x * 256 + threadIdx.x;
-  if (f >= L) return;
-  float* s = track_sum + (long)f * K1;
-  int sup = support[f];
-  for (int i = 0; i < n; ++i) {
+// f: the frame inside its video; s / support / mean_out: the frame's own row; the clips i0 .. i1 - 1 of the n are walked.
+__device__ __forceinline__ void stitch_frame(const float* __restrict__ clip_scores, int V, int n, int T, int K1,
+                                             const int* __restrict__ starts, int i0, int i1, int count_all, int f,
+                                             float* __restrict__ s, int* __restrict__ support, float* __restrict__ mean_out) {
+  int sup = *support;
+  for (int i = i0; i < i1; ++i) {
     const long t = (long)f - starts[i];
     if (t < 0 || t >= T) continue;
     for (int v = 0; v < V; ++v) {
@@ -79,11 +109,45 @@ __global__ __launch_bounds__(256) void stitch_scores_kernel(const float* __restr
       sup += (count_all || nz) ? 1 : 0;
     }
   }
-  support[f] = sup;
+  *support = sup;
   if (mean_out) {
     const float d = (float)(sup > 1 ? sup : 1);
-    for (int k = 0; k < K1; ++k) mean_out[(long)f * K1 + k] = s[k] / d;     // IEEE division (no fast-math in this build)
+    for (int k = 0; k < K1; ++k) mean_out[k] = s[k] / d;     // IEEE division (no fast-math in this build)
   }
+}
+
+__global__ __launch_bounds__(256) void stitch_scores_kernel(const float* __restrict__ clip_scores, int V, int n, int T, int K1,
+                                                            const int* __restrict__ starts, int count_all, int L,
+                                                            float* __restrict__ track_sum, int* __restrict__ support,
+                                                            float* __restrict__ mean_out) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  if (f >= L) return;
+  stitch_frame(clip_scores, V, n, T, K1, starts, 0, n, count_all, f, track_sum + (long)f * K1, support + f,
+               mean_out ? mean_out + (long)f * K1 : nullptr);
+}
+
+// Several videos packed one after the other (evalutil.group_clip_table): one thread per packed frame p.  It finds its video
+// v (seg_off[v] <= p < seg_off[v+1], a binary search over the nv + 1 offsets) and walks only that video's clips
+// clip_off[v] .. clip_off[v+1] - 1, in the order given: per frame the additions of the one-video kernel on that video alone.
+__global__ __launch_bounds__(256) void stitch_scores_seg_kernel(const float* __restrict__ clip_scores, int V, int n, int T, int K1,
+                                                                const int* __restrict__ starts, const int* __restrict__ seg_off,
+                                                                const int* __restrict__ clip_off, int nv, int count_all, int L,
+                                                                float* __restrict__ track_sum, int* __restrict__ support,
+                                                                float* __restrict__ mean_out) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= L) return;
+  int lo = 0, hi = nv;                                         // seg_off[lo] <= p < seg_off[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (seg_off[mid] <= p) lo = mid; else hi = mid;
+  }
+  const int f = p - seg_off[lo];
+  int i0 = clip_off[lo], i1 = clip_off[lo + 1];
+  i0 = i0 > 0 ? i0 : 0;                                        // a table entry outside the clip list reads nothing
+  i1 = i1 < n ? i1 : n;
+  TD_DEV_ASSERT(f >= 0 && p < seg_off[lo + 1]);
+  stitch_frame(clip_scores, V, n, T, K1, starts, i0, i1, count_all, f, track_sum + (long)p * K1, support + p,
+               mean_out ? mean_out + (long)p * K1 : nullptr);
 }
 
 extern "C" int tdeed_stitch_scores(const float* clip_scores, int V, int n, int T, int K1, const int* starts, int count_all,
@@ -94,5 +158,18 @@ extern "C" int tdeed_stitch_scores(const float* clip_scores, int V, int n, int T
   hipLaunchKernelGGL(stitch_scores_kernel, dim3(cdiv(L, 256)), dim3(256), 0, (hipStream_t)stream, clip_scores, V, n, T, K1,
                      starts, count_all, L, track_sum, support, mean_out);
   TD_LAUNCH_CHECK("stitch_scores");
+  return TDEED_OK;
+}
+
+extern "C" int tdeed_stitch_scores_seg(const float* clip_scores, int V, int n, int T, int K1, const int* starts, const int* seg_off,
+                                       const int* clip_off, int nv, int count_all, int L_total, float* track_sum, int* support,
+                                       float* mean_out, void* stream) {
+  TD_CHECK(clip_scores && starts && seg_off && clip_off && track_sum && support, "stitch_scores_seg: null pointer");
+  TD_CHECK(V > 0 && n > 0 && T > 0 && K1 > 0 && L_total > 0 && nv > 0, "stitch_scores_seg: bad sizes");
+  TD_CHECK(nv <= 65535, "stitch_scores_seg: %d videos in one group, at most 65535", nv);
+  TD_CHECK(count_all == 0 || count_all == 1, "stitch_scores_seg: count_all must be 0 or 1");
+  hipLaunchKernelGGL(stitch_scores_seg_kernel, dim3(cdiv(L_total, 256)), dim3(256), 0, (hipStream_t)stream, clip_scores, V, n, T,
+                     K1, starts, seg_off, clip_off, nv, count_all, L_total, track_sum, support, mean_out);
+  TD_LAUNCH_CHECK("stitch_scores_seg");
   return TDEED_OK;
 }

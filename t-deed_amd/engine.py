@@ -1050,12 +1050,17 @@ class ForwardEngine:
         self.run_plan(plan)
         return plan.head_out, plan
 
-    def forward_from_video(self, video_u8, starts_dev, augment_inference=False, slot=0):
+    def forward_from_video(self, video_u8, starts_dev, augment_inference=False, slot=0, clip_base=None, clip_len_v=None):
         """forward() over clip windows of a frame buffer that is resident on the device: video_u8 uint8 (L,3,H,W), starts_dev
         int32 (B,) on the device (first frame of each clip; windows that hang over either end are zero padded like the
         evaluation reader's).  The windows are gathered straight into the plan's input buffers (ops.clip_gather, one launch
         per sub-batch) in place of set_frames' copy of a materialised batch; same plan keys and graphs as forward(), so the
-        result carries the same bits as forward() on the materialised windows."""
+        result carries the same bits as forward() on the materialised windows.
+        clip_base / clip_len_v (int32 (B,) on the device, both or neither): video_u8 packs several videos, clip b belongs to
+        the one that starts at packed frame clip_base[b] and has clip_len_v[b] frames, starts_dev is local to it and the
+        window is padded at that video's ends (ops.clip_gather_seg)."""
+        if (clip_base is None) != (clip_len_v is None):
+            raise ValueError("clip_base and clip_len_v go together")
         if video_u8.dtype != torch.uint8 or video_u8.dim() != 4 or not video_u8.is_cuda:
             raise TypeError("video frames must be a uint8 (L,3,H,W) tensor on the device")
         if starts_dev.dtype != torch.int32 or starts_dev.dim() != 1 or not starts_dev.is_cuda:
@@ -1065,7 +1070,11 @@ class ForwardEngine:
         plan = self.plan(B, H, W, augment_inference, (), slot=slot)
         Bs = B // len(plan.subs)
         for i, sb in enumerate(plan.subs):
-            ops.clip_gather(video_u8, starts_dev[i * Bs:(i + 1) * Bs], self.pw.clip_len, sb.frames)
+            part = slice(i * Bs, (i + 1) * Bs)
+            if clip_base is None:
+                ops.clip_gather(video_u8, starts_dev[part], self.pw.clip_len, sb.frames)
+            else:
+                ops.clip_gather_seg(video_u8, starts_dev[part], clip_base[part], clip_len_v[part], self.pw.clip_len, sb.frames)
         self.run_plan(plan)
         return plan.head_out, plan
 

@@ -109,16 +109,124 @@ def stitch_clip_scores(scores, starts, L, flip_scores=None):
     return sums, support
 
 
-def stitch_videos(model, videos, n_cols, augment=False, batch_size=8, overlap_len=None, decode_ahead=1):
+def group_clip_table(lengths, clip_len, overlap_len, pad_len=5, clip_starts=None):
+    """The tables of a group of videos scored as one packed job (`TDEEDModel.predict_video_group`): the videos' frames sit
+    one after the other in one buffer, their clips one after the other in one list -- video-major, within a video in the
+    order given; that order is what the gather, the batches and the stitch kernel walk.  lengths: frames per video;
+    clip_starts: optional list (one entry per video) of each video's first frames, default `video_clip_starts` per video.
+    Returns int32 arrays (seg_off (nv+1,): first packed frame of every video, the total last; clip_off (nv+1,): first clip
+    of every video; starts (n,): video-local first frame of every clip; clip_base (n,) / clip_len_v (n,): seg_off and
+    length of the clip's video).  Raises ValueError for a video without frames or without clips."""
+    lengths = [int(x) for x in lengths]
+    if clip_starts is not None and len(clip_starts) != len(lengths):
+        raise ValueError(f"group_clip_table: clip starts for {len(clip_starts)} videos, {len(lengths)} lengths")
+    seg_off, clip_off, starts, base, len_v = [0], [0], [], [], []
+    for v, L in enumerate(lengths):
+        if L <= 0:
+            raise ValueError(f"group_clip_table: video {v} is empty")
+        mine = video_clip_starts(L, clip_len, overlap_len, pad_len=pad_len) if clip_starts is None else \
+            [int(x) for x in clip_starts[v]]
+        if not mine:
+            raise ValueError(f"group_clip_table: video {v} has no clips")
+        starts += mine
+        base += [seg_off[-1]] * len(mine)
+        len_v += [L] * len(mine)
+        seg_off.append(seg_off[-1] + L)
+        clip_off.append(clip_off[-1] + len(mine))
+    if seg_off[-1] >= 1 << 31:
+        raise ValueError(f"group_clip_table: {seg_off[-1]} frames in one group do not fit int32")
+    return tuple(np.asarray(a, np.int32) for a in (seg_off, clip_off, starts, base, len_v))
+
+
+def video_groups(lengths, frame_shapes, group_videos, max_resident_bytes):
+    """Split consecutive videos, in the order given, into groups for `predict_video_group`: lists of indices.  A group closes
+    when it holds `group_videos` videos, when the next video would push the frames of the group over `max_resident_bytes`,
+    or when the frame geometry (3,H,W) changes.  A single video over the budget raises the ValueError predict_video
+    raises for it."""
+    if int(group_videos) < 1:
+        raise ValueError("video_groups: group_videos must be positive")
+    groups, cur, cur_bytes, cur_shape = [], [], 0, None
+    for j, (L, shape) in enumerate(zip(lengths, frame_shapes)):
+        shape = tuple(int(x) for x in shape)
+        need = int(L) * int(np.prod(shape))
+        if need > max_resident_bytes:
+            raise ValueError(f"predict_video: the video needs {need} bytes on the device, more than max_resident_bytes="
+                             f"{max_resident_bytes} (a ring buffer for longer videos is not implemented)")
+        if cur and (len(cur) >= int(group_videos) or cur_bytes + need > max_resident_bytes or shape != cur_shape):
+            groups.append(cur)
+            cur, cur_bytes = [], 0
+        cur.append(j)
+        cur_bytes += need
+        cur_shape = shape
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def stitch_clip_scores_seg(scores, starts, seg_off, clip_off, flip_scores=None):
+    """numpy twin of the segmented stitch kernel (ops.stitch_scores_seg): `stitch_clip_scores` per video of a group on the
+    clips clip_off[v]:clip_off[v+1] of the group's clip list.  Returns (sums (sum L,K+1), support (sum L,)) over the packed
+    frames."""
+    scores = np.asarray(scores, np.float32)
+    sums = np.zeros((int(seg_off[-1]), scores.shape[2]), np.float32)
+    support = np.zeros(int(seg_off[-1]), np.int32)
+    for v in range(len(seg_off) - 1):
+        a, b, lo, hi = int(seg_off[v]), int(seg_off[v + 1]), int(clip_off[v]), int(clip_off[v + 1])
+        sums[a:b], support[a:b] = stitch_clip_scores(scores[lo:hi], starts[lo:hi], b - a,
+                                                     None if flip_scores is None else np.asarray(flip_scores)[lo:hi])
+    return sums, support
+
+
+def _decoded_groups(videos, group_videos, max_resident_bytes):
+    """The sources of `videos` (name, length, fps, frames | callable) in groups: batches of `group_videos` consecutive
+    videos are materialised -- callables on a worker thread, one batch ahead of the consumer -- and each batch is then
+    split by `video_groups` (budget, geometry).  Yields lists of (name, length, fps, frames)."""
+    from concurrent.futures import ThreadPoolExecutor
+    import torch
+    gv = int(group_videos)
+    batches = [videos[lo:lo + gv] for lo in range(0, len(videos), gv)]
+
+    def decode(batch):
+        return [src() if callable(src) else src for _, _, _, src in batch]
+
+    with ThreadPoolExecutor(max_workers=1, thread_name_prefix="tdeed-video") as ex:
+        fut = ex.submit(decode, batches[0]) if batches else None
+        for bi, batch in enumerate(batches):
+            frames = fut.result()
+            fut = ex.submit(decode, batches[bi + 1]) if bi + 1 < len(batches) else None
+            frames = [f if isinstance(f, torch.Tensor) else torch.as_tensor(np.asarray(f)) for f in frames]
+            for (name, length, _, _), f in zip(batch, frames):
+                if int(f.shape[0]) != int(length):
+                    raise ValueError(f"video {name}: {int(f.shape[0])} frames delivered, {int(length)} announced")
+            for idx in video_groups([b[1] for b in batch], [tuple(f.shape[1:]) for f in frames], gv, max_resident_bytes):
+                yield [(batch[j][0], batch[j][1], batch[j][2], frames[j]) for j in idx]
+
+
+def stitch_videos(model, videos, n_cols, augment=False, batch_size=8, overlap_len=None, decode_ahead=1, group_videos=1,
+                  max_resident_bytes=16 << 30):
     """Whole-video counterpart of `stitch_predictions`: `videos` yields (name, length, fps, frames) with frames a uint8
     (length,3,H,W) tensor of the sampled frames or a callable returning one (e.g. a `feeder.load_video` closure); every
     video goes through `model.predict_video` once and its (sums, support) become the video's track of the returned
     ScoreStitcher, so `normalised()`, `frame_events`, both NMS functions and `mean_average_precisions` work on it
     unchanged.  Callables run up to `decode_ahead` videos ahead on a worker thread: decoding video v+1 overlaps scoring
-    video v."""
+    video v.
+    group_videos > 1: up to that many consecutive videos (as far as `max_resident_bytes` and one frame geometry allow,
+    `video_groups`) go through `model.predict_video_group` as one packed job whose batches are cut across the videos; the
+    callables of the next `group_videos` videos are decoded on the worker thread meanwhile."""
     from concurrent.futures import ThreadPoolExecutor
     videos = list(videos)
     st = ScoreStitcher([(v, n, f) for v, n, f, _ in videos], n_cols)
+    if int(group_videos) > 1:
+        for group in _decoded_groups(videos, group_videos, max_resident_bytes):
+            out = model.predict_video_group([g[3] for g in group], overlap_len=overlap_len, batch_size=batch_size,
+                                            augment=augment, max_resident_bytes=max_resident_bytes)
+            for (name, _, _, _), (sums, support) in zip(group, out):
+                if sums.shape[1] != n_cols:
+                    raise ValueError(f"video {name}: the model scores {sums.shape[1]} columns, the stitcher holds {n_cols}")
+                track, sup = st.tracks[name]
+                track[...] = sums
+                sup[...] = support
+        return st
     ahead = max(int(decode_ahead), 0)
     with ThreadPoolExecutor(max_workers=1, thread_name_prefix="tdeed-video") as ex:
         pending = {}
@@ -321,37 +429,45 @@ def event_dicts(frames, classes_idx, scores, inv):
 
 
 def spot_videos(model, videos, classes, suppress, high_recall_score_threshold=0.01, augment=False, batch_size=8,
-                overlap_len=None, decode_ahead=1):
+                overlap_len=None, decode_ahead=1, group_videos=1, max_resident_bytes=16 << 30):
     """Whole-video counterpart of `stitch_videos` + `frame_events` + the two NMS functions with the tail on the device:
     `videos` as in `stitch_videos`; every video goes through `model.spot_video` once.  suppress: entries (kind, window,
     threshold) with kind "nms" | "snms".  Returns (pred_events, [one list of video records per suppress entry],
     {video: pred (L,) int32}), videos in sorted order, records as `frame_events` / `non_maximum_suppression` /
     `soft_non_maximum_suppression` build them ('num_events' included), so `mean_average_precisions` works on them
-    unchanged.  The label-dependent error / F1 counters of `frame_events` follow from the returned pred on the host."""
+    unchanged.  The label-dependent error / F1 counters of `frame_events` follow from the returned pred on the host.
+    group_videos > 1: groups of videos go through `model.spot_video_group` as in `stitch_videos`."""
     from concurrent.futures import ThreadPoolExecutor
     videos = list(videos)
     suppress = [tuple(e) for e in suppress]
-    inv = {v: k for k, v in classes.items()}
-    ahead = max(int(decode_ahead), 0)
     done = {}
-    with ThreadPoolExecutor(max_workers=1, thread_name_prefix="tdeed-video") as ex:
-        pending = {}
+    if int(group_videos) > 1:
+        for group in _decoded_groups(videos, group_videos, max_resident_bytes):
+            out = model.spot_video_group([g[3] for g in group], classes, suppress=suppress,
+                                         high_recall_score_threshold=high_recall_score_threshold, overlap_len=overlap_len,
+                                         batch_size=batch_size, augment=augment, max_resident_bytes=max_resident_bytes)
+            for (name, _, fps, _), r in zip(group, out):
+                done[name] = (fps, r)
+    else:
+        ahead = max(int(decode_ahead), 0)
+        with ThreadPoolExecutor(max_workers=1, thread_name_prefix="tdeed-video") as ex:
+            pending = {}
 
-        def fetch(j):
-            if j < len(videos) and j not in pending:
-                src = videos[j][3]
-                pending[j] = ex.submit(src) if callable(src) else None
+            def fetch(j):
+                if j < len(videos) and j not in pending:
+                    src = videos[j][3]
+                    pending[j] = ex.submit(src) if callable(src) else None
 
-        for j, (name, length, fps, src) in enumerate(videos):
-            for k in range(j, j + ahead + 1):
-                fetch(k)
-            fut = pending.pop(j)
-            frames = src if fut is None else fut.result()
-            if int(frames.shape[0]) != int(length):
-                raise ValueError(f"video {name}: {int(frames.shape[0])} frames delivered, {int(length)} announced")
-            done[name] = (fps, model.spot_video(frames, classes, suppress=suppress,
-                                                high_recall_score_threshold=high_recall_score_threshold,
-                                                overlap_len=overlap_len, batch_size=batch_size, augment=augment))
+            for j, (name, length, fps, src) in enumerate(videos):
+                for k in range(j, j + ahead + 1):
+                    fetch(k)
+                fut = pending.pop(j)
+                frames = src if fut is None else fut.result()
+                if int(frames.shape[0]) != int(length):
+                    raise ValueError(f"video {name}: {int(frames.shape[0])} frames delivered, {int(length)} announced")
+                done[name] = (fps, model.spot_video(frames, classes, suppress=suppress,
+                                                    high_recall_score_threshold=high_recall_score_threshold,
+                                                    overlap_len=overlap_len, batch_size=batch_size, augment=augment))
     pred_events, lists, preds = [], [[] for _ in suppress], {}
     for name in sorted(done):
         fps, r = done[name]

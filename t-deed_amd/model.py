@@ -473,34 +473,171 @@ class TDEEDModel:
         self.last_video_stats = stats
         return dict(pred=pred_np, events=events, suppressed=suppressed)
 
+    def predict_video_group(self, frames_list, clip_starts=None, overlap_len=None, pad_len=5, batch_size=8, augment=False,
+                            use_amp=True, max_resident_bytes=16 << 30):
+        """predict_video for a group of videos scored as one packed job -> [(scores_sum (L_v,K+1) float32, support (L_v,)
+        int32)], per video what predict_video returns for the same batches.
+
+        frames_list: uint8 (L_v,3,H,W) tensors of one geometry, host (pinned or pageable) or device; clip_starts: optional
+        list of one start list per video.  Every frame is uploaded once into one packed buffer (video v from frame
+        seg_off[v] on, `evalutil.group_clip_table`), in `video_chunk_bytes` chunks on the copy stream; the clips of all
+        videos form one list, video-major, and batches of `batch_size` are cut from it ACROSS the videos, so only the
+        group's last batch may be short (short videos fill whole batches together); a batch waits only for the chunk with
+        the last packed frame one of its clips reads.  All clip scores go into one (V,n,T,K+1) buffer and one segmented
+        stitch launch (ops.stitch_scores_seg) adds them per frame in ScoreStitcher's order for that frame's video.  Apart
+        from the warm-up of a geometry seen for the first time the host synchronises once per group.
+        last_video_stats: predict_video's keys as totals over the group, plus videos and host_syncs.
+        Raises ValueError for an empty list, an empty video, mixed geometries or a group over `max_resident_bytes`."""
+        track, support, _, s0, stats, keep, g = self._packed_track(
+            "predict_video_group", list(frames_list), clip_starts, overlap_len, pad_len, batch_size, augment, use_amp,
+            max_resident_bytes, want_mean=False, group=True)
+        L, K1 = track.shape
+        with torch.cuda.stream(s0):
+            out_sum = torch.empty((L, K1), dtype=torch.float32).pin_memory()
+            out_sup = torch.empty((L,), dtype=torch.int32).pin_memory()
+            out_sum.copy_(track, non_blocking=True)
+            out_sup.copy_(support, non_blocking=True)
+            s0.synchronize()
+        del keep
+        stats["host_syncs"] = 1
+        self.last_video_stats = stats
+        sums, sup, off = out_sum.numpy(), out_sup.numpy(), g.seg_off
+        return [(sums[off[v]:off[v + 1]].copy(), sup[off[v]:off[v + 1]].copy()) for v in range(g.nv)]
+
+    def spot_video_group(self, frames_list, classes, suppress=(("nms", 1, 0.01), ("snms", 3, 0.01)),
+                         high_recall_score_threshold=0.01, clip_starts=None, overlap_len=None, pad_len=5, batch_size=8,
+                         augment=False, use_amp=True, max_resident_bytes=16 << 30):
+        """spot_video for a group of videos scored as one packed job (predict_video_group's pipeline) -> one spot_video
+        dict per video.  On the packed track: one segmented event launch (ops.frame_events_seg), one suppression launch per
+        entry of `suppress` with a workgroup per (class, video) (ops.nms_track_seg), whose compaction leaves the videos' event
+        lists one after the other in video order.  The host synchronises twice per group: once for pred bytes, their scores,
+        the event offsets and the rounds, once for one contiguous range of events per entry (skipped when nothing was
+        kept).  last_video_stats: totals over the group; nms_rounds per entry is the maximum over videos and classes."""
+        from . import evalutil
+        suppress = [tuple(e) for e in suppress]
+        for kind, window, _ in suppress:
+            if kind not in ("nms", "snms"):
+                raise ValueError(f"spot_video_group: suppression kind {kind!r} (nms | snms)")
+        inv = {v: k for k, v in classes.items()}
+        K1 = self._score_cols(torch.bfloat16 if use_amp else torch.float32)
+        if K1 > 256:
+            raise ValueError(f"spot_video_group: {K1} score columns, at most 256")
+        if sorted(inv) != list(range(1, K1)):
+            raise ValueError(f"spot_video_group: classes must name the indices 1..{K1 - 1} of the model's score columns")
+        track, _, mean, s0, stats, keep, g = self._packed_track(
+            "spot_video_group", list(frames_list), clip_starts, overlap_len, pad_len, batch_size, augment, use_amp,
+            max_resident_bytes, want_mean=True, group=True)
+        L, nv = track.shape[0], g.nv
+        hr = float(high_recall_score_threshold)
+        n = len(suppress)
+        with torch.cuda.stream(s0):
+            pred8 = torch.empty((L,), dtype=torch.uint8, device=mean.device)
+            _, pred_score, first, _ = ops.frame_events_seg(mean, g.seg_off_dev, g.max_len, hr, pred_u8=pred8,
+                                                           first_init=g.first_init)
+            lists = [ops.nms_track_seg(mean, g.seg_off_dev, g.max_len, window, thr, kind == "snms", first, hr)
+                     for kind, window, thr in suppress]
+            h_pred = torch.empty((L,), dtype=torch.uint8).pin_memory()
+            h_score = torch.empty((L,), dtype=torch.float32).pin_memory()
+            h_small = torch.empty((n, nv + 1 + nv * K1), dtype=torch.int32).pin_memory()     # event offsets, rounds
+            h_pred.copy_(pred8, non_blocking=True)
+            h_score.copy_(pred_score, non_blocking=True)
+            for i, (_, _, _, event_off, rounds) in enumerate(lists):
+                h_small[i, :nv + 1].copy_(event_off, non_blocking=True)
+                h_small[i, nv + 1:].copy_(rounds.view(-1), non_blocking=True)
+            s0.synchronize()
+            syncs = 1
+            small = h_small.numpy()
+            totals = [int(small[i, nv]) for i in range(n)]
+            host = []
+            for (fr, c8, sc, _, _), m in zip(lists, totals):
+                bufs = (torch.empty((m,), dtype=torch.int32).pin_memory(), torch.empty((m,), dtype=torch.uint8).pin_memory(),
+                        torch.empty((m,), dtype=torch.float64).pin_memory())
+                if m:
+                    for dst, src in zip(bufs, (fr, c8, sc)):
+                        dst.copy_(src[:m], non_blocking=True)
+                host.append(tuple(b.numpy() for b in bufs))
+            if any(totals):
+                s0.synchronize()
+                syncs += 1
+        del keep
+        pred_all = h_pred.numpy().astype(np.int32)
+        score_all = h_score.numpy()
+        out = []
+        for v in range(nv):
+            a, b = int(g.seg_off[v]), int(g.seg_off[v + 1])
+            pred_np, score_np = pred_all[a:b].copy(), score_all[a:b]
+            fg = np.nonzero(pred_np != 0)[0]
+            events = [{"label": inv[int(pred_np[i])], "frame": int(i), "score": float(score_np[i])} for i in fg]
+            suppressed = []
+            for i, (f, c, s_) in enumerate(host):
+                e0, e1 = int(small[i, v]), int(small[i, v + 1])
+                suppressed.append(evalutil.event_dicts(f[e0:e1], c[e0:e1], s_[e0:e1], inv))
+            out.append(dict(pred=pred_np, events=events, suppressed=suppressed))
+        stats["events_d2h_bytes"] = L * 5 + n * (nv + 1 + nv * K1) * 4 + 13 * sum(totals)
+        stats["nms_rounds"] = [int(small[i, nv + 1:].max()) for i in range(n)]
+        stats["host_syncs"] = syncs
+        self.last_video_stats = stats
+        return out
+
     def _video_track(self, frames, clip_starts, overlap_len, pad_len, batch_size, augment, use_amp, max_resident_bytes,
                      want_mean):
         """The body of predict_video up to and including the stitch launch, nothing synchronised: -> (track (L,K+1) fp32,
         support (L,) int32, mean (L,K+1) fp32 | None: device tensors written on stream s0; s0; the last_video_stats dict; the
         resident buffers, to be kept alive until s0 has been synchronised)."""
+        return self._packed_track("predict_video", [frames], clip_starts, overlap_len, pad_len, batch_size, augment, use_amp,
+                                  max_resident_bytes, want_mean, group=False)[:6]
+
+    def _packed_track(self, who, frames_list, clip_starts, overlap_len, pad_len, batch_size, augment, use_amp,
+                      max_resident_bytes, want_mean, group):
+        """One or several videos through upload, batches and the stitch launch, nothing synchronised.  group=False: one video,
+        clip_starts its flat list (what `_video_track` returns, through ops.clip_gather / ops.stitch_scores).  group=True:
+        the videos are packed one after the other into one resident buffer and one clip list (evalutil.group_clip_table,
+        clip_starts one list per video), batches are cut from that list across the videos, the gathers and the stitch are
+        the segmented kernels; track / support / mean cover the packed frames.  -> `_video_track`'s tuple plus a namespace
+        of the group's tables (None for group=False)."""
+        from types import SimpleNamespace
         from . import evalutil
         from .streams import new_stream
-        if not isinstance(frames, torch.Tensor):
-            frames = torch.as_tensor(np.asarray(frames))
-        if frames.dtype != torch.uint8 or frames.dim() != 4:
-            raise TypeError("predict_video: frames must be a uint8 (L,3,H,W) tensor")
-        L = int(frames.shape[0])
-        fb = int(frames[0].numel()) if L else 0
-        if L == 0:
-            raise ValueError("predict_video: empty video")
+        srcs = []
+        for fr in frames_list:
+            if not isinstance(fr, torch.Tensor):
+                fr = torch.as_tensor(np.asarray(fr))
+            if fr.dtype != torch.uint8 or fr.dim() != 4:
+                raise TypeError(f"{who}: frames must be a uint8 (L,3,H,W) tensor")
+            srcs.append(fr)
+        if not srcs:
+            raise ValueError(f"{who}: no videos")
+        lengths = [int(fr.shape[0]) for fr in srcs]
+        if min(lengths) == 0:
+            raise ValueError(f"{who}: empty video")
+        shape = tuple(srcs[0].shape[1:])
+        if any(tuple(fr.shape[1:]) != shape for fr in srcs):
+            raise ValueError(f"{who}: the videos of one group share one frame geometry, got "
+                             f"{sorted({tuple(fr.shape[1:]) for fr in srcs})}")
+        nv, L = len(srcs), sum(lengths)
+        fb = int(srcs[0][0].numel())
+        if nv > ops.MAX_GROUP_VIDEOS:
+            raise ValueError(f"{who}: {nv} videos in one group, at most {ops.MAX_GROUP_VIDEOS}")
         if L * fb > max_resident_bytes:
-            raise ValueError(f"predict_video: the video needs {L * fb} bytes on the device, more than max_resident_bytes="
-                             f"{max_resident_bytes} (a ring buffer for longer videos is not implemented)")
+            raise ValueError(f"{who}: the {'group' if group else 'video'} needs {L * fb} bytes on the device, more than "
+                             f"max_resident_bytes={max_resident_bytes} (a ring buffer for longer videos is not implemented)")
         T = self._args.clip_len
-        if clip_starts is None:
-            ov = T // 4 * 3 if overlap_len is None else int(overlap_len)
-            clip_starts = evalutil.video_clip_starts(L, T, ov, pad_len=pad_len)
-        starts = [int(s) for s in clip_starts]
+        ov = T // 4 * 3 if overlap_len is None else int(overlap_len)
+        if group:
+            seg_off, clip_off, starts_np, base_np, lenv_np = evalutil.group_clip_table(lengths, T, ov, pad_len, clip_starts)
+            starts, base, len_v = starts_np.tolist(), base_np.tolist(), lenv_np.tolist()
+        else:
+            if clip_starts is None:
+                clip_starts = evalutil.video_clip_starts(L, T, ov, pad_len=pad_len)
+            starts = [int(s) for s in clip_starts]
+            base, len_v = [0] * len(starts), [L] * len(starts)
         n = len(starts)
         if n == 0:
-            raise ValueError("predict_video: no clips")
+            raise ValueError(f"{who}: no clips")
         if batch_size < 1:
-            raise ValueError("predict_video: batch_size must be positive")
+            raise ValueError(f"{who}: batch_size must be positive")
+        # last packed frame a clip reads (-1: none before the front of its video)
+        last_of = [b + min(lv - 1, s_ + T - 1) if s_ + T - 1 >= 0 else -1 for s_, b, lv in zip(starts, base, len_v)]
         V = 2 if augment else 1
         self._model.eval()
         dt = torch.bfloat16 if use_amp else torch.float32
@@ -518,21 +655,35 @@ class TDEEDModel:
         cur = torch.cuda.current_stream()
         for st in streams + [cp]:
             st.wait_stream(cur)
-        # ---- the resident buffers (kept alive until the one synchronisation at the end)
-        starts_host = torch.tensor(starts, dtype=torch.int32).pin_memory()
-        starts_dev = torch.empty((n,), dtype=torch.int32, device=dev)
+        # ---- the resident buffers (kept alive until the one synchronisation at the end); the tables travel in one copy
+        g = None
+        if group:
+            first_init = np.repeat(np.asarray(lengths, np.int32), K1)
+            parts = [starts_np, base_np, lenv_np, seg_off, clip_off, first_init]
+            tab_host = torch.from_numpy(np.concatenate(parts)).pin_memory()
+        else:
+            tab_host = torch.tensor(starts, dtype=torch.int32).pin_memory()
+        tab_dev = torch.empty((tab_host.numel(),), dtype=torch.int32, device=dev)
         clip_scores = torch.empty((V, n, T, K1), dtype=torch.float32, device=dev)
         with torch.cuda.stream(cp):
-            starts_dev.copy_(starts_host, non_blocking=True)
+            tab_dev.copy_(tab_host, non_blocking=True)
             ev_starts = torch.cuda.Event()
             ev_starts.record(cp)
+        starts_dev = tab_dev[:n]
+        if group:
+            cuts = np.cumsum([0] + [len(x) for x in parts]).tolist()
+            base_dev, lenv_dev, seg_dev, coff_dev, first_dev = (tab_dev[cuts[i]:cuts[i + 1]] for i in range(1, 6))
+            g = SimpleNamespace(nv=nv, lengths=lengths, seg_off=seg_off, max_len=max(lengths), seg_off_dev=seg_dev,
+                                first_init=first_dev.view(nv, K1), K1=K1)
         h2d = 0
-        on_host = not frames.is_cuda
-        frames = frames.contiguous()
-        if on_host:
-            video = torch.empty(frames.shape, dtype=torch.uint8, device=dev)
+        srcs = [fr.contiguous() if not fr.is_cuda else fr.to(dev).contiguous() for fr in srcs]
+        packed = group or not srcs[0].is_cuda
+        if packed:
+            # one buffer for all frames, filled in chunks of video_chunk_bytes on the copy stream (a chunk may span videos)
+            video = torch.empty((L,) + shape, dtype=torch.uint8, device=dev)
             per = max(1, int(self.video_chunk_bytes) // fb)
             bounds = [(lo, min(lo + per, L)) for lo in range(0, L, per)]
+            offs = np.concatenate([[0], np.cumsum(lengths)]).tolist()
             arrived = []
 
             def upload_through(c):
@@ -540,15 +691,18 @@ class TDEEDModel:
                 with torch.cuda.stream(cp):
                     while len(arrived) <= min(c, len(bounds) - 1):
                         lo, hi = bounds[len(arrived)]
-                        video[lo:hi].copy_(frames[lo:hi], non_blocking=True)
-                        h2d += (hi - lo) * fb
+                        for v, fr in enumerate(srcs):
+                            a, b = max(lo, offs[v]), min(hi, offs[v + 1])
+                            if a < b:
+                                video[a:b].copy_(fr[a - offs[v]:b - offs[v]], non_blocking=True)
+                                h2d += 0 if fr.is_cuda else (b - a) * fb
                         ev = torch.cuda.Event()
                         ev.record(cp)
                         arrived.append(ev)
-            if frames.is_pinned():
-                upload_through(len(bounds) - 1)       # asynchronous copies: queue the whole video behind the first chunk
+            if all(fr.is_cuda or fr.is_pinned() for fr in srcs):
+                upload_through(len(bounds) - 1)       # asynchronous copies: queue all frames behind the first chunk
         else:
-            video = frames.to(dev)
+            video = srcs[0]
         # ---- the batches: gather -> forward -> post-processing, two in flight
         n_batches = 0
         for bi, lo in enumerate(range(0, n, batch_size)):
@@ -556,16 +710,17 @@ class TDEEDModel:
             slot = bi % 2
             st = streams[slot]
             need = ev_starts
-            if on_host:
-                last = min(L - 1, max(starts[lo:lo + B]) + T - 1)
+            if packed:
+                last = max(last_of[lo:lo + B])
                 if last >= 0:
                     c = last // per
                     upload_through(c + 1)             # pageable frames: the copy call stages on the host, keep one chunk ahead
                     need = arrived[c]
             with torch.cuda.stream(st):
-                st.wait_event(need)
+                st.wait_event(need)                   # a chunk's event follows the tables' on the copy stream
+                tables = dict(clip_base=base_dev[lo:lo + B], clip_len_v=lenv_dev[lo:lo + B]) if group else {}
                 for v in range(V):
-                    head, _ = eng.forward_from_video(video, starts_dev[lo:lo + B], augment_inference=bool(v), slot=slot)
+                    head, _ = eng.forward_from_video(video, starts_dev[lo:lo + B], augment_inference=bool(v), slot=slot, **tables)
                     pred, _ = self._model._pack_head(head, B, T, pw.n_cls, pw.displ_col, None)
                     # head is a view of the slot's buffer: consumed here, on the launching stream, before the slot runs again
                     self._process_pred(pred, B, T, dt, out=clip_scores[v, lo:lo + B])
@@ -575,9 +730,15 @@ class TDEEDModel:
         s0.wait_stream(streams[1])
         s0.wait_stream(cp)
         with torch.cuda.stream(s0):
-            track, support, mean = ops.stitch_scores(clip_scores, starts_dev, L, count_all=augment, mean=want_mean)
+            if group:
+                track, support, mean = ops.stitch_scores_seg(clip_scores, starts_dev, seg_dev, coff_dev, L, count_all=augment,
+                                                             mean=want_mean)
+            else:
+                track, support, mean = ops.stitch_scores(clip_scores, starts_dev, L, count_all=augment, mean=want_mean)
         stats = dict(frames=L, clips=n, batches=n_batches, views=V, frames_h2d_bytes=h2d)
-        return track, support, mean, s0, stats, (video, frames, clip_scores, starts_dev, starts_host)
+        if group:
+            stats["videos"] = nv
+        return track, support, mean, s0, stats, (video, srcs, clip_scores, tab_dev, tab_host), g
 
     def epoch(self, loader, optimizer=None, scaler=None, lr_scheduler=None, acc_grad_iter=1, fg_weight=5,
               valMAP=False):

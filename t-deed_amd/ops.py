@@ -777,6 +777,154 @@ def nms_track(mean, window, threshold, soft, hr_threshold=0.01, first_frame=None
     return frames, classes, scores, count, rounds
 
 
+# ---- a group of videos packed one after the other (tables: evalutil.group_clip_table, int32 on the device)
+MAX_GROUP_VIDEOS = 65535
+
+
+def _chk_table(tab, n, dev, who, what):
+    if not isinstance(tab, torch.Tensor) or tab.dtype != torch.int32 or tab.dim() != 1 or tab.numel() != n \
+            or not tab.is_contiguous() or tab.device != dev:
+        raise ValueError(f"{who}: {what} must be a contiguous int32 ({n},) tensor on the data's device")
+
+
+def _chk_group(seg_off, dev, who):
+    if not isinstance(seg_off, torch.Tensor) or seg_off.dtype != torch.int32:
+        raise TypeError(f"{who}: seg_off must be an int32 tensor")
+    nv = seg_off.numel() - 1
+    if nv < 1:
+        raise ValueError(f"{who}: seg_off needs at least two entries")
+    if nv > MAX_GROUP_VIDEOS:
+        raise ValueError(f"{who}: {nv} videos in one group, at most {MAX_GROUP_VIDEOS}")
+    _chk_table(seg_off, nv + 1, dev, who, "seg_off")
+    return nv
+
+
+def clip_gather_seg(video_u8, starts_dev, clip_base, clip_len_v, T, out):
+    """clip_gather over several videos packed into video_u8 (sum L, ...): out[b*T + t] = video_u8[clip_base[b] + starts[b] + t]
+    when 0 <= starts[b] + t < clip_len_v[b], a zero frame otherwise -- the window ends where the clip's own video ends.
+    starts_dev / clip_base / clip_len_v: int32 (B,) on the device."""
+    if video_u8.dtype != torch.uint8 or out.dtype != torch.uint8 or starts_dev.dtype != torch.int32:
+        raise TypeError("clip_gather_seg: uint8 frames and int32 starts")
+    if not (video_u8.is_contiguous() and out.is_contiguous() and starts_dev.is_contiguous()):
+        raise ValueError("clip_gather_seg: contiguous tensors only")
+    L, B = video_u8.shape[0], starts_dev.numel()
+    _chk_table(starts_dev, B, video_u8.device, "clip_gather_seg", "starts")
+    _chk_table(clip_base, B, video_u8.device, "clip_gather_seg", "clip_base")
+    _chk_table(clip_len_v, B, video_u8.device, "clip_gather_seg", "clip_len_v")
+    fb = video_u8[0].numel()
+    if out.numel() != B * T * fb:
+        raise ValueError(f"clip_gather_seg: out holds {out.numel()} bytes, {B} clips of {T} frames need {B * T * fb}")
+    call("tdeed_clip_gather_seg_u8", ptr(video_u8), L, fb, ptr(starts_dev), ptr(clip_base), ptr(clip_len_v), B, T, ptr(out),
+         stream_ptr())
+    return out
+
+
+def stitch_scores_seg(clip_scores, starts_dev, seg_off, clip_off, L, count_all=None, track_sum=None, support=None, mean=False):
+    """stitch_scores per video of a group: clip_scores fp32 (V,n,T,K1) of the group's clip list (video-major), starts_dev
+    int32 (n,) video-local, seg_off / clip_off int32 (nv+1,) on the device, L = sum of the lengths.  -> (track_sum (sum L,K1), support (sum L,) int32,
+    mean | None) over the packed frames; rows seg_off[v]:seg_off[v+1] carry the bits of stitch_scores on video v alone."""
+    if not isinstance(clip_scores, torch.Tensor) or clip_scores.dim() != 4:
+        raise TypeError("stitch_scores_seg: clip_scores must be a (V,n,T,K1) tensor")
+    V, n, T, K1 = clip_scores.shape
+    if clip_scores.dtype != torch.float32 or starts_dev.dtype != torch.int32 or not clip_scores.is_contiguous():
+        raise TypeError("stitch_scores_seg: contiguous float32 scores and int32 starts")
+    dev = clip_scores.device
+    nv = _chk_group(seg_off, dev, "stitch_scores_seg")
+    _chk_table(starts_dev, n, dev, "stitch_scores_seg", "starts")
+    _chk_table(clip_off, nv + 1, dev, "stitch_scores_seg", "clip_off")
+    L = int(L)
+    if L < nv:
+        raise ValueError(f"stitch_scores_seg: {L} packed frames for {nv} videos")
+    if track_sum is None:
+        track_sum = torch.zeros((L, K1), dtype=torch.float32, device=dev)
+    if support is None:
+        support = torch.zeros((L,), dtype=torch.int32, device=dev)
+    if tuple(track_sum.shape) != (L, K1) or tuple(support.shape) != (L,) or track_sum.dtype != torch.float32 \
+            or support.dtype != torch.int32 or not (track_sum.is_contiguous() and support.is_contiguous()) \
+            or track_sum.device != dev or support.device != dev:
+        raise ValueError("stitch_scores_seg: track_sum float32 (L,K1) and support int32 (L,), contiguous")
+    mean_out = torch.empty((L, K1), dtype=torch.float32, device=dev) if mean else None
+    ca = (V > 1) if count_all is None else bool(count_all)
+    call("tdeed_stitch_scores_seg", ptr(clip_scores), V, n, T, K1, ptr(starts_dev), ptr(seg_off), ptr(clip_off), nv, int(ca), L,
+         ptr(track_sum), ptr(support), ptr(mean_out), stream_ptr())
+    return track_sum, support, mean_out
+
+
+def frame_events_seg(mean, seg_off, max_len, hr_threshold=0.01, pred_u8=None, first_init=None):
+    """frame_events per video of a packed track: mean fp32 (sum L,K1), seg_off int32 (nv+1,) on the device, max_len the
+    longest video (a host number).  -> (pred (sum L,) int32, pred_score (sum L,) fp32, first_frame (nv,K1) int32 in
+    video-local frames, L_v where a class has no candidate, count (nv,K1) int32).  first_init: optional int32 (nv,K1) tensor
+    already holding L_v in row v (a caller that uploads its tables anyway); it is written to and returned."""
+    L, K1 = _chk_track(mean, "frame_events_seg")
+    dev = mean.device
+    nv = _chk_group(seg_off, dev, "frame_events_seg")
+    max_len = int(max_len)
+    if not 1 <= max_len <= L:
+        raise ValueError(f"frame_events_seg: max_len {max_len} for {L} packed frames")
+    if pred_u8 is not None:
+        if K1 > 256:
+            raise ValueError(f"frame_events_seg: {K1} columns do not fit a one-byte prediction")
+        if pred_u8.dtype != torch.uint8 or tuple(pred_u8.shape) != (L,) or not pred_u8.is_contiguous() or pred_u8.device != dev:
+            raise ValueError("frame_events_seg: pred_u8 must be a contiguous uint8 (L,) tensor on the track's device")
+    if first_init is None:
+        first = (seg_off[1:] - seg_off[:-1]).unsqueeze(1).repeat(1, K1)
+    else:
+        first = first_init
+        if first.dtype != torch.int32 or tuple(first.shape) != (nv, K1) or not first.is_contiguous() or first.device != dev:
+            raise ValueError("frame_events_seg: first_init must be a contiguous int32 (nv,K1) tensor on the track's device")
+    pred = torch.empty((L,), dtype=torch.int32, device=dev)
+    pred_score = torch.empty((L,), dtype=torch.float32, device=dev)
+    count = torch.zeros((nv, K1), dtype=torch.int32, device=dev)
+    call("tdeed_frame_events_seg", ptr(mean), ptr(seg_off), nv, L, max_len, K1, float(hr_threshold), ptr(pred), ptr(pred_u8),
+         ptr(pred_score), ptr(first), ptr(count), stream_ptr())
+    return pred, pred_score, first, count
+
+
+def nms_track_seg(mean, seg_off, max_len, window, threshold, soft, first_frame, hr_threshold=0.01):
+    """nms_track per video of a packed track, one launch for the whole group: mean fp32 (sum L,K1), seg_off int32 (nv+1,),
+    first_frame int32 (nv,K1) from frame_events_seg with the same hr_threshold; window / threshold / soft as nms_track.
+    Returns device tensors (frames int32, classes uint8, scores float64, event_off int32 (nv+1,), rounds int32 (nv,K1)):
+    entries event_off[v]:event_off[v+1] are video v's kept events (video-local frames, nms_track's order), the lists of
+    the videos following each other densely in video order."""
+    L, K1 = _chk_track(mean, "nms_track_seg")
+    dev = mean.device
+    nv = _chk_group(seg_off, dev, "nms_track_seg")
+    max_len = int(max_len)
+    if not 1 <= max_len <= L:
+        raise ValueError(f"nms_track_seg: max_len {max_len} for {L} packed frames")
+    soft = bool(soft)
+    is_list = isinstance(window, (list, tuple))
+    wins = [int(w) for w in window] if is_list else [int(window)]
+    if is_list and len(wins) < K1 - 1:
+        raise ValueError(f"nms_track_seg: a window list of {len(wins)} entries for {K1 - 1} classes")
+    if is_list and len(wins) == 1:
+        is_list = False
+    if any(w < (1 if soft else 0) or w > 1 << 30 for w in wins):
+        raise ValueError(f"nms_track_seg: windows {wins}: soft suppression needs windows >= 1, hard suppression >= 0 (and at most 2^30)")
+    wins = wins[:K1 - 1] if is_list else wins[:1]
+    if not isinstance(first_frame, torch.Tensor) or first_frame.dtype != torch.int32 or tuple(first_frame.shape) != (nv, K1) \
+            or not first_frame.is_contiguous() or first_frame.device != dev:
+        raise ValueError("nms_track_seg: first_frame must be a contiguous int32 (nv,K1) tensor on the track's device")
+    cap = L * (K1 - 1)
+    ws_bytes = int(_lib.load().tdeed_nms_track_seg_workspace(L, max_len, K1))
+    ws = torch.empty((ws_bytes // 8 + 1,), dtype=torch.float64, device=dev) if ws_bytes else None
+    emitted = torch.empty((K1, L), dtype=torch.uint8, device=dev)
+    kept = torch.empty((K1, L), dtype=torch.float64, device=dev)
+    st_i = torch.empty((cap + nv,), dtype=torch.int32, device=dev)           # staged frames, then the nv list lengths
+    st_c = torch.empty((cap,), dtype=torch.uint8, device=dev)
+    st_s = torch.empty((cap,), dtype=torch.float64, device=dev)
+    frames = torch.empty((cap,), dtype=torch.int32, device=dev)
+    classes = torch.empty((cap,), dtype=torch.uint8, device=dev)
+    scores = torch.empty((cap,), dtype=torch.float64, device=dev)
+    event_off = torch.empty((nv + 1,), dtype=torch.int32, device=dev)
+    rounds = torch.empty((nv, K1), dtype=torch.int32, device=dev)
+    warr = (ctypes.c_int * len(wins))(*wins)
+    call("tdeed_nms_track_seg", ptr(mean), ptr(seg_off), nv, L, max_len, K1, float(hr_threshold), float(threshold), int(soft),
+         warr, len(wins), ptr(first_frame), ptr(ws), ptr(emitted), ptr(kept), ptr(st_i), ptr(st_c), ptr(st_s), ptr(st_i[cap:]),
+         ptr(frames), ptr(classes), ptr(scores), ptr(event_off), ptr(rounds), stream_ptr())
+    return frames, classes, scores, event_off, rounds
+
+
 def cast_bf16(src_f32):
     out = torch.empty(src_f32.shape, dtype=torch.bfloat16, device=src_f32.device)
     call("tdeed_cast_f32_to_bf16", ptr(src_f32), ptr(out), src_f32.numel(), stream_ptr())

@@ -6,6 +6,8 @@
     python tools/bench_video.py --decode [--decode-frames 400]          host only: load_video vs clip_batches, JPEG decode
     python tools/bench_video.py --spot [--frames 5625]                  events: predict_video + the host chain against
                                                                         spot_video, one JSON line
+    python tools/bench_video.py --group [--group-videos 32]             short videos: spot_videos video by video against
+                                                                        spot_videos in packed groups, one JSON line
 
 Routes (RegNetY-200MF, T = 100, 224 x 224, bf16; 3/4 overlap like the evaluation datasets):
   A  the clip route: `evalutil.stitch_predictions` over host-resident PINNED uint8 clip batches of the video, at loader
@@ -212,6 +214,116 @@ def spot(a):
     return 0 if "error" not in out else 1
 
 
+GROUP_SPLITS = dict(diving=(96, 66, 220, 2.14), tennis=(48, 178, 1442, 2.78))     # videos, shortest, longest, skew
+
+
+def group_lengths(split):
+    """lengths of a synthetic split from a fixed hash: u in [0,1) per video, L = lo + (hi - lo) * u ** skew, the skew chosen
+    so that the median sits near the median of the dataset the split is named after (101 / 362 frames)"""
+    nvid, lo, hi, skew = GROUP_SPLITS[split]
+    mix = lambda h: ((h ^ (h >> 29)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF          # FNV's high bits barely move
+    u = [(mix(synth.fnv1a64(f"{split}{i}")) >> 11) / float(1 << 53) for i in range(nvid)]
+    out = [lo + int((hi - lo) * x ** skew) for x in u]
+    out[0], out[1] = lo, hi                                             # both ends of the range occur
+    return out
+
+
+def _event_keys(lists):
+    return {(i, rec["video"], e["label"], e["frame"]): e["score"] for i, lst in enumerate(lists) for rec in lst
+            for e in rec["events"]}
+
+
+def group(a):
+    """Two routes over the same synthetic split of short videos, alternating: A `evalutil.spot_videos(group_videos=1)` (one
+    spot_video per video), B `spot_videos(group_videos=a.group_videos)` (packed groups).  Pinned frames, default suppression,
+    batch size 8, bf16.  Per route: median / min / max seconds over `--repeats` passes, videos/s, clips/s, forward batches,
+    host synchronisations and forward plans (one captured graph each) of one pass."""
+    from tdeed_amd.model import TDEEDModel
+    from types import SimpleNamespace
+    T = CFG["clip_len"]
+    m = TDEEDModel(device="cuda", args=SimpleNamespace(modality="rgb", temporal_arch="ed_sgp_mixer", pretrain=None, **CFG))
+    m.load({k: torch.from_numpy(v) for k, v in synth.make_state(state_layout.model_state_shapes(CFG), 0).items()})
+    classes = {f"c{k}": k for k in range(1, CFG["num_classes"] + 1)}
+    suppress = (("nms", 1, 0.01), ("snms", 3, 0.01))
+    eng = m._model.engine(torch.bfloat16)
+    seen = dict(batches=0, syncs=0, plans=set())
+    real_plan, real_sync = eng.plan, torch.cuda.Stream.synchronize
+
+    def plan(*args, **kw):
+        p = real_plan(*args, **kw)
+        seen["plans"].add(id(p))
+        return p
+
+    def sync(self):
+        seen["syncs"] += 1
+        return real_sync(self)
+    eng.plan = plan
+    torch.cuda.Stream.synchronize = sync
+    for name in ("spot_video", "spot_video_group"):
+        def wrapped(*args, _fn=getattr(m, name), **kw):
+            r = _fn(*args, **kw)
+            seen["batches"] += m.last_video_stats["batches"]
+            return r
+        setattr(m, name, wrapped)
+    out = dict(kind="video_groups", cfg=CFG, batch_size=8, group_videos=a.group_videos, repeats=a.repeats, suppress=suppress,
+               splits={})
+    for split in a.splits.split(","):
+        lengths = group_lengths(split)
+        off = np.concatenate([[0], np.cumsum(lengths)])
+        packed = torch.empty((int(off[-1]), 3, H, W), dtype=torch.uint8).pin_memory()
+        for lo in range(0, int(off[-1]), 2048):                         # generated on the device in pieces
+            hi = min(lo + 2048, int(off[-1]))
+            packed[lo:hi].copy_(ops.fill_u8_hash((hi - lo, 3, H, W), 9 + lo, "cuda"))
+        vids = [(f"v{i:03d}", L, 25.0, packed[off[i]:off[i + 1]]) for i, L in enumerate(lengths)]
+        n_clips = sum(len(E.video_clip_starts(L, T, T // 4 * 3)) for L in lengths)
+        routes = dict(A=lambda: E.spot_videos(m, vids, classes, suppress, batch_size=8, group_videos=1),
+                      B=lambda: E.spot_videos(m, vids, classes, suppress, batch_size=8, group_videos=a.group_videos))
+        res, counts = {}, {}
+        for k, fn in routes.items():                                    # warm-up of every shape; the second pass is counted
+            fn()
+            seen.update(batches=0, syncs=0, plans=set())
+            res[k] = fn()
+            counts[k] = dict(batches=seen["batches"], host_syncs=seen["syncs"], graphs=len(seen["plans"]))
+        times = {k: [] for k in routes}
+        for _ in range(a.repeats):
+            for k, fn in routes.items():                                # alternating
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                times[k].append(time.perf_counter() - t0)
+        st = {}
+        for k, v in times.items():
+            t = np.asarray(v)
+            med = float(np.median(t))
+            st[k] = dict(ms_median=round(med * 1e3, 2), ms_min=round(float(t.min()) * 1e3, 2),
+                         ms_max=round(float(t.max()) * 1e3, 2), videos_per_s=round(len(lengths) / med, 1),
+                         clips_per_s=round(n_clips / med, 1), **counts[k])
+        ka, kb = _event_keys(res["A"][1]), _event_keys(res["B"][1])
+        common = set(ka) & set(kb)
+        spread = st["A"]["ms_max"] - st["A"]["ms_min"]
+        out["splits"][split] = dict(
+            videos=len(lengths), frames=int(off[-1]), clips=n_clips, length_min=min(lengths),
+            length_median=float(np.median(lengths)), length_max=max(lengths), routes=st,
+            speedup_B_over_A=round(st["A"]["ms_median"] / st["B"]["ms_median"], 3),
+            B_not_slower_than_A_by_more_than_A_spread=bool(st["B"]["ms_median"] <= st["A"]["ms_median"] + spread),
+            equal=bool(res["A"][0] == res["B"][0] and res["A"][1] == res["B"][1]),
+            events=dict(A=len(ka), B=len(kb), common=len(common),
+                        max_score_diff_common=max([abs(ka[k] - kb[k]) for k in common], default=0.0)))
+        if split == a.splits.split(",")[0]:
+            # fp32, the first six videos: per-frame mean scores of the two routes (other batches: a bound, not equality)
+            six = [v[3] for v in vids[:6]]
+            grp = m.predict_video_group(six, batch_size=8, use_amp=False)
+            worst = 0.0
+            for fr, (gs, gn) in zip(six, grp):
+                s1, n1 = m.predict_video(fr, batch_size=8, use_amp=False)
+                d = np.maximum(n1, 1)[:, None].astype(np.float32)
+                worst = max(worst, float(np.abs(s1 / d - gs / d).max()))
+            out["fp32_max_mean_diff_first6"] = worst
+        del vids, packed
+    print(json.dumps(out))
+    return 0
+
+
 def gather_only(a):
     T, B, L = 100, 8, 400
     video = ops.fill_u8_hash((L, 3, H, W), 9, "cuda")
@@ -265,6 +377,9 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=None, help="default 2030, with --spot 5625")
     ap.add_argument("--spot", action="store_true")
+    ap.add_argument("--group", action="store_true")
+    ap.add_argument("--group-videos", type=int, default=32, help="--group: videos per packed group of route B")
+    ap.add_argument("--splits", default="diving,tennis", help="--group: synthetic splits to run")
     ap.add_argument("--window", type=int, default=12, help="--spot: NMS / soft-NMS window")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--gather-only", action="store_true")
@@ -274,4 +389,5 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if a.frames is None:
         a.frames = 5625 if a.spot else 2030
-    sys.exit(decode(a) if a.decode else gather_only(a) if a.gather_only else spot(a) if a.spot else bench(a))
+    sys.exit(decode(a) if a.decode else gather_only(a) if a.gather_only else group(a) if a.group else spot(a) if a.spot
+             else bench(a))
