@@ -478,6 +478,31 @@ int tdeed_nms_track_seg(const float* mean, const int* seg_off, int nv, int L_tot
                         int* st_count, int* out_frame, unsigned char* out_class_u8, double* out_score, int* event_off, int* rounds,
                         void* stream);
 
+/* ---- training clips drawn from resident videos (trainclips.hip) -----------------------------------------------------
+ * frames: uint8 [total_frames][frame_bytes], the frames of all resident videos packed one after the other.  The tables are
+ * DEVICE int64[B], per clip: first = first packed frame of the clip's video, nframes = that video's length, base = the
+ * clip's first original frame (may be negative).  out[b][t] = frames[first[b] + base[b] + t*stride] when
+ * 0 <= base[b] + t*stride < nframes[b], else a zero frame (FrameReader.load_paths / load_frames(pad=True),
+ * dataset/frame.py:274-382): a window that hangs over the end of its video never reads the next one, and an entry that
+ * points outside the packed buffer is not followed.  16-byte accesses when frame_bytes % 16 == 0 and both buffers are
+ * 16-byte aligned, a byte path otherwise.  B * T <= 65535. */
+int tdeed_train_clip_gather_u8(const uint8_t* frames, long total_frames, long frame_bytes, const long* first, const long* base,
+                               const long* nframes, int B, int T, int stride, uint8_t* out, void* stream);
+/* Mixup of two such windows without their uint8 intermediates: out fp32 [B][T][frame_bytes] =
+ * lam[b] * A[b][t] + (1 - lam[b]) * B[b][t], bit for bit what tdeed_mix_frames gives on the two batches
+ * tdeed_train_clip_gather_u8 would write (a padded frame contributes 0).  4-byte loads / 16-byte stores when
+ * frame_bytes % 4 == 0 and the buffers are aligned for them, a scalar path otherwise. */
+int tdeed_train_clip_gather_mix_f32(const uint8_t* frames, long total_frames, long frame_bytes, const long* first_a,
+                                    const long* base_a, const long* nframes_a, const long* first_b, const long* base_b,
+                                    const long* nframes_b, const float* lam, int B, int T, int stride, float* out, void* stream);
+/* Labels of n clips (dataset/frame.py:151-159, 226-233): clip_video / clip_base DEVICE int64[n] (video index, first original
+ * frame), ev_off int32[nv+1] / ev_frame / ev_class int32[n_events] the videos' events in file order.  Per (clip, t) the
+ * events of the clip's video are walked in order, idx = floor((ev_frame - base) / stride); the last one with
+ * |t - idx| <= r gives label[clip][t] = its class and labelD[clip][t] = t - idx, 0 / 0 when there is none.  label / labelD
+ * int64 [n][T] (labelD may be NULL).  One thread per position, no atomics. */
+int tdeed_clip_labels(const long* clip_video, const long* clip_base, int n, int T, int stride, int r, const int* ev_off,
+                      const int* ev_frame, const int* ev_class, int nv, int n_events, long* label, long* labelD, void* stream);
+
 /* ---- backward of the SGP encoder-decoder (training path; sgp_bwd.hip) ------------------------------------------
  * Activations and activation gradients share the forward dtype; parameter gradients are fp32.  Every parameter
  * gradient is produced as caller-owned per-workgroup partials (`part*`) folded in a fixed order: no float atomics,

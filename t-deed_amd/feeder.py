@@ -555,6 +555,47 @@ class PinnedRing:
         self.consumed[j] = ev
 
 
+class PackedUpload:
+    """The frames of several videos in ONE device buffer `video` (sum L,3,H,W), filled in chunks of `chunk_bytes` on the
+    copy stream `stream` (a chunk may span videos), one arrival event per chunk: the resident buffer of
+    `TDEEDModel.predict_video` / `predict_video_group` and of `trainclips.ResidentClips`.  srcs: contiguous uint8
+    (L_v,3,H,W) tensors of one frame geometry -- host, pinned or device.  `through(c)` queues the chunks up to c;
+    pinned and device sources copy asynchronously, so all of them may be queued at once (`asynchronous`), while a copy
+    from pageable memory stages on the host inside the call: a consumer keeps such an upload one chunk ahead."""
+
+    def __init__(self, srcs, device, stream, chunk_bytes):
+        self.srcs, self.stream = srcs, stream
+        lengths = [int(fr.shape[0]) for fr in srcs]
+        L = sum(lengths)
+        self.frame_bytes = fb = int(srcs[0][0].numel())
+        self.video = torch.empty((L,) + tuple(srcs[0].shape[1:]), dtype=torch.uint8, device=device)
+        self.per = max(1, int(chunk_bytes) // fb)
+        self.bounds = [(lo, min(lo + self.per, L)) for lo in range(0, L, self.per)]
+        self.offs = np.concatenate([[0], np.cumsum(lengths)]).tolist()
+        self.arrived = []
+        self.h2d = 0                              # bytes that crossed the host-device link so far
+        self.asynchronous = all(fr.is_cuda or fr.is_pinned() for fr in srcs)
+
+    def through(self, c):
+        """Queue every chunk up to and including c (clamped to the last) that is not queued yet."""
+        with torch.cuda.stream(self.stream):
+            while len(self.arrived) <= min(c, len(self.bounds) - 1):
+                lo, hi = self.bounds[len(self.arrived)]
+                for v, fr in enumerate(self.srcs):
+                    a, b = max(lo, self.offs[v]), min(hi, self.offs[v + 1])
+                    if a < b:
+                        self.video[a:b].copy_(fr[a - self.offs[v]:b - self.offs[v]], non_blocking=True)
+                        self.h2d += 0 if fr.is_cuda else (b - a) * self.frame_bytes
+                ev = torch.cuda.Event()
+                ev.record(self.stream)
+                self.arrived.append(ev)
+
+    def all(self):
+        """Queue everything; -> the event after which the whole buffer is resident."""
+        self.through(len(self.bounds) - 1)
+        return self.arrived[-1]
+
+
 def wait(batch, stream=None):
     """Explicit mode of `prefetch`: make `stream` (default: the current one) wait for the batch's frames to have arrived."""
     slot = batch.get("_slot")
@@ -581,6 +622,8 @@ def prefetch(loader, device="cuda", key="frame", depth=3, auto=True):
 
     def start(batch):
         nonlocal ring
+        if "_slot" in batch:                 # a device-side loader (trainclips.ResidentClips): its batch is already on the
+            return dict(batch)               # device and brings its own arrival event / release holder
         fr = batch[key]
         if not isinstance(fr, torch.Tensor):
             fr = torch.as_tensor(np.asarray(fr))

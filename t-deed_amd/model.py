@@ -675,32 +675,16 @@ class TDEEDModel:
             base_dev, lenv_dev, seg_dev, coff_dev, first_dev = (tab_dev[cuts[i]:cuts[i + 1]] for i in range(1, 6))
             g = SimpleNamespace(nv=nv, lengths=lengths, seg_off=seg_off, max_len=max(lengths), seg_off_dev=seg_dev,
                                 first_init=first_dev.view(nv, K1), K1=K1)
-        h2d = 0
         srcs = [fr.contiguous() if not fr.is_cuda else fr.to(dev).contiguous() for fr in srcs]
         packed = group or not srcs[0].is_cuda
+        up = None
         if packed:
             # one buffer for all frames, filled in chunks of video_chunk_bytes on the copy stream (a chunk may span videos)
-            video = torch.empty((L,) + shape, dtype=torch.uint8, device=dev)
-            per = max(1, int(self.video_chunk_bytes) // fb)
-            bounds = [(lo, min(lo + per, L)) for lo in range(0, L, per)]
-            offs = np.concatenate([[0], np.cumsum(lengths)]).tolist()
-            arrived = []
-
-            def upload_through(c):
-                nonlocal h2d
-                with torch.cuda.stream(cp):
-                    while len(arrived) <= min(c, len(bounds) - 1):
-                        lo, hi = bounds[len(arrived)]
-                        for v, fr in enumerate(srcs):
-                            a, b = max(lo, offs[v]), min(hi, offs[v + 1])
-                            if a < b:
-                                video[a:b].copy_(fr[a - offs[v]:b - offs[v]], non_blocking=True)
-                                h2d += 0 if fr.is_cuda else (b - a) * fb
-                        ev = torch.cuda.Event()
-                        ev.record(cp)
-                        arrived.append(ev)
-            if all(fr.is_cuda or fr.is_pinned() for fr in srcs):
-                upload_through(len(bounds) - 1)       # asynchronous copies: queue all frames behind the first chunk
+            from . import feeder
+            up = feeder.PackedUpload(srcs, dev, cp, self.video_chunk_bytes)
+            video, per, arrived = up.video, up.per, up.arrived
+            if up.asynchronous:
+                up.all()                              # asynchronous copies: queue all frames behind the first chunk
         else:
             video = srcs[0]
         # ---- the batches: gather -> forward -> post-processing, two in flight
@@ -714,7 +698,7 @@ class TDEEDModel:
                 last = max(last_of[lo:lo + B])
                 if last >= 0:
                     c = last // per
-                    upload_through(c + 1)             # pageable frames: the copy call stages on the host, keep one chunk ahead
+                    up.through(c + 1)                 # pageable frames: the copy call stages on the host, keep one chunk ahead
                     need = arrived[c]
             with torch.cuda.stream(st):
                 st.wait_event(need)                   # a chunk's event follows the tables' on the copy stream
@@ -735,7 +719,7 @@ class TDEEDModel:
                                                              mean=want_mean)
             else:
                 track, support, mean = ops.stitch_scores(clip_scores, starts_dev, L, count_all=augment, mean=want_mean)
-        stats = dict(frames=L, clips=n, batches=n_batches, views=V, frames_h2d_bytes=h2d)
+        stats = dict(frames=L, clips=n, batches=n_batches, views=V, frames_h2d_bytes=up.h2d if up is not None else 0)
         if group:
             stats["videos"] = nv
         return track, support, mean, s0, stats, (video, srcs, clip_scores, tab_dev, tab_host), g
@@ -824,20 +808,25 @@ def _train_epoch_impl(self, loader, optimizer, lr_scheduler, acc_grad_iter, fg_w
             def u8(x):
                 x = x.to(self.device)
                 return (x if x.dtype == torch.uint8 else x.round().clamp_(0, 255).to(torch.uint8)).contiguous()
-            frame = u8(batch["frame"])
+            # trainclips.ResidentClips with mixup: the blend is deferred until lam is drawn, no uint8 clip is delivered
+            mix = batch.get("mix")
+            frame = u8(batch["frame"]) if mix is None else None
             label = batch["label"].to(self.device)
             labelD = batch["labelD"].to(self.device).float() if "labelD" in batch else None
-            B, T = frame.shape[:2]
+            B, T = (frame if frame is not None else label).shape[:2]
             soft = None
             dataset = None
             if self._model._double_head:
                 dataset = torch.as_tensor(batch["dataset"]).to(self.device).long()
                 label = update_labels_2heads(label.clone(), dataset, self._args.num_classes)
-            if "frame2" in batch:
+            if "frame2" in batch or mix is not None:
                 from . import ops_bwd
                 K1 = self._num_classes                               # train_tdeed.py:148 widens it for the double head
                 lam = torch.tensor([random.betavariate(0.2, 0.2) for _ in range(B)], dtype=torch.float32, device=self.device)
-                frame = ops_bwd.mix_frames(frame, u8(batch["frame2"]), lam)          # fp32 0..255 frames
+                if mix is not None:
+                    frame = mix(lam)                                 # gather + blend in one launch, the same fp32 bits
+                else:
+                    frame = ops_bwd.mix_frames(frame, u8(batch["frame2"]), lam)      # fp32 0..255 frames
                 label2 = batch["label2"].to(self.device)
                 oh = torch.nn.functional.one_hot
                 soft = (lam.view(B, 1, 1) * oh(label, K1).float() + (1 - lam).view(B, 1, 1) * oh(label2, K1).float())

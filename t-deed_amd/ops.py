@@ -997,3 +997,77 @@ def sgp_gemm_gelu_chsum(A, Wp, bias, N, out, chs_out, form=None, out16=None):
     call("tdeed_sgp_gemm_gelu_chsum", ptr(A), B, T, K, ptr(Wp), ptr(bias), N, ptr(out), ptr(chs_out), ptr(out16),
          form[0] * 16 + form[1], dtype_code(out.dtype), stream_ptr())
     return out
+
+
+# ---- training clips drawn from resident videos (trainclips.hip; tables: trainclips.train_clip_table, int64 on the device)
+def _chk_clip_tables(frames_u8, tabs, who):
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() < 2:
+        raise TypeError(f"{who}: frames must be uint8 (L, ...)")
+    if not frames_u8.is_cuda or not frames_u8.is_contiguous():
+        raise ValueError(f"{who}: frames must be a contiguous GPU tensor")
+    if not tabs or not all(isinstance(tab, torch.Tensor) for tab in tabs):
+        raise ValueError(f"{who}: the clip tables must be tensors")
+    B = tabs[0].numel()
+    for tab in tabs:
+        if tab.dtype != torch.int64 or tab.dim() != 1 or tab.numel() != B or not tab.is_contiguous() \
+                or tab.device != frames_u8.device:
+            raise ValueError(f"{who}: the clip tables must be contiguous int64 ({B},) tensors on the frames' device")
+    return B, int(frames_u8.shape[0]), int(frames_u8[0].numel())
+
+
+def train_clip_gather(frames_u8, first, base, nframes, T, stride, out):
+    """out[b*T + t] = frames_u8[first[b] + base[b] + t*stride] when 0 <= base[b] + t*stride < nframes[b], a zero frame
+    otherwise.  frames_u8: the packed frames of all resident videos (sum L, ...); first / base / nframes: int64 (B,) on the
+    device (first packed frame and length of the clip's video, the clip's first original frame)."""
+    B, L, fb = _chk_clip_tables(frames_u8, (first, base, nframes), "train_clip_gather")
+    if out.dtype != torch.uint8 or not out.is_contiguous() or out.device != frames_u8.device:
+        raise TypeError("train_clip_gather: out must be a contiguous uint8 tensor on the frames' device")
+    if out.numel() != B * T * fb:
+        raise ValueError(f"train_clip_gather: out holds {out.numel()} bytes, {B} clips of {T} frames need {B * T * fb}")
+    call("tdeed_train_clip_gather_u8", ptr(frames_u8), L, fb, ptr(first), ptr(base), ptr(nframes), B, T, stride, ptr(out),
+         stream_ptr())
+    return out
+
+
+def train_clip_gather_mix(frames_u8, tabs_a, tabs_b, lam, T, stride, out=None):
+    """fp32 (B,T,...) = lam[b] * A[b] + (1 - lam[b]) * B[b] with A / B the windows train_clip_gather would write for the
+    table triples tabs_a / tabs_b = (first, base, nframes): the bits of ops_bwd.mix_frames on those two batches, which are
+    never materialised.  lam: fp32 (B,) on the device."""
+    if not isinstance(tabs_a, (tuple, list)) or not isinstance(tabs_b, (tuple, list)) or len(tabs_a) != 3 or len(tabs_b) != 3:
+        raise ValueError("train_clip_gather_mix: (first, base, nframes) per operand")
+    B, L, fb = _chk_clip_tables(frames_u8, tuple(tabs_a) + tuple(tabs_b), "train_clip_gather_mix")
+    if lam.dtype != torch.float32 or lam.numel() != B or not lam.is_contiguous() or lam.device != frames_u8.device:
+        raise ValueError(f"train_clip_gather_mix: lam must be a contiguous fp32 ({B},) tensor on the frames' device")
+    if out is None:
+        out = torch.empty((B, T) + tuple(frames_u8.shape[1:]), dtype=torch.float32, device=frames_u8.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * T * fb or out.device != frames_u8.device:
+        raise ValueError(f"train_clip_gather_mix: out must be a contiguous fp32 tensor of {B * T * fb} elements")
+    call("tdeed_train_clip_gather_mix_f32", ptr(frames_u8), L, fb, *(ptr(x) for x in tabs_a), *(ptr(x) for x in tabs_b),
+         ptr(lam), B, T, stride, ptr(out), stream_ptr())
+    return out
+
+
+def clip_labels(clip_video, clip_base, T, stride, r, ev_off, ev_frame, ev_class, label=None, labelD=None, displ=True):
+    """Per-frame labels of n clips from their videos' event lists (trainclips.rasterise_labels on the device): clip_video /
+    clip_base int64 (n,), ev_off int32 (nv+1,), ev_frame / ev_class int32 (n_events,), all on the device.
+    -> (label int64 (n,T), labelD int64 (n,T) or None when displ is False)."""
+    dev = clip_video.device
+    n = clip_video.numel()
+    for tab, dt, what in ((clip_video, torch.int64, "clip_video"), (clip_base, torch.int64, "clip_base"),
+                          (ev_off, torch.int32, "ev_off"), (ev_frame, torch.int32, "ev_frame"), (ev_class, torch.int32, "ev_class")):
+        if not isinstance(tab, torch.Tensor) or tab.dtype != dt or tab.dim() != 1 or not tab.is_contiguous() \
+                or not tab.is_cuda or tab.device != dev:
+            raise ValueError(f"clip_labels: {what} must be a contiguous 1-d {dt} GPU tensor")
+    if clip_base.numel() != n or ev_class.numel() != ev_frame.numel() or ev_off.numel() < 2:
+        raise ValueError("clip_labels: table lengths do not match")
+    if label is None:
+        label = torch.empty((n, T), dtype=torch.int64, device=dev)
+    if labelD is None and displ:
+        labelD = torch.empty((n, T), dtype=torch.int64, device=dev)
+    for o in (label, labelD):
+        if o is not None and (o.dtype != torch.int64 or not o.is_contiguous() or o.numel() != n * T or o.device != dev):
+            raise ValueError(f"clip_labels: outputs must be contiguous int64 ({n},{T}) tensors")
+    ne = ev_frame.numel()
+    call("tdeed_clip_labels", ptr(clip_video), ptr(clip_base), n, T, stride, r, ptr(ev_off), ptr(ev_frame) if ne else None,
+         ptr(ev_class) if ne else None, ev_off.numel() - 1, ne, ptr(label), ptr(labelD), stream_ptr())
+    return label, labelD

@@ -1,0 +1,179 @@
+"""Feeding the training step: clips drawn from resident videos against clips decoded from JPEG, in ONE process.
+
+    python tools/bench_train_feed.py [--videos 4] [--frames 300] [--clips 96] [--procs 16]     one JSON record, printed
+                                                                                               and written to profiles/train_feed.json
+
+Synthetic JPEG videos (224 x 224, quality 90) are written to a temporary directory with a label file.  Measured:
+  loader   clips/s of `trainclips.ResidentClips` alone (T = 100, batch 8), without mixup (the uint8 batch) and with it (labels
+           of both clips + the deferred gather-and-blend with Beta(0.2, 0.2) weights), after the one-off decode of every frame;
+  epoch    clips/s of a RegNetY-200MF training epoch (`TDEEDModel.epoch`, bf16, mixup as train_tdeed.py trains) fed
+           A  by `feeder.clip_batches` + `ProcessDecodePool(--procs)`: the same clips decoded from JPEG per draw, two per item,
+           B  by `ResidentClips`;
+           one warm-up epoch each, then `--repeats` timed epochs, alternating; every round draws new clips, the same ones on
+           both routes."""
+import argparse
+import json
+import os
+import random
+import shutil
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import tdeed_amd  # noqa: E402,F401
+from tdeed_amd import synth, state_layout, feeder  # noqa: E402
+from tdeed_amd import trainclips as TC  # noqa: E402
+
+CFG = dict(feature_arch="rny002_gsf", clip_len=100, crop_dim=224, n_layers=2, sgp_ks=7, sgp_r=4, num_classes=4,
+           radi_displacement=2)
+H = W = 224
+CLASSES = {"a": 1, "b": 2, "c": 3, "d": 4}
+DATASET = "fs_comp"                                  # frame_dir/<video>/frame<N>.jpg
+
+
+def write_videos(root, n_videos, n_frames):
+    from PIL import Image
+    rs = np.random.RandomState(0)
+    videos = []
+    for v in range(n_videos):
+        name = f"video{v:02d}"
+        os.makedirs(os.path.join(root, name))
+        base = rs.randint(0, 256, (H // 8, W // 8, 3), dtype=np.uint8)        # blocky content: ~10-20 KB per frame
+        for i in range(n_frames):
+            img = np.kron(np.roll(base, i, axis=1), np.ones((8, 8, 1), dtype=np.uint8))
+            img = (img.astype(np.int16) + rs.randint(-12, 13, img.shape)).clip(0, 255).astype(np.uint8)
+            Image.fromarray(img).save(os.path.join(root, name, f"frame{i}.jpg"), quality=90)
+        frames = sorted(rs.choice(n_frames, size=max(1, n_frames // 25), replace=False).tolist())
+        videos.append(dict(video=name, num_frames=n_frames,
+                           events=[dict(frame=int(f), label=list(CLASSES)[int(rs.randint(0, 4))]) for f in frames]))
+    return videos
+
+
+def decoded_loader(root, videos, pool, mixup, dataset_len, batch_size, seed):
+    """The reference's route on the same draws: every drawn clip decoded from its JPEGs (`feeder.load_paths` ->
+    `feeder.clip_batches`), two clips per item with mixup; labels from the host rule."""
+    T, r = CFG["clip_len"], CFG["radi_displacement"]
+    tab = TC.train_clip_table(videos, CLASSES, T)
+    draws = list(TC.ClipDraws(len(tab.clip_video), dataset_len, batch_size, mixup, seed, drop_last=True))
+
+    def descr(ids):
+        return [dict(paths=feeder.load_paths(root, DATASET, videos[int(tab.clip_video[c])]["video"], int(tab.clip_base[c]),
+                                             int(tab.clip_base[c]) + T, stride=1), stride=1) for c in ids]
+    # (the pool hands out its staging slots per (depth, shape): the partner stream asks for another depth to get its own)
+    streams = [feeder.clip_batches(descr(np.concatenate([d[k] for d in draws])), batch_size, (3, H, W), T, pool=pool, depth=3 + k)
+               for k in range(2 if mixup else 1)]
+    for (ia, ib), *got in zip(draws, *streams):
+        lab, labD = TC.rasterise_labels(tab, ia, T, 1, r)
+        b = dict(frame=got[0]["frame"], _src=got[0]["_src"], label=torch.from_numpy(lab), labelD=torch.from_numpy(labD))
+        if mixup:
+            lab2, labD2 = TC.rasterise_labels(tab, ib, T, 1, r)
+            b.update(frame2=got[1]["frame"], label2=torch.from_numpy(lab2), labelD2=torch.from_numpy(labD2))
+        yield b
+
+
+def _rate(times, clips):
+    t = np.asarray(times)
+    return dict(clips_per_s=round(clips / float(np.median(t)), 1), clips_per_s_min=round(clips / float(t.max()), 1),
+                clips_per_s_max=round(clips / float(t.min()), 1), s_median=round(float(np.median(t)), 3))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--videos", type=int, default=4)
+    ap.add_argument("--frames", type=int, default=300)
+    ap.add_argument("--clips", type=int, default=96, help="clips per epoch (dataset_len)")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--procs", type=int, default=16)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_feed.json"))
+    a = ap.parse_args()
+    from tdeed_amd.model import TDEEDModel
+    from types import SimpleNamespace
+    T, r, bs = CFG["clip_len"], CFG["radi_displacement"], a.batch
+    root = tempfile.mkdtemp(prefix="tdeed_train_feed_")
+    out = dict(kind="train_feed", cfg=CFG, videos=a.videos, frames_per_video=a.frames, clips_per_epoch=a.clips, batch_size=bs,
+               decode_processes=a.procs, repeats=a.repeats)
+    pool = None
+    try:
+        videos = write_videos(root, a.videos, a.frames)
+        threads = feeder.DecodePool(a.procs)
+        t0 = time.perf_counter()
+        frames = TC.load_resident_videos(root, DATASET, videos, pool=threads)
+        out["decode_once_s"] = round(time.perf_counter() - t0, 3)
+        out["decode_once_frames_per_s"] = round(a.videos * a.frames / (time.perf_counter() - t0), 1)
+        threads.close()
+        common = dict(clip_len=T, radi_displacement=r, batch_size=bs, drop_last=True, device="cuda")
+
+        # ---- the loader alone
+        out["loader"] = {}
+        for mixup in (False, True):
+            n = 64 * bs
+            ld = TC.ResidentClips(videos, frames, CLASSES, mixup=mixup, dataset_len=n, seed=1, **common)
+            times = []
+            for rep in range(a.repeats + 1):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for b in feeder.prefetch(ld, "cuda"):
+                    if mixup:
+                        lam = torch.tensor([random.betavariate(0.2, 0.2) for _ in range(bs)], dtype=torch.float32, device="cuda")
+                        b["mix"](lam)
+                torch.cuda.synchronize()
+                if rep:
+                    times.append(time.perf_counter() - t0)
+            out["loader"]["mixup" if mixup else "plain"] = _rate(times, n)
+            del ld
+
+        # ---- a training epoch fed by either route
+        m = TDEEDModel(device="cuda", args=SimpleNamespace(modality="rgb", temporal_arch="ed_sgp_mixer", pretrain=None, **CFG))
+        m.load({k: torch.from_numpy(v) for k, v in synth.make_state(state_layout.model_state_shapes(CFG), 0).items()})
+        opt, _ = m.get_optimizer({"lr": 1e-4})
+        pool = feeder.ProcessDecodePool(a.procs)
+        # both routes draw the SAME clips in every round: a fresh draw stream from seed 2 + round per epoch and route
+        resident = TC.ResidentClips(videos, frames, CLASSES, mixup=True, dataset_len=a.clips, seed=2, **common)
+        rnd = {"i": 0}
+
+        def route_b():
+            resident.reseed(2 + rnd["i"])
+            return resident
+        routes = dict(A_decoded=lambda: decoded_loader(root, videos, pool, True, a.clips, bs, 2 + rnd["i"]), B_resident=route_b)
+        times = {k: [] for k in routes}
+        losses = {}
+        for rep in range(a.repeats + 1):
+            rnd["i"] = rep
+            for k, mk in routes.items():                                     # alternating; the first round warms up
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                losses[k] = m.epoch(mk(), optimizer=opt)
+                torch.cuda.synchronize()
+                if rep:
+                    times[k].append(time.perf_counter() - t0)
+        n_epoch = a.clips // bs * bs
+        out["epoch"] = {k: dict(_rate(v, n_epoch), last_loss=round(float(losses[k]), 5)) for k, v in times.items()}
+        ra, rb = out["epoch"]["A_decoded"], out["epoch"]["B_resident"]
+        out["epoch"]["speedup_B_over_A"] = round(rb["clips_per_s"] / ra["clips_per_s"], 3)
+        out["epoch"]["B_not_slower_than_A"] = bool(rb["clips_per_s"] >= ra["clips_per_s_min"])
+        out["epoch"]["notes"] = [
+            "every round draws new clips (seed 2 + round), the same for both routes; the JPEG files themselves stay in the "
+            "page cache, so route A pays decode, not disk",
+            "route B's one-off cost -- the JPEG decode of every frame (decode_once_s) and the upload -- is not in its epochs",
+            "route A's mixup partner clip ('frame2') is uploaded by epoch()'s blocking copy, not by the prefetch ring: that is "
+            "how epoch() treats any host loader today, and it counts against route A"]
+    finally:
+        if pool is not None:
+            pool.close()
+        shutil.rmtree(root, ignore_errors=True)
+    line = json.dumps(out)
+    print(line)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as fh:
+        fh.write(line + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

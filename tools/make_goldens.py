@@ -469,6 +469,76 @@ def video_clips(name="video_clips"):
     save(name, dict(kind="video_clips", lengths=lengths, names=[f"v{n:05d}" for n in lengths], cases=cases), **arrays)
 
 
+def train_clips(name="train_clips"):
+    """The reference's TRAINING dataset (dataset/frame.py:30-256 ActionSpotDataset, store_mode='store') on a temporary label
+    file and frame directories of tiny JPEGs: per case the clip list (video, base_idx) of `_store_clips` and, after
+    `random.seed(s)`, the label / labelD / label2 / labelD2 rows of the first 12 `__getitem__` calls (the reference's own
+    `_get_one`, frames decoded and thrown away).  Dataset names other than soccernet / soccernetball.  The events hold two
+    of different classes closer than 2r (overwrite order), events within r of frame 0 and of the last frame, events before
+    a clip's base (negative numerator of the floor division) and events at frames that are no multiple of the stride."""
+    import random
+    import tempfile
+    from PIL import Image
+    import dataset.frame as rframe
+    classes = {"dive": 1, "turn": 2, "land": 3}
+    ev = lambda *pairs: [dict(frame=f, label=l) for f, l in pairs]     # noqa: E731
+    videos = [
+        dict(video="v00003", num_frames=3, events=ev((1, "dive"))),
+        dict(video="v00006", num_frames=6, events=ev((0, "turn"), (5, "land"))),
+        dict(video="v00007", num_frames=7, events=ev((3, "land"), (4, "dive"))),
+        dict(video="v00037", num_frames=37, events=ev((0, "dive"), (1, "turn"), (17, "land"), (19, "dive"), (35, "land"),
+                                                      (36, "turn"))),
+        dict(video="v00101", num_frames=101, events=ev((2, "turn"), (53, "land"), (50, "dive"), (99, "dive"), (100, "turn"))),
+        dict(video="v00430", num_frames=430, events=ev((1, "land"), (7, "dive"), (100, "turn"), (103, "land"), (215, "dive"),
+                                                       (301, "turn"), (300, "land"), (427, "dive"), (429, "turn"))),
+    ]
+    settings = [  # (clip_len, stride, overlap, radi_displacement, mixup, dataset, seed)
+        (8, 1, 1, 0, True, "fs_comp", 11), (8, 1, 1, 2, True, "fs_comp", 12), (8, 2, 1, 2, True, "fs_perf", 13),
+        (8, 3, 0.5, 1, True, "fs_comp", 14), (100, 1, 1, 4, True, "fs_perf", 15), (100, 12, 1, 2, True, "fs_comp", 16),
+        (8, 1, 1, 2, False, "fs_comp", 17),
+    ]
+    n_items = 12
+    arrays, cases = {}, []
+    with tempfile.TemporaryDirectory() as tmp:
+        for v in videos:
+            d = os.path.join(tmp, "frames", v["video"])
+            os.makedirs(d)
+            for i in range(v["num_frames"]):
+                Image.fromarray(synth.uint8_clip(700 + i, (8, 8, 3))).save(os.path.join(d, f"frame{i}.jpg"), quality=90)
+        lf = os.path.join(tmp, "train.json")
+        with open(lf, "w") as fh:
+            json.dump(videos, fh)
+        names = [v["video"] for v in videos]
+        for ci, (clip_len, stride, overlap, radi, mixup, ds, seed) in enumerate(settings):
+            d = rframe.ActionSpotDataset(classes, lf, os.path.join(tmp, "frames"), os.path.join(tmp, f"store{ci}"), "store", "rgb",
+                                         clip_len, n_items, stride=stride, overlap=overlap, radi_displacement=radi, mixup=mixup,
+                                         dataset=ds)
+            # the clip list: _frame_paths holds [base_path, found_start, pad_start, pad_end, ndigits, length] per kept clip;
+            # base_idx is recovered by replaying the reference's own range and its keep rule on its own load_paths
+            kept_video, kept_base = [], []
+            k = 0
+            for vi, v in enumerate(videos):
+                for base_idx in range(-d._pad_len * d._stride, max(0, v["num_frames"] - 1 + (2 * d._pad_len - d._clip_len) * d._stride),
+                                      d._overlap):
+                    paths = d._frame_reader.load_paths(v["video"], base_idx, base_idx + d._clip_len * d._stride, stride=d._stride)
+                    if paths[1] != -1:
+                        assert d._frame_paths[k] == paths, (ci, vi, base_idx)
+                        kept_video.append(vi)
+                        kept_base.append(base_idx)
+                        k += 1
+            assert k == len(d._frame_paths) == d._total_len
+            arrays[f"clip_video__{ci}"] = np.array(kept_video, np.int32)
+            arrays[f"clip_base__{ci}"] = np.array(kept_base, np.int64)
+            random.seed(seed)
+            items = [d[i] for i in range(n_items)]
+            keys = ["label"] + (["labelD"] if radi > 0 else []) + ((["label2"] + (["labelD2"] if radi > 0 else [])) if mixup else [])
+            for key in keys:
+                arrays[f"{key}__{ci}"] = np.stack([it[key] for it in items]).astype(np.int64)
+            cases.append(dict(clip_len=clip_len, stride=stride, overlap=overlap, radi_displacement=radi, mixup=mixup, dataset=ds,
+                              seed=seed, pad_len=rframe.DEFAULT_PAD_LEN, n_clips=int(d._total_len), keys=keys))
+    save(name, dict(kind="train_clips", classes=classes, videos=videos, names=names, n_items=n_items, cases=cases), **arrays)
+
+
 # ----------------------------------------------------------------------------- training (VERDICT r4 item 3; SURVEY 8c)
 TRAIN_KEYS = [
     "_features.stem.conv.weight", "_features.stem.bn.weight", "_features.s1.b1.downsample.conv.weight",
@@ -666,6 +736,7 @@ CASES = {
     "snb_t250": lambda: full_model("snb_t250", CFG_SNB, 1, 160, 160),
     "train_step_tiny_rny002": lambda: train_step("train_step_tiny_rny002"),
     "train_epoch_tiny_rny002": lambda: train_epoch("train_epoch_tiny_rny002"),
+    "train_clips": train_clips,
 }
 
 
