@@ -452,6 +452,16 @@ int tdeed_nms_track(const float* mean, int L, int K1, float hr_threshold, double
  * window is cut at the ends of the clip's OWN video.  Forms and limits of tdeed_clip_gather_u8. */
 int tdeed_clip_gather_seg_u8(const uint8_t* video, int L_total, long frame_bytes, const int* starts, const int* clip_base,
                              const int* clip_len_v, int B, int T, uint8_t* clips_out, void* stream);
+/* Clip windows of per-frame ROWS: maps [rows][row_bytes] resident on the device (any element type; the trunk map of every
+ * frame, computed once), of which the first L (L_total) rows are the frames of the video (the packed group).  out[b][t] =
+ * maps[starts[b] + t] when that frame lies inside its video -- 0 <= starts[b] + t < L, or < clip_len_v[b] with the row offset
+ * by clip_base[b] in the segmented form, exactly the windows of tdeed_clip_gather_u8 / _seg_u8 -- and maps[pad_row] otherwise
+ * (the row of a black frame: its map is not zero).  L <= rows, 0 <= pad_row < rows.  16-byte accesses when row_bytes % 16 == 0
+ * and both buffers are 16-byte aligned, a byte path otherwise.  B * T <= 65535. */
+int tdeed_rows_gather(const void* maps, int rows, long row_bytes, int L, int pad_row, const int* starts, int B, int T, void* out,
+                      void* stream);
+int tdeed_rows_gather_seg(const void* maps, int rows, long row_bytes, int L_total, int pad_row, const int* starts,
+                          const int* clip_base, const int* clip_len_v, int B, int T, void* out, void* stream);
 /* tdeed_stitch_scores per video: one thread per packed frame walks only the clips clip_off[v] .. clip_off[v+1]-1 of its
  * video, in the order given, views inner -- per frame the additions of tdeed_stitch_scores on that video alone (same bits).
  * track_sum [L_total][K1], support [L_total] (accumulated onto), mean_out [L_total][K1] or NULL. */

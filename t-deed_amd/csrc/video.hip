@@ -86,6 +86,76 @@ extern "C" int tdeed_clip_gather_seg_u8(const uint8_t* video, int L_total, long 
   return clip_gather_launch<true>(video, L_total, frame_bytes, starts, clip_base, clip_len_v, B, T, clips_out, stream);
 }
 
+// =========================================================================== row gather (per-frame trunk maps)
+// out[b][t] = maps[starts[b] + t]: the clip gather over a resident buffer of per-frame ROWS of any type (the trunk map of every
+// frame, computed once), with one difference: a frame outside its video copies row `pad_row` instead of zeros -- the map of
+// a black frame is not zero.  L (L_total for SEG) rows are frames, rows >= L belong to the caller (pad_row is one of them).
+template <bool SEG>
+__global__ __launch_bounds__(256) void rows_gather_v16_kernel(const u32x4* __restrict__ maps, int L, long chunks, int pad_row,
+                                                              const int* __restrict__ starts, const int* __restrict__ clip_base,
+                                                              const int* __restrict__ clip_len_v, int T,
+                                                              u32x4* __restrict__ out) {
+  const int slot = blockIdx.y;
+  const long f = clip_gather_source<SEG>(L, starts, clip_base, clip_len_v, T, slot);
+  const u32x4* src = maps + (f >= 0 ? f : (long)pad_row) * chunks;
+  u32x4* dst = out + (long)slot * chunks;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < chunks; i += (long)gridDim.x * 256) dst[i] = src[i];
+}
+
+// row sizes that are no multiple of 16 bytes (or unaligned buffers)
+template <bool SEG>
+__global__ __launch_bounds__(256) void rows_gather_u8_kernel(const uint8_t* __restrict__ maps, int L, long row_bytes, int pad_row,
+                                                             const int* __restrict__ starts, const int* __restrict__ clip_base,
+                                                             const int* __restrict__ clip_len_v, int T,
+                                                             uint8_t* __restrict__ out) {
+  const int slot = blockIdx.y;
+  const long f = clip_gather_source<SEG>(L, starts, clip_base, clip_len_v, T, slot);
+  const uint8_t* src = maps + (f >= 0 ? f : (long)pad_row) * row_bytes;
+  uint8_t* dst = out + (long)slot * row_bytes;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < row_bytes; i += (long)gridDim.x * 256) dst[i] = src[i];
+}
+
+template <bool SEG>
+static int rows_gather_launch(const uint8_t* maps, int L, long row_bytes, int pad_row, const int* starts, const int* clip_base,
+                              const int* clip_len_v, int B, int T, uint8_t* out, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const bool v16 = row_bytes % 16 == 0 && (((uintptr_t)maps | (uintptr_t)out) & 15) == 0;
+  if (v16) {
+    const long chunks = row_bytes / 16;
+    const int gx = (int)(cdiv(chunks, 256 * 4) < 64 ? cdiv(chunks, 256 * 4) : 64);     // 4+ chunks per thread
+    hipLaunchKernelGGL(rows_gather_v16_kernel<SEG>, dim3(gx, B * T), dim3(256), 0, st, (const u32x4*)maps, L, chunks, pad_row,
+                       starts, clip_base, clip_len_v, T, (u32x4*)out);
+  } else {
+    const int gx = (int)(cdiv(row_bytes, 256 * 4) < 64 ? cdiv(row_bytes, 256 * 4) : 64);
+    hipLaunchKernelGGL(rows_gather_u8_kernel<SEG>, dim3(gx, B * T), dim3(256), 0, st, maps, L, row_bytes, pad_row, starts,
+                       clip_base, clip_len_v, T, out);
+  }
+  TD_LAUNCH_CHECK("rows_gather");
+  return TDEED_OK;
+}
+
+extern "C" int tdeed_rows_gather(const void* maps, int rows, long row_bytes, int L, int pad_row, const int* starts, int B, int T,
+                                 void* out, void* stream) {
+  TD_CHECK(maps && starts && out, "rows_gather: null pointer");
+  TD_CHECK(rows > 0 && row_bytes > 0 && L > 0 && B > 0 && T > 0, "rows_gather: bad sizes");
+  TD_CHECK(L <= rows && pad_row >= 0 && pad_row < rows, "rows_gather: L=%d frames and pad_row=%d must lie inside the %d rows", L,
+           pad_row, rows);
+  TD_CHECK((long)B * T <= 65535, "rows_gather: B*T=%ld row slots exceed the grid's 65535", (long)B * T);
+  return rows_gather_launch<false>((const uint8_t*)maps, L, row_bytes, pad_row, starts, nullptr, nullptr, B, T, (uint8_t*)out,
+                                   stream);
+}
+
+extern "C" int tdeed_rows_gather_seg(const void* maps, int rows, long row_bytes, int L_total, int pad_row, const int* starts,
+                                     const int* clip_base, const int* clip_len_v, int B, int T, void* out, void* stream) {
+  TD_CHECK(maps && starts && clip_base && clip_len_v && out, "rows_gather_seg: null pointer");
+  TD_CHECK(rows > 0 && row_bytes > 0 && L_total > 0 && B > 0 && T > 0, "rows_gather_seg: bad sizes");
+  TD_CHECK(L_total <= rows && pad_row >= 0 && pad_row < rows,
+           "rows_gather_seg: L_total=%d frames and pad_row=%d must lie inside the %d rows", L_total, pad_row, rows);
+  TD_CHECK((long)B * T <= 65535, "rows_gather_seg: B*T=%ld row slots exceed the grid's 65535", (long)B * T);
+  return rows_gather_launch<true>((const uint8_t*)maps, L_total, row_bytes, pad_row, starts, clip_base, clip_len_v, B, T,
+                                  (uint8_t*)out, stream);
+}
+
 // =========================================================================== score stitching
 // Device twin of evalutil.ScoreStitcher (add / add_views / normalised).  One thread owns one video frame: it walks the
 // clips in the order given and, per covering clip, adds the views one after the other -- the same sequence of fp32

@@ -17,7 +17,7 @@ import torch
 
 from . import ops, _lib
 from .streams import new_stream
-from .regnet_spec import regnet_spec, sgp_up_size, pyramid_lengths
+from .regnet_spec import regnet_spec, sgp_up_size, pyramid_lengths, first_site_block
 # the weight layouts (also importable from here, where they used to live)
 from .packing import (_np, _f32, _dense, pack_ws_weights, pack_se_bf16, pack_mfma_frags, pack_se_mfma,  # noqa: F401
                       pack_front_weights, _stem_frags_np, gs_source_order_columns, _gsf_q_frags_np, pack_gsf_q_frags,
@@ -642,6 +642,7 @@ class ForwardEngine:
         # where the sub-batch pipelines join inside the trunk (index into the block list; None = behind the last block)
         self.join_at = None
         self._plans = {}
+        self._frame_starts = {}
 
     # ------------------------------------------------------------------ plan construction
     def _se_conv3(self, bw, N, h2, w2, y2, pooled, gate, sc, out, out2=None, sc_from=None):
@@ -908,6 +909,15 @@ class ForwardEngine:
         return SimpleNamespace(frames=frames, steps=steps, keep=keep, head_out=head_out,
                                pool_bytes=pool.total_bytes(), B=B, T=T)
 
+    def _map_geometry(self, k, H, W):
+        """(h, w, channels) of the map that block k reads, for H x W frames (centre crop included)."""
+        ch = self.crop_dim if (self.crop_dim and self.crop_dim > 0) else H
+        cw = self.crop_dim if (self.crop_dim and self.crop_dim > 0) else W
+        hh, ww = (ch + 1) // 2, (cw + 1) // 2
+        for b_ in self.pw.W.blocks[:k]:
+            hh, ww = (hh - 1) // b_.spec.stride + 1, (ww - 1) // b_.spec.stride + 1
+        return hh, ww, self.pw.W.blocks[k - 1].spec.cout
+
     def plan(self, B, H, W, flip=False, taps=(), slot=0):
         """Launch plan for a batch geometry.  With n_split > 1 (and no taps) the batch is cut into n_split
         sub-batches of whole clips, each with its own buffers and its own HIP stream: two half-batch
@@ -925,7 +935,7 @@ class ForwardEngine:
             Bs = B // ns
             T = self.pw.clip_len
             head_out = torch.empty((B * T, self.pw.n_out), dtype=torch.float32, device=self.device)
-            tail = None
+            tail = trunk_map = None
             if self.merge_tail:
                 feat = torch.empty((B, T, self.pw.spec.feat_dim), dtype=sgp_stream_dtype(self.act_dtype, self.device),
                                    device=self.device)
@@ -933,13 +943,8 @@ class ForwardEngine:
                 if k is not None and 0 < k < len(self.pw.W.blocks):
                     # the sub-batches split only the bandwidth-bound head of the trunk (blocks [0, k)); the latency-bound
                     # small maps behind it run once for the whole batch, like the temporal stage
-                    blk = self.pw.W.blocks[k - 1].spec
-                    ch = self.crop_dim if (self.crop_dim and self.crop_dim > 0) else H
-                    cw = self.crop_dim if (self.crop_dim and self.crop_dim > 0) else W
-                    hh, ww = (ch + 1) // 2, (cw + 1) // 2
-                    for b_ in self.pw.W.blocks[:k]:
-                        hh, ww = (hh - 1) // b_.spec.stride + 1, (ww - 1) // b_.spec.stride + 1
-                    shared = torch.empty((B * T, hh, ww, blk.cout), dtype=self.act_dtype, device=self.device)
+                    hh, ww, cc = self._map_geometry(k, H, W)
+                    shared = trunk_map = torch.empty((B * T, hh, ww, cc), dtype=self.act_dtype, device=self.device)
                     subs = [self._build(Bs, H, W, bool(flip), set(), stop_at=k,
                                         trunk_out=shared[i * Bs * T:(i + 1) * Bs * T]) for i in range(ns)]
                     tail = self._build_tail(B, feat, head_out, trunk_in=(shared, hh, ww), start=k)
@@ -958,7 +963,8 @@ class ForwardEngine:
             plan = SimpleNamespace(subs=subs, streams=[None] + forks,
                                    head_out=head_out, keep=subs[0].keep, graph=None, tail=tail,
                                    steps=[st for sb in subs for st in sb.steps] + (tail.steps if tail else []),
-                                   pool_bytes=sum(sb.pool_bytes for sb in subs) + (tail.pool_bytes if tail else 0), B=B, T=T)
+                                   pool_bytes=sum(sb.pool_bytes for sb in subs) + (tail.pool_bytes if tail else 0), B=B, T=T,
+                                   trunk_map=trunk_map)       # (the block-join_at input of all B clips, None without a trunk join)
         self._plans[key] = plan
         return plan
 
@@ -1075,6 +1081,97 @@ class ForwardEngine:
                 ops.clip_gather(video_u8, starts_dev[part], self.pw.clip_len, sb.frames)
             else:
                 ops.clip_gather_seg(video_u8, starts_dev[part], clip_base[part], clip_len_v[part], self.pw.clip_len, sb.frames)
+        self.run_plan(plan)
+        return plan.head_out, plan
+
+    # ------------------------------------------------------------------ whole videos: the per-frame trunk stages once per frame
+    def first_site_block(self):
+        """Index k of the first block with a gate-shift site: the stem and the blocks [0, k) are functions of one frame."""
+        return first_site_block(self.pw.spec)
+
+    def _reuse_k(self):
+        k = self.first_site_block()
+        if not 0 < k < len(self.pw.W.blocks):
+            raise ValueError(f"frame reuse needs a gate-shift site behind the first block ({self.pw.arch}: k = {k})")
+        return k
+
+    def frame_map_shape(self, H, W):
+        """(h, w, C) of one frame's row of the resident map: the input of block first_site_block()."""
+        return self._map_geometry(self._reuse_k(), H, W)
+
+    def frame_plan(self, Bf, H, W, flip=False):
+        """Plan of the per-frame head of the trunk -- stem and blocks [0, k), k = first_site_block() -- for Bf * clip_len
+        consecutive FRAMES (no clip structure: nothing in front of block k mixes frames): plan.subs[0].frames is the input,
+        plan.out (Bf*T, h, w, C) the block-k input map of those frames.  The launches are those of a sub-batch of Bf clips of a
+        join_at = k plan.  Replays as a HIP graph through run_plan."""
+        key = ("frames", Bf, H, W, bool(flip))
+        if key in self._plans:
+            return self._plans[key]
+        k, T = self._reuse_k(), self.pw.clip_len
+        hh, ww, cc = self._map_geometry(k, H, W)
+        out = torch.empty((Bf * T, hh, ww, cc), dtype=self.act_dtype, device=self.device)
+        sub = self._build(Bf, H, W, bool(flip), set(), stop_at=k, trunk_out=out)
+        plan = SimpleNamespace(subs=[sub], streams=[None], head_out=None, keep=sub.keep, graph=None, tail=None, steps=sub.steps,
+                               pool_bytes=sub.pool_bytes, B=Bf, T=T, out=out, h=hh, w=ww)
+        self._plans[key] = plan
+        return plan
+
+    def tail_plan(self, B, h, w, slot=0):
+        """Plan of everything behind the per-frame head for B clips -- blocks [k:], pooling, SGP encoder-decoder, heads -- on a
+        fixed input buffer plan.trunk_in (B*T, h, w, C): the tail of a join_at = k plan.  One per slot; the flipped view needs
+        none of its own (the flip happens at the frames)."""
+        key = ("tail", B, h, w, slot)
+        if key in self._plans:
+            return self._plans[key]
+        k, T = self._reuse_k(), self.pw.clip_len
+        cc = self.pw.W.blocks[k - 1].spec.cout
+        buf = torch.empty((B * T, h, w, cc), dtype=self.act_dtype, device=self.device)
+        head_out = torch.empty((B * T, self.pw.n_out), dtype=torch.float32, device=self.device)
+        feat = torch.empty((B, T, self.pw.spec.feat_dim), dtype=sgp_stream_dtype(self.act_dtype, self.device), device=self.device)
+        tail = self._build_tail(B, feat, head_out, trunk_in=(buf, h, w), start=k)
+        plan = SimpleNamespace(subs=[tail], streams=[None], head_out=head_out, keep={}, graph=None, tail=None, steps=tail.steps,
+                               pool_bytes=tail.pool_bytes, B=B, T=T, trunk_in=buf)
+        self._plans[key] = plan
+        return plan
+
+    def frame_maps(self, video_u8, first_frame, maps_out, Bf, flip=False):
+        """Run the frame plan over the Bf * clip_len frames of video_u8 (L,3,H,W) from `first_frame` on (frames past the end
+        are black: ops.clip_gather's padding) and store their maps in maps_out (Bf*T, h, w, C), a slice of the resident map."""
+        T = self.pw.clip_len
+        _, _, H, W = video_u8.shape
+        plan = self.frame_plan(Bf, H, W, flip)
+        key = (Bf, int(first_frame))
+        starts = self._frame_starts.get(key)
+        if starts is None:             # (built once per chunk position: nothing is uploaded in the steady state)
+            starts = self._frame_starts[key] = torch.arange(int(first_frame), int(first_frame) + Bf * T, T, dtype=torch.int32,
+                                                            device=self.device)
+        ops.clip_gather(video_u8, starts, T, plan.subs[0].frames)
+        self.run_plan(plan)
+        maps_out.copy_(plan.out, non_blocking=True)
+        return plan
+
+    def forward_from_frame_maps(self, maps, starts_dev, pad_row, slot=0, clip_base=None, clip_len_v=None, n_frames=None):
+        """forward_from_video over the resident per-frame maps instead of the frames: maps (rows, h, w, C) in the activation
+        dtype, row f the block-k input map of frame f (frame_maps), rows >= n_frames (default: pad_row) those of black frames
+        and pad_row one of them; starts_dev int32 (B,) on the device, clip_base / clip_len_v as in forward_from_video.  The
+        windows are gathered into the tail plan's input (ops.rows_gather[_seg], launched in front of the replay) and the tail
+        runs.  Returns head_out (a view of the slot's buffer) and the plan."""
+        if (clip_base is None) != (clip_len_v is None):
+            raise ValueError("clip_base and clip_len_v go together")
+        if maps.dtype != self.act_dtype or maps.dim() != 4 or not maps.is_cuda:
+            raise TypeError(f"frame maps must be a {self.act_dtype} (rows,h,w,C) tensor on the device")
+        if starts_dev.dtype != torch.int32 or starts_dev.dim() != 1 or not starts_dev.is_cuda:
+            raise TypeError("clip starts must be an int32 (B,) tensor on the device")
+        B, T = starts_dev.numel(), self.pw.clip_len
+        _, h, w, cc = maps.shape
+        plan = self.tail_plan(B, h, w, slot)
+        if tuple(plan.trunk_in.shape[1:]) != (h, w, cc):
+            raise ValueError(f"frame maps of {(h, w, cc)}, block {self._reuse_k()} reads {tuple(plan.trunk_in.shape[1:])}")
+        L = int(pad_row if n_frames is None else n_frames)
+        if clip_base is None:
+            ops.rows_gather(maps, starts_dev, L, int(pad_row), T, plan.trunk_in)
+        else:
+            ops.rows_gather_seg(maps, starts_dev, clip_base, clip_len_v, L, int(pad_row), T, plan.trunk_in)
         self.run_plan(plan)
         return plan.head_out, plan
 

@@ -138,6 +138,34 @@ def group_clip_table(lengths, clip_len, overlap_len, pad_len=5, clip_starts=None
     return tuple(np.asarray(a, np.int32) for a in (seg_off, clip_off, starts, base, len_v))
 
 
+def frame_map_rows(L, clip_len, frame_batch):
+    """Row arithmetic of the per-frame trunk maps of a video (or packed group) of L frames (`predict_video(reuse_frames=
+    True)`): the frame pass runs chunks of frame_batch * clip_len consecutive frames, frames past the end black, and there is
+    always at least one black row -- the map that a padded frame of a clip window copies.  -> (rows, pad_row, chunk):
+    rows = ceil((L + 1) / chunk) * chunk, pad_row = L (the first black row), chunk = frame_batch * clip_len."""
+    L, chunk = int(L), int(frame_batch) * int(clip_len)
+    if L < 1 or chunk < 1:
+        raise ValueError(f"frame_map_rows: {L} frames in chunks of {chunk}")
+    return -(-(L + 1) // chunk) * chunk, L, chunk
+
+
+def rows_gather_ref(maps, starts, L, pad_row, T, clip_base=None, clip_len_v=None):
+    """numpy twin of ops.rows_gather / ops.rows_gather_seg: out[b, t] = maps[base[b] + starts[b] + t] when
+    0 <= starts[b] + t < len[b] (one video: base 0, len L), maps[pad_row] otherwise."""
+    if (clip_base is None) != (clip_len_v is None):
+        raise ValueError("rows_gather_ref: clip_base and clip_len_v go together")
+    maps = np.asarray(maps)
+    B = len(starts)
+    out = np.empty((B, T) + maps.shape[1:], maps.dtype)
+    for b in range(B):
+        base, lv = (0, int(L)) if clip_base is None else (int(clip_base[b]), int(clip_len_v[b]))
+        for t in range(T):
+            f = int(starts[b]) + t
+            ok = 0 <= f < lv and base >= 0 and base + f < int(L)
+            out[b, t] = maps[base + f if ok else pad_row]
+    return out
+
+
 def video_groups(lengths, frame_shapes, group_videos, max_resident_bytes):
     """Split consecutive videos, in the order given, into groups for `predict_video_group`: lists of indices.  A group closes
     when it holds `group_videos` videos, when the next video would push the frames of the group over `max_resident_bytes`,
@@ -203,7 +231,7 @@ def _decoded_groups(videos, group_videos, max_resident_bytes):
 
 
 def stitch_videos(model, videos, n_cols, augment=False, batch_size=8, overlap_len=None, decode_ahead=1, group_videos=1,
-                  max_resident_bytes=16 << 30):
+                  max_resident_bytes=16 << 30, reuse_frames=False):
     """Whole-video counterpart of `stitch_predictions`: `videos` yields (name, length, fps, frames) with frames a uint8
     (length,3,H,W) tensor of the sampled frames or a callable returning one (e.g. a `feeder.load_video` closure); every
     video goes through `model.predict_video` once and its (sums, support) become the video's track of the returned
@@ -212,14 +240,16 @@ def stitch_videos(model, videos, n_cols, augment=False, batch_size=8, overlap_le
     video v.
     group_videos > 1: up to that many consecutive videos (as far as `max_resident_bytes` and one frame geometry allow,
     `video_groups`) go through `model.predict_video_group` as one packed job whose batches are cut across the videos; the
-    callables of the next `group_videos` videos are decoded on the worker thread meanwhile."""
+    callables of the next `group_videos` videos are decoded on the worker thread meanwhile.
+    reuse_frames: passed on to `predict_video` / `predict_video_group` (the per-frame trunk stages once per frame)."""
     from concurrent.futures import ThreadPoolExecutor
     videos = list(videos)
+    reuse = dict(reuse_frames=True) if reuse_frames else {}
     st = ScoreStitcher([(v, n, f) for v, n, f, _ in videos], n_cols)
     if int(group_videos) > 1:
         for group in _decoded_groups(videos, group_videos, max_resident_bytes):
             out = model.predict_video_group([g[3] for g in group], overlap_len=overlap_len, batch_size=batch_size,
-                                            augment=augment, max_resident_bytes=max_resident_bytes)
+                                            augment=augment, max_resident_bytes=max_resident_bytes, **reuse)
             for (name, _, _, _), (sums, support) in zip(group, out):
                 if sums.shape[1] != n_cols:
                     raise ValueError(f"video {name}: the model scores {sums.shape[1]} columns, the stitcher holds {n_cols}")
@@ -243,7 +273,8 @@ def stitch_videos(model, videos, n_cols, augment=False, batch_size=8, overlap_le
             frames = src if fut is None else fut.result()
             if int(frames.shape[0]) != int(length):
                 raise ValueError(f"video {name}: {int(frames.shape[0])} frames delivered, {int(length)} announced")
-            sums, support = model.predict_video(frames, overlap_len=overlap_len, batch_size=batch_size, augment=augment)
+            sums, support = model.predict_video(frames, overlap_len=overlap_len, batch_size=batch_size, augment=augment,
+                                                      **reuse)
             if sums.shape[1] != n_cols:
                 raise ValueError(f"video {name}: the model scores {sums.shape[1]} columns, the stitcher holds {n_cols}")
             track, sup = st.tracks[name]
@@ -429,23 +460,26 @@ def event_dicts(frames, classes_idx, scores, inv):
 
 
 def spot_videos(model, videos, classes, suppress, high_recall_score_threshold=0.01, augment=False, batch_size=8,
-                overlap_len=None, decode_ahead=1, group_videos=1, max_resident_bytes=16 << 30):
+                overlap_len=None, decode_ahead=1, group_videos=1, max_resident_bytes=16 << 30, reuse_frames=False):
     """Whole-video counterpart of `stitch_videos` + `frame_events` + the two NMS functions with the tail on the device:
     `videos` as in `stitch_videos`; every video goes through `model.spot_video` once.  suppress: entries (kind, window,
     threshold) with kind "nms" | "snms".  Returns (pred_events, [one list of video records per suppress entry],
     {video: pred (L,) int32}), videos in sorted order, records as `frame_events` / `non_maximum_suppression` /
     `soft_non_maximum_suppression` build them ('num_events' included), so `mean_average_precisions` works on them
     unchanged.  The label-dependent error / F1 counters of `frame_events` follow from the returned pred on the host.
-    group_videos > 1: groups of videos go through `model.spot_video_group` as in `stitch_videos`."""
+    group_videos > 1: groups of videos go through `model.spot_video_group` as in `stitch_videos`.  reuse_frames: passed on
+    to `spot_video` / `spot_video_group`."""
     from concurrent.futures import ThreadPoolExecutor
     videos = list(videos)
+    reuse = dict(reuse_frames=True) if reuse_frames else {}
     suppress = [tuple(e) for e in suppress]
     done = {}
     if int(group_videos) > 1:
         for group in _decoded_groups(videos, group_videos, max_resident_bytes):
             out = model.spot_video_group([g[3] for g in group], classes, suppress=suppress,
                                          high_recall_score_threshold=high_recall_score_threshold, overlap_len=overlap_len,
-                                         batch_size=batch_size, augment=augment, max_resident_bytes=max_resident_bytes)
+                                         batch_size=batch_size, augment=augment, max_resident_bytes=max_resident_bytes,
+                                         **reuse)
             for (name, _, fps, _), r in zip(group, out):
                 done[name] = (fps, r)
     else:
@@ -467,7 +501,8 @@ def spot_videos(model, videos, classes, suppress, high_recall_score_threshold=0.
                     raise ValueError(f"video {name}: {int(frames.shape[0])} frames delivered, {int(length)} announced")
                 done[name] = (fps, model.spot_video(frames, classes, suppress=suppress,
                                                     high_recall_score_threshold=high_recall_score_threshold,
-                                                    overlap_len=overlap_len, batch_size=batch_size, augment=augment))
+                                                    overlap_len=overlap_len, batch_size=batch_size, augment=augment,
+                                                    **reuse))
     pred_events, lists, preds = [], [[] for _ in suppress], {}
     for name in sorted(done):
         fps, r = done[name]

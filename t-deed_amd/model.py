@@ -375,7 +375,7 @@ class TDEEDModel:
     video_chunk_bytes = 64 << 20        # upload granularity of predict_video (one arrival event per chunk)
 
     def predict_video(self, frames, clip_starts=None, overlap_len=None, pad_len=5, batch_size=8, augment=False, use_amp=True,
-                      max_resident_bytes=16 << 30):
+                      max_resident_bytes=16 << 30, reuse_frames=False):
         """Score a whole video from one resident frame buffer: what the prediction loop of `evaluate` (util/eval.py:284-349)
         leaves in its per-video track, -> (scores_sum (L,K+1) float32, support (L,) int32) numpy, i.e.
         `ScoreStitcher.tracks[video]`.
@@ -391,9 +391,19 @@ class TDEEDModel:
         batches alternate over two engine slots / streams like epoch()'s validation loop, the clip scores stay on the
         device and one stitch launch (ops.stitch_scores) adds them per frame in ScoreStitcher's order.  Apart from the
         warm-up of a geometry seen for the first time (graph capture) the host synchronises once per video.
-        Raises ValueError when the video does not fit `max_resident_bytes`."""
+        Raises ValueError when the video does not fit `max_resident_bytes`.
+
+        reuse_frames=True: the trunk stages in front of the first gate-shift site (stem and blocks [0, k), k =
+        `ForwardEngine.first_site_block()`; functions of one frame alone in eval mode) run ONCE per frame and view, in chunks
+        of `frame_batch` clips' worth of consecutive frames, into a resident map of the block-k inputs; a batch gathers its
+        windows from that map (ops.rows_gather, the row of a black frame as padding) and runs only the rest of the network
+        (`ForwardEngine.forward_from_frame_maps`).  The maps count towards `max_resident_bytes`; last_video_stats gains
+        frame_pass_frames (views x rows of the map) and map_bytes.  The launches are those of the engine's join_at = k
+        plan: same scores bit for bit where that plan would have served the batch (an even batch size), the first site's
+        launch form otherwise."""
         track, support, _, s0, stats, keep = self._video_track(frames, clip_starts, overlap_len, pad_len, batch_size, augment,
-                                                               use_amp, max_resident_bytes, want_mean=False)
+                                                               use_amp, max_resident_bytes, want_mean=False,
+                                                               reuse_frames=reuse_frames)
         L, K1 = track.shape
         with torch.cuda.stream(s0):
             out_sum = torch.empty((L, K1), dtype=torch.float32).pin_memory()
@@ -407,7 +417,7 @@ class TDEEDModel:
 
     def spot_video(self, frames, classes, suppress=(("nms", 1, 0.01), ("snms", 3, 0.01)), high_recall_score_threshold=0.01,
                    clip_starts=None, overlap_len=None, pad_len=5, batch_size=8, augment=False, use_amp=True,
-                   max_resident_bytes=16 << 30):
+                   max_resident_bytes=16 << 30, reuse_frames=False):
         """Score a whole video like predict_video and spot its events on the device: the tail of `evaluate`
         (util/eval.py:87-261, 386-391) -- `frame_events` and (soft) non-maximum suppression of the high-recall list -- without
         the (L,K+1) track ever leaving the device.  classes: name -> index (1-based); suppress: entries (kind, window,
@@ -432,7 +442,8 @@ class TDEEDModel:
         if sorted(inv) != list(range(1, K1)):
             raise ValueError(f"spot_video: classes must name the indices 1..{K1 - 1} of the model's score columns")
         track, _, mean, s0, stats, keep = self._video_track(frames, clip_starts, overlap_len, pad_len, batch_size, augment,
-                                                            use_amp, max_resident_bytes, want_mean=True)
+                                                            use_amp, max_resident_bytes, want_mean=True,
+                                                            reuse_frames=reuse_frames)
         L = track.shape[0]
         hr = float(high_recall_score_threshold)
         n = len(suppress)
@@ -474,7 +485,7 @@ class TDEEDModel:
         return dict(pred=pred_np, events=events, suppressed=suppressed)
 
     def predict_video_group(self, frames_list, clip_starts=None, overlap_len=None, pad_len=5, batch_size=8, augment=False,
-                            use_amp=True, max_resident_bytes=16 << 30):
+                            use_amp=True, max_resident_bytes=16 << 30, reuse_frames=False):
         """predict_video for a group of videos scored as one packed job -> [(scores_sum (L_v,K+1) float32, support (L_v,)
         int32)], per video what predict_video returns for the same batches.
 
@@ -490,7 +501,7 @@ class TDEEDModel:
         Raises ValueError for an empty list, an empty video, mixed geometries or a group over `max_resident_bytes`."""
         track, support, _, s0, stats, keep, g = self._packed_track(
             "predict_video_group", list(frames_list), clip_starts, overlap_len, pad_len, batch_size, augment, use_amp,
-            max_resident_bytes, want_mean=False, group=True)
+            max_resident_bytes, want_mean=False, group=True, reuse_frames=reuse_frames)
         L, K1 = track.shape
         with torch.cuda.stream(s0):
             out_sum = torch.empty((L, K1), dtype=torch.float32).pin_memory()
@@ -506,7 +517,7 @@ class TDEEDModel:
 
     def spot_video_group(self, frames_list, classes, suppress=(("nms", 1, 0.01), ("snms", 3, 0.01)),
                          high_recall_score_threshold=0.01, clip_starts=None, overlap_len=None, pad_len=5, batch_size=8,
-                         augment=False, use_amp=True, max_resident_bytes=16 << 30):
+                         augment=False, use_amp=True, max_resident_bytes=16 << 30, reuse_frames=False):
         """spot_video for a group of videos scored as one packed job (predict_video_group's pipeline) -> one spot_video
         dict per video.  On the packed track: one segmented event launch (ops.frame_events_seg), one suppression launch per
         entry of `suppress` with a workgroup per (class, video) (ops.nms_track_seg), whose compaction leaves the videos' event
@@ -526,7 +537,7 @@ class TDEEDModel:
             raise ValueError(f"spot_video_group: classes must name the indices 1..{K1 - 1} of the model's score columns")
         track, _, mean, s0, stats, keep, g = self._packed_track(
             "spot_video_group", list(frames_list), clip_starts, overlap_len, pad_len, batch_size, augment, use_amp,
-            max_resident_bytes, want_mean=True, group=True)
+            max_resident_bytes, want_mean=True, group=True, reuse_frames=reuse_frames)
         L, nv = track.shape[0], g.nv
         hr = float(high_recall_score_threshold)
         n = len(suppress)
@@ -580,21 +591,27 @@ class TDEEDModel:
         return out
 
     def _video_track(self, frames, clip_starts, overlap_len, pad_len, batch_size, augment, use_amp, max_resident_bytes,
-                     want_mean):
+                     want_mean, reuse_frames=False):
         """The body of predict_video up to and including the stitch launch, nothing synchronised: -> (track (L,K+1) fp32,
         support (L,) int32, mean (L,K+1) fp32 | None: device tensors written on stream s0; s0; the last_video_stats dict; the
         resident buffers, to be kept alive until s0 has been synchronised)."""
         return self._packed_track("predict_video", [frames], clip_starts, overlap_len, pad_len, batch_size, augment, use_amp,
-                                  max_resident_bytes, want_mean, group=False)[:6]
+                                  max_resident_bytes, want_mean, group=False, reuse_frames=reuse_frames)[:6]
+
+    frame_batch = 2                     # clips' worth of frames per launch of the per-frame pass (reuse_frames=True)
 
     def _packed_track(self, who, frames_list, clip_starts, overlap_len, pad_len, batch_size, augment, use_amp,
-                      max_resident_bytes, want_mean, group):
+                      max_resident_bytes, want_mean, group, reuse_frames=False):
         """One or several videos through upload, batches and the stitch launch, nothing synchronised.  group=False: one video,
         clip_starts its flat list (what `_video_track` returns, through ops.clip_gather / ops.stitch_scores).  group=True:
         the videos are packed one after the other into one resident buffer and one clip list (evalutil.group_clip_table,
         clip_starts one list per video), batches are cut from that list across the videos, the gathers and the stitch are
         the segmented kernels; track / support / mean cover the packed frames.  -> `_video_track`'s tuple plus a namespace
-        of the group's tables (None for group=False)."""
+        of the group's tables (None for group=False).
+        reuse_frames: the per-frame trunk stages run once per (packed) frame and view into a resident map, chunk by chunk on a
+        stream of their own with an event per chunk -- the chunk with the first black row (the padding of every window)
+        first, then in frame order; a batch waits for the chunk that holds its last frame and runs the rest of the network
+        on rows gathered from the map."""
         from types import SimpleNamespace
         from . import evalutil
         from .streams import new_stream
@@ -645,6 +662,15 @@ class TDEEDModel:
         pw = eng.pw
         K1 = self._score_cols(dt)
         dev = self.device
+        if reuse_frames:
+            Bf = int(self.frame_batch)
+            mh, mw, mc = eng.frame_map_shape(*shape[1:])
+            rows, pad_row, chunk = evalutil.frame_map_rows(L, T, Bf)
+            map_bytes = V * rows * mh * mw * mc * (2 if dt == torch.bfloat16 else 4)
+            if L * fb + map_bytes > max_resident_bytes:
+                raise ValueError(f"{who}: the {'group' if group else 'video'} needs {L * fb + map_bytes} bytes on the device "
+                                 f"({map_bytes} of them per-frame maps), more than max_resident_bytes={max_resident_bytes} "
+                                 "(a ring buffer for longer videos is not implemented)")
         if self._stream is None:
             self._stream = new_stream()
         if getattr(self, "_stream2", None) is None:
@@ -655,6 +681,10 @@ class TDEEDModel:
         cur = torch.cuda.current_stream()
         for st in streams + [cp]:
             st.wait_stream(cur)
+        if reuse_frames:
+            if getattr(self, "_frame_stream", None) is None:
+                self._frame_stream = new_stream(avoid=[self._stream, self._stream2, self._copy_stream])
+            self._frame_stream.wait_stream(cur)
         # ---- the resident buffers (kept alive until the one synchronisation at the end); the tables travel in one copy
         g = None
         if group:
@@ -687,6 +717,31 @@ class TDEEDModel:
                 up.all()                              # asynchronous copies: queue all frames behind the first chunk
         else:
             video = srcs[0]
+        # ---- the per-frame pass (reuse_frames): chunk fc covers the rows [fc * chunk, (fc + 1) * chunk) of every view's map
+        maps = None
+        if reuse_frames:
+            maps = torch.empty((V, rows, mh, mw, mc), dtype=dt, device=dev)
+            n_chunks = rows // chunk
+            order = [n_chunks - 1] + list(range(n_chunks - 1))          # the chunk of pad_row first: every padded window reads it
+            pos = {fc: i for i, fc in enumerate(order)}
+            map_ready = {}
+
+            def frame_pass_through(fc_need):
+                while len(map_ready) <= pos[fc_need]:
+                    fc = order[len(map_ready)]
+                    need = ev_starts
+                    last = min((fc + 1) * chunk, L) - 1
+                    if packed and last >= fc * chunk:
+                        c = last // per
+                        up.through(c + 1)
+                        need = arrived[c]
+                    with torch.cuda.stream(self._frame_stream):
+                        self._frame_stream.wait_event(need)
+                        for v in range(V):
+                            eng.frame_maps(video, fc * chunk, maps[v, fc * chunk:(fc + 1) * chunk], Bf, flip=bool(v))
+                        ev = torch.cuda.Event()
+                        ev.record(self._frame_stream)
+                    map_ready[fc] = ev
         # ---- the batches: gather -> forward -> post-processing, two in flight
         n_batches = 0
         for bi, lo in enumerate(range(0, n, batch_size)):
@@ -694,7 +749,15 @@ class TDEEDModel:
             slot = bi % 2
             st = streams[slot]
             need = ev_starts
-            if packed:
+            if reuse_frames:
+                # (every chunk's event follows the first one's -- the chunk of pad_row -- on the frame stream, and the tables')
+                last = max(last_of[lo:lo + B])
+                fc = last // chunk if last >= 0 else order[0]
+                if last >= 0 and fc == order[0]:
+                    fc = order[-1]                    # frames of pad_row's own chunk: the chunks in front of it run behind it
+                frame_pass_through(fc)
+                need = map_ready[fc]
+            elif packed:
                 last = max(last_of[lo:lo + B])
                 if last >= 0:
                     c = last // per
@@ -704,7 +767,11 @@ class TDEEDModel:
                 st.wait_event(need)                   # a chunk's event follows the tables' on the copy stream
                 tables = dict(clip_base=base_dev[lo:lo + B], clip_len_v=lenv_dev[lo:lo + B]) if group else {}
                 for v in range(V):
-                    head, _ = eng.forward_from_video(video, starts_dev[lo:lo + B], augment_inference=bool(v), slot=slot, **tables)
+                    if reuse_frames:
+                        head, _ = eng.forward_from_frame_maps(maps[v], starts_dev[lo:lo + B], pad_row, slot=slot, **tables)
+                    else:
+                        head, _ = eng.forward_from_video(video, starts_dev[lo:lo + B], augment_inference=bool(v), slot=slot,
+                                                         **tables)
                     pred, _ = self._model._pack_head(head, B, T, pw.n_cls, pw.displ_col, None)
                     # head is a view of the slot's buffer: consumed here, on the launching stream, before the slot runs again
                     self._process_pred(pred, B, T, dt, out=clip_scores[v, lo:lo + B])
@@ -713,6 +780,9 @@ class TDEEDModel:
         s0 = streams[0]
         s0.wait_stream(streams[1])
         s0.wait_stream(cp)
+        if reuse_frames:
+            frame_pass_through(order[-1])             # (rows nobody read: the count of the stats holds, and nothing is left unqueued)
+            s0.wait_stream(self._frame_stream)
         with torch.cuda.stream(s0):
             if group:
                 track, support, mean = ops.stitch_scores_seg(clip_scores, starts_dev, seg_dev, coff_dev, L, count_all=augment,
@@ -722,7 +792,10 @@ class TDEEDModel:
         stats = dict(frames=L, clips=n, batches=n_batches, views=V, frames_h2d_bytes=up.h2d if up is not None else 0)
         if group:
             stats["videos"] = nv
-        return track, support, mean, s0, stats, (video, srcs, clip_scores, tab_dev, tab_host), g
+        if reuse_frames:
+            stats["frame_pass_frames"] = V * rows
+            stats["map_bytes"] = map_bytes
+        return track, support, mean, s0, stats, (video, srcs, clip_scores, tab_dev, tab_host, maps), g
 
     def epoch(self, loader, optimizer=None, scaler=None, lr_scheduler=None, acc_grad_iter=1, fg_weight=5,
               valMAP=False):

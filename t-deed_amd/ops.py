@@ -819,6 +819,47 @@ def clip_gather_seg(video_u8, starts_dev, clip_base, clip_len_v, T, out):
     return out
 
 
+def _chk_rows_gather(maps, starts_dev, L, pad_row, T, out, who):
+    if not all(isinstance(t_, torch.Tensor) for t_ in (maps, starts_dev, out)):
+        raise TypeError(f"{who}: tensors only")
+    if maps.dtype != out.dtype or starts_dev.dtype != torch.int32:
+        raise TypeError(f"{who}: maps and out of one dtype ({maps.dtype} / {out.dtype}) and int32 starts ({starts_dev.dtype})")
+    if not (maps.is_contiguous() and out.is_contiguous()):
+        raise ValueError(f"{who}: contiguous tensors only")
+    if maps.dim() < 2 or not maps.is_cuda or out.device != maps.device:
+        raise ValueError(f"{who}: maps (rows, ...) and out on one device")
+    rows, B = maps.shape[0], starts_dev.numel()
+    _chk_table(starts_dev, B, maps.device, who, "starts")
+    if B < 1 or T < 1 or not (0 < L <= rows) or not (0 <= pad_row < rows):
+        raise ValueError(f"{who}: {B} clips of {T} frames, {L} frames and pad_row {pad_row} in {rows} rows")
+    rb = maps[0].numel() * maps.element_size()
+    if out.numel() * out.element_size() != B * T * rb:
+        raise ValueError(f"{who}: out holds {out.numel() * out.element_size()} bytes, {B} clips of {T} rows need {B * T * rb}")
+    return rows, rb, B
+
+
+def rows_gather(maps, starts_dev, L, pad_row, T, out):
+    """out[b*T + t] = maps[starts[b] + t] when 0 <= starts[b] + t < L, maps[pad_row] otherwise: clip windows of per-frame rows
+    (the trunk map of every frame of a video) with the row of a black frame as padding.  maps: (rows, ...) of any dtype on
+    the device, rows >= L; starts_dev: int32 (B,) on the device; out: B*T rows of maps' dtype."""
+    rows, rb, B = _chk_rows_gather(maps, starts_dev, L, pad_row, T, out, "rows_gather")
+    call("tdeed_rows_gather", ptr(maps), rows, rb, int(L), int(pad_row), ptr(starts_dev), B, T, ptr(out), stream_ptr())
+    return out
+
+
+def rows_gather_seg(maps, starts_dev, clip_base, clip_len_v, L, pad_row, T, out):
+    """rows_gather over the packed rows of several videos (clip_gather_seg's tables): out[b*T + t] = maps[clip_base[b] +
+    starts[b] + t] when 0 <= starts[b] + t < clip_len_v[b], maps[pad_row] otherwise.  L: the packed total."""
+    if (clip_base is None) != (clip_len_v is None):
+        raise ValueError("rows_gather_seg: clip_base and clip_len_v go together")
+    rows, rb, B = _chk_rows_gather(maps, starts_dev, L, pad_row, T, out, "rows_gather_seg")
+    _chk_table(clip_base, B, maps.device, "rows_gather_seg", "clip_base")
+    _chk_table(clip_len_v, B, maps.device, "rows_gather_seg", "clip_len_v")
+    call("tdeed_rows_gather_seg", ptr(maps), rows, rb, int(L), int(pad_row), ptr(starts_dev), ptr(clip_base), ptr(clip_len_v),
+         B, T, ptr(out), stream_ptr())
+    return out
+
+
 def stitch_scores_seg(clip_scores, starts_dev, seg_off, clip_off, L, count_all=None, track_sum=None, support=None, mean=False):
     """stitch_scores per video of a group: clip_scores fp32 (V,n,T,K1) of the group's clip list (video-major), starts_dev
     int32 (n,) video-local, seg_off / clip_off int32 (nv+1,) on the device, L = sum of the lengths.  -> (track_sum (sum L,K1), support (sum L,) int32,

@@ -88,6 +88,15 @@ def regnet_spec(feature_arch: str, crop: int = 224) -> RegNetSpec:
     return RegNetSpec(arch=base, stem_w=32, widths=widths, depths=depths, gw=gw, blocks=tuple(blocks))
 
 
+def first_site_block(spec: RegNetSpec) -> int:
+    """Index of the first block whose conv1 is wrapped by GatedShift (len(blocks) without one).  Everything in front of it --
+    the stem and the blocks [0, k) -- is a function of one frame alone in eval mode: no temporal mixing, folded BatchNorms."""
+    for i, blk in enumerate(spec.blocks):
+        if blk.gsf_fold > 0:
+            return i
+    return len(spec.blocks)
+
+
 def sgp_up_size(ks: int, r) -> int:
     """Wide depthwise kernel size of an SGP block (/root/reference/model/modules.py:119-120)."""
     up = round((ks + 1) * r)

@@ -8,6 +8,8 @@
                                                                         spot_video, one JSON line
     python tools/bench_video.py --group [--group-videos 32]             short videos: spot_videos video by video against
                                                                         spot_videos in packed groups, one JSON line
+    python tools/bench_video.py --reuse [--frames 2030]                 predict_video against predict_video(reuse_frames=
+                                                                        True), one JSON line, also written to --out
 
 Routes (RegNetY-200MF, T = 100, 224 x 224, bf16; 3/4 overlap like the evaluation datasets):
   A  the clip route: `evalutil.stitch_predictions` over host-resident PINNED uint8 clip batches of the video, at loader
@@ -324,6 +326,56 @@ def group(a):
     return 0
 
 
+def reuse(a):
+    """Two routes over the same video, alternating: predict_video(batch_size=8) as it is, and with reuse_frames=True (stem and
+    the blocks in front of the first gate-shift site once per frame instead of once per clip window).  Plain and augmented
+    (two views), frames from pinned host memory and resident on the device.  Per setting: both times, their ratio, the
+    frames that went through the per-frame stages on either route, and how far the scores are apart."""
+    from tdeed_amd.model import TDEEDModel
+    from types import SimpleNamespace
+    T, L = CFG["clip_len"], a.frames
+    m = TDEEDModel(device="cuda", args=SimpleNamespace(modality="rgb", temporal_arch="ed_sgp_mixer", pretrain=None, **CFG))
+    m.load({k: torch.from_numpy(v) for k, v in synth.make_state(state_layout.model_state_shapes(CFG), 0).items()})
+    dev_video = ops.fill_u8_hash((L, 3, H, W), 9, "cuda")
+    sources = dict(pinned=dev_video.cpu().pin_memory(), device=dev_video)
+    eng = m._model.engine(torch.bfloat16)
+    out = dict(kind="video_frame_reuse", cfg=CFG, frames=L, batch_size=8, repeats=a.repeats, frame_batch=m.frame_batch,
+               first_site_block=eng.first_site_block(), settings={})
+    for src, video in sources.items():
+        for augment in (False, True):
+            routes = dict(default=lambda: m.predict_video(video, batch_size=8, augment=augment),
+                          reuse=lambda: m.predict_video(video, batch_size=8, augment=augment, reuse_frames=True))
+            res, stats = {}, {}
+            for k, fn in routes.items():                                # warm-up of every shape
+                res[k] = fn()
+                stats[k] = dict(m.last_video_stats)
+            times = {k: [] for k in routes}
+            for _ in range(a.repeats):
+                for k, fn in routes.items():                            # alternating
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    times[k].append(time.perf_counter() - t0)
+            V, n = stats["reuse"]["views"], stats["reuse"]["clips"]
+            st = {k: _stat(v, L, n * V) for k, v in times.items()}
+            d = np.maximum(res["default"][1], 1)[:, None].astype(np.float32)
+            out["settings"][f"{src}_{'augment' if augment else 'plain'}"] = dict(
+                routes=st, ratio_reuse_over_default=round(st["reuse"]["ms_median"] / st["default"]["ms_median"], 3),
+                speedup=round(st["default"]["ms_median"] / st["reuse"]["ms_median"], 3),
+                views=V, clips=n, front_frames_default=V * n * T, frame_pass_frames=stats["reuse"]["frame_pass_frames"],
+                map_bytes=stats["reuse"]["map_bytes"], frame_bytes=L * 3 * H * W,
+                support_equal=bool(np.array_equal(res["default"][1], res["reuse"][1])),
+                sums_equal=bool(np.array_equal(res["default"][0], res["reuse"][0])),
+                max_abs_mean_score_diff=float(np.abs(res["default"][0] / d - res["reuse"][0] / d).max()))
+    line = json.dumps(out)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+    print(line)
+    return 0
+
+
 def gather_only(a):
     T, B, L = 100, 8, 400
     video = ops.fill_u8_hash((L, 3, H, W), 9, "cuda")
@@ -378,6 +430,8 @@ if __name__ == "__main__":
     ap.add_argument("--frames", type=int, default=None, help="default 2030, with --spot 5625")
     ap.add_argument("--spot", action="store_true")
     ap.add_argument("--group", action="store_true")
+    ap.add_argument("--reuse", action="store_true", help="predict_video against predict_video(reuse_frames=True)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "video_frame_reuse.json"), help="--reuse: where the JSON goes")
     ap.add_argument("--group-videos", type=int, default=32, help="--group: videos per packed group of route B")
     ap.add_argument("--splits", default="diving,tennis", help="--group: synthetic splits to run")
     ap.add_argument("--window", type=int, default=12, help="--spot: NMS / soft-NMS window")
@@ -389,5 +443,5 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if a.frames is None:
         a.frames = 5625 if a.spot else 2030
-    sys.exit(decode(a) if a.decode else gather_only(a) if a.gather_only else group(a) if a.group else spot(a) if a.spot
-             else bench(a))
+    sys.exit(decode(a) if a.decode else gather_only(a) if a.gather_only else reuse(a) if a.reuse else group(a) if a.group
+             else spot(a) if a.spot else bench(a))

@@ -110,6 +110,12 @@ def plans(E, synth, state_layout, show_forms=False):
         show("stem tap", dt, lambda: eng.plan(2, 224, 224, taps=("_features.stem",)))
         flips = torch.zeros((2 * 16,), dtype=torch.uint8, device="meta")
         show("per-frame flips, fp32 frames 200x200", dt, lambda: eng._build(2, 200, 200, flips, set(), frames_dtype=torch.float32))
+    # whole videos with the per-frame stages once per frame: the frame plan (blocks [0, k)) and the tail plan (blocks [k:] on)
+    for (arch, n, T, B), dt in itertools.product([("rny002_gsf", 2, 100, 8), ("rny008_gsf", 3, 100, 8)], DTYPES):
+        eng = engine(arch, n, T, dt)
+        h, w, _ = eng.frame_map_shape(224, 224)
+        show(f"{arch} n{n} T{T} frame plan Bf2 224x224 k{eng.first_site_block()}", dt, lambda: eng.frame_plan(2, 224, 224))
+        show(f"{arch} n{n} T{T} tail plan B{B} {h}x{w}", dt, lambda: eng.tail_plan(B, h, w))
 
 
 def tensors(obj, path=""):
