@@ -831,6 +831,26 @@ int tdeed_sgp_gemm_gelu_chsum(const void* A, int B, int T, int K, const void* Wp
                               float* chs_out, void* out16 /* optional bf16 copy of out */, int form, int dtype_o,
                               void* stream);
 
+/* ---- baseline JPEG decode of a video's frames on the device (csrc/jpeg.hip, csrc/jpeg_core.h; tables and packing:
+ * tdeed_amd/jpegdev.py).  sampling: 0 greyscale, 1 4:4:4, 2 4:2:2, 3 4:2:0.  A frame's coefficients are
+ * tdeed_jpeg_frame_coeffs int16 values: per component the blocks of the padded MCU grid, row-major, 64 values each in
+ * natural order, un-dequantised.
+ * tdeed_jpeg_entropy: one lane per row of the segment table (int32 [n_segments][6]: frame, first MCU, MCU count, byte offset
+ *   into stream, byte length, table set); waves int32 [n_waves][2] = (first row, count <= 64), the rows of a wave consecutive
+ *   and of one table set; table_sets [n_sets][4240] bytes (JcTableSet).  Frames frame_lo .. frame_lo + n_frames - 1 decode into
+ *   coeff (zero-filled by the caller on the same stream); rows of other frames get status 7.  status int32 [n_segments]:
+ *   0, or 1 data exhausted, 2 marker inside the segment, 3 no code within 16 bits, 4 DC category > 11, 5 AC size > 10,
+ *   6 run past 63, 7 row outside its buffers.  A lane never reads outside its segment nor stores outside its frame.
+ * tdeed_jpeg_pixels: coeff of the same frame range -> out uint8 [all frames][3][H][W] rows frame_lo ..; dequantisation, integer
+ *   IDCT, triangle up-sampling and YCbCr -> RGB, bit-identical to libjpeg-turbo's defaults.  frame_table_set int32 per
+ *   frame of the whole video; a frame with a negative entry is left untouched (the caller decodes it on the host). */
+long tdeed_jpeg_frame_coeffs(int W, int H, int sampling);
+int tdeed_jpeg_entropy(const uint8_t* stream, long stream_bytes, const int* segments, int n_segments, const int* waves,
+                       int n_waves, const uint8_t* table_sets, int n_sets, int W, int H, int sampling, int frame_lo,
+                       int n_frames, int16_t* coeff, int* status, void* hip_stream);
+int tdeed_jpeg_pixels(const int16_t* coeff, const int* frame_table_set, const uint8_t* table_sets, int n_sets, uint8_t* out,
+                      int frame_lo, int n_frames, int H, int W, int sampling, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

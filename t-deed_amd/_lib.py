@@ -192,6 +192,9 @@ _SIGS = {
     "tdeed_train_clip_gather_u8": ([P, c_long, c_long, P, P, P, c_int, c_int, c_int, P, P], c_int),
     "tdeed_train_clip_gather_mix_f32": ([P, c_long, c_long, P, P, P, P, P, P, P, c_int, c_int, c_int, P, P], c_int),
     "tdeed_clip_labels": ([P, P, c_int, c_int, c_int, c_int, P, P, P, c_int, c_int, P, P, P], c_int),
+    "tdeed_jpeg_frame_coeffs": ([c_int, c_int, c_int], c_long),
+    "tdeed_jpeg_entropy": ([P, c_long, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P], c_int),
+    "tdeed_jpeg_pixels": ([P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P], c_int),
     "tdeed_comm_unique_id": ([P], c_int),
     "tdeed_comm_init": ([POINTER(c_void_p), P, c_int, c_int], c_int),
     "tdeed_comm_info": ([P, POINTER(c_int), POINTER(c_int)], c_int),

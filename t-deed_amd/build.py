@@ -10,7 +10,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libtdeed_hip.so")
-SOURCES = ["gemm.hip", "conv.hip", "front.hip", "gsf.hip", "sgp.hip", "sgp_fused.hip", "sgp_gemm.hip", "bneck.hip", "sgp_bwd.hip", "trunk_bwd.hip", "trunk_bwd2.hip", "trunk_bwd3.hip", "gsf_bwd.hip", "train.hip", "misc.hip", "augment.hip", "comm.hip", "video.hip", "spot.hip", "trainclips.hip"]
+SOURCES = ["gemm.hip", "conv.hip", "front.hip", "gsf.hip", "sgp.hip", "sgp_fused.hip", "sgp_gemm.hip", "bneck.hip", "sgp_bwd.hip", "trunk_bwd.hip", "trunk_bwd2.hip", "trunk_bwd3.hip", "gsf_bwd.hip", "train.hip", "misc.hip", "augment.hip", "comm.hip", "video.hip", "spot.hip", "trainclips.hip", "jpeg.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=fast", "-Wall",
          "-Wno-unused-function"]
 # MFMA accumulators in VGPRs instead of AGPRs for the files whose epilogues are VALU-bound: every accumulator element
@@ -44,7 +44,7 @@ def build(force=False, verbose=True, flavour="release", only=None):
     sources and do not link (a quick does-it-compile check)."""
     debug = flavour == "debug"
     flags, lib, osuf = (DEBUG_FLAGS, LIB_DEBUG, ".dbg.o") if debug else (FLAGS, LIB, ".o")
-    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "sgp_tile.h"), os.path.join(CSRC, "se_excite.h"),
+    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "sgp_tile.h"), os.path.join(CSRC, "se_excite.h"), os.path.join(CSRC, "jpeg_core.h"),
             os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "tdeed_hip.h")]
     jobs = []
     objs = []

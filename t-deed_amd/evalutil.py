@@ -205,6 +205,19 @@ def stitch_clip_scores_seg(scores, starts, seg_off, clip_off, flip_scores=None):
     return sums, support
 
 
+def _with_loader(videos, decode):
+    """A source that is a dict of `feeder.load_video` keyword arguments (frame_dir, dataset, video_name, num_frames, ...)
+    becomes a callable: `feeder.load_video` for decode="host", `feeder.load_video_device` for decode="device".  Tensors
+    and callables pass through."""
+    if decode not in ("host", "device"):
+        raise ValueError(f"decode must be 'host' or 'device', not {decode!r}")
+    import functools
+    from . import feeder
+    loader = feeder.load_video_device if decode == "device" else feeder.load_video
+    return [(name, length, fps, functools.partial(loader, **src) if isinstance(src, dict) else src)
+            for name, length, fps, src in videos]
+
+
 def _decoded_groups(videos, group_videos, max_resident_bytes):
     """The sources of `videos` (name, length, fps, frames | callable) in groups: batches of `group_videos` consecutive
     videos are materialised -- callables on a worker thread, one batch ahead of the consumer -- and each batch is then
@@ -231,7 +244,7 @@ def _decoded_groups(videos, group_videos, max_resident_bytes):
 
 
 def stitch_videos(model, videos, n_cols, augment=False, batch_size=8, overlap_len=None, decode_ahead=1, group_videos=1,
-                  max_resident_bytes=16 << 30, reuse_frames=False):
+                  max_resident_bytes=16 << 30, reuse_frames=False, decode="host"):
     """Whole-video counterpart of `stitch_predictions`: `videos` yields (name, length, fps, frames) with frames a uint8
     (length,3,H,W) tensor of the sampled frames or a callable returning one (e.g. a `feeder.load_video` closure); every
     video goes through `model.predict_video` once and its (sums, support) become the video's track of the returned
@@ -241,9 +254,11 @@ def stitch_videos(model, videos, n_cols, augment=False, batch_size=8, overlap_le
     group_videos > 1: up to that many consecutive videos (as far as `max_resident_bytes` and one frame geometry allow,
     `video_groups`) go through `model.predict_video_group` as one packed job whose batches are cut across the videos; the
     callables of the next `group_videos` videos are decoded on the worker thread meanwhile.
-    reuse_frames: passed on to `predict_video` / `predict_video_group` (the per-frame trunk stages once per frame)."""
+    reuse_frames: passed on to `predict_video` / `predict_video_group` (the per-frame trunk stages once per frame).
+    decode: a `frames` entry may also be a dict of `feeder.load_video` keyword arguments; "host" loads it with
+    `feeder.load_video`, "device" with `feeder.load_video_device` (JPEG decode on the device, same frames)."""
     from concurrent.futures import ThreadPoolExecutor
-    videos = list(videos)
+    videos = _with_loader(list(videos), decode)
     reuse = dict(reuse_frames=True) if reuse_frames else {}
     st = ScoreStitcher([(v, n, f) for v, n, f, _ in videos], n_cols)
     if int(group_videos) > 1:
@@ -460,7 +475,8 @@ def event_dicts(frames, classes_idx, scores, inv):
 
 
 def spot_videos(model, videos, classes, suppress, high_recall_score_threshold=0.01, augment=False, batch_size=8,
-                overlap_len=None, decode_ahead=1, group_videos=1, max_resident_bytes=16 << 30, reuse_frames=False):
+                overlap_len=None, decode_ahead=1, group_videos=1, max_resident_bytes=16 << 30, reuse_frames=False,
+                decode="host"):
     """Whole-video counterpart of `stitch_videos` + `frame_events` + the two NMS functions with the tail on the device:
     `videos` as in `stitch_videos`; every video goes through `model.spot_video` once.  suppress: entries (kind, window,
     threshold) with kind "nms" | "snms".  Returns (pred_events, [one list of video records per suppress entry],
@@ -468,9 +484,9 @@ def spot_videos(model, videos, classes, suppress, high_recall_score_threshold=0.
     `soft_non_maximum_suppression` build them ('num_events' included), so `mean_average_precisions` works on them
     unchanged.  The label-dependent error / F1 counters of `frame_events` follow from the returned pred on the host.
     group_videos > 1: groups of videos go through `model.spot_video_group` as in `stitch_videos`.  reuse_frames: passed on
-    to `spot_video` / `spot_video_group`."""
+    to `spot_video` / `spot_video_group`.  decode: as in `stitch_videos`."""
     from concurrent.futures import ThreadPoolExecutor
-    videos = list(videos)
+    videos = _with_loader(list(videos), decode)
     reuse = dict(reuse_frames=True) if reuse_frames else {}
     suppress = [tuple(e) for e in suppress]
     done = {}

@@ -14,7 +14,9 @@ over PCIe, no overlap with the forward.  Here
   * `prefetch(loader, ...)` wraps any iterable of batch dicts (the reference's loaders) so that batch i+1 is staged and
     copied while batch i is being processed: `TDEEDModel.epoch()` uses it for both the validation and the training loop.
 
-Only plumbing lives here (host memory, streams, events); nothing in this file computes on the device.
+Only plumbing lives here (host memory, streams, events); nothing in this file computes on the device, with one opt-in
+exception: `load_video_device` hands the JPEG bytes of a video to the decode kernels (csrc/jpeg.hip) and returns the
+frames as a device tensor.
 """
 import os
 
@@ -85,6 +87,160 @@ def load_video(frame_dir, dataset, video_name, num_frames, stride=1, source_info
     else:
         for nm, dst in jobs:
             read_frame(nm, out=dst)
+    return out[:L]
+
+
+last_decode_stats = {}      # filled by load_video_device: what its last call did
+
+
+def _read_file(path):
+    with open(path, "rb") as f:
+        return f.read()
+
+
+class DeviceJpegs:
+    """A `jpegdev.PackedJpegs` on the device: the tables go up in ONE copy from a page-locked block (segment table, table
+    set per frame, the wave tables of every frame chunk, the table sets), the entropy stream in pieces of `piece_bytes`
+    as the chunks need it (`stream_through`).  chunks: [(frame_lo, frame_hi, waves tensor | None)]; status: int32 per
+    segment row, zero-filled."""
+
+    def __init__(self, packed, device, chunk_frames, piece_bytes=16 << 20):
+        from . import jpegdev
+        self.packed, self.piece = packed, int(piece_bytes)
+        n = packed.n_frames
+        bounds = [(lo, min(lo + chunk_frames, n)) for lo in range(0, n, chunk_frames)]
+        waves = [packed.waves(lo, hi) for lo, hi in bounds]
+        parts = [packed.segments.reshape(-1).view(np.uint8), packed.frame_set.view(np.uint8)] + \
+                [w.reshape(-1).view(np.uint8) for w in waves] + [packed.table_sets.reshape(-1)]
+        offs, total = [], 0
+        for a in parts:
+            offs.append(total)
+            total += (a.size + 15) & ~15
+        host = torch.zeros(max(total, 16), dtype=torch.uint8).pin_memory()
+        hv = host.numpy()
+        for a, o in zip(parts, offs):
+            hv[o:o + a.size] = a
+        self._meta_host = host                      # keeps the page-locked block alive until the copy has run
+        meta = torch.empty(host.numel(), dtype=torch.uint8, device=device)
+        meta.copy_(host, non_blocking=True)
+
+        def view(i, dtype, shape):
+            nbytes = parts[i].size
+            return meta[offs[i]:offs[i] + nbytes].view(dtype).view(*shape)
+        self.segments = view(0, torch.int32, (packed.n_segments, 6))
+        self.frame_set = view(1, torch.int32, (n,))
+        self.table_sets = view(len(parts) - 1, torch.uint8, (packed.n_sets, jpegdev.TABLE_SET_BYTES))
+        self.chunks = [(lo, hi, view(2 + i, torch.int32, (w.shape[0], 2)) if w.shape[0] else None)
+                       for i, ((lo, hi), w) in enumerate(zip(bounds, waves))]
+        src = packed.stream if isinstance(packed.stream, torch.Tensor) else torch.from_numpy(packed.stream_np)
+        self._src = src
+        self.stream = torch.empty(src.numel(), dtype=torch.uint8, device=device)
+        self.uploaded = 0
+        self.status = torch.zeros(max(packed.n_segments, 1), dtype=torch.int32, device=device)
+        self.meta_bytes = int(host.numel())
+
+    def stream_through(self, nbytes):
+        """queue the pieces of the entropy stream up to byte `nbytes` that are not queued yet (current stream)"""
+        end = min(int(nbytes), self._src.numel())
+        while self.uploaded < end:
+            hi = min(self.uploaded + self.piece, self._src.numel())
+            self.stream[self.uploaded:hi].copy_(self._src[self.uploaded:hi], non_blocking=True)
+            self.uploaded = hi
+
+    def need(self, lo, hi):
+        """the stream bytes the frames [lo, hi) reach up to"""
+        rows = self.packed.rows(lo, hi)
+        seg = self.packed.segments
+        return int((seg[rows, 3].astype(np.int64) + seg[rows, 4]).max()) + 8 if rows.size else 0
+
+
+def decode_packed(packed, out, max_coeff_bytes=512 << 20):
+    """Run the entropy and pixel kernels over a `jpegdev.PackedJpegs` on the current stream: frame j of the pack lands in
+    out[j] (device uint8 (>= n_frames,3,H,W)); frames without a table set are left untouched.  The coefficient buffer is
+    transient and holds at most max_coeff_bytes (at least one frame).  Returns (DeviceJpegs, number of chunks); nothing is
+    synchronised -- the statuses are in `.status` on the device."""
+    from . import ops
+    fc = ops.jpeg_frame_coeffs(packed.width, packed.height, packed.samp)
+    per = min(max(1, int(max_coeff_bytes) // (2 * fc)), 65535, max(packed.n_frames, 1))
+    dj = DeviceJpegs(packed, out.device, per)
+    coeff = torch.empty(per * fc, dtype=torch.int16, device=out.device)
+    chunks = 0
+    for lo, hi, waves in dj.chunks:
+        if waves is None:
+            continue
+        dj.stream_through(dj.need(lo, hi))
+        coeff[:(hi - lo) * fc].zero_()
+        ops.jpeg_entropy(dj.stream, dj.segments, waves, dj.table_sets, packed.width, packed.height, packed.samp, lo, hi - lo,
+                         coeff, dj.status)
+        ops.jpeg_pixels(coeff, dj.frame_set, dj.table_sets, out, lo, hi - lo, packed.samp)
+        chunks += 1
+    return dj, chunks
+
+
+def load_video_device(frame_dir, dataset, video_name, num_frames, stride=1, source_info=None, device="cuda", out=None,
+                      stream=None, max_coeff_bytes=512 << 20, pool=None):
+    """`load_video` with the decode on the device: the same uint8 (L,3,H,W) frames, bit for bit, as a DEVICE tensor; the
+    JPEG files cross the host-device link instead of the decoded frames.  The files are read (through `pool`'s threads
+    when a DecodePool is given), parsed and packed on the host (`jpegdev.pack`), uploaded on `stream` (default: the
+    current one), and decoded there by csrc/jpeg.hip in chunks of frames whose transient coefficient buffer stays under
+    max_coeff_bytes.  One host synchronisation per call, for the per-segment statuses.  Frames outside the decoder's
+    subset (`jpegdev.parse`: progressive, CMYK, ...) and frames whose status is non-zero are decoded with `read_frame`
+    and copied into their rows: whatever Pillow does with such a file, raising included, is then the behaviour.
+    Missing files are treated as by `load_video`.  out: optional device uint8 (>= L,3,H,W) buffer.
+    `last_decode_stats` tells what the call did."""
+    from . import jpegdev
+    _, _, _, path_fn = frame_locator(frame_dir, dataset, video_name, source_info)
+    L = (int(num_frames) + stride - 1) // stride
+    names = [path_fn(j * stride) for j in range(L)]
+    have = [os.path.exists(p) for p in names]
+    n_real = L
+    while n_real > 0 and not have[n_real - 1]:
+        n_real -= 1
+    if n_real == 0:
+        raise FileNotFoundError(f"video {video_name}: no frame found (looked for {names[0] if names else frame_dir})")
+    if not all(have[:n_real]):
+        raise FileNotFoundError(f"video {video_name}: {names[have.index(False)]} is missing although later frames exist")
+    datas = list(pool.ex.map(_read_file, names[:n_real])) if pool is not None and hasattr(pool, "ex") else \
+        [_read_file(p) for p in names[:n_real]]
+    packed = jpegdev.pack(datas)
+    first = None
+    if packed.n_segments == 0:                       # nothing for the device: the geometry comes from Pillow
+        first = read_frame(names[0])
+        H, W = int(first.shape[1]), int(first.shape[2])
+    else:
+        H, W = packed.height, packed.width
+    dev = torch.device(device)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(st):
+        if out is None:
+            out = torch.empty((L, 3, H, W), dtype=torch.uint8, device=dev)
+        else:
+            if not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous():
+                raise TypeError("load_video_device: out must be a contiguous uint8 tensor on the device")
+            if out.shape[0] < L:
+                raise ValueError(f"the buffer holds {out.shape[0]} frames, the video has {L}")
+            if tuple(out.shape[1:]) != (3, H, W):
+                raise ValueError(f"video {video_name}: frames {(3, H, W)} do not fit the buffer {tuple(out.shape[1:])}")
+        if n_real < L:
+            out[n_real:L].zero_()
+        bad, chunks, uploaded = set(packed.fallback), 0, 0
+        if packed.n_segments:
+            dj, chunks = decode_packed(packed, out, max_coeff_bytes)
+            status = torch.empty(packed.n_segments, dtype=torch.int32).pin_memory()
+            status.copy_(dj.status[:packed.n_segments], non_blocking=True)
+            st.synchronize()
+            uploaded = dj.uploaded + dj.meta_bytes
+            bad.update(int(f) for f in np.unique(packed.segments[status.numpy() != 0, 0]))
+        for j in sorted(bad):
+            fr = first if (j == 0 and first is not None) else read_frame(names[j])
+            if tuple(fr.shape) != (3, H, W):
+                raise ValueError(f"frame {names[j]}: {tuple(fr.shape)} does not fit the buffer {(3, H, W)}")
+            out[j].copy_(fr)
+        if bad:
+            st.synchronize()
+    last_decode_stats.clear()
+    last_decode_stats.update(frames=L, device_frames=n_real - len(bad), fallback_frames=len(bad), stream_bytes=int(uploaded),
+                             table_sets=packed.n_sets, segments=packed.n_segments, chunks=chunks)
     return out[:L]
 
 

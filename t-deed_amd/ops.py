@@ -984,6 +984,67 @@ def fill_u8_hash(shape, seed, device="cuda"):
     return out[:n].view(*shape)
 
 
+# ---------------------------------------------------------------------------------------------- JPEG decode (jpeg.hip)
+def jpeg_frame_coeffs(W, H, sampling):
+    """int16 values of one frame's coefficient range (jpegdev.geometry(...).frame_blocks * 64)"""
+    n = int(_lib.load().tdeed_jpeg_frame_coeffs(int(W), int(H), int(sampling)))
+    if n < 0:
+        raise ValueError(f"jpeg_frame_coeffs: bad geometry {H}x{W}, sampling {sampling}")
+    return n
+
+
+def _chk_jpeg_tables(who, dev, **tabs):
+    for name, (t_, dtype) in tabs.items():
+        if not isinstance(t_, torch.Tensor) or t_.dtype != dtype or t_.device != dev or not t_.is_contiguous():
+            raise TypeError(f"{who}: {name} must be a contiguous {dtype} tensor on {dev}")
+
+
+def jpeg_entropy(stream, segments, waves, table_sets, W, H, sampling, frame_lo, n_frames, coeff, status):
+    """Entropy-decode the segments listed by `waves` (jpegdev.PackedJpegs.waves(frame_lo, frame_lo + n_frames)) into coeff,
+    int16 (>= n_frames * jpeg_frame_coeffs) that the caller has zero-filled on this stream; status int32 (n_segments,)
+    gets 0 or the error code per decoded row.  stream uint8, segments int32 (n_segments, 6), waves int32 (n_waves, 2),
+    table_sets uint8 (n_sets, 4240): all on the device."""
+    dev = coeff.device
+    _chk(coeff, "coeff", torch.int16)
+    _chk_jpeg_tables("jpeg_entropy", dev, stream=(stream, torch.uint8), segments=(segments, torch.int32),
+                     waves=(waves, torch.int32), table_sets=(table_sets, torch.uint8), status=(status, torch.int32))
+    if segments.dim() != 2 or segments.shape[1] != 6 or waves.dim() != 2 or waves.shape[1] != 2:
+        raise ValueError("jpeg_entropy: segments (n, 6) and waves (n, 2)")
+    if table_sets.dim() != 2 or table_sets.shape[1] != 4240 or table_sets.shape[0] < 1:
+        raise ValueError("jpeg_entropy: table_sets (n_sets, 4240)")
+    if status.numel() < segments.shape[0]:
+        raise ValueError(f"jpeg_entropy: {status.numel()} status entries for {segments.shape[0]} segments")
+    fc = jpeg_frame_coeffs(W, H, sampling)
+    if coeff.numel() < int(n_frames) * fc:
+        raise ValueError(f"jpeg_entropy: coeff holds {coeff.numel()} values, {n_frames} frames need {int(n_frames) * fc}")
+    call("tdeed_jpeg_entropy", ptr(stream), stream.numel(), ptr(segments), segments.shape[0], ptr(waves), waves.shape[0],
+         ptr(table_sets), table_sets.shape[0], int(W), int(H), int(sampling), int(frame_lo), int(n_frames), ptr(coeff),
+         ptr(status), stream_ptr())
+    return coeff
+
+
+def jpeg_pixels(coeff, frame_set, table_sets, out, frame_lo, n_frames, sampling):
+    """coeff of the frames frame_lo .. frame_lo + n_frames - 1 (jpeg_entropy) -> out[frame_lo : frame_lo + n_frames] of the
+    uint8 (L,3,H,W) video buffer; frame_set int32 (L,) table set per frame, a frame with -1 is left as it is."""
+    dev = out.device
+    _chk(out, "out", torch.uint8)
+    _chk(coeff, "coeff", torch.int16)
+    _chk_jpeg_tables("jpeg_pixels", dev, frame_set=(frame_set, torch.int32), table_sets=(table_sets, torch.uint8))
+    if out.dim() != 4 or out.shape[1] != 3:
+        raise ValueError("jpeg_pixels: out must be (L,3,H,W)")
+    L, _, H, W = out.shape
+    if table_sets.dim() != 2 or table_sets.shape[1] != 4240 or table_sets.shape[0] < 1:
+        raise ValueError("jpeg_pixels: table_sets (n_sets, 4240)")
+    if frame_lo < 0 or n_frames < 1 or frame_lo + n_frames > L or frame_set.numel() < frame_lo + n_frames:
+        raise ValueError(f"jpeg_pixels: frames {frame_lo}..{frame_lo + n_frames} outside the {L} of out / {frame_set.numel()} of frame_set")
+    fc = jpeg_frame_coeffs(W, H, sampling)
+    if coeff.numel() < int(n_frames) * fc:
+        raise ValueError(f"jpeg_pixels: coeff holds {coeff.numel()} values, {n_frames} frames need {int(n_frames) * fc}")
+    call("tdeed_jpeg_pixels", ptr(coeff), ptr(frame_set), ptr(table_sets), table_sets.shape[0], ptr(out), int(frame_lo),
+         int(n_frames), int(H), int(W), int(sampling), stream_ptr())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- SGP contractions (sgp_gemm.hip)
 def sgp_gemm_ksteps(K):
     return int(_lib.load().tdeed_sgp_gemm_ksteps(K))

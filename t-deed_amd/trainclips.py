@@ -138,16 +138,20 @@ class ClipDraws:
             yield np.asarray(a, np.int64), (np.asarray(b, np.int64) if self.mixup else None)
 
 
-def load_resident_videos(frame_dir, dataset, videos, pool=None):
+def load_resident_videos(frame_dir, dataset, videos, pool=None, decode="host"):
     """The `frames` argument of `ResidentClips` from a frame directory: per video of the label list one uint8
     (num_frames,3,H,W) tensor (page-locked when a GPU runtime is there), every JPEG decoded once by
     `feeder.load_video(..., stride=1)` -- concurrently when `pool` is a `feeder.DecodePool`.
     `feeder.load_video` turns trailing missing files into zero frames, which is right for a clip window but not for the
     clip LIST: the reference drops a clip whose sampled frames do not exist, and `train_clip_table` decides that from
     `num_frames`.  A video whose last frame file is missing therefore raises ValueError here: list it with the number of
-    frames that exist."""
+    frames that exist.
+    decode: "host" (Pillow, host tensors) or "device" (`feeder.load_video_device`: the JPEG bytes go to the device and are
+    decoded there; device tensors with the same contents, which `ResidentClips` takes as they are)."""
     import os
     from . import feeder
+    if decode not in ("host", "device"):
+        raise ValueError(f"decode must be 'host' or 'device', not {decode!r}")
     out = []
     for v in videos:
         n = int(v["num_frames"])
@@ -155,6 +159,10 @@ def load_resident_videos(frame_dir, dataset, videos, pool=None):
         if n < 1 or not os.path.exists(path_fn(n - 1)):
             raise ValueError(f"video {v['video']}: num_frames={n}, but {path_fn(max(n, 1) - 1)} does not exist -- num_frames must "
                              "be the number of frames that exist")
+        if decode == "device":
+            out.append(feeder.load_video_device(frame_dir, dataset, v["video"], n, stride=1, source_info=v.get("_source_info"),
+                                                pool=pool))
+            continue
         out.append(feeder.load_video(frame_dir, dataset, v["video"], n, stride=1, source_info=v.get("_source_info"), pool=pool))
     return out
 

@@ -4,6 +4,9 @@
     python tools/bench_video.py --gather-only                           the gather launch alone (run it under
                                                                         `rocprofv3 --kernel-trace --stats -- python ...`)
     python tools/bench_video.py --decode [--decode-frames 400]          host only: load_video vs clip_batches, JPEG decode
+    python tools/bench_video.py --decode-device [--decode-frames 400]   JPEG decode: load_video with 8 threads and with 16
+                                                                        worker processes against load_video_device, one JSON
+                                                                        line, also written to profiles/jpeg_device_decode.json
     python tools/bench_video.py --spot [--frames 5625]                  events: predict_video + the host chain against
                                                                         spot_video, one JSON line
     python tools/bench_video.py --group [--group-videos 32]             short videos: spot_videos video by video against
@@ -425,6 +428,98 @@ def decode(a):
     return 0
 
 
+def decode_device(a):
+    """JPEG decode of one video, three routes in one process, alternating, `--repeats` timed passes after a warm-up each:
+    load_video with a DecodePool of 8 threads, load_video with a ProcessDecodePool of 16 workers (both into page-locked
+    host memory, which is where those routes end), load_video_device (ends with the frames on the device).  Then the two
+    kernels alone (HIP events) and the host's share of the device route alone (file reads, parse, pack)."""
+    import tempfile
+    from PIL import Image
+    from tdeed_amd import jpegdev
+    n = a.decode_frames
+    dev = torch.device("cuda")
+
+    def rate(times):
+        t = np.asarray(times)
+        return dict(frames_per_s=round(n / float(np.median(t)), 1), frames_per_s_min=round(n / float(t.max()), 1),
+                    frames_per_s_max=round(n / float(t.min()), 1), ms_median=round(float(np.median(t)) * 1e3, 2))
+
+    with tempfile.TemporaryDirectory() as tmp:
+        d = os.path.join(tmp, "vid")
+        os.makedirs(d)
+        for i in range(n):
+            Image.fromarray(synth.uint8_clip(700 + i % 16, (H, W, 3))).save(os.path.join(d, f"frame{i}.jpg"), quality=90)
+        names = [os.path.join(d, f"frame{i}.jpg") for i in range(n)]
+        file_bytes = sum(os.path.getsize(p) for p in names)
+        tpool, ppool = feeder.DecodePool(8), feeder.ProcessDecodePool(16)
+        try:
+            slot = ppool.make_slots(1, (n, 3, H, W))[0]
+            pinned = torch.zeros((n, 3, H, W), dtype=torch.uint8).pin_memory()
+            dbuf = torch.empty((n, 3, H, W), dtype=torch.uint8, device=dev)
+            routes = dict(
+                host_threads_8=lambda: feeder.load_video(tmp, "soccernetball", "vid", n, out=pinned, pool=tpool),
+                host_processes_16=lambda: feeder.load_video(tmp, "soccernetball", "vid", n, out=slot, pool=ppool),
+                device=lambda: feeder.load_video_device(tmp, "soccernetball", "vid", n, out=dbuf, pool=tpool))
+            for fn in routes.values():
+                fn()
+            torch.cuda.synchronize()
+            want = pinned.clone()
+            same = bool(torch.equal(dbuf.cpu(), want)) and bool(torch.equal(slot, want))
+            stats = dict(feeder.last_decode_stats)
+            times = {k: [] for k in routes}
+            for _ in range(a.repeats):
+                for k, fn in routes.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    times[k].append(time.perf_counter() - t0)
+            # the host's share of the device route
+            host_t = []
+            for _ in range(a.repeats):
+                t0 = time.perf_counter()
+                pk = jpegdev.pack([feeder._read_file(p) for p in names])
+                host_t.append(time.perf_counter() - t0)
+            # the kernels alone
+            fc = ops.jpeg_frame_coeffs(W, H, pk.samp)
+            dj = feeder.DeviceJpegs(pk, dev, n)
+            dj.stream_through(pk.stream_np.size)
+            (lo, hi, waves), = dj.chunks
+            coeff = torch.zeros(n * fc, dtype=torch.int16, device=dev)
+            k_ent, k_pix = [], []
+            for it in range(a.repeats + 1):
+                coeff.zero_()
+                e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                e[0].record()
+                ops.jpeg_entropy(dj.stream, dj.segments, waves, dj.table_sets, W, H, pk.samp, 0, n, coeff, dj.status)
+                e[1].record()
+                ops.jpeg_pixels(coeff, dj.frame_set, dj.table_sets, dbuf, 0, n, pk.samp)
+                e[2].record()
+                torch.cuda.synchronize()
+                if it:
+                    k_ent.append(e[0].elapsed_time(e[1]) * 1e-3)
+                    k_pix.append(e[1].elapsed_time(e[2]) * 1e-3)
+        finally:
+            tpool.close()
+            ppool.close()
+    r = {k: rate(v) for k, v in times.items()}
+    rec = dict(kind="jpeg_device_decode", device=torch.cuda.get_device_name(0), measured_on_gpu=True, frames=n,
+               frame="224x224 4:2:0 quality 90, the tool's hash-noise frames (16 distinct)", repeats=a.repeats,
+               identical_to_load_video=same, routes=r,
+               ratio_device_over_host_threads_8=round(r["device"]["frames_per_s"] / r["host_threads_8"]["frames_per_s"], 2),
+               ratio_device_over_host_processes_16=round(r["device"]["frames_per_s"] / r["host_processes_16"]["frames_per_s"], 2),
+               entropy_kernel=rate(k_ent), pixels_kernel=rate(k_pix), host_read_parse_pack=rate(host_t),
+               pcie_bytes_per_frame=dict(host_routes=3 * H * W, device=round(stats["stream_bytes"] / n, 1)),
+               jpeg_file_bytes_per_frame=round(file_bytes / n, 1), last_decode_stats=stats)
+    out = os.path.join(ROOT, "profiles", "jpeg_device_decode.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rec))
+    return 0
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=None, help="default 2030, with --spot 5625")
@@ -438,10 +533,11 @@ if __name__ == "__main__":
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--gather-only", action="store_true")
     ap.add_argument("--decode", action="store_true")
+    ap.add_argument("--decode-device", action="store_true", help="JPEG decode: two host routes against load_video_device")
     ap.add_argument("--decode-frames", type=int, default=400)
     ap.add_argument("--threads", type=int, default=8)
     a = ap.parse_args()
     if a.frames is None:
         a.frames = 5625 if a.spot else 2030
-    sys.exit(decode(a) if a.decode else gather_only(a) if a.gather_only else reuse(a) if a.reuse else group(a) if a.group
+    sys.exit(decode_device(a) if a.decode_device else decode(a) if a.decode else gather_only(a) if a.gather_only else reuse(a) if a.reuse else group(a) if a.group
              else spot(a) if a.spot else bench(a))
