@@ -409,41 +409,10 @@ int tdeed_fill_u8_hash(uint8_t* dst, long n, uint64_t seed, void* stream); /* sy
  * aligned, a byte path otherwise.  B * T <= 65535. */
 int tdeed_clip_gather_u8(const uint8_t* video, int L, long frame_bytes, const int* starts, int B, int T,
                          uint8_t* clips_out, void* stream);
-/* clip_scores fp32 [V][n][T][K1] (V views of n clips), starts: DEVICE int32[n].  Per video frame f, over the clips i in the
- * order given with 0 <= f - starts[i] < T, view after view: track_sum[f] += clip_scores[v][i][f - starts[i]] and
- * support[f] += 1 (count_all = 1: always; count_all = 0: only when the added row has a non-zero entry).  track_sum [L][K1]
- * and support int32[L] are accumulated onto (the caller zeroes them); mean_out [L][K1] (or NULL) = track_sum /
- * float(max(support, 1)).  One thread per frame, fixed order, no atomics: bit-identical to the host loop of
- * util/eval.py:284-349. */
-int tdeed_stitch_scores(const float* clip_scores, int V, int n, int T, int K1, const int* starts, int count_all, int L,
-                        float* track_sum, int* support, float* mean_out, void* stream);
 
-/* ---- event spotting on the resident track (spot.hip) --------------------------------------------------------------
- * mean fp32 [L][K1] (tdeed_stitch_scores' mean_out).  pred int32[L]: first maximum of each row (np.argmax), pred_score
- * fp32[L] that entry.  Per class c >= 1 the frames with mean[f][c] >= hr_threshold (fp32 comparison, util/eval.py:160):
- * count[c] += their number, first_frame[c] = min(first_frame[c], the first of them).  pred_u8 (or NULL; K1 <= 256): pred in
- * one byte per frame, the form in which it is copied to the host.  The caller fills first_frame
- * int32[K1] with L and count int32[K1] with 0. */
-int tdeed_frame_events(const float* mean, int L, int K1, float hr_threshold, int* pred, unsigned char* pred_u8, float* pred_score,
-                       int* first_frame, int* count, void* stream);
-/* bytes of workspace tdeed_nms_track needs for this track (0: the suppression state fits the LDS of a workgroup) */
-long tdeed_nms_track_workspace(int L, int K1);
-/* Exact hard (soft = 0, util/eval.py:195-226) or soft (soft = 1, util/eval.py:228-261) non-maximum suppression of the
- * high-recall candidates of every class c >= 1 (frames with mean[f][c] >= hr_threshold, score (double)mean[f][c]), one
- * workgroup per class, in rounds (evalutil.nms_rounds states the rule); events are kept while their score is >= threshold
- * (double comparison).  windows: HOST int32[n_windows], n_windows = 1 (every class) or >= K1 - 1 (indexed by the rank of
- * (first_frame[c], c) among the classes that have a candidate: the order in which labels appear in the host's list); soft
- * needs windows >= 1.  first_frame: DEVICE int32[K1] as tdeed_frame_events leaves it.  emitted uint8 [K1][L] and kept_score
- * double [K1][L] are scratch.  Output: out_count[0] events in out_frame / out_class (int32) / out_score (double), each with
- * room for L * (K1 - 1) entries (out_class_u8, or NULL: the classes once more in one byte each, for the copy to the host), ordered by ascending frame and within a frame by that rank (the host's stable sort);
- * rounds int32[K1]: rounds taken per class (<= its candidates).  Deterministic; K1 - 1 <= 64. */
-int tdeed_nms_track(const float* mean, int L, int K1, float hr_threshold, double threshold, int soft, const int* windows,
-                    int n_windows, const int* first_frame, void* workspace, unsigned char* emitted, double* kept_score,
-                    int* out_frame, int* out_class, unsigned char* out_class_u8, double* out_score, int* out_count, int* rounds, void* stream);
-
-/* ---- a group of videos scored as one packed job (video.hip, spot.hip) ------------------------------------------------
- * The videos' frames sit one after the other in one buffer of L_total frames, their clips one after the other (video-major)
- * in one clip list; evalutil.group_clip_table builds the tables, all DEVICE int32: seg_off[nv+1] first packed frame of
+/* ---- videos scored as one packed job: gathers, score stitching (video.hip), event spotting (spot.hip) --------------------
+ * One video is a group of nv = 1 (seg_off = {0, L}, clip_off = {0, n}).  The videos' frames sit one after the other in one
+ * buffer of L_total frames, their clips one after the other (video-major) in one clip list; evalutil.group_clip_table builds the tables, all DEVICE int32: seg_off[nv+1] first packed frame of
  * every video (seg_off[nv] = L_total), clip_off[nv+1] first clip of every video, starts[n] video-local first frame of
  * every clip, clip_base[n] / clip_len_v[n] = seg_off / length of the clip's video.  nv <= 65535.  max_len: the longest
  * video of the group (sizes grids, workgroups and LDS; a video longer than max_len is left out).  A table entry that
@@ -462,26 +431,39 @@ int tdeed_rows_gather(const void* maps, int rows, long row_bytes, int L, int pad
                       void* stream);
 int tdeed_rows_gather_seg(const void* maps, int rows, long row_bytes, int L_total, int pad_row, const int* starts,
                           const int* clip_base, const int* clip_len_v, int B, int T, void* out, void* stream);
-/* tdeed_stitch_scores per video: one thread per packed frame walks only the clips clip_off[v] .. clip_off[v+1]-1 of its
- * video, in the order given, views inner -- per frame the additions of tdeed_stitch_scores on that video alone (same bits).
- * track_sum [L_total][K1], support [L_total] (accumulated onto), mean_out [L_total][K1] or NULL. */
+/* clip_scores fp32 [V][n][T][K1] (V views of the n clips of the group's list).  Per packed frame p of video v (f = p -
+ * seg_off[v]), over the clips i = clip_off[v] .. clip_off[v+1]-1 in the order given with 0 <= f - starts[i] < T, view after
+ * view: track_sum[p] += clip_scores[view][i][f - starts[i]] and support[p] += 1 (count_all = 1: always; count_all = 0: only
+ * when the added row has a non-zero entry).  track_sum [L_total][K1] and support int32[L_total] are accumulated onto (the
+ * caller zeroes them); mean_out [L_total][K1] (or NULL) = track_sum / float(max(support, 1)).  One thread per frame, fixed
+ * order, no atomics: per video bit-identical to the host loop of util/eval.py:284-349. */
 int tdeed_stitch_scores_seg(const float* clip_scores, int V, int n, int T, int K1, const int* starts, const int* seg_off,
                             const int* clip_off, int nv, int count_all, int L_total, float* track_sum, int* support,
                             float* mean_out, void* stream);
-/* tdeed_frame_events per video: pred / pred_u8 / pred_score per packed frame; first_frame int32 [nv][K1] in video-local
- * frames (the caller fills row v with the video's length), count int32 [nv][K1] (the caller zeroes it). */
+/* mean fp32 [L_total][K1] (tdeed_stitch_scores_seg's mean_out).  pred int32[L_total]: first maximum of each row (np.argmax),
+ * pred_score fp32[L_total] that entry; pred_u8 (or NULL; K1 <= 256): pred in one byte per frame, the form in which it is
+ * copied to the host.  Per video v and class c >= 1 the frames with mean[f][c] >= hr_threshold (fp32 comparison,
+ * util/eval.py:160): count[v][c] += their number, first_frame[v][c] = min(first_frame[v][c], the first of them), in
+ * video-local frames.  The caller fills row v of first_frame int32 [nv][K1] with the video's length and count int32 [nv][K1]
+ * with 0. */
 int tdeed_frame_events_seg(const float* mean, const int* seg_off, int nv, int L_total, int max_len, int K1, float hr_threshold,
                            int* pred, unsigned char* pred_u8, float* pred_score, int* first_frame, int* count, void* stream);
 /* bytes of workspace tdeed_nms_track_seg needs (0: max_len frames of suppression state fit the LDS of a workgroup) */
 long tdeed_nms_track_seg_workspace(int L_total, int max_len, int K1);
 /* threads of the suppression / compaction workgroups tdeed_nms_track_seg launches for this max_len */
 int tdeed_nms_track_seg_threads(int max_len);
-/* tdeed_nms_track per video, one workgroup per (class, video), same rule and arithmetic, video-local frames / windows /
- * ranks from first_frame [nv][K1] (tdeed_frame_events_seg).  emitted uint8 [K1][L_total], kept_score double [K1][L_total],
- * st_frame / st_class_u8 / st_score (L_total * (K1-1) entries each) and st_count int32[nv] are scratch.  Output: the kept
- * events of video v, in tdeed_nms_track's order with video-local frames, are entries event_off[v] .. event_off[v+1]-1 of
- * out_frame (int32) / out_class_u8 / out_score (double), each with room for L_total * (K1-1) entries: the videos' lists
- * follow each other densely in video order, event_off int32[nv+1].  rounds int32 [nv][K1].  Deterministic. */
+/* Exact hard (soft = 0, util/eval.py:195-226) or soft (soft = 1, util/eval.py:228-261) non-maximum suppression, per video,
+ * of the high-recall candidates of every class c >= 1 (frames with mean[f][c] >= hr_threshold, score (double)mean[f][c]),
+ * one workgroup per (class, video), in rounds (evalutil.nms_rounds states the rule); events are kept while their score is
+ * >= threshold (double comparison).  windows: HOST int32[n_windows], n_windows = 1 (every class) or >= K1 - 1 (indexed by the
+ * rank of (first_frame[v][c], c) among the classes of video v that have a candidate: the order in which labels appear in the
+ * host's list); soft needs windows >= 1.  first_frame: DEVICE int32 [nv][K1] as tdeed_frame_events_seg leaves it.  emitted
+ * uint8 [K1][L_total], kept_score double [K1][L_total], st_frame / st_class_u8 / st_score (L_total * (K1-1) entries each)
+ * and st_count int32[nv] are scratch.  Output: the kept events of video v, ordered by ascending video-local frame and within
+ * a frame by that rank (the host's stable sort), are entries event_off[v] .. event_off[v+1]-1 of out_frame (int32) /
+ * out_class_u8 / out_score (double), each with room for L_total * (K1-1) entries: the videos' lists follow each other
+ * densely in video order, event_off int32[nv+1].  rounds int32 [nv][K1]: rounds taken per class (<= its candidates).
+ * Deterministic; K1 - 1 <= 64. */
 int tdeed_nms_track_seg(const float* mean, const int* seg_off, int nv, int L_total, int max_len, int K1, float hr_threshold,
                         double threshold, int soft, const int* windows, int n_windows, const int* first_frame, void* workspace,
                         unsigned char* emitted, double* kept_score, int* st_frame, unsigned char* st_class_u8, double* st_score,

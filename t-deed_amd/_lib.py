@@ -176,10 +176,6 @@ _SIGS = {
     "tdeed_multi_cast_transpose": ([P, c_int, c_long, c_int, P], c_int),
     "tdeed_fill_u8_hash": ([P, c_long, c_uint64, P], c_int),
     "tdeed_clip_gather_u8": ([P, c_int, c_long, P, c_int, c_int, P, P], c_int),
-    "tdeed_stitch_scores": ([P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P], c_int),
-    "tdeed_frame_events": ([P, c_int, c_int, c_float, P, P, P, P, P, P], c_int),
-    "tdeed_nms_track_workspace": ([c_int, c_int], c_long),
-    "tdeed_nms_track": ([P, c_int, c_int, c_float, c_double, c_int, P, c_int, P, P, P, P, P, P, P, P, P, P, P], c_int),
     "tdeed_clip_gather_seg_u8": ([P, c_int, c_long, P, P, P, c_int, c_int, P, P], c_int),
     "tdeed_rows_gather": ([P, c_int, c_long, c_int, c_int, P, c_int, c_int, P, P], c_int),
     "tdeed_rows_gather_seg": ([P, c_int, c_long, c_int, c_int, P, P, P, c_int, c_int, P, P], c_int),

@@ -3,7 +3,7 @@
 #include "common.h"
 
 #define SPOT_MAX_CLASSES 64           // K1 - 1: the windows travel by value in the kernel arguments
-#define SPOT_NT 1024                  // threads of a suppression / compaction workgroup
+#define SPOT_NT 1024                  // threads of the largest suppression / compaction workgroup (tdeed_nms_track_seg_threads)
 #define SPOT_LDS_FRAMES 16000         // longest track whose suppression state (9 bytes per frame) stays in LDS
 #define SPOT_CB 8                     // flags a compaction thread loads at a time
 
@@ -12,50 +12,13 @@ struct SpotWindows {
 };
 
 // =========================================================================== frame events
-// One thread per frame: pred = first maximum of the row (np.argmax), pred_score = that entry; pred_u8 (optional, K1 <= 256)
-// the same index in one byte, the form in which it travels to the host.  Per class c >= 1 the frames
-// with mean[f][c] >= hr (fp32 comparison): their number and the first of them, one integer atomic pair per wave and class
-// (integer add / min: the result does not depend on the order).  first_frame arrives filled with L, count with 0.
-__global__ __launch_bounds__(256) void frame_events_kernel(const float* __restrict__ mean, int L, int K1, float hr,
-                                                           int* __restrict__ pred, unsigned char* __restrict__ pred_u8,
-                                                           float* __restrict__ pred_score, int* __restrict__ first_frame, int* __restrict__ count) {
-  const int f = blockIdx.x * 256 + threadIdx.x;
-  const bool in = f < L;
-  const float* row = mean + (long)(in ? f : 0) * K1;
-  const int wave_first = blockIdx.x * 256 + (threadIdx.x & ~63);
-  float best = row[0];
-  int bi = 0;
-  for (int k = 1; k < K1; ++k) {
-    const float x = row[k];
-    if (x > best) { best = x; bi = k; }
-    const unsigned long long m = __ballot(in && x >= hr);
-    if (m != 0ull && (threadIdx.x & 63) == 0) {
-      atomicAdd(count + k, __popcll(m));
-      atomicMin(first_frame + k, wave_first + (__ffsll((long long)m) - 1));
-    }
-  }
-  if (in) {
-    pred[f] = bi;
-    pred_score[f] = best;
-    if (pred_u8) pred_u8[f] = (unsigned char)bi;
-  }
-}
-
-extern "C" int tdeed_frame_events(const float* mean, int L, int K1, float hr_threshold, int* pred, unsigned char* pred_u8,
-                                  float* pred_score,
-                                  int* first_frame, int* count, void* stream) {
-  TD_CHECK(mean && pred && pred_score && first_frame && count, "frame_events: null pointer");
-  TD_CHECK(L > 0 && K1 > 1, "frame_events: bad sizes");
-  TD_CHECK(!pred_u8 || K1 <= 256, "frame_events: %d columns do not fit the one-byte prediction", K1);
-  hipLaunchKernelGGL(frame_events_kernel, dim3(cdiv(L, 256)), dim3(256), 0, (hipStream_t)stream, mean, L, K1, hr_threshold,
-                     pred, pred_u8, pred_score, first_frame, count);
-  TD_LAUNCH_CHECK("frame_events");
-  return TDEED_OK;
-}
-
-// Several videos packed one after the other: blockIdx.y = video, blockIdx.x = block of 256 frames inside it, so no wave
-// straddles two videos and the ballot / atomic pair per wave and class stays as above (workgroups past the end of a short
-// video leave at once).  Frames are video-local in first_frame [nv][K1] (filled with the video's length), count [nv][K1].
+// One thread per frame of a track that packs nv videos one after the other (one video: nv = 1): pred = first maximum of the
+// row (np.argmax), pred_score = that entry; pred_u8 (optional, K1 <= 256) the same index in one byte, the form in which it
+// travels to the host.  Per video and class c >= 1 the frames with mean[f][c] >= hr (fp32 comparison): their number and the
+// first of them, one integer atomic pair per wave and class (integer add / min: the result does not depend on the order).
+// blockIdx.y = video, blockIdx.x = block of 256 frames inside it, so no wave straddles two videos (workgroups past the end
+// of a short video leave at once).  Frames are video-local in first_frame [nv][K1] (arrives filled with the video's length),
+// count [nv][K1] (arrives 0).
 __global__ __launch_bounds__(256) void frame_events_seg_kernel(const float* __restrict__ mean, const int* __restrict__ seg_off,
                                                                int L_total, int K1, float hr, int* __restrict__ pred,
                                                                unsigned char* __restrict__ pred_u8, float* __restrict__ pred_score,
@@ -207,28 +170,7 @@ __device__ __forceinline__ void nms_track_body(const float* __restrict__ mean, i
   if (tid == 0) rounds_out[c] = rounds;
 }
 
-template <bool IN_LDS>
-__global__ __launch_bounds__(SPOT_NT) void nms_track_kernel(const float* __restrict__ mean, int L, int K1, float hr, double thr,
-                                                            int soft, SpotWindows win_list, int is_list,
-                                                            const int* __restrict__ first_frame, unsigned char* ws,
-                                                            unsigned char* __restrict__ emitted, double* __restrict__ kept_score,
-                                                            int* __restrict__ rounds_out) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char spot_smem[];
-  const int c = blockIdx.x + 1;
-  double* s;
-  unsigned char* win;
-  if (IN_LDS) {
-    s = reinterpret_cast<double*>(spot_smem);
-    win = spot_smem + (long)L * 8;
-  } else {
-    s = reinterpret_cast<double*>(ws) + (long)blockIdx.x * L;
-    win = ws + (long)(K1 - 1) * L * 8 + (long)blockIdx.x * L;
-  }
-  nms_track_body<SPOT_NT>(mean, L, K1, c, hr, thr, soft, win_list, is_list, first_frame, s, win, emitted + (long)c * L,
-                          kept_score + (long)c * L, rounds_out);
-}
-
-// Several videos packed one after the other: blockIdx.x + 1 = class, blockIdx.y = video.  The workgroup runs the body above on
+// blockIdx.x + 1 = class, blockIdx.y = video of the packed track.  The workgroup runs the body above on
 // its video's segment of the packed track with that video's first_frame row (video-local frames, windows and rank);
 // emitted / kept_score are [K1][L_total], the state in LDS is sized by the group's longest video, the workspace form keeps
 // [K1-1][L_total] doubles and as many bytes.  NT threads: chosen by the launcher from the longest video.
@@ -355,16 +297,7 @@ __device__ __forceinline__ void spot_compact_body(const unsigned char* __restric
   }
 }
 
-__global__ __launch_bounds__(SPOT_NT) void spot_compact_kernel(const unsigned char* __restrict__ emitted,
-                                                               const double* __restrict__ kept_score, int L, int K1,
-                                                               const int* __restrict__ first_frame, int* __restrict__ out_frame,
-                                                               int* __restrict__ out_class, unsigned char* __restrict__ out_class_u8,
-                                                               double* __restrict__ out_score,
-                                                               int* __restrict__ out_count) {
-  spot_compact_body<SPOT_NT>(emitted, kept_score, L, L, K1, first_frame, out_frame, out_class, out_class_u8, out_score, out_count);
-}
-
-// Several videos packed one after the other, three steps.  (1) One workgroup per video compacts its own list, in the order
+// The videos of a packed track, three steps.  (1) One workgroup per video compacts its own list, in the order
 // above, into the video's share of a staging list (room for L_v * (K1-1) events from seg_off[v] * (K1-1) on) and writes its
 // length.  (2) One workgroup turns the nv lengths into event_off[nv+1] (exclusive scan, every thread a contiguous run of
 // videos).  (3) One workgroup per video moves its staged list to event_off[v] of the dense list: the videos' lists follow each
@@ -440,57 +373,6 @@ __global__ __launch_bounds__(256) void spot_pack_events_kernel(const int* __rest
   }
 }
 
-extern "C" long tdeed_nms_track_workspace(int L, int K1) {
-  if (L <= SPOT_LDS_FRAMES || L <= 0 || K1 < 2) return 0;
-  return (long)(K1 - 1) * L * 9;
-}
-
-extern "C" int tdeed_nms_track(const float* mean, int L, int K1, float hr_threshold, double threshold, int soft,
-                               const int* windows, int n_windows, const int* first_frame, void* workspace,
-                               unsigned char* emitted, double* kept_score, int* out_frame, int* out_class, unsigned char* out_class_u8,
-                               double* out_score,
-                               int* out_count, int* rounds, void* stream) {
-  TD_CHECK(mean && windows && first_frame && emitted && kept_score && out_frame && out_class && out_score && out_count && rounds,
-           "nms_track: null pointer");
-  TD_CHECK(L > 0 && K1 > 1, "nms_track: bad sizes");
-  TD_CHECK(L <= (1 << 29), "nms_track: L = %d, at most 2^29 frames", L);
-  TD_CHECK(K1 - 1 <= SPOT_MAX_CLASSES, "nms_track: %d classes, at most %d", K1 - 1, SPOT_MAX_CLASSES);
-  TD_CHECK((long)L * (K1 - 1) < (1l << 31), "nms_track: L * classes = %ld does not fit the int32 event count", (long)L * (K1 - 1));
-  TD_CHECK(soft == 0 || soft == 1, "nms_track: soft must be 0 or 1");
-  TD_CHECK(n_windows == 1 || n_windows >= K1 - 1, "nms_track: %d windows for %d classes (one, or one per class)", n_windows, K1 - 1);
-  TD_CHECK(threshold == threshold && threshold > -__builtin_inf() && hr_threshold == hr_threshold && hr_threshold > -__builtin_inff(),
-           "nms_track: thresholds must be numbers above -inf");
-  SpotWindows wl = {};
-  for (int i = 0; i < (n_windows == 1 ? 1 : K1 - 1); ++i) {
-    TD_CHECK(windows[i] >= soft && windows[i] <= (1 << 30), "nms_track: window %d (soft suppression needs >= 1)", windows[i]);
-    wl.w[i] = windows[i];
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int is_list = n_windows == 1 ? 0 : 1;
-  if (L <= SPOT_LDS_FRAMES) {
-    static TdDevOnce once;
-    if (!once.get()) {
-      hipError_t e = hipFuncSetAttribute((const void*)nms_track_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         SPOT_LDS_FRAMES * 9);
-      if (e != hipSuccess) { tdeed_set_error("nms_track: hipFuncSetAttribute: %s", hipGetErrorString(e)); return TDEED_ERR_RUNTIME; }
-      once.set();
-    }
-    hipLaunchKernelGGL(nms_track_kernel<true>, dim3(K1 - 1), dim3(SPOT_NT), (size_t)L * 9, st, mean, L, K1, hr_threshold,
-                       threshold, soft, wl, is_list, first_frame, (unsigned char*)nullptr, emitted, kept_score, rounds);
-  } else {
-    TD_CHECK(workspace && ((uintptr_t)workspace & 7) == 0, "nms_track: L = %d needs an 8-byte aligned workspace of %ld bytes", L,
-             tdeed_nms_track_workspace(L, K1));
-    hipLaunchKernelGGL(nms_track_kernel<false>, dim3(K1 - 1), dim3(SPOT_NT), 0, st, mean, L, K1, hr_threshold, threshold, soft, wl,
-                       is_list, first_frame, (unsigned char*)workspace, emitted, kept_score, rounds);
-  }
-  TD_LAUNCH_CHECK("nms_track");
-  hipLaunchKernelGGL(spot_compact_kernel, dim3(1), dim3(SPOT_NT), 0, st, emitted, kept_score, L, K1, first_frame, out_frame,
-                     out_class, out_class_u8, out_score, out_count);
-  TD_LAUNCH_CHECK("spot_compact");
-  return TDEED_OK;
-}
-
-// ---- the same for a group of videos packed one after the other
 extern "C" long tdeed_nms_track_seg_workspace(int L_total, int max_len, int K1) {
   if (max_len <= SPOT_LDS_FRAMES || L_total <= 0 || max_len <= 0 || K1 < 2) return 0;
   return (long)(K1 - 1) * L_total * 9;

@@ -186,19 +186,9 @@ __device__ __forceinline__ void stitch_frame(const float* __restrict__ clip_scor
   }
 }
 
-__global__ __launch_bounds__(256) void stitch_scores_kernel(const float* __restrict__ clip_scores, int V, int n, int T, int K1,
-                                                            const int* __restrict__ starts, int count_all, int L,
-                                                            float* __restrict__ track_sum, int* __restrict__ support,
-                                                            float* __restrict__ mean_out) {
-  const int f = blockIdx.x * 256 + threadIdx.x;
-  if (f >= L) return;
-  stitch_frame(clip_scores, V, n, T, K1, starts, 0, n, count_all, f, track_sum + (long)f * K1, support + f,
-               mean_out ? mean_out + (long)f * K1 : nullptr);
-}
-
-// Several videos packed one after the other (evalutil.group_clip_table): one thread per packed frame p.  It finds its video
-// v (seg_off[v] <= p < seg_off[v+1], a binary search over the nv + 1 offsets) and walks only that video's clips
-// clip_off[v] .. clip_off[v+1] - 1, in the order given: per frame the additions of the one-video kernel on that video alone.
+// nv videos packed one after the other (evalutil.group_clip_table; one video: nv = 1): one thread per packed frame p.  It
+// finds its video v (seg_off[v] <= p < seg_off[v+1], a binary search over the nv + 1 offsets) and walks only that video's
+// clips clip_off[v] .. clip_off[v+1] - 1, in the order given: per frame the additions of ScoreStitcher on that video alone.
 __global__ __launch_bounds__(256) void stitch_scores_seg_kernel(const float* __restrict__ clip_scores, int V, int n, int T, int K1,
                                                                 const int* __restrict__ starts, const int* __restrict__ seg_off,
                                                                 const int* __restrict__ clip_off, int nv, int count_all, int L,
@@ -218,17 +208,6 @@ __global__ __launch_bounds__(256) void stitch_scores_seg_kernel(const float* __r
   TD_DEV_ASSERT(f >= 0 && p < seg_off[lo + 1]);
   stitch_frame(clip_scores, V, n, T, K1, starts, i0, i1, count_all, f, track_sum + (long)p * K1, support + p,
                mean_out ? mean_out + (long)p * K1 : nullptr);
-}
-
-extern "C" int tdeed_stitch_scores(const float* clip_scores, int V, int n, int T, int K1, const int* starts, int count_all,
-                                   int L, float* track_sum, int* support, float* mean_out, void* stream) {
-  TD_CHECK(clip_scores && starts && track_sum && support, "stitch_scores: null pointer");
-  TD_CHECK(V > 0 && n > 0 && T > 0 && K1 > 0 && L > 0, "stitch_scores: bad sizes");
-  TD_CHECK(count_all == 0 || count_all == 1, "stitch_scores: count_all must be 0 or 1");
-  hipLaunchKernelGGL(stitch_scores_kernel, dim3(cdiv(L, 256)), dim3(256), 0, (hipStream_t)stream, clip_scores, V, n, T, K1,
-                     starts, count_all, L, track_sum, support, mean_out);
-  TD_LAUNCH_CHECK("stitch_scores");
-  return TDEED_OK;
 }
 
 extern "C" int tdeed_stitch_scores_seg(const float* clip_scores, int V, int n, int T, int K1, const int* starts, const int* seg_off,

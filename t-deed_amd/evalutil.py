@@ -88,25 +88,10 @@ def video_clip_starts(num_frames, clip_len, overlap_len, stride=1, pad_len=5):
 
 
 def stitch_clip_scores(scores, starts, L, flip_scores=None):
-    """numpy twin of the stitch kernel (ops.stitch_scores), and the statement of its order: per video frame, over the clips
-    in the order given, the plain view's row and then the flipped view's row are added one after the other.
-    scores (n,T,K+1) fp32, starts: n first frames (may be negative / hang over L).  Without flip_scores support counts
-    the added rows that are not all zero (`ScoreStitcher.add`); with flip_scores (n,T,K+1) it counts every added row
-    (`ScoreStitcher.add_views`, once per view).  Returns (sums (L,K+1) float32, support (L,) int32) -- equal, bit for bit,
-    to what ScoreStitcher's clip-major loop leaves in its track."""
-    scores = np.asarray(scores, np.float32)
-    views = [scores] if flip_scores is None else [scores, np.asarray(flip_scores, np.float32)]
-    n, T, K1 = scores.shape
-    sums = np.zeros((L, K1), np.float32)
-    support = np.zeros(L, np.int32)
-    for f in range(L):
-        for i in range(n):
-            t = f - int(starts[i])
-            if 0 <= t < T:
-                for p in views:
-                    sums[f] += p[i, t]
-                    support[f] += 1 if (flip_scores is not None or np.any(p[i, t] != 0)) else 0
-    return sums, support
+    """`stitch_clip_scores_seg` for one video of L frames (a group of one): scores (n,T,K+1) fp32, starts: n first frames
+    (may be negative / hang over L).  Returns (sums (L,K+1) float32, support (L,) int32) -- equal, bit for bit, to what
+    ScoreStitcher's clip-major loop leaves in its track."""
+    return stitch_clip_scores_seg(scores, starts, [0, int(L)], [0, len(starts)], flip_scores)
 
 
 def group_clip_table(lengths, clip_len, overlap_len, pad_len=5, clip_starts=None):
@@ -192,16 +177,26 @@ def video_groups(lengths, frame_shapes, group_videos, max_resident_bytes):
 
 
 def stitch_clip_scores_seg(scores, starts, seg_off, clip_off, flip_scores=None):
-    """numpy twin of the segmented stitch kernel (ops.stitch_scores_seg): `stitch_clip_scores` per video of a group on the
-    clips clip_off[v]:clip_off[v+1] of the group's clip list.  Returns (sums (sum L,K+1), support (sum L,)) over the packed
-    frames."""
+    """numpy twin of the stitch kernel (ops.stitch_scores_seg), and the statement of its order: per frame of video v, over
+    that video's clips clip_off[v]:clip_off[v+1] of the group's clip list in the order given, the plain view's row and then
+    the flipped view's row are added one after the other.  scores (n,T,K+1) fp32, starts: n video-local first frames (may be
+    negative / hang over the video's end).  Without flip_scores support counts the added rows that are not all zero
+    (`ScoreStitcher.add`); with flip_scores (n,T,K+1) it counts every added row (`ScoreStitcher.add_views`, once per view).
+    Returns (sums (sum L,K+1) float32, support (sum L,) int32) over the packed frames."""
     scores = np.asarray(scores, np.float32)
-    sums = np.zeros((int(seg_off[-1]), scores.shape[2]), np.float32)
+    views = [scores] if flip_scores is None else [scores, np.asarray(flip_scores, np.float32)]
+    _, T, K1 = scores.shape
+    sums = np.zeros((int(seg_off[-1]), K1), np.float32)
     support = np.zeros(int(seg_off[-1]), np.int32)
     for v in range(len(seg_off) - 1):
-        a, b, lo, hi = int(seg_off[v]), int(seg_off[v + 1]), int(clip_off[v]), int(clip_off[v + 1])
-        sums[a:b], support[a:b] = stitch_clip_scores(scores[lo:hi], starts[lo:hi], b - a,
-                                                     None if flip_scores is None else np.asarray(flip_scores)[lo:hi])
+        a, b = int(seg_off[v]), int(seg_off[v + 1])
+        for f in range(b - a):
+            for i in range(int(clip_off[v]), int(clip_off[v + 1])):
+                t = f - int(starts[i])
+                if 0 <= t < T:
+                    for p in views:
+                        sums[a + f] += p[i, t]
+                        support[a + f] += 1 if (flip_scores is not None or np.any(p[i, t] != 0)) else 0
     return sums, support
 
 
@@ -218,23 +213,25 @@ def _with_loader(videos, decode):
             for name, length, fps, src in videos]
 
 
-def _decoded_groups(videos, group_videos, max_resident_bytes):
+def _decoded_groups(videos, group_videos, max_resident_bytes, decode_ahead=1):
     """The sources of `videos` (name, length, fps, frames | callable) in groups: batches of `group_videos` consecutive
-    videos are materialised -- callables on a worker thread, one batch ahead of the consumer -- and each batch is then
-    split by `video_groups` (budget, geometry).  Yields lists of (name, length, fps, frames)."""
+    videos are materialised -- callables on a worker thread, up to `decode_ahead` batches ahead of the consumer -- and each
+    batch is then split by `video_groups` (budget, geometry).  Yields lists of (name, length, fps, frames)."""
     from concurrent.futures import ThreadPoolExecutor
     import torch
-    gv = int(group_videos)
+    gv, ahead = int(group_videos), max(int(decode_ahead), 0)
     batches = [videos[lo:lo + gv] for lo in range(0, len(videos), gv)]
 
     def decode(batch):
         return [src() if callable(src) else src for _, _, _, src in batch]
 
     with ThreadPoolExecutor(max_workers=1, thread_name_prefix="tdeed-video") as ex:
-        fut = ex.submit(decode, batches[0]) if batches else None
+        pending = {}
         for bi, batch in enumerate(batches):
-            frames = fut.result()
-            fut = ex.submit(decode, batches[bi + 1]) if bi + 1 < len(batches) else None
+            for k in range(bi, min(bi + ahead + 1, len(batches))):
+                if k not in pending:
+                    pending[k] = ex.submit(decode, batches[k])
+            frames = pending.pop(bi).result()
             frames = [f if isinstance(f, torch.Tensor) else torch.as_tensor(np.asarray(f)) for f in frames]
             for (name, length, _, _), f in zip(batch, frames):
                 if int(f.shape[0]) != int(length):
@@ -247,49 +244,22 @@ def stitch_videos(model, videos, n_cols, augment=False, batch_size=8, overlap_le
                   max_resident_bytes=16 << 30, reuse_frames=False, decode="host"):
     """Whole-video counterpart of `stitch_predictions`: `videos` yields (name, length, fps, frames) with frames a uint8
     (length,3,H,W) tensor of the sampled frames or a callable returning one (e.g. a `feeder.load_video` closure); every
-    video goes through `model.predict_video` once and its (sums, support) become the video's track of the returned
-    ScoreStitcher, so `normalised()`, `frame_events`, both NMS functions and `mean_average_precisions` work on it
-    unchanged.  Callables run up to `decode_ahead` videos ahead on a worker thread: decoding video v+1 overlaps scoring
-    video v.
-    group_videos > 1: up to that many consecutive videos (as far as `max_resident_bytes` and one frame geometry allow,
-    `video_groups`) go through `model.predict_video_group` as one packed job whose batches are cut across the videos; the
-    callables of the next `group_videos` videos are decoded on the worker thread meanwhile.
-    reuse_frames: passed on to `predict_video` / `predict_video_group` (the per-frame trunk stages once per frame).
+    video is scored once and its (sums, support) become the video's track of the returned ScoreStitcher, so
+    `normalised()`, `frame_events`, both NMS functions and `mean_average_precisions` work on it unchanged.
+    group_videos: up to that many consecutive videos (as far as `max_resident_bytes` and one frame geometry allow,
+    `video_groups`) go through `model.predict_video_group` as one packed job whose batches are cut across the videos; 1
+    (the default) scores video by video, each a group of one.  The callables of the next `decode_ahead` batches of
+    `group_videos` videos are decoded on a worker thread meanwhile: decoding overlaps scoring.
+    reuse_frames: passed on to `predict_video_group` (the per-frame trunk stages once per frame).
     decode: a `frames` entry may also be a dict of `feeder.load_video` keyword arguments; "host" loads it with
     `feeder.load_video`, "device" with `feeder.load_video_device` (JPEG decode on the device, same frames)."""
-    from concurrent.futures import ThreadPoolExecutor
     videos = _with_loader(list(videos), decode)
     reuse = dict(reuse_frames=True) if reuse_frames else {}
     st = ScoreStitcher([(v, n, f) for v, n, f, _ in videos], n_cols)
-    if int(group_videos) > 1:
-        for group in _decoded_groups(videos, group_videos, max_resident_bytes):
-            out = model.predict_video_group([g[3] for g in group], overlap_len=overlap_len, batch_size=batch_size,
-                                            augment=augment, max_resident_bytes=max_resident_bytes, **reuse)
-            for (name, _, _, _), (sums, support) in zip(group, out):
-                if sums.shape[1] != n_cols:
-                    raise ValueError(f"video {name}: the model scores {sums.shape[1]} columns, the stitcher holds {n_cols}")
-                track, sup = st.tracks[name]
-                track[...] = sums
-                sup[...] = support
-        return st
-    ahead = max(int(decode_ahead), 0)
-    with ThreadPoolExecutor(max_workers=1, thread_name_prefix="tdeed-video") as ex:
-        pending = {}
-
-        def fetch(j):
-            if j < len(videos) and j not in pending:
-                src = videos[j][3]
-                pending[j] = ex.submit(src) if callable(src) else None
-
-        for j, (name, length, _, src) in enumerate(videos):
-            for k in range(j, j + ahead + 1):
-                fetch(k)
-            fut = pending.pop(j)
-            frames = src if fut is None else fut.result()
-            if int(frames.shape[0]) != int(length):
-                raise ValueError(f"video {name}: {int(frames.shape[0])} frames delivered, {int(length)} announced")
-            sums, support = model.predict_video(frames, overlap_len=overlap_len, batch_size=batch_size, augment=augment,
-                                                      **reuse)
+    for group in _decoded_groups(videos, group_videos, max_resident_bytes, decode_ahead):
+        out = model.predict_video_group([g[3] for g in group], overlap_len=overlap_len, batch_size=batch_size,
+                                        augment=augment, max_resident_bytes=max_resident_bytes, **reuse)
+        for (name, _, _, _), (sums, support) in zip(group, out):
             if sums.shape[1] != n_cols:
                 raise ValueError(f"video {name}: the model scores {sums.shape[1]} columns, the stitcher holds {n_cols}")
             track, sup = st.tracks[name]
@@ -478,47 +448,23 @@ def spot_videos(model, videos, classes, suppress, high_recall_score_threshold=0.
                 overlap_len=None, decode_ahead=1, group_videos=1, max_resident_bytes=16 << 30, reuse_frames=False,
                 decode="host"):
     """Whole-video counterpart of `stitch_videos` + `frame_events` + the two NMS functions with the tail on the device:
-    `videos` as in `stitch_videos`; every video goes through `model.spot_video` once.  suppress: entries (kind, window,
+    `videos` as in `stitch_videos`; every video is scored and spotted once.  suppress: entries (kind, window,
     threshold) with kind "nms" | "snms".  Returns (pred_events, [one list of video records per suppress entry],
     {video: pred (L,) int32}), videos in sorted order, records as `frame_events` / `non_maximum_suppression` /
     `soft_non_maximum_suppression` build them ('num_events' included), so `mean_average_precisions` works on them
     unchanged.  The label-dependent error / F1 counters of `frame_events` follow from the returned pred on the host.
-    group_videos > 1: groups of videos go through `model.spot_video_group` as in `stitch_videos`.  reuse_frames: passed on
-    to `spot_video` / `spot_video_group`.  decode: as in `stitch_videos`."""
-    from concurrent.futures import ThreadPoolExecutor
+    group_videos / decode_ahead: groups of videos go through `model.spot_video_group` as in `stitch_videos`.  reuse_frames:
+    passed on to `spot_video_group`.  decode: as in `stitch_videos`."""
     videos = _with_loader(list(videos), decode)
     reuse = dict(reuse_frames=True) if reuse_frames else {}
     suppress = [tuple(e) for e in suppress]
     done = {}
-    if int(group_videos) > 1:
-        for group in _decoded_groups(videos, group_videos, max_resident_bytes):
-            out = model.spot_video_group([g[3] for g in group], classes, suppress=suppress,
-                                         high_recall_score_threshold=high_recall_score_threshold, overlap_len=overlap_len,
-                                         batch_size=batch_size, augment=augment, max_resident_bytes=max_resident_bytes,
-                                         **reuse)
-            for (name, _, fps, _), r in zip(group, out):
-                done[name] = (fps, r)
-    else:
-        ahead = max(int(decode_ahead), 0)
-        with ThreadPoolExecutor(max_workers=1, thread_name_prefix="tdeed-video") as ex:
-            pending = {}
-
-            def fetch(j):
-                if j < len(videos) and j not in pending:
-                    src = videos[j][3]
-                    pending[j] = ex.submit(src) if callable(src) else None
-
-            for j, (name, length, fps, src) in enumerate(videos):
-                for k in range(j, j + ahead + 1):
-                    fetch(k)
-                fut = pending.pop(j)
-                frames = src if fut is None else fut.result()
-                if int(frames.shape[0]) != int(length):
-                    raise ValueError(f"video {name}: {int(frames.shape[0])} frames delivered, {int(length)} announced")
-                done[name] = (fps, model.spot_video(frames, classes, suppress=suppress,
-                                                    high_recall_score_threshold=high_recall_score_threshold,
-                                                    overlap_len=overlap_len, batch_size=batch_size, augment=augment,
-                                                    **reuse))
+    for group in _decoded_groups(videos, group_videos, max_resident_bytes, decode_ahead):
+        out = model.spot_video_group([g[3] for g in group], classes, suppress=suppress,
+                                     high_recall_score_threshold=high_recall_score_threshold, overlap_len=overlap_len,
+                                     batch_size=batch_size, augment=augment, max_resident_bytes=max_resident_bytes, **reuse)
+        for (name, _, fps, _), r in zip(group, out):
+            done[name] = (fps, r)
     pred_events, lists, preds = [], [[] for _ in suppress], {}
     for name in sorted(done):
         fps, r = done[name]

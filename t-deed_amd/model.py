@@ -389,31 +389,22 @@ class TDEEDModel:
         Host frames are uploaded ONCE, in chunks of `video_chunk_bytes` on a copy stream; a batch waits only for the chunk
         that holds its last frame.  Clip windows are gathered on the device into the engine's input buffers, consecutive
         batches alternate over two engine slots / streams like epoch()'s validation loop, the clip scores stay on the
-        device and one stitch launch (ops.stitch_scores) adds them per frame in ScoreStitcher's order.  Apart from the
+        device and one stitch launch (ops.stitch_scores_seg) adds them per frame in ScoreStitcher's order.  Apart from the
         warm-up of a geometry seen for the first time (graph capture) the host synchronises once per video.
         Raises ValueError when the video does not fit `max_resident_bytes`.
 
         reuse_frames=True: the trunk stages in front of the first gate-shift site (stem and blocks [0, k), k =
         `ForwardEngine.first_site_block()`; functions of one frame alone in eval mode) run ONCE per frame and view, in chunks
         of `frame_batch` clips' worth of consecutive frames, into a resident map of the block-k inputs; a batch gathers its
-        windows from that map (ops.rows_gather, the row of a black frame as padding) and runs only the rest of the network
+        windows from that map (ops.rows_gather_seg, the row of a black frame as padding) and runs only the rest of the network
         (`ForwardEngine.forward_from_frame_maps`).  The maps count towards `max_resident_bytes`; last_video_stats gains
         frame_pass_frames (views x rows of the map) and map_bytes.  The launches are those of the engine's join_at = k
         plan: same scores bit for bit where that plan would have served the batch (an even batch size), the first site's
         launch form otherwise."""
-        track, support, _, s0, stats, keep = self._video_track(frames, clip_starts, overlap_len, pad_len, batch_size, augment,
-                                                               use_amp, max_resident_bytes, want_mean=False,
-                                                               reuse_frames=reuse_frames)
-        L, K1 = track.shape
-        with torch.cuda.stream(s0):
-            out_sum = torch.empty((L, K1), dtype=torch.float32).pin_memory()
-            out_sup = torch.empty((L,), dtype=torch.int32).pin_memory()
-            out_sum.copy_(track, non_blocking=True)
-            out_sup.copy_(support, non_blocking=True)
-            s0.synchronize()
-        del keep
-        self.last_video_stats = stats
-        return out_sum.numpy().copy(), out_sup.numpy().copy()
+        out = self._predict_videos("predict_video", [frames], None if clip_starts is None else [clip_starts], overlap_len, pad_len,
+                                   batch_size, augment, use_amp, max_resident_bytes, reuse_frames)
+        self._one_video_stats()
+        return out[0]
 
     def spot_video(self, frames, classes, suppress=(("nms", 1, 0.01), ("snms", 3, 0.01)), high_recall_score_threshold=0.01,
                    clip_starts=None, overlap_len=None, pad_len=5, batch_size=8, augment=False, use_amp=True,
@@ -430,59 +421,15 @@ class TDEEDModel:
         every event list.  Class indices travel as one byte (pred: 1 + 4 bytes per frame with its score; an event: frame
         int32, class uint8, score float64 = 13 bytes), which limits K+1 to 256 columns here.  last_video_stats gains events_d2h_bytes and nms_rounds (per suppress entry, the maximum over
         the classes)."""
-        from . import evalutil
-        suppress = [tuple(e) for e in suppress]
-        for kind, window, _ in suppress:
-            if kind not in ("nms", "snms"):
-                raise ValueError(f"spot_video: suppression kind {kind!r} (nms | snms)")
-        inv = {v: k for k, v in classes.items()}
-        K1 = self._score_cols(torch.bfloat16 if use_amp else torch.float32)
-        if K1 > 256:
-            raise ValueError(f"spot_video: {K1} score columns, at most 256")
-        if sorted(inv) != list(range(1, K1)):
-            raise ValueError(f"spot_video: classes must name the indices 1..{K1 - 1} of the model's score columns")
-        track, _, mean, s0, stats, keep = self._video_track(frames, clip_starts, overlap_len, pad_len, batch_size, augment,
-                                                            use_amp, max_resident_bytes, want_mean=True,
-                                                            reuse_frames=reuse_frames)
-        L = track.shape[0]
-        hr = float(high_recall_score_threshold)
-        n = len(suppress)
-        with torch.cuda.stream(s0):
-            pred8 = torch.empty((L,), dtype=torch.uint8, device=mean.device)
-            _, pred_score, first, _ = ops.frame_events(mean, hr, pred_u8=pred8)
-            cls8 = [torch.empty((L * (K1 - 1),), dtype=torch.uint8, device=mean.device) for _ in suppress]
-            lists = [ops.nms_track(mean, window, thr, kind == "snms", hr, first_frame=first, classes_u8=c8)
-                     for (kind, window, thr), c8 in zip(suppress, cls8)]
-            h_pred = torch.empty((L,), dtype=torch.uint8).pin_memory()
-            h_score = torch.empty((L,), dtype=torch.float32).pin_memory()
-            h_small = torch.empty((n, 1 + K1), dtype=torch.int32).pin_memory()       # count, rounds per class
-            h_pred.copy_(pred8, non_blocking=True)
-            h_score.copy_(pred_score, non_blocking=True)
-            for i, (_, _, _, count, rounds) in enumerate(lists):
-                h_small[i, :1].copy_(count, non_blocking=True)
-                h_small[i, 1:].copy_(rounds, non_blocking=True)
-            s0.synchronize()
-            counts = [int(h_small[i, 0]) for i in range(n)]
-            host = []
-            for (fr, _, sc, _, _), c8, m in zip(lists, cls8, counts):
-                bufs = (torch.empty((m,), dtype=torch.int32).pin_memory(), torch.empty((m,), dtype=torch.uint8).pin_memory(),
-                        torch.empty((m,), dtype=torch.float64).pin_memory())
-                if m:
-                    for dst, src in zip(bufs, (fr, c8, sc)):
-                        dst.copy_(src[:m], non_blocking=True)
-                host.append(bufs)
-            if any(counts):
-                s0.synchronize()
-        del keep
-        pred_np = h_pred.numpy().astype(np.int32)
-        score_np = h_score.numpy()
-        fg = np.nonzero(pred_np != 0)[0]
-        events = [{"label": inv[int(pred_np[i])], "frame": int(i), "score": float(score_np[i])} for i in fg]
-        suppressed = [evalutil.event_dicts(f.numpy(), c.numpy(), s.numpy(), inv) for f, c, s in host]
-        stats["events_d2h_bytes"] = L * 5 + n * (1 + K1) * 4 + 13 * sum(counts)
-        stats["nms_rounds"] = [int(h_small[i, 1:].max()) for i in range(n)]
-        self.last_video_stats = stats
-        return dict(pred=pred_np, events=events, suppressed=suppressed)
+        out = self._spot_videos("spot_video", [frames], classes, suppress, high_recall_score_threshold,
+                                None if clip_starts is None else [clip_starts], overlap_len, pad_len, batch_size, augment, use_amp,
+                                max_resident_bytes, reuse_frames)
+        self._one_video_stats()
+        return out[0]
+
+    def _one_video_stats(self):
+        """last_video_stats of the one-video methods: the group's keys without the group's own (videos, host_syncs)"""
+        self.last_video_stats = {k: v for k, v in self.last_video_stats.items() if k not in ("videos", "host_syncs")}
 
     def predict_video_group(self, frames_list, clip_starts=None, overlap_len=None, pad_len=5, batch_size=8, augment=False,
                             use_amp=True, max_resident_bytes=16 << 30, reuse_frames=False):
@@ -499,9 +446,15 @@ class TDEEDModel:
         from the warm-up of a geometry seen for the first time the host synchronises once per group.
         last_video_stats: predict_video's keys as totals over the group, plus videos and host_syncs.
         Raises ValueError for an empty list, an empty video, mixed geometries or a group over `max_resident_bytes`."""
-        track, support, _, s0, stats, keep, g = self._packed_track(
-            "predict_video_group", list(frames_list), clip_starts, overlap_len, pad_len, batch_size, augment, use_amp,
-            max_resident_bytes, want_mean=False, group=True, reuse_frames=reuse_frames)
+        return self._predict_videos("predict_video_group", list(frames_list), clip_starts, overlap_len, pad_len, batch_size,
+                                    augment, use_amp, max_resident_bytes, reuse_frames)
+
+    def _predict_videos(self, who, frames_list, clip_starts, overlap_len, pad_len, batch_size, augment, use_amp,
+                        max_resident_bytes, reuse_frames):
+        """predict_video_group under the name `who` (the prefix of its errors): predict_video is the group of one video."""
+        track, support, _, s0, stats, keep, g = self._packed_track(who, frames_list, clip_starts, overlap_len, pad_len, batch_size,
+                                                                   augment, use_amp, max_resident_bytes, want_mean=False,
+                                                                   reuse_frames=reuse_frames)
         L, K1 = track.shape
         with torch.cuda.stream(s0):
             out_sum = torch.empty((L, K1), dtype=torch.float32).pin_memory()
@@ -524,20 +477,26 @@ class TDEEDModel:
         lists one after the other in video order.  The host synchronises twice per group: once for pred bytes, their scores,
         the event offsets and the rounds, once for one contiguous range of events per entry (skipped when nothing was
         kept).  last_video_stats: totals over the group; nms_rounds per entry is the maximum over videos and classes."""
+        return self._spot_videos("spot_video_group", list(frames_list), classes, suppress, high_recall_score_threshold,
+                                 clip_starts, overlap_len, pad_len, batch_size, augment, use_amp, max_resident_bytes, reuse_frames)
+
+    def _spot_videos(self, who, frames_list, classes, suppress, high_recall_score_threshold, clip_starts, overlap_len, pad_len,
+                     batch_size, augment, use_amp, max_resident_bytes, reuse_frames):
+        """spot_video_group under the name `who` (the prefix of its errors): spot_video is the group of one video."""
         from . import evalutil
         suppress = [tuple(e) for e in suppress]
         for kind, window, _ in suppress:
             if kind not in ("nms", "snms"):
-                raise ValueError(f"spot_video_group: suppression kind {kind!r} (nms | snms)")
+                raise ValueError(f"{who}: suppression kind {kind!r} (nms | snms)")
         inv = {v: k for k, v in classes.items()}
         K1 = self._score_cols(torch.bfloat16 if use_amp else torch.float32)
         if K1 > 256:
-            raise ValueError(f"spot_video_group: {K1} score columns, at most 256")
+            raise ValueError(f"{who}: {K1} score columns, at most 256")
         if sorted(inv) != list(range(1, K1)):
-            raise ValueError(f"spot_video_group: classes must name the indices 1..{K1 - 1} of the model's score columns")
-        track, _, mean, s0, stats, keep, g = self._packed_track(
-            "spot_video_group", list(frames_list), clip_starts, overlap_len, pad_len, batch_size, augment, use_amp,
-            max_resident_bytes, want_mean=True, group=True, reuse_frames=reuse_frames)
+            raise ValueError(f"{who}: classes must name the indices 1..{K1 - 1} of the model's score columns")
+        track, _, mean, s0, stats, keep, g = self._packed_track(who, frames_list, clip_starts, overlap_len, pad_len, batch_size,
+                                                                augment, use_amp, max_resident_bytes, want_mean=True,
+                                                                reuse_frames=reuse_frames)
         L, nv = track.shape[0], g.nv
         hr = float(high_recall_score_threshold)
         n = len(suppress)
@@ -549,16 +508,18 @@ class TDEEDModel:
                      for kind, window, thr in suppress]
             h_pred = torch.empty((L,), dtype=torch.uint8).pin_memory()
             h_score = torch.empty((L,), dtype=torch.float32).pin_memory()
-            h_small = torch.empty((n, nv + 1 + nv * K1), dtype=torch.int32).pin_memory()     # event offsets, rounds
+            # per entry the ends of the videos' event lists (event_off[1:]; event_off[0] is 0) and the rounds
+            h_small = torch.empty((n, nv + nv * K1), dtype=torch.int32).pin_memory()
             h_pred.copy_(pred8, non_blocking=True)
             h_score.copy_(pred_score, non_blocking=True)
             for i, (_, _, _, event_off, rounds) in enumerate(lists):
-                h_small[i, :nv + 1].copy_(event_off, non_blocking=True)
-                h_small[i, nv + 1:].copy_(rounds.view(-1), non_blocking=True)
+                h_small[i, :nv].copy_(event_off[1:], non_blocking=True)
+                h_small[i, nv:].copy_(rounds.view(-1), non_blocking=True)
             s0.synchronize()
             syncs = 1
             small = h_small.numpy()
-            totals = [int(small[i, nv]) for i in range(n)]
+            ends = [[0] + small[i, :nv].tolist() for i in range(n)]
+            totals = [e[-1] for e in ends]
             host = []
             for (fr, c8, sc, _, _), m in zip(lists, totals):
                 bufs = (torch.empty((m,), dtype=torch.int32).pin_memory(), torch.empty((m,), dtype=torch.uint8).pin_memory(),
@@ -580,34 +541,26 @@ class TDEEDModel:
             fg = np.nonzero(pred_np != 0)[0]
             events = [{"label": inv[int(pred_np[i])], "frame": int(i), "score": float(score_np[i])} for i in fg]
             suppressed = []
-            for i, (f, c, s_) in enumerate(host):
-                e0, e1 = int(small[i, v]), int(small[i, v + 1])
-                suppressed.append(evalutil.event_dicts(f[e0:e1], c[e0:e1], s_[e0:e1], inv))
+            for (f, c, s_), e in zip(host, ends):
+                suppressed.append(evalutil.event_dicts(f[e[v]:e[v + 1]], c[e[v]:e[v + 1]], s_[e[v]:e[v + 1]], inv))
             out.append(dict(pred=pred_np, events=events, suppressed=suppressed))
-        stats["events_d2h_bytes"] = L * 5 + n * (nv + 1 + nv * K1) * 4 + 13 * sum(totals)
-        stats["nms_rounds"] = [int(small[i, nv + 1:].max()) for i in range(n)]
+        stats["events_d2h_bytes"] = L * 5 + n * (nv + nv * K1) * 4 + 13 * sum(totals)
+        stats["nms_rounds"] = [int(small[i, nv:].max()) for i in range(n)]
         stats["host_syncs"] = syncs
         self.last_video_stats = stats
         return out
 
-    def _video_track(self, frames, clip_starts, overlap_len, pad_len, batch_size, augment, use_amp, max_resident_bytes,
-                     want_mean, reuse_frames=False):
-        """The body of predict_video up to and including the stitch launch, nothing synchronised: -> (track (L,K+1) fp32,
-        support (L,) int32, mean (L,K+1) fp32 | None: device tensors written on stream s0; s0; the last_video_stats dict; the
-        resident buffers, to be kept alive until s0 has been synchronised)."""
-        return self._packed_track("predict_video", [frames], clip_starts, overlap_len, pad_len, batch_size, augment, use_amp,
-                                  max_resident_bytes, want_mean, group=False, reuse_frames=reuse_frames)[:6]
-
     frame_batch = 2                     # clips' worth of frames per launch of the per-frame pass (reuse_frames=True)
 
     def _packed_track(self, who, frames_list, clip_starts, overlap_len, pad_len, batch_size, augment, use_amp,
-                      max_resident_bytes, want_mean, group, reuse_frames=False):
-        """One or several videos through upload, batches and the stitch launch, nothing synchronised.  group=False: one video,
-        clip_starts its flat list (what `_video_track` returns, through ops.clip_gather / ops.stitch_scores).  group=True:
-        the videos are packed one after the other into one resident buffer and one clip list (evalutil.group_clip_table,
-        clip_starts one list per video), batches are cut from that list across the videos, the gathers and the stitch are
-        the segmented kernels; track / support / mean cover the packed frames.  -> `_video_track`'s tuple plus a namespace
-        of the group's tables (None for group=False).
+                      max_resident_bytes, want_mean, reuse_frames=False):
+        """A group of videos (one video: a group of one) through upload, batches and the stitch launch, nothing synchronised.
+        The videos are packed one after the other into one resident buffer -- a single video that is on the device already
+        is used where it is -- and one clip list (evalutil.group_clip_table, clip_starts one list per video), batches are
+        cut from that list across the videos, the gathers and the stitch are the segmented kernels.  -> (track (sum L,K+1)
+        fp32, support (sum L,) int32, mean (sum L,K+1) fp32 | None: device tensors over the packed frames, written on stream
+        s0; s0; the last_video_stats dict; the resident buffers, to be kept alive until s0 has been synchronised; a
+        namespace of the group's tables).  who: the public method, the prefix of the errors.
         reuse_frames: the per-frame trunk stages run once per (packed) frame and view into a resident map, chunk by chunk on a
         stream of their own with an event per chunk -- the chunk with the first black row (the padding of every window)
         first, then in frame order; a batch waits for the chunk that holds its last frame and runs the rest of the network
@@ -635,22 +588,15 @@ class TDEEDModel:
         fb = int(srcs[0][0].numel())
         if nv > ops.MAX_GROUP_VIDEOS:
             raise ValueError(f"{who}: {nv} videos in one group, at most {ops.MAX_GROUP_VIDEOS}")
+        what = "group" if who.endswith("_group") else "video"
         if L * fb > max_resident_bytes:
-            raise ValueError(f"{who}: the {'group' if group else 'video'} needs {L * fb} bytes on the device, more than "
+            raise ValueError(f"{who}: the {what} needs {L * fb} bytes on the device, more than "
                              f"max_resident_bytes={max_resident_bytes} (a ring buffer for longer videos is not implemented)")
         T = self._args.clip_len
         ov = T // 4 * 3 if overlap_len is None else int(overlap_len)
-        if group:
-            seg_off, clip_off, starts_np, base_np, lenv_np = evalutil.group_clip_table(lengths, T, ov, pad_len, clip_starts)
-            starts, base, len_v = starts_np.tolist(), base_np.tolist(), lenv_np.tolist()
-        else:
-            if clip_starts is None:
-                clip_starts = evalutil.video_clip_starts(L, T, ov, pad_len=pad_len)
-            starts = [int(s) for s in clip_starts]
-            base, len_v = [0] * len(starts), [L] * len(starts)
+        seg_off, clip_off, starts_np, base_np, lenv_np = evalutil.group_clip_table(lengths, T, ov, pad_len, clip_starts)
+        starts, base, len_v = starts_np.tolist(), base_np.tolist(), lenv_np.tolist()
         n = len(starts)
-        if n == 0:
-            raise ValueError(f"{who}: no clips")
         if batch_size < 1:
             raise ValueError(f"{who}: batch_size must be positive")
         # last packed frame a clip reads (-1: none before the front of its video)
@@ -668,7 +614,7 @@ class TDEEDModel:
             rows, pad_row, chunk = evalutil.frame_map_rows(L, T, Bf)
             map_bytes = V * rows * mh * mw * mc * (2 if dt == torch.bfloat16 else 4)
             if L * fb + map_bytes > max_resident_bytes:
-                raise ValueError(f"{who}: the {'group' if group else 'video'} needs {L * fb + map_bytes} bytes on the device "
+                raise ValueError(f"{who}: the {what} needs {L * fb + map_bytes} bytes on the device "
                                  f"({map_bytes} of them per-frame maps), more than max_resident_bytes={max_resident_bytes} "
                                  "(a ring buffer for longer videos is not implemented)")
         if self._stream is None:
@@ -686,27 +632,21 @@ class TDEEDModel:
                 self._frame_stream = new_stream(avoid=[self._stream, self._stream2, self._copy_stream])
             self._frame_stream.wait_stream(cur)
         # ---- the resident buffers (kept alive until the one synchronisation at the end); the tables travel in one copy
-        g = None
-        if group:
-            first_init = np.repeat(np.asarray(lengths, np.int32), K1)
-            parts = [starts_np, base_np, lenv_np, seg_off, clip_off, first_init]
-            tab_host = torch.from_numpy(np.concatenate(parts)).pin_memory()
-        else:
-            tab_host = torch.tensor(starts, dtype=torch.int32).pin_memory()
+        first_init = np.repeat(np.asarray(lengths, np.int32), K1)
+        parts = [starts_np, base_np, lenv_np, seg_off, clip_off, first_init]
+        tab_host = torch.from_numpy(np.concatenate(parts)).pin_memory()
         tab_dev = torch.empty((tab_host.numel(),), dtype=torch.int32, device=dev)
         clip_scores = torch.empty((V, n, T, K1), dtype=torch.float32, device=dev)
         with torch.cuda.stream(cp):
             tab_dev.copy_(tab_host, non_blocking=True)
             ev_starts = torch.cuda.Event()
             ev_starts.record(cp)
-        starts_dev = tab_dev[:n]
-        if group:
-            cuts = np.cumsum([0] + [len(x) for x in parts]).tolist()
-            base_dev, lenv_dev, seg_dev, coff_dev, first_dev = (tab_dev[cuts[i]:cuts[i + 1]] for i in range(1, 6))
-            g = SimpleNamespace(nv=nv, lengths=lengths, seg_off=seg_off, max_len=max(lengths), seg_off_dev=seg_dev,
-                                first_init=first_dev.view(nv, K1), K1=K1)
+        cuts = np.cumsum([0] + [len(x) for x in parts]).tolist()
+        starts_dev, base_dev, lenv_dev, seg_dev, coff_dev, first_dev = (tab_dev[cuts[i]:cuts[i + 1]] for i in range(6))
+        g = SimpleNamespace(nv=nv, lengths=lengths, seg_off=seg_off, max_len=max(lengths), seg_off_dev=seg_dev,
+                            first_init=first_dev.view(nv, K1), K1=K1)
         srcs = [fr.contiguous() if not fr.is_cuda else fr.to(dev).contiguous() for fr in srcs]
-        packed = group or not srcs[0].is_cuda
+        packed = nv > 1 or not srcs[0].is_cuda
         up = None
         if packed:
             # one buffer for all frames, filled in chunks of video_chunk_bytes on the copy stream (a chunk may span videos)
@@ -765,7 +705,7 @@ class TDEEDModel:
                     need = arrived[c]
             with torch.cuda.stream(st):
                 st.wait_event(need)                   # a chunk's event follows the tables' on the copy stream
-                tables = dict(clip_base=base_dev[lo:lo + B], clip_len_v=lenv_dev[lo:lo + B]) if group else {}
+                tables = dict(clip_base=base_dev[lo:lo + B], clip_len_v=lenv_dev[lo:lo + B])
                 for v in range(V):
                     if reuse_frames:
                         head, _ = eng.forward_from_frame_maps(maps[v], starts_dev[lo:lo + B], pad_row, slot=slot, **tables)
@@ -784,14 +724,9 @@ class TDEEDModel:
             frame_pass_through(order[-1])             # (rows nobody read: the count of the stats holds, and nothing is left unqueued)
             s0.wait_stream(self._frame_stream)
         with torch.cuda.stream(s0):
-            if group:
-                track, support, mean = ops.stitch_scores_seg(clip_scores, starts_dev, seg_dev, coff_dev, L, count_all=augment,
-                                                             mean=want_mean)
-            else:
-                track, support, mean = ops.stitch_scores(clip_scores, starts_dev, L, count_all=augment, mean=want_mean)
-        stats = dict(frames=L, clips=n, batches=n_batches, views=V, frames_h2d_bytes=up.h2d if up is not None else 0)
-        if group:
-            stats["videos"] = nv
+            track, support, mean = ops.stitch_scores_seg(clip_scores, starts_dev, seg_dev, coff_dev, L, count_all=augment,
+                                                         mean=want_mean)
+        stats = dict(frames=L, clips=n, batches=n_batches, views=V, frames_h2d_bytes=up.h2d if up is not None else 0, videos=nv)
         if reuse_frames:
             stats["frame_pass_frames"] = V * rows
             stats["map_bytes"] = map_bytes

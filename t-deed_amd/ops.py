@@ -672,36 +672,27 @@ def clip_gather(video_u8, starts_dev, T, out):
     return out
 
 
-def stitch_scores(clip_scores, starts_dev, L, count_all=None, track_sum=None, support=None, mean=False):
-    """clip_scores fp32 (V,n,T,K1), starts_dev int32 (n,) on the device -> (track_sum (L,K1), support (L,) int32, mean
-    (L,K1) | None): the device twin of evalutil.ScoreStitcher (add per clip for count_all=False, add_views per view for
-    count_all=True; default: True when V > 1).  track_sum / support: accumulate onto these instead of fresh zeros."""
-    V, n, T, K1 = clip_scores.shape
-    if clip_scores.dtype != torch.float32 or starts_dev.dtype != torch.int32 or not clip_scores.is_contiguous():
-        raise TypeError("stitch_scores: contiguous float32 scores and int32 starts")
-    if starts_dev.numel() != n:
-        raise ValueError(f"stitch_scores: {starts_dev.numel()} starts for {n} clips")
-    dev = clip_scores.device
-    if track_sum is None:
-        track_sum = torch.zeros((L, K1), dtype=torch.float32, device=dev)
-    if support is None:
-        support = torch.zeros((L,), dtype=torch.int32, device=dev)
-    if tuple(track_sum.shape) != (L, K1) or tuple(support.shape) != (L,) or track_sum.dtype != torch.float32 \
-            or support.dtype != torch.int32 or not (track_sum.is_contiguous() and support.is_contiguous()):
-        raise ValueError("stitch_scores: track_sum float32 (L,K1) and support int32 (L,), contiguous")
-    mean_out = torch.empty((L, K1), dtype=torch.float32, device=dev) if mean else None
-    ca = (V > 1) if count_all is None else bool(count_all)
-    call("tdeed_stitch_scores", ptr(clip_scores), V, n, T, K1, ptr(starts_dev), int(ca), L, ptr(track_sum), ptr(support),
-         ptr(mean_out), stream_ptr())
-    return track_sum, support, mean_out
-
-
 def _chk_track(mean, who):
     if not isinstance(mean, torch.Tensor) or mean.dtype != torch.float32:
         raise TypeError(f"{who}: the track must be a float32 tensor")
     if mean.dim() != 2 or mean.shape[0] < 1 or mean.shape[1] < 2 or not mean.is_contiguous():
         raise ValueError(f"{who}: the track must be a contiguous (L, K+1) tensor with L >= 1 and K >= 1")
     return int(mean.shape[0]), int(mean.shape[1])
+
+
+def _one_video(dev, *ends):
+    """the offset table [0, end] of a group of one video, per end, as int32 tensors on dev"""
+    tab = torch.tensor([x for e in ends for x in (0, int(e))], dtype=torch.int32, device=dev)
+    return [tab[2 * i:2 * i + 2] for i in range(len(ends))]
+
+
+# ---- one video: conveniences over the group functions below (a video is a group of one; tests and tools use them)
+def stitch_scores(clip_scores, starts_dev, L, count_all=None, track_sum=None, support=None, mean=False):
+    """clip_scores fp32 (V,n,T,K1), starts_dev int32 (n,) on the device -> (track_sum (L,K1), support (L,) int32, mean
+    (L,K1) | None): the device twin of evalutil.ScoreStitcher (add per clip for count_all=False, add_views per view for
+    count_all=True; default: True when V > 1).  track_sum / support: accumulate onto these instead of fresh zeros."""
+    seg_off, clip_off = _one_video(clip_scores.device, L, clip_scores.shape[1])
+    return stitch_scores_seg(clip_scores, starts_dev, seg_off, clip_off, L, count_all, track_sum, support, mean)
 
 
 def frame_events(mean, hr_threshold=0.01, pred_u8=None):
@@ -711,20 +702,9 @@ def frame_events(mean, hr_threshold=0.01, pred_u8=None):
     frames).  The comparison is in fp32, as numpy compares an fp32 array with a python float.
     pred_u8: optional uint8 (L,) tensor that receives pred once more, one byte per frame (K1 <= 256): what spot_video copies
     to the host."""
-    L, K1 = _chk_track(mean, "frame_events")
-    dev = mean.device
-    if pred_u8 is not None:
-        if K1 > 256:
-            raise ValueError(f"frame_events: {K1} columns do not fit a one-byte prediction")
-        if pred_u8.dtype != torch.uint8 or tuple(pred_u8.shape) != (L,) or not pred_u8.is_contiguous() or pred_u8.device != dev:
-            raise ValueError("frame_events: pred_u8 must be a contiguous uint8 (L,) tensor on the track's device")
-    pred = torch.empty((L,), dtype=torch.int32, device=dev)
-    pred_score = torch.empty((L,), dtype=torch.float32, device=dev)
-    first = torch.full((K1,), L, dtype=torch.int32, device=dev)
-    count = torch.zeros((K1,), dtype=torch.int32, device=dev)
-    call("tdeed_frame_events", ptr(mean), L, K1, float(hr_threshold), ptr(pred), ptr(pred_u8), ptr(pred_score), ptr(first),
-         ptr(count), stream_ptr())
-    return pred, pred_score, first, count
+    L, _ = _chk_track(mean, "frame_events")
+    pred, pred_score, first, count = frame_events_seg(mean, _one_video(mean.device, L)[0], L, hr_threshold, pred_u8)
+    return pred, pred_score, first[0], count[0]
 
 
 def nms_track(mean, window, threshold, soft, hr_threshold=0.01, first_frame=None, classes_u8=None):
@@ -736,45 +716,23 @@ def nms_track(mean, window, threshold, soft, hr_threshold=0.01, first_frame=None
     it already.  Returns device tensors (frames int32, classes int32, scores float64, count int32 (1,), rounds int32 (K1,)):
     the first `count` entries are the events, ascending frame and within a frame by label appearance; rounds[c] is the number
     of rounds class c took.  classes_u8: optional uint8 tensor of L*(K1-1) entries that receives the classes once more, one
-    byte each: what spot_video copies to the host.
+    byte each.
     Raises ValueError for a soft window below 1, a negative window, or a window list with fewer than K1-1 entries -- the host
     only fails (IndexError) once more labels appear than the list has entries; this wrapper refuses the list up front."""
     L, K1 = _chk_track(mean, "nms_track")
-    soft = bool(soft)
-    is_list = isinstance(window, (list, tuple))
-    wins = [int(w) for w in window] if is_list else [int(window)]
-    if is_list and len(wins) < K1 - 1:
-        raise ValueError(f"nms_track: a window list of {len(wins)} entries for {K1 - 1} classes")
-    if is_list and len(wins) == 1:
-        is_list = False                                 # K1 == 2: one class, the entry is its window
-    if any(w < (1 if soft else 0) or w > 1 << 30 for w in wins):
-        raise ValueError(f"nms_track: windows {wins}: soft suppression needs windows >= 1, hard suppression >= 0 (and at most 2^30)")
-    wins = wins[:K1 - 1] if is_list else wins[:1]
-    dev = mean.device
-    if first_frame is None:
-        first_frame = frame_events(mean, hr_threshold)[2]
-    if first_frame.dtype != torch.int32 or tuple(first_frame.shape) != (K1,) or not first_frame.is_contiguous() \
-            or first_frame.device != dev:
-        raise ValueError("nms_track: first_frame must be a contiguous int32 (K1,) tensor on the track's device")
-    cap = L * (K1 - 1)
+    dev, cap = mean.device, L * (K1 - 1)
     if classes_u8 is not None and (classes_u8.dtype != torch.uint8 or classes_u8.numel() != cap or not classes_u8.is_contiguous()
                                    or classes_u8.device != dev):
         raise ValueError(f"nms_track: classes_u8 must be a contiguous uint8 tensor of {cap} entries on the track's device")
-    ws_bytes = int(_lib.load().tdeed_nms_track_workspace(L, K1))
-    ws = torch.empty((ws_bytes // 8 + 1,), dtype=torch.float64, device=dev) if ws_bytes else None
-    emitted = torch.empty((K1, L), dtype=torch.uint8, device=dev)
-    kept = torch.empty((K1, L), dtype=torch.float64, device=dev)
-    frames = torch.empty((cap,), dtype=torch.int32, device=dev)
-    classes = torch.empty((cap,), dtype=torch.int32, device=dev)
-    scores = torch.empty((cap,), dtype=torch.float64, device=dev)
-    count = torch.empty((1,), dtype=torch.int32, device=dev)
-    rounds = torch.empty((K1,), dtype=torch.int32, device=dev)
-    warr = (ctypes.c_int * len(wins))(*wins)
-    call("tdeed_nms_track", ptr(mean), L, K1, float(hr_threshold), float(threshold), int(soft), warr, len(wins),
-         ptr(first_frame), ptr(ws), ptr(emitted), ptr(kept), ptr(frames), ptr(classes), ptr(classes_u8), ptr(scores), ptr(count),
-         ptr(rounds),
-         stream_ptr())
-    return frames, classes, scores, count, rounds
+    seg_off = _one_video(dev, L)[0]
+    if first_frame is None:
+        first_frame = frame_events_seg(mean, seg_off, L, hr_threshold)[2]
+    elif isinstance(first_frame, torch.Tensor) and first_frame.dim() == 1:
+        first_frame = first_frame.unsqueeze(0)
+    frames, cls8, scores, event_off, rounds = nms_track_seg(mean, seg_off, L, window, threshold, soft, first_frame, hr_threshold)
+    if classes_u8 is not None:
+        classes_u8.view(-1).copy_(cls8)
+    return frames, cls8.to(torch.int32), scores, event_off[1:], rounds[0]
 
 
 # ---- a group of videos packed one after the other (tables: evalutil.group_clip_table, int32 on the device)
@@ -797,6 +755,18 @@ def _chk_group(seg_off, dev, who):
         raise ValueError(f"{who}: {nv} videos in one group, at most {MAX_GROUP_VIDEOS}")
     _chk_table(seg_off, nv + 1, dev, who, "seg_off")
     return nv
+
+
+def _chk_windows(window, K1, soft, who):
+    """window: an int for every class, or a list / tuple with an entry per class (K1 - 1 of them, further ones are ignored)
+    -> the list of ints the C entry takes: one entry, or K1 - 1."""
+    is_list = isinstance(window, (list, tuple))
+    wins = [int(w) for w in window] if is_list else [int(window)]
+    if is_list and len(wins) < K1 - 1:
+        raise ValueError(f"{who}: a window list of {len(wins)} entries for {K1 - 1} classes")
+    if any(w < (1 if soft else 0) or w > 1 << 30 for w in wins):
+        raise ValueError(f"{who}: windows {wins}: soft suppression needs windows >= 1, hard suppression >= 0 (and at most 2^30)")
+    return wins[:K1 - 1] if is_list and len(wins) > 1 else wins[:1]       # (K1 == 2: one class, the entry is its window)
 
 
 def clip_gather_seg(video_u8, starts_dev, clip_base, clip_len_v, T, out):
@@ -923,7 +893,8 @@ def frame_events_seg(mean, seg_off, max_len, hr_threshold=0.01, pred_u8=None, fi
 
 def nms_track_seg(mean, seg_off, max_len, window, threshold, soft, first_frame, hr_threshold=0.01):
     """nms_track per video of a packed track, one launch for the whole group: mean fp32 (sum L,K1), seg_off int32 (nv+1,),
-    first_frame int32 (nv,K1) from frame_events_seg with the same hr_threshold; window / threshold / soft as nms_track.
+    first_frame int32 (nv,K1) from frame_events_seg with the same hr_threshold; window / threshold / soft as nms_track
+    (which is this function on a group of one video).
     Returns device tensors (frames int32, classes uint8, scores float64, event_off int32 (nv+1,), rounds int32 (nv,K1)):
     entries event_off[v]:event_off[v+1] are video v's kept events (video-local frames, nms_track's order), the lists of
     the videos following each other densely in video order."""
@@ -934,15 +905,7 @@ def nms_track_seg(mean, seg_off, max_len, window, threshold, soft, first_frame, 
     if not 1 <= max_len <= L:
         raise ValueError(f"nms_track_seg: max_len {max_len} for {L} packed frames")
     soft = bool(soft)
-    is_list = isinstance(window, (list, tuple))
-    wins = [int(w) for w in window] if is_list else [int(window)]
-    if is_list and len(wins) < K1 - 1:
-        raise ValueError(f"nms_track_seg: a window list of {len(wins)} entries for {K1 - 1} classes")
-    if is_list and len(wins) == 1:
-        is_list = False
-    if any(w < (1 if soft else 0) or w > 1 << 30 for w in wins):
-        raise ValueError(f"nms_track_seg: windows {wins}: soft suppression needs windows >= 1, hard suppression >= 0 (and at most 2^30)")
-    wins = wins[:K1 - 1] if is_list else wins[:1]
+    wins = _chk_windows(window, K1, soft, "nms_track_seg")
     if not isinstance(first_frame, torch.Tensor) or first_frame.dtype != torch.int32 or tuple(first_frame.shape) != (nv, K1) \
             or not first_frame.is_contiguous() or first_frame.device != dev:
         raise ValueError("nms_track_seg: first_frame must be a contiguous int32 (nv,K1) tensor on the track's device")

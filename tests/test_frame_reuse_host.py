@@ -163,6 +163,9 @@ def test_evalutil_passes_the_flag_on_only_when_set():
             seen.append(kw)
             return np.zeros((int(frames.shape[0]), 4), np.float32), np.zeros(int(frames.shape[0]), np.int32)
 
+        def predict_video_group(self, frames_list, **kw):               # what stitch_videos calls: a video is a group of one
+            return [self.predict_video(f, **kw) for f in frames_list]
+
     videos = [("a", 5, 25.0, torch.zeros((5, 3, 4, 4), dtype=torch.uint8))]
     E.stitch_videos(Model(), videos, 4)
     E.stitch_videos(Model(), videos, 4, reuse_frames=True)

@@ -309,8 +309,8 @@ def test_reuse_counts_the_maps_towards_max_resident_bytes(plain_model, tiny_vide
     budget = tiny_video.numel() + map_bytes - 1
     m.predict_video(tiny_video, batch_size=4, max_resident_bytes=budget)          # the frames alone fit
     launched = []
-    monkeypatch.setattr(ops, "clip_gather", lambda *a, **k: launched.append(1))
-    monkeypatch.setattr(ops, "rows_gather", lambda *a, **k: launched.append(1))
+    for gather in ("clip_gather", "clip_gather_seg", "rows_gather", "rows_gather_seg"):       # every gather the model may call
+        monkeypatch.setattr(ops, gather, lambda *a, **k: launched.append(1))
     with pytest.raises(ValueError, match="max_resident_bytes"):
         m.predict_video(tiny_video, batch_size=4, max_resident_bytes=budget, reuse_frames=True)
     with pytest.raises(ValueError, match="max_resident_bytes"):

@@ -94,13 +94,29 @@ def test_nms_track_many_classes(L, variant):
 def test_nms_track_dense_long_track():
     """one class, every one of 20 000 frames a candidate (hr_threshold 0): beyond the LDS-resident state of the kernel"""
     L = 20000
-    assert ops._lib.load().tdeed_nms_track_workspace(L, 2) > 0 and ops._lib.load().tdeed_nms_track_workspace(1025, 18) == 0
+    ws_bytes = ops._lib.load().tdeed_nms_track_seg_workspace
+    assert ws_bytes(L, L, 2) > 0 and ws_bytes(1025, 1025, 18) == 0
     mean = np.zeros((L, 2), np.float32)
     mean[:, 1] = np.random.RandomState(11).rand(L).astype(np.float32)
     mean[::7, 1] = np.float32(0.5)                                    # ties across the whole track
     n_hard, _ = _check_case(mean, 5, 0.0, False, 0.0, "dense hard")
     n_soft, _ = _check_case(mean, 5, 0.3, True, 0.0, "dense soft")
     assert n_hard > L // 11 and n_soft > 0
+
+
+def test_nms_track_single_video_workgroup_sizes():
+    """A single video gets the workgroup size its length selects (128 / 256 / 512 / 1024 threads): both sides of every
+    threshold above the 128-thread form that the grid's lengths stay in."""
+    threads = ops._lib.load().tdeed_nms_track_seg_threads
+    assert [threads(L) for L in (128, 129, 256, 257, 512, 513)] == [128, 256, 256, 512, 512, 1024]
+    n = 0
+    for L in (128, 129, 256, 257, 512, 513):
+        mean = H.make_track(L, 5, "sharp", 3 * L + 1)
+        for soft in (False, True):
+            got = _device_route(mean, 2, 0.02, soft, 0.01)
+            H.check_equal(got, H.host_chain(mean, 2, 0.02, soft, 0.01), (L, soft))
+            n += len(got[0])
+    assert n > 0
 
 
 def test_nms_track_golden_inputs():

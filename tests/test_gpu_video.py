@@ -216,7 +216,8 @@ def test_predict_video_frame_sources_and_repeat(tiny_model, tiny_video):
 
 def test_predict_video_refuses_a_video_that_does_not_fit(tiny_model, tiny_video, monkeypatch):
     launched = []
-    monkeypatch.setattr(ops, "clip_gather", lambda *a, **k: launched.append(1))
+    for gather in ("clip_gather", "clip_gather_seg", "rows_gather", "rows_gather_seg"):       # every gather the model may call
+        monkeypatch.setattr(ops, gather, lambda *a, **k: launched.append(1))
     with pytest.raises(ValueError, match="max_resident_bytes"):
         tiny_model.predict_video(tiny_video, max_resident_bytes=tiny_video.numel() - 1)
     assert not launched

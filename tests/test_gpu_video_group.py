@@ -1,5 +1,5 @@
 """A group of videos scored as one packed job on the MI355X: the segmented gather / stitch / event / suppression kernels
-against their one-video twins and the host chain, `TDEEDModel.predict_video_group` / `spot_video_group` bit for bit against
+against the same video scored alone (a group of one, through the one-video wrappers) and the host chain, `TDEEDModel.predict_video_group` / `spot_video_group` bit for bit against
 the clip-batch route on the same packed batches, and `evalutil.spot_videos(group_videos=...)`.  -m gpu only."""
 import math
 
@@ -376,7 +376,7 @@ def test_spot_video_group_equals_the_host_chain(tiny_model, tiny_videos, augment
     assert kept > 0
     assert stats["frames"] == 70 and stats["clips"] == 36 and stats["batches"] == 9 and stats["videos"] == 4
     assert stats["host_syncs"] == 2
-    assert stats["events_d2h_bytes"] == 70 * 5 + 2 * (5 + 4 * 4) * 4 + 13 * kept
+    assert stats["events_d2h_bytes"] == 70 * 5 + 2 * (4 + 4 * 4) * 4 + 13 * kept       # per entry: 4 list ends, 4 x 4 rounds
     assert len(stats["nms_rounds"]) == 2 and all(1 <= x <= 37 for x in stats["nms_rounds"])
 
 
@@ -482,8 +482,8 @@ def test_group_full_size_once():
 def test_group_refusals_launch_nothing(tiny_model, tiny_videos, monkeypatch):
     m = tiny_model
     launched = []
-    monkeypatch.setattr(ops, "clip_gather_seg", lambda *a, **k: launched.append(1))
-    monkeypatch.setattr(ops, "clip_gather", lambda *a, **k: launched.append(1))
+    for gather in ("clip_gather", "clip_gather_seg", "rows_gather", "rows_gather_seg"):       # every gather the model may call
+        monkeypatch.setattr(ops, gather, lambda *a, **k: launched.append(1))
     small = t(synth.uint8_clip(7, (5, 3, 32, 32)))
     with pytest.raises(ValueError, match="geometry"):
         m.predict_video_group([tiny_videos[1], small])

@@ -252,6 +252,9 @@ def test_decode_keyword_selects_the_loader(monkeypatch):
         def predict_video(self, frames, **kw):
             return np.zeros((int(frames.shape[0]), 4), np.float32), np.ones(int(frames.shape[0]), np.int32)
 
+        def predict_video_group(self, frames_list, **kw):               # what stitch_videos calls: a video is a group of one
+            return [self.predict_video(f, **kw) for f in frames_list]
+
     base = os.path.join(ROOT, "tests", "golden", "frames", "soccernetball")
     src = dict(frame_dir=base, dataset="soccernetball", video_name="game_a/clip_1", num_frames=7)
     called = []

@@ -88,9 +88,9 @@ class FakeGroupModel(FakeModel):
         super().__init__()
         self.group_calls = []
 
-    def predict_video_group(self, frames_list, overlap_len=None, batch_size=8, augment=False, max_resident_bytes=None, **kw):
+    def predict_video_group(self, frames_list, **kw):
         self.group_calls.append(([int(np.asarray(f)[0, 0, 0, 0]) for f in frames_list], threading.current_thread().name))
-        return [self.predict_video(f, overlap_len=overlap_len, batch_size=batch_size, augment=augment) for f in frames_list]
+        return super().predict_video_group(frames_list, **kw)
 
     def _spot(self, frames, classes, suppress, hr, **kw):
         sums, sup = self.predict_video(frames, **kw)
@@ -225,6 +225,7 @@ def test_group_entry_points_validate_before_launching():
         nms(L=40000, max_len=20000)
     lib = load()
     assert lib.tdeed_nms_track_seg_workspace(20037, 20000, 2) == 20037 * 9
-    assert lib.tdeed_nms_track_seg_workspace(20037, 16000, 18) == 0 and lib.tdeed_nms_track_workspace(16000, 18) == 0
+    assert lib.tdeed_nms_track_seg_workspace(20037, 16000, 18) == 0 and lib.tdeed_nms_track_seg_workspace(16000, 16000, 18) == 0
+    assert lib.tdeed_nms_track_seg_workspace(16001, 16001, 2) == 16001 * 9                # one video over the LDS-resident state
     assert [lib.tdeed_nms_track_seg_threads(x) for x in (1, 101, 128, 129, 256, 257, 512, 513, 1 << 20)] == \
         [128, 128, 128, 256, 256, 512, 512, 1024, 1024]

@@ -208,6 +208,10 @@ class FakeModel:
         flip = np.stack([self.clip_scores(vid, i, True) for i in range(len(starts))]) if augment else None
         return E.stitch_clip_scores(plain, starts, L, flip_scores=flip)
 
+    def predict_video_group(self, frames_list, max_resident_bytes=None, **kw):
+        """what stitch_videos calls, also for single videos: the per-video route applied to every video of the group"""
+        return [self.predict_video(f, **kw) for f in frames_list]
+
 
 @pytest.mark.parametrize("augment", [False, True])
 def test_stitch_videos_fills_the_tracks_like_stitch_predictions(augment):
@@ -267,7 +271,10 @@ def test_video_entry_points_validate_before_launching():
         call("tdeed_clip_gather_u8", None, 4, 48, None, 1, 1, None, None)
     with pytest.raises(HipCallError, match="65535"):
         call("tdeed_clip_gather_u8", 1 << 20, 4, 48, 1 << 20, 700, 100, 1 << 20, None)
+    P = 1 << 20
     with pytest.raises(HipCallError, match="null pointer"):
-        call("tdeed_stitch_scores", None, 1, 1, 8, 4, None, 0, 10, None, None, None, None)
+        call("tdeed_stitch_scores_seg", None, 1, 1, 8, 4, None, P, P, 1, 0, 10, None, None, None, None)
+    with pytest.raises(HipCallError, match="null pointer"):
+        call("tdeed_stitch_scores_seg", P, 1, 1, 8, 4, P, P, P, 1, 0, 10, P, None, None, None)       # no support
     with pytest.raises(HipCallError, match="count_all"):
-        call("tdeed_stitch_scores", 1 << 20, 1, 1, 8, 4, 1 << 20, 2, 10, 1 << 20, 1 << 20, None, None)
+        call("tdeed_stitch_scores_seg", P, 1, 1, 8, 4, P, P, P, 1, 2, 10, P, P, None, None)

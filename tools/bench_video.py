@@ -142,7 +142,7 @@ def _median_ms(fn, repeats):
 def spot(a):
     """Two routes on the same video, alternating: (1) predict_video -> ScoreStitcher.normalised -> frame_events -> NMS ->
     soft-NMS on the host, (2) spot_video.  Then the tail alone on a synthetic peaky track of the same length with K+1 = 13
-    columns: the host chain against ops.frame_events + ops.nms_track (+ the copies of the event lists)."""
+    columns: the host chain against ops.frame_events_seg + ops.nms_track_seg (+ the copies of the event lists)."""
     from tdeed_amd.model import TDEEDModel
     from types import SimpleNamespace
     L = a.frames
@@ -192,20 +192,23 @@ def spot(a):
         return [x[0]["events"] for x in _host_chain({"v": mean}, pk_classes, {"v": 25.0}, suppress, hr)[2]]
 
     last = {}
+    seg_off = torch.tensor([0, L], dtype=torch.int32, device="cuda")    # one video: a group of one; uploaded once, not timed
+
+    def events_and_lists():
+        first = torch.full((1, K1), L, dtype=torch.int32, device="cuda")
+        _, _, first, cnt = ops.frame_events_seg(dmean, seg_off, L, hr, first_init=first)
+        return cnt, [ops.nms_track_seg(dmean, seg_off, L, w, thr, kind == "snms", first, hr) for kind, w, thr in suppress]
 
     def tail_device():
-        _, _, first, cnt = ops.frame_events(dmean, hr)
-        lists = [ops.nms_track(dmean, w, thr, kind == "snms", hr, first_frame=first) for kind, w, thr in suppress]
-        counts = [int(x[3].cpu()[0]) for x in lists]                    # synchronises
+        cnt, lists = events_and_lists()
+        counts = [int(x[3].cpu()[1]) for x in lists]                    # synchronises
         host = [[t[:n].cpu().numpy() for t in x[:3]] for x, n in zip(lists, counts)]
         last["rounds"] = [int(x[4].max().cpu()) for x in lists]
         last["recall"] = int(cnt.sum().cpu())
         return [E.event_dicts(f, c, s, inv) for f, c, s in host]
 
     def tail_device_kernels():
-        _, _, first, _ = ops.frame_events(dmean, hr)
-        for kind, w, thr in suppress:
-            ops.nms_track(dmean, w, thr, kind == "snms", hr, first_frame=first)
+        events_and_lists()
         torch.cuda.synchronize()
 
     th, td = tail_host(), tail_device()
