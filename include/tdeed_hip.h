@@ -197,6 +197,19 @@ int tdeed_c1_gconv_fwd(const void* x, const void* G, int Fp, int N, int Hi, int 
                        const void* w1f, const float* s1, const float* h1, const void* wfrag, const float* scale,
                        const float* shift, void* y, float* pooled, void* stream);
 
+/* tdeed_c1_gconv_fwd of a stride-2 block whose input is not in memory: the launch also computes the producer's conv3 (Cp <=
+ * 32 channels in and out: one k-step) per pixel tile in front of conv1, from its operand y2p, its shortcut map scp (both
+ * [N][Hi][Wi][Cp] bf16), its SE gate [N][Cp] fp32, its weights w3f = pack_ws_weights(W3) and its fold s3 / h3 (ReLU applied).
+ * xs2 optional [N][ceil(Hi/2)][ceil(Wi/2)][Cp]: the producer's output at even rows and columns (what the block's shortcut
+ * conv reads).  The rest as tdeed_c1_gconv_fwd with Cin = Cp, stride 2.  Bit-identical to tdeed_gemm_ws_fwd (a_scale = gate,
+ * R = scp, ReLU) followed by tdeed_c1_gconv_fwd; the producer's output map never exists.
+ * tdeed_c1_gconv_c3in_fits: Cp in 8..32, C <= 64 (one channel slab) and tdeed_c1_gconv_fits(Hi, Wi, Cp, C, 2). */
+int tdeed_c1_gconv_c3in_fits(int Hi, int Wi, int Cp, int C);
+int tdeed_c1_gconv_c3in_fwd(const void* y2p, const void* scp, const float* gate, const void* w3f, const float* s3,
+                            const float* h3, void* xs2, int N, int Hi, int Wi, int Cp, int C, int gw, const void* w1f,
+                            const float* s1, const float* h1, const void* wfrag, const float* scale, const float* shift,
+                            void* y, float* pooled, void* stream);
+
 /* A whole stride-1 RegNetY bottleneck with identity shortcut on a small map in ONE launch (timm Bottleneck.forward:
  * conv1 -> conv2 -> se -> conv3 + shortcut -> ReLU, with the gate-shift splice of shift.py:89-93 on conv1's operand;
  * SURVEY §8 a2 / a3): the frames of a workgroup stay in LDS, only x and the output cross HBM.  bf16.

@@ -610,14 +610,29 @@ __global__ __launch_bounds__(256) void gconv3x3_mfma_kernel(const bf16_t* __rest
 // (w1f: [slabs * CSP / 16][KS1][64], engine.pack_mfma_frags, zero padded).
 // (A form that also produced the downsample shortcut from the same x fragments was measured slower and is parked:
 // experiments/r4_parked/conv_with_c1_gconv_ds.hip.)
-template <int STRIDE, int KS1>
-__global__ __launch_bounds__(256, KS1 == 4 ? 3 : 1) void c1_gconv_mfma_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ G, int Fp,
+//
+// C3IN (STRIDE 2, KS1 1): the block's input x is not read, it is COMPUTED per pixel tile in front of conv1 -- x is the output
+// of the producer's conv3 (SE gate on the operand, BatchNorm, shortcut map, ReLU: gemm_ws_kernel with one k-step), whose
+// operands y2p / scp ([N][Hi][Wi][Cin]) and gate ([N][Cin] fp32) arrive in C3In with its weights in gemm_ws's fragment layout
+// and its fold.  gemm_ws permutes its weight rows so that the accumulators of a tile pair leave lane (pixel, q) with channels
+// 8q .. 8q+7 of one pixel, which IS conv1's B fragment: two MFMAs and the epilogue per tile, no LDS and no re-layout, the
+// bits of the two launches.  The producer's output map is neither written nor read; the pixels at even rows and columns,
+// all that the block's shortcut conv reads of it, go to the compact map xs2 ([N][Ho][Wo][Cin]).
+struct C3In {
+  const bf16_t* y2p; const bf16_t* scp; const float* gate;
+  const bf16x8* w3f; const float* s3; const float* h3;
+  bf16_t* xs2;
+};
+template <int STRIDE, int KS1, bool C3IN = false>
+__global__ __launch_bounds__(256, (KS1 == 4 || C3IN) ? 3 : 1) void c1_gconv_mfma_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ G, int Fp,
                                                             int Hi, int Wi, int Cin, int C, const bf16x8* __restrict__ w1f,
                                                             const float* __restrict__ s1, const float* __restrict__ h1,
                                                             const bf16x8* __restrict__ wfrag, const float* __restrict__ scale,
                                                             const float* __restrict__ shift, bf16_t* __restrict__ y,
                                                             float* __restrict__ pooled, int Ho, int Wo, int band, int nbands,
-                                                            int CSP, int PS, int rows_in, int relu, long long* dbg) {
+                                                            int CSP, int PS, int rows_in, int relu, long long* dbg,
+                                                            const C3In c3) {
+  static_assert(!C3IN || (STRIDE == 2 && KS1 == 1), "the conv3-in-front form exists for stride 2 and one k-step");
   extern __shared__ __attribute__((aligned(16))) unsigned char tile[];
   __shared__ float red[4][32];
   __shared__ float redq[4][32];
@@ -635,8 +650,12 @@ __global__ __launch_bounds__(256, KS1 == 4 ? 3 : 1) void c1_gconv_mfma_kernel(co
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int pl = lane & 15, q = lane >> 4;
   const int nts = CSP >> 4;                                // conv1 output tiles of this slab (<= 4)
-  GcW gw_;                                                 // the grouped conv's weights travel under conv1 -- where the
-  if constexpr (KS1 <= 2) gw_ = gconv_load_w(wfrag, slab, CSP);   // registers allow (at KS1 >= 4 they cost the third workgroup per CU)
+  // the grouped conv's weights travel under conv1 -- where the registers allow (at KS1 >= 4 they cost the third workgroup per
+  // CU, and so they do next to C3IN's operands: 168 registers and 52 bytes of scratch with them, 140 and none without; two
+  // tiles per load group with the early weights are 160)
+  constexpr bool GW_EARLY = KS1 <= 2 && !C3IN;
+  GcW gw_;
+  if constexpr (GW_EARLY) gw_ = gconv_load_w(wfrag, slab, CSP);
   // conv1 weights of the slab, BN affine of this lane's 4 channels per tile
   bf16x8 w1r[4][KS1];
   float a1[4][4], b1[4][4];
@@ -739,6 +758,95 @@ __global__ __launch_bounds__(256, KS1 == 4 ? 3 : 1) void c1_gconv_mfma_kernel(co
         tile_load(ra, ca, xa);
         tile_mma(pb, rb, cb, xb);
       }
+    } else if constexpr (C3IN) {
+      const int k8 = 8 * q;
+      const bool kok = k8 < Cin;                                    // (Cin is a multiple of 8: a chunk is inside or outside)
+      const int kc = min(k8, Cin - 8);
+      const bf16_t* yn = c3.y2p + (long)n * Hi * Wi * Cin;
+      const bf16_t* rn = c3.scp + (long)n * Hi * Wi * Cin;
+      // workgroup-invariant: conv3's fragment pair, its fold and the frame's gate for this lane's 8 channels (channels beyond
+      // Cin: scale 1, shift 0, no residual, a zero operand -- exact zeros)
+      const bf16x8 w3a = c3.w3f[lane], w3b = c3.w3f[64 + lane];
+      float g8[8], sc3[8], sh3[8];
+#pragma unroll
+      for (int e4 = 0; e4 < 8; e4 += 4) {
+        const f32x4 gv = *reinterpret_cast<const f32x4*>(c3.gate + (long)n * Cin + kc + e4);
+        const f32x4 sv = *reinterpret_cast<const f32x4*>(c3.s3 + kc + e4), hv = *reinterpret_cast<const f32x4*>(c3.h3 + kc + e4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          g8[e4 + e] = gv[e];
+          sc3[e4 + e] = kok ? sv[e] : 1.f;
+          sh3[e4 + e] = kok ? hv[e] : 0.f;
+        }
+      }
+      bf16_t* xsn = c3.xs2 ? c3.xs2 + (long)n * Ho * Wo * Cin : nullptr;
+      for (int tb = wv; tb < ntl; tb += 4 * NPF) {
+        u32x4 yf[NPF], rf[NPF];
+        int rrs[NPF], ccs[NPF];
+        bool poks[NPF];
+#pragma unroll
+        for (int g = 0; g < NPF; ++g) {                             // both operands of the whole group, clamped, no branch
+          const int t0 = tb + 4 * g;
+          const int p = t0 * 16 + pl;
+          poks[g] = t0 < ntl && p < npx;
+          dwi.divmod(poks[g] ? p : 0, rrs[g], ccs[g]);
+          const long o = ((long)(r_lo + rrs[g]) * Wi + ccs[g]) * Cin + kc;
+          yf[g] = *reinterpret_cast<const u32x4*>(yn + o);
+          rf[g] = *reinterpret_cast<const u32x4*>(rn + o);
+        }
+#pragma unroll
+        for (int g = 0; g < NPF; ++g) {
+          if (tb + 4 * g >= ntl) break;                             // (wave-uniform)
+          const bool pok = poks[g];
+          // the producer's conv3: gate on the operand (fp32 product, rounded), two MFMAs, fold, residual, ReLU, rounding --
+          // gemm_ws_kernel's expressions in its order
+          const bf16x8 y8 = *reinterpret_cast<const bf16x8*>(&yf[g]), r8 = *reinterpret_cast<const bf16x8*>(&rf[g]);
+          bf16x8 a8;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            float f = (float)y8[e];
+            f *= g8[e];
+            a8[e] = (bf16_t)f;
+          }
+          const u32x4 zero4 = {0u, 0u, 0u, 0u};
+          const u32x4 am = (pok && kok) ? *reinterpret_cast<const u32x4*>(&a8) : zero4;
+          const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+          const f32x4 c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w3a, *reinterpret_cast<const bf16x8*>(&am), z4, 0, 0, 0);
+          const f32x4 c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w3b, *reinterpret_cast<const bf16x8*>(&am), z4, 0, 0, 0);
+          float v[8];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            v[r] = c0[r] * sc3[r] + sh3[r];
+            v[4 + r] = c1[r] * sc3[4 + r] + sh3[4 + r];
+          }
+          bf16x8 o8;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            v[e] += (float)r8[e];
+            v[e] = fmaxf(v[e], 0.f);
+            o8[e] = (bf16_t)v[e];
+          }
+          const u32x4 xm = kok ? *reinterpret_cast<const u32x4*>(&o8) : zero4;
+          const bf16x8 xf = *reinterpret_cast<const bf16x8*>(&xm);
+          const int row = r_lo + rrs[g], col = ccs[g];
+          // the compact map: even rows and columns; row 2 oy belongs to the band that owns output row oy (no row twice)
+          if (xsn && pok && kok && !((row | col) & 1) && (row >> 1) >= oy0 && (row >> 1) < oy0 + nrows_out)
+            *reinterpret_cast<u32x4*>(xsn + ((long)(row >> 1) * Wo + (col >> 1)) * Cin + k8) = xm;
+          unsigned char* dst = tile + ((long)(row - iy0) * WP + col + 1) * PS + 8 * q;
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            if (t < nts) {
+              const f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1r[t][0], xf, z4, 0, 0, 0);
+              if (pok) {
+                bf16x4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = (bf16_t)fmaxf(acc[e] * a1[t][e] + b1[t][e], 0.f);
+                *reinterpret_cast<bf16x4*>(dst + t * 32) = o;
+              }
+            }
+          }
+        }
+      }
     } else
     for (int tb = wv; tb < ntl; tb += 4 * NPF) {
       bf16x8 xf[NPF][KS1];
@@ -785,7 +893,7 @@ __global__ __launch_bounds__(256, KS1 == 4 ? 3 : 1) void c1_gconv_mfma_kernel(co
     }
   }
   GC_STAMP(2);
-  if constexpr (KS1 > 2) gw_ = gconv_load_w(wfrag, slab, CSP);
+  if constexpr (!GW_EARLY) gw_ = gconv_load_w(wfrag, slab, CSP);
   __syncthreads();
   GC_STAMP(3);
   gconv_band_mma<STRIDE>(gw_, tile, red, redq, Wi, C, wfrag, scale, shift, y, pooled, nullptr, Ho, Wo, nbands, CSP, PS, relu, n, bnd,
@@ -899,7 +1007,7 @@ extern "C" int tdeed_c1_gconv_fwd(const void* x, const void* G, int Fp, int N, i
 #define TD_C1G(Sv, Kv)                                                                                                     \
   hipLaunchKernelGGL((c1_gconv_mfma_kernel<Sv, Kv>), grid, dim3(256), smem, st, (const bf16_t*)x, (const bf16_t*)G,           \
                      G ? Fp : 0, Hi, Wi, Cin, C, (const bf16x8*)w1f, s1, h1, (const bf16x8*)wfrag, scale, shift, (bf16_t*)y,  \
-                     pooled, Ho, Wo, g.band, g.nbands, g.CSP, g.PS, g.rows_in, 1, g_c1g_dbg)
+                     pooled, Ho, Wo, g.band, g.nbands, g.CSP, g.PS, g.rows_in, 1, g_c1g_dbg, C3In{})
 #define TD_C1G_K(Sv)                                                                                                       \
   do {                                                                                                                     \
     if (KS1 == 1) TD_C1G(Sv, 1); else if (KS1 == 2) TD_C1G(Sv, 2); else if (KS1 == 4) TD_C1G(Sv, 4);                      \
@@ -909,6 +1017,37 @@ extern "C" int tdeed_c1_gconv_fwd(const void* x, const void* G, int Fp, int N, i
 #undef TD_C1G_K
 #undef TD_C1G
   TD_LAUNCH_CHECK("c1_gconv");
+  return TDEED_OK;
+}
+
+// tdeed_c1_gconv_fwd of a stride-2 block whose input is not in memory: the producer's conv3 (one k-step: Cp <= 32 channels in
+// and out, SE gate on its operand, BatchNorm fold, shortcut map, ReLU) runs per pixel tile in front of conv1 (C3IN above).
+// y2p / scp [N][Hi][Wi][Cp] bf16, gate [N][Cp] fp32, w3f = pack_ws_weights(W3) ([2][1][64] x 16 B), s3 / h3 its fold; xs2
+// optional [N][Ho][Wo][Cp]: the producer's output at even rows and columns, what the block's shortcut conv gathers.  The rest
+// as tdeed_c1_gconv_fwd with Cin = Cp.  Bit-identical to tdeed_gemm_ws_fwd followed by tdeed_c1_gconv_fwd.
+// tdeed_c1_gconv_c3in_fits: Cp <= 32, one channel slab (C <= 64: conv3 would be recomputed per slab) and the band fits.
+extern "C" int tdeed_c1_gconv_c3in_fits(int Hi, int Wi, int Cp, int C) {
+  if (Cp < 8 || Cp > 32 || Cp % 8 != 0 || C > 64 || !tdeed_c1_gconv_fits(Hi, Wi, Cp, C, 2)) return 0;
+  return gc_geom(Hi, Wi, C, 2).nslabs == 1 ? 1 : 0;
+}
+extern "C" int tdeed_c1_gconv_c3in_fwd(const void* y2p, const void* scp, const float* gate, const void* w3f, const float* s3,
+                                       const float* h3, void* xs2, int N, int Hi, int Wi, int Cp, int C, int gw,
+                                       const void* w1f, const float* s1, const float* h1, const void* wfrag,
+                                       const float* scale, const float* shift, void* y, float* pooled, void* stream) {
+  TD_CHECK(y2p && scp && gate && w3f && s3 && h3, "c1_gconv_c3in: null pointer (the producer's operands)");
+  TD_CHECK(w1f && s1 && h1 && wfrag && scale && shift && y && pooled, "c1_gconv_c3in: null pointer");
+  TD_CHECK((gw == 8 || gw == 16) && C % gw == 0, "c1_gconv_c3in: group width %d / C %d unsupported", gw, C);
+  TD_CHECK(N > 0 && N <= 65535 && tdeed_c1_gconv_c3in_fits(Hi, Wi, Cp, C), "c1_gconv_c3in: Hi=%d Wi=%d Cp=%d C=%d unsupported",
+           Hi, Wi, Cp, C);
+  const GcGeom g = gc_geom(Hi, Wi, C, 2);
+  const int Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1;
+  dim3 grid((unsigned)((long)g.nbands * N));
+  const size_t smem = (size_t)g.rows_in * (Wi + 2) * g.PS;
+  const C3In c3{(const bf16_t*)y2p, (const bf16_t*)scp, gate, (const bf16x8*)w3f, s3, h3, (bf16_t*)xs2};
+  hipLaunchKernelGGL((c1_gconv_mfma_kernel<2, 1, true>), grid, dim3(256), smem, (hipStream_t)stream, (const bf16_t*)nullptr,
+                     (const bf16_t*)nullptr, 0, Hi, Wi, Cp, C, (const bf16x8*)w1f, s1, h1, (const bf16x8*)wfrag, scale, shift,
+                     (bf16_t*)y, pooled, Ho, Wo, g.band, g.nbands, g.CSP, g.PS, g.rows_in, 1, g_c1g_dbg, c3);
+  TD_LAUNCH_CHECK("c1_gconv_c3in");
   return TDEED_OK;
 }
 

@@ -205,6 +205,10 @@ C1_GCONV_MAX_CIN = 160
 # the shortcut conv of a strided block as a second contraction inside conv3's launch (tdeed_gemm_ws_sc_fwd): no `.downsample`
 # launch, and the shortcut map is neither written nor read back
 SC_IN_CONV3 = True
+# conv3 of the block in the fused front (s1.b1) inside the conv1 + grouped-conv launch of the block behind it
+# (tdeed_c1_gconv_c3in_fwd): no `s1.b1.conv3` launch, and s1.b1's output map is neither written nor read -- only its pixels at
+# even rows and columns, which the shortcut conv of s2.b1 gathers, are stored
+S1_CONV3_IN_C1G = True
 
 
 # The launch form of one bottleneck of a run (block_forms):
@@ -218,14 +222,18 @@ SC_IN_CONV3 = True
 # qtail           the launch's tail writes the NEXT site's tap maps
 # slice_next      channels of the compact slice written for the next block's site (0: none)
 # sc_in_conv3     the shortcut conv is a second contraction inside conv3's launch (tdeed_gemm_ws_sc_fwd)
-BlockForm = namedtuple("BlockForm", "h w h2 w2 one_launch c1g site Fp slice_in q_given blend_in qtail slice_next sc_in_conv3")
+# conv3_in        the conv1 + grouped-conv launch also computes the PRODUCER's conv3 from its y2, shortcut map and gate
+#                 (tdeed_c1_gconv_c3in_fwd): the block's input map never exists, its shortcut reads a compact stride-2 copy
+BlockForm = namedtuple("BlockForm",
+                       "h w h2 w2 one_launch c1g site Fp slice_in q_given blend_in qtail slice_next sc_in_conv3 conv3_in")
 
 
-def block_forms(blocks, h, w, act_dtype, taps, last_out_is_slice):
+def block_forms(blocks, h, w, act_dtype, taps, last_out_is_slice, pending=None):
     """The launch form of every bottleneck of a run over an (h, w) input map: one BlockForm per block.  Pure: decided from the
     block specs, from which packed forms the weights have, from the module switches (read now) and from the library's host
     predicates; nothing is allocated, packed or written.  last_out_is_slice: the last block writes into a slice of a shared
-    buffer (no one-launch form: its output is not contiguous)."""
+    buffer (no one-launch form: its output is not contiguous).  pending: the weights of the block in the fused front when its
+    conv3 has not been emitted yet (the run's input map does not exist so far): the first block may take it in (conv3_in)."""
     forms = []
     for bi, bw in enumerate(blocks):
         blk = bw.spec
@@ -253,7 +261,14 @@ def block_forms(blocks, h, w, act_dtype, taps, last_out_is_slice):
                            and ops.gemm_ws_sc_fits(blk.cout, blk.cin, blk.cout, act_dtype))
         h2, w2 = (h - 1) // blk.stride + 1, (w - 1) // blk.stride + 1
         slice_in, q_given = bool(site and forms and forms[-1].slice_next == Fp), bool(forms and forms[-1].qtail)
-        forms.append(BlockForm(h, w, h2, w2, one_launch, c1g, site, Fp, slice_in, q_given, blend_in, qtail, slice_next, sc_in_conv3))
+        # the producer's conv3 in this block's first launch: nobody else may read the producer's output (no site here, no tap
+        # there), its conv3 is one k-step of the weight-stationary kernel, and this block has a shortcut conv (stride 2)
+        conv3_in = bool(S1_CONV3_IN_C1G and pending is not None and bi == 0 and c1g and not site and blk.stride == 2
+                        and blk.has_downsample and act_dtype == torch.bfloat16 and pending.w3.ws
+                        and pending.spec.cout == blk.cin and ("_features." + pending.spec.name) not in taps
+                        and ops.c1_gconv_c3in_fits(h, w, blk.cin, blk.cout))
+        forms.append(BlockForm(h, w, h2, w2, one_launch, c1g, site, Fp, slice_in, q_given, blend_in, qtail, slice_next, sc_in_conv3,
+                               conv3_in))
         h, w = h2, w2
     return forms
 
@@ -758,11 +773,13 @@ class ForwardEngine:
                           2 * M * blk.cout * (2 * blk.cout + blk.gw * 9)))
         return out, xs_next, q_next
 
-    def _chain(self, pool, steps, B, bw, f, x, y1, G, out, dead_site):
+    def _chain(self, pool, steps, B, bw, f, x, y1, G, out, dead_site, front=None):
         """Appends a bottleneck as a chain of launches: conv1 into y1 and the grouped conv, or both in one launch (f.c1g, no
         y1); SE; the shortcut conv, unless conv3's launch computes it (f.sc_in_conv3); conv3.  G: the blended slice of the
         block's site that conv1 splices in (None without a site), out: where the block writes instead of a pool buffer,
-        dead_site: the site's buffers.  Returns the output, the next site's compact slice and everything that dies here."""
+        dead_site: the site's buffers.  front (f.conv3_in): the fused front's block, whose conv3 the first launch computes
+        from front.y2 / sc / gate -- there is no x; the shortcut reads the compact stride-2 map that launch writes.
+        Returns the output, the next site's compact slice and everything that dies here."""
         blk, dt = bw.spec, self.act_dtype
         N, es, s = B * self.pw.clip_len, _esz(dt), blk.stride
         h, w, h2, w2 = f.h, f.w, f.h2, f.w2
@@ -775,9 +792,22 @@ class ForwardEngine:
         parts = ops.gconv3x3_parts(h, w, blk.cout, s, dt) if bw.w2frag is not None else 1
         pooled = pool.take((N, parts, blk.cout), torch.float32)
         gate = pool.take((N, blk.cout), torch.float32)
-        if f.c1g:
-            if bw.c1g_w1f is None:
-                bw.c1g_w1f = pack_mfma_frags(bw.w1_raw, self.device, rows=16 * ops.c1_gconv_slab_tiles(h, w, blk.cout, s))
+        if f.c1g and bw.c1g_w1f is None:
+            bw.c1g_w1f = pack_mfma_frags(bw.w1_raw, self.device, rows=16 * ops.c1_gconv_slab_tiles(h, w, blk.cout, s))
+        xs2 = None
+        if f.conv3_in:
+            pbw = front.bw
+            xs2 = pool.take((N, h2, w2, blk.cin), dt)
+            steps.append(Step(blk.name + ".conv1_conv2", "c1_gconv", lambda: ops.c1_gconv_c3in(
+                front.y2, front.sc, front.gate, pbw.w3.w, pbw.s3, pbw.h3, bw.c1g_w1f, bw.s1, bw.h1, bw.w2frag, bw.s2, bw.h2,
+                blk.gw, blk.cout, xs2=xs2, out=y2, pooled=pooled),
+                # the producer's y2 and shortcut map in, this block's y2 and the compact map out, the three weights
+                (2 * M * blk.cin + M2 * blk.cout + M2 * blk.cin) * es + (blk.cin * blk.cin + blk.cout * (blk.cin + blk.gw * 9)) * es,
+                2 * M * blk.cin * blk.cin + 2 * M * blk.cin * blk.cout + 2 * M2 * blk.cout * blk.gw * 9))
+            for t_ in (front.y2, front.sc, front.pooled, front.gate):       # the front block's temporaries die with that launch
+                pool.give(t_)
+            x = xs2
+        elif f.c1g:
             steps.append(Step(blk.name + ".conv1_conv2", "c1_gconv", lambda: ops.c1_gconv(
                 x, bw.c1g_w1f, bw.s1, bw.h1, bw.w2frag, bw.s2, bw.h2, blk.gw, s, blk.cout, G=G, out=y2, pooled=pooled),
                 (M * blk.cin + M2 * blk.cout) * es + blk.cout * (blk.cin + blk.gw * 9) * es,
@@ -787,7 +817,7 @@ class ForwardEngine:
                 y1, bw.w2, bw.s2, bw.h2, blk.gw, s, wfrag=bw.w2frag, out=y2, pooled=pooled),
                 (M + M2) * blk.cout * es + blk.cout * blk.gw * 9 * 4, 2 * M2 * blk.cout * blk.gw * 9))
         sc, shortcut, sc_from = x, [], None
-        gather = (s, h, w, h2, w2) if s > 1 else None
+        gather = (s, h, w, h2, w2) if (s > 1 and xs2 is None) else None      # (the compact map holds the gathered rows)
         if f.sc_in_conv3:
             sc, sc_from = None, (x, gather)
         elif blk.has_downsample:
@@ -800,16 +830,29 @@ class ForwardEngine:
         se, conv3 = self._se_conv3(bw, N, h2, w2, y2, pooled, gate, sc, out, out2=xs_next, sc_from=sc_from)
         steps += [se, *shortcut, conv3]                     # (the shortcut conv launches between the two)
         # liveness: everything but `out` (and the next block's slice) dies here
-        return out, xs_next, ([y1] if y1 is not None else []) + [y2, pooled, gate] + dead_site + ([sc] if shortcut else [])
+        return out, xs_next, (([y1] if y1 is not None else []) + [y2, pooled, gate] + dead_site + ([sc] if shortcut else [])
+                              + ([xs2] if xs2 is not None else []))
 
-    def _blocks(self, pool, steps, keep, taps, B, x, h, w, blocks, x_kept, out_last=None):
+    def _blocks(self, pool, steps, keep, taps, B, x, h, w, blocks, x_kept, out_last=None, front=None):
         """Appends the launches of a run of bottlenecks for B clips (N = B*T frames) to `steps`, each in the form that
         block_forms chose; x (N,h,w,Cin) is the input map (owned by `pool` unless x_kept).  out_last: where the last block
         writes its output (a slice of a buffer shared with the plan that continues the trunk) instead of a pool buffer.
-        Returns (x, h, w, x_kept)."""
+        front: the run stands behind the fused front, whose block (front.bw) has left y2 / sc / pooled / gate and still
+        lacks SE + conv3: x does not exist yet.  They are appended here, conv3 as its own launch into a map x or, when the
+        first block takes it in (conv3_in), inside that block's first launch.  Returns (x, h, w, x_kept)."""
         N, dt = B * self.pw.clip_len, self.act_dtype
         xs = q = None       # the compact slice and the tap maps of the coming block's site, where the launch in front wrote them
-        for bi, f in enumerate(block_forms(blocks, h, w, dt, taps, out_last is not None)):
+        forms = block_forms(blocks, h, w, dt, taps, out_last is not None, *(() if front is None else (front.bw,)))
+        if front is not None:
+            if forms and forms[0].conv3_in:
+                steps.append(self._se_conv3(front.bw, N, h, w, front.y2, front.pooled, front.gate, front.sc, None)[0])
+            else:
+                x = pool.take((N, h, w, front.bw.spec.cout), dt)
+                steps += self._se_conv3(front.bw, N, h, w, front.y2, front.pooled, front.gate, front.sc, x)
+                x_kept = self._block_done(pool, keep, taps, front.bw.spec, (front.y2, front.sc, front.pooled, front.gate), None,
+                                          True, x)
+                front = None
+        for bi, f in enumerate(forms):
             bw, last = blocks[bi], bi + 1 == len(blocks)
             # (conv1's map is taken in front of the site's buffers: the pool is best-fit, so the order of takes decides which
             # buffer a tensor lands in)
@@ -820,7 +863,8 @@ class ForwardEngine:
             if f.one_launch:
                 out, xs, q = self._one_launch(pool, steps, B, bw, f, x, xg, gb, None if last else blocks[bi + 1])
             else:
-                out, xs, dead = self._chain(pool, steps, B, bw, f, x, y1, gb.get("out"), out_last if last else None, dead)
+                out, xs, dead = self._chain(pool, steps, B, bw, f, x, y1, gb.get("out"), out_last if last else None, dead,
+                                            front if f.conv3_in else None)
                 q = None
             x_kept = self._block_done(pool, keep, taps, bw.spec, dead, x, x_kept, out)
             x, h, w = out, f.h2, f.w2
@@ -869,16 +913,16 @@ class ForwardEngine:
             sc = pool.take((N, h2, w2, blk.cout), dt)
             pooled = pool.take((N, parts, blk.cout), torch.float32)
             gate = pool.take((N, blk.cout), torch.float32)
-            out = pool.take((N, h2, w2, blk.cout), dt)
             M2 = N * h2 * w2
             steps.append(Step("s1_front", "s1_front", lambda y2=y2, sc=sc, pooled=pooled: ops.s1_front(
                 frames, Wt.front, crop, flip, y2=y2, shortcut=sc, pooled=pooled),
                               N * 3 * ch * cw + 2 * M2 * blk.cout * es,
                               2 * N * Ho * Wo * 32 * (27 + 2 * blk.cout) // 1 + 2 * M2 * blk.cout * blk.gw * 9))
-            steps += self._se_conv3(bw, N, h2, w2, y2, pooled, gate, sc, out)
-            x_kept = self._block_done(pool, keep, taps, blk, (y2, sc, pooled, gate), None, True, out)
-            x, h, w = out, h2, w2
+            # the block's SE + conv3 follow in _blocks, where the form of the block behind decides how conv3 is launched
+            front = SimpleNamespace(bw=bw, y2=y2, sc=sc, pooled=pooled, gate=gate)
+            x, h, w, x_kept = None, h2, w2, True
         else:
+            front = None
             x = pool.take((N, Ho, Wo, 32), dt)
             steps.append(Step("stem", "stem", lambda x=x: ops.stem(frames, Wt.stem_w, Wt.stem_scale, Wt.stem_shift, dt, crop,
                                                                    flip, out=x),
@@ -891,7 +935,7 @@ class ForwardEngine:
             blocks = blocks[:max(0, stop_at - (1 if fused_front else 0))]
         if trunk_out is not None and not blocks:
             raise ValueError("join_at must leave at least one un-fused bottleneck in the sub-batch plans")
-        x, h, w, x_kept = self._blocks(pool, steps, keep, taps, B, x, h, w, blocks, x_kept, out_last=trunk_out)
+        x, h, w, x_kept = self._blocks(pool, steps, keep, taps, B, x, h, w, blocks, x_kept, out_last=trunk_out, front=front)
         if stop_at is not None:          # trunk head only: the rest of the trunk runs once for all sub-batches (plan.tail)
             return SimpleNamespace(frames=frames, steps=steps, keep=keep, head_out=None, pool_bytes=pool.total_bytes(), B=B, T=T,
                                    h=h, w=w)

@@ -158,6 +158,35 @@ def c1_gconv(x, w1f, s1, h1, wfrag, scale, shift, gw, stride, C, G=None, out=Non
     return out, pooled
 
 
+def c1_gconv_c3in_fits(Hi, Wi, Cp, C):
+    """True when c1_gconv_c3in() serves a stride-2 block of Cp -> C channels behind a producer conv3 of Cp -> Cp."""
+    lib = _lib.load()
+    if not hasattr(lib, "tdeed_c1_gconv_c3in_fits"):    # an A/B flavour of the library built from an older revision
+        return False
+    return lib.tdeed_c1_gconv_c3in_fits(Hi, Wi, Cp, C) != 0
+
+
+def c1_gconv_c3in(y2p, scp, gate, w3frag, s3, h3, w1f, s1, h1, wfrag, scale, shift, gw, C, xs2=None, out=None, pooled=None):
+    """c1_gconv(gemm_ws(y2p, w3frag, Cp, Cp, s3, h3, ACT_RELU, residual=scp, a_scale=gate, a_scale_rows=Hi*Wi), ..., stride 2)
+    in one launch (tdeed_c1_gconv_c3in_fwd), bit for bit: the producer's conv3 runs per pixel tile in front of conv1 and its
+    output map never exists.  y2p / scp (N,Hi,Wi,Cp) bf16, gate (N,Cp) fp32, w3frag from packing.pack_ws_weights.
+    xs2 (N,Ho,Wo,Cp): receives the producer's output at even rows and columns (the rows the block's shortcut conv gathers)."""
+    _chk(y2p, "y2p", torch.bfloat16); _chk(scp, "scp", torch.bfloat16); _chk(gate, "gate", torch.float32)
+    _chk(xs2, "xs2", torch.bfloat16)
+    N, Hi, Wi, Cp = y2p.shape
+    Ho, Wo = (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1
+    if tuple(scp.shape) != (N, Hi, Wi, Cp) or gate.numel() != N * Cp or (xs2 is not None and xs2.numel() != N * Ho * Wo * Cp):
+        raise ValueError(f"c1_gconv_c3in: y2p {tuple(y2p.shape)}, scp {tuple(scp.shape)}, gate {tuple(gate.shape)}, "
+                         f"xs2 {None if xs2 is None else tuple(xs2.shape)} do not belong together")
+    if out is None:
+        out = torch.empty((N, Ho, Wo, C), dtype=y2p.dtype, device=y2p.device)
+    if pooled is None:
+        pooled = torch.empty((N, gconv3x3_parts(Hi, Wi, C, 2, y2p.dtype), C), dtype=torch.float32, device=y2p.device)
+    call("tdeed_c1_gconv_c3in_fwd", ptr(y2p), ptr(scp), ptr(gate), ptr(w3frag), ptr(s3), ptr(h3), ptr(xs2), N, Hi, Wi, Cp, C, gw,
+         ptr(w1f), ptr(s1), ptr(h1), ptr(wfrag), ptr(scale), ptr(shift), ptr(out), ptr(pooled), stream_ptr())
+    return out, pooled
+
+
 def bneck_fits(h, w, C, R):
     return _lib.load().tdeed_bneck_fits(h, w, C, R) != 0
 

@@ -1,5 +1,6 @@
 """GPU tool: conv1 + grouped 3x3 in one launch (tdeed_c1_gconv_fwd) alone at the shapes of the shipped models, with its phase
-time stamps (tdeed_c1_gconv_set_debug).
+time stamps (tdeed_c1_gconv_set_debug); then the form that also computes the producer's conv3 (tdeed_c1_gconv_c3in_fwd) against the
+two launches it replaces, at 800 x 56 x 56 x 24 -> 56, with the stamps of both.
     python tools/bench_c1_gconv.py"""
 import os
 import sys
@@ -7,7 +8,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from tdeed_amd import ops, _lib
-from tdeed_amd.engine import pack_mfma_frags, pack_gconv_frags
+from tdeed_amd.engine import pack_mfma_frags, pack_gconv_frags, pack_ws_weights
 
 DEV = "cuda"
 
@@ -65,3 +66,68 @@ for name, N, Hi, Cin, C, gw, stride in SHAPES:
     print(f"{name} N={N} {Hi}x{Hi} {Cin}->{C} stride {stride}: {us:7.1f} us per launch, {byt / us / 1e3:6.0f} GB/s algorithmic, {nwg} workgroups "
           f"({int(ok.sum())} stamped); first start -> last end {(d[:, 6].max() - d[:, 0].min()):.1f} us; workgroup median "
           f"{np.median(d[:, 6] - d[:, 0]):.2f} us: " + ", ".join(f"{n_} {v:.2f}" for n_, v in zip(names, ph)), flush=True)
+
+
+# ---- the producer's conv3 in front of conv1 (engine.S1_CONV3_IN_C1G): s1.b1.conv3 + s2.b1.conv1_conv2 of RegNetY-200MF
+PHASES = ["weights + halo", "conv1 tiles (wave 0)", "barrier", "grouped conv setup", "grouped conv tiles + stores", "squeeze sums"]
+
+
+def stamped(run, nwg):
+    """median phase times (us) of one stamped launch of `run`, and the median workgroup time"""
+    dbg = torch.zeros((nwg + 64, 8), dtype=torch.int64, device=DEV)
+    _lib.call("tdeed_c1_gconv_set_debug", dbg.data_ptr())
+    run()
+    torch.cuda.synchronize()
+    _lib.call("tdeed_c1_gconv_set_debug", None)
+    d = dbg.cpu().numpy().astype(np.float64)[:nwg] * 10.0 / 1e3
+    d = d[d[:, 6] > 0]
+    return [float(np.median(d[:, i + 1] - d[:, i])) for i in range(6)], float(np.median(d[:, 6] - d[:, 0]))
+
+
+N, Hi, Cp, C, gw = 800, 56, 24, 56, 8
+if not ops.c1_gconv_c3in_fits(Hi, Hi, Cp, C):
+    print("conv3 in front of conv1: not served by this library")
+    sys.exit(0)
+g = torch.Generator().manual_seed(1)
+y2p = torch.relu(torch.randn(N, Hi, Hi, Cp, generator=g)).to(torch.bfloat16).to(DEV)
+scp = torch.randn(N, Hi, Hi, Cp, generator=g).to(torch.bfloat16).to(DEV)
+gate = torch.sigmoid(torch.randn(N, Cp, generator=g)).to(DEV)
+W3 = pack_ws_weights((torch.randn(Cp, Cp, generator=g) / Cp ** 0.5).numpy(), torch.bfloat16, DEV)
+W1 = torch.randn(C, Cp, generator=g) / Cp ** 0.5
+W2 = torch.randn(C, gw, 3, 3, generator=g) / (gw * 9) ** 0.5
+vec = lambda n, s=0.1, o=0.0: (torch.randn(n, generator=g) * s + o).to(DEV)          # noqa: E731
+s3, h3, s1, h1, s2, h2 = vec(Cp, .1, 1.), vec(Cp), vec(C, .1, 1.), vec(C), vec(C, .1, 1.), vec(C)
+w1f = pack_mfma_frags(W1.numpy(), DEV, rows=16 * ops.c1_gconv_slab_tiles(Hi, Hi, C, 2))
+w2f = pack_gconv_frags(W2.numpy(), gw, DEV)
+Ho = (Hi - 1) // 2 + 1
+parts = ops.gconv3x3_parts(Hi, Hi, C, 2, torch.bfloat16)
+mid = torch.empty((N, Hi, Hi, Cp), dtype=torch.bfloat16, device=DEV)
+out, out_f = (torch.empty((N, Ho, Ho, C), dtype=torch.bfloat16, device=DEV) for _ in range(2))
+pooled, pooled_f = (torch.empty((N, parts, C), device=DEV) for _ in range(2))
+xs2 = torch.empty((N, Ho, Ho, Cp), dtype=torch.bfloat16, device=DEV)
+
+
+def conv3():
+    ops.gemm_ws(y2p, W3, Cp, Cp, s3, h3, ops.ACT_RELU, residual=scp, a_scale=gate, a_scale_rows=Hi * Hi, out=mid.view(-1, Cp))
+
+
+def c1g():
+    ops.c1_gconv(mid, w1f, s1, h1, w2f, s2, h2, gw, 2, C, out=out, pooled=pooled)
+
+
+def chain():
+    conv3()
+    c1g()
+
+
+def fused():
+    ops.c1_gconv_c3in(y2p, scp, gate, W3, s3, h3, w1f, s1, h1, w2f, s2, h2, gw, C, xs2=xs2, out=out_f, pooled=pooled_f)
+
+
+t3, tc, tch, tf = timeit(conv3), timeit(c1g), timeit(chain), timeit(fused)
+same = torch.equal(out, out_f) and torch.equal(pooled, pooled_f) and torch.equal(xs2, mid[:, ::2, ::2, :])
+print(f"conv3 in front of conv1, N={N} {Hi}x{Hi} {Cp}->{C}: conv3 alone {t3:.1f} us, c1_gconv alone {tc:.1f} us, the two back to back "
+      f"{tch:.1f} us, fused {tf:.1f} us; outputs identical: {same}")
+for label, run in (("c1_gconv", c1g), ("fused   ", fused)):
+    ph, wg = stamped(run, N * parts)
+    print(f"  {label} workgroup median {wg:.2f} us: " + ", ".join(f"{n_} {v:.2f}" for n_, v in zip(PHASES, ph)), flush=True)

@@ -24,7 +24,7 @@ import torch
 
 VARIANTS = [{}, {"TDEED_BNECK": "0"}, {"TDEED_C1_GCONV": "0"}, {"TDEED_GS_SRC_ORDER": "0"}, {"TDEED_SGP_GEMM": "0"},
             {"TDEED_SGP_FUSED": "0"}, {"TDEED_SGP_F32_STREAM": "0"}, ["BNECK_BLEND=False"], ["BNECK_QTAIL=False"], ["SC_IN_CONV3=False"],
-            ["BNECK_ONE_LAUNCH=False", "C1_GCONV=False"]]
+            ["S1_CONV3_IN_C1G=False"], ["BNECK_ONE_LAUNCH=False", "C1_GCONV=False"]]
 GEOMETRIES = [("rny002_gsf", 2, 100, 8, 224), ("rny008_gsf", 3, 100, 16, 224), ("rny008_gsf", 3, 250, 4, 224),
               ("rny002_gsm", 2, 16, 2, 224), ("rny002", 2, 16, 2, 224), ("rny002_gsf", 2, 16, 2, 112), ("rny002_gsf", 2, 16, 2, 96)]
 OPTIONS = [{}, dict(n_split=2), dict(n_split=2, join_at=3), dict(n_split=2, merge_tail=False), dict(fuse_front=False)]
