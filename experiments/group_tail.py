@@ -1,7 +1,7 @@
 """PARKED (round 4, measured slower): one temporal stage per GROUP of batches in flight.
 
 VERDICT r3 item 4 asked for the SGP encoder-decoder + heads to run once per group of in-flight batches (24 clips instead of
-3 x 8): built as three methods of ForwardEngine (below, verbatim; bind them with `attach(ForwardEngine)`), tested (every
+3 x 8): built as three methods of ForwardEngine (below; bind them with `attach(ForwardEngine)`), tested (every
 slot's logits equal the B=1 forwards, partial groups flushed) and measured on MI355X, cfg2, bf16, same box, bench.py with
 `--inflight D`:
 
@@ -43,14 +43,18 @@ def plan_group(self, B, H, W, depth=3, flip=False):
     N = depth * B
     f_slot = [torch.empty((B, T, C), dtype=self.act_dtype, device=dev) for _ in range(depth)]
     r_slot = [torch.empty((B * T, 2), dtype=torch.float32, device=dev) for _ in range(depth)]
-    subs = [self._build(B, H, W, bool(flip), set(), feat_out=f_slot[i], feat_rs=r_slot[i]) for i in range(depth)]
+    subs = []
+    for i in range(depth):
+        tb = self._builder(B)
+        tb.avgpool(*tb.trunk(H, W, self.crop_dim, bool(flip)), f_slot[i], r_slot[i])
+        subs.append(tb.sub_plan())
     feats = [torch.empty((N, T, C), dtype=self.act_dtype, device=dev) for _ in range(2)]
     frss = [torch.empty((N * T, 2), dtype=torch.float32, device=dev) for _ in range(2)]
     heads = [torch.empty((N * T, pw.n_out), dtype=torch.float32, device=dev) for _ in range(2)]
     tails = []
     for par in range(2):
         feats[par]._td_rowstat = frss[par]
-        tails.append(self._build_tail(N, feats[par], heads[par]))
+        tails.append(self._tail(N, feats[par], heads[par]))
     grp = SimpleNamespace(subs=subs, tails=tails, tail=tails[0], depth=depth, B=B, T=T, f_slot=f_slot, r_slot=r_slot,
                           feats=feats, frss=frss, heads=heads, head_out=heads[0], par=0, graphs=None, tail_graphs=None,
                           tail_stream=new_stream(dev), trunk_ev=[[torch.cuda.Event() for _ in range(depth)] for _ in range(2)],

@@ -501,6 +501,326 @@ class SgpBuilder:
         return cur
 
 
+TrunkGeometry = namedtuple("TrunkGeometry", "crop ch cw maps")
+
+
+def trunk_geometry(blocks, crop, H, W):
+    """Map sizes of the trunk over H x W frames.  Pure.  blocks: the block specs; crop: side of the centre crop (None or 0:
+    none).  crop: the rectangle (top, left, ch, cw) the first launch reads (None: the whole frame), ch, cw: its size;
+    maps[k]: (h, w, channels) of the map that block k reads -- maps[0] is the stem's output, maps[len(blocks)] the trunk's."""
+    ch, cw, rect = H, W, None
+    if crop is not None and crop > 0 and (crop != H or crop != W):
+        ch = cw = crop
+        rect = (int(round((H - ch) / 2.0)), int(round((W - cw) / 2.0)), ch, cw)
+    h, w = (ch + 1) // 2, (cw + 1) // 2
+    maps = [(h, w, blocks[0].cin)]
+    for blk in blocks:
+        h, w = (h - 1) // blk.stride + 1, (w - 1) // blk.stride + 1
+        maps.append((h, w, blk.cout))
+    return TrunkGeometry(rect, ch, cw, maps)
+
+
+class SubPlan:
+    """One chain of launches of a plan, issued on one stream: those of a sub-batch (`frames` is their input buffer; h, w: the
+    size of the map they end in, where they stop inside the trunk) or, with frames = None, those behind the sub-batches' join
+    over all the plan's clips.  sgp_out: the encoder-decoder's output, where the chain holds the temporal stage."""
+    __slots__ = ("frames", "steps", "keep", "head_out", "pool_bytes", "B", "T", "h", "w", "sgp_out")
+
+    def __init__(self, frames, steps, keep, head_out, pool_bytes, B, T, h=None, w=None):
+        self.frames, self.steps, self.keep, self.head_out, self.pool_bytes = frames, steps, keep, head_out, pool_bytes
+        self.B, self.T, self.h, self.w, self.sgp_out = B, T, h, w, keep.get("sgp_out")
+
+
+class Plan:
+    """What run_plan launches: subs[i] on streams[i] (None: the launching stream), then `tail` behind their join."""
+    __slots__ = ("subs", "streams", "tail", "steps", "head_out", "keep", "graph", "pool_bytes", "B", "T", "trunk_map", "out", "h",
+                 "w", "trunk_in", "flip_buf")
+
+    def __init__(self, subs, head_out, B, T, streams=None, tail=None, trunk_map=None, out=None, h=None, w=None, trunk_in=None,
+                 flip_buf=None):
+        self.subs, self.streams, self.tail = subs, streams or [None] * len(subs), tail
+        chains = subs + ([] if tail is None else [tail])
+        self.steps = [st for c in chains for st in c.steps]
+        self.pool_bytes = sum(c.pool_bytes for c in chains)
+        self.head_out, self.keep, self.graph, self.B, self.T = head_out, (subs[0].keep if subs else {}), None, B, T
+        self.trunk_map, self.out, self.h, self.w, self.trunk_in, self.flip_buf = trunk_map, out, h, w, trunk_in, flip_buf
+
+
+# the block in the fused front while its SE + conv3 are still to be emitted; behind bw its temporaries, in the order taken
+_Front = namedtuple("_Front", "bw y2 sc pooled gate")
+
+
+class TrunkBuilder:
+    """Appends the launches of B clips -- the trunk (fused front or stem, bottlenecks), the pooling, the temporal stage with
+    the heads: the three stages below -- to a step list of its own over a buffer pool of its own."""
+
+    def __init__(self, pw, act_dtype, device, taps, B, fuse_front=True):
+        self.pw, self.act_dtype, self.device, self.taps, self.B, self.fuse_front = pw, act_dtype, device, taps, B, fuse_front
+        self.pool, self.steps, self.keep = _Pool(device), [], {}
+        self.N = B * pw.clip_len
+        self.frames = self.head_out = None
+        self.front = None          # the _Front of a trunk whose first block sits in the fused front, until its conv3 is emitted
+
+    # ------------------------------------------------------------------ bottlenecks
+    def _se_conv3(self, bw, h2, w2, y2, pooled, gate, sc, out, out2=None, sc_from=None):
+        """The last two steps of a bottleneck that is not one launch: the SE excitation from the grouped conv's pooled sums,
+        and conv3 with the gate on its operand + shortcut `sc` + ReLU (out2: the next block's gate-shift slice beside `out`).
+        sc_from = (x, gather): no `sc` map -- conv3's launch computes the shortcut conv from the block's input x itself."""
+        blk, es, N, M2 = bw.spec, _esz(self.act_dtype), self.N, self.N * h2 * w2
+        se = Step(blk.name + ".se", "se_gate", lambda: _se(pooled, 1.0 / (h2 * w2), bw, gate),
+                  2 * N * blk.cout * 4 + 2 * blk.cout * blk.se_rd * 4, 4 * N * blk.cout * blk.se_rd)
+        if sc_from is not None:
+            x, gather = sc_from
+            return (se, Step(blk.name + ".conv3", "gemm_ws", lambda: ops.gemm_ws_sc(
+                y2, bw.w3.w, blk.cout, blk.cout, bw.s3, bw.h3, x, bw.wd.w, blk.cin, bw.sd, bw.hd, ops.ACT_RELU, a_scale=gate,
+                a_scale_rows=h2 * w2, gather=gather, out=out, M=M2, out2=out2),
+                # y2, the gathered rows of x, out, both weights
+                (M2 * (2 * blk.cout + blk.cin) + blk.cout * (blk.cout + blk.cin)) * es,
+                2 * M2 * blk.cout * (blk.cout + blk.cin)))
+        return (se, Step(blk.name + ".conv3", bw.w3.kern(M2), lambda: bw.w3.run(
+            y2, bw.s3, bw.h3, ops.ACT_RELU, residual=sc, a_scale=gate, a_scale_rows=h2 * w2, out=out, M=M2, out2=out2),
+            *gemm_cost(M2, blk.cout, blk.cout, es, True)))
+
+    def _block_done(self, blk, dead, x, x_kept, out):
+        """A bottleneck's epilogue: its temporaries `dead` and its input x (unless a tap keeps it, or it is not the pool's) go
+        back to the pool, its output is recorded when it is a tap.  Returns whether the output must be kept."""
+        for t_ in dead:
+            self.pool.give(t_)
+        if not x_kept and hasattr(x, "_td_raw"):
+            self.pool.give(x)
+        tapname = "_features." + blk.name
+        if tapname in self.taps:
+            self.keep[tapname] = out
+        return tapname in self.taps
+
+    def _gs_site(self, bw, f, xg, q):
+        """Appends the gate-shift launch of a block's site over xg (the block's input, or its compact slice) and returns the
+        site's buffers.  q: the site's tap maps where the launch in front of the block wrote them (f.q_given).  Under
+        f.blend_in the launch leaves only the gates and the sums (the blend runs inside the bottleneck's launch); otherwise
+        gb["out"] is the blended slice that conv1 splices in."""
+        pool, B, blk, T = self.pool, self.B, bw.spec, self.pw.clip_len
+        N, F, Fp = self.N, blk.gsf_fold, f.Fp
+        M = N * f.h * f.w
+        gb = dict(gate=pool.take((N, f.h, f.w, 2), torch.float32),
+                  q=(q if f.q_given else pool.take((N, f.h, f.w, 6), torch.float32)),
+                  ysum=pool.take((N, F), torch.float32),
+                  xsum=pool.take((N, F), torch.float32))
+        if not f.blend_in:
+            gb["out"] = pool.take((M, Fp), self.act_dtype)
+            if bw.gs_cw1 is not None:
+                gb["fw"] = pool.take((B, F, T), torch.float32)
+        self.steps.append(Step(blk.name + ".gate_shift", "gate_shift", lambda: ops.gate_shift(
+            xg, B, T, F, Fp, bw.gs_scale, bw.gs_shift, bw.gs_wq, bw.gs_b3d, bw.gs_cw1, bw.gs_cb1,
+            bw.gs_cw2, bw.gs_cb2, bufs=gb, wqf=bw.gs_wqf, src_order=bw.gs_src, gates_only=f.blend_in, q_given=f.q_given),
+            M * ((1 if f.blend_in else 2) * F + (0 if f.blend_in else Fp)) * _esz(self.act_dtype) + M * 16, 2 * M * F * 27))
+        tap = "_features." + blk.name + ".gs_out"
+        if tap in self.taps:
+            if bw.gs_src:
+                raise ValueError("the gs_out tap is in module channel order: build the engine with TDEED_GS_SRC_ORDER=0")
+            self.keep[tap] = gb["out"]
+        return gb
+
+    def _one_launch(self, bw, f, x, xg, gb, nbw):
+        """Appends a bottleneck as ONE launch, conv1 (+ splice) -> conv2 -> SE -> conv3 + shortcut: only x and the output cross
+        HBM.  gb: the buffers of the block's site ({} without one), xg: what the site read, nbw: the next block's weights.
+        Returns the output, the next site's compact slice and the next site's tap maps (None where the form has none)."""
+        pool, blk, T, dt = self.pool, bw.spec, self.pw.clip_len, self.act_dtype
+        N, es = self.N, _esz(dt)
+        M = N * f.h * f.w
+        out = pool.take((N, f.h, f.w, blk.cout), dt)
+        xs_next = pool.take((N, f.h, f.w, f.slice_next), dt) if f.slice_next else None
+        o2 = xs_next.view(-1, f.slice_next) if f.slice_next else None
+        q_next = None
+        if f.blend_in:
+            qt = None
+            if f.qtail:
+                q_next = pool.take((N, f.h, f.w, 6), torch.float32)
+                qt = (nbw.gs_wpf, nbw.gs_bnq, nbw.spec.gsf_fold, q_next)
+            run = lambda: ops.bneck_gs(                                                                       # noqa: E731
+                x, xg, gb["gate"], gb["ysum"], gb["xsum"], bw.gs_cw1, bw.gs_cb1, bw.gs_cw2, bw.gs_cb2, T, blk.gsf_fold, f.Fp,
+                bw.fused.w1f, bw.s1, bw.h1, bw.fused.w2f, bw.s2, bw.h2, bw.se_mf.w1f, bw.se_b1, bw.se_mf.w2f, bw.se_b2,
+                blk.se_rd, bw.fused.w3f, bw.s3, bw.h3, out=out, out2=o2, w2_tap_major=bw.fused.w2_tap_major, qtail=qt)
+        else:
+            G = gb.get("out")
+            run = lambda: ops.bneck(                                                                          # noqa: E731
+                x, bw.fused.w1f, bw.s1, bw.h1, bw.fused.w2f, bw.s2, bw.h2, bw.se_mf.w1f, bw.se_b1, bw.se_mf.w2f, bw.se_b2,
+                blk.se_rd, bw.fused.w3f, bw.s3, bw.h3, G=G, out=out, out2=o2, w2_tap_major=bw.fused.w2_tap_major)
+        self.steps.append(Step(blk.name + ".bneck", "bneck", run,
+                               # x in, out; with the blend: each slice piece's temporal neighbour and the gate maps; the tail's Q
+                               (2 * M * blk.cout + (M * f.Fp if f.blend_in else 0)) * es + (8 * M if f.blend_in else 0)
+                               + (24 * M if f.qtail else 0)
+                               + (2 * blk.cout * blk.cout + blk.cout * blk.gw * 9) * es,
+                               2 * M * blk.cout * (2 * blk.cout + blk.gw * 9)))
+        return out, xs_next, q_next
+
+    def _chain(self, bw, f, x, y1, G, out, dead_site):
+        """Appends a bottleneck as a chain of launches: conv1 into y1 and the grouped conv, or both in one launch (f.c1g, no
+        y1); SE; the shortcut conv, unless conv3's launch computes it (f.sc_in_conv3); conv3.  G: the blended slice of the
+        block's site that conv1 splices in (None without a site), out: where the block writes instead of a pool buffer,
+        dead_site: the site's buffers.  Under f.conv3_in the first launch computes the conv3 of the fused front's block
+        (self.front) from its y2 / sc / gate -- there is no x; the shortcut reads the compact stride-2 map that launch writes.
+        Returns the output, the next site's compact slice and everything that dies here."""
+        pool, steps, blk, dt = self.pool, self.steps, bw.spec, self.act_dtype
+        N, es, s = self.N, _esz(dt), blk.stride
+        h, w, h2, w2 = f.h, f.w, f.h2, f.w2
+        M, M2 = N * h * w, N * h2 * w2
+        if y1 is not None:
+            splice = dict(A0=G, k0=f.Fp) if f.site else {}
+            steps.append(Step(blk.name + ".conv1", bw.w1.kern(M), lambda: bw.w1.run(
+                x, bw.s1, bw.h1, ops.ACT_RELU, out=y1, M=M, **splice), *gemm_cost(M, blk.cin, blk.cout, es)))
+        y2 = pool.take((N, h2, w2, blk.cout), dt)
+        parts = ops.gconv3x3_parts(h, w, blk.cout, s, dt) if bw.w2frag is not None else 1
+        pooled = pool.take((N, parts, blk.cout), torch.float32)
+        gate = pool.take((N, blk.cout), torch.float32)
+        if f.c1g and bw.c1g_w1f is None:
+            bw.c1g_w1f = pack_mfma_frags(bw.w1_raw, self.device, rows=16 * ops.c1_gconv_slab_tiles(h, w, blk.cout, s))
+        xs2 = None
+        if f.conv3_in:
+            front, self.front = self.front, None
+            pbw = front.bw
+            xs2 = pool.take((N, h2, w2, blk.cin), dt)
+            steps.append(Step(blk.name + ".conv1_conv2", "c1_gconv", lambda: ops.c1_gconv_c3in(
+                front.y2, front.sc, front.gate, pbw.w3.w, pbw.s3, pbw.h3, bw.c1g_w1f, bw.s1, bw.h1, bw.w2frag, bw.s2, bw.h2,
+                blk.gw, blk.cout, xs2=xs2, out=y2, pooled=pooled),
+                # the producer's y2 and shortcut map in, this block's y2 and the compact map out, the three weights
+                (2 * M * blk.cin + M2 * blk.cout + M2 * blk.cin) * es + (blk.cin * blk.cin + blk.cout * (blk.cin + blk.gw * 9)) * es,
+                2 * M * blk.cin * blk.cin + 2 * M * blk.cin * blk.cout + 2 * M2 * blk.cout * blk.gw * 9))
+            for t_ in front[1:]:                                            # the front block's temporaries die with that launch
+                pool.give(t_)
+            x = xs2
+        elif f.c1g:
+            steps.append(Step(blk.name + ".conv1_conv2", "c1_gconv", lambda: ops.c1_gconv(
+                x, bw.c1g_w1f, bw.s1, bw.h1, bw.w2frag, bw.s2, bw.h2, blk.gw, s, blk.cout, G=G, out=y2, pooled=pooled),
+                (M * blk.cin + M2 * blk.cout) * es + blk.cout * (blk.cin + blk.gw * 9) * es,
+                2 * M * blk.cin * blk.cout + 2 * M2 * blk.cout * blk.gw * 9))
+        else:
+            steps.append(Step(blk.name + ".conv2", "gconv3x3", lambda: ops.gconv3x3(
+                y1, bw.w2, bw.s2, bw.h2, blk.gw, s, wfrag=bw.w2frag, out=y2, pooled=pooled),
+                (M + M2) * blk.cout * es + blk.cout * blk.gw * 9 * 4, 2 * M2 * blk.cout * blk.gw * 9))
+        sc, shortcut, sc_from = x, [], None
+        gather = (s, h, w, h2, w2) if (s > 1 and xs2 is None) else None      # (the compact map holds the gathered rows)
+        if f.sc_in_conv3:
+            sc, sc_from = None, (x, gather)
+        elif blk.has_downsample:
+            sc = pool.take((N, h2, w2, blk.cout), dt)
+            shortcut = [Step(blk.name + ".downsample", bw.wd.kern(M2), lambda: bw.wd.run(
+                x, bw.sd, bw.hd, ops.ACT_NONE, gather=gather, out=sc, M=M2), *gemm_cost(M2, blk.cin, blk.cout, es))]
+        if out is None:
+            out = pool.take((N, h2, w2, blk.cout), dt)
+        xs_next = pool.take((N, h2, w2, f.slice_next), dt) if f.slice_next else None
+        se, conv3 = self._se_conv3(bw, h2, w2, y2, pooled, gate, sc, out, out2=xs_next, sc_from=sc_from)
+        steps += [se, *shortcut, conv3]                     # (the shortcut conv launches between the two)
+        # liveness: everything but `out` (and the next block's slice) dies here
+        return out, xs_next, (([y1] if y1 is not None else []) + [y2, pooled, gate] + dead_site + ([sc] if shortcut else [])
+                              + ([xs2] if xs2 is not None else []))
+
+    def _blocks(self, x, h, w, blocks, x_kept, out_last=None):
+        """Appends the launches of a run of bottlenecks, each in the form that block_forms chose; x (N,h,w,Cin) is the input
+        map (owned by the pool unless x_kept).  out_last: where the last block writes its output (a slice of a buffer shared
+        with the plan that continues the trunk) instead of a pool buffer.  Behind the fused front (self.front) x does not
+        exist yet: the front block's SE + conv3 are appended here, conv3 as its own launch into a map x or, when the first
+        block takes it in (conv3_in), inside that block's first launch.  Returns (x, h, w, x_kept)."""
+        pool, N, dt, fr = self.pool, self.N, self.act_dtype, self.front
+        xs = q = None       # the compact slice and the tap maps of the coming block's site, where the launch in front wrote them
+        forms = block_forms(blocks, h, w, dt, self.taps, out_last is not None, *(() if fr is None else (fr.bw,)))
+        if fr is not None:
+            if forms and forms[0].conv3_in:
+                self.steps.append(self._se_conv3(fr.bw, h, w, fr.y2, fr.pooled, fr.gate, fr.sc, None)[0])
+            else:
+                x = pool.take((N, h, w, fr.bw.spec.cout), dt)
+                self.steps += self._se_conv3(fr.bw, h, w, fr.y2, fr.pooled, fr.gate, fr.sc, x)
+                x_kept = self._block_done(fr.bw.spec, fr[1:], None, True, x)
+                self.front = None
+        for bi, f in enumerate(forms):
+            bw, last = blocks[bi], bi + 1 == len(blocks)
+            # (conv1's map is taken in front of the site's buffers: the pool is best-fit, so the order of takes decides which
+            # buffer a tensor lands in)
+            y1 = None if (f.one_launch or f.c1g) else pool.take((N, f.h, f.w, bw.spec.cout), dt)
+            xg = xs if f.slice_in else x
+            gb = self._gs_site(bw, f, xg, q) if f.site else {}
+            dead = list(gb.values()) + ([xs] if f.slice_in else [])
+            if f.one_launch:
+                out, xs, q = self._one_launch(bw, f, x, xg, gb, None if last else blocks[bi + 1])
+            else:
+                out, xs, dead = self._chain(bw, f, x, y1, gb.get("out"), out_last if last else None, dead)
+                q = None
+            x_kept = self._block_done(bw.spec, dead, x, x_kept, out)
+            x, h, w = out, f.h2, f.w2
+        return x, h, w, x_kept
+
+    # ------------------------------------------------------------------ the three stages
+    def trunk(self, H, W, crop, flip, frames_dtype=torch.uint8, stop=None, out_last=None):
+        """Stage 1: the fused front or the stem over self.frames (N,3,H,W), made here, and the blocks [0, stop) (None: all).
+        crop: side of the centre crop (None: the caller's window as it is); flip: bool (all frames) or a uint8 device tensor
+        (N,) of per-frame flags (the augmented eval path); out_last: see _blocks.  Returns (x, h, w, x_kept) of its map."""
+        Wt, pool, steps, N, dt, es = self.pw.W, self.pool, self.steps, self.N, self.act_dtype, _esz(self.act_dtype)
+        geo = trunk_geometry(self.pw.spec.blocks, crop, H, W)
+        rect, ch, cw, (Ho, Wo, c0) = geo.crop, geo.ch, geo.cw, geo.maps[0]
+        self.frames = frames = torch.empty((N, 3, H, W), dtype=frames_dtype, device=self.device)
+        blocks = list(Wt.blocks[:stop])
+        if (Wt.front is not None and "_features.stem" not in self.taps and self.fuse_front and frames_dtype == torch.uint8
+                and not isinstance(flip, torch.Tensor) and ops.s1_front_parts(ch, cw, Wt.blocks[0].spec.cout) > 0):
+            bw = blocks.pop(0)
+            blk, (h, w, _) = bw.spec, geo.maps[1]
+            parts, M2 = ops.s1_front_parts(ch, cw, blk.cout), N * h * w
+            y2 = pool.take((N, h, w, blk.cout), dt)
+            sc = pool.take((N, h, w, blk.cout), dt)
+            pooled = pool.take((N, parts, blk.cout), torch.float32)
+            gate = pool.take((N, blk.cout), torch.float32)
+            steps.append(Step("s1_front", "s1_front", lambda: ops.s1_front(
+                frames, Wt.front, rect, flip, y2=y2, shortcut=sc, pooled=pooled),
+                              N * 3 * ch * cw + 2 * M2 * blk.cout * es,
+                              2 * N * Ho * Wo * 32 * (27 + 2 * blk.cout) // 1 + 2 * M2 * blk.cout * blk.gw * 9))
+            # the block's SE + conv3 follow in _blocks, where the form of the block behind decides how conv3 is launched
+            self.front = _Front(bw, y2, sc, pooled, gate)
+            x, x_kept = None, True
+        else:
+            x, h, w = pool.take((N, Ho, Wo, c0), dt), Ho, Wo
+            steps.append(Step("stem", "stem", lambda: ops.stem(frames, Wt.stem_w, Wt.stem_scale, Wt.stem_shift, dt, rect, flip,
+                                                               out=x),
+                              N * 3 * ch * cw + N * Ho * Wo * 32 * es, 2 * N * Ho * Wo * 32 * 27))
+            x_kept = "_features.stem" in self.taps
+            if x_kept:
+                self.keep["_features.stem"] = x
+        if out_last is not None and not blocks:
+            raise ValueError("join_at must leave at least one un-fused bottleneck in the sub-batch plans")
+        return self._blocks(x, h, w, blocks, x_kept, out_last=out_last)
+
+    def avgpool(self, x, h, w, x_kept, feat=None, frs=None):
+        """Stage 2: avg-pool + positional encoding of the trunk's map x into feat (default: a pool buffer of the temporal
+        stage's stream type), with the LayerNorm statistics of the feature rows for the first SGP block's front kernel (frs:
+        the caller's slice of a shared buffer); x goes back to the pool unless x_kept.  Returns feat."""
+        pw, Wt, B, C = self.pw, self.pw.W, self.B, self.pw.spec.feat_dim
+        if feat is None:
+            feat = self.pool.take((B, pw.clip_len, C), sgp_stream_dtype(self.act_dtype, self.device))
+        if frs is None:
+            frs = torch.empty((self.N, 2), dtype=torch.float32, device=self.device)
+        feat._td_rowstat = frs
+        self.steps.append(Step("avgpool", "avgpool_posenc", lambda: ops.avgpool_posenc(x, B, pw.clip_len, Wt.temp_enc, out=feat,
+                                                                                      rowstat=frs),
+                               (self.N * h * w + self.N) * C * _esz(self.act_dtype)))
+        self.keep["feat"] = feat
+        if not x_kept:
+            self.pool.give(x)
+        return feat
+
+    def sgp_heads(self, feat, head_out=None):
+        """Stage 3: the SGP encoder-decoder over feat (its output: keep["sgp_out"]) and the heads into head_out (default: a
+        buffer of its own)."""
+        pw, Wt, N, C = self.pw, self.pw.W, self.N, self.pw.spec.feat_dim
+        if head_out is None:
+            head_out = torch.empty((N, pw.n_out), dtype=torch.float32, device=self.device)
+        self.head_out = head_out
+        cur = SgpBuilder(self.pool, self.steps, self.keep, self.taps, self.B, self.act_dtype).pyramid(
+            feat, pw.clip_len, pw.n_layers, Wt.sgp, Wt.mixer)
+        self.steps.append(Step("heads", "heads", lambda: ops.heads(cur, Wt.head_w, Wt.head_b, out=head_out),
+                               N * C * _esz(self.act_dtype) + N * pw.n_out * 4, 2 * N * C * pw.n_out))
+        self.keep["sgp_out"] = cur
+
+    def sub_plan(self, h=None, w=None):
+        return SubPlan(self.frames, self.steps, self.keep, self.head_out, self.pool.total_bytes(), self.B, self.pw.clip_len, h, w)
+
+
 class PackedWeights:
     """Device-side weights in kernel layouts.  ``state``: reference key grammar."""
 
@@ -660,307 +980,35 @@ class ForwardEngine:
         self._frame_starts = {}
 
     # ------------------------------------------------------------------ plan construction
-    def _se_conv3(self, bw, N, h2, w2, y2, pooled, gate, sc, out, out2=None, sc_from=None):
-        """The last two steps of a bottleneck that is not one launch: the SE excitation from the grouped conv's pooled sums,
-        and conv3 with the gate on its operand + shortcut `sc` + ReLU (out2: the next block's gate-shift slice beside `out`).
-        sc_from = (x, gather): no `sc` map -- conv3's launch computes the shortcut conv from the block's input x itself."""
-        blk, es, M2 = bw.spec, _esz(self.act_dtype), N * h2 * w2
-        se = Step(blk.name + ".se", "se_gate", lambda: _se(pooled, 1.0 / (h2 * w2), bw, gate),
-                  2 * N * blk.cout * 4 + 2 * blk.cout * blk.se_rd * 4, 4 * N * blk.cout * blk.se_rd)
-        if sc_from is not None:
-            x, gather = sc_from
-            return (se, Step(blk.name + ".conv3", "gemm_ws", lambda: ops.gemm_ws_sc(
-                y2, bw.w3.w, blk.cout, blk.cout, bw.s3, bw.h3, x, bw.wd.w, blk.cin, bw.sd, bw.hd, ops.ACT_RELU, a_scale=gate,
-                a_scale_rows=h2 * w2, gather=gather, out=out, M=M2, out2=out2),
-                # y2, the gathered rows of x, out, both weights
-                (M2 * (2 * blk.cout + blk.cin) + blk.cout * (blk.cout + blk.cin)) * es,
-                2 * M2 * blk.cout * (blk.cout + blk.cin)))
-        return (se, Step(blk.name + ".conv3", bw.w3.kern(M2), lambda: bw.w3.run(
-            y2, bw.s3, bw.h3, ops.ACT_RELU, residual=sc, a_scale=gate, a_scale_rows=h2 * w2, out=out, M=M2, out2=out2),
-            *gemm_cost(M2, blk.cout, blk.cout, es, True)))
+    def _builder(self, B, taps=()):
+        return TrunkBuilder(self.pw, self.act_dtype, self.device, set(taps), B, self.fuse_front)
 
-    @staticmethod
-    def _block_done(pool, keep, taps, blk, dead, x, x_kept, out):
-        """A bottleneck's epilogue: its temporaries `dead` and its input x (unless a tap keeps it, or it is not the pool's) go
-        back to the pool, its output is recorded when it is a tap.  Returns whether the output must be kept."""
-        for t_ in dead:
-            pool.give(t_)
-        if not x_kept and hasattr(x, "_td_raw"):
-            pool.give(x)
-        tapname = "_features." + blk.name
-        if tapname in taps:
-            keep[tapname] = out
-        return tapname in taps
+    def _geometry(self, H, W):
+        return trunk_geometry(self.pw.spec.blocks, self.crop_dim, H, W)
 
-    def _avgpool(self, steps, B, x, h, w, feat, frs=None):
-        """Appends avg-pool + positional encoding of the trunk's map x into feat, with the LayerNorm statistics of the feature
-        rows for the first SGP block's front kernel (frs: the caller's slice of a shared buffer)."""
-        pw, Wt = self.pw, self.pw.W
-        N, C = B * pw.clip_len, pw.spec.feat_dim
-        if frs is None:
-            frs = torch.empty((N, 2), dtype=torch.float32, device=self.device)
-        feat._td_rowstat = frs
-        steps.append(Step("avgpool", "avgpool_posenc", lambda: ops.avgpool_posenc(x, B, pw.clip_len, Wt.temp_enc, out=feat,
-                                                                                 rowstat=frs),
-                          (N * h * w + N) * C * _esz(self.act_dtype)))
+    def _whole(self, B, H, W, flip, taps=(), crop=None, head_out=None, frames_dtype=torch.uint8):
+        """Sub-plan of a whole forward of B clips: the three stages in a row."""
+        tb = self._builder(B, taps)
+        feat = tb.avgpool(*tb.trunk(H, W, crop, flip, frames_dtype))
+        tb.sgp_heads(feat, head_out)
+        return tb.sub_plan()
 
-    def _sgp_heads(self, pool, steps, keep, taps, B, feat, head_out):
-        """Appends the SGP encoder-decoder over feat and the heads; returns the encoder-decoder's output."""
-        pw, Wt = self.pw, self.pw.W
-        N, C = B * pw.clip_len, pw.spec.feat_dim
-        cur = SgpBuilder(pool, steps, keep, taps, B, self.act_dtype).pyramid(feat, pw.clip_len, pw.n_layers, Wt.sgp, Wt.mixer)
-        steps.append(Step("heads", "heads", lambda: ops.heads(cur, Wt.head_w, Wt.head_b, out=head_out),
-                          N * C * _esz(self.act_dtype) + N * pw.n_out * 4, 2 * N * C * pw.n_out))
-        return cur
+    def _head(self, B, H, W, flip, k, out):
+        """Sub-plan of the trunk's head for B clips: the front or stem and the blocks [0, k), the last one writing into `out`."""
+        tb = self._builder(B)
+        _, h, w, _ = tb.trunk(H, W, self.crop_dim, flip, stop=k, out_last=out)
+        return tb.sub_plan(h, w)
 
-    def _gs_site(self, pool, steps, keep, taps, B, bw, f, xg, q):
-        """Appends the gate-shift launch of a block's site over xg (the block's input, or its compact slice) and returns the
-        site's buffers.  q: the site's tap maps where the launch in front of the block wrote them (f.q_given).  Under
-        f.blend_in the launch leaves only the gates and the sums (the blend runs inside the bottleneck's launch); otherwise
-        gb["out"] is the blended slice that conv1 splices in."""
-        blk, T = bw.spec, self.pw.clip_len
-        N, F, Fp = B * T, blk.gsf_fold, f.Fp
-        M = N * f.h * f.w
-        gb = dict(gate=pool.take((N, f.h, f.w, 2), torch.float32),
-                  q=(q if f.q_given else pool.take((N, f.h, f.w, 6), torch.float32)),
-                  ysum=pool.take((N, F), torch.float32),
-                  xsum=pool.take((N, F), torch.float32))
-        if not f.blend_in:
-            gb["out"] = pool.take((M, Fp), self.act_dtype)
-            if bw.gs_cw1 is not None:
-                gb["fw"] = pool.take((B, F, T), torch.float32)
-        steps.append(Step(blk.name + ".gate_shift", "gate_shift", lambda: ops.gate_shift(
-            xg, B, T, F, Fp, bw.gs_scale, bw.gs_shift, bw.gs_wq, bw.gs_b3d, bw.gs_cw1, bw.gs_cb1,
-            bw.gs_cw2, bw.gs_cb2, bufs=gb, wqf=bw.gs_wqf, src_order=bw.gs_src, gates_only=f.blend_in, q_given=f.q_given),
-            M * ((1 if f.blend_in else 2) * F + (0 if f.blend_in else Fp)) * _esz(self.act_dtype) + M * 16, 2 * M * F * 27))
-        tap = "_features." + blk.name + ".gs_out"
-        if tap in taps:
-            if bw.gs_src:
-                raise ValueError("the gs_out tap is in module channel order: build the engine with TDEED_GS_SRC_ORDER=0")
-            keep[tap] = gb["out"]
-        return gb
-
-    def _one_launch(self, pool, steps, B, bw, f, x, xg, gb, nbw):
-        """Appends a bottleneck as ONE launch, conv1 (+ splice) -> conv2 -> SE -> conv3 + shortcut: only x and the output cross
-        HBM.  gb: the buffers of the block's site ({} without one), xg: what the site read, nbw: the next block's weights.
-        Returns the output, the next site's compact slice and the next site's tap maps (None where the form has none)."""
-        blk, T, dt = bw.spec, self.pw.clip_len, self.act_dtype
-        N, es = B * T, _esz(dt)
-        M = N * f.h * f.w
-        out = pool.take((N, f.h, f.w, blk.cout), dt)
-        xs_next = pool.take((N, f.h, f.w, f.slice_next), dt) if f.slice_next else None
-        o2 = xs_next.view(-1, f.slice_next) if f.slice_next else None
-        q_next = None
-        if f.blend_in:
-            qt = None
-            if f.qtail:
-                q_next = pool.take((N, f.h, f.w, 6), torch.float32)
-                qt = (nbw.gs_wpf, nbw.gs_bnq, nbw.spec.gsf_fold, q_next)
-            run = lambda: ops.bneck_gs(                                                                       # noqa: E731
-                x, xg, gb["gate"], gb["ysum"], gb["xsum"], bw.gs_cw1, bw.gs_cb1, bw.gs_cw2, bw.gs_cb2, T, blk.gsf_fold, f.Fp,
-                bw.fused.w1f, bw.s1, bw.h1, bw.fused.w2f, bw.s2, bw.h2, bw.se_mf.w1f, bw.se_b1, bw.se_mf.w2f, bw.se_b2,
-                blk.se_rd, bw.fused.w3f, bw.s3, bw.h3, out=out, out2=o2, w2_tap_major=bw.fused.w2_tap_major, qtail=qt)
-        else:
-            G = gb.get("out")
-            run = lambda: ops.bneck(                                                                          # noqa: E731
-                x, bw.fused.w1f, bw.s1, bw.h1, bw.fused.w2f, bw.s2, bw.h2, bw.se_mf.w1f, bw.se_b1, bw.se_mf.w2f, bw.se_b2,
-                blk.se_rd, bw.fused.w3f, bw.s3, bw.h3, G=G, out=out, out2=o2, w2_tap_major=bw.fused.w2_tap_major)
-        steps.append(Step(blk.name + ".bneck", "bneck", run,
-                          # x in, out; with the blend: each slice piece's temporal neighbour and the gate maps; the tail's Q
-                          (2 * M * blk.cout + (M * f.Fp if f.blend_in else 0)) * es + (8 * M if f.blend_in else 0)
-                          + (24 * M if f.qtail else 0)
-                          + (2 * blk.cout * blk.cout + blk.cout * blk.gw * 9) * es,
-                          2 * M * blk.cout * (2 * blk.cout + blk.gw * 9)))
-        return out, xs_next, q_next
-
-    def _chain(self, pool, steps, B, bw, f, x, y1, G, out, dead_site, front=None):
-        """Appends a bottleneck as a chain of launches: conv1 into y1 and the grouped conv, or both in one launch (f.c1g, no
-        y1); SE; the shortcut conv, unless conv3's launch computes it (f.sc_in_conv3); conv3.  G: the blended slice of the
-        block's site that conv1 splices in (None without a site), out: where the block writes instead of a pool buffer,
-        dead_site: the site's buffers.  front (f.conv3_in): the fused front's block, whose conv3 the first launch computes
-        from front.y2 / sc / gate -- there is no x; the shortcut reads the compact stride-2 map that launch writes.
-        Returns the output, the next site's compact slice and everything that dies here."""
-        blk, dt = bw.spec, self.act_dtype
-        N, es, s = B * self.pw.clip_len, _esz(dt), blk.stride
-        h, w, h2, w2 = f.h, f.w, f.h2, f.w2
-        M, M2 = N * h * w, N * h2 * w2
-        if y1 is not None:
-            splice = dict(A0=G, k0=f.Fp) if f.site else {}
-            steps.append(Step(blk.name + ".conv1", bw.w1.kern(M), lambda: bw.w1.run(
-                x, bw.s1, bw.h1, ops.ACT_RELU, out=y1, M=M, **splice), *gemm_cost(M, blk.cin, blk.cout, es)))
-        y2 = pool.take((N, h2, w2, blk.cout), dt)
-        parts = ops.gconv3x3_parts(h, w, blk.cout, s, dt) if bw.w2frag is not None else 1
-        pooled = pool.take((N, parts, blk.cout), torch.float32)
-        gate = pool.take((N, blk.cout), torch.float32)
-        if f.c1g and bw.c1g_w1f is None:
-            bw.c1g_w1f = pack_mfma_frags(bw.w1_raw, self.device, rows=16 * ops.c1_gconv_slab_tiles(h, w, blk.cout, s))
-        xs2 = None
-        if f.conv3_in:
-            pbw = front.bw
-            xs2 = pool.take((N, h2, w2, blk.cin), dt)
-            steps.append(Step(blk.name + ".conv1_conv2", "c1_gconv", lambda: ops.c1_gconv_c3in(
-                front.y2, front.sc, front.gate, pbw.w3.w, pbw.s3, pbw.h3, bw.c1g_w1f, bw.s1, bw.h1, bw.w2frag, bw.s2, bw.h2,
-                blk.gw, blk.cout, xs2=xs2, out=y2, pooled=pooled),
-                # the producer's y2 and shortcut map in, this block's y2 and the compact map out, the three weights
-                (2 * M * blk.cin + M2 * blk.cout + M2 * blk.cin) * es + (blk.cin * blk.cin + blk.cout * (blk.cin + blk.gw * 9)) * es,
-                2 * M * blk.cin * blk.cin + 2 * M * blk.cin * blk.cout + 2 * M2 * blk.cout * blk.gw * 9))
-            for t_ in (front.y2, front.sc, front.pooled, front.gate):       # the front block's temporaries die with that launch
-                pool.give(t_)
-            x = xs2
-        elif f.c1g:
-            steps.append(Step(blk.name + ".conv1_conv2", "c1_gconv", lambda: ops.c1_gconv(
-                x, bw.c1g_w1f, bw.s1, bw.h1, bw.w2frag, bw.s2, bw.h2, blk.gw, s, blk.cout, G=G, out=y2, pooled=pooled),
-                (M * blk.cin + M2 * blk.cout) * es + blk.cout * (blk.cin + blk.gw * 9) * es,
-                2 * M * blk.cin * blk.cout + 2 * M2 * blk.cout * blk.gw * 9))
-        else:
-            steps.append(Step(blk.name + ".conv2", "gconv3x3", lambda: ops.gconv3x3(
-                y1, bw.w2, bw.s2, bw.h2, blk.gw, s, wfrag=bw.w2frag, out=y2, pooled=pooled),
-                (M + M2) * blk.cout * es + blk.cout * blk.gw * 9 * 4, 2 * M2 * blk.cout * blk.gw * 9))
-        sc, shortcut, sc_from = x, [], None
-        gather = (s, h, w, h2, w2) if (s > 1 and xs2 is None) else None      # (the compact map holds the gathered rows)
-        if f.sc_in_conv3:
-            sc, sc_from = None, (x, gather)
-        elif blk.has_downsample:
-            sc = pool.take((N, h2, w2, blk.cout), dt)
-            shortcut = [Step(blk.name + ".downsample", bw.wd.kern(M2), lambda: bw.wd.run(
-                x, bw.sd, bw.hd, ops.ACT_NONE, gather=gather, out=sc, M=M2), *gemm_cost(M2, blk.cin, blk.cout, es))]
-        if out is None:
-            out = pool.take((N, h2, w2, blk.cout), dt)
-        xs_next = pool.take((N, h2, w2, f.slice_next), dt) if f.slice_next else None
-        se, conv3 = self._se_conv3(bw, N, h2, w2, y2, pooled, gate, sc, out, out2=xs_next, sc_from=sc_from)
-        steps += [se, *shortcut, conv3]                     # (the shortcut conv launches between the two)
-        # liveness: everything but `out` (and the next block's slice) dies here
-        return out, xs_next, (([y1] if y1 is not None else []) + [y2, pooled, gate] + dead_site + ([sc] if shortcut else [])
-                              + ([xs2] if xs2 is not None else []))
-
-    def _blocks(self, pool, steps, keep, taps, B, x, h, w, blocks, x_kept, out_last=None, front=None):
-        """Appends the launches of a run of bottlenecks for B clips (N = B*T frames) to `steps`, each in the form that
-        block_forms chose; x (N,h,w,Cin) is the input map (owned by `pool` unless x_kept).  out_last: where the last block
-        writes its output (a slice of a buffer shared with the plan that continues the trunk) instead of a pool buffer.
-        front: the run stands behind the fused front, whose block (front.bw) has left y2 / sc / pooled / gate and still
-        lacks SE + conv3: x does not exist yet.  They are appended here, conv3 as its own launch into a map x or, when the
-        first block takes it in (conv3_in), inside that block's first launch.  Returns (x, h, w, x_kept)."""
-        N, dt = B * self.pw.clip_len, self.act_dtype
-        xs = q = None       # the compact slice and the tap maps of the coming block's site, where the launch in front wrote them
-        forms = block_forms(blocks, h, w, dt, taps, out_last is not None, *(() if front is None else (front.bw,)))
-        if front is not None:
-            if forms and forms[0].conv3_in:
-                steps.append(self._se_conv3(front.bw, N, h, w, front.y2, front.pooled, front.gate, front.sc, None)[0])
-            else:
-                x = pool.take((N, h, w, front.bw.spec.cout), dt)
-                steps += self._se_conv3(front.bw, N, h, w, front.y2, front.pooled, front.gate, front.sc, x)
-                x_kept = self._block_done(pool, keep, taps, front.bw.spec, (front.y2, front.sc, front.pooled, front.gate), None,
-                                          True, x)
-                front = None
-        for bi, f in enumerate(forms):
-            bw, last = blocks[bi], bi + 1 == len(blocks)
-            # (conv1's map is taken in front of the site's buffers: the pool is best-fit, so the order of takes decides which
-            # buffer a tensor lands in)
-            y1 = None if (f.one_launch or f.c1g) else pool.take((N, f.h, f.w, bw.spec.cout), dt)
-            xg = xs if f.slice_in else x
-            gb = self._gs_site(pool, steps, keep, taps, B, bw, f, xg, q) if f.site else {}
-            dead = list(gb.values()) + ([xs] if f.slice_in else [])
-            if f.one_launch:
-                out, xs, q = self._one_launch(pool, steps, B, bw, f, x, xg, gb, None if last else blocks[bi + 1])
-            else:
-                out, xs, dead = self._chain(pool, steps, B, bw, f, x, y1, gb.get("out"), out_last if last else None, dead,
-                                            front if f.conv3_in else None)
-                q = None
-            x_kept = self._block_done(pool, keep, taps, bw.spec, dead, x, x_kept, out)
-            x, h, w = out, f.h2, f.w2
-        return x, h, w, x_kept
-
-    def _build_tail(self, B, feat, head_out, trunk_in=None, start=None):
-        """The launches behind the sub-batch join, over all B clips: optionally the rest of the trunk (blocks[start:] on the
-        map `trunk_in` = (x, h, w) that the sub-batch plans wrote) + avg-pool, then SGP encoder-decoder + heads."""
-        pool, steps, keep = _Pool(self.device), [], {}
+    def _tail(self, B, feat, head_out, trunk_in=None, k=None):
+        """The launches behind the sub-batch join, over all B clips: optionally the rest of the trunk (the blocks from k on, over
+        the map `trunk_in` = (x, h, w) that the sub-batch plans wrote) + avg-pool, then SGP encoder-decoder + heads."""
+        tb = self._builder(B)
         if trunk_in is not None:
-            x, h, w = trunk_in
-            x, h, w, _ = self._blocks(pool, steps, keep, set(), B, x, h, w, list(self.pw.W.blocks[start:]), True)
-            self._avgpool(steps, B, x, h, w, feat)
-        cur = self._sgp_heads(pool, steps, keep, set(), B, feat, head_out)
-        return SimpleNamespace(steps=steps, pool_bytes=pool.total_bytes(), sgp_out=cur)
-
-    def _build(self, B, H, W, flip, taps, head_out=None, feat_out=None, stop_at=None, trunk_out=None, feat_rs=None,
-               frames_dtype=torch.uint8):
-        """flip: bool (all frames) or a uint8 device tensor (B*T,) of per-frame flags (the augmented eval path)."""
-        pw, Wt = self.pw, self.pw.W
-        T = pw.clip_len
-        N = B * T
-        dt = self.act_dtype
-        dev = self.device
-        pool = _Pool(dev)
-        steps = []
-        keep = {}
-        crop = None
-        ch, cw = H, W
-        if self.crop_dim is not None and self.crop_dim > 0 and (self.crop_dim != H or self.crop_dim != W):
-            ch = cw = self.crop_dim
-            crop = (int(round((H - ch) / 2.0)), int(round((W - cw) / 2.0)), ch, cw)
-        frames = torch.empty((N, 3, H, W), dtype=frames_dtype, device=dev)
-        Ho, Wo = (ch + 1) // 2, (cw + 1) // 2
-        es = _esz(dt)
-        blocks = list(Wt.blocks)
-        fused_front = (Wt.front is not None and "_features.stem" not in taps and self.fuse_front
-                       and frames_dtype == torch.uint8 and not isinstance(flip, torch.Tensor)
-                       and ops.s1_front_parts(ch, cw, Wt.blocks[0].spec.cout) > 0)
-        if fused_front:
-            bw = blocks.pop(0)
-            blk = bw.spec
-            h2, w2 = (Ho + 1) // 2, (Wo + 1) // 2
-            parts = ops.s1_front_parts(ch, cw, blk.cout)
-            y2 = pool.take((N, h2, w2, blk.cout), dt)
-            sc = pool.take((N, h2, w2, blk.cout), dt)
-            pooled = pool.take((N, parts, blk.cout), torch.float32)
-            gate = pool.take((N, blk.cout), torch.float32)
-            M2 = N * h2 * w2
-            steps.append(Step("s1_front", "s1_front", lambda y2=y2, sc=sc, pooled=pooled: ops.s1_front(
-                frames, Wt.front, crop, flip, y2=y2, shortcut=sc, pooled=pooled),
-                              N * 3 * ch * cw + 2 * M2 * blk.cout * es,
-                              2 * N * Ho * Wo * 32 * (27 + 2 * blk.cout) // 1 + 2 * M2 * blk.cout * blk.gw * 9))
-            # the block's SE + conv3 follow in _blocks, where the form of the block behind decides how conv3 is launched
-            front = SimpleNamespace(bw=bw, y2=y2, sc=sc, pooled=pooled, gate=gate)
-            x, h, w, x_kept = None, h2, w2, True
-        else:
-            front = None
-            x = pool.take((N, Ho, Wo, 32), dt)
-            steps.append(Step("stem", "stem", lambda x=x: ops.stem(frames, Wt.stem_w, Wt.stem_scale, Wt.stem_shift, dt, crop,
-                                                                   flip, out=x),
-                              N * 3 * ch * cw + N * Ho * Wo * 32 * es, 2 * N * Ho * Wo * 32 * 27))
-            h, w = Ho, Wo
-            x_kept = "_features.stem" in taps
-            if x_kept:
-                keep["_features.stem"] = x
-        if stop_at is not None:
-            blocks = blocks[:max(0, stop_at - (1 if fused_front else 0))]
-        if trunk_out is not None and not blocks:
-            raise ValueError("join_at must leave at least one un-fused bottleneck in the sub-batch plans")
-        x, h, w, x_kept = self._blocks(pool, steps, keep, taps, B, x, h, w, blocks, x_kept, out_last=trunk_out, front=front)
-        if stop_at is not None:          # trunk head only: the rest of the trunk runs once for all sub-batches (plan.tail)
-            return SimpleNamespace(frames=frames, steps=steps, keep=keep, head_out=None, pool_bytes=pool.total_bytes(), B=B, T=T,
-                                   h=h, w=w)
-        feat = pool.take((B, T, pw.spec.feat_dim), sgp_stream_dtype(dt, dev)) if feat_out is None else feat_out
-        self._avgpool(steps, B, x, h, w, feat, feat_rs)
-        keep["feat"] = feat
-        if not x_kept:
-            pool.give(x)
-        if feat_out is not None:         # trunk only: the temporal stage runs once for all sub-batches (plan.tail)
-            return SimpleNamespace(frames=frames, steps=steps, keep=keep, head_out=None, pool_bytes=pool.total_bytes(), B=B, T=T)
-
-        if head_out is None:
-            head_out = torch.empty((N, pw.n_out), dtype=torch.float32, device=dev)
-        keep["sgp_out"] = self._sgp_heads(pool, steps, keep, taps, B, feat, head_out)
-        return SimpleNamespace(frames=frames, steps=steps, keep=keep, head_out=head_out,
-                               pool_bytes=pool.total_bytes(), B=B, T=T)
-
-    def _map_geometry(self, k, H, W):
-        """(h, w, channels) of the map that block k reads, for H x W frames (centre crop included)."""
-        ch = self.crop_dim if (self.crop_dim and self.crop_dim > 0) else H
-        cw = self.crop_dim if (self.crop_dim and self.crop_dim > 0) else W
-        hh, ww = (ch + 1) // 2, (cw + 1) // 2
-        for b_ in self.pw.W.blocks[:k]:
-            hh, ww = (hh - 1) // b_.spec.stride + 1, (ww - 1) // b_.spec.stride + 1
-        return hh, ww, self.pw.W.blocks[k - 1].spec.cout
+            x, h, w, _ = tb._blocks(*trunk_in, list(self.pw.W.blocks[k:]), True)
+            # (x_kept: the trunk's last map is not given back, so the temporal stage takes no buffer of the trunk's size)
+            tb.avgpool(x, h, w, True, feat)
+        tb.sgp_heads(feat, head_out)
+        return tb.sub_plan()
 
     def plan(self, B, H, W, flip=False, taps=(), slot=0):
         """Launch plan for a batch geometry.  With n_split > 1 (and no taps) the batch is cut into n_split
@@ -970,45 +1018,42 @@ class ForwardEngine:
         key = (B, H, W, bool(flip), tuple(sorted(taps)), slot)
         if key in self._plans:
             return self._plans[key]
+        flip, T, dev = bool(flip), self.pw.clip_len, self.device
         ns = self.n_split if (not taps and self.n_split > 1 and B % self.n_split == 0 and B >= self.n_split) else 1
         if ns == 1:
-            sub = self._build(B, H, W, bool(flip), set(taps))
-            plan = SimpleNamespace(subs=[sub], streams=[None], head_out=sub.head_out, keep=sub.keep, graph=None, tail=None,
-                                   steps=sub.steps, pool_bytes=sub.pool_bytes, B=B, T=sub.T)
+            sub = self._whole(B, H, W, flip, taps, self.crop_dim)
+            plan = Plan([sub], sub.head_out, B, T)
         else:
             Bs = B // ns
-            T = self.pw.clip_len
-            head_out = torch.empty((B * T, self.pw.n_out), dtype=torch.float32, device=self.device)
+            rows = [slice(i * Bs * T, (i + 1) * Bs * T) for i in range(ns)]          # the frames of sub-batch i
+            head_out = torch.empty((B * T, self.pw.n_out), dtype=torch.float32, device=dev)
             tail = trunk_map = None
-            if self.merge_tail:
-                feat = torch.empty((B, T, self.pw.spec.feat_dim), dtype=sgp_stream_dtype(self.act_dtype, self.device),
-                                   device=self.device)
+            if not self.merge_tail:
+                subs = [self._whole(Bs, H, W, flip, (), self.crop_dim, head_out=head_out[r]) for r in rows]
+            else:
+                feat = torch.empty((B, T, self.pw.spec.feat_dim), dtype=sgp_stream_dtype(self.act_dtype, dev), device=dev)
                 k = self.join_at
                 if k is not None and 0 < k < len(self.pw.W.blocks):
                     # the sub-batches split only the bandwidth-bound head of the trunk (blocks [0, k)); the latency-bound
                     # small maps behind it run once for the whole batch, like the temporal stage
-                    hh, ww, cc = self._map_geometry(k, H, W)
-                    shared = trunk_map = torch.empty((B * T, hh, ww, cc), dtype=self.act_dtype, device=self.device)
-                    subs = [self._build(Bs, H, W, bool(flip), set(), stop_at=k,
-                                        trunk_out=shared[i * Bs * T:(i + 1) * Bs * T]) for i in range(ns)]
-                    tail = self._build_tail(B, feat, head_out, trunk_in=(shared, hh, ww), start=k)
+                    hh, ww, cc = self._geometry(H, W).maps[k]
+                    trunk_map = torch.empty((B * T, hh, ww, cc), dtype=self.act_dtype, device=dev)
+                    subs = [self._head(Bs, H, W, flip, k, trunk_map[r]) for r in rows]
+                    tail = self._tail(B, feat, head_out, trunk_in=(trunk_map, hh, ww), k=k)
                 else:
-                    frs = torch.empty((B * T, 2), dtype=torch.float32, device=self.device)
+                    frs = torch.empty((B * T, 2), dtype=torch.float32, device=dev)
                     feat._td_rowstat = frs
-                    subs = [self._build(Bs, H, W, bool(flip), set(), feat_out=feat[i * Bs:(i + 1) * Bs],
-                                        feat_rs=frs[i * Bs * T:(i + 1) * Bs * T]) for i in range(ns)]
-                    tail = self._build_tail(B, feat, head_out)
-            else:
-                subs = [self._build(Bs, H, W, bool(flip), set(), head_out=head_out[i * Bs * T:(i + 1) * Bs * T])
-                        for i in range(ns)]
+                    subs = []
+                    for i, r in enumerate(rows):          # trunk and pooling into the sub-batch's rows of the shared features
+                        tb = self._builder(Bs)
+                        tb.avgpool(*tb.trunk(H, W, self.crop_dim, flip), feat[i * Bs:(i + 1) * Bs], frs[r])
+                        subs.append(tb.sub_plan())
+                    tail = self._tail(B, feat, head_out)
             forks = []
             for _ in range(ns - 1):
-                forks.append(new_stream(self.device, avoid=forks))
-            plan = SimpleNamespace(subs=subs, streams=[None] + forks,
-                                   head_out=head_out, keep=subs[0].keep, graph=None, tail=tail,
-                                   steps=[st for sb in subs for st in sb.steps] + (tail.steps if tail else []),
-                                   pool_bytes=sum(sb.pool_bytes for sb in subs) + (tail.pool_bytes if tail else 0), B=B, T=T,
-                                   trunk_map=trunk_map)       # (the block-join_at input of all B clips, None without a trunk join)
+                forks.append(new_stream(dev, avoid=forks))
+            # (trunk_map: the block-join_at input of all B clips, None without a trunk join)
+            plan = Plan(subs, head_out, B, T, streams=[None] + forks, tail=tail, trunk_map=trunk_map)
         self._plans[key] = plan
         return plan
 
@@ -1021,14 +1066,11 @@ class ForwardEngine:
 
     # ------------------------------------------------------------------ execution
     def _launch_all(self, plan, main):
-        """Issue every sub-batch's launches: sub-batch 0 on `main`, the others forked onto their own streams."""
-        if len(plan.subs) == 1:
-            for s_ in plan.subs[0].steps:
-                s_.fn()
-            return
-        fork = torch.cuda.Event()
-        fork.record(main)
+        """Issue every sub-batch's launches: sub-batch 0 on `main`, the others forked onto their own streams; then the tail's."""
         joins = []
+        if len(plan.subs) > 1:
+            fork = torch.cuda.Event()
+            fork.record(main)
         for sb, st in zip(plan.subs, plan.streams):
             if st is None or st.cuda_stream == main.cuda_stream:   # (the pool handed the launching stream out again)
                 for s_ in sb.steps:
@@ -1141,7 +1183,7 @@ class ForwardEngine:
 
     def frame_map_shape(self, H, W):
         """(h, w, C) of one frame's row of the resident map: the input of block first_site_block()."""
-        return self._map_geometry(self._reuse_k(), H, W)
+        return self._geometry(H, W).maps[self._reuse_k()]
 
     def frame_plan(self, Bf, H, W, flip=False):
         """Plan of the per-frame head of the trunk -- stem and blocks [0, k), k = first_site_block() -- for Bf * clip_len
@@ -1152,11 +1194,9 @@ class ForwardEngine:
         if key in self._plans:
             return self._plans[key]
         k, T = self._reuse_k(), self.pw.clip_len
-        hh, ww, cc = self._map_geometry(k, H, W)
+        hh, ww, cc = self._geometry(H, W).maps[k]
         out = torch.empty((Bf * T, hh, ww, cc), dtype=self.act_dtype, device=self.device)
-        sub = self._build(Bf, H, W, bool(flip), set(), stop_at=k, trunk_out=out)
-        plan = SimpleNamespace(subs=[sub], streams=[None], head_out=None, keep=sub.keep, graph=None, tail=None, steps=sub.steps,
-                               pool_bytes=sub.pool_bytes, B=Bf, T=T, out=out, h=hh, w=ww)
+        plan = Plan([self._head(Bf, H, W, bool(flip), k, out)], None, Bf, T, out=out, h=hh, w=ww)
         self._plans[key] = plan
         return plan
 
@@ -1168,13 +1208,11 @@ class ForwardEngine:
         if key in self._plans:
             return self._plans[key]
         k, T = self._reuse_k(), self.pw.clip_len
-        cc = self.pw.W.blocks[k - 1].spec.cout
+        cc = self._geometry(h, w).maps[k][2]          # (the channels do not depend on the frame size)
         buf = torch.empty((B * T, h, w, cc), dtype=self.act_dtype, device=self.device)
         head_out = torch.empty((B * T, self.pw.n_out), dtype=torch.float32, device=self.device)
         feat = torch.empty((B, T, self.pw.spec.feat_dim), dtype=sgp_stream_dtype(self.act_dtype, self.device), device=self.device)
-        tail = self._build_tail(B, feat, head_out, trunk_in=(buf, h, w), start=k)
-        plan = SimpleNamespace(subs=[tail], streams=[None], head_out=head_out, keep={}, graph=None, tail=None, steps=tail.steps,
-                               pool_bytes=tail.pool_bytes, B=B, T=T, trunk_in=buf)
+        plan = Plan([], head_out, B, T, tail=self._tail(B, feat, head_out, trunk_in=(buf, h, w), k=k), trunk_in=buf)
         self._plans[key] = plan
         return plan
 
@@ -1232,20 +1270,15 @@ class ForwardEngine:
         key = ("aug", B, H, W, frames.dtype, flip_frames is not None)
         plan = self._plans.get(key)
         if plan is None:
-            fbuf = torch.zeros((B * T,), dtype=torch.uint8, device=self.device) if flip_frames is not None else False
-            crop_dim, self.crop_dim = self.crop_dim, None           # the caller's window: no centre crop on top of it
-            try:
-                sub = self._build(B, H, W, fbuf, set(), frames_dtype=frames.dtype)
-            finally:
-                self.crop_dim = crop_dim
-            plan = SimpleNamespace(sub=sub, flip_buf=fbuf if flip_frames is not None else None, graph=None)
-            self._plans[key] = plan
-        plan.sub.frames.copy_(frames.reshape(B * T, Cc, H, W), non_blocking=True)
+            fbuf = torch.zeros((B * T,), dtype=torch.uint8, device=self.device) if flip_frames is not None else None
+            # (crop=None: the caller's window, no centre crop on top of it)
+            sub = self._whole(B, H, W, False if fbuf is None else fbuf, crop=None, frames_dtype=frames.dtype)
+            plan = self._plans[key] = Plan([sub], sub.head_out, B, T, flip_buf=fbuf)
+        plan.subs[0].frames.copy_(frames.reshape(B * T, Cc, H, W), non_blocking=True)
         if flip_frames is not None:
             plan.flip_buf.copy_(flip_frames.to(torch.uint8), non_blocking=True)
-        for s_ in plan.sub.steps:
-            s_.fn()
-        return plan.sub.head_out, plan
+        self._launch_all(plan, torch.cuda.current_stream())
+        return plan.head_out, plan
 
     def __del__(self):
         # graph executables are not destroyed from a finaliser (it may run at any allocation, e.g. inside another engine's

@@ -109,7 +109,7 @@ def plans(E, synth, state_layout, show_forms=False):
         show("flip + taps", dt, lambda: eng.plan(2, 224, 224, flip=True, taps=("_features.s3.b2", "_temp_fine._sgp.1")))
         show("stem tap", dt, lambda: eng.plan(2, 224, 224, taps=("_features.stem",)))
         flips = torch.zeros((2 * 16,), dtype=torch.uint8, device="meta")
-        show("per-frame flips, fp32 frames 200x200", dt, lambda: eng._build(2, 200, 200, flips, set(), frames_dtype=torch.float32))
+        show("per-frame flips, fp32 frames 200x200", dt, lambda: eng._whole(2, 200, 200, flips, frames_dtype=torch.float32))
     # whole videos with the per-frame stages once per frame: the frame plan (blocks [0, k)) and the tail plan (blocks [k:] on)
     for (arch, n, T, B), dt in itertools.product([("rny002_gsf", 2, 100, 8), ("rny008_gsf", 3, 100, 8)], DTYPES):
         eng = engine(arch, n, T, dt)
