@@ -124,3 +124,25 @@ def chained_scheduler(opt, warm_steps, cos_steps):
     from torch.optim.lr_scheduler import ChainedScheduler, LinearLR, CosineAnnealingLR
     return ChainedScheduler([LinearLR(opt, start_factor=0.01, end_factor=1.0, total_iters=warm_steps),
                              CosineAnnealingLR(opt, cos_steps)])
+
+
+# ----------------------------------------------------------------------------- guarded output buffers of the GPU tests
+GUARD = 4096                           # elements in front of and behind each output buffer
+
+
+class Guarded:
+    """an output buffer of `shape` in the middle of a NaN-filled allocation: a store outside the output lands in a guard,
+    an element the kernel does not write stays NaN (and fails the finiteness check of roundoff.assert_within)"""
+
+    def __init__(self, shape, dtype=torch.bfloat16, device="cuda"):
+        n = int(np.prod(shape))
+        self.flat = torch.full((n + 2 * GUARD,), float("nan"), dtype=dtype, device=device)
+        self.view = self.flat[GUARD:GUARD + n].view(*shape)
+
+    def check(self, name=""):
+        torch.cuda.synchronize()
+        n = self.view.numel()
+        assert bool(torch.isnan(self.flat[:GUARD]).all()), f"{name}: store in front of the output"
+        assert bool(torch.isnan(self.flat[GUARD + n:]).all()), f"{name}: store behind the output"
+        assert bool(torch.isfinite(self.view).all()), f"{name}: non-finite or unwritten output elements"
+        return self.view

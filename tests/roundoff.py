@@ -18,6 +18,35 @@ Every term is derived, none is fitted to a kernel's output:
                          2^-21, a bf16-grade defect is 2^-8, three orders of magnitude apart, so anything from 4 to 64
                          separates them (torch's own fp32 gelu on the CPU uses 0.3 of the term: test_roundoff_host.py).
 
+The SGP stage (sgp_fused.hip, sgp_tile.h, sgp_gemm.hip, sgp.hip) adds, with u = 2^-24:
+
+  product                d(ab) = |a| d_b + |b| d_a + d_a d_b + u |ab|
+  sum of n values        d = sum d_i + n 2^-23 sum |v_i|                 (the fp32 summation bound n u, doubled as above)
+  depthwise conv over T  zero padding, K taps in one fp32 fma chain: the contraction rule with K = number of taps
+  mean over T            d = mean d + (T + 4) 2^-23 mean |x|
+  linear up-sampling     align_corners=True: l0 x[i0] + l1 x[i1] is a two-term contraction; the position scale * t is an fp32
+                         product of an fp32 quotient, off by at most T_hi 2^-23, which moves the value by that times the
+                         steepest of the segment's and its two neighbours' slopes (the position may cross a node)
+  max-pool               d = max of d over the window (exact on exact inputs)
+  LayerNorm / GroupNorm  one pass in fp32: s = sum x, q = sum x^2 over n values carry the doubled summation bound,
+                         m = s / n (+ u |m|), var = max(q/n - m^2, 0) with d_var = d_q/n + 2 |m| d_m + d_m^2 + 3 u (q/n + m^2)
+                         (the cancellation term: three roundings of magnitude q/n, m^2 and their difference),
+                         rstd = 1 / sqrt(var + eps) with d_rstd / rstd = d_var / (2 (var + eps)) + 2 u, then through
+                         (x - m) rstd w + b; the rounding term 4 2^-23 (rstd |w| (|x| + |m|) + |b|) is that of the table form
+                         fmaf(x, rstd w, fmaf(-m, rstd w, b)) of sgp_gemm.hip, which the direct forms stay inside
+  handed statistics      (mean, rstd) pairs, chsum parts and rowstat partial sums are exact operands, in fp64: only the
+                         arithmetic behind them carries error -- the ordered sum of the parts (doubled summation bound over
+                         the number of parts), q/n - m^2, the rsqrt
+  GELU of sgp_gemm.hip   Abramowitz-Stegun 7.1.26 with rcpf and exp2f: |err| <= 1.5e-7 on erf is 0.75e-7 |x| on the output; rcpf
+                         and exp2f are good to 2^-23 relative, rcpf's error reaches erf through t poly'(t) / poly(t) <= 3.5, the
+                         five fmas of the Horner form add 5 u of partial sums <= 1.5: together below 1.3e-6 on erf, 6.5e-7 |x| on
+                         the output, inside the existing transcendental term 16 u (|x| + |f(x)|) >= 9.5e-7 |x|
+                         (test_roundoff_sgp_host.py measures it, with both intrinsics pushed one ulp either way)
+
+The first-order rule for rstd FAILS as var -> 0 (d_var / (var + eps) is no longer small, and with q/n >> var the cancellation
+term alone exceeds var): the bound is stated for rows and groups with var >= E[x^2] / 32, which `first_order` returns and the
+tests assert on every reference.
+
 CPU torch / numpy in fp64 only; no GPU, no kernel."""
 from collections import namedtuple
 
@@ -186,6 +215,252 @@ def normalised_f32(frames_u8, crop=None, flip=False):
     return RB((u / 255.0 - mean) / std, 4 * U_F32 * (u / 255.0 + mean) / std)
 
 
+# ----------------------------------------------------------------------------- the SGP stage: element-wise pieces
+def product(a, b):
+    ab = a.ref * b.ref
+    return RB(ab, a.ref.abs() * b.d + b.ref.abs() * a.d + a.d * b.d + U_F32 * ab.abs())
+
+
+def total(*vs):
+    """fp32 sum of the values, in any order"""
+    ref, d, mag = sum(v.ref for v in vs), sum(v.d for v in vs), sum(v.ref.abs() for v in vs)
+    return RB(ref, d + len(vs) * 2.0 ** -23 * mag)
+
+
+def scale_shift(v, w, b):
+    """fmaf(w, v, b) per channel (last dim): the contraction rule with K = 1"""
+    w, b = f64(w), f64(b)
+    return RB(w * v.ref + b, w.abs() * v.d + 5 * 2.0 ** -23 * ((w * v.ref).abs() + b.abs()))
+
+
+def dwconv(x, w, b):
+    """depthwise temporal convolution of x (B, T, C) with w (C, K), bias b (C): zero padding, K taps, one fp32 fma chain"""
+    w, b = f64(w), f64(b)
+    C, K = w.shape
+    cv = lambda a, k: F.conv1d(a.transpose(1, 2), k.unsqueeze(1), padding=K // 2, groups=C).transpose(1, 2)   # noqa: E731
+    mag = cv(x.ref.abs(), w.abs()) + b.abs()
+    return RB(cv(x.ref, w) + b, cv(x.d, w.abs()) + (K + 4) * 2.0 ** -23 * mag)
+
+
+def mean_T(x):
+    T = x.ref.shape[1]
+    return RB(x.ref.mean(1), x.d.mean(1) + (T + 4) * 2.0 ** -23 * x.ref.abs().mean(1))
+
+
+def upsample_linear(x, T_hi):
+    """nn.Upsample(T_hi, 'linear', align_corners=True) of x (B, T_lo, C), as modules.py:236"""
+    B, T_lo, C = x.ref.shape
+    if T_hi == T_lo:
+        return x
+    pos = torch.arange(T_hi, dtype=torch.float64) * ((T_lo - 1) / (T_hi - 1) if T_hi > 1 else 0.0)
+    i0 = pos.floor().long().clamp(max=T_lo - 1)
+    i1 = (i0 + 1).clamp(max=T_lo - 1)
+    l1 = (pos - i0).view(1, -1, 1)
+    l0 = 1.0 - l1
+    ref = l0 * x.ref[:, i0] + l1 * x.ref[:, i1]
+    slope = torch.zeros(B, T_lo + 1, C, dtype=torch.float64)            # slope[j] = |x[j] - x[j-1]|, 0 outside
+    if T_lo > 1:
+        slope[:, 1:T_lo] = (x.ref[:, 1:] - x.ref[:, :-1]).abs()
+    steep = torch.maximum(torch.maximum(slope[:, i0], slope[:, i1]), slope[:, (i0 + 2).clamp(max=T_lo)])
+    dnode = torch.maximum(torch.maximum(x.d[:, i0], x.d[:, i1]), x.d[:, (i0 - 1).clamp(min=0)])
+    dpos = T_hi * 2.0 ** -23
+    d = (l0 * x.d[:, i0] + l1 * x.d[:, i1] + dpos * (steep + dnode)
+         + 6 * 2.0 ** -23 * (l0 * x.ref[:, i0].abs() + l1 * x.ref[:, i1].abs()))
+    return RB(ref, d)
+
+
+def pool_windows(T_in, T_out):
+    return [((i * T_in) // T_out, -((-(i + 1) * T_in) // T_out)) for i in range(T_out)]
+
+
+def maxpool(x, T_out):
+    """AdaptiveMaxPool1d(T_out) along T of (B, T, C)"""
+    win = pool_windows(x.ref.shape[1], T_out)
+    return RB(torch.stack([x.ref[:, lo:hi].amax(1) for lo, hi in win], 1), torch.stack([x.d[:, lo:hi].amax(1) for lo, hi in win], 1))
+
+
+# ----------------------------------------------------------------------------- the SGP stage: normalisation
+Stats = namedtuple("Stats", "m d_m rstd d_rstd var ex2")     # per row / group; ex2 = E[x^2] (None for a handed (mean, rstd))
+
+
+def sums_of(x, dims):
+    """(s, d_s, q, d_q, n) of x.ref over dims, summed in fp32 in one pass"""
+    n = int(np.prod([x.ref.shape[i] for i in dims]))
+    a = x.ref.abs()
+    q = (x.ref * x.ref).sum(dims)
+    return (x.ref.sum(dims), x.d.sum(dims) + n * 2.0 ** -23 * a.sum(dims),
+            q, (2 * a * x.d + x.d * x.d).sum(dims) + n * 2.0 ** -23 * q, n)
+
+
+def handed_sums(parts, dims):
+    """parts (..., 2) = (sum, sum of squares) partials, exact operands; summed over dims in fp32, in order"""
+    p = f64(parts)
+    nterms = int(np.prod([p.shape[i] for i in dims]))
+    s, q = p[..., 0].sum(dims), p[..., 1].sum(dims)
+    return s, nterms * 2.0 ** -23 * p[..., 0].abs().sum(dims), q, nterms * 2.0 ** -23 * p[..., 1].abs().sum(dims)
+
+
+def moments(s, d_s, q, d_q, n, eps):
+    m = s / n
+    d_m = d_s / n + U_F32 * m.abs()
+    ex2 = q / n
+    var = (ex2 - m * m).clamp_min(0.0)
+    d_var = d_q / n + 2 * m.abs() * d_m + d_m * d_m + 3 * U_F32 * (ex2 + m * m)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    return Stats(m, d_m, rstd, rstd * (d_var / (2 * (var + eps)) + 2 * U_F32), var, ex2)
+
+
+def handed_mean_rstd(rowstat):
+    """(mean, rstd) pairs (rows, 2) handed to the kernel: exact operands"""
+    r = f64(rowstat)
+    z = torch.zeros_like(r[..., 0])
+    return Stats(r[..., 0], z, r[..., 1], z, None, None)
+
+
+def first_order(st):
+    """smallest var / E[x^2] over the rows / groups: the bound is stated for >= 1 / 32"""
+    return float((st.var / st.ex2.clamp_min(1e-300)).min())
+
+
+def normalise(x, m, d_m, rstd, d_rstd, w, b):
+    """(x - m) rstd w + b; the statistics already broadcast to x, w and b along the last dim"""
+    w, b = f64(w), f64(b)
+    xm = x.ref - m
+    dxm = x.d + d_m
+    d = w.abs() * (rstd * dxm + xm.abs() * d_rstd + dxm * d_rstd)
+    return RB(xm * rstd * w + b, d + 4 * 2.0 ** -23 * (rstd * w.abs() * (x.ref.abs() + m.abs()) + b.abs()))
+
+
+def layernorm_stats(x, eps, rowstat=None):
+    """rowstat: None (computed from the row), (rows, 2) handed (mean, rstd), (parts, rows, 2) handed partial sums"""
+    C = x.ref.shape[-1]
+    if rowstat is None:
+        s, d_s, q, d_q, n = sums_of(x, (-1,))
+        return moments(s, d_s, q, d_q, n, eps)
+    if rowstat.dim() == 2:
+        st = handed_mean_rstd(rowstat)
+        return Stats(*[None if v is None else v.view(x.ref.shape[:-1]) for v in st])
+    s, d_s, q, d_q = handed_sums(rowstat, (0,))
+    shp = x.ref.shape[:-1]
+    return moments(s.view(shp), d_s.view(shp), q.view(shp), d_q.view(shp), C, eps)
+
+
+def layernorm(x, w, b, eps=1e-5, rowstat=None):
+    """channel LayerNorm over the last dim of x (B, T, C) (modules.py:320-363: biased variance, eps inside the sqrt)"""
+    st = layernorm_stats(x, eps, rowstat)
+    u = lambda v: v.unsqueeze(-1)                                       # noqa: E731
+    return normalise(x, u(st.m), u(st.d_m), u(st.rstd), u(st.d_rstd), w, b), st
+
+
+def groupnorm_stats(x, G, eps, chsum=None):
+    """chsum: None or handed (parts, B, C, 2) / (B, C, 2) per-channel (sum, sum of squares) over the clip's rows"""
+    B, T, C = x.ref.shape
+    cg = C // G
+    if chsum is None:
+        xg = RB(x.ref.view(B, T, G, cg), x.d.view(B, T, G, cg))
+        s, d_s, q, d_q, n = sums_of(xg, (1, 3))
+        return moments(s, d_s, q, d_q, n, eps)
+    p = f64(chsum)
+    p = p.unsqueeze(0) if p.dim() == 3 else p
+    s, d_s, q, d_q = handed_sums(p.view(p.shape[0], B, G, cg, 2), (0, 3))
+    return moments(s, d_s, q, d_q, T * cg, eps)
+
+
+def groupnorm(x, G, w, b, eps=1e-5, chsum=None):
+    """GroupNorm(G) of x (B, T, C) over (C / G) x T"""
+    st = groupnorm_stats(x, G, eps, chsum)
+    cg = x.ref.shape[-1] // G
+    u = lambda v: v.repeat_interleave(cg, dim=1).unsqueeze(1)            # noqa: E731  (B, G) -> (B, 1, C)
+    return normalise(x, u(st.m), u(st.d_m), u(st.rstd), u(st.d_rstd), w, b), st
+
+
+def round_bf16(v):
+    """an INTERMEDIATE bf16 rounding of a value known to d << one bf16 ulp (an fp32 value in front of a bf16 operand or a
+    bf16 LDS tile).  store_bf16 would carry 2^-8 |v| through every term of the contraction or convolution behind it, a
+    worst-case sum a defect in one term hides under.  Rounding is monotone, so the kernel's value lies between the roundings
+    of ref - d and ref + d: the reference is the rounding of ref itself and d what those two can differ from it -- zero unless
+    a rounding boundary lies within d of ref.  (The interval is widened by 2^-23 for the cast's own path through fp32.)"""
+    r = lambda a: a.float().to(BF).double()                                           # noqa: E731
+    w = v.d + 2.0 ** -23 * v.ref.abs()
+    mid, lo, hi = r(v.ref), r(v.ref - w), r(v.ref + w)
+    return RB(mid, torch.maximum((hi - mid).abs(), (lo - mid).abs()))
+
+
+def as_stored(v, dtype):
+    """the fp32 value v written out as `dtype`: one bf16 rounding, or none (the fp32 store keeps the value)"""
+    return store_bf16(v) if dtype == BF else v
+
+
+def as_stream(v, dtype):
+    """a value kept in the residual stream's type inside a kernel: a rounding point for bf16, none for fp32"""
+    return round_bf16(v) if dtype == BF else v
+
+
+# ----------------------------------------------------------------------------- the SGP stage: its five launches
+def dw_split(dw, db, ks, up):
+    """dw (C, 2 ks + up + 2) = [psi | convw | convkw | fc | global_fc], db (5, C) as engine._dwpack lays them out"""
+    return dict(psi=(dw[:, :ks], db[0]), cw=(dw[:, ks:2 * ks], db[1]), ckw=(dw[:, 2 * ks:2 * ks + up], db[2]),
+                fc=(dw[:, 2 * ks + up], db[3]), g=(dw[:, 2 * ks + up + 1], db[4]))
+
+
+def branches(o, dw, db, ks, up):
+    """(conv_gate, inst, phi) of sgp_tile.h on the normalised sequence o (B, T, C): (convw + convkw) psi, fc phi"""
+    p = dw_split(dw, db, ks, up)
+    gate = product(total(dwconv(o, *p["cw"]), dwconv(o, *p["ckw"])), dwconv(o, *p["psi"]))
+    phi = relu(scale_shift(mean_T(o), *p["g"]))
+    inst = product(scale_shift(o, *p["fc"]), RB(phi.ref.unsqueeze(1), phi.d.unsqueeze(1)))
+    return gate, inst, phi
+
+
+def sgp_front_ref(x, ks, up, ln_w, ln_b, dw, db, eps=1e-5, rowstat=None):
+    """sgp_front_kernel: y = x + ((fc phi + (convw + convkw) psi) + LN(x)) in fp32, LN(x) NOT rounded in either stream type.
+    -> (y in fp32 before the store, dict of the parts)"""
+    xe = exact(x)
+    o, st = layernorm(xe, ln_w, ln_b, eps, rowstat)
+    gate, inst, phi = branches(o, dw, db, ks, up)
+    return total(xe, o, inst, gate), dict(ln=o, gate=gate, inst=inst, phi=phi, stats=st)
+
+
+def mixer_front_ref(z, xlo, ks, up, ln1_w, ln1_b, ln2_w, ln2_b, dw1, db1, dw2, db2, eps=1e-5, rowstat_z=None, rowstat_x=None):
+    """mixer_front_kernel: zn = LN1(z) and xn = LN2(x_lo) rounded to the stream's type, xu = up(xn) rounded to it again, the
+    branches on zn and xu; cat = [out1 | out2 | out3 | out4 | zn | xu] before its store.  -> (cat, parts)"""
+    T_hi, sdt = z.shape[1], z.dtype
+    zn, stz = layernorm(exact(z), ln1_w, ln1_b, eps, rowstat_z)
+    xn, stx = layernorm(exact(xlo), ln2_w, ln2_b, eps, rowstat_x)
+    zn, xn = as_stream(zn, sdt), as_stream(xn, sdt)
+    xu = as_stream(upsample_linear(xn, T_hi), sdt)
+    g1, i1, p1 = branches(zn, dw1, db1, ks, up)
+    g2, i2, p2 = branches(xu, dw2, db2, ks, up)
+    slabs = [g1, g2, i1, i2, zn, xu]
+    cat = RB(torch.cat([s.ref for s in slabs], -1), torch.cat([s.d for s in slabs], -1))
+    return cat, dict(slabs=slabs, phi=(p1, p2), stats=(stz, stx))
+
+
+def rows(v):
+    return reshape(v, -1, v.ref.shape[-1])
+
+
+def gn_fc1_ref(y, chsum, gn_w, gn_b, W, bias, G=16, eps=1e-5):
+    """MODE 0 of sgp_gemm.hip: the GroupNorm table from the handed channel sums, the normalised operand rounded to bf16 (the B
+    operand of the MFMA), fp32 accumulation, + bias, GELU, one bf16 store.  -> (H (B, T, N), Stats)"""
+    B, T, K = y.shape
+    a, st = groupnorm(exact(y), G, gn_w, gn_b, eps, chsum)
+    h = store_bf16(gelu(linear(rows(round_bf16(a)), W, None, bias)))
+    return reshape(h, B, T, -1), st
+
+
+def fc2_ref(H, W, bias, resid):
+    """MODE 1 before its store: resid + H W^T + b in fp32 (B, T, N)"""
+    B, T, K = H.shape
+    return reshape(linear(rows(exact(H)), W, None, bias, rows(exact(resid))), B, T, -1)
+
+
+def cat_fc_ref(A, W, bias):
+    """MODE 2 before its store: GELU(A W^T + b) in fp32 (B, T, N)"""
+    B, T, K = A.shape
+    return reshape(gelu(linear(rows(exact(A)), W, None, bias)), B, T, -1)
+
+
 # ----------------------------------------------------------------------------- checks
 def _index(flat, shape, nhwc):
     idx = np.unravel_index(int(flat), tuple(shape))
@@ -247,6 +522,26 @@ def assert_pooled_consistent(pooled, y, name=""):
     print(f"[roundoff] {name}: squeeze sums worst err/tol {float(ratio.reshape(-1)[worst]):.3f}, {nviol} of {got.numel()} outside")
     assert nviol == 0, (f"{name}: {nviol} of {got.numel()} squeeze sums are not the sums of the stored outputs, worst err/tol "
                         f"{float(ratio.reshape(-1)[worst]):.3f} at (frame, channel) {_index(worst, got.shape, False)}")
+
+
+def assert_sums_consistent(got, v, dims, name=""):
+    """handed statistics are those of the STORED values: got (..., 2) = (sum, sum of squares), already summed over its parts,
+    against the fp64 sums over `dims` of the tensor v the kernel itself stored, within the doubled fp32 summation bound
+    n 2^-23 sum|v| and the same form for v^2"""
+    vv, g = f64(v), f64(got)
+    n = int(np.prod([vv.shape[i] for i in dims]))
+    assert bool(torch.isfinite(g).all()), f"{name}: non-finite statistics"
+    worst = 0.0
+    for k, (want, mag) in enumerate(((vv.sum(dims), vv.abs().sum(dims)), ((vv * vv).sum(dims), (vv * vv).sum(dims)))):
+        gk = g[..., k].reshape(want.shape)
+        err, tol = (gk - want).abs(), n * 2.0 ** -23 * mag
+        ratio = torch.where(err == 0, torch.zeros_like(err), err / tol.clamp_min(1e-300))
+        nviol = int((err > tol).sum())
+        worst = max(worst, float(ratio.max()))
+        print(f"[roundoff] {name}: {('sums', 'sums of squares')[k]} worst err/tol {float(ratio.max()):.3f}, {nviol} of {err.numel()} outside")
+        assert nviol == 0, (f"{name}: {nviol} of {err.numel()} {('sums', 'sums of squares')[k]} are not those of the stored "
+                            f"values, worst err/tol {float(ratio.max()):.3f}")
+    return worst
 
 
 def old_metric(out, ref):

@@ -9,13 +9,12 @@ import pytest
 import torch
 
 import roundoff as R
-from helpers import act, t
+from helpers import Guarded, act, t
 from tdeed_amd import synth
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 BF = torch.bfloat16
-GUARD = 4096                           # elements in front of and behind each output buffer
 
 
 @pytest.fixture(scope="module")
@@ -27,24 +26,6 @@ def ops():
 
 def rnd(seed, name, shape, scale=1.0):
     return t(act(seed, name, shape, scale))
-
-
-class Guarded:
-    """an output buffer of `shape` in the middle of a NaN-filled allocation: a store outside the output lands in a guard,
-    an element the kernel does not write stays NaN (and fails the finiteness check of assert_within)"""
-
-    def __init__(self, shape, dtype=BF):
-        n = int(np.prod(shape))
-        self.flat = torch.full((n + 2 * GUARD,), float("nan"), dtype=dtype, device=DEV)
-        self.view = self.flat[GUARD:GUARD + n].view(*shape)
-
-    def check(self, name=""):
-        torch.cuda.synchronize()
-        n = self.view.numel()
-        assert bool(torch.isnan(self.flat[:GUARD]).all()), f"{name}: store in front of the output"
-        assert bool(torch.isnan(self.flat[GUARD + n:]).all()), f"{name}: store behind the output"
-        assert bool(torch.isfinite(self.view).all()), f"{name}: non-finite or unwritten output elements"
-        return self.view
 
 
 def enough_for_bias(ref):
