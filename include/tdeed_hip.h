@@ -196,6 +196,17 @@ int tdeed_c1_gconv_slab_tiles(int Hi, int Wi, int C, int stride);
 int tdeed_c1_gconv_fwd(const void* x, const void* G, int Fp, int N, int Hi, int Wi, int Cin, int C, int gw, int stride,
                        const void* w1f, const float* s1, const float* h1, const void* wfrag, const float* scale,
                        const float* shift, void* y, float* pooled, void* stream);
+/* tdeed_c1_gconv_fwd has two forms with the same bits: one workgroup per (frame, band, channel slab), and the slab loop --
+ * one workgroup per (frame, band) that keeps its x / G fragments in registers and walks the slabs.
+ * tdeed_c1_gconv_slab_loop_fits: the slab loop exists for the shape (stride 2, several slabs, Cin in 33..64 or 129..160, a
+ * wave's share of the band's pixel tiles fits its registers); which fitting shapes take it is routed per instance from
+ * measurements.  tdeed_c1_gconv_set_form (tests, tools): -1 as routed (default), 0 per slab everywhere, 1 the slab loop
+ * wherever it fits.  tdeed_c1_gconv_workgroups: the grid of tdeed_c1_gconv_fwd for N frames under the form in force (0: not
+ * served).  In the slab loop the time stamps are: 1 prologue (halo, fold, everything requested), 2 slab 0's conv1, 3 barrier,
+ * 4 slab 0's grouped conv, 5 the other slabs, 6 = 5. */
+int tdeed_c1_gconv_set_form(int form);
+int tdeed_c1_gconv_slab_loop_fits(int Hi, int Wi, int Cin, int C, int stride);
+int tdeed_c1_gconv_workgroups(int N, int Hi, int Wi, int Cin, int C, int stride);
 
 /* tdeed_c1_gconv_fwd of a stride-2 block whose input is not in memory: the launch also computes the producer's conv3 (Cp <=
  * 32 channels in and out: one k-step) per pixel tile in front of conv1, from its operand y2p, its shortcut map scp (both

@@ -67,6 +67,9 @@ _SIGS = {
     "tdeed_c1_gconv_slab_tiles": ([c_int, c_int, c_int, c_int], c_int),
     "tdeed_c1_gconv_fwd": ([P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P,
                             P], c_int),
+    "tdeed_c1_gconv_set_form": ([c_int], c_int),
+    "tdeed_c1_gconv_slab_loop_fits": ([c_int, c_int, c_int, c_int, c_int], c_int),
+    "tdeed_c1_gconv_workgroups": ([c_int, c_int, c_int, c_int, c_int, c_int], c_int),
     "tdeed_c1_gconv_c3in_fits": ([c_int, c_int, c_int, c_int], c_int),
     "tdeed_c1_gconv_c3in_fwd": ([P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P,
                                  P], c_int),

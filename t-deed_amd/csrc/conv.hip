@@ -618,6 +618,24 @@ __global__ __launch_bounds__(256) void gconv3x3_mfma_kernel(const bf16_t* __rest
 // 8q .. 8q+7 of one pixel, which IS conv1's B fragment: two MFMAs and the epilogue per tile, no LDS and no re-layout, the
 // bits of the two launches.  The producer's output map is neither written nor read; the pixels at even rows and columns,
 // all that the block's shortcut conv reads of it, go to the compact map xs2 ([N][Ho][Wo][Cin]).
+// zero the halo columns of every band row and the rows that fall outside the map (c1_gconv_mfma_kernel: the interior is
+// written by conv1)
+__device__ __forceinline__ void c1g_zero_halo(unsigned char* tile, int nrow_used, int Hi, int Wi, int PS, int iy0) {
+  const int tid = threadIdx.x, WP = Wi + 2;
+  const int cpp = PS >> 4;
+  for (int i = tid; i < nrow_used * 2 * cpp; i += 256) {
+    const int j = i % cpp, rc = i / cpp;
+    const int rr = rc >> 1, col = (rc & 1) ? (Wi + 1) : 0;
+    *reinterpret_cast<u32x4*>(tile + ((long)rr * WP + col) * PS + j * 16) = (u32x4){0u, 0u, 0u, 0u};
+  }
+  for (int rr = 0; rr < nrow_used; ++rr) {
+    const int r = iy0 + rr;
+    if (r >= 0 && r < Hi) continue;
+    for (int i = tid; i < WP * cpp; i += 256)
+      *reinterpret_cast<u32x4*>(tile + (long)rr * WP * PS + (long)i * 16) = (u32x4){0u, 0u, 0u, 0u};
+  }
+  // the 16 pad bytes behind the channels of every interior pixel are never read (k-slot offsets stay below CSP * 2)
+}
 struct C3In {
   const bf16_t* y2p; const bf16_t* scp; const float* gate;
   const bf16x8* w3f; const float* s3; const float* h3;
@@ -677,22 +695,7 @@ __global__ __launch_bounds__(256, (KS1 == 4 || C3IN) ? 3 : 1) void c1_gconv_mfma
       b1[t][e] = ok ? bv[e] : 0.f;
     }
   }
-  // ---- zero the halo columns of every band row and the rows that fall outside the map
-  {
-    const int cpp = PS >> 4;
-    for (int i = tid; i < nrow_used * 2 * cpp; i += 256) {
-      const int j = i % cpp, rc = i / cpp;
-      const int rr = rc >> 1, col = (rc & 1) ? (Wi + 1) : 0;
-      *reinterpret_cast<u32x4*>(tile + ((long)rr * WP + col) * PS + j * 16) = (u32x4){0u, 0u, 0u, 0u};
-    }
-    for (int rr = 0; rr < nrow_used; ++rr) {
-      const int r = iy0 + rr;
-      if (r >= 0 && r < Hi) continue;
-      for (int i = tid; i < WP * cpp; i += 256)
-        *reinterpret_cast<u32x4*>(tile + (long)rr * WP * PS + (long)i * 16) = (u32x4){0u, 0u, 0u, 0u};
-    }
-    // the 16 pad bytes behind the channels of every interior pixel are never read (k-slot offsets stay below CSP * 2)
-  }
+  c1g_zero_halo(tile, nrow_used, Hi, Wi, PS, iy0);
   GC_STAMP(1);
   // ---- conv1 over the band's pixels (rows inside the map), 16 pixels per MFMA tile, tiles dealt over the four waves
   {
@@ -900,6 +903,155 @@ __global__ __launch_bounds__(256, (KS1 == 4 || C3IN) ? 3 : 1) void c1_gconv_mfma
                          slab, oy0, nrows_out, GcStat{nullptr, nullptr, nullptr, nullptr}, dbg);
 }
 
+// The slab loop: c1_gconv_mfma_kernel for the multi-slab stride-2 blocks (STRIDE 2, KS1 2 or 5) in which a workgroup owns a (frame, band) and walks the channel slabs
+// itself instead of one workgroup per (frame, band, slab).  The halo, the pixel coordinates and the x / G fragments of the
+// wave's tiles do not depend on the slab: the halo is zeroed once, the fragments are requested once and stay in registers
+// (C1G_SLAB_TILES tiles per wave), conv1's fold of every slab sits in LDS, and per slab only conv1's weights and the grouped
+// conv's weights change -- conv1 runs in two halves of two channel tiles; the next slab's first half of w1f is requested
+// behind this slab's first half (it travels under the second half and the grouped conv, in the registers conv1 has finished
+// with), its second half and the grouped conv's weights behind the grouped conv (under the barrier and the first half), all
+// unconditionally with a clamped slab index.  Same MFMA k order, rounding points, tile-to-wave dealing and squeeze-sum order
+// per slab as the per-slab form: the same bits.
+#define C1G_SLAB_TILES(KS1v) ((KS1v) <= 2 ? 5 : 4)
+#define C1G_SLAB_MAXC 512
+template <int STRIDE, int KS1>
+__global__ __launch_bounds__(256, KS1 == 2 ? 3 : 2) void c1_gconv_slab_loop_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ G, int Fp,
+                                                            int Hi, int Wi, int Cin, int C, const bf16x8* __restrict__ w1f,
+                                                            const float* __restrict__ s1, const float* __restrict__ h1,
+                                                            const bf16x8* __restrict__ wfrag, const float* __restrict__ scale,
+                                                            const float* __restrict__ shift, bf16_t* __restrict__ y,
+                                                            float* __restrict__ pooled, int Ho, int Wo, int band, int nbands,
+                                                            int CSP, int PS, int rows_in, int relu, long long* dbg) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char tile[];
+  __shared__ float red[4][32];
+  __shared__ float redq[4][32];
+  GC_STAMP(0);
+  const long lid = xcd_logical_id(blockIdx.x, gridDim.x);
+  const int nslabs_ = (C + CSP - 1) >> 6;                  // (several slabs: CSP is 64)
+  int bnd, n;
+  td_split(lid, nbands, n, bnd);
+  const int oy0 = bnd * band;
+  const int nrows_out = min(band, Ho - oy0);
+  const int WP = Wi + 2;
+  const int iy0 = oy0 * STRIDE - 1;
+  const int nrow_used = (nrows_out - 1) * STRIDE + 3;
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int pl = lane & 15, q = lane >> 4;
+  static_assert(STRIDE == 2 && (KS1 == 2 || KS1 == 5), "the slab loop exists for the stride-2 multi-slab blocks");
+  constexpr int NT = C1G_SLAB_TILES(KS1);                // pixel tiles per wave (host: c1g_slab_loop_fits)
+  // several slabs: CSP is 64.  As a constant it folds the unit-count branch around gconv_load_w's requests, behind which
+  // hipcc waited for every load in flight (x included) in front of the halo
+  constexpr int SCSP = 64;
+  const int r_lo = max(iy0, 0), r_hi = min(iy0 + nrow_used, Hi);
+  const int npx = (r_hi - r_lo) * Wi;
+  const int ntl = (npx + 15) >> 4;
+  const IDiv dwi(Wi);
+  const bf16_t* xn = x + (long)n * Hi * Wi * Cin;
+  const bf16_t* gn = G ? G + (long)n * Hi * Wi * Fp : nullptr;
+  // conv1's BatchNorm fold of every slab goes to LDS once (requested first: it is written behind the halo, in front of the
+  // one barrier of the prologue, while the fragments below still travel)
+  __shared__ __attribute__((aligned(16))) float fold[2][C1G_SLAB_MAXC];
+  float fa[C1G_SLAB_MAXC / 256], fb[C1G_SLAB_MAXC / 256];
+#pragma unroll
+  for (int j = 0; j < C1G_SLAB_MAXC / 256; ++j) {
+    const int c = min(tid + 256 * j, C - 1);
+    fa[j] = s1[c];
+    fb[j] = h1[c];
+  }
+  // ---- the x / G fragments of all of this wave's tiles: one request, resident across the slabs (tiles beyond the band are
+  // clamped repeats nobody uses)
+  u32x4 xv[NT][KS1];
+  int dsto[NT];
+  bool poks[NT];
+#pragma unroll
+  for (int g = 0; g < NT; ++g) {
+    const int t0 = wv + 4 * g;
+    const int p = t0 * 16 + pl;
+    poks[g] = t0 < ntl && p < npx;
+    int rr, cc;
+    dwi.divmod(poks[g] ? p : 0, rr, cc);
+    const long pix = (long)(r_lo + rr) * Wi + cc;
+    dsto[g] = ((r_lo + rr - iy0) * WP + cc + 1) * PS + 8 * q;
+#pragma unroll
+    for (int ks = 0; ks < KS1; ++ks) {
+      const int k = 32 * ks + 8 * q;
+      const bool ok = poks[g] && k < Cin;
+      const bf16_t* src = (gn && k < Fp) ? gn + pix * Fp + k : xn + pix * Cin + k;
+      xv[g][ks] = *reinterpret_cast<const u32x4*>(ok ? src : xn);
+    }
+  }
+  // conv1's weights of a slab in two halves (tiles 0, 1 and 2, 3 of its four 16-channel tiles), then the grouped conv's
+  // weights of slab 0
+  bf16x8 w1r[4][KS1];
+  auto load_w1 = [&](int sl, int tlo) {
+#pragma unroll
+    for (int t = tlo; t < tlo + 2; ++t)
+#pragma unroll
+      for (int ks = 0; ks < KS1; ++ks) w1r[t][ks] = w1f[((long)(sl * 4 + t) * KS1 + ks) * 64 + lane];
+  };
+  load_w1(0, 0);
+  load_w1(0, 2);
+  GcW gw_ = gconv_load_w(wfrag, 0, SCSP);
+  c1g_zero_halo(tile, nrow_used, Hi, Wi, PS, iy0);
+#pragma unroll
+  for (int j = 0; j < C1G_SLAB_MAXC / 256; ++j) {
+    const int c = tid + 256 * j;
+    fold[0][c] = c < C ? fa[j] : 0.f;                       // channels beyond C: exact zeros
+    fold[1][c] = c < C ? fb[j] : 0.f;
+  }
+  __syncthreads();
+  GC_STAMP(1);
+  // the zeroing selects of the fragments (pixels beyond the band, k beyond Cin) wait for them: behind the barrier, so that
+  // the halo and the fold are written while the fragments travel
+  bf16x8 xf[NT][KS1];
+#pragma unroll
+  for (int g = 0; g < NT; ++g)
+#pragma unroll
+    for (int ks = 0; ks < KS1; ++ks) {
+      const u32x4 z = {0u, 0u, 0u, 0u};
+      const u32x4 w = (poks[g] && 32 * ks + 8 * q < Cin) ? xv[g][ks] : z;
+      xf[g][ks] = *reinterpret_cast<const bf16x8*>(&w);
+    }
+  // conv1 of two channel tiles of slab sl over this wave's pixel tiles: BN + ReLU + rounding into the band
+  auto conv1_pair = [&](int sl, int tlo) {
+#pragma unroll
+    for (int t = tlo; t < tlo + 2; ++t) {
+      const f32x4 av = *reinterpret_cast<const f32x4*>(&fold[0][sl * 64 + t * 16 + 4 * q]);
+      const f32x4 bv = *reinterpret_cast<const f32x4*>(&fold[1][sl * 64 + t * 16 + 4 * q]);
+#pragma unroll
+      for (int g = 0; g < NT; ++g) {
+        if (wv + 4 * g >= ntl) break;                       // (wave-uniform)
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KS1; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1r[t][ks], xf[g][ks], acc, 0, 0, 0);
+        if (poks[g]) {
+          bf16x4 o;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] = (bf16_t)fmaxf(acc[e] * av[e] + bv[e], 0.f);
+          *reinterpret_cast<bf16x4*>(tile + dsto[g] + t * 32) = o;
+        }
+      }
+    }
+  };
+  for (int s = 0; s < nslabs_; ++s) {
+    const int sn = min(s + 1, nslabs_ - 1);                 // (clamped: behind a branch hipcc waits for every load in flight)
+    conv1_pair(s, 0);
+    load_w1(sn, 0);                                         // travels under tiles 2, 3 and the grouped conv
+    conv1_pair(s, 2);
+    if (s == 0) GC_STAMP(2);
+    __syncthreads();
+    if (s == 0) GC_STAMP(3);
+    gconv_band_mma<STRIDE>(gw_, tile, red, redq, Wi, C, wfrag, scale, shift, y, pooled, nullptr, Ho, Wo, nbands, SCSP, PS, relu, n,
+                           bnd, s, oy0, nrows_out);
+    if (s == 0) GC_STAMP(4);
+    load_w1(sn, 2);                                         // travel under the barrier and the next slab's tiles 0, 1
+    gw_ = gconv_load_w(wfrag, sn, SCSP);
+    __syncthreads();                                        // the next slab's conv1 overwrites the band
+  }
+  GC_STAMP(5);
+  GC_STAMP(6);
+}
+
 static long long* g_c1g_dbg = nullptr;
 extern "C" int tdeed_c1_gconv_set_debug(void* buf) { g_c1g_dbg = (long long*)buf; return TDEED_OK; }
 
@@ -989,6 +1141,41 @@ extern "C" int tdeed_c1_gconv_slab_tiles(int Hi, int Wi, int C, int stride) {   
   const GcGeom g = gc_geom(Hi, Wi, C, stride);
   return g.nslabs * (g.CSP >> 4);
 }
+// The slab loop (c1_gconv_slab_loop_kernel): one workgroup per (frame, band) walks the channel slabs.  tdeed_c1_gconv_slab_loop_fits: the
+// form exists for this shape -- stride 2, several slabs, Cin of 2 or 5 k-steps, and a wave's share of the band's pixel tiles
+// fits the registers that keep the x fragments.  Which of the shapes that fit take it is decided per instance from
+// measurements (c1g_slab_loop_wins); tdeed_c1_gconv_set_form overrides that for tests and tools: -1 as
+// routed, 0 the per-slab form everywhere, 1 the slab loop wherever it fits.  tdeed_c1_gconv_workgroups: the grid that
+// tdeed_c1_gconv_fwd launches for N frames of this shape under the form in force.
+static int g_c1g_form = -1;
+extern "C" int tdeed_c1_gconv_set_form(int form) {
+  TD_CHECK(form >= -1 && form <= 1, "c1_gconv_set_form: %d (-1 routed, 0 per slab, 1 slab loop)", form);
+  g_c1g_form = form;
+  return TDEED_OK;
+}
+extern "C" int tdeed_c1_gconv_slab_loop_fits(int Hi, int Wi, int Cin, int C, int stride) {
+  if (stride != 2 || !tdeed_c1_gconv_fits(Hi, Wi, Cin, C, stride)) return 0;
+  const int ks1 = (Cin + 31) / 32;
+  if (ks1 != 2 && ks1 != 5) return 0;
+  const GcGeom g = gc_geom(Hi, Wi, C, stride);
+  if (g.nslabs < 2 || g.nslabs * g.CSP > C1G_SLAB_MAXC) return 0;
+  const int rows = g.rows_in < Hi ? g.rows_in : Hi;                  // band rows inside the map, at most
+  const int tiles = (rows * Wi + 15) / 16;
+  return (tiles + 3) / 4 <= C1G_SLAB_TILES(ks1) ? 1 : 0;
+}
+// measured: alone the slab loop is 19 % faster at two k-steps (s3.b1 of RegNetY-200MF, s2.b1 of 800MF) and a
+// tie at five (s4.b1 of 200MF: 800 workgroups at two per CU are 1.6 rounds of a 31 us workgroup); with three batches in flight
+// both are gains (fewer workgroup-microseconds per CU), so every instance that fits takes it
+static bool c1g_slab_loop_wins(int ks1) { return ks1 == 2 || ks1 == 5; }
+static bool c1g_slab_loop(int Hi, int Wi, int Cin, int C, int stride) {
+  if (g_c1g_form == 0 || !tdeed_c1_gconv_slab_loop_fits(Hi, Wi, Cin, C, stride)) return false;
+  return g_c1g_form == 1 || c1g_slab_loop_wins((Cin + 31) / 32);
+}
+extern "C" int tdeed_c1_gconv_workgroups(int N, int Hi, int Wi, int Cin, int C, int stride) {
+  if (N <= 0 || !tdeed_c1_gconv_fits(Hi, Wi, Cin, C, stride)) return 0;
+  const GcGeom g = gc_geom(Hi, Wi, C, stride);
+  return N * g.nbands * (c1g_slab_loop(Hi, Wi, Cin, C, stride) ? 1 : g.nslabs);
+}
 extern "C" int tdeed_c1_gconv_fwd(const void* x, const void* G, int Fp, int N, int Hi, int Wi, int Cin, int C, int gw,
                                   int stride, const void* w1f, const float* s1, const float* h1, const void* wfrag,
                                   const float* scale, const float* shift, void* y, float* pooled, void* stream) {
@@ -1000,11 +1187,12 @@ extern "C" int tdeed_c1_gconv_fwd(const void* x, const void* G, int Fp, int N, i
   TD_CHECK(!G || (Fp % 8 == 0 && Fp > 0 && Fp <= Cin), "c1_gconv: bad splice width %d", Fp);
   const GcGeom g = gc_geom(Hi, Wi, C, stride);
   const int Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1;
-  dim3 grid((unsigned)((long)g.nbands * g.nslabs * N));
+  const bool slabs = c1g_slab_loop(Hi, Wi, Cin, C, stride);
+  dim3 grid((unsigned)((long)g.nbands * (slabs ? 1 : g.nslabs) * N));
   const size_t smem = (size_t)g.rows_in * (Wi + 2) * g.PS;
   hipStream_t st = (hipStream_t)stream;
   const int KS1 = (Cin + 31) / 32;
-#define TD_C1G(Sv, Kv)                                                                                                     \
+#define TD_C1G(Sv, Kv)                                                                                                       \
   hipLaunchKernelGGL((c1_gconv_mfma_kernel<Sv, Kv>), grid, dim3(256), smem, st, (const bf16_t*)x, (const bf16_t*)G,           \
                      G ? Fp : 0, Hi, Wi, Cin, C, (const bf16x8*)w1f, s1, h1, (const bf16x8*)wfrag, scale, shift, (bf16_t*)y,  \
                      pooled, Ho, Wo, g.band, g.nbands, g.CSP, g.PS, g.rows_in, 1, g_c1g_dbg, C3In{})
@@ -1013,7 +1201,14 @@ extern "C" int tdeed_c1_gconv_fwd(const void* x, const void* G, int Fp, int N, i
     if (KS1 == 1) TD_C1G(Sv, 1); else if (KS1 == 2) TD_C1G(Sv, 2); else if (KS1 == 4) TD_C1G(Sv, 4);                      \
     else TD_C1G(Sv, 5);                                                                                                    \
   } while (0)
-  if (stride == 2) TD_C1G_K(2); else TD_C1G_K(1);
+  if (slabs) {
+#define TD_C1G_SL(Kv)                                                                                                       \
+  hipLaunchKernelGGL((c1_gconv_slab_loop_kernel<2, Kv>), grid, dim3(256), smem, st, (const bf16_t*)x, (const bf16_t*)G,        \
+                     G ? Fp : 0, Hi, Wi, Cin, C, (const bf16x8*)w1f, s1, h1, (const bf16x8*)wfrag, scale, shift, (bf16_t*)y,  \
+                     pooled, Ho, Wo, g.band, g.nbands, g.CSP, g.PS, g.rows_in, 1, g_c1g_dbg)
+    if (KS1 == 2) TD_C1G_SL(2); else TD_C1G_SL(5);
+#undef TD_C1G_SL
+  } else if (stride == 2) TD_C1G_K(2); else TD_C1G_K(1);
 #undef TD_C1G_K
 #undef TD_C1G
   TD_LAUNCH_CHECK("c1_gconv");

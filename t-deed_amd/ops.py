@@ -139,6 +139,24 @@ def c1_gconv_fits(Hi, Wi, Cin, C, stride):
     return _lib.load().tdeed_c1_gconv_fits(Hi, Wi, Cin, C, stride) != 0
 
 
+def c1_gconv_slab_loop_fits(Hi, Wi, Cin, C, stride):
+    """True when the slab-loop form of c1_gconv (one workgroup per (frame, band) walks the channel slabs) exists for the shape."""
+    lib = _lib.load()
+    if not hasattr(lib, "tdeed_c1_gconv_slab_loop_fits"):    # an A/B flavour of the library built from an older revision
+        return False
+    return lib.tdeed_c1_gconv_slab_loop_fits(Hi, Wi, Cin, C, stride) != 0
+
+
+def c1_gconv_set_form(form):
+    """-1: c1_gconv's form as routed per instance (default); 0: per slab everywhere; 1: the slab loop wherever it fits."""
+    call("tdeed_c1_gconv_set_form", form)
+
+
+def c1_gconv_workgroups(N, Hi, Wi, Cin, C, stride):
+    """the grid c1_gconv launches for N frames of this shape under the form in force"""
+    return _lib.load().tdeed_c1_gconv_workgroups(N, Hi, Wi, Cin, C, stride)
+
+
 def c1_gconv_slab_tiles(Hi, Wi, C, stride):
     return _lib.load().tdeed_c1_gconv_slab_tiles(Hi, Wi, C, stride)
 

@@ -1,6 +1,7 @@
 """GPU tool: conv1 + grouped 3x3 in one launch (tdeed_c1_gconv_fwd) alone at the shapes of the shipped models, with its phase
-time stamps (tdeed_c1_gconv_set_debug); then the form that also computes the producer's conv3 (tdeed_c1_gconv_c3in_fwd) against the
-two launches it replaces, at 800 x 56 x 56 x 24 -> 56, with the stamps of both.
+time stamps (tdeed_c1_gconv_set_debug), in both forms (per slab / slab loop) where both exist; then the form that also
+computes the producer's conv3 (tdeed_c1_gconv_c3in_fwd) against the two launches it replaces, at 800 x 56 x 56 x 24 -> 56,
+with the stamps of both.
     python tools/bench_c1_gconv.py"""
 import os
 import sys
@@ -49,23 +50,35 @@ for name, N, Hi, Cin, C, gw, stride in SHAPES:
     def run():
         ops.c1_gconv(x, w1f, s1, h1, w2f, s2, h2, gw, stride, C, out=out, pooled=pooled)
 
-    us = timeit(run)
-    nslabs = rows // 16 // max(1, (min(C, 64) + 15) // 16) if C >= 64 else 1
-    nwg = N * parts * ((C + 63) // 64)
-    dbg = torch.zeros((nwg + 64, 8), dtype=torch.int64, device=DEV)
-    _lib.call("tdeed_c1_gconv_set_debug", dbg.data_ptr())
-    run()
-    torch.cuda.synchronize()
-    _lib.call("tdeed_c1_gconv_set_debug", None)
-    d = dbg.cpu().numpy().astype(np.float64)[:nwg] * 10.0 / 1e3          # us
-    ok = d[:, 6] > 0
-    d = d[ok]
+    # both forms where the slab loop exists for the shape (tdeed_c1_gconv_set_form): one workgroup per (frame, band, slab),
+    # and one per (frame, band) that walks the slabs -- whose stamps are prologue, slab 0's conv1, barrier, slab 0's grouped
+    # conv, the other slabs
     byt = (x.numel() + out.numel()) * 2
-    names = ["weights + halo", "conv1 tiles (wave 0)", "barrier", "grouped conv setup", "grouped conv tiles + stores", "squeeze sums"]
-    ph = [np.median(d[:, i + 1] - d[:, i]) for i in range(6)]
-    print(f"{name} N={N} {Hi}x{Hi} {Cin}->{C} stride {stride}: {us:7.1f} us per launch, {byt / us / 1e3:6.0f} GB/s algorithmic, {nwg} workgroups "
-          f"({int(ok.sum())} stamped); first start -> last end {(d[:, 6].max() - d[:, 0].min()):.1f} us; workgroup median "
-          f"{np.median(d[:, 6] - d[:, 0]):.2f} us: " + ", ".join(f"{n_} {v:.2f}" for n_, v in zip(names, ph)), flush=True)
+    forms = (0, 1) if ops.c1_gconv_slab_loop_fits(Hi, Hi, Cin, C, stride) else (0,)
+    outs = {}
+    for form in forms:
+        ops.c1_gconv_set_form(form)
+        us = timeit(run)
+        nwg = ops.c1_gconv_workgroups(N, Hi, Hi, Cin, C, stride)
+        dbg = torch.zeros((nwg + 64, 8), dtype=torch.int64, device=DEV)
+        _lib.call("tdeed_c1_gconv_set_debug", dbg.data_ptr())
+        run()
+        torch.cuda.synchronize()
+        _lib.call("tdeed_c1_gconv_set_debug", None)
+        outs[form] = (out.clone(), pooled.clone())
+        d = dbg.cpu().numpy().astype(np.float64)[:nwg] * 10.0 / 1e3          # us
+        ok = d[:, 6] > 0
+        d = d[ok]
+        names = (["prologue (halo, fold, requests)", "slab 0 conv1 (wave 0)", "barrier", "slab 0 grouped conv", "other slabs", "-"] if form
+                 else ["weights + halo", "conv1 tiles (wave 0)", "barrier", "grouped conv setup", "grouped conv tiles + stores", "squeeze sums"])
+        ph = [np.median(d[:, i + 1] - d[:, i]) for i in range(6)]
+        print(f"{name} N={N} {Hi}x{Hi} {Cin}->{C} stride {stride}, {'slab loop' if form else 'per slab '}: {us:7.1f} us per launch, "
+              f"{byt / us / 1e3:6.0f} GB/s algorithmic, {nwg} workgroups ({int(ok.sum())} stamped); first start -> last end "
+              f"{(d[:, 6].max() - d[:, 0].min()):.1f} us; workgroup median {np.median(d[:, 6] - d[:, 0]):.2f} us: "
+              + ", ".join(f"{n_} {v:.2f}" for n_, v in zip(names, ph)), flush=True)
+    ops.c1_gconv_set_form(-1)
+    if len(outs) == 2:
+        print(f"  forms identical: {torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])}", flush=True)
 
 
 # ---- the producer's conv3 in front of conv1 (engine.S1_CONV3_IN_C1G): s1.b1.conv3 + s2.b1.conv1_conv2 of RegNetY-200MF
