@@ -220,6 +220,16 @@ int tdeed_c1_gconv_c3in_fwd(const void* y2p, const void* scp, const float* gate,
                             const float* h3, void* xs2, int N, int Hi, int Wi, int Cp, int C, int gw, const void* w1f,
                             const float* s1, const float* h1, const void* wfrag, const float* scale, const float* shift,
                             void* y, float* pooled, void* stream);
+/* tdeed_c1_gconv_c3in_fwd has two forms with the same bits: one workgroup per (frame, band), and the band walk -- one
+ * workgroup per (frame, run of `walk` consecutive bands) that runs the prologue once per run, copies the input row two
+ * adjacent bands share inside LDS instead of computing it twice, and requests the next band's operands under the grouped conv.
+ * tdeed_c1_gconv_c3in_walk: the routed run length for the shape (1: the per-band form; a function of the shape alone, never of
+ * N; 0: not served).  tdeed_c1_gconv_c3in_set_walk (tests, tools): 0 as routed (default), 1 the per-band form, k >= 2 runs of
+ * k bands (clamped to the frame's band count); a negative value is an error.  tdeed_c1_gconv_c3in_workgroups: the grid of
+ * tdeed_c1_gconv_c3in_fwd for N frames under the form in force (0: not served). */
+int tdeed_c1_gconv_c3in_set_walk(int walk);
+int tdeed_c1_gconv_c3in_walk(int Hi, int Wi, int Cp, int C);
+int tdeed_c1_gconv_c3in_workgroups(int N, int Hi, int Wi, int Cp, int C);
 
 /* A whole stride-1 RegNetY bottleneck with identity shortcut on a small map in ONE launch (timm Bottleneck.forward:
  * conv1 -> conv2 -> se -> conv3 + shortcut -> ReLU, with the gate-shift splice of shift.py:89-93 on conv1's operand;

@@ -73,6 +73,9 @@ _SIGS = {
     "tdeed_c1_gconv_c3in_fits": ([c_int, c_int, c_int, c_int], c_int),
     "tdeed_c1_gconv_c3in_fwd": ([P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P,
                                  P], c_int),
+    "tdeed_c1_gconv_c3in_set_walk": ([c_int], c_int),
+    "tdeed_c1_gconv_c3in_walk": ([c_int, c_int, c_int, c_int], c_int),
+    "tdeed_c1_gconv_c3in_workgroups": ([c_int, c_int, c_int, c_int, c_int], c_int),
     "tdeed_bneck_fits": ([c_int, c_int, c_int, c_int], c_int),
     "tdeed_bneck_set_debug": ([P], c_int),
     "tdeed_bneck_fwd": ([P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, c_int, P, P, P, P, P, c_int,

@@ -1052,6 +1052,244 @@ __global__ __launch_bounds__(256, KS1 == 2 ? 3 : 2) void c1_gconv_slab_loop_kern
   GC_STAMP(6);
 }
 
+// The band walk: c1_gconv_mfma_kernel<2, 1, true> in which a workgroup owns a frame and a RUN of `walk` consecutive bands
+// instead of one band.  What a band's workgroup repeats per band happens once per run: conv1's fragments, conv3's fragment
+// pair, the folds of all three layers and the frame's gate row (all in LDS, read back per band: kept in registers across the
+// grouped conv they spill), and the halo columns (conv1 only writes the interior, so they stay zero for the run).  The grouped
+// conv's weights are requested again per band (resident: 160 bytes of scratch).  Adjacent bands share one input row:
+// the last row of band b is the first of band b + 1, so behind band b's grouped conv that row is COPIED inside LDS (row
+// nrow_used - 1 -> row 0) and conv3 + conv1 run on the band * 2 new rows only -- per frame the rows that exist, not 25 % more.
+// The y2p / scp chunks of the next band's first tile group are requested in front of the grouped conv, unconditionally (band
+// index clamped at the run's end: the last request is a repeat nobody uses), and consumed behind it.  Per pixel the
+// expressions of c1_gconv_mfma_kernel<2, 1, true> in its order; MFMA columns are independent, so which pixels share a tile
+// changes no bit; the grouped conv is gconv_band_mma per band with that band's index: the same y rows and pooled partial rows.
+// The compact map keeps its ownership rule (row 2 oy belongs to the band that owns output row oy); the shared row is odd.
+// Time stamps: 0 start, 1 prologue end, 2 first band's conv1 end, 3 first band's grouped conv end, 4 / 5 the same of the
+// second band (a steady-state band is 5 - 3), 6 run end.
+#define C3W_NPF 4
+template <int CSP>
+__global__ __launch_bounds__(256, 3) void c1_gconv_c3in_walk_kernel(int Hi, int Wi, int Cin, int C, const bf16x8* __restrict__ w1f,
+                                                            const float* __restrict__ s1, const float* __restrict__ h1,
+                                                            const bf16x8* __restrict__ wfrag, const float* __restrict__ scale,
+                                                            const float* __restrict__ shift, bf16_t* __restrict__ y,
+                                                            float* __restrict__ pooled, int Ho, int Wo, int band, int nbands,
+                                                            int walk, long long* dbg, const C3In c3) {
+  // the slab width as a constant: it folds the pixel stride and the unit-count branch of gconv_band_mma / gconv_load_w, whose
+  // unused form otherwise leaves its per-lane invariants in registers across the band loop
+  constexpr int PS = CSP * 2 + 16;
+  extern __shared__ __attribute__((aligned(16))) unsigned char tile[];
+  __shared__ float red[4][32];
+  __shared__ float redq[4][32];
+  __shared__ __attribute__((aligned(16))) float f1[2][64];          // conv1's fold (channels beyond C: exact zeros)
+  __shared__ __attribute__((aligned(16))) float f2[2][64];          // the grouped conv's fold
+  __shared__ __attribute__((aligned(16))) float f3[3][32];          // the frame's gate row, conv3's fold
+  __shared__ __attribute__((aligned(16))) bf16x8 wl[6][64];         // conv1's fragments (4 channel tiles), conv3's pair
+  GC_STAMP(0);
+  const long lid = xcd_logical_id(blockIdx.x, gridDim.x);
+  const int nruns = (nbands + walk - 1) / walk;
+  int n, run;
+  td_split(lid, nruns, n, run);
+  const int b0 = run * walk, b1 = min(b0 + walk, nbands);
+  const int WP = Wi + 2;
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int pl = lane & 15, q = lane >> 4;
+  const int nts = CSP >> 4;
+  const int k8 = 8 * q;
+  const bool kok = k8 < Cin;                                        // (Cin is a multiple of 8: a chunk is inside or outside)
+  const int kc = min(k8, Cin - 8);
+  const bf16_t* yn = c3.y2p + (long)n * Hi * Wi * Cin;
+  const bf16_t* rn = c3.scp + (long)n * Hi * Wi * Cin;
+  bf16_t* xsn = c3.xs2 ? c3.xs2 + (long)n * Ho * Wo * Cin : nullptr;
+  const IDiv dwi(Wi);
+  // a band of the run: its output rows, its rows in LDS (row rr holds input row iy0 + rr) and the input rows [r_lo, r_hi) that
+  // conv3 + conv1 compute for it -- all of them in the run's first band, all but the shared first one in every further band
+  struct Bg { int oy0, nrows_out, iy0, nrow_used, r_lo, npx, ntl; };
+  auto geom = [&](int b, bool first) {
+    Bg g;
+    g.oy0 = b * band;
+    g.nrows_out = min(band, Ho - g.oy0);
+    g.iy0 = g.oy0 * 2 - 1;
+    g.nrow_used = (g.nrows_out - 1) * 2 + 3;
+    g.r_lo = first ? max(g.iy0, 0) : g.iy0 + 1;                     // (2 oy0 < Hi: a further band has a new row inside the map)
+    g.npx = (min(g.iy0 + g.nrow_used, Hi) - g.r_lo) * Wi;
+    g.ntl = (g.npx + 15) >> 4;
+    return g;
+  };
+  // both operands of a wave's tile group (tiles tb, tb + 4, ...), clamped, no branch
+  auto request = [&](const Bg& g, int tb, u32x4 (&yf)[C3W_NPF], u32x4 (&rf)[C3W_NPF]) {
+#pragma unroll
+    for (int i = 0; i < C3W_NPF; ++i) {
+      const int t0 = tb + 4 * i;
+      const int p = t0 * 16 + pl;
+      int rr, cc;
+      dwi.divmod((t0 < g.ntl && p < g.npx) ? p : 0, rr, cc);
+      const unsigned o = (unsigned)(((g.r_lo + rr) * Wi + cc) * Cin + kc) * 2u;   // (host: a frame is below 2^31 bytes)
+      yf[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(yn) + o);
+      rf[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(rn) + o);
+    }
+  };
+  Bg cur = geom(b0, true);
+  u32x4 yf[C3W_NPF], rf[C3W_NPF];
+  request(cur, wv, yf, rf);                              // the first band's operands travel under the prologue
+  // ---- prologue, once per run
+  // gconv_load_w's fragments of slab 0 from a wave-uniform base: one scalar pointer and the lane's offset instead of a 64-bit
+  // address per k-step in registers across the band loop
+  auto load_gw = [&]() {
+    constexpr int pairs = CSP >= 32 ? CSP >> 5 : 1;
+    const unsigned char* wu = reinterpret_cast<const unsigned char*>(wfrag + (CSP >= 32 ? (wv % pairs) * 2 * 5 * 64 : 0));
+    unsigned lo = (unsigned)lane * 16u;
+    asm volatile("" : "+v"(lo));                                    // (keeps base + lane out of the loop's hoisted invariants)
+    GcW w;
+#pragma unroll
+    for (int ks = 0; ks < 5; ++ks) {
+      w.a[ks] = *reinterpret_cast<const bf16x8*>(wu + ks * 1024 + lo);
+      w.b[ks] = CSP >= 32 ? *reinterpret_cast<const bf16x8*>(wu + (5 + ks) * 1024 + lo) : w.a[ks];
+    }
+    return w;
+  };
+  GcW gw_;
+  {
+    // conv1's four fragments and conv3's pair (the same for every wave): 6 x 64 chunks, read back per band
+    const int i0 = tid, i1 = min(tid + 256, 6 * 64 - 1);
+    const bf16x8 wv0 = w1f[(long)min(i0 >> 6, nts - 1) * 64 + (i0 & 63)];
+    const bf16x8 wv1 = c3.w3f[i1 - 256];
+    const int c = tid & 63, cc = min(c, C - 1), c3c = min(tid & 31, Cin - 1);
+    const bool ok = c < C, ok3 = (tid & 31) < Cin;
+    const float v1a = s1[cc], v1b = h1[cc], v2a = scale[cc], v2b = shift[cc];
+    const float v3g = c3.gate[(long)n * Cin + c3c], v3a = c3.s3[c3c], v3b = c3.h3[c3c];
+    c1g_zero_halo(tile, cur.nrow_used, Hi, Wi, PS, cur.iy0);        // (the first band of a run has the most rows)
+    if (tid < 64) {
+      f1[0][c] = ok ? v1a : 0.f;
+      f1[1][c] = ok ? v1b : 0.f;
+      f2[0][c] = ok ? v2a : 0.f;
+      f2[1][c] = ok ? v2b : 0.f;
+    } else if (tid < 96) {
+      // channels beyond Cin: scale 1, shift 0, a zero operand -- exact zeros
+      f3[0][tid & 31] = v3g;
+      f3[1][tid & 31] = ok3 ? v3a : 1.f;
+      f3[2][tid & 31] = ok3 ? v3b : 0.f;
+    }
+    wl[i0 >> 6][i0 & 63] = wv0;
+    if (tid < 128) wl[4 + (tid >> 6)][tid & 63] = wv1;
+  }
+  __syncthreads();
+  GC_STAMP(1);
+  // conv3 + conv1 of one tile group into the band: c1_gconv_mfma_kernel<2, 1, true>'s expressions in its order
+  auto compute = [&](const Bg& g, int tb, const u32x4 (&yfi)[C3W_NPF], const u32x4 (&rfi)[C3W_NPF]) {
+    float g8[8], sc3[8], sh3[8];
+#pragma unroll
+    for (int e4 = 0; e4 < 8; e4 += 4) {
+      const f32x4 gv = *reinterpret_cast<const f32x4*>(&f3[0][kc + e4]);
+      const f32x4 sv = *reinterpret_cast<const f32x4*>(&f3[1][k8 + e4]), hv = *reinterpret_cast<const f32x4*>(&f3[2][k8 + e4]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        g8[e4 + e] = gv[e];
+        sc3[e4 + e] = sv[e];
+        sh3[e4 + e] = hv[e];
+      }
+    }
+    f32x4 a1[4], b1[4];
+    bf16x8 w1r[4];
+    const bf16x8 w3a = wl[4][lane], w3b = wl[5][lane];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      w1r[t] = wl[t][lane];
+      a1[t] = *reinterpret_cast<const f32x4*>(&f1[0][t * 16 + 4 * q]);
+      b1[t] = *reinterpret_cast<const f32x4*>(&f1[1][t * 16 + 4 * q]);
+    }
+#pragma unroll
+    for (int i = 0; i < C3W_NPF; ++i) {
+      const int t0 = tb + 4 * i;
+      if (t0 >= g.ntl) break;                                       // (wave-uniform)
+      const int p = t0 * 16 + pl;
+      const bool pok = p < g.npx;
+      int rr, col;
+      dwi.divmod(pok ? p : 0, rr, col);
+      const bf16x8 y8 = *reinterpret_cast<const bf16x8*>(&yfi[i]), r8 = *reinterpret_cast<const bf16x8*>(&rfi[i]);
+      bf16x8 a8;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float f = (float)y8[e];
+        f *= g8[e];
+        a8[e] = (bf16_t)f;
+      }
+      const u32x4 zero4 = {0u, 0u, 0u, 0u};
+      const u32x4 am = (pok && kok) ? *reinterpret_cast<const u32x4*>(&a8) : zero4;
+      const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+      const f32x4 c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w3a, *reinterpret_cast<const bf16x8*>(&am), z4, 0, 0, 0);
+      const f32x4 c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w3b, *reinterpret_cast<const bf16x8*>(&am), z4, 0, 0, 0);
+      float v[8];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        v[r] = c0[r] * sc3[r] + sh3[r];
+        v[4 + r] = c1[r] * sc3[4 + r] + sh3[4 + r];
+      }
+      bf16x8 o8;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        v[e] += (float)r8[e];
+        v[e] = fmaxf(v[e], 0.f);
+        o8[e] = (bf16_t)v[e];
+      }
+      const u32x4 xm = kok ? *reinterpret_cast<const u32x4*>(&o8) : zero4;
+      const bf16x8 xf = *reinterpret_cast<const bf16x8*>(&xm);
+      const int row = g.r_lo + rr;
+      // the compact map: even rows and columns; row 2 oy belongs to the band that owns output row oy (no row twice)
+      if (xsn && pok && kok && !((row | col) & 1) && (row >> 1) >= g.oy0 && (row >> 1) < g.oy0 + g.nrows_out)
+        *reinterpret_cast<u32x4*>(xsn + ((long)(row >> 1) * Wo + (col >> 1)) * Cin + k8) = xm;
+      unsigned char* dst = tile + ((long)(row - g.iy0) * WP + col + 1) * PS + 8 * q;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        if (t < nts) {
+          const f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1r[t], xf, z4, 0, 0, 0);
+          if (pok) {
+            bf16x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = (bf16_t)fmaxf(acc[e] * a1[t][e] + b1[t][e], 0.f);
+            *reinterpret_cast<bf16x4*>(dst + t * 32) = o;
+          }
+        }
+      }
+    }
+  };
+  const int rowchunks = (WP * PS) >> 4;                             // 16-byte chunks of one band row (PS is a multiple of 16)
+  for (int b = b0; b < b1; ++b) {
+    TD_ISSUE_FENCE();                                               // (the folds are read from LDS per band, not kept in registers)
+    // a row below the map holds the band before's data: zero again.  Only the bottom row of a frame's last band at odd Hi
+    // (the band's last input row is at most 2 Ho - 1 <= Hi)
+    const int rz = Hi - cur.iy0;
+    if (b != b0 && rz < cur.nrow_used)
+      for (int i = tid; i < rowchunks; i += 256)
+        *reinterpret_cast<u32x4*>(tile + rz * (WP * PS) + i * 16) = (u32x4){0u, 0u, 0u, 0u};
+    compute(cur, wv, yf, rf);
+    for (int tb = wv + 4 * C3W_NPF; tb < cur.ntl; tb += 4 * C3W_NPF) {   // (a run's first band, wide maps: one round trip each)
+      request(cur, tb, yf, rf);
+      compute(cur, tb, yf, rf);
+    }
+    const Bg nxt = geom(min(b + 1, b1 - 1), false);
+    gw_ = load_gw();                                                // in front of the operands: its wait leaves them in flight
+    request(nxt, wv, yf, rf);                            // travels under the grouped conv (always: see above)
+    if (b == b0) GC_STAMP(2);
+    if (b == b0 + 1) GC_STAMP(4);
+    __syncthreads();
+    // wait for the grouped conv's weights HERE, by count: the operands requested behind them stay in flight.  Left to itself
+    // hipcc drains every load in flight in front of the grouped conv's tile loop (a loop that uses loaded registers and holds
+    // no load gets vmcnt(0) in its preheader), the prefetch included.  vmcnt(2 * C3W_NPF), the other counters untouched
+    __builtin_amdgcn_s_waitcnt(0x0F70 | (2 * C3W_NPF));
+    gconv_band_mma<2>(gw_, tile, red, redq, Wi, C, wfrag, f2[0], f2[1], y, pooled, nullptr, Ho, Wo, nbands, CSP, PS, 1, n, b, 0,
+                      cur.oy0, cur.nrows_out);
+    // every wave is behind the grouped conv's barrier, i.e. behind every wave's reads of the band: the shared row moves to the
+    // top (halo columns included: zeros), then one barrier in front of the next band's stores into the band
+    for (int i = tid; i < rowchunks; i += 256)
+      *reinterpret_cast<u32x4*>(tile + i * 16) = *reinterpret_cast<const u32x4*>(tile + (cur.nrow_used - 1) * (WP * PS) + i * 16);
+    __syncthreads();
+    if (b == b0) GC_STAMP(3);
+    if (b == b0 + 1) GC_STAMP(5);
+    cur = nxt;
+  }
+  GC_STAMP(6);
+}
+
 static long long* g_c1g_dbg = nullptr;
 extern "C" int tdeed_c1_gconv_set_debug(void* buf) { g_c1g_dbg = (long long*)buf; return TDEED_OK; }
 
@@ -1225,6 +1463,40 @@ extern "C" int tdeed_c1_gconv_c3in_fits(int Hi, int Wi, int Cp, int C) {
   if (Cp < 8 || Cp > 32 || Cp % 8 != 0 || C > 64 || !tdeed_c1_gconv_fits(Hi, Wi, Cp, C, 2)) return 0;
   return gc_geom(Hi, Wi, C, 2).nslabs == 1 ? 1 : 0;
 }
+// The band walk (c1_gconv_c3in_walk_kernel): one workgroup per (frame, run of `walk` bands).  tdeed_c1_gconv_c3in_walk: the routed
+// run length, a function of the shape alone (never of N), chosen from measurements; 1 is the per-band kernel.
+// tdeed_c1_gconv_c3in_set_walk overrides it for tests and tools: 0 as routed, 1 the per-band kernel, k >= 2 runs of k bands
+// (clamped to the frame's band count).  tdeed_c1_gconv_c3in_workgroups: the grid under the form in force.
+// measured (profiles/c1_gconv_c3in_walk_ab.json): alone at 800 x 56 x 56 runs of 1 / 2 / 3 / 4 / 5 / 7 / 14 bands take
+// 135.9 / 114.4 / 111.3 / 121.4 / 111.1 / 116.5 / 138.0 us; in the headline runs of 5 gain 3.1 %, runs of 3 2.2 %
+#define C3IN_WALK_ROUTED 5
+static int g_c3in_walk = 0;
+extern "C" int tdeed_c1_gconv_c3in_set_walk(int walk) {
+  TD_CHECK(walk >= 0 && walk <= 65535, "c1_gconv_c3in_set_walk: %d (0 routed, 1 per band, k >= 2 runs of k bands)", walk);
+  g_c3in_walk = walk;
+  return TDEED_OK;
+}
+extern "C" int tdeed_c1_gconv_c3in_walk(int Hi, int Wi, int Cp, int C) {
+  if (!tdeed_c1_gconv_c3in_fits(Hi, Wi, Cp, C)) return 0;
+  if ((long)Hi * Wi * Cp * 2 >= (1L << 31)) return 1;                // (the walk addresses a frame with 32-bit byte offsets)
+  const int nb = gc_geom(Hi, Wi, C, 2).nbands;
+  return C3IN_WALK_ROUTED < nb ? C3IN_WALK_ROUTED : nb;
+}
+static int c3in_walk_in_force(int Hi, int Wi, int Cp, int C) {
+  // (TDEED_C3IN_WALK: the override for a process that cannot call set_walk -- the headline A/B of two run lengths)
+  static int env = -1;
+  if (env < 0) { const char* e = getenv("TDEED_C3IN_WALK"); env = e ? atoi(e) : 0; if (env < 0) env = 0; }
+  const int forced = g_c3in_walk ? g_c3in_walk : env;
+  if (forced == 0) return tdeed_c1_gconv_c3in_walk(Hi, Wi, Cp, C);
+  if ((long)Hi * Wi * Cp * 2 >= (1L << 31)) return 1;                // (the walk addresses a frame with 32-bit byte offsets)
+  const int nb = gc_geom(Hi, Wi, C, 2).nbands;
+  return forced < nb ? forced : nb;
+}
+extern "C" int tdeed_c1_gconv_c3in_workgroups(int N, int Hi, int Wi, int Cp, int C) {
+  if (N <= 0 || !tdeed_c1_gconv_c3in_fits(Hi, Wi, Cp, C)) return 0;
+  const int nb = gc_geom(Hi, Wi, C, 2).nbands, walk = c3in_walk_in_force(Hi, Wi, Cp, C);
+  return N * ((nb + walk - 1) / walk);
+}
 extern "C" int tdeed_c1_gconv_c3in_fwd(const void* y2p, const void* scp, const float* gate, const void* w3f, const float* s3,
                                        const float* h3, void* xs2, int N, int Hi, int Wi, int Cp, int C, int gw,
                                        const void* w1f, const float* s1, const float* h1, const void* wfrag,
@@ -1239,6 +1511,18 @@ extern "C" int tdeed_c1_gconv_c3in_fwd(const void* y2p, const void* scp, const f
   dim3 grid((unsigned)((long)g.nbands * N));
   const size_t smem = (size_t)g.rows_in * (Wi + 2) * g.PS;
   const C3In c3{(const bf16_t*)y2p, (const bf16_t*)scp, gate, (const bf16x8*)w3f, s3, h3, (bf16_t*)xs2};
+  const int walk = c3in_walk_in_force(Hi, Wi, Cp, C);
+  if (walk >= 2) {
+    dim3 wgrid((unsigned)((long)((g.nbands + walk - 1) / walk) * N));
+#define TD_C3W(CSPv)                                                                                                        \
+  hipLaunchKernelGGL((c1_gconv_c3in_walk_kernel<CSPv>), wgrid, dim3(256), smem, (hipStream_t)stream, Hi, Wi,  \
+                     Cp, C, (const bf16x8*)w1f, s1, h1, (const bf16x8*)wfrag, scale, shift, (bf16_t*)y, pooled, Ho, Wo,       \
+                     g.band, g.nbands, walk, g_c1g_dbg, c3)
+    if (g.CSP == 64) TD_C3W(64); else if (g.CSP == 32) TD_C3W(32); else TD_C3W(16);
+#undef TD_C3W
+    TD_LAUNCH_CHECK("c1_gconv_c3in_walk");
+    return TDEED_OK;
+  }
   hipLaunchKernelGGL((c1_gconv_mfma_kernel<2, 1, true>), grid, dim3(256), smem, (hipStream_t)stream, (const bf16_t*)nullptr,
                      (const bf16_t*)nullptr, 0, Hi, Wi, Cp, C, (const bf16x8*)w1f, s1, h1, (const bf16x8*)wfrag, scale, shift,
                      (bf16_t*)y, pooled, Ho, Wo, g.band, g.nbands, g.CSP, g.PS, g.rows_in, 1, g_c1g_dbg, c3);

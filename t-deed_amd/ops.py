@@ -184,6 +184,22 @@ def c1_gconv_c3in_fits(Hi, Wi, Cp, C):
     return lib.tdeed_c1_gconv_c3in_fits(Hi, Wi, Cp, C) != 0
 
 
+def c1_gconv_c3in_set_walk(walk):
+    """0: the run length of c1_gconv_c3in's band walk as routed per shape (default); 1: one workgroup per (frame, band);
+    k >= 2: one workgroup per (frame, run of k bands), clamped to the frame's band count."""
+    call("tdeed_c1_gconv_c3in_set_walk", walk)
+
+
+def c1_gconv_c3in_walk(Hi, Wi, Cp, C):
+    """the routed run length of c1_gconv_c3in for the shape (1: the per-band kernel)"""
+    return _lib.load().tdeed_c1_gconv_c3in_walk(Hi, Wi, Cp, C)
+
+
+def c1_gconv_c3in_workgroups(N, Hi, Wi, Cp, C):
+    """the grid c1_gconv_c3in launches for N frames of this shape under the run length in force"""
+    return _lib.load().tdeed_c1_gconv_c3in_workgroups(N, Hi, Wi, Cp, C)
+
+
 def c1_gconv_c3in(y2p, scp, gate, w3frag, s3, h3, w1f, s1, h1, wfrag, scale, shift, gw, C, xs2=None, out=None, pooled=None):
     """c1_gconv(gemm_ws(y2p, w3frag, Cp, Cp, s3, h3, ACT_RELU, residual=scp, a_scale=gate, a_scale_rows=Hi*Wi), ..., stride 2)
     in one launch (tdeed_c1_gconv_c3in_fwd), bit for bit: the producer's conv3 runs per pixel tile in front of conv1 and its

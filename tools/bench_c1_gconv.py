@@ -1,8 +1,9 @@
 """GPU tool: conv1 + grouped 3x3 in one launch (tdeed_c1_gconv_fwd) alone at the shapes of the shipped models, with its phase
 time stamps (tdeed_c1_gconv_set_debug), in both forms (per slab / slab loop) where both exist; then the form that also
 computes the producer's conv3 (tdeed_c1_gconv_c3in_fwd) against the two launches it replaces, at 800 x 56 x 56 x 24 -> 56,
-with the stamps of both.
-    python tools/bench_c1_gconv.py"""
+with the stamps of both; then the band walk of that form (tdeed_c1_gconv_c3in_set_walk): the launch alone at every run length
+of the sweep, with the stamps of a walking workgroup.
+    python tools/bench_c1_gconv.py [--c3in]        (--c3in: only the conv3-in section)"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -29,7 +30,7 @@ def timeit(fn, reps=30):
 
 SHAPES = [("200MF s2.b1", 800, 56, 24, 56, 8, 2), ("200MF s3.b1", 800, 28, 56, 152, 8, 2), ("200MF s4.b1", 800, 14, 152, 368, 8, 2),
           ("800MF s2.b1", 1600, 56, 64, 128, 16, 2), ("800MF s2.b2", 1600, 28, 128, 128, 16, 1), ("800MF s3.b1", 1600, 28, 128, 320, 16, 2)]
-for name, N, Hi, Cin, C, gw, stride in SHAPES:
+for name, N, Hi, Cin, C, gw, stride in ([] if "--c3in" in sys.argv else SHAPES):
     g = torch.Generator().manual_seed(0)
     if not ops.c1_gconv_fits(Hi, Hi, Cin, C, stride):
         print(f"{name}: not served")
@@ -137,6 +138,9 @@ def fused():
     ops.c1_gconv_c3in(y2p, scp, gate, W3, s3, h3, w1f, s1, h1, w2f, s2, h2, gw, C, xs2=xs2, out=out_f, pooled=pooled_f)
 
 
+HAS_WALK = hasattr(_lib.load(), "tdeed_c1_gconv_c3in_set_walk")     # (not in an A/B flavour built from an older revision)
+if HAS_WALK:
+    ops.c1_gconv_c3in_set_walk(1)
 t3, tc, tch, tf = timeit(conv3), timeit(c1g), timeit(chain), timeit(fused)
 same = torch.equal(out, out_f) and torch.equal(pooled, pooled_f) and torch.equal(xs2, mid[:, ::2, ::2, :])
 print(f"conv3 in front of conv1, N={N} {Hi}x{Hi} {Cp}->{C}: conv3 alone {t3:.1f} us, c1_gconv alone {tc:.1f} us, the two back to back "
@@ -144,3 +148,35 @@ print(f"conv3 in front of conv1, N={N} {Hi}x{Hi} {Cp}->{C}: conv3 alone {t3:.1f}
 for label, run in (("c1_gconv", c1g), ("fused   ", fused)):
     ph, wg = stamped(run, N * parts)
     print(f"  {label} workgroup median {wg:.2f} us: " + ", ".join(f"{n_} {v:.2f}" for n_, v in zip(PHASES, ph)), flush=True)
+
+
+# ---- the band walk: one workgroup per (frame, run of `walk` bands).  The launch alone per run length (event timing, three
+# rounds interleaved over the run lengths so that a drift of the box hits all of them), outputs against the per-band form, and
+# the stamps of a walking workgroup: 0 start, 1 prologue end, 2 / 3 the first band's conv3 + conv1 and grouped conv (with the row
+# copy and the barrier behind it), 4 / 5 the second band's, 6 run end
+if HAS_WALK:
+    WALK_PHASES = ["prologue", "first band conv3 + conv1", "first band grouped conv + row copy", "second band conv3 + conv1",
+                   "second band grouped conv + row copy", "the other bands"]
+    ref = (out_f.clone(), pooled_f.clone(), xs2.clone())
+    walks = [1, 2, 3, 4, 5, 7, 14]
+    times = {w: [] for w in walks}
+    for _ in range(3):
+        for w in walks:
+            ops.c1_gconv_c3in_set_walk(w)
+            times[w].append(timeit(fused))
+    routed = ops.c1_gconv_c3in_walk(Hi, Hi, Cp, C)
+    print(f"band walk, N={N} {Hi}x{Hi} {Cp}->{C}, {parts} bands per frame, routed run length {routed}:")
+    for w in walks:
+        ops.c1_gconv_c3in_set_walk(w)
+        nwg = ops.c1_gconv_c3in_workgroups(N, Hi, Hi, Cp, C)
+        out_f.fill_(-7.0); xs2.fill_(-7.0); pooled_f.fill_(float("nan"))
+        fused()
+        torch.cuda.synchronize()
+        same = torch.equal(out_f, ref[0]) and torch.equal(pooled_f, ref[1]) and torch.equal(xs2, ref[2])
+        line = (f"  walk {w:2d}: {nwg:5d} workgroups, " + " / ".join(f"{t_:.1f}" for t_ in times[w])
+                + f" us per launch (median {float(np.median(times[w])):.1f}); identical to walk 1: {same}")
+        if w >= 2:
+            ph, wg = stamped(fused, nwg)
+            line += f"; workgroup median {wg:.2f} us: " + ", ".join(f"{n_} {v:.2f}" for n_, v in zip(WALK_PHASES, ph))
+        print(line, flush=True)
+    ops.c1_gconv_c3in_set_walk(0)
