@@ -504,6 +504,37 @@ int tdeed_nms_track_seg(const float* mean, const int* seg_off, int nv, int L_tot
                         int* st_count, int* out_frame, unsigned char* out_class_u8, double* out_score, int* event_off, int* rounds,
                         void* stream);
 
+/* ---- average precision of the spotted events (ap.hip) ----------------------------------------------------------------
+ * The dataset: NV videos, video `ord` (the index of its name in sorted order) owns the frames vid_off[ord] .. vid_off[ord+1]-1
+ * of LT_all (vid_off int32[NV+1]).  The truth: gt_off int32[NV*K1 + 1], entry ord*K1 + c the start of the ground-truth frames
+ * of class c in video ord inside gt_frames int32[G], in the truth record's list order (duplicates stay).  All on the device. */
+/* longest video whose events are ordered in LDS; longer ones are ordered in place in ev_score / ev_frame */
+int tdeed_ap_lds_frames(void);
+/* tolerances one launch takes */
+int tdeed_ap_max_tolerances(void);
+/* ground-truth frames one class may have in one video with n_tol tolerances (they live in LDS); 0: n_tol out of range */
+int tdeed_ap_max_truth(int n_tol);
+/* Segment + match, one workgroup per class c >= 1 and video v of a group's packed track (mean, seg_off, nv, L_total, max_len as
+ * for tdeed_nms_track_seg; ords int32[nv] the videos' ordinals).  Events: emitted == NULL: the frames with mean[f][c] >=
+ * hr_threshold, score (double)mean[f][c]; otherwise the frames with emitted[c][f] != 0, score kept_score[c][f], the planes
+ * [K1][L_total] of tdeed_nms_track_seg.  They are ordered by score descending, frame ascending and stored: ev_score double /
+ * ev_frame int32 [K1-1][LT_all] from vid_off[ord] on, ev_count int32 [K1-1][NV].  Then per tolerance (HOST int32[n_tol], each
+ * >= 0) the greedy matching of util/score.py:45-96 restricted to the video: hit_pos int32 [n_tol][G], entry gt_off[ord*K1+c] + k
+ * the position of the k-th hit in the ordered list, hit_count int32 [n_tol][NV*K1].  max_gt: the longest ground-truth list.
+ * Deterministic: no atomics. */
+int tdeed_ap_match_seg(const float* mean, const unsigned char* emitted, const double* kept_score, const int* seg_off, int nv,
+                       int L_total, int max_len, int K1, float hr_threshold, const int* ords, int NV, const int* vid_off,
+                       long LT_all, const int* gt_off, const int* gt_frames, int G, int max_gt, const int* tolerances, int n_tol,
+                       double* ev_score, int* ev_frame, int* ev_count, int* hit_pos, int* hit_count, void* stream);
+/* Rank + AP, once every video has been matched; the buffers above with a leading [n_entries] axis.  rank int32
+ * [n_entries][n_tol][G]: per hit its 1-based position among all predictions of its class in the order score descending, video
+ * ordinal ascending, frame ascending.  class_off int32[K1+1]: class c owns class_off[c] .. class_off[c+1]-1 of the G entries of
+ * psorted double [n_entries][n_tol][G] (scratch; the precisions in rank order), i.e. class_off[c+1] - class_off[c] is the
+ * class's ground-truth count.  ap double / nhits int32 [n_entries][n_tol][K1]: interpolated average precision and hits. */
+int tdeed_ap_rank(const double* ev_score, const int* ev_count, const int* vid_off, int NV, long LT_all, const int* gt_off, int G,
+                  int K1, int n_entries, int n_tol, const int* hit_pos, const int* hit_count, const int* class_off, int* rank,
+                  double* psorted, double* ap, int* nhits, void* stream);
+
 /* ---- training clips drawn from resident videos (trainclips.hip) -----------------------------------------------------
  * frames: uint8 [total_frames][frame_bytes], the frames of all resident videos packed one after the other.  The tables are
  * DEVICE int64[B], per clip: first = first packed frame of the clip's video, nframes = that video's length, base = the

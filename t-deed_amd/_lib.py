@@ -194,6 +194,12 @@ _SIGS = {
     "tdeed_nms_track_seg_threads": ([c_int], c_int),
     "tdeed_nms_track_seg": ([P, P, c_int, c_int, c_int, c_int, c_float, c_double, c_int, P, c_int, P, P, P, P, P, P, P, P, P, P, P,
                              P, P, P], c_int),
+    "tdeed_ap_lds_frames": ([], c_int),
+    "tdeed_ap_max_tolerances": ([], c_int),
+    "tdeed_ap_max_truth": ([c_int], c_int),
+    "tdeed_ap_match_seg": ([P, P, P, P, c_int, c_int, c_int, c_int, c_float, P, c_int, P, c_long, P, P, c_int, c_int, P, c_int, P, P,
+                            P, P, P, P], c_int),
+    "tdeed_ap_rank": ([P, P, P, c_int, c_long, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P], c_int),
     "tdeed_train_clip_gather_u8": ([P, c_long, c_long, P, P, P, c_int, c_int, c_int, P, P], c_int),
     "tdeed_train_clip_gather_mix_f32": ([P, c_long, c_long, P, P, P, P, P, P, P, c_int, c_int, c_int, P, P], c_int),
     "tdeed_clip_labels": ([P, P, c_int, c_int, c_int, c_int, P, P, P, c_int, c_int, P, P, P], c_int),

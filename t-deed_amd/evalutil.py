@@ -518,3 +518,167 @@ def mean_average_precisions(truth, pred, tolerances=(0, 1, 2, 4)):
     aps = {lab: [average_precision(flat.get(lab, []), by_label[lab], tol) for tol in tolerances] for lab in sorted(by_label)}
     maps = [float(np.mean([aps[lab][i] for lab in aps])) for i in range(len(tolerances))]
     return maps, aps
+
+
+# ----------------------------------------------------------------------------- average precision by counting
+# `average_precision` walks one globally sorted list, but (1) whether a prediction recalls a ground-truth frame depends only
+# on the earlier predictions of its own video, and (2) only the hits need a global position.  The three functions below state
+# that decomposition; they are the oracle of the device route (csrc/ap.hip), as `nms_rounds` is of the suppression kernel.
+def ap_match_video(frames, scores, gt, tolerance):
+    """The greedy matching of `average_precision` for ONE label in ONE video.  frames / scores: the video's predictions of the
+    label, frames unique; gt: its ground-truth frames in the truth record's list order, duplicates kept.
+    -> (order, hits): order sorts the predictions by (score descending, frame ascending) -- the global order restricted to the
+    video; hits are the positions in that order that recall a ground-truth frame: the closest open one within `tolerance`, the
+    first in list order on equal distance; a hit closes every entry with that frame.  Stops when nothing is open."""
+    frames, scores = np.asarray(frames, np.int64), np.asarray(scores, np.float64)
+    order = np.lexsort((frames, -scores))
+    open_gt, hits = [int(f) for f in gt], []
+    for i, e in enumerate(order):
+        if not open_gt:
+            break
+        d = np.abs(np.asarray(open_gt, np.int64) - frames[e])
+        j = int(np.argmin(d))
+        if d[j] <= tolerance:
+            hit = open_gt[j]
+            open_gt = [f for f in open_gt if f != hit]
+            hits.append(i)
+    return order, hits
+
+
+def ap_hit_ranks(sorted_scores, hits):
+    """sorted_scores: per video, in ordinal order, the label's scores in `ap_match_video`'s order; hits: per video the hit
+    positions.  -> per video the hits' 1-based ranks among ALL predictions of the label in the order (score descending, video
+    ordinal ascending, frame ascending) -- Python's stable sort(reverse=True) of the list `mean_average_precisions` builds --
+    by counting: an earlier video precedes on equal score, a later one only with a greater score."""
+    neg = [-np.asarray(s, np.float64) for s in sorted_scores]
+    out = []
+    for v, hv in enumerate(hits):
+        ranks = []
+        for pos in hv:
+            s = neg[v][pos]
+            before = int(pos)
+            for u, a in enumerate(neg):
+                if u != v:
+                    before += int(np.searchsorted(a, s, side="right" if u < v else "left"))
+            ranks.append(before + 1)
+        out.append(ranks)
+    return out
+
+
+def ap_from_ranks(ranks, total):
+    """ranks: the hits' global ranks, any order; total: the label's ground-truth count (duplicates included).  The k-th hit by
+    rank has precision k / rank; running maximum from the right, sum, / total."""
+    if len(ranks) == 0:
+        return 0.0
+    r = np.sort(np.asarray(ranks, np.int64))
+    pc = np.arange(1, len(r) + 1) / r
+    return float(np.maximum.accumulate(pc[::-1]).sum() / total)
+
+
+def ap_restated(events, truth, tolerance):
+    """One label over a dataset: events / truth per video in ordinal order, (frames, scores) and [ground-truth frames].
+    -> dict(ap, hits: per video the hit positions, ranks: per video, frames / scores: per video in matching order, total)."""
+    total = sum(len(g) for g in truth)
+    frames, scores, hits = [], [], []
+    for (f, s), g in zip(events, truth):
+        f, s = np.asarray(f, np.int64), np.asarray(s, np.float64)
+        order, hv = ap_match_video(f, s, g, tolerance)
+        frames.append(f[order])
+        scores.append(s[order])
+        hits.append(hv)
+    ranks = ap_hit_ranks(scores, hits)
+    return dict(ap=ap_from_ranks([r for rv in ranks for r in rv], total), hits=hits, ranks=ranks, frames=frames, scores=scores,
+                total=total)
+
+
+def mean_average_precisions_by_counting(truth, pred, tolerances=(0, 1, 2, 4)):
+    """`mean_average_precisions` through the decomposition above (the video ordinal is the record's position in `pred`) ->
+    (mAP per tolerance, {label: [AP per tolerance]}, {(label, tolerance): ap_restated's dict})."""
+    assert {v["video"] for v in truth} == {v["video"] for v in pred}, "Video set mismatch!"
+    names = [x["video"] for x in pred]
+    ordinal = {v: i for i, v in enumerate(names)}
+    gt = defaultdict(lambda: [[] for _ in names])
+    for x in truth:
+        for e in x["events"]:
+            gt[e["label"]][ordinal[x["video"]]].append(e["frame"])
+    ev = defaultdict(lambda: [([], []) for _ in names])
+    for x in pred:
+        for e in x["events"]:
+            f, s = ev[e["label"]][ordinal[x["video"]]]
+            f.append(e["frame"])
+            s.append(e["score"])
+    detail = {(lab, tol): ap_restated(ev[lab], gt[lab], tol) for lab in sorted(gt) for tol in tolerances}
+    aps = {lab: [detail[lab, tol]["ap"] for tol in tolerances] for lab in sorted(gt)}
+    maps = [float(np.mean([aps[lab][i] for lab in aps])) for i in range(len(tolerances))]
+    return maps, aps, detail
+
+
+def truth_table(truth, ordinal, classes):
+    """The truth records as the table `ops.ap_state` uploads: {(video ordinal, class index): [frames in list order]}."""
+    table = defaultdict(list)
+    for x in truth:
+        for e in x["events"]:
+            if e["label"] not in classes:
+                raise ValueError(f"truth label {e['label']!r} is not one of the model's classes")
+            table[ordinal[x["video"]], classes[e["label"]]].append(e["frame"])
+    return dict(table)
+
+
+def map_suppress_entries(suppress, who):
+    """the suppress entries of a mAP pass as tuples: ("raw",) or (kind, window, threshold) with kind "nms" | "snms", at least one"""
+    suppress = [tuple(e) for e in suppress]
+    for e in suppress:
+        if not e or e[0] not in ("raw", "nms", "snms") or len(e) != (1 if e[0] == "raw" else 3):
+            raise ValueError(f"{who}: suppress entry {e!r}: ('raw',) or (kind, window, threshold) with kind nms | snms")
+    if not suppress:
+        raise ValueError(f"{who}: no suppress entry")
+    return suppress
+
+
+def map_videos(model, videos, classes, truth, suppress, tolerances=(0, 1, 2, 4), high_recall_score_threshold=0.01, augment=False,
+               batch_size=8, overlap_len=None, decode_ahead=1, group_videos=1, max_resident_bytes=16 << 30, reuse_frames=False,
+               decode="host"):
+    """`spot_videos` + `mean_average_precisions` per suppress entry with the whole tail on the device: no event list reaches the
+    host.  videos and the keyword arguments as in `spot_videos`; truth: the records `mean_average_precisions` takes; suppress:
+    entries ("raw",) -- the unsuppressed high-recall list -- or (kind, window, threshold) with kind "nms" | "snms".
+    Returns per suppress entry (mAP per tolerance, {label: [AP per tolerance]}), `mean_average_precisions`' result: the APs
+    come from the device (csrc/ap.hip), the mean over the truth's labels is taken here, in sorted label order.  The video
+    ordinal -- the index of a video's name in sorted order -- decides ties between videos, whatever order the groups arrive
+    in.  The host synchronises once per group and once for the (entries, tolerances, K+1) table; model.last_video_stats:
+    the groups' totals plus groups, host_syncs and ap_d2h_bytes."""
+    from . import ops
+    videos = list(videos)
+    suppress = map_suppress_entries(suppress, "map_videos")
+    tols = ops.ap_tolerances(tolerances, "map_videos")
+    names = sorted(v[0] for v in videos)
+    assert {x["video"] for x in truth} == set(names), "Video set mismatch!"
+    if len(set(names)) != len(names):
+        raise ValueError("map_videos: video names must be unique")
+    ordinal = {v: i for i, v in enumerate(names)}
+    length = {v[0]: int(v[1]) for v in videos}
+    K1 = len(classes) + 1
+    table = truth_table(truth, ordinal, classes)
+    videos = _with_loader(videos, decode)
+    reuse = dict(reuse_frames=True) if reuse_frames else {}
+    state = ops.ap_state([length[v] for v in names], table, K1, len(suppress), tols, device=model.device)
+    totals, groups = defaultdict(int), 0
+    for group in _decoded_groups(videos, group_videos, max_resident_bytes, decode_ahead):
+        model.map_video_group([g[3] for g in group], classes, state, [ordinal[g[0]] for g in group], suppress=suppress,
+                              high_recall_score_threshold=high_recall_score_threshold, overlap_len=overlap_len,
+                              batch_size=batch_size, augment=augment, max_resident_bytes=max_resident_bytes, **reuse)
+        groups += 1
+        for k, v in model.last_video_stats.items():
+            if k != "views":
+                totals[k] += v
+    ap, _ = model.map_finish(state)
+    for k, v in model.last_video_stats.items():
+        totals[k] += v
+    totals["groups"] = groups
+    model.last_video_stats = dict(totals)
+    inv = {v: k for k, v in classes.items()}
+    labels = sorted(inv[c] for c in range(1, K1) if state.totals[c] > 0)
+    out = []
+    for i in range(len(suppress)):
+        aps = {lab: [float(ap[i, t, classes[lab]]) for t in range(len(tols))] for lab in labels}
+        out.append(([float(np.mean([aps[lab][t] for lab in aps])) for t in range(len(tols))], aps))
+    return out

@@ -550,6 +550,78 @@ class TDEEDModel:
         self.last_video_stats = stats
         return out
 
+    def map_video_group(self, frames_list, classes, state, ordinals, suppress=(("nms", 1, 0.01), ("snms", 3, 0.01)),
+                        high_recall_score_threshold=0.01, clip_starts=None, overlap_len=None, pad_len=5, batch_size=8,
+                        augment=False, use_amp=True, max_resident_bytes=16 << 30, reuse_frames=False):
+        """spot_video_group's pipeline for a mAP pass (evalutil.map_videos): the group is scored as one packed job, then on the
+        packed track one event launch, per entry of `suppress` its suppression launch (none for ("raw",), the unsuppressed
+        high-recall list) and the segment + match launch (ops.ap_match_seg), which leaves the group's ordered predictions and
+        hits in `state` (ops.ap_state, one per dataset, as many entries as `suppress`).  ordinals: per video its index among
+        the dataset's sorted names.  Nothing is copied to the host -- no pred, no event list; the host synchronises once, so
+        that the resident buffers outlive the stream work.  Returns state.  last_video_stats: the group's totals, host_syncs
+        1, ap_d2h_bytes 0."""
+        who = "map_video_group"
+        from . import evalutil
+        frames_list = list(frames_list)
+        suppress = evalutil.map_suppress_entries(suppress, who)
+        if not isinstance(state, ops.ApState):
+            raise TypeError(f"{who}: state must come from ops.ap_state")
+        K1 = self._score_cols(torch.bfloat16 if use_amp else torch.float32)
+        if K1 > 256:
+            raise ValueError(f"{who}: {K1} score columns, at most 256")
+        if sorted(classes.values()) != list(range(1, K1)):
+            raise ValueError(f"{who}: classes must name the indices 1..{K1 - 1} of the model's score columns")
+        ordinals = [int(o) for o in ordinals]
+        if state.K1 != K1 or state.E != len(suppress):
+            raise ValueError(f"{who}: a state of {state.K1} columns and {state.E} entries for {K1} columns and {len(suppress)} entries")
+        if len(ordinals) != len(frames_list) or len(set(ordinals)) != len(ordinals) \
+                or any(not 0 <= o < state.NV or state.lengths[o] != int(fr.shape[0]) for o, fr in zip(ordinals, frames_list)):
+            raise ValueError(f"{who}: ordinals {ordinals} do not name {len(frames_list)} videos of the state's dataset by length")
+        _, _, mean, s0, stats, keep, g = self._packed_track(who, frames_list, clip_starts, overlap_len, pad_len, batch_size,
+                                                            augment, use_amp, max_resident_bytes, want_mean=True,
+                                                            reuse_frames=reuse_frames)
+        hr = float(high_recall_score_threshold)
+        h_ords = torch.tensor(ordinals, dtype=torch.int32).pin_memory()
+        with torch.cuda.stream(s0):
+            ords = torch.empty((g.nv,), dtype=torch.int32, device=mean.device)
+            ords.copy_(h_ords, non_blocking=True)
+            first = None
+            for i, e in enumerate(suppress):
+                planes = None
+                if e[0] != "raw":
+                    if first is None:
+                        first = ops.frame_events_seg(mean, g.seg_off_dev, g.max_len, hr, first_init=g.first_init)[2]
+                    planes = ops.nms_track_seg(mean, g.seg_off_dev, g.max_len, e[1], e[2], e[0] == "snms", first, hr,
+                                               planes=True)[5:]
+                ops.ap_match_seg(state, i, mean, g.seg_off_dev, ords, g.max_len, hr, planes=planes)
+            s0.synchronize()
+        del keep, h_ords
+        stats["host_syncs"] = 1
+        stats["ap_d2h_bytes"] = 0
+        self.last_video_stats = stats
+        return state
+
+    def map_finish(self, state):
+        """The end of a mAP pass: rank + AP over everything the groups left in `state` (ops.ap_rank), then the one copy of the
+        pass: -> (ap float64 (entries, tolerances, K+1), hits int32 of that shape) numpy.  One host synchronisation;
+        last_video_stats: host_syncs 1 and ap_d2h_bytes, 12 bytes per (entry, tolerance, column) whatever the events."""
+        if not isinstance(state, ops.ApState):
+            raise TypeError("map_finish: state must come from ops.ap_state")
+        from .streams import new_stream
+        if self._stream is None:
+            self._stream = new_stream()
+        s0 = self._stream
+        s0.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s0):
+            ap, nhits, _ = ops.ap_rank(state)
+            h_ap = torch.empty(ap.shape, dtype=torch.float64).pin_memory()
+            h_n = torch.empty(nhits.shape, dtype=torch.int32).pin_memory()
+            h_ap.copy_(ap, non_blocking=True)
+            h_n.copy_(nhits, non_blocking=True)
+            s0.synchronize()
+        self.last_video_stats = dict(host_syncs=1, ap_d2h_bytes=ap.numel() * 12)
+        return h_ap.numpy().copy(), h_n.numpy().copy()
+
     frame_batch = 2                     # clips' worth of frames per launch of the per-frame pass (reuse_frames=True)
 
     def _packed_track(self, who, frames_list, clip_starts, overlap_len, pad_len, batch_size, augment, use_amp,

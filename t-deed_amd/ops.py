@@ -7,6 +7,7 @@ launches the HIP kernel on the current stream.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -954,13 +955,15 @@ def frame_events_seg(mean, seg_off, max_len, hr_threshold=0.01, pred_u8=None, fi
     return pred, pred_score, first, count
 
 
-def nms_track_seg(mean, seg_off, max_len, window, threshold, soft, first_frame, hr_threshold=0.01):
+def nms_track_seg(mean, seg_off, max_len, window, threshold, soft, first_frame, hr_threshold=0.01, planes=False):
     """nms_track per video of a packed track, one launch for the whole group: mean fp32 (sum L,K1), seg_off int32 (nv+1,),
     first_frame int32 (nv,K1) from frame_events_seg with the same hr_threshold; window / threshold / soft as nms_track
     (which is this function on a group of one video).
     Returns device tensors (frames int32, classes uint8, scores float64, event_off int32 (nv+1,), rounds int32 (nv,K1)):
     entries event_off[v]:event_off[v+1] are video v's kept events (video-local frames, nms_track's order), the lists of
-    the videos following each other densely in video order."""
+    the videos following each other densely in video order.
+    planes=True: the dense planes the kernel leaves behind follow as two more entries: emitted uint8 (K1,sum L), non-zero where
+    class c keeps frame f, and kept_score float64 (K1,sum L), that event's score -- what ap_match_seg reads (row 0 is unused)."""
     L, K1 = _chk_track(mean, "nms_track_seg")
     dev = mean.device
     nv = _chk_group(seg_off, dev, "nms_track_seg")
@@ -989,7 +992,139 @@ def nms_track_seg(mean, seg_off, max_len, window, threshold, soft, first_frame, 
     call("tdeed_nms_track_seg", ptr(mean), ptr(seg_off), nv, L, max_len, K1, float(hr_threshold), float(threshold), int(soft),
          warr, len(wins), ptr(first_frame), ptr(ws), ptr(emitted), ptr(kept), ptr(st_i), ptr(st_c), ptr(st_s), ptr(st_i[cap:]),
          ptr(frames), ptr(classes), ptr(scores), ptr(event_off), ptr(rounds), stream_ptr())
+    if planes:
+        return frames, classes, scores, event_off, rounds, emitted, kept
     return frames, classes, scores, event_off, rounds
+
+
+# ---- average precision of the spotted events on the device (ap.hip; evalutil.ap_restated is the written statement)
+def ap_lds_frames():
+    """longest video whose events ap_match_seg orders in LDS (longer ones are ordered in place in the store)"""
+    return int(_lib.load().tdeed_ap_lds_frames())
+
+
+def ap_max_tolerances():
+    return int(_lib.load().tdeed_ap_max_tolerances())
+
+
+def ap_max_truth(n_tol):
+    """ground-truth frames one class may have in one video when n_tol tolerances are scored at once"""
+    return int(_lib.load().tdeed_ap_max_truth(int(n_tol)))
+
+
+def ap_tolerances(tolerances, who="ap_state"):
+    """the tolerance list as ints: 1 .. ap_max_tolerances() whole numbers >= 0 (needs no device)"""
+    tols = list(tolerances)
+    if not 1 <= len(tols) <= ap_max_tolerances():
+        raise ValueError(f"{who}: {len(tols)} tolerances, 1 to {ap_max_tolerances()} are scored at once")
+    if any(int(t_) != t_ or not 0 <= int(t_) < 1 << 31 for t_ in tols):
+        raise ValueError(f"{who}: tolerances {tols} must be whole numbers of frames >= 0")
+    return [int(t_) for t_ in tols]
+
+
+class ApState:
+    """The device side of one mAP pass over a dataset (ap_state builds it): the tables of the videos and the truth, the
+    ordered predictions of every (entry, class, video) and the hits of every (entry, tolerance, class, video)."""
+
+
+def ap_state(lengths, truth, K1, n_entries, tolerances, device="cuda"):
+    """lengths: frames of every video in ORDINAL order (the index of the video's name in sorted order); truth: {(ordinal,
+    class index): [ground-truth frames in the truth record's list order, duplicates kept]}, classes 1 .. K1-1; n_entries:
+    event lists scored side by side (the suppress entries); tolerances: in frames.  Uploads the tables once and allocates the
+    stores ap_match_seg fills group by group: 12 bytes per frame, class and entry for the ordered predictions, 4 bytes per
+    ground-truth frame, tolerance and entry for the hits."""
+    tols = ap_tolerances(tolerances)
+    lengths = [int(x) for x in lengths]
+    NV, K1, E, T = len(lengths), int(K1), int(n_entries), len(tols)
+    if NV < 1 or min(lengths) < 1 or sum(lengths) >= 1 << 31 or not 2 <= K1 <= 256 or E < 1 or NV * K1 >= 1 << 31:
+        raise ValueError(f"ap_state: {NV} videos of {sum(lengths)} frames, {K1} columns, {E} entries")
+    gt_off = np.zeros(NV * K1 + 1, np.int64)
+    for (o, c), fr in truth.items():
+        if not (0 <= int(o) < NV and 1 <= int(c) < K1):
+            raise ValueError(f"ap_state: truth for video {o}, class {c} outside {NV} videos and the classes 1..{K1 - 1}")
+        if any(int(f) != f or not 0 <= int(f) < 1 << 31 for f in fr):
+            raise ValueError(f"ap_state: the ground-truth frames of video {o}, class {c} must be whole numbers >= 0")
+        gt_off[int(o) * K1 + int(c) + 1] = len(fr)
+    max_gt = int(gt_off.max())
+    if max_gt > ap_max_truth(T):
+        raise ValueError(f"ap_state: {max_gt} ground-truth frames of one class in one video, at most {ap_max_truth(T)} with {T} "
+                         "tolerances")
+    per_class = gt_off[1:].reshape(NV, K1).sum(axis=0)
+    gt_off = np.cumsum(gt_off)
+    G = int(gt_off[-1])
+    if G >= 1 << 31:
+        raise ValueError(f"ap_state: {G} ground-truth frames")
+    frames = np.zeros(max(G, 1), np.int32)
+    for (o, c), fr in truth.items():
+        a = int(gt_off[int(o) * K1 + int(c)])
+        frames[a:a + len(fr)] = np.asarray(fr, np.int64)
+    st = ApState()
+    st.NV, st.K1, st.E, st.T, st.G, st.max_gt, st.tolerances, st.lengths = NV, K1, E, T, G, max_gt, tols, lengths
+    st.LT = sum(lengths)
+    st.totals = [int(x) for x in per_class]
+    st.vid_off_host = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(device)
+    st.vid_off, st.gt_off, st.gt_frames = up(st.vid_off_host), up(gt_off), up(frames)
+    st.class_off = up(np.concatenate([[0], np.cumsum(per_class)]))
+    dev = st.vid_off.device
+    st.device = dev
+    Gb = max(G, 1)
+    st.ev_score = torch.empty((E, K1 - 1, st.LT), dtype=torch.float64, device=dev)
+    st.ev_frame = torch.empty((E, K1 - 1, st.LT), dtype=torch.int32, device=dev)
+    st.ev_count = torch.zeros((E, K1 - 1, NV), dtype=torch.int32, device=dev)
+    st.hit_pos = torch.zeros((E, T, Gb), dtype=torch.int32, device=dev)
+    st.hit_count = torch.zeros((E, T, NV * K1), dtype=torch.int32, device=dev)
+    return st
+
+
+def ap_match_seg(state, entry, mean, seg_off, ords, max_len, hr_threshold=0.01, planes=None):
+    """Segment + match for one entry of one group of videos: mean fp32 (sum L,K1) the group's packed track, seg_off int32
+    (nv+1,), ords int32 (nv,) the videos' ordinals in the dataset of `state`, all on the state's device; max_len the longest
+    video (a host number).  planes=None: the raw high-recall list (mean[f,c] >= float32(hr_threshold), score
+    float64(mean[f,c])); planes=(emitted, kept_score) of nms_track_seg(..., planes=True): that suppression's list.  Fills the
+    state's stores for these videos (the launch is asynchronous on the current stream); nothing is returned."""
+    if not isinstance(state, ApState):
+        raise TypeError("ap_match_seg: state must come from ap_state")
+    L, K1 = _chk_track(mean, "ap_match_seg")
+    dev = mean.device
+    nv = _chk_group(seg_off, dev, "ap_match_seg")
+    _chk_table(ords, nv, dev, "ap_match_seg", "ords")
+    max_len, entry = int(max_len), int(entry)
+    if K1 != state.K1 or dev != state.device:
+        raise ValueError(f"ap_match_seg: a track of {K1} columns on {dev} for a state of {state.K1} columns on {state.device}")
+    if not 1 <= max_len <= L or L > state.LT or nv > state.NV:
+        raise ValueError(f"ap_match_seg: max_len {max_len}, {L} packed frames, {nv} videos for a dataset of {state.LT} / {state.NV}")
+    if not 0 <= entry < state.E:
+        raise ValueError(f"ap_match_seg: entry {entry} of {state.E}")
+    em = ks = None
+    if planes is not None:
+        em, ks = planes
+        if em.dtype != torch.uint8 or ks.dtype != torch.float64 or tuple(em.shape) != (K1, L) or tuple(ks.shape) != (K1, L) \
+                or not (em.is_contiguous() and ks.is_contiguous()) or em.device != dev or ks.device != dev:
+            raise ValueError("ap_match_seg: planes are (emitted uint8 (K1,L), kept_score float64 (K1,L)), contiguous, on the track's device")
+    tarr = (ctypes.c_int * state.T)(*state.tolerances)
+    call("tdeed_ap_match_seg", ptr(mean), ptr(em), ptr(ks), ptr(seg_off), nv, L, max_len, K1, float(hr_threshold), ptr(ords),
+         state.NV, ptr(state.vid_off), state.LT, ptr(state.gt_off), ptr(state.gt_frames), state.G, state.max_gt, tarr, state.T,
+         ptr(state.ev_score[entry]), ptr(state.ev_frame[entry]), ptr(state.ev_count[entry]), ptr(state.hit_pos[entry]),
+         ptr(state.hit_count[entry]), stream_ptr())
+
+
+def ap_rank(state):
+    """Rank + AP once every video of the state's dataset went through ap_match_seg for every entry -> device tensors (ap
+    float64 (entries, tolerances, K1): the interpolated average precision per class, column 0 and classes without truth 0;
+    nhits int32 of that shape; rank int32 (entries, tolerances, max(G,1)): per hit, in the truth table's layout, its 1-based
+    position among the class's predictions of all videos)."""
+    if not isinstance(state, ApState):
+        raise TypeError("ap_rank: state must come from ap_state")
+    E, T, K1, dev = state.E, state.T, state.K1, state.device
+    rank = torch.zeros((E, T, max(state.G, 1)), dtype=torch.int32, device=dev)
+    psorted = torch.empty((E, T, max(state.G, 1)), dtype=torch.float64, device=dev)
+    ap = torch.empty((E, T, K1), dtype=torch.float64, device=dev)
+    nhits = torch.empty((E, T, K1), dtype=torch.int32, device=dev)
+    call("tdeed_ap_rank", ptr(state.ev_score), ptr(state.ev_count), ptr(state.vid_off), state.NV, state.LT, ptr(state.gt_off),
+         state.G, K1, E, T, ptr(state.hit_pos), ptr(state.hit_count), ptr(state.class_off), ptr(rank), ptr(psorted), ptr(ap),
+         ptr(nhits), stream_ptr())
+    return ap, nhits, rank
 
 
 def cast_bf16(src_f32):

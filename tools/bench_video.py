@@ -11,6 +11,9 @@
                                                                         spot_video, one JSON line
     python tools/bench_video.py --group [--group-videos 32]             short videos: spot_videos video by video against
                                                                         spot_videos in packed groups, one JSON line
+    python tools/bench_video.py --map [--map-videos 24]                 validation mAP: spot_videos + mean_average_precisions
+                                                                        against map_videos, one JSON line, also written to
+                                                                        profiles/video_map.json
     python tools/bench_video.py --reuse [--frames 2030]                 predict_video against predict_video(reuse_frames=
                                                                         True), one JSON line, also written to --out
 
@@ -332,6 +335,165 @@ def group(a):
     return 0
 
 
+def map_bench(a):
+    """Two routes from the same synthetic videos and model to the mAP tables of a validation pass, alternating: (a)
+    `evalutil.spot_videos` + `mean_average_precisions` per suppress entry (event lists to the host, dicts, the Python walk),
+    (b) `evalutil.map_videos` (segment + match per group and one rank + AP launch on the device, one small table back).  Per
+    route: wall time over `--repeats` passes, host synchronisations and device-to-host bytes of one pass.  The two results
+    must agree within max(1, total) * 2^-52 per AP (summation order).  No speed-up is promised: route (a)'s time on the same
+    box in the same run is what route (b) is read against."""
+    from tdeed_amd.model import TDEEDModel
+    from types import SimpleNamespace
+    m = TDEEDModel(device="cuda", args=SimpleNamespace(modality="rgb", temporal_arch="ed_sgp_mixer", pretrain=None, **CFG))
+    m.load({k: torch.from_numpy(v) for k, v in synth.make_state(state_layout.model_state_shapes(CFG), 0).items()})
+    K = CFG["num_classes"]
+    classes = {f"c{k}": k for k in range(1, K + 1)}
+    suppress = (("nms", 1, 0.10), ("snms", 3, 0.01))
+    tols = [0, 1, 2, 4, 8]
+    lengths = group_lengths("diving")[:a.map_videos]
+    off = np.concatenate([[0], np.cumsum(lengths)])
+    packed = torch.empty((int(off[-1]), 3, H, W), dtype=torch.uint8).pin_memory()
+    for lo in range(0, int(off[-1]), 2048):
+        hi = min(lo + 2048, int(off[-1]))
+        packed[lo:hi].copy_(ops.fill_u8_hash((hi - lo, 3, H, W), 9 + lo, "cuda"))
+    vids = [(f"v{i:03d}", L, 25.0, packed[off[i]:off[i + 1]]) for i, L in enumerate(lengths)]
+    # a ground-truth event every 20 frames, the classes in turn
+    truth = [{"video": f"v{i:03d}", "events": [{"label": f"c{1 + (f // 20) % K}", "frame": f} for f in range(7, L, 20)]}
+             for i, L in enumerate(lengths)]
+    totals = {lab: sum(1 for x in truth for e in x["events"] if e["label"] == lab) for lab in classes}
+    seen = dict(syncs=0, d2h=0)
+    real_sync, real_group = torch.cuda.Stream.synchronize, m.spot_video_group
+
+    def sync(self):
+        seen["syncs"] += 1
+        return real_sync(self)
+
+    def spot_group(*args, **kw):
+        r = real_group(*args, **kw)
+        seen["d2h"] += m.last_video_stats["events_d2h_bytes"]
+        return r
+    torch.cuda.Stream.synchronize = sync
+    m.spot_video_group = spot_group
+    kw = dict(batch_size=8, group_videos=a.group_videos)
+
+    def route_a():
+        _, lists, _ = E.spot_videos(m, vids, classes, suppress, **kw)
+        seen["events"] = [sum(len(x["events"]) for x in lst) for lst in lists]
+        return [E.mean_average_precisions(truth, lst, tols) for lst in lists]
+
+    def route_b():
+        r = E.map_videos(m, vids, classes, truth, suppress, tols, **kw)
+        seen["d2h"] += m.last_video_stats["ap_d2h_bytes"]
+        return r
+    routes = dict(a_spot_videos_host_map=route_a, b_map_videos=route_b)
+    res, counts = {}, {}
+    for k, fn in routes.items():                                        # warm-up of every shape; the second pass is counted
+        fn()
+        seen.update(syncs=0, d2h=0)
+        res[k] = fn()
+        counts[k] = dict(host_syncs=seen["syncs"], d2h_bytes=seen["d2h"])
+    times = {k: [] for k in routes}
+    for _ in range(a.repeats):
+        for k, fn in routes.items():                                    # alternating
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            times[k].append(time.perf_counter() - t0)
+    torch.cuda.Stream.synchronize = real_sync
+    worst, ok = 0.0, True
+    for (_, aps_a), (_, aps_b) in zip(res["a_spot_videos_host_map"], res["b_map_videos"]):
+        ok = ok and sorted(aps_a) == sorted(aps_b)
+        for lab in aps_a:
+            for x, y in zip(aps_a[lab], aps_b.get(lab, [])):
+                worst = max(worst, abs(x - y))
+                ok = ok and abs(x - y) <= max(1, totals[lab]) * 2.0 ** -52
+    st = {}
+    for k, v in times.items():
+        tt = np.asarray(v)
+        st[k] = dict(ms_median=round(float(np.median(tt)) * 1e3, 2), ms_min=round(float(tt.min()) * 1e3, 2),
+                     ms_max=round(float(tt.max()) * 1e3, 2), **counts[k])
+    rec = dict(kind="video_map", device=torch.cuda.get_device_name(0), measured_on_gpu=True, cfg=CFG, videos=len(lengths),
+               frames=int(off[-1]), group_videos=a.group_videos, batch_size=8, repeats=a.repeats, suppress=suppress, tolerances=tols,
+               truth_events=totals, events_after_suppression=seen.get("events"), routes=st,
+               ratio_a_over_b=round(st["a_spot_videos_host_map"]["ms_median"] / st["b_map_videos"]["ms_median"], 3),
+               maps_a=[r[0] for r in res["a_spot_videos_host_map"]], maps_b=[r[0] for r in res["b_map_videos"]],
+               max_abs_ap_diff=worst, agree_within_bound=bool(ok))
+    if a.map_tail_videos:
+        rec["tail_noise"] = _map_tail(a, tols)
+        ok = ok and rec["tail_noise"]["agree_within_bound"]
+    out = os.path.join(ROOT, "profiles", "video_map.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rec))
+    assert ok, f"the two routes differ (model route by {worst})"
+    return 0
+
+
+def _map_tail(a, tols):
+    """The tail alone at validation-set size, no model: `--map-tail-videos` noise tracks of 3 000 frames with K = 12 (noise
+    gives far more high-recall events than a trained model: the upper end), entries raw and ("nms", 1, 0.10).  Host: the
+    event records (raw: `evalutil.frame_events`; NMS: the device suppression's lists copied back and turned into dicts, as
+    `spot_videos` does) and `mean_average_precisions`, one pass, each step timed.  Device: tables, event launch, suppression,
+    segment + match, rank + AP and the copy of the table, `--repeats` passes."""
+    nv, L, K1, hr = a.map_tail_videos, 3000, 13, 0.01
+    rng = np.random.RandomState(1)
+    tracks = []
+    for _ in range(nv):
+        x = rng.rand(L, K1).astype(np.float32)
+        tracks.append(np.ascontiguousarray(x / x.sum(axis=1, keepdims=True), np.float32))
+    names = [f"t{i:03d}" for i in range(nv)]
+    classes = {f"c{k}": k for k in range(1, K1)}
+    inv = {v: k for k, v in classes.items()}
+    truth = [{"video": v, "events": [{"label": f"c{1 + (f // 20) % (K1 - 1)}", "frame": f} for f in range(7, L, 20)]} for v in names]
+    totals = {lab: sum(1 for x in truth for e in x["events"] if e["label"] == lab) for lab in classes}
+    entries = (("raw",), ("nms", 1, 0.10))
+    table = E.truth_table(truth, {v: i for i, v in enumerate(names)}, classes)
+    mean = torch.from_numpy(np.concatenate(tracks)).cuda()
+    seg_off = torch.tensor(np.arange(nv + 1) * L, dtype=torch.int32, device="cuda")
+    ords = torch.arange(nv, dtype=torch.int32, device="cuda")
+
+    def device():
+        state = ops.ap_state([L] * nv, table, K1, len(entries), tols, "cuda")
+        first = ops.frame_events_seg(mean, seg_off, L, hr)[2]
+        for i, e in enumerate(entries):
+            planes = None if e[0] == "raw" else ops.nms_track_seg(mean, seg_off, L, e[1], e[2], e[0] == "snms", first, hr,
+                                                                  planes=True)[5:]
+            ops.ap_match_seg(state, i, mean, seg_off, ords, L, hr, planes=planes)
+        return ops.ap_rank(state)[0].cpu().numpy()                      # synchronises
+    ap = device()
+    dev_ms = _median_ms(device, a.repeats)
+    host = {}
+    t0 = time.perf_counter()
+    raw = E.frame_events({v: m_ for v, m_ in zip(names, tracks)}, classes, {v: 25.0 for v in names}, high_recall_score_threshold=hr)[1]
+    host["raw_records_s"] = round(time.perf_counter() - t0, 3)
+    t0 = time.perf_counter()
+    first = ops.frame_events_seg(mean, seg_off, L, hr)[2]
+    fr, c8, sc, eoff, _ = ops.nms_track_seg(mean, seg_off, L, 1, 0.10, False, first, hr)
+    eo = eoff.cpu().numpy()
+    fr, c8, sc = fr[:eo[-1]].cpu().numpy(), c8[:eo[-1]].cpu().numpy(), sc[:eo[-1]].cpu().numpy()
+    nms = [{"video": v, "events": E.event_dicts(fr[eo[i]:eo[i + 1]], c8[eo[i]:eo[i + 1]], sc[eo[i]:eo[i + 1]], inv)}
+           for i, v in enumerate(names)]
+    host["nms_device_suppression_copy_records_s"] = round(time.perf_counter() - t0, 3)
+    worst, ok, maps = 0.0, True, []
+    for i, (key, lst) in enumerate((("raw", raw), ("nms", nms))):
+        t0 = time.perf_counter()
+        m_, aps = E.mean_average_precisions(truth, lst, tols)
+        host[f"{key}_mean_average_precisions_s"] = round(time.perf_counter() - t0, 3)
+        host[f"{key}_events"] = sum(len(x["events"]) for x in lst)
+        maps.append(m_)
+        for lab in aps:
+            for ti in range(len(tols)):
+                d = abs(aps[lab][ti] - float(ap[i, ti, classes[lab]]))
+                worst = max(worst, d)
+                ok = ok and d <= max(1, totals[lab]) * 2.0 ** -52
+    return dict(videos=nv, frames_per_video=L, K1=K1, entries=entries, tolerances=tols, truth_events=sum(totals.values()),
+                host_one_pass=host, host_total_s=round(sum(v for k, v in host.items() if k.endswith("_s")), 3),
+                device_ms_median=dev_ms, d2h_bytes_device=int(ap.size) * 8, maps_host=maps, max_abs_ap_diff=worst,
+                agree_within_bound=bool(ok))
+
+
 def reuse(a):
     """Two routes over the same video, alternating: predict_video(batch_size=8) as it is, and with reuse_frames=True (stem and
     the blocks in front of the first gate-shift site once per frame instead of once per clip window).  Plain and augmented
@@ -528,6 +690,9 @@ if __name__ == "__main__":
     ap.add_argument("--frames", type=int, default=None, help="default 2030, with --spot 5625")
     ap.add_argument("--spot", action="store_true")
     ap.add_argument("--group", action="store_true")
+    ap.add_argument("--map", action="store_true", help="spot_videos + mean_average_precisions against map_videos")
+    ap.add_argument("--map-videos", type=int, default=24, help="--map: videos of the synthetic diving split")
+    ap.add_argument("--map-tail-videos", type=int, default=40, help="--map: noise tracks of the tail-only measurement (0: skip it)")
     ap.add_argument("--reuse", action="store_true", help="predict_video against predict_video(reuse_frames=True)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "video_frame_reuse.json"), help="--reuse: where the JSON goes")
     ap.add_argument("--group-videos", type=int, default=32, help="--group: videos per packed group of route B")
@@ -542,5 +707,5 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if a.frames is None:
         a.frames = 5625 if a.spot else 2030
-    sys.exit(decode_device(a) if a.decode_device else decode(a) if a.decode else gather_only(a) if a.gather_only else reuse(a) if a.reuse else group(a) if a.group
+    sys.exit(map_bench(a) if a.map else decode_device(a) if a.decode_device else decode(a) if a.decode else gather_only(a) if a.gather_only else reuse(a) if a.reuse else group(a) if a.group
              else spot(a) if a.spot else bench(a))
