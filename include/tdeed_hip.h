@@ -214,19 +214,21 @@ int tdeed_c1_gconv_workgroups(int N, int Hi, int Wi, int Cin, int C, int stride)
  * xs2 optional [N][ceil(Hi/2)][ceil(Wi/2)][Cp]: the producer's output at even rows and columns (what the block's shortcut
  * conv reads).  The rest as tdeed_c1_gconv_fwd with Cin = Cp, stride 2.  Bit-identical to tdeed_gemm_ws_fwd (a_scale = gate,
  * R = scp, ReLU) followed by tdeed_c1_gconv_fwd; the producer's output map never exists.
- * tdeed_c1_gconv_c3in_fits: Cp in 8..32, C <= 64 (one channel slab) and tdeed_c1_gconv_fits(Hi, Wi, Cp, C, 2). */
+ * tdeed_c1_gconv_c3in_fits: Cp in 8..32, C <= 64 (one channel slab), tdeed_c1_gconv_fits(Hi, Wi, Cp, C, 2), and a frame of the
+ * operands below 2^31 bytes (Hi * Wi * Cp * 2: the kernel addresses a frame with 32-bit byte offsets). */
 int tdeed_c1_gconv_c3in_fits(int Hi, int Wi, int Cp, int C);
 int tdeed_c1_gconv_c3in_fwd(const void* y2p, const void* scp, const float* gate, const void* w3f, const float* s3,
                             const float* h3, void* xs2, int N, int Hi, int Wi, int Cp, int C, int gw, const void* w1f,
                             const float* s1, const float* h1, const void* wfrag, const float* scale, const float* shift,
                             void* y, float* pooled, void* stream);
-/* tdeed_c1_gconv_c3in_fwd has two forms with the same bits: one workgroup per (frame, band), and the band walk -- one
- * workgroup per (frame, run of `walk` consecutive bands) that runs the prologue once per run, copies the input row two
- * adjacent bands share inside LDS instead of computing it twice, and requests the next band's operands under the grouped conv.
- * tdeed_c1_gconv_c3in_walk: the routed run length for the shape (1: the per-band form; a function of the shape alone, never of
- * N; 0: not served).  tdeed_c1_gconv_c3in_set_walk (tests, tools): 0 as routed (default), 1 the per-band form, k >= 2 runs of
- * k bands (clamped to the frame's band count); a negative value is an error.  tdeed_c1_gconv_c3in_workgroups: the grid of
- * tdeed_c1_gconv_c3in_fwd for N frames under the form in force (0: not served). */
+/* tdeed_c1_gconv_c3in_fwd is one kernel, the band walk: one workgroup per (frame, run of `walk` consecutive bands) that runs
+ * the prologue once per run, copies the input row two adjacent bands share inside LDS instead of computing it twice, and
+ * requests the next band's operands under the grouped conv.  The bits are the same at every run length.
+ * tdeed_c1_gconv_c3in_walk: the routed run length for the shape (at most the frame's band count; a function of the shape
+ * alone, never of N; 0: not served).  tdeed_c1_gconv_c3in_set_walk (tests, tools): 0 as routed (default), k >= 1 runs of k
+ * bands (clamped to the frame's band count; 1: runs of one band, a workgroup per (frame, band)); a negative value is an
+ * error.  tdeed_c1_gconv_c3in_workgroups: the grid of tdeed_c1_gconv_c3in_fwd for N frames under the run length in force (0:
+ * not served). */
 int tdeed_c1_gconv_c3in_set_walk(int walk);
 int tdeed_c1_gconv_c3in_walk(int Hi, int Wi, int Cp, int C);
 int tdeed_c1_gconv_c3in_workgroups(int N, int Hi, int Wi, int Cp, int C);

@@ -149,7 +149,7 @@ def c1_gconv_slab_loop_fits(Hi, Wi, Cin, C, stride):
 
 
 def c1_gconv_set_form(form):
-    """-1: c1_gconv's form as routed per instance (default); 0: per slab everywhere; 1: the slab loop wherever it fits."""
+    """-1: c1_gconv's form as routed (default: the slab loop wherever it fits); 0: per slab everywhere; 1: the same as -1."""
     call("tdeed_c1_gconv_set_form", form)
 
 
@@ -178,7 +178,8 @@ def c1_gconv(x, w1f, s1, h1, wfrag, scale, shift, gw, stride, C, G=None, out=Non
 
 
 def c1_gconv_c3in_fits(Hi, Wi, Cp, C):
-    """True when c1_gconv_c3in() serves a stride-2 block of Cp -> C channels behind a producer conv3 of Cp -> Cp."""
+    """True when c1_gconv_c3in() serves a stride-2 block of Cp -> C channels behind a producer conv3 of Cp -> Cp (one channel
+    slab, the band fits LDS, a frame of the operands below 2^31 bytes)."""
     lib = _lib.load()
     if not hasattr(lib, "tdeed_c1_gconv_c3in_fits"):    # an A/B flavour of the library built from an older revision
         return False
@@ -186,13 +187,13 @@ def c1_gconv_c3in_fits(Hi, Wi, Cp, C):
 
 
 def c1_gconv_c3in_set_walk(walk):
-    """0: the run length of c1_gconv_c3in's band walk as routed per shape (default); 1: one workgroup per (frame, band);
-    k >= 2: one workgroup per (frame, run of k bands), clamped to the frame's band count."""
+    """0: the run length of c1_gconv_c3in's band walk as routed per shape (default); k >= 1: one workgroup per (frame, run
+    of k bands), clamped to the frame's band count (1: runs of one band).  The same kernel and the same bits at every k."""
     call("tdeed_c1_gconv_c3in_set_walk", walk)
 
 
 def c1_gconv_c3in_walk(Hi, Wi, Cp, C):
-    """the routed run length of c1_gconv_c3in for the shape (1: the per-band kernel)"""
+    """the routed run length of c1_gconv_c3in for the shape (at most the frame's band count; 0: the shape is not served)"""
     return _lib.load().tdeed_c1_gconv_c3in_walk(Hi, Wi, Cp, C)
 
 

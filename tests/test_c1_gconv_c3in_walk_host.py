@@ -1,5 +1,6 @@
 """The band walk of the conv3-in c1_gconv launch without a GPU: the override's argument checking, the routed run length and
-the grid per shape (never a function of N), the new kernel's registers, and cfg2's plan, which no walk setting changes."""
+the grid per shape (never a function of N), the kernels' registers, and cfg2's plan, which no walk setting changes."""
+import functools
 import os
 import re
 
@@ -12,6 +13,11 @@ from test_s1_conv3_in_c1g_plan import _plan, _cost
 # (Hi, Wi, Cp, C) -> bands per frame
 SHAPES = {(19, 56, 24, 56): 5, (18, 56, 24, 56): 5, (10, 56, 24, 56): 3, (15, 13, 24, 56): 1, (12, 20, 32, 64): 1,
           (8, 6, 8, 32): 1, (56, 56, 24, 56): 14}
+
+
+@functools.lru_cache(maxsize=None)
+def _conv_usage():
+    return _resource_usage("conv.hip")                      # (one compile for the tests that read it)
 
 
 @pytest.fixture(scope="module")
@@ -77,15 +83,58 @@ def test_shapes_the_form_does_not_serve(lib):
         assert ops.c1_gconv_c3in_walk(*shape) == 0 and ops.c1_gconv_c3in_workgroups(8, *shape) == 0
 
 
+def test_a_frame_of_two_gib_is_not_served(lib):
+    """the kernel addresses a frame with 32-bit byte offsets: from 2^31 bytes per frame on the form does not fit (the engine
+    then runs the chain), at every run length setting.  Host calls only: nothing is allocated."""
+    from tdeed_amd import ops
+    shape = (600000, 56, 32, 64)
+    assert shape[0] * shape[1] * shape[2] * 2 >= 2 ** 31
+    for walk in (0, 1, 5):
+        ops.c1_gconv_c3in_set_walk(walk)
+        assert not ops.c1_gconv_c3in_fits(*shape)
+        assert ops.c1_gconv_c3in_walk(*shape) == 0
+        assert ops.c1_gconv_c3in_workgroups(1, *shape) == 0 and ops.c1_gconv_c3in_workgroups(800, *shape) == 0
+    # the last row count below the limit is served
+    below = ((2 ** 31 - 1) // (56 * 32 * 2), 56, 32, 64)
+    assert below[0] * below[1] * below[2] * 2 < 2 ** 31 and ops.c1_gconv_c3in_fits(*below)
+    assert ops.c1_gconv_c3in_walk(*below) == 5
+
+
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_the_walk_kernel_keeps_three_workgroups_per_cu_without_scratch():
-    use = _resource_usage("conv.hip")
+    use = _conv_usage()
     inst = {int(m.group(1)): u for k, u in use.items() for m in [re.search(r"c1_gconv_c3in_walk_kernelILi(\d+)E", k)] if m}
     assert sorted(inst) == [16, 32, 64], sorted(use)
     assert not any("c1_gconv_mfma_kernel" in k for k in use if "c3in_walk" in k)
     for csp, u in inst.items():
         # 12 waves per CU (three workgroups of four, 42 KB band + 8 KB static LDS each): at most 168 registers, nothing in scratch
         assert u["scratch"] == 0 and u["vgpr"] <= 168, (csp, u)
+
+
+# VGPRs and scratch bytes per lane of the c1_gconv kernels at the commit before the conv3-in kernels became one (the same helper
+# on that commit's conv.hip): (kernel, template arguments) -> (VGPRs, scratch).  No kernel may need more.
+BEFORE = {("c1_gconv_mfma_kernel", (1, 1)): (127, 0), ("c1_gconv_mfma_kernel", (1, 2)): (157, 0),
+          ("c1_gconv_mfma_kernel", (1, 4)): (168, 0), ("c1_gconv_mfma_kernel", (1, 5)): (147, 0),
+          ("c1_gconv_mfma_kernel", (2, 1)): (127, 0), ("c1_gconv_mfma_kernel", (2, 2)): (157, 0),
+          ("c1_gconv_mfma_kernel", (2, 4)): (168, 0), ("c1_gconv_mfma_kernel", (2, 5)): (147, 0),
+          ("c1_gconv_slab_loop_kernel", (2, 2)): (168, 0), ("c1_gconv_slab_loop_kernel", (2, 5)): (242, 0),
+          ("c1_gconv_c3in_walk_kernel", (16,)): (130, 0), ("c1_gconv_c3in_walk_kernel", (32,)): (160, 0),
+          ("c1_gconv_c3in_walk_kernel", (64,)): (167, 0)}
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_one_conv3_in_kernel_and_no_c1_gconv_kernel_needs_more_registers():
+    use = _conv_usage()
+    inst = {}
+    for k, u in use.items():
+        m = re.match(r"_Z\d+(c1_gconv_\w+?_kernel)I((?:L[ib]\d+E)+)Ev", k)
+        if m:
+            inst[(m.group(1), tuple(int(a) for a in re.findall(r"L[ib](\d+)E", m.group(2))))] = u
+    mfma = sorted(a for n, a in inst if n == "c1_gconv_mfma_kernel")
+    assert mfma == [(s, k) for s in (1, 2) for k in (1, 2, 4, 5)], mfma     # eight, none with a third template argument
+    assert sorted(inst) == sorted(BEFORE), sorted(inst)
+    for key, (vgpr, scratch) in BEFORE.items():
+        assert inst[key]["vgpr"] <= vgpr and inst[key]["scratch"] <= scratch, (key, inst[key])
 
 
 def test_cfg2_plan_is_the_same_under_every_walk_setting(lib, monkeypatch):

@@ -1,7 +1,8 @@
 """The band walk of the conv3-in c1_gconv launch (c1_gconv_c3in_walk_kernel, tdeed_c1_gconv_c3in_set_walk): a workgroup that
-owns a run of bands of a frame gives the bits of the per-band kernel, of the two launches that kernel replaced and of the
-stride-2 pixels of the map nobody writes -- at every run length, at the shapes where the walk can go wrong (a re-zeroed bottom
-row, a short last band, an odd frame count, one band), and over a whole forward.  -m gpu only."""
+owns a run of bands of a frame gives the bits of a workgroup per band (runs of one band: the same kernel since the per-band
+kernel left), of the two launches the form replaced -- the independent reference -- and of the stride-2 pixels of the map
+nobody writes -- at every run length, 1 included, at the shapes where the walk can go wrong (a re-zeroed bottom row, a short
+last band, an odd frame count, one band), and over a whole forward.  -m gpu only."""
 import numpy as np
 import pytest
 import torch
@@ -17,7 +18,7 @@ BF = torch.bfloat16
 CASES = [(19, 56, 24, 56, 8, 2, 5),    # five bands, the last one's bottom row outside the map (the re-zero)
          (18, 56, 24, 56, 8, 2, 5),    # five bands, the last of one output row (short last band, compact-row ownership)
          (10, 56, 24, 56, 8, 3, 3),    # three bands, an odd frame count
-         (15, 13, 24, 56, 8, 2, 1),    # one band: the walk degenerates to the per-band kernel
+         (15, 13, 24, 56, 8, 2, 1),    # one band: a run of one band at every setting
          (12, 20, 32, 64, 16, 2, 1),
          (8, 6, 8, 32, 8, 2, 1)]
 SENTINEL = -7.0                        # every defined output is behind a ReLU
@@ -65,7 +66,7 @@ def test_every_run_length_gives_the_bits_of_the_per_band_kernel_and_of_the_chain
     s2, h2 = _fold(seed, "2", C)
     w1f = pack_mfma_frags(W1, DEV, rows=16 * ops.c1_gconv_slab_tiles(Hi, Wi, C, 2))
     w2f = pack_gconv_frags(W2, gw, DEV)
-    # the references, once: the chain, the stride-2 pixels of its map, the per-band launch
+    # the references, once: the chain, the stride-2 pixels of its map, the launch in runs of one band
     out = ops.gemm_ws(y2p, W3, Cp, Cp, s3, h3, ops.ACT_RELU, residual=scp, a_scale=gate, a_scale_rows=Hi * Wi).view(N, Hi, Wi, Cp)
     y_ref, p_ref = ops.c1_gconv(out, w1f, s1, h1, w2f, s2, h2, gw, 2, C)
     xs_ref = out[:, ::2, ::2, :].contiguous()
@@ -79,7 +80,7 @@ def test_every_run_length_gives_the_bits_of_the_per_band_kernel_and_of_the_chain
     assert 0.2 < frac < 0.8, frac                                            # conv3's ReLU is neither always open nor shut
     routed = ops.c1_gconv_c3in_walk(Hi, Wi, Cp, C)
     assert 1 <= routed <= bands
-    for walk in sorted({2, 3, bands, routed}) + [0]:                         # (0: as routed, through the default setting)
+    for walk in sorted({1, 2, 3, bands, routed}) + [0]:                      # (0: as routed, through the default setting)
         ops.c1_gconv_c3in_set_walk(walk)
         eff = min(walk if walk else routed, bands)
         assert ops.c1_gconv_c3in_workgroups(N, Hi, Wi, Cp, C) == N * -(-bands // eff), walk

@@ -1,8 +1,8 @@
 """GPU tool: conv1 + grouped 3x3 in one launch (tdeed_c1_gconv_fwd) alone at the shapes of the shipped models, with its phase
 time stamps (tdeed_c1_gconv_set_debug), in both forms (per slab / slab loop) where both exist; then the form that also
 computes the producer's conv3 (tdeed_c1_gconv_c3in_fwd) against the two launches it replaces, at 800 x 56 x 56 x 24 -> 56,
-with the stamps of both; then the band walk of that form (tdeed_c1_gconv_c3in_set_walk): the launch alone at every run length
-of the sweep, with the stamps of a walking workgroup.
+with c1_gconv's stamps; then the band walk, which is that form's one kernel (tdeed_c1_gconv_c3in_set_walk): the launch alone at
+every run length of the sweep, 1 (runs of one band) included, with the stamps of a walking workgroup.
     python tools/bench_c1_gconv.py [--c3in]        (--c3in: only the conv3-in section)"""
 import os
 import sys
@@ -140,20 +140,19 @@ def fused():
 
 HAS_WALK = hasattr(_lib.load(), "tdeed_c1_gconv_c3in_set_walk")     # (not in an A/B flavour built from an older revision)
 if HAS_WALK:
-    ops.c1_gconv_c3in_set_walk(1)
+    ops.c1_gconv_c3in_set_walk(1)                                   # runs of one band
 t3, tc, tch, tf = timeit(conv3), timeit(c1g), timeit(chain), timeit(fused)
 same = torch.equal(out, out_f) and torch.equal(pooled, pooled_f) and torch.equal(xs2, mid[:, ::2, ::2, :])
 print(f"conv3 in front of conv1, N={N} {Hi}x{Hi} {Cp}->{C}: conv3 alone {t3:.1f} us, c1_gconv alone {tc:.1f} us, the two back to back "
       f"{tch:.1f} us, fused {tf:.1f} us; outputs identical: {same}")
-for label, run in (("c1_gconv", c1g), ("fused   ", fused)):
-    ph, wg = stamped(run, N * parts)
-    print(f"  {label} workgroup median {wg:.2f} us: " + ", ".join(f"{n_} {v:.2f}" for n_, v in zip(PHASES, ph)), flush=True)
+ph, wg = stamped(c1g, N * parts)
+print(f"  c1_gconv workgroup median {wg:.2f} us: " + ", ".join(f"{n_} {v:.2f}" for n_, v in zip(PHASES, ph)), flush=True)
 
 
 # ---- the band walk: one workgroup per (frame, run of `walk` bands).  The launch alone per run length (event timing, three
-# rounds interleaved over the run lengths so that a drift of the box hits all of them), outputs against the per-band form, and
+# rounds interleaved over the run lengths so that a drift of the box hits all of them), outputs against runs of one band, and
 # the stamps of a walking workgroup: 0 start, 1 prologue end, 2 / 3 the first band's conv3 + conv1 and grouped conv (with the row
-# copy and the barrier behind it), 4 / 5 the second band's, 6 run end
+# copy and the barrier behind it), 4 / 5 the second band's (runs of two bands or more), 6 run end
 if HAS_WALK:
     WALK_PHASES = ["prologue", "first band conv3 + conv1", "first band grouped conv + row copy", "second band conv3 + conv1",
                    "second band grouped conv + row copy", "the other bands"]
@@ -174,9 +173,9 @@ if HAS_WALK:
         torch.cuda.synchronize()
         same = torch.equal(out_f, ref[0]) and torch.equal(pooled_f, ref[1]) and torch.equal(xs2, ref[2])
         line = (f"  walk {w:2d}: {nwg:5d} workgroups, " + " / ".join(f"{t_:.1f}" for t_ in times[w])
-                + f" us per launch (median {float(np.median(times[w])):.1f}); identical to walk 1: {same}")
-        if w >= 2:
-            ph, wg = stamped(fused, nwg)
-            line += f"; workgroup median {wg:.2f} us: " + ", ".join(f"{n_} {v:.2f}" for n_, v in zip(WALK_PHASES, ph))
+                + f" us per launch (median {float(np.median(times[w])):.1f}); identical to runs of one band: {same}")
+        ph, wg = stamped(fused, nwg)
+        names = WALK_PHASES if w >= 2 else WALK_PHASES[:3]          # (runs of one band: no second band's stamps)
+        line += f"; workgroup median {wg:.2f} us: " + ", ".join(f"{n_} {v:.2f}" for n_, v in zip(names, ph))
         print(line, flush=True)
     ops.c1_gconv_c3in_set_walk(0)
