@@ -457,6 +457,12 @@ int tdeed_clip_gather_u8(const uint8_t* video, int L, long frame_bytes, const in
  * window is cut at the ends of the clip's OWN video.  Forms and limits of tdeed_clip_gather_u8. */
 int tdeed_clip_gather_seg_u8(const uint8_t* video, int L_total, long frame_bytes, const int* starts, const int* clip_base,
                              const int* clip_len_v, int B, int T, uint8_t* clips_out, void* stream);
+/* tdeed_clip_gather_seg_u8 over a VIRTUAL packed buffer of L_total frames of which only a ring of ring_frames rows is on the
+ * device: packed frame p sits in ring[p % ring_frames] (the frame ring of a video longer than the device budget).  Which
+ * frame a slot reads and whether it is padding is decided exactly as by _seg_u8 on the whole buffer.  That every frame a
+ * clip reads is live in the ring when the launch runs (T <= ring_frames, upload order) is the caller's duty. */
+int tdeed_clip_gather_ring_u8(const uint8_t* ring, int ring_frames, int L_total, long frame_bytes, const int* starts,
+                              const int* clip_base, const int* clip_len_v, int B, int T, uint8_t* clips_out, void* stream);
 /* Clip windows of per-frame ROWS: maps [rows][row_bytes] resident on the device (any element type; the trunk map of every
  * frame, computed once), of which the first L (L_total) rows are the frames of the video (the packed group).  out[b][t] =
  * maps[starts[b] + t] when that frame lies inside its video -- 0 <= starts[b] + t < L, or < clip_len_v[b] with the row offset

@@ -186,6 +186,7 @@ _SIGS = {
     "tdeed_fill_u8_hash": ([P, c_long, c_uint64, P], c_int),
     "tdeed_clip_gather_u8": ([P, c_int, c_long, P, c_int, c_int, P, P], c_int),
     "tdeed_clip_gather_seg_u8": ([P, c_int, c_long, P, P, P, c_int, c_int, P, P], c_int),
+    "tdeed_clip_gather_ring_u8": ([P, c_int, c_int, c_long, P, P, P, c_int, c_int, P, P], c_int),
     "tdeed_rows_gather": ([P, c_int, c_long, c_int, c_int, P, c_int, c_int, P, P], c_int),
     "tdeed_rows_gather_seg": ([P, c_int, c_long, c_int, c_int, P, P, P, c_int, c_int, P, P], c_int),
     "tdeed_stitch_scores_seg": ([P, c_int, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, P, P, P, P], c_int),

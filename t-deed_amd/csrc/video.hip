@@ -20,15 +20,25 @@ __device__ __forceinline__ long clip_gather_source(int L, const int* __restrict_
   return f >= 0 && f < clip_len_v[b] && base >= 0 && p < L ? p : -1;
 }
 
-template <bool SEG>
-__global__ __launch_bounds__(256) void clip_gather_v16_kernel(const u32x4* __restrict__ video, int L, long chunks,
+// RING: `video` holds only ring_frames rows of the (virtual) buffer of L frames, frame p in row p % ring_frames -- the frame
+// ring of a video longer than the device budget (feeder.RingUpload).  Which frame a slot reads, and whether it is padding,
+// is decided as for the whole buffer; only the row differs.  The slot is uniform over the workgroup: one 32-bit remainder
+// per workgroup, scalar.  Which rows are live the kernel cannot know: T <= ring_frames and the upload order are the caller's.
+template <bool RING>
+__device__ __forceinline__ long clip_gather_row(long f, int ring_frames) {
+  if (f < 0) return 0;
+  return RING ? (long)((unsigned)f % (unsigned)ring_frames) : f;
+}
+
+template <bool SEG, bool RING>
+__global__ __launch_bounds__(256) void clip_gather_v16_kernel(const u32x4* __restrict__ video, int L, int ring_frames, long chunks,
                                                               const int* __restrict__ starts, const int* __restrict__ clip_base,
                                                               const int* __restrict__ clip_len_v, int T,
                                                               u32x4* __restrict__ out) {
   const int slot = blockIdx.y;
   const long f = clip_gather_source<SEG>(L, starts, clip_base, clip_len_v, T, slot);
   const bool real = f >= 0;
-  const u32x4* src = video + (real ? f : 0) * chunks;
+  const u32x4* src = video + clip_gather_row<RING>(f, ring_frames) * chunks;
   u32x4* dst = out + (long)slot * chunks;
   const u32x4 zero = {0u, 0u, 0u, 0u};
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < chunks; i += (long)gridDim.x * 256)
@@ -36,34 +46,35 @@ __global__ __launch_bounds__(256) void clip_gather_v16_kernel(const u32x4* __res
 }
 
 // frame sizes that are no multiple of 16 bytes (or unaligned buffers)
-template <bool SEG>
-__global__ __launch_bounds__(256) void clip_gather_u8_kernel(const uint8_t* __restrict__ video, int L, long frame_bytes,
-                                                             const int* __restrict__ starts, const int* __restrict__ clip_base,
+template <bool SEG, bool RING>
+__global__ __launch_bounds__(256) void clip_gather_u8_kernel(const uint8_t* __restrict__ video, int L, int ring_frames,
+                                                             long frame_bytes, const int* __restrict__ starts,
+                                                             const int* __restrict__ clip_base,
                                                              const int* __restrict__ clip_len_v, int T,
                                                              uint8_t* __restrict__ out) {
   const int slot = blockIdx.y;
   const long f = clip_gather_source<SEG>(L, starts, clip_base, clip_len_v, T, slot);
   const bool real = f >= 0;
-  const uint8_t* src = video + (real ? f : 0) * frame_bytes;
+  const uint8_t* src = video + clip_gather_row<RING>(f, ring_frames) * frame_bytes;
   uint8_t* dst = out + (long)slot * frame_bytes;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < frame_bytes; i += (long)gridDim.x * 256)
     dst[i] = real ? src[i] : (uint8_t)0;
 }
 
-template <bool SEG>
+template <bool SEG, bool RING = false>
 static int clip_gather_launch(const uint8_t* video, int L, long frame_bytes, const int* starts, const int* clip_base,
-                              const int* clip_len_v, int B, int T, uint8_t* clips_out, void* stream) {
+                              const int* clip_len_v, int B, int T, uint8_t* clips_out, void* stream, int ring_frames = 0) {
   hipStream_t st = (hipStream_t)stream;
   const bool v16 = frame_bytes % 16 == 0 && (((uintptr_t)video | (uintptr_t)clips_out) & 15) == 0;
   if (v16) {
     const long chunks = frame_bytes / 16;
     const int gx = (int)(cdiv(chunks, 256 * 4) < 64 ? cdiv(chunks, 256 * 4) : 64);     // 4+ chunks per thread
-    hipLaunchKernelGGL(clip_gather_v16_kernel<SEG>, dim3(gx, B * T), dim3(256), 0, st, (const u32x4*)video, L, chunks, starts,
-                       clip_base, clip_len_v, T, (u32x4*)clips_out);
+    hipLaunchKernelGGL((clip_gather_v16_kernel<SEG, RING>), dim3(gx, B * T), dim3(256), 0, st, (const u32x4*)video, L, ring_frames,
+                       chunks, starts, clip_base, clip_len_v, T, (u32x4*)clips_out);
   } else {
     const int gx = (int)(cdiv(frame_bytes, 256 * 4) < 64 ? cdiv(frame_bytes, 256 * 4) : 64);
-    hipLaunchKernelGGL(clip_gather_u8_kernel<SEG>, dim3(gx, B * T), dim3(256), 0, st, video, L, frame_bytes, starts, clip_base,
-                       clip_len_v, T, clips_out);
+    hipLaunchKernelGGL((clip_gather_u8_kernel<SEG, RING>), dim3(gx, B * T), dim3(256), 0, st, video, L, ring_frames, frame_bytes,
+                       starts, clip_base, clip_len_v, T, clips_out);
   }
   TD_LAUNCH_CHECK("clip_gather");
   return TDEED_OK;
@@ -84,6 +95,16 @@ extern "C" int tdeed_clip_gather_seg_u8(const uint8_t* video, int L_total, long 
   TD_CHECK(L_total > 0 && frame_bytes > 0 && B > 0 && T > 0, "clip_gather_seg: bad sizes");
   TD_CHECK((long)B * T <= 65535, "clip_gather_seg: B*T=%ld frame slots exceed the grid's 65535", (long)B * T);
   return clip_gather_launch<true>(video, L_total, frame_bytes, starts, clip_base, clip_len_v, B, T, clips_out, stream);
+}
+
+extern "C" int tdeed_clip_gather_ring_u8(const uint8_t* ring, int ring_frames, int L_total, long frame_bytes, const int* starts,
+                                         const int* clip_base, const int* clip_len_v, int B, int T, uint8_t* clips_out,
+                                         void* stream) {
+  TD_CHECK(ring && starts && clip_base && clip_len_v && clips_out, "clip_gather_ring: null pointer");
+  TD_CHECK(ring_frames > 0 && L_total > 0 && frame_bytes > 0 && B > 0 && T > 0, "clip_gather_ring: bad sizes");
+  TD_CHECK((long)B * T <= 65535, "clip_gather_ring: B*T=%ld frame slots exceed the grid's 65535", (long)B * T);
+  return clip_gather_launch<true, true>(ring, L_total, frame_bytes, starts, clip_base, clip_len_v, B, T, clips_out, stream,
+                                        ring_frames);
 }
 
 // =========================================================================== row gather (per-frame trunk maps)

@@ -1142,7 +1142,8 @@ class ForwardEngine:
         self.run_plan(plan)
         return plan.head_out, plan
 
-    def forward_from_video(self, video_u8, starts_dev, augment_inference=False, slot=0, clip_base=None, clip_len_v=None):
+    def forward_from_video(self, video_u8, starts_dev, augment_inference=False, slot=0, clip_base=None, clip_len_v=None,
+                           ring=None):
         """forward() over clip windows of a frame buffer that is resident on the device: video_u8 uint8 (L,3,H,W), starts_dev
         int32 (B,) on the device (first frame of each clip; windows that hang over either end are zero padded like the
         evaluation reader's).  The windows are gathered straight into the plan's input buffers (ops.clip_gather, one launch
@@ -1150,9 +1151,13 @@ class ForwardEngine:
         result carries the same bits as forward() on the materialised windows.
         clip_base / clip_len_v (int32 (B,) on the device, both or neither): video_u8 packs several videos, clip b belongs to
         the one that starts at packed frame clip_base[b] and has clip_len_v[b] frames, starts_dev is local to it and the
-        window is padded at that video's ends (ops.clip_gather_seg)."""
+        window is padded at that video's ends (ops.clip_gather_seg).
+        ring = (ring_frames, L_total): video_u8 is a ring of ring_frames rows of a packed buffer of L_total frames, packed
+        frame p in row p % ring_frames (ops.clip_gather_ring; needs the tables).  Only the gather differs."""
         if (clip_base is None) != (clip_len_v is None):
             raise ValueError("clip_base and clip_len_v go together")
+        if ring is not None and clip_base is None:
+            raise ValueError("a frame ring is gathered with the group's tables (clip_base, clip_len_v)")
         if video_u8.dtype != torch.uint8 or video_u8.dim() != 4 or not video_u8.is_cuda:
             raise TypeError("video frames must be a uint8 (L,3,H,W) tensor on the device")
         if starts_dev.dtype != torch.int32 or starts_dev.dim() != 1 or not starts_dev.is_cuda:
@@ -1165,6 +1170,9 @@ class ForwardEngine:
             part = slice(i * Bs, (i + 1) * Bs)
             if clip_base is None:
                 ops.clip_gather(video_u8, starts_dev[part], self.pw.clip_len, sb.frames)
+            elif ring is not None:
+                ops.clip_gather_ring(video_u8, ring[0], ring[1], starts_dev[part], clip_base[part], clip_len_v[part],
+                                     self.pw.clip_len, sb.frames)
             else:
                 ops.clip_gather_seg(video_u8, starts_dev[part], clip_base[part], clip_len_v[part], self.pw.clip_len, sb.frames)
         self.run_plan(plan)

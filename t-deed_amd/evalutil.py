@@ -151,11 +151,89 @@ def rows_gather_ref(maps, starts, L, pad_row, T, clip_base=None, clip_len_v=None
     return out
 
 
-def video_groups(lengths, frame_shapes, group_videos, max_resident_bytes):
+def clip_gather_ring_ref(video, lo, ring_frames, starts, T, clip_base, clip_len_v, fill=0xA5):
+    """numpy twin of ops.clip_gather_ring, with the ring it reads: `video` (L_total, ...) is the VIRTUAL packed buffer, of
+    which the frames [lo, lo + ring_frames) (cut at L_total) are live: ring[p % ring_frames] = video[p] for those, every
+    other row holds `fill`.  out[b, t] = ring[(clip_base[b] + starts[b] + t) % ring_frames] when 0 <= starts[b] + t <
+    clip_len_v[b], zeros otherwise.  A real frame outside the live window is the caller's error (ValueError): the kernel
+    would read whatever the row holds.  -> (out (B,T,...), ring (ring_frames,...))."""
+    video = np.asarray(video)
+    L, lo, rf = int(video.shape[0]), int(lo), int(ring_frames)
+    if rf < 1 or not 0 <= lo < L:
+        raise ValueError(f"clip_gather_ring_ref: a window from {lo} of {rf} rows over {L} frames")
+    ring = np.full((rf,) + video.shape[1:], fill, video.dtype)
+    for p in range(lo, min(lo + rf, L)):
+        ring[p % rf] = video[p]
+    B = len(starts)
+    out = np.zeros((B, T) + video.shape[1:], video.dtype)
+    for b in range(B):
+        base, lv = int(clip_base[b]), int(clip_len_v[b])
+        for t in range(T):
+            f = int(starts[b]) + t
+            if 0 <= f < lv and base >= 0 and base + f < L:
+                p = base + f
+                if not lo <= p < lo + rf:
+                    raise ValueError(f"clip_gather_ring_ref: clip {b} reads frame {p}, live are [{lo}, {lo + rf})")
+                out[b, t] = ring[p % rf]
+    return out, ring
+
+
+def ring_plan(lengths, frame_bytes, chunk_frames, max_resident_bytes, starts, clip_base, clip_len_v, clip_len, batch_size):
+    """The plan of scoring a packed group whose frames exceed `max_resident_bytes` through a ring of frame chunks
+    (`predict_video(stream_frames=True)`, `feeder.RingUpload`); pure host arithmetic.  Chunks are PackedUpload's: chunk c
+    holds the packed frames [c * chunk_frames, (c + 1) * chunk_frames).  The ring has ring_chunks = max_resident_bytes //
+    (chunk_frames * frame_bytes) slots of one chunk, chunk c lives in slot c % ring_chunks, so packed frame p sits in ring
+    row p % ring_frames, ring_frames = ring_chunks * chunk_frames.  starts / clip_base / clip_len_v: `group_clip_table`'s;
+    batches of `batch_size` are cut from the clip list in order.
+    -> None when the frames fit the budget (the resident route serves them), else a namespace of ring_chunks, ring_frames
+    and int arrays first / last (per batch: the chunks of the lowest / highest real packed frame the batch reads, -1 for a
+    batch of nothing but padding) and last_reader (per chunk: the last batch that reads it, -1 for none).
+    Raises ValueError when `first` decreases from one reading batch to the next (the ring moves forward only), and when
+    the widest batch plus the one chunk the upload keeps ahead, max(last - first + 1) + 1 chunks, do not fit the ring.
+    Together the two give what the upload relies on: when the host queues chunk c for a batch, every reader of the chunk
+    it overwrites, c - ring_chunks, is an EARLIER batch (last_reader[c - ring_chunks] < that batch), and all frames one
+    batch reads lie in distinct ring rows (clip_len <= ring_frames included)."""
+    from types import SimpleNamespace
+    lengths = [int(x) for x in lengths]
+    L, fb, per, T, bs = sum(lengths), int(frame_bytes), int(chunk_frames), int(clip_len), int(batch_size)
+    if min(fb, per, T, bs) < 1 or L < 1:
+        raise ValueError(f"ring_plan: {L} frames of {fb} bytes in chunks of {per}, clips of {T} in batches of {bs}")
+    if L * fb <= max_resident_bytes:
+        return None
+    ring_chunks = int(max_resident_bytes) // (per * fb)
+    n = len(starts)
+    n_chunks = -(-L // per)
+    n_batches = -(-n // bs)
+    first = np.full(n_batches, -1, np.int64)
+    last = np.full(n_batches, -1, np.int64)
+    last_reader = np.full(n_chunks, -1, np.int64)
+    for i in range(n):
+        s, base, lv = int(starts[i]), int(clip_base[i]), int(clip_len_v[i])
+        a, z = base + max(s, 0), min(base + min(s + T, lv), L) - 1         # lowest / highest real packed frame of the clip
+        if base < 0 or z < a:
+            continue
+        b, ca, cz = i // bs, a // per, z // per
+        first[b] = ca if first[b] < 0 else min(first[b], ca)
+        last[b] = max(last[b], cz)
+        last_reader[ca:cz + 1] = b
+    reading = np.nonzero(first >= 0)[0]
+    for b0, b1 in zip(reading[:-1], reading[1:]):
+        if first[b1] < first[b0]:
+            raise ValueError(f"ring_plan: the streamed route needs clips in ascending order: batch {b1} reads from chunk "
+                             f"{first[b1]} on, batch {b0} before it from chunk {first[b0]} on")
+    need = (int((last - first).max()) + 1 if reading.size else 0) + 1
+    if need > ring_chunks:
+        raise ValueError(f"ring_plan: max_resident_bytes={max_resident_bytes} holds a ring of {ring_chunks} chunks of {per} "
+                         f"frames, one batch and the chunk uploaded ahead of it need {need}: at least {need * per * fb} bytes")
+    return SimpleNamespace(ring_chunks=ring_chunks, ring_frames=ring_chunks * per, first=first, last=last,
+                           last_reader=last_reader)
+
+
+def video_groups(lengths, frame_shapes, group_videos, max_resident_bytes, stream_frames=False):
     """Split consecutive videos, in the order given, into groups for `predict_video_group`: lists of indices.  A group closes
     when it holds `group_videos` videos, when the next video would push the frames of the group over `max_resident_bytes`,
     or when the frame geometry (3,H,W) changes.  A single video over the budget raises the ValueError predict_video
-    raises for it."""
+    raises for it; with stream_frames=True it becomes a group of its own instead (scored through the frame ring)."""
     if int(group_videos) < 1:
         raise ValueError("video_groups: group_videos must be positive")
     groups, cur, cur_bytes, cur_shape = [], [], 0, None
@@ -163,8 +241,14 @@ def video_groups(lengths, frame_shapes, group_videos, max_resident_bytes):
         shape = tuple(int(x) for x in shape)
         need = int(L) * int(np.prod(shape))
         if need > max_resident_bytes:
-            raise ValueError(f"predict_video: the video needs {need} bytes on the device, more than max_resident_bytes="
-                             f"{max_resident_bytes} (a ring buffer for longer videos is not implemented)")
+            if not stream_frames:
+                raise ValueError(f"predict_video: the video needs {need} bytes on the device, more than max_resident_bytes="
+                                 f"{max_resident_bytes} (stream_frames=True scores longer videos through a frame ring)")
+            if cur:
+                groups.append(cur)
+            groups.append([j])
+            cur, cur_bytes = [], 0
+            continue
         if cur and (len(cur) >= int(group_videos) or cur_bytes + need > max_resident_bytes or shape != cur_shape):
             groups.append(cur)
             cur, cur_bytes = [], 0
@@ -213,10 +297,10 @@ def _with_loader(videos, decode):
             for name, length, fps, src in videos]
 
 
-def _decoded_groups(videos, group_videos, max_resident_bytes, decode_ahead=1):
+def _decoded_groups(videos, group_videos, max_resident_bytes, decode_ahead=1, stream_frames=False):
     """The sources of `videos` (name, length, fps, frames | callable) in groups: batches of `group_videos` consecutive
     videos are materialised -- callables on a worker thread, up to `decode_ahead` batches ahead of the consumer -- and each
-    batch is then split by `video_groups` (budget, geometry).  Yields lists of (name, length, fps, frames)."""
+    batch is then split by `video_groups` (budget, geometry, stream_frames).  Yields lists of (name, length, fps, frames)."""
     from concurrent.futures import ThreadPoolExecutor
     import torch
     gv, ahead = int(group_videos), max(int(decode_ahead), 0)
@@ -236,12 +320,13 @@ def _decoded_groups(videos, group_videos, max_resident_bytes, decode_ahead=1):
             for (name, length, _, _), f in zip(batch, frames):
                 if int(f.shape[0]) != int(length):
                     raise ValueError(f"video {name}: {int(f.shape[0])} frames delivered, {int(length)} announced")
-            for idx in video_groups([b[1] for b in batch], [tuple(f.shape[1:]) for f in frames], gv, max_resident_bytes):
+            for idx in video_groups([b[1] for b in batch], [tuple(f.shape[1:]) for f in frames], gv, max_resident_bytes,
+                                    stream_frames):
                 yield [(batch[j][0], batch[j][1], batch[j][2], frames[j]) for j in idx]
 
 
 def stitch_videos(model, videos, n_cols, augment=False, batch_size=8, overlap_len=None, decode_ahead=1, group_videos=1,
-                  max_resident_bytes=16 << 30, reuse_frames=False, decode="host"):
+                  max_resident_bytes=16 << 30, reuse_frames=False, decode="host", stream_frames=False):
     """Whole-video counterpart of `stitch_predictions`: `videos` yields (name, length, fps, frames) with frames a uint8
     (length,3,H,W) tensor of the sampled frames or a callable returning one (e.g. a `feeder.load_video` closure); every
     video is scored once and its (sums, support) become the video's track of the returned ScoreStitcher, so
@@ -251,12 +336,16 @@ def stitch_videos(model, videos, n_cols, augment=False, batch_size=8, overlap_le
     (the default) scores video by video, each a group of one.  The callables of the next `decode_ahead` batches of
     `group_videos` videos are decoded on a worker thread meanwhile: decoding overlaps scoring.
     reuse_frames: passed on to `predict_video_group` (the per-frame trunk stages once per frame).
+    stream_frames: a video over `max_resident_bytes` becomes a group of its own and is scored through a ring of frame chunks
+    (`predict_video_group(stream_frames=True)`) instead of raising.
     decode: a `frames` entry may also be a dict of `feeder.load_video` keyword arguments; "host" loads it with
     `feeder.load_video`, "device" with `feeder.load_video_device` (JPEG decode on the device, same frames)."""
     videos = _with_loader(list(videos), decode)
     reuse = dict(reuse_frames=True) if reuse_frames else {}
+    if stream_frames:
+        reuse["stream_frames"] = True
     st = ScoreStitcher([(v, n, f) for v, n, f, _ in videos], n_cols)
-    for group in _decoded_groups(videos, group_videos, max_resident_bytes, decode_ahead):
+    for group in _decoded_groups(videos, group_videos, max_resident_bytes, decode_ahead, stream_frames):
         out = model.predict_video_group([g[3] for g in group], overlap_len=overlap_len, batch_size=batch_size,
                                         augment=augment, max_resident_bytes=max_resident_bytes, **reuse)
         for (name, _, _, _), (sums, support) in zip(group, out):
@@ -446,7 +535,7 @@ def event_dicts(frames, classes_idx, scores, inv):
 
 def spot_videos(model, videos, classes, suppress, high_recall_score_threshold=0.01, augment=False, batch_size=8,
                 overlap_len=None, decode_ahead=1, group_videos=1, max_resident_bytes=16 << 30, reuse_frames=False,
-                decode="host"):
+                decode="host", stream_frames=False):
     """Whole-video counterpart of `stitch_videos` + `frame_events` + the two NMS functions with the tail on the device:
     `videos` as in `stitch_videos`; every video is scored and spotted once.  suppress: entries (kind, window,
     threshold) with kind "nms" | "snms".  Returns (pred_events, [one list of video records per suppress entry],
@@ -454,12 +543,14 @@ def spot_videos(model, videos, classes, suppress, high_recall_score_threshold=0.
     `soft_non_maximum_suppression` build them ('num_events' included), so `mean_average_precisions` works on them
     unchanged.  The label-dependent error / F1 counters of `frame_events` follow from the returned pred on the host.
     group_videos / decode_ahead: groups of videos go through `model.spot_video_group` as in `stitch_videos`.  reuse_frames:
-    passed on to `spot_video_group`.  decode: as in `stitch_videos`."""
+    passed on to `spot_video_group`.  decode, stream_frames: as in `stitch_videos`."""
     videos = _with_loader(list(videos), decode)
     reuse = dict(reuse_frames=True) if reuse_frames else {}
+    if stream_frames:
+        reuse["stream_frames"] = True
     suppress = [tuple(e) for e in suppress]
     done = {}
-    for group in _decoded_groups(videos, group_videos, max_resident_bytes, decode_ahead):
+    for group in _decoded_groups(videos, group_videos, max_resident_bytes, decode_ahead, stream_frames):
         out = model.spot_video_group([g[3] for g in group], classes, suppress=suppress,
                                      high_recall_score_threshold=high_recall_score_threshold, overlap_len=overlap_len,
                                      batch_size=batch_size, augment=augment, max_resident_bytes=max_resident_bytes, **reuse)
@@ -637,7 +728,7 @@ def map_suppress_entries(suppress, who):
 
 def map_videos(model, videos, classes, truth, suppress, tolerances=(0, 1, 2, 4), high_recall_score_threshold=0.01, augment=False,
                batch_size=8, overlap_len=None, decode_ahead=1, group_videos=1, max_resident_bytes=16 << 30, reuse_frames=False,
-               decode="host"):
+               decode="host", stream_frames=False):
     """`spot_videos` + `mean_average_precisions` per suppress entry with the whole tail on the device: no event list reaches the
     host.  videos and the keyword arguments as in `spot_videos`; truth: the records `mean_average_precisions` takes; suppress:
     entries ("raw",) -- the unsuppressed high-recall list -- or (kind, window, threshold) with kind "nms" | "snms".
@@ -660,15 +751,19 @@ def map_videos(model, videos, classes, truth, suppress, tolerances=(0, 1, 2, 4),
     table = truth_table(truth, ordinal, classes)
     videos = _with_loader(videos, decode)
     reuse = dict(reuse_frames=True) if reuse_frames else {}
+    if stream_frames:
+        reuse["stream_frames"] = True
     state = ops.ap_state([length[v] for v in names], table, K1, len(suppress), tols, device=model.device)
     totals, groups = defaultdict(int), 0
-    for group in _decoded_groups(videos, group_videos, max_resident_bytes, decode_ahead):
+    for group in _decoded_groups(videos, group_videos, max_resident_bytes, decode_ahead, stream_frames):
         model.map_video_group([g[3] for g in group], classes, state, [ordinal[g[0]] for g in group], suppress=suppress,
                               high_recall_score_threshold=high_recall_score_threshold, overlap_len=overlap_len,
                               batch_size=batch_size, augment=augment, max_resident_bytes=max_resident_bytes, **reuse)
         groups += 1
         for k, v in model.last_video_stats.items():
-            if k != "views":
+            if k in ("ring_frames", "ring_chunks", "resident_bytes"):       # (of the groups that streamed: the largest ring)
+                totals[k] = max(totals[k], v)
+            elif k != "views":
                 totals[k] += v
     ap, _ = model.map_finish(state)
     for k, v in model.last_video_stats.items():

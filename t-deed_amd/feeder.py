@@ -752,6 +752,79 @@ class PackedUpload:
         return self.arrived[-1]
 
 
+class RingUpload:
+    """PackedUpload for frames that do not fit the device budget: the same chunks of the same packed buffer, uploaded in the
+    same order on the copy stream with the same `through(c)` / `arrived[c]` protocol and `h2d` count, but into a RING
+    `video` of (ring_chunks * per,3,H,W) rows.  Chunk c lives in slot c % ring_chunks, so packed frame p sits in row
+    p % (ring_chunks * per) -- what ops.clip_gather_ring reads.  A chunk that spans videos is written piece by piece.
+    last_reader: `evalutil.ring_plan`'s, per chunk the last batch that reads it.  The consumer calls `release(b, stream)`
+    after batch b's forward has been queued on its stream; before chunk c >= ring_chunks is copied over chunk c -
+    ring_chunks, the copy stream waits for the release of every batch up to last_reader[c - ring_chunks] -- the latest
+    event of each stream the batches ran on.  ring_plan guarantees that those batches have been released when the host
+    queues the copy, so nothing here synchronises the host.  Copies are queued only as far as `through` asks, never all
+    at once (`asynchronous` tells whether a call returns before its copies have run, as for PackedUpload)."""
+
+    def __init__(self, srcs, device, stream, chunk_bytes, ring_chunks, last_reader):
+        self.srcs, self.stream = srcs, stream
+        lengths = [int(fr.shape[0]) for fr in srcs]
+        L = sum(lengths)
+        self.frame_bytes = fb = int(srcs[0][0].numel())
+        self.per = max(1, int(chunk_bytes) // fb)
+        self.ring_chunks = int(ring_chunks)
+        if self.ring_chunks < 1:
+            raise ValueError("RingUpload: a ring needs at least one chunk")
+        self.ring_frames = self.ring_chunks * self.per
+        self.video = torch.empty((self.ring_frames,) + tuple(srcs[0].shape[1:]), dtype=torch.uint8, device=device)
+        self.bounds = [(lo, min(lo + self.per, L)) for lo in range(0, L, self.per)]
+        self.last_reader = [int(b) for b in last_reader]
+        if len(self.last_reader) != len(self.bounds):
+            raise ValueError(f"RingUpload: last_reader for {len(self.last_reader)} chunks, the frames make {len(self.bounds)}")
+        self.offs = np.concatenate([[0], np.cumsum(lengths)]).tolist()
+        self.arrived = []
+        self.released = []                        # per batch (stream, event)
+        self.h2d = 0                              # bytes that crossed the host-device link so far
+        self.asynchronous = all(fr.is_cuda or fr.is_pinned() for fr in srcs)
+
+    def release(self, b, stream):
+        """Batch b (they come in order) no longer reads the ring after everything queued on `stream` so far."""
+        if b != len(self.released):
+            raise ValueError(f"RingUpload: batch {b} released, {len(self.released)} is next")
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        self.released.append((stream, ev))
+
+    def _wait_readers(self, upto):
+        """the copy stream waits for every released batch <= upto: the latest event of each stream among them"""
+        if upto >= len(self.released):
+            raise RuntimeError(f"RingUpload: batch {upto} still reads the slot to overwrite and has not been released "
+                               f"({len(self.released)} batches have): the ring is too small for this order (evalutil.ring_plan)")
+        streams, seen = {id(s) for s, _ in self.released[:upto + 1]}, set()
+        for s, ev in reversed(self.released[:upto + 1]):
+            if id(s) not in seen:
+                seen.add(id(s))
+                self.stream.wait_event(ev)
+                if len(seen) == len(streams):
+                    break
+
+    def through(self, c):
+        """Queue every chunk up to and including c (clamped to the last) that is not queued yet."""
+        with torch.cuda.stream(self.stream):
+            while len(self.arrived) <= min(c, len(self.bounds) - 1):
+                ci = len(self.arrived)
+                lo, hi = self.bounds[ci]
+                if ci >= self.ring_chunks and self.last_reader[ci - self.ring_chunks] >= 0:
+                    self._wait_readers(self.last_reader[ci - self.ring_chunks])
+                row = (ci % self.ring_chunks) * self.per - lo          # packed frame p -> ring row p + row
+                for v, fr in enumerate(self.srcs):
+                    a, b = max(lo, self.offs[v]), min(hi, self.offs[v + 1])
+                    if a < b:
+                        self.video[a + row:b + row].copy_(fr[a - self.offs[v]:b - self.offs[v]], non_blocking=True)
+                        self.h2d += 0 if fr.is_cuda else (b - a) * self.frame_bytes
+                ev = torch.cuda.Event()
+                ev.record(self.stream)
+                self.arrived.append(ev)
+
+
 def wait(batch, stream=None):
     """Explicit mode of `prefetch`: make `stream` (default: the current one) wait for the batch's frames to have arrived."""
     slot = batch.get("_slot")

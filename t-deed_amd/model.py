@@ -375,7 +375,7 @@ class TDEEDModel:
     video_chunk_bytes = 64 << 20        # upload granularity of predict_video (one arrival event per chunk)
 
     def predict_video(self, frames, clip_starts=None, overlap_len=None, pad_len=5, batch_size=8, augment=False, use_amp=True,
-                      max_resident_bytes=16 << 30, reuse_frames=False):
+                      max_resident_bytes=16 << 30, reuse_frames=False, stream_frames=False):
         """Score a whole video from one resident frame buffer: what the prediction loop of `evaluate` (util/eval.py:284-349)
         leaves in its per-video track, -> (scores_sum (L,K+1) float32, support (L,) int32) numpy, i.e.
         `ScoreStitcher.tracks[video]`.
@@ -393,6 +393,16 @@ class TDEEDModel:
         warm-up of a geometry seen for the first time (graph capture) the host synchronises once per video.
         Raises ValueError when the video does not fit `max_resident_bytes`.
 
+        stream_frames=True: host frames that do not fit `max_resident_bytes` are scored through a RING of upload chunks
+        instead (`feeder.RingUpload`, `evalutil.ring_plan`): the device holds max_resident_bytes // chunk bytes chunks, chunk
+        c in slot c mod that count, and a chunk is copied over an older one once the batches that read the older one have
+        run (stream events, no host synchronisation).  Every frame still crosses the link once, the batches, graphs and
+        the stitch launch are the same and so are the bits of the result.  The clips must come in ascending order and one
+        batch plus one chunk must fit the ring (ValueError otherwise, naming the budget that would do).  last_video_stats
+        gains ring_frames, ring_chunks and resident_bytes.  Frames that fit take the resident route untouched; a video
+        that is a device tensor already is used where it is; together with reuse_frames it works only when frames and
+        maps fit (ValueError otherwise: the maps have no ring).
+
         reuse_frames=True: the trunk stages in front of the first gate-shift site (stem and blocks [0, k), k =
         `ForwardEngine.first_site_block()`; functions of one frame alone in eval mode) run ONCE per frame and view, in chunks
         of `frame_batch` clips' worth of consecutive frames, into a resident map of the block-k inputs; a batch gathers its
@@ -402,13 +412,13 @@ class TDEEDModel:
         plan: same scores bit for bit where that plan would have served the batch (an even batch size), the first site's
         launch form otherwise."""
         out = self._predict_videos("predict_video", [frames], None if clip_starts is None else [clip_starts], overlap_len, pad_len,
-                                   batch_size, augment, use_amp, max_resident_bytes, reuse_frames)
+                                   batch_size, augment, use_amp, max_resident_bytes, reuse_frames, stream_frames)
         self._one_video_stats()
         return out[0]
 
     def spot_video(self, frames, classes, suppress=(("nms", 1, 0.01), ("snms", 3, 0.01)), high_recall_score_threshold=0.01,
                    clip_starts=None, overlap_len=None, pad_len=5, batch_size=8, augment=False, use_amp=True,
-                   max_resident_bytes=16 << 30, reuse_frames=False):
+                   max_resident_bytes=16 << 30, reuse_frames=False, stream_frames=False):
         """Score a whole video like predict_video and spot its events on the device: the tail of `evaluate`
         (util/eval.py:87-261, 386-391) -- `frame_events` and (soft) non-maximum suppression of the high-recall list -- without
         the (L,K+1) track ever leaving the device.  classes: name -> index (1-based); suppress: entries (kind, window,
@@ -423,7 +433,7 @@ class TDEEDModel:
         the classes)."""
         out = self._spot_videos("spot_video", [frames], classes, suppress, high_recall_score_threshold,
                                 None if clip_starts is None else [clip_starts], overlap_len, pad_len, batch_size, augment, use_amp,
-                                max_resident_bytes, reuse_frames)
+                                max_resident_bytes, reuse_frames, stream_frames)
         self._one_video_stats()
         return out[0]
 
@@ -432,7 +442,7 @@ class TDEEDModel:
         self.last_video_stats = {k: v for k, v in self.last_video_stats.items() if k not in ("videos", "host_syncs")}
 
     def predict_video_group(self, frames_list, clip_starts=None, overlap_len=None, pad_len=5, batch_size=8, augment=False,
-                            use_amp=True, max_resident_bytes=16 << 30, reuse_frames=False):
+                            use_amp=True, max_resident_bytes=16 << 30, reuse_frames=False, stream_frames=False):
         """predict_video for a group of videos scored as one packed job -> [(scores_sum (L_v,K+1) float32, support (L_v,)
         int32)], per video what predict_video returns for the same batches.
 
@@ -445,16 +455,17 @@ class TDEEDModel:
         stitch launch (ops.stitch_scores_seg) adds them per frame in ScoreStitcher's order for that frame's video.  Apart
         from the warm-up of a geometry seen for the first time the host synchronises once per group.
         last_video_stats: predict_video's keys as totals over the group, plus videos and host_syncs.
-        Raises ValueError for an empty list, an empty video, mixed geometries or a group over `max_resident_bytes`."""
+        Raises ValueError for an empty list, an empty video, mixed geometries or a group over `max_resident_bytes`;
+        stream_frames=True scores a group of host videos over the budget through predict_video's frame ring instead."""
         return self._predict_videos("predict_video_group", list(frames_list), clip_starts, overlap_len, pad_len, batch_size,
-                                    augment, use_amp, max_resident_bytes, reuse_frames)
+                                    augment, use_amp, max_resident_bytes, reuse_frames, stream_frames)
 
     def _predict_videos(self, who, frames_list, clip_starts, overlap_len, pad_len, batch_size, augment, use_amp,
-                        max_resident_bytes, reuse_frames):
+                        max_resident_bytes, reuse_frames, stream_frames=False):
         """predict_video_group under the name `who` (the prefix of its errors): predict_video is the group of one video."""
         track, support, _, s0, stats, keep, g = self._packed_track(who, frames_list, clip_starts, overlap_len, pad_len, batch_size,
                                                                    augment, use_amp, max_resident_bytes, want_mean=False,
-                                                                   reuse_frames=reuse_frames)
+                                                                   reuse_frames=reuse_frames, stream_frames=stream_frames)
         L, K1 = track.shape
         with torch.cuda.stream(s0):
             out_sum = torch.empty((L, K1), dtype=torch.float32).pin_memory()
@@ -470,7 +481,7 @@ class TDEEDModel:
 
     def spot_video_group(self, frames_list, classes, suppress=(("nms", 1, 0.01), ("snms", 3, 0.01)),
                          high_recall_score_threshold=0.01, clip_starts=None, overlap_len=None, pad_len=5, batch_size=8,
-                         augment=False, use_amp=True, max_resident_bytes=16 << 30, reuse_frames=False):
+                         augment=False, use_amp=True, max_resident_bytes=16 << 30, reuse_frames=False, stream_frames=False):
         """spot_video for a group of videos scored as one packed job (predict_video_group's pipeline) -> one spot_video
         dict per video.  On the packed track: one segmented event launch (ops.frame_events_seg), one suppression launch per
         entry of `suppress` with a workgroup per (class, video) (ops.nms_track_seg), whose compaction leaves the videos' event
@@ -478,10 +489,11 @@ class TDEEDModel:
         the event offsets and the rounds, once for one contiguous range of events per entry (skipped when nothing was
         kept).  last_video_stats: totals over the group; nms_rounds per entry is the maximum over videos and classes."""
         return self._spot_videos("spot_video_group", list(frames_list), classes, suppress, high_recall_score_threshold,
-                                 clip_starts, overlap_len, pad_len, batch_size, augment, use_amp, max_resident_bytes, reuse_frames)
+                                 clip_starts, overlap_len, pad_len, batch_size, augment, use_amp, max_resident_bytes, reuse_frames,
+                                 stream_frames)
 
     def _spot_videos(self, who, frames_list, classes, suppress, high_recall_score_threshold, clip_starts, overlap_len, pad_len,
-                     batch_size, augment, use_amp, max_resident_bytes, reuse_frames):
+                     batch_size, augment, use_amp, max_resident_bytes, reuse_frames, stream_frames=False):
         """spot_video_group under the name `who` (the prefix of its errors): spot_video is the group of one video."""
         from . import evalutil
         suppress = [tuple(e) for e in suppress]
@@ -496,7 +508,7 @@ class TDEEDModel:
             raise ValueError(f"{who}: classes must name the indices 1..{K1 - 1} of the model's score columns")
         track, _, mean, s0, stats, keep, g = self._packed_track(who, frames_list, clip_starts, overlap_len, pad_len, batch_size,
                                                                 augment, use_amp, max_resident_bytes, want_mean=True,
-                                                                reuse_frames=reuse_frames)
+                                                                reuse_frames=reuse_frames, stream_frames=stream_frames)
         L, nv = track.shape[0], g.nv
         hr = float(high_recall_score_threshold)
         n = len(suppress)
@@ -552,7 +564,7 @@ class TDEEDModel:
 
     def map_video_group(self, frames_list, classes, state, ordinals, suppress=(("nms", 1, 0.01), ("snms", 3, 0.01)),
                         high_recall_score_threshold=0.01, clip_starts=None, overlap_len=None, pad_len=5, batch_size=8,
-                        augment=False, use_amp=True, max_resident_bytes=16 << 30, reuse_frames=False):
+                        augment=False, use_amp=True, max_resident_bytes=16 << 30, reuse_frames=False, stream_frames=False):
         """spot_video_group's pipeline for a mAP pass (evalutil.map_videos): the group is scored as one packed job, then on the
         packed track one event launch, per entry of `suppress` its suppression launch (none for ("raw",), the unsuppressed
         high-recall list) and the segment + match launch (ops.ap_match_seg), which leaves the group's ordered predictions and
@@ -579,7 +591,7 @@ class TDEEDModel:
             raise ValueError(f"{who}: ordinals {ordinals} do not name {len(frames_list)} videos of the state's dataset by length")
         _, _, mean, s0, stats, keep, g = self._packed_track(who, frames_list, clip_starts, overlap_len, pad_len, batch_size,
                                                             augment, use_amp, max_resident_bytes, want_mean=True,
-                                                            reuse_frames=reuse_frames)
+                                                            reuse_frames=reuse_frames, stream_frames=stream_frames)
         hr = float(high_recall_score_threshold)
         h_ords = torch.tensor(ordinals, dtype=torch.int32).pin_memory()
         with torch.cuda.stream(s0):
@@ -625,7 +637,7 @@ class TDEEDModel:
     frame_batch = 2                     # clips' worth of frames per launch of the per-frame pass (reuse_frames=True)
 
     def _packed_track(self, who, frames_list, clip_starts, overlap_len, pad_len, batch_size, augment, use_amp,
-                      max_resident_bytes, want_mean, reuse_frames=False):
+                      max_resident_bytes, want_mean, reuse_frames=False, stream_frames=False):
         """A group of videos (one video: a group of one) through upload, batches and the stitch launch, nothing synchronised.
         The videos are packed one after the other into one resident buffer -- a single video that is on the device already
         is used where it is -- and one clip list (evalutil.group_clip_table, clip_starts one list per video), batches are
@@ -636,7 +648,10 @@ class TDEEDModel:
         reuse_frames: the per-frame trunk stages run once per (packed) frame and view into a resident map, chunk by chunk on a
         stream of their own with an event per chunk -- the chunk with the first black row (the padding of every window)
         first, then in frame order; a batch waits for the chunk that holds its last frame and runs the rest of the network
-        on rows gathered from the map."""
+        on rows gathered from the map.
+        stream_frames: host frames over the budget go through feeder.RingUpload instead of PackedUpload -- the same chunks
+        into a ring of them, per evalutil.ring_plan -- and the batches gather with ops.clip_gather_ring; a batch records its
+        release on its stream, the upload waits for the releases of a slot's last readers before it overwrites the slot."""
         from types import SimpleNamespace
         from . import evalutil
         from .streams import new_stream
@@ -661,9 +676,12 @@ class TDEEDModel:
         if nv > ops.MAX_GROUP_VIDEOS:
             raise ValueError(f"{who}: {nv} videos in one group, at most {ops.MAX_GROUP_VIDEOS}")
         what = "group" if who.endswith("_group") else "video"
-        if L * fb > max_resident_bytes:
+        # over the budget: only host frames can stream through a ring (a device tensor is where it is)
+        over = L * fb > max_resident_bytes
+        if over and not (stream_frames and not any(fr.is_cuda for fr in srcs)):
             raise ValueError(f"{who}: the {what} needs {L * fb} bytes on the device, more than "
-                             f"max_resident_bytes={max_resident_bytes} (a ring buffer for longer videos is not implemented)")
+                             f"max_resident_bytes={max_resident_bytes} (stream_frames=True scores host frames over the "
+                             "budget through a frame ring)")
         T = self._args.clip_len
         ov = T // 4 * 3 if overlap_len is None else int(overlap_len)
         seg_off, clip_off, starts_np, base_np, lenv_np = evalutil.group_clip_table(lengths, T, ov, pad_len, clip_starts)
@@ -686,9 +704,20 @@ class TDEEDModel:
             rows, pad_row, chunk = evalutil.frame_map_rows(L, T, Bf)
             map_bytes = V * rows * mh * mw * mc * (2 if dt == torch.bfloat16 else 4)
             if L * fb + map_bytes > max_resident_bytes:
+                if stream_frames:
+                    raise ValueError(f"{who}: stream_frames=True and reuse_frames=True are not combined yet: the {what} needs "
+                                     f"{L * fb + map_bytes} bytes on the device ({map_bytes} of them per-frame maps, which "
+                                     f"have no ring), more than max_resident_bytes={max_resident_bytes}")
                 raise ValueError(f"{who}: the {what} needs {L * fb + map_bytes} bytes on the device "
                                  f"({map_bytes} of them per-frame maps), more than max_resident_bytes={max_resident_bytes} "
-                                 "(a ring buffer for longer videos is not implemented)")
+                                 "(the maps have no ring: stream_frames=True streams frames only)")
+        ring = None
+        if over:
+            try:
+                ring = evalutil.ring_plan(lengths, fb, max(1, int(self.video_chunk_bytes) // fb), max_resident_bytes, starts_np,
+                                          base_np, lenv_np, T, batch_size)
+            except ValueError as e:
+                raise ValueError(f"{who}: {e}") from None
         if self._stream is None:
             self._stream = new_stream()
         if getattr(self, "_stream2", None) is None:
@@ -723,9 +752,14 @@ class TDEEDModel:
         if packed:
             # one buffer for all frames, filled in chunks of video_chunk_bytes on the copy stream (a chunk may span videos)
             from . import feeder
-            up = feeder.PackedUpload(srcs, dev, cp, self.video_chunk_bytes)
+            if ring is not None:
+                # over the budget: the same chunks into a ring of them; a chunk is queued when a batch asks for it, behind
+                # the release events of the batches that read the chunk it overwrites (never all at once)
+                up = feeder.RingUpload(srcs, dev, cp, self.video_chunk_bytes, ring.ring_chunks, ring.last_reader)
+            else:
+                up = feeder.PackedUpload(srcs, dev, cp, self.video_chunk_bytes)
             video, per, arrived = up.video, up.per, up.arrived
-            if up.asynchronous:
+            if ring is None and up.asynchronous:
                 up.all()                              # asynchronous copies: queue all frames behind the first chunk
         else:
             video = srcs[0]
@@ -756,6 +790,7 @@ class TDEEDModel:
                     map_ready[fc] = ev
         # ---- the batches: gather -> forward -> post-processing, two in flight
         n_batches = 0
+        ring_arg = None if ring is None else (ring.ring_frames, L)
         for bi, lo in enumerate(range(0, n, batch_size)):
             B = min(batch_size, n - lo)
             slot = bi % 2
@@ -783,10 +818,12 @@ class TDEEDModel:
                         head, _ = eng.forward_from_frame_maps(maps[v], starts_dev[lo:lo + B], pad_row, slot=slot, **tables)
                     else:
                         head, _ = eng.forward_from_video(video, starts_dev[lo:lo + B], augment_inference=bool(v), slot=slot,
-                                                         **tables)
+                                                         ring=ring_arg, **tables)
                     pred, _ = self._model._pack_head(head, B, T, pw.n_cls, pw.displ_col, None)
                     # head is a view of the slot's buffer: consumed here, on the launching stream, before the slot runs again
                     self._process_pred(pred, B, T, dt, out=clip_scores[v, lo:lo + B])
+                if ring is not None:
+                    up.release(bi, st)                # the last gather of this batch is behind: its chunks may be overwritten
             n_batches += 1
         # ---- one stitch launch
         s0 = streams[0]
@@ -802,6 +839,8 @@ class TDEEDModel:
         if reuse_frames:
             stats["frame_pass_frames"] = V * rows
             stats["map_bytes"] = map_bytes
+        if ring is not None:
+            stats.update(ring_frames=ring.ring_frames, ring_chunks=ring.ring_chunks, resident_bytes=ring.ring_frames * fb)
         return track, support, mean, s0, stats, (video, srcs, clip_scores, tab_dev, tab_host, maps), g
 
     def epoch(self, loader, optimizer=None, scaler=None, lr_scheduler=None, acc_grad_iter=1, fg_weight=5,

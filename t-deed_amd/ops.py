@@ -854,6 +854,28 @@ def clip_gather_seg(video_u8, starts_dev, clip_base, clip_len_v, T, out):
     return out
 
 
+def clip_gather_ring(ring_u8, ring_frames, L_total, starts_dev, clip_base, clip_len_v, T, out):
+    """clip_gather_seg over a virtual packed buffer of L_total frames of which ring_u8 (ring_frames, ...) holds a window:
+    packed frame p sits in ring_u8[p % ring_frames] (feeder.RingUpload).  The windows and their padding are clip_gather_seg's
+    on the whole buffer.  That the frames a clip reads are live in the ring is the caller's duty (evalutil.ring_plan)."""
+    if ring_u8.dtype != torch.uint8 or out.dtype != torch.uint8 or starts_dev.dtype != torch.int32:
+        raise TypeError("clip_gather_ring: uint8 frames and int32 starts")
+    if not (ring_u8.is_contiguous() and out.is_contiguous() and starts_dev.is_contiguous()):
+        raise ValueError("clip_gather_ring: contiguous tensors only")
+    ring_frames, L_total, B = int(ring_frames), int(L_total), starts_dev.numel()
+    if ring_u8.shape[0] != ring_frames or ring_frames < 1 or L_total < 1:
+        raise ValueError(f"clip_gather_ring: a ring of {ring_u8.shape[0]} rows for ring_frames={ring_frames}, L_total={L_total}")
+    _chk_table(starts_dev, B, ring_u8.device, "clip_gather_ring", "starts")
+    _chk_table(clip_base, B, ring_u8.device, "clip_gather_ring", "clip_base")
+    _chk_table(clip_len_v, B, ring_u8.device, "clip_gather_ring", "clip_len_v")
+    fb = ring_u8[0].numel()
+    if out.numel() != B * T * fb:
+        raise ValueError(f"clip_gather_ring: out holds {out.numel()} bytes, {B} clips of {T} frames need {B * T * fb}")
+    call("tdeed_clip_gather_ring_u8", ptr(ring_u8), ring_frames, L_total, fb, ptr(starts_dev), ptr(clip_base), ptr(clip_len_v),
+         B, T, ptr(out), stream_ptr())
+    return out
+
+
 def _chk_rows_gather(maps, starts_dev, L, pad_row, T, out, who):
     if not all(isinstance(t_, torch.Tensor) for t_ in (maps, starts_dev, out)):
         raise TypeError(f"{who}: tensors only")

@@ -16,6 +16,9 @@
                                                                         profiles/video_map.json
     python tools/bench_video.py --reuse [--frames 2030]                 predict_video against predict_video(reuse_frames=
                                                                         True), one JSON line, also written to --out
+    python tools/bench_video.py --ring [--frames 2030]                  predict_video resident against predict_video(
+                                                                        stream_frames=True) at a quarter of the video's bytes,
+                                                                        one JSON line, also written to profiles/video_ring.json
 
 Routes (RegNetY-200MF, T = 100, 224 x 224, bf16; 3/4 overlap like the evaluation datasets):
   A  the clip route: `evalutil.stitch_predictions` over host-resident PINNED uint8 clip batches of the video, at loader
@@ -544,6 +547,60 @@ def reuse(a):
     return 0
 
 
+def ring(a):
+    """Two routes over the same host video, alternating: predict_video(batch_size=8) with the frames resident, and with
+    stream_frames=True at a budget of a QUARTER of the video's bytes (the frame ring).  Upload chunks of 8 MiB on both routes
+    (the default 64 MiB chunk is 445 frames: a batch of 8 clips spans 275, and a quarter of the tool's video could not hold
+    a batch plus one chunk of that size).  Pinned and pageable frames, plain and augmented.  Per setting: both wall times,
+    their ratio against the resident route's own spread, frames_h2d_bytes, ring_frames and whether the tracks are equal."""
+    from tdeed_amd.model import TDEEDModel
+    from types import SimpleNamespace
+    L = a.frames
+    m = TDEEDModel(device="cuda", args=SimpleNamespace(modality="rgb", temporal_arch="ed_sgp_mixer", pretrain=None, **CFG))
+    m.load({k: torch.from_numpy(v) for k, v in synth.make_state(state_layout.model_state_shapes(CFG), 0).items()})
+    m.video_chunk_bytes = 8 << 20
+    fb = 3 * H * W
+    budget = L * fb // 4
+    host = ops.fill_u8_hash((L, 3, H, W), 9, "cuda").cpu()
+    sources = dict(pinned=host.pin_memory(), pageable=host)
+    out = dict(kind="video_ring", device=torch.cuda.get_device_name(0), measured_on_gpu=True, cfg=CFG, frames=L, batch_size=8,
+               repeats=a.repeats, video_bytes=L * fb, max_resident_bytes=budget, video_chunk_bytes=m.video_chunk_bytes,
+               settings={})
+    for src, video in sources.items():
+        for augment in (False, True):
+            routes = dict(resident=lambda: m.predict_video(video, batch_size=8, augment=augment),
+                          ring=lambda: m.predict_video(video, batch_size=8, augment=augment, max_resident_bytes=budget,
+                                                       stream_frames=True))
+            res, stats = {}, {}
+            for k, fn in routes.items():                                # warm-up of every shape
+                res[k] = fn()
+                stats[k] = dict(m.last_video_stats)
+            times = {k: [] for k in routes}
+            for _ in range(a.repeats):
+                for k, fn in routes.items():                            # alternating
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    times[k].append(time.perf_counter() - t0)
+            V, n = stats["ring"]["views"], stats["ring"]["clips"]
+            st = {k: _stat(v, L, n * V) for k, v in times.items()}
+            spread = st["resident"]["ms_max"] - st["resident"]["ms_min"]
+            out["settings"][f"{src}_{'augment' if augment else 'plain'}"] = dict(
+                routes=st, ratio_ring_over_resident=round(st["ring"]["ms_median"] / st["resident"]["ms_median"], 3),
+                resident_spread_ms=round(spread, 2),
+                ring_within_resident_spread=bool(st["ring"]["ms_median"] <= st["resident"]["ms_median"] + spread),
+                frames_h2d_bytes={k: stats[k]["frames_h2d_bytes"] for k in stats}, ring_frames=stats["ring"]["ring_frames"],
+                ring_chunks=stats["ring"]["ring_chunks"], resident_bytes=stats["ring"]["resident_bytes"],
+                tracks_equal=bool(np.array_equal(res["resident"][0], res["ring"][0])
+                                  and np.array_equal(res["resident"][1], res["ring"][1])))
+    path = os.path.join(ROOT, "profiles", "video_ring.json")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        f.write(json.dumps(out, indent=1) + "\n")
+    print(json.dumps(out))
+    return 0 if all(s["tracks_equal"] for s in out["settings"].values()) else 1
+
+
 def gather_only(a):
     T, B, L = 100, 8, 400
     video = ops.fill_u8_hash((L, 3, H, W), 9, "cuda")
@@ -694,6 +751,7 @@ if __name__ == "__main__":
     ap.add_argument("--map-videos", type=int, default=24, help="--map: videos of the synthetic diving split")
     ap.add_argument("--map-tail-videos", type=int, default=40, help="--map: noise tracks of the tail-only measurement (0: skip it)")
     ap.add_argument("--reuse", action="store_true", help="predict_video against predict_video(reuse_frames=True)")
+    ap.add_argument("--ring", action="store_true", help="predict_video resident against the frame ring (stream_frames=True)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "video_frame_reuse.json"), help="--reuse: where the JSON goes")
     ap.add_argument("--group-videos", type=int, default=32, help="--group: videos per packed group of route B")
     ap.add_argument("--splits", default="diving,tennis", help="--group: synthetic splits to run")
@@ -707,5 +765,5 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if a.frames is None:
         a.frames = 5625 if a.spot else 2030
-    sys.exit(map_bench(a) if a.map else decode_device(a) if a.decode_device else decode(a) if a.decode else gather_only(a) if a.gather_only else reuse(a) if a.reuse else group(a) if a.group
+    sys.exit(ring(a) if a.ring else map_bench(a) if a.map else decode_device(a) if a.decode_device else decode(a) if a.decode else gather_only(a) if a.gather_only else reuse(a) if a.reuse else group(a) if a.group
              else spot(a) if a.spot else bench(a))
