@@ -898,13 +898,20 @@ int tdeed_sgp_gemm_gelu_chsum(const void* A, int B, int T, int K, const void* Wp
  *   6 run past 63, 7 row outside its buffers.  A lane never reads outside its segment nor stores outside its frame.
  * tdeed_jpeg_pixels: coeff of the same frame range -> out uint8 [all frames][3][H][W] rows frame_lo ..; dequantisation, integer
  *   IDCT, triangle up-sampling and YCbCr -> RGB, bit-identical to libjpeg-turbo's defaults.  frame_table_set int32 per
- *   frame of the whole video; a frame with a negative entry is left untouched (the caller decodes it on the host). */
+ *   frame of the whole video; a frame with a negative entry is left untouched (the caller decodes it on the host).
+ * tdeed_jpeg_pixels_rows: the same kernel body with a row table: pack frame f (frame_lo <= f < frame_lo + n_frames) goes to
+ *   out + dst_row[f] * 3*H*W, out uint8 [out_rows][3][H][W] (the rows i*T + t of a (B,T,3,H,W) clip-batch slot); a frame
+ *   with dst_row[f] < 0, dst_row[f] >= out_rows or a negative table set stores nothing.  dst_row int32, one entry per
+ *   frame of the whole pack, on the device. */
 long tdeed_jpeg_frame_coeffs(int W, int H, int sampling);
 int tdeed_jpeg_entropy(const uint8_t* stream, long stream_bytes, const int* segments, int n_segments, const int* waves,
                        int n_waves, const uint8_t* table_sets, int n_sets, int W, int H, int sampling, int frame_lo,
                        int n_frames, int16_t* coeff, int* status, void* hip_stream);
 int tdeed_jpeg_pixels(const int16_t* coeff, const int* frame_table_set, const uint8_t* table_sets, int n_sets, uint8_t* out,
                       int frame_lo, int n_frames, int H, int W, int sampling, void* hip_stream);
+int tdeed_jpeg_pixels_rows(const int16_t* coeff, const int* frame_table_set, const uint8_t* table_sets, int n_sets,
+                           uint8_t* out, long out_rows, const int* dst_row, int frame_lo, int n_frames, int H, int W,
+                           int sampling, void* hip_stream);
 
 #ifdef __cplusplus
 }

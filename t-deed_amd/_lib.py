@@ -207,6 +207,7 @@ _SIGS = {
     "tdeed_jpeg_frame_coeffs": ([c_int, c_int, c_int], c_long),
     "tdeed_jpeg_entropy": ([P, c_long, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P], c_int),
     "tdeed_jpeg_pixels": ([P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P], c_int),
+    "tdeed_jpeg_pixels_rows": ([P, P, P, c_int, P, c_long, P, c_int, c_int, c_int, c_int, c_int, P], c_int),
     "tdeed_comm_unique_id": ([P], c_int),
     "tdeed_comm_init": ([POINTER(c_void_p), P, c_int, c_int], c_int),
     "tdeed_comm_info": ([P, POINTER(c_int), POINTER(c_int)], c_int),

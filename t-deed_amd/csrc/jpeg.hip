@@ -73,6 +73,8 @@ extern "C" long tdeed_jpeg_frame_coeffs(int W, int H, int sampling) {
 // below the band (the up-sampling taps reach one chroma sample across the MCU border), taken from a recomputed IDCT of
 // the neighbouring band's chroma blocks.  Phase 2: one thread per 16 pixels of a row: triangle taps, colour conversion,
 // three 16-byte stores (V16) or guarded byte stores.
+// The frame lands in row dst_row[frame] of out when ROWS (tdeed_jpeg_pixels_rows: the frames of a clip batch go to rows
+// i * T + t of the batch slot), in row frame otherwise; a row outside [0, out_rows) stores nothing.
 struct BandPlanes {
   const uint8_t* y;
   const uint8_t* cb;
@@ -83,10 +85,11 @@ struct BandPlanes {
   }
 };
 
-template <int SAMP, bool V16>
+template <int SAMP, bool V16, bool ROWS>
 __global__ __launch_bounds__(256) void jpeg_pixels_kernel(const int16_t* __restrict__ coef, const int* __restrict__ frame_set,
                                                           const JcTableSet* __restrict__ sets, int n_sets, int frame_lo,
-                                                          int W, int H, int mcus_x, int mcus_y, uint8_t* __restrict__ out) {
+                                                          int W, int H, int mcus_x, int mcus_y, uint8_t* __restrict__ out,
+                                                          const int* __restrict__ dst_row, long out_rows) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   constexpr int HS = (SAMP == JC_422 || SAMP == JC_420) ? 2 : 1, VS = SAMP == JC_420 ? 2 : 1;
   constexpr int NC = SAMP == JC_GREY ? 0 : 2;                 // chroma planes
@@ -95,6 +98,9 @@ __global__ __launch_bounds__(256) void jpeg_pixels_kernel(const int16_t* __restr
   const int band = blockIdx.x, fl = blockIdx.y;
   const int set = frame_set[frame_lo + fl];
   if (set < 0 || set >= n_sets) return;                        // a frame that is decoded on the host
+  const long row = ROWS ? (long)dst_row[frame_lo + fl] : (long)frame_lo + fl;
+  if (ROWS && (row < 0 || row >= out_rows)) return;            // a frame that no row of the slot takes
+  TD_DEV_ASSERT(row >= 0 && (!ROWS || row < out_rows));
   const JcTableSet* ts = sets + set;
   const int bw0 = mcus_x * HS, ypitch = bw0 * 8, cpitch = mcus_x * 8;
   uint8_t* ly = lds;
@@ -139,7 +145,7 @@ __global__ __launch_bounds__(256) void jpeg_pixels_kernel(const int16_t* __restr
   const int y_lo = band * 8 * VS, rows_here = H - y_lo < 8 * VS ? H - y_lo : 8 * VS;
   const int chunks = (W + 15) / 16;
   const long plane_px = (long)H * W;
-  uint8_t* of = out + (long)(frame_lo + fl) * 3 * plane_px;
+  uint8_t* of = out + row * 3 * plane_px;
   for (int t = threadIdx.x; t < rows_here * chunks; t += 256) {
     const int ry = t / chunks, x0 = (t - ry * chunks) * 16, y = y_lo + ry;
     uint32_t pr[4] = {0, 0, 0, 0}, pg[4] = {0, 0, 0, 0}, pb[4] = {0, 0, 0, 0};
@@ -169,9 +175,10 @@ __global__ __launch_bounds__(256) void jpeg_pixels_kernel(const int16_t* __restr
   }
 }
 
+// dst_row == nullptr: the identity-row instance (tdeed_jpeg_pixels)
 template <int SAMP>
-static int jpeg_pixels_launch(const int16_t* coef, const int* frame_set, const uint8_t* sets, int n_sets, uint8_t* out, int frame_lo,
-                              int n_frames, int H, int W, hipStream_t st) {
+static int jpeg_pixels_launch(const int16_t* coef, const int* frame_set, const uint8_t* sets, int n_sets, uint8_t* out,
+                              const int* dst_row, long out_rows, int frame_lo, int n_frames, int H, int W, hipStream_t st) {
   const JcGeom g = jc_geom(W, H, SAMP);
   const int halo = SAMP == JC_420 ? 1 : 0, nc = SAMP == JC_GREY ? 0 : 2;
   const long lds = 8L * g.vs * g.bw[0] * 8 + (long)nc * (8 + 2 * halo) * g.mcus_x * 8;
@@ -179,18 +186,22 @@ static int jpeg_pixels_launch(const int16_t* coef, const int* frame_set, const u
   TD_CHECK(g.mcus_y <= 65535 && n_frames <= 65535, "jpeg_pixels: %d bands x %d frames exceed the grid", g.mcus_y, n_frames);
   const bool v16 = W % 16 == 0 && (((uintptr_t)out) & 15) == 0;
   const dim3 grid(g.mcus_y, n_frames);
-  if (v16)
-    hipLaunchKernelGGL((jpeg_pixels_kernel<SAMP, true>), grid, dim3(256), lds, st, coef, frame_set, (const JcTableSet*)sets, n_sets,
-                       frame_lo, W, H, g.mcus_x, g.mcus_y, out);
-  else
-    hipLaunchKernelGGL((jpeg_pixels_kernel<SAMP, false>), grid, dim3(256), lds, st, coef, frame_set, (const JcTableSet*)sets,
-                       n_sets, frame_lo, W, H, g.mcus_x, g.mcus_y, out);
+#define JPEG_PIXELS_GO(V16, ROWS)                                                                                              \
+  hipLaunchKernelGGL((jpeg_pixels_kernel<SAMP, V16, ROWS>), grid, dim3(256), lds, st, coef, frame_set, (const JcTableSet*)sets, \
+                     n_sets, frame_lo, W, H, g.mcus_x, g.mcus_y, out, dst_row, out_rows)
+  if (dst_row) {
+    if (v16) JPEG_PIXELS_GO(true, true); else JPEG_PIXELS_GO(false, true);
+  } else {
+    if (v16) JPEG_PIXELS_GO(true, false); else JPEG_PIXELS_GO(false, false);
+  }
+#undef JPEG_PIXELS_GO
   TD_LAUNCH_CHECK("jpeg_pixels");
   return TDEED_OK;
 }
 
-extern "C" int tdeed_jpeg_pixels(const int16_t* coeff, const int* frame_table_set, const uint8_t* table_sets, int n_sets,
-                                 uint8_t* out, int frame_lo, int n_frames, int H, int W, int sampling, void* hip_stream) {
+static int jpeg_pixels_any(const int16_t* coeff, const int* frame_table_set, const uint8_t* table_sets, int n_sets, uint8_t* out,
+                           const int* dst_row, long out_rows, int frame_lo, int n_frames, int H, int W, int sampling,
+                           void* hip_stream) {
   TD_CHECK(coeff && frame_table_set && table_sets && out, "jpeg_pixels: null pointer");
   TD_CHECK(n_sets > 0 && n_frames > 0 && frame_lo >= 0, "jpeg_pixels: bad sizes");
   TD_CHECK(W > 0 && H > 0 && W <= 65535 && H <= 65535, "jpeg_pixels: bad frame size %dx%d", H, W);
@@ -198,11 +209,29 @@ extern "C" int tdeed_jpeg_pixels(const int16_t* coeff, const int* frame_table_se
            "jpeg_pixels: table sets and coefficients must be 16-byte aligned");
   hipStream_t st = (hipStream_t)hip_stream;
   switch (sampling) {
-    case JC_GREY: return jpeg_pixels_launch<JC_GREY>(coeff, frame_table_set, table_sets, n_sets, out, frame_lo, n_frames, H, W, st);
-    case JC_444: return jpeg_pixels_launch<JC_444>(coeff, frame_table_set, table_sets, n_sets, out, frame_lo, n_frames, H, W, st);
-    case JC_422: return jpeg_pixels_launch<JC_422>(coeff, frame_table_set, table_sets, n_sets, out, frame_lo, n_frames, H, W, st);
-    case JC_420: return jpeg_pixels_launch<JC_420>(coeff, frame_table_set, table_sets, n_sets, out, frame_lo, n_frames, H, W, st);
+    case JC_GREY:
+      return jpeg_pixels_launch<JC_GREY>(coeff, frame_table_set, table_sets, n_sets, out, dst_row, out_rows, frame_lo, n_frames, H, W, st);
+    case JC_444:
+      return jpeg_pixels_launch<JC_444>(coeff, frame_table_set, table_sets, n_sets, out, dst_row, out_rows, frame_lo, n_frames, H, W, st);
+    case JC_422:
+      return jpeg_pixels_launch<JC_422>(coeff, frame_table_set, table_sets, n_sets, out, dst_row, out_rows, frame_lo, n_frames, H, W, st);
+    case JC_420:
+      return jpeg_pixels_launch<JC_420>(coeff, frame_table_set, table_sets, n_sets, out, dst_row, out_rows, frame_lo, n_frames, H, W, st);
   }
   TD_CHECK(false, "jpeg_pixels: sampling %d (0 grey, 1 4:4:4, 2 4:2:2, 3 4:2:0)", sampling);
   return TDEED_OK;
+}
+
+extern "C" int tdeed_jpeg_pixels(const int16_t* coeff, const int* frame_table_set, const uint8_t* table_sets, int n_sets,
+                                 uint8_t* out, int frame_lo, int n_frames, int H, int W, int sampling, void* hip_stream) {
+  return jpeg_pixels_any(coeff, frame_table_set, table_sets, n_sets, out, nullptr, 0, frame_lo, n_frames, H, W, sampling, hip_stream);
+}
+
+extern "C" int tdeed_jpeg_pixels_rows(const int16_t* coeff, const int* frame_table_set, const uint8_t* table_sets, int n_sets,
+                                      uint8_t* out, long out_rows, const int* dst_row, int frame_lo, int n_frames, int H, int W,
+                                      int sampling, void* hip_stream) {
+  TD_CHECK(dst_row && (((uintptr_t)dst_row) & 3) == 0, "jpeg_pixels_rows: dst_row must be a 4-byte aligned device pointer");
+  TD_CHECK(out_rows > 0, "jpeg_pixels_rows: out_rows %ld", out_rows);
+  return jpeg_pixels_any(coeff, frame_table_set, table_sets, n_sets, out, dst_row, out_rows, frame_lo, n_frames, H, W, sampling,
+                         hip_stream);
 }

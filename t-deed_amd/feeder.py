@@ -16,7 +16,8 @@ over PCIe, no overlap with the forward.  Here
 
 Only plumbing lives here (host memory, streams, events); nothing in this file computes on the device, with one opt-in
 exception: `load_video_device` hands the JPEG bytes of a video to the decode kernels (csrc/jpeg.hip) and returns the
-frames as a device tensor.
+frames as a device tensor, and `device_clip_batches` does the same per training batch (`clip_batches` with the decode on
+the device).
 """
 import os
 
@@ -104,7 +105,7 @@ class DeviceJpegs:
     as the chunks need it (`stream_through`).  chunks: [(frame_lo, frame_hi, waves tensor | None)]; status: int32 per
     segment row, zero-filled."""
 
-    def __init__(self, packed, device, chunk_frames, piece_bytes=16 << 20):
+    def __init__(self, packed, device, chunk_frames, piece_bytes=16 << 20, rows=None):
         from . import jpegdev
         self.packed, self.piece = packed, int(piece_bytes)
         n = packed.n_frames
@@ -112,6 +113,11 @@ class DeviceJpegs:
         waves = [packed.waves(lo, hi) for lo, hi in bounds]
         parts = [packed.segments.reshape(-1).view(np.uint8), packed.frame_set.view(np.uint8)] + \
                 [w.reshape(-1).view(np.uint8) for w in waves] + [packed.table_sets.reshape(-1)]
+        if rows is not None:                        # the row of every frame in the output (ops.jpeg_pixels_rows): same copy
+            rows = np.ascontiguousarray(rows, dtype=np.int32)
+            if rows.shape != (n,):
+                raise ValueError(f"DeviceJpegs: {rows.shape} rows for {n} frames")
+            parts.append(rows.view(np.uint8))
         offs, total = [], 0
         for a in parts:
             offs.append(total)
@@ -129,7 +135,8 @@ class DeviceJpegs:
             return meta[offs[i]:offs[i] + nbytes].view(dtype).view(*shape)
         self.segments = view(0, torch.int32, (packed.n_segments, 6))
         self.frame_set = view(1, torch.int32, (n,))
-        self.table_sets = view(len(parts) - 1, torch.uint8, (packed.n_sets, jpegdev.TABLE_SET_BYTES))
+        self.table_sets = view(2 + len(waves), torch.uint8, (packed.n_sets, jpegdev.TABLE_SET_BYTES))
+        self.dst_row = view(3 + len(waves), torch.int32, (n,)) if rows is not None else None
         self.chunks = [(lo, hi, view(2 + i, torch.int32, (w.shape[0], 2)) if w.shape[0] else None)
                        for i, ((lo, hi), w) in enumerate(zip(bounds, waves))]
         src = packed.stream if isinstance(packed.stream, torch.Tensor) else torch.from_numpy(packed.stream_np)
@@ -154,16 +161,28 @@ class DeviceJpegs:
         return int((seg[rows, 3].astype(np.int64) + seg[rows, 4]).max()) + 8 if rows.size else 0
 
 
-def decode_packed(packed, out, max_coeff_bytes=512 << 20):
+def coeff_chunk(packed, max_coeff_bytes=512 << 20):
+    """(int16 values per frame, frames per chunk) of `decode_packed`'s coefficient buffer under max_coeff_bytes"""
+    from . import ops
+    fc = ops.jpeg_frame_coeffs(packed.width, packed.height, packed.samp)
+    return fc, min(max(1, int(max_coeff_bytes) // (2 * fc)), 65535, max(packed.n_frames, 1))
+
+
+def decode_packed(packed, out, max_coeff_bytes=512 << 20, rows=None, coeff=None):
     """Run the entropy and pixel kernels over a `jpegdev.PackedJpegs` on the current stream: frame j of the pack lands in
     out[j] (device uint8 (>= n_frames,3,H,W)); frames without a table set are left untouched.  The coefficient buffer is
     transient and holds at most max_coeff_bytes (at least one frame).  Returns (DeviceJpegs, number of chunks); nothing is
-    synchronised -- the statuses are in `.status` on the device."""
+    synchronised -- the statuses are in `.status` on the device.
+    rows: int32 (n_frames,) -- frame j lands in row rows[j] of out instead (a contiguous (...,3,H,W) buffer flattened to
+    rows; a negative row stores nothing): the frames of a clip batch (`device_clip_batches`).  coeff: a caller-owned int16
+    buffer of at least `coeff_chunk` values to use instead of a transient one."""
     from . import ops
-    fc = ops.jpeg_frame_coeffs(packed.width, packed.height, packed.samp)
-    per = min(max(1, int(max_coeff_bytes) // (2 * fc)), 65535, max(packed.n_frames, 1))
-    dj = DeviceJpegs(packed, out.device, per)
-    coeff = torch.empty(per * fc, dtype=torch.int16, device=out.device)
+    fc, per = coeff_chunk(packed, max_coeff_bytes)
+    dj = DeviceJpegs(packed, out.device, per, rows=rows)
+    if coeff is None:
+        coeff = torch.empty(per * fc, dtype=torch.int16, device=out.device)
+    elif coeff.numel() < per * fc:
+        raise ValueError(f"decode_packed: the coefficient buffer holds {coeff.numel()} values, a chunk needs {per * fc}")
     chunks = 0
     for lo, hi, waves in dj.chunks:
         if waves is None:
@@ -172,7 +191,10 @@ def decode_packed(packed, out, max_coeff_bytes=512 << 20):
         coeff[:(hi - lo) * fc].zero_()
         ops.jpeg_entropy(dj.stream, dj.segments, waves, dj.table_sets, packed.width, packed.height, packed.samp, lo, hi - lo,
                          coeff, dj.status)
-        ops.jpeg_pixels(coeff, dj.frame_set, dj.table_sets, out, lo, hi - lo, packed.samp)
+        if rows is None:
+            ops.jpeg_pixels(coeff, dj.frame_set, dj.table_sets, out, lo, hi - lo, packed.samp)
+        else:
+            ops.jpeg_pixels_rows(coeff, dj.frame_set, dj.table_sets, out, dj.dst_row, lo, hi - lo, packed.samp)
         chunks += 1
     return dj, chunks
 
@@ -668,6 +690,185 @@ def clip_batches(clips, batch_size, frame_shape, clip_len, pool=None, depth=3, p
     finally:
         if own:
             pool.close()
+
+
+def _clip_names(paths, stride):
+    base, start, pad_start, pad_end, ndigits, length = paths
+    nums = [start + j * stride for j in range(length - pad_start - pad_end)]
+    return [(os.path.join(base, "frame") + str(n) + ".jpg") if ndigits == -1 else (base + "/" + str(n).zfill(ndigits) + ".jpg")
+            for n in nums]
+
+
+def clip_batch_rows(group, clip_len):
+    """The row table of one batch of `device_clip_batches` (pure; no file is touched).  group: B clip descriptors.  The
+    batch slot is (n,B,T,3,H,W) with n = 2 when the descriptors carry 'paths2' (the mixup twin: rows B*T .. 2*B*T - 1),
+    flattened to rows: real frame j of clip i sits in row i*T + pad_start + j.
+    -> (names, rows, zero): the file of every real frame, clip by clip and the twins behind; int32 row per file; the row
+    ranges [(lo, hi), ...] that hold no frame (start and end padding of every clip), which a batch shows as zeros."""
+    B, T = len(group), int(clip_len)
+    names, rows, zero = [], [], []
+    for half, (kp, ks) in enumerate((("paths", "stride"), ("paths2", "stride2"))):
+        if half and "paths2" not in group[0]:
+            break
+        for i, c in enumerate(group):
+            _, _, pad_start, pad_end, _, length = c[kp]
+            n_real = length - pad_start - pad_end
+            if pad_start < 0 or n_real < 0 or pad_start + n_real > T:
+                raise ValueError(f"clip {i}: {pad_start} + {n_real} frames do not fit a clip of {T}")
+            first = (half * B + i) * T
+            names += _clip_names(c[kp], c.get(ks, 1))
+            rows += range(first + pad_start, first + pad_start + n_real)
+            if pad_start:
+                zero.append((first, first + pad_start))
+            if pad_start + n_real < T:
+                zero.append((first + pad_start + n_real, first + T))
+    return names, np.asarray(rows, dtype=np.int32), zero
+
+
+def _read_file_stat(path):
+    with open(path, "rb") as f:
+        st = os.fstat(f.fileno())
+        return f.read(), st.st_size, st.st_mtime_ns
+
+
+class _DeviceSlots:
+    """The `depth` device batch slots of `device_clip_batches` and their release events (the `_slot` holder of its
+    batches: `feeder.done` calls release)."""
+
+    def __init__(self, depth, shape, device):
+        self.buf = [torch.empty(shape, dtype=torch.uint8, device=device) for _ in range(depth)]
+        self.consumed = [None] * depth
+        self.out = [False] * depth
+
+    def release(self, j, stream=None):
+        ev = torch.cuda.Event()
+        ev.record(stream if stream is not None else torch.cuda.current_stream())
+        self.consumed[j] = ev
+        self.out[j] = False
+
+
+def device_clip_batches(clips, batch_size, frame_shape, clip_len, device="cuda", pool=None, depth=3, pad=True,
+                        max_coeff_bytes=512 << 20, parse_cache=None):
+    """`clip_batches` with the decode on the device: the same descriptors, the same batches bit for bit, but 'frame' is a
+    DEVICE uint8 (B,T,3,H,W) tensor decoded by csrc/jpeg.hip from the JPEG files, which cross the host-device link
+    instead of the decoded frames.  A descriptor may carry 'paths2' / 'stride2' for the mixup twin: the batch then holds
+    'frame2' as well (both halves of one (2,B,T,3,H,W) slot, one pack, one decode).  Every batch brings the hand-over of
+    `prefetch`'s device batches ('_slot'): bracket its use with `wait(batch)` / `done(batch)`, or iterate through
+    `prefetch` (`TDEEDModel.epoch()` does); a slot is decoded into again only after its batch was released.
+
+    All device work runs on one decode stream of the feed: the upload of the packed entropy stream and tables
+    (`jpegdev.pack_frames` over the batch's files, `DeviceJpegs`), the kernels (`decode_packed` with the row table of
+    `clip_batch_rows`, one persistent coefficient buffer chunked under max_coeff_bytes), the zeros of the padding rows
+    (those rows only, every batch) and the copies of host-decoded frames.  The host never waits for the device as a
+    whole, and the consumer's stream is never synchronised: the statuses of batch b are copied to page-locked memory
+    behind an event, batch b + 1 is queued (when a slot is free) before the host waits for that event, and only then are
+    b's statuses read.  Frames outside the decoder's subset (`packed.fallback`) and frames whose status is non-zero are
+    decoded with `read_frame` and copied into their rows on the decode stream -- whatever Pillow does with such a file,
+    raising included, is then the behaviour; a frame of another size raises ValueError.
+    pool: a DecodePool whose threads read the files.  parse_cache: a `jpegdev.ParseCache` (default: a new one for this
+    call) -- keep one across epochs and the files are parsed once.  pad: as for `clip_batches`, the rows behind a clip's
+    real frames are zero either way.  The tail of `clips` that does not fill a batch is dropped.  `last_decode_stats`
+    holds the numbers of the batch yielded last."""
+    from collections import deque
+    from . import jpegdev
+    from .streams import new_stream
+    B, T = int(batch_size), int(clip_len)
+    C, H, W = (int(v) for v in frame_shape)
+    if C != 3:
+        raise ValueError(f"device_clip_batches: frames are (3,H,W), not {tuple(frame_shape)}")
+    dev = torch.device(device)
+    cache = parse_cache if parse_cache is not None else jpegdev.ParseCache()
+    groups = [clips[lo:lo + B] for lo in range(0, len(clips) - B + 1, B)]
+    if not groups:
+        return
+    twin = "paths2" in groups[0][0]
+    halves = 2 if twin else 1
+    n_rows = halves * B * T
+    dec = new_stream(dev)
+    with torch.cuda.stream(dec):
+        slots = _DeviceSlots(depth, (halves, B, T, 3, H, W), dev)
+    host_status = [None] * depth                    # page-locked int32, grown as a batch needs
+    coeff = [None]
+    reader = pool.ex.map if pool is not None and hasattr(pool, "ex") else map
+
+    def fallback_copy(rows_view, names, rows, f):
+        fr = read_frame(names[f])
+        if tuple(fr.shape) != (3, H, W):
+            raise ValueError(f"frame {names[f]}: {tuple(fr.shape)} does not fit the buffer {(3, H, W)}")
+        rows_view[int(rows[f])].copy_(fr)
+
+    def enqueue(bi):
+        j = bi % depth
+        group = groups[bi]
+        if any(("paths2" in c) != twin for c in group):
+            raise ValueError("device_clip_batches: either every descriptor has 'paths2' or none")
+        names, rows, zero = clip_batch_rows(group, T)
+        files = list(reader(_read_file_stat, names))
+        infos = [cache.lookup(nm, size, mtime, data) for nm, (data, size, mtime) in zip(names, files)]
+        packed = jpegdev.pack_frames([f[0] for f in files], infos)
+        if packed.n_segments and (packed.height, packed.width) != (H, W):
+            raise ValueError(f"batch {bi}: frames {(3, packed.height, packed.width)} do not fit the buffer {(3, H, W)}")
+        slot = slots.buf[j]
+        rows_view = slot.view(n_rows, 3, H, W)
+        st = SimpleNamespace(bi=bi, j=j, names=names, rows=rows, packed=packed, rows_view=rows_view, dj=None, event=None,
+                             status=None, chunks=0, late=[])
+        with torch.cuda.stream(dec):
+            if slots.consumed[j] is not None:       # the consumer's last use of the slot, on whichever stream it ran
+                dec.wait_event(slots.consumed[j])
+                slots.consumed[j] = None
+            for lo, hi in zero:
+                rows_view[lo:hi].zero_()
+            if packed.n_segments:
+                fc, per = coeff_chunk(packed, max_coeff_bytes)
+                if coeff[0] is None or coeff[0].numel() < per * fc:
+                    coeff[0] = torch.empty(per * fc, dtype=torch.int16, device=dev)
+                st.dj, st.chunks = decode_packed(packed, slot, max_coeff_bytes, rows=rows, coeff=coeff[0])
+                if host_status[j] is None or host_status[j].numel() < packed.n_segments:
+                    host_status[j] = torch.empty(packed.n_segments, dtype=torch.int32).pin_memory()
+                st.status = host_status[j][:packed.n_segments]
+                st.status.copy_(st.dj.status[:packed.n_segments], non_blocking=True)
+            for f in packed.fallback:
+                fallback_copy(rows_view, names, rows, f)
+            st.event = torch.cuda.Event()
+            st.event.record(dec)
+        slots.out[j] = True
+        return st
+
+    def finish(st):
+        st.event.synchronize()                      # this batch's decode; the next batch is already queued behind it
+        packed = st.packed
+        if st.status is not None:
+            st.late = sorted(int(f) for f in np.unique(packed.segments[st.status.numpy() != 0, 0]))
+        with torch.cuda.stream(dec):
+            for f in st.late:
+                fallback_copy(st.rows_view, st.names, st.rows, f)
+            ready = torch.cuda.Event()
+            ready.record(dec)
+        n_bad = len(packed.fallback) + len(st.late)
+        last_decode_stats.clear()
+        last_decode_stats.update(frames=n_rows, device_frames=len(st.names) - n_bad, fallback_frames=n_bad,
+                                 stream_bytes=int(st.dj.uploaded + st.dj.meta_bytes) if st.dj is not None else 0,
+                                 table_sets=packed.n_sets, segments=packed.n_segments, chunks=st.chunks,
+                                 status_frames=list(st.late))
+        group = groups[st.bi]
+        extra = {k: [c[k] for c in group] for k in group[0] if k not in ("paths", "stride", "paths2", "stride2")}
+        batch = dict(frame=slots.buf[st.j][0], _slot=(slots, st.j, ready), **extra)
+        if twin:
+            batch["frame2"] = slots.buf[st.j][1]
+        return batch
+
+    queued, nxt = deque(), 0
+    while True:
+        # run one batch ahead of the one handed out, as far as released slots allow
+        while nxt < len(groups) and len(queued) < 2 and not slots.out[nxt % depth]:
+            queued.append(enqueue(nxt))
+            nxt += 1
+        if not queued:
+            if nxt < len(groups):
+                raise RuntimeError(f"device_clip_batches: the batch handed out {depth} batches ago was never released "
+                                   "(feeder.done / feeder.prefetch); its slot cannot be reused")
+            return
+        yield finish(queued.popleft())
 
 
 class PinnedRing:

@@ -3,7 +3,8 @@ tables for the kernels, and a slow numpy model of the whole decode that the test
 
 Nothing here decodes pixels on the product path: `parse` walks the markers of one file, `pack` lays the entropy-coded
 segments of many files into one buffer with a segment table and de-duplicated table sets (the layouts of
-csrc/jpeg_core.h), and the kernels do the rest.  Supported files: baseline / extended-sequential Huffman (SOF0, SOF1),
+csrc/jpeg_core.h), and the kernels do the rest.  `pack_frames` is `pack` for the frames of a clip batch (many videos,
+already parsed infos accepted), `ParseCache` keeps the parse results across epochs.  Supported files: baseline / extended-sequential Huffman (SOF0, SOF1),
 8-bit samples, greyscale or YCbCr with component ids 1, 2, 3, luma sampling 1x1, 2x1 or 2x2 with 1x1 chroma, one
 interleaved scan, optional restart intervals, no Adobe marker.  Everything else makes `parse` return None, and the
 caller decodes that frame with Pillow (feeder.load_video_device).
@@ -297,7 +298,18 @@ def pack(datas, pinned=True):
     """Pack the files of one video (bytes or uint8 arrays, one per frame) -> PackedJpegs.  Geometry and sampling are
     those of the first supported frame; a supported frame of another geometry raises ValueError (as feeder.load_video
     does when a frame does not fit), one of another sampling takes the fallback."""
-    infos = [parse(d) for d in datas]
+    return pack_frames(datas, None, pinned)
+
+
+def pack_frames(datas, infos=None, pinned=True):
+    """`pack` for any list of frames -- the frames of a clip batch come from many videos -- with the same layout and the
+    same rules: geometry and sampling of the first supported frame, another sampling -> fallback, another geometry ->
+    ValueError.  infos: the `parse` result of every file (None for an unsupported one) when the caller has them already,
+    e.g. from a ParseCache; an info that carries `table_set` (ParseCache's do) spares building the tables again."""
+    if infos is None:
+        infos = [parse(d) for d in datas]
+    elif len(infos) != len(datas):
+        raise ValueError(f"pack_frames: {len(infos)} infos for {len(datas)} files")
     arrs = [np.frombuffer(d, np.uint8) if not isinstance(d, np.ndarray) else d for d in datas]
     first = next((i for i in infos if i is not None), None)
     n = len(datas)
@@ -316,7 +328,8 @@ def pack(datas, pinned=True):
         sid = sets.get(info.tables_key)
         if sid is None:
             sid = sets[info.tables_key] = len(set_rows)
-            set_rows.append(table_set(info))
+            ready = getattr(info, "table_set", None)
+            set_rows.append(table_set(info) if ready is None else ready)
         frame_set[f] = sid
         ri = info.restart_interval or info.mcus
         for s in range(info.n_segments):
@@ -346,6 +359,51 @@ def pack(datas, pinned=True):
         stream_np[off:off + ln] = arrs[f][src:src + ln]
     tsets = np.stack(set_rows) if set_rows else np.zeros((0, TABLE_SET_BYTES), np.uint8)
     return PackedJpegs(first.width, first.height, first.samp, n, stream, stream_np, seg, tsets, frame_set, fallback)
+
+
+class ParseCache:
+    """What `parse` finds in a file, kept per (path, size, mtime_ns), so that an epoch over files seen before only reads
+    them and copies their segment bytes (`pack_frames(datas, infos)`).  An entry is what pack_frames needs short of the
+    file's bytes: geometry, sampling, the segment byte ranges, tables_key and the built table set (one array per distinct
+    tables_key, shared by its files); None for a file outside the decoder's subset.  Never pixel data or file contents.
+    A file whose size or modification time changed is parsed again and replaces its entry."""
+
+    def __init__(self):
+        self._files = {}            # path -> (size, mtime_ns, info | None)
+        self._sets = {}             # tables_key -> table set (uint8 TABLE_SET_BYTES)
+        self.hits = self.misses = 0
+
+    def __len__(self):
+        return len(self._files)
+
+    def lookup(self, path, size, mtime_ns, data):
+        """the entry of `path`, whose size / mtime_ns (os.stat) and bytes the caller has read"""
+        e = self._files.get(path)
+        if e is not None and e[0] == size and e[1] == mtime_ns:
+            self.hits += 1
+            return e[2]
+        self.misses += 1
+        full = parse(data)
+        info = None
+        if full is not None:
+            ts = self._sets.get(full.tables_key)
+            if ts is None:
+                ts = self._sets[full.tables_key] = table_set(full)
+            info = SimpleNamespace(width=full.width, height=full.height, samp=full.samp, ncomp=full.ncomp,
+                                   restart_interval=full.restart_interval, mcus=full.mcus, n_segments=full.n_segments,
+                                   seg_start=full.seg_start, seg_len=full.seg_len, tables_key=full.tables_key, table_set=ts)
+        self._files[path] = (size, mtime_ns, info)
+        return info
+
+    def get(self, path, data=None):
+        """the entry of `path` (stat here; the file is read only when it has to be parsed and `data` is not given)"""
+        import os
+        st = os.stat(path)
+        e = self._files.get(path)
+        if data is None and not (e is not None and e[0] == st.st_size and e[1] == st.st_mtime_ns):
+            with open(path, "rb") as f:
+                data = f.read()
+        return self.lookup(path, st.st_size, st.st_mtime_ns, data)
 
 
 # ------------------------------------------------------------------------------------------------- the numpy model

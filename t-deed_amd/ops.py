@@ -1229,6 +1229,33 @@ def jpeg_pixels(coeff, frame_set, table_sets, out, frame_lo, n_frames, sampling)
     return out
 
 
+def jpeg_pixels_rows(coeff, frame_set, table_sets, out, dst_row, frame_lo, n_frames, sampling):
+    """jpeg_pixels with a row table: pack frame f (frame_lo <= f < frame_lo + n_frames) -> row dst_row[f] of out, a contiguous
+    uint8 (...,3,H,W) buffer whose leading dimensions are flattened to rows (a (B,T,3,H,W) batch slot: row i * T + t).
+    dst_row int32 (>= frame_lo + n_frames,) on the device; a frame whose row is negative or past the last row, or whose
+    frame_set entry is -1, stores nothing."""
+    dev = out.device
+    _chk(out, "out", torch.uint8)
+    _chk(coeff, "coeff", torch.int16)
+    _chk_jpeg_tables("jpeg_pixels_rows", dev, frame_set=(frame_set, torch.int32), table_sets=(table_sets, torch.uint8),
+                     dst_row=(dst_row, torch.int32))
+    if out.dim() < 4 or out.shape[-3] != 3:
+        raise ValueError("jpeg_pixels_rows: out must be (...,3,H,W)")
+    H, W = int(out.shape[-2]), int(out.shape[-1])
+    rows = out.numel() // (3 * H * W)
+    if table_sets.dim() != 2 or table_sets.shape[1] != 4240 or table_sets.shape[0] < 1:
+        raise ValueError("jpeg_pixels_rows: table_sets (n_sets, 4240)")
+    if rows < 1 or frame_lo < 0 or n_frames < 1 or min(frame_set.numel(), dst_row.numel()) < frame_lo + n_frames:
+        raise ValueError(f"jpeg_pixels_rows: frames {frame_lo}..{frame_lo + n_frames} outside the {frame_set.numel()} of frame_set / "
+                         f"{dst_row.numel()} of dst_row, or out has no row")
+    fc = jpeg_frame_coeffs(W, H, sampling)
+    if coeff.numel() < int(n_frames) * fc:
+        raise ValueError(f"jpeg_pixels_rows: coeff holds {coeff.numel()} values, {n_frames} frames need {int(n_frames) * fc}")
+    call("tdeed_jpeg_pixels_rows", ptr(coeff), ptr(frame_set), ptr(table_sets), table_sets.shape[0], ptr(out), rows, ptr(dst_row),
+         int(frame_lo), int(n_frames), int(H), int(W), int(sampling), stream_ptr())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- SGP contractions (sgp_gemm.hip)
 def sgp_gemm_ksteps(K):
     return int(_lib.load().tdeed_sgp_gemm_ksteps(K))

@@ -2,6 +2,8 @@
 
     python tools/bench_train_feed.py [--videos 4] [--frames 300] [--clips 96] [--procs 16]     one JSON record, printed
                                                                                                and written to profiles/train_feed.json
+    python tools/bench_train_feed.py --decode-device [same options]      the JPEG decode on the device against the decode on the
+                                                                         host (decode_device_main), profiles/train_feed_device_decode.json
 
 Synthetic JPEG videos (224 x 224, quality 90) are written to a temporary directory with a label file.  Measured:
   loader   clips/s of `trainclips.ResidentClips` alone (T = 100, batch 8), without mixup (the uint8 batch) and with it (labels
@@ -76,6 +78,129 @@ def decoded_loader(root, videos, pool, mixup, dataset_len, batch_size, seed):
         yield b
 
 
+def device_loader(root, videos, threads, mixup, dataset_len, batch_size, seed, cache, stats=None):
+    """The same draws fed by `feeder.device_clip_batches`: the JPEG files go to the device and are decoded there, the
+    mixup twin in the same slot.  stats: a list that collects the per-batch `feeder.last_decode_stats`."""
+    T, r = CFG["clip_len"], CFG["radi_displacement"]
+    tab = TC.train_clip_table(videos, CLASSES, T)
+    draws = list(TC.ClipDraws(len(tab.clip_video), dataset_len, batch_size, mixup, seed, drop_last=True))
+
+    def paths(c):
+        return feeder.load_paths(root, DATASET, videos[int(tab.clip_video[c])]["video"], int(tab.clip_base[c]),
+                                 int(tab.clip_base[c]) + T, stride=1)
+    clips = []
+    for ia, ib in draws:
+        for i, c in enumerate(ia):
+            d = dict(paths=paths(c), stride=1)
+            if mixup:
+                d.update(paths2=paths(ib[i]), stride2=1)
+            clips.append(d)
+    feed = feeder.device_clip_batches(clips, batch_size, (3, H, W), T, pool=threads, parse_cache=cache)
+    for (ia, ib), got in zip(draws, feed):
+        if stats is not None:
+            stats.append(dict(feeder.last_decode_stats))
+        lab, labD = TC.rasterise_labels(tab, ia, T, 1, r)
+        b = dict(frame=got["frame"], _slot=got["_slot"], label=torch.from_numpy(lab), labelD=torch.from_numpy(labD))
+        if mixup:
+            lab2, labD2 = TC.rasterise_labels(tab, ib, T, 1, r)
+            b.update(frame2=got["frame2"], label2=torch.from_numpy(lab2), labelD2=torch.from_numpy(labD2))
+        yield b
+
+
+def decode_device_main(a):
+    """--decode-device: `feeder.device_clip_batches` against `feeder.clip_batches` + ProcessDecodePool + `prefetch` on the
+    same noise-frame videos, in one run, the routes alternating: (a) the loader alone, the device feed with a cold and
+    with a warm parse cache, (b) a 200MF training epoch with mixup fed by each; and the bytes per batch that cross the
+    host-device link.  One JSON record, printed and written to profiles/train_feed_device_decode.json."""
+    from tdeed_amd import jpegdev
+    from tdeed_amd.model import TDEEDModel
+    from types import SimpleNamespace
+    T, bs = CFG["clip_len"], a.batch
+    root = tempfile.mkdtemp(prefix="tdeed_train_feed_")
+    out = dict(kind="train_feed_device_decode", cfg=CFG, videos=a.videos, frames_per_video=a.frames, clips_per_epoch=a.clips,
+               batch_size=bs, decode_processes=a.procs, read_threads=a.read_threads, repeats=a.repeats,
+               device=torch.cuda.get_device_name(0))
+    pool = threads = None
+    try:
+        videos = write_videos(root, a.videos, a.frames)
+        sizes = [os.path.getsize(os.path.join(root, v["video"], f"frame{i}.jpg")) for v in videos for i in range(a.frames)]
+        out["jpeg_bytes_per_frame"] = round(float(np.mean(sizes)), 1)
+        pool = feeder.ProcessDecodePool(a.procs)
+        threads = feeder.DecodePool(a.read_threads) if a.read_threads > 0 else None       # None: the feed reads the files itself
+        n_epoch = a.clips // bs * bs
+
+        def drain(loader):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in feeder.prefetch(loader, "cuda"):
+                pass
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+
+        # ---- (a) the loader alone, plain clips; every round draws new clips, the same for both routes
+        t_host, t_cold, t_warm, stats = [], [], [], []
+        for rep in range(a.repeats + 1):
+            seed = 10 + rep
+            th = drain(decoded_loader(root, videos, pool, False, a.clips, bs, seed))
+            tc = drain(device_loader(root, videos, threads, False, a.clips, bs, seed, jpegdev.ParseCache()))
+            cache = jpegdev.ParseCache()
+            drain(device_loader(root, videos, threads, False, a.clips, bs, seed, cache))
+            tw = drain(device_loader(root, videos, threads, False, a.clips, bs, seed, cache, stats if rep else None))
+            if rep:                                                            # the first round warms up
+                t_host.append(th), t_cold.append(tc), t_warm.append(tw)
+        out["loader"] = dict(host_decoded=_rate(t_host, n_epoch), device_first_epoch=_rate(t_cold, n_epoch),
+                             device_warm_cache=_rate(t_warm, n_epoch))
+        out["loader"]["device_warm_over_host"] = round(out["loader"]["device_warm_cache"]["clips_per_s"] /
+                                                       out["loader"]["host_decoded"]["clips_per_s"], 3)
+        out["link_bytes_per_batch"] = dict(host_decoded=bs * T * 3 * H * W,
+                                           device_decoded=int(np.mean([s["stream_bytes"] for s in stats])))
+        out["device_batch"] = {k: float(np.mean([s[k] for s in stats])) for k in
+                               ("frames", "device_frames", "fallback_frames", "table_sets", "segments", "chunks")}
+
+        # ---- (b) a training epoch with mixup fed by either route
+        m = TDEEDModel(device="cuda", args=SimpleNamespace(modality="rgb", temporal_arch="ed_sgp_mixer", pretrain=None, **CFG))
+        m.load({k: torch.from_numpy(v) for k, v in synth.make_state(state_layout.model_state_shapes(CFG), 0).items()})
+        opt, _ = m.get_optimizer({"lr": 1e-4})
+        cache = jpegdev.ParseCache()
+        rnd = {"i": 0}
+        routes = dict(A_host_decoded=lambda: decoded_loader(root, videos, pool, True, a.clips, bs, 2 + rnd["i"]),
+                      C_device_decoded=lambda: device_loader(root, videos, threads, True, a.clips, bs, 2 + rnd["i"], cache))
+        times, losses = {k: [] for k in routes}, {}
+        for rep in range(a.repeats + 1):
+            rnd["i"] = rep
+            for k, mk in routes.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                losses[k] = m.epoch(mk(), optimizer=opt)
+                torch.cuda.synchronize()
+                if rep:
+                    times[k].append(time.perf_counter() - t0)
+        out["epoch"] = {k: dict(_rate(v, n_epoch), last_loss=round(float(losses[k]), 5)) for k, v in times.items()}
+        ra, rc = out["epoch"]["A_host_decoded"], out["epoch"]["C_device_decoded"]
+        out["epoch"]["speedup_C_over_A"] = round(rc["clips_per_s"] / ra["clips_per_s"], 3)
+        out["epoch"]["C_not_slower_than_A"] = bool(rc["clips_per_s"] >= ra["clips_per_s_min"])
+        out["notes"] = [
+            "the JPEG files stay in the page cache on both routes: decode is measured, not disk",
+            "loader: plain clips (no twin), drained through feeder.prefetch; device_first_epoch parses every file "
+            "(jpegdev.parse in Python), device_warm_cache has every file in the ParseCache",
+            "epoch: mixup as train_tdeed.py trains; route A uploads 'frame2' by epoch()'s blocking copy, route C decodes it into "
+            "the second half of the batch slot; route C's parse cache is cold in the warm-up round only where clips repeat",
+            "link_bytes_per_batch is per plain batch; with the twin both routes move twice as much"]
+    finally:
+        if pool is not None:
+            pool.close()
+        if threads is not None:
+            threads.close()
+        shutil.rmtree(root, ignore_errors=True)
+    line = json.dumps(out)
+    print(line)
+    path = a.out if a.out else os.path.join(ROOT, "profiles", "train_feed_device_decode.json")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as fh:
+        fh.write(line + "\n")
+    return 0
+
+
 def _rate(times, clips):
     t = np.asarray(times)
     return dict(clips_per_s=round(clips / float(np.median(t)), 1), clips_per_s_min=round(clips / float(t.max()), 1),
@@ -90,8 +215,16 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--procs", type=int, default=16)
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_feed.json"))
+    ap.add_argument("--decode-device", action="store_true",
+                    help="measure feeder.device_clip_batches against the host-decoded feed instead (profiles/train_feed_device_decode.json)")
+    ap.add_argument("--read-threads", type=int, default=0,
+                    help="--decode-device: threads that read the files (0: the feed's own thread; the files sit in the page cache, "
+                         "where a read is too short to be worth a hand-over between threads)")
+    ap.add_argument("--out", default=None, help="default: profiles/train_feed.json (train_feed_device_decode.json with --decode-device)")
     a = ap.parse_args()
+    if a.decode_device:
+        return decode_device_main(a)
+    a.out = a.out or os.path.join(ROOT, "profiles", "train_feed.json")
     from tdeed_amd.model import TDEEDModel
     from types import SimpleNamespace
     T, r, bs = CFG["clip_len"], CFG["radi_displacement"], a.batch
