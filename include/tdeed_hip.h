@@ -913,6 +913,31 @@ int tdeed_jpeg_pixels_rows(const int16_t* coeff, const int* frame_table_set, con
                            uint8_t* out, long out_rows, const int* dst_row, int frame_lo, int n_frames, int H, int W,
                            int sampling, void* hip_stream);
 
+/* ---- entropy streams that stay on the device (trainclips.ResidentJpegClips).  A piece is a run of MCUs of one segment
+ * that decodes on its own from a recorded decoder state; the piece table has 72-byte rows (JcPiece, csrc/jpeg_core.h:
+ * int64 position of the next unread byte in the stream; int32 segment, first MCU, MCU count, table set, bytes left in the
+ * segment, spare; the state: uint64 bits, int32 byte offset in the segment, valid bits n, pad, marker, three DC predictors,
+ * spare).  MCU m of a segment starts a piece when m is its first MCU or m % split_mcus == 0.
+ * tdeed_jpeg_entropy_index: one lane per row of `segments`, the rows of one shard whose byte offsets count from
+ *   stream + base (stream_bytes: the whole resident stream, may exceed 2^31).  Stores no coefficients; writes the piece
+ *   rows of row i at pieces[piece_off[i] ..] (piece_off int32 [n_segments + 1], below n_pieces; `segment` = seg_base + i)
+ *   and status[i] as tdeed_jpeg_entropy does.
+ * tdeed_jpeg_entropy_items: one lane per item; items int32 [n_items][2] = (piece row, coefficient slot), waves int32
+ *   [n_waves][2] = (first item, count <= 64), the items of a wave of one table set.  Slots slot_lo .. slot_lo + n_slots - 1
+ *   decode into coeff (zero-filled by the caller).  An item or row that points outside any buffer counts as status 7 and
+ *   touches nothing; *err (uint32, on the device) gets bit `status` set for every non-zero status met.
+ * tdeed_jpeg_slot_fill: rows of out uint8 [n_rows][frame_bytes] that no decode fills: fill[row] = -2 leaves the row, -1
+ *   zeroes it, r >= 0 copies row r of side uint8 [side_rows][frame_bytes] (r >= side_rows stores nothing). */
+int tdeed_jpeg_entropy_index(const uint8_t* stream, long stream_bytes, long base, const int* segments, int n_segments,
+                             const int* waves, int n_waves, const uint8_t* table_sets, int n_sets, int W, int H, int sampling,
+                             int split_mcus, const int* piece_off, int seg_base, void* pieces, int n_pieces, int* status,
+                             void* hip_stream);
+int tdeed_jpeg_entropy_items(const uint8_t* stream, long stream_bytes, const void* pieces, int n_pieces, const int* items,
+                             int n_items, const int* waves, int n_waves, const uint8_t* table_sets, int n_sets, int W, int H,
+                             int sampling, int slot_lo, int n_slots, int16_t* coeff, unsigned* err, void* hip_stream);
+int tdeed_jpeg_slot_fill(const uint8_t* side, long side_rows, long frame_bytes, const int* fill, int n_rows, uint8_t* out,
+                         void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

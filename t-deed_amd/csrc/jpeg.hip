@@ -1,7 +1,8 @@
 // Baseline JPEG decode of a video's frames: entropy decode (one lane per segment) into an int16 coefficient buffer, then
 // dequantisation, IDCT, up-sampling and colour conversion into the planar uint8 (n,3,H,W) layout of the resident-video
 // consumers.  The arithmetic lives in jpeg_core.h (shared with tools/jpeg_host_check.cpp); tables and the packed stream
-// come from tdeed_amd/jpegdev.py.
+// come from tdeed_amd/jpegdev.py.  For entropy streams that stay on the device (trainclips.ResidentJpegClips) an index pass
+// records decoder states inside the segments and the batches decode one lane per piece.
 #include "common.h"
 #include "jpeg_core.h"
 
@@ -59,6 +60,209 @@ extern "C" int tdeed_jpeg_entropy(const uint8_t* stream, long stream_bytes, cons
                      (const JcSegment*)segments, n_segments, waves, (const JcTableSet*)table_sets, n_sets, sampling, g.mcus_x,
                      g.mcus_y, frame_lo, n_frames, (long)g.frame_blocks * 64, coeff, status);
   TD_LAUNCH_CHECK("jpeg_entropy");
+  return TDEED_OK;
+}
+
+// =========================================================================== resident streams: index pass and pieces
+// The streams of a training set stay on the device (trainclips.ResidentJpegClips) and every batch decodes the frames it
+// drew.  A frame without restart markers is one segment, one lane; so one pass at construction walks every segment
+// (one lane per segment, as above, nothing stored) and records the decoder state at the split points of the segment
+// (jc_piece_count's rule): the rows of the piece table, which the batches then decode one lane per piece.
+// Row k of segment row i lands in pieces[piece_off[i] + k], as long as that stays below piece_off[i + 1] and n_pieces.
+struct PieceWriter {
+  static constexpr bool on = true;
+  JcPiece* rows;
+  long seg_pos;
+  int room, k, seg_len, segment, set, end_mcu, split;
+  __device__ __forceinline__ void operator()(int m, const JcState& st) {
+    if (k < room) {
+      JcPiece p;
+      p.pos = seg_pos + st.byte_off;
+      p.segment = segment; p.first_mcu = m; p.set = set; p.spare = 0;
+      const int to_next = split - m % split;
+      p.n_mcu = to_next < end_mcu - m ? to_next : end_mcu - m;
+      p.left = seg_len - st.byte_off;
+      p.st = st;
+      rows[k] = p;
+    }
+    ++k;
+  }
+};
+
+// segs / waves / piece_off / status: the rows of one shard (jpegdev.pack_frames), whose offsets count from stream + base;
+// seg_base: the shard's first row in the set's segment numbering (what the piece rows carry)
+__global__ __launch_bounds__(64) void jpeg_entropy_index_kernel(const uint8_t* __restrict__ stream, long stream_bytes, long base,
+                                                                const JcSegment* __restrict__ segs, int n_segments,
+                                                                const int* __restrict__ waves, const JcTableSet* __restrict__ sets,
+                                                                int n_sets, int samp, int mcus_x, int mcus_y, int split_mcus,
+                                                                const int* __restrict__ piece_off, int seg_base,
+                                                                JcPiece* __restrict__ pieces, int n_pieces, int* __restrict__ status) {
+  __shared__ __attribute__((aligned(16))) JcTableSet ts;
+  const int lane = threadIdx.x;
+  int first = waves[2 * blockIdx.x], count = waves[2 * blockIdx.x + 1];
+  if (first < 0 || first >= n_segments) return;
+  count = count < 64 ? count : 64;
+  count = count < n_segments - first ? count : n_segments - first;
+  const int set = segs[first].set;
+  if (set < 0 || set >= n_sets) {
+    if (lane < count) status[first + lane] = JC_ERR_TABLE;
+    return;
+  }
+  const u32x4* src = reinterpret_cast<const u32x4*>(sets + set);
+  u32x4* dst = reinterpret_cast<u32x4*>(&ts);
+  for (int i = lane; i < JC_TABLE_SET_BYTES / 16; i += 64) dst[i] = src[i];
+  __syncthreads();
+  if (lane >= count) return;
+  const int row = first + lane;
+  const JcSegment s = segs[row];
+  const int p_lo = piece_off[row], p_hi = piece_off[row + 1];
+  if (!jc_segment_ok(s, stream_bytes - base, n_sets, mcus_x * mcus_y) || s.set != set || p_lo < 0 || p_hi <= p_lo ||
+      p_hi > n_pieces) {
+    status[row] = JC_ERR_TABLE;
+    return;
+  }
+  PieceWriter w;
+  w.rows = pieces + p_lo; w.room = p_hi - p_lo; w.k = 0;
+  w.seg_pos = base + s.offset; w.seg_len = s.length; w.segment = seg_base + row; w.set = set;
+  w.end_mcu = s.first_mcu + s.n_mcu; w.split = split_mcus;
+  const JcState zero = jc_zero_state();
+  {                                                            // the first piece starts where the segment does
+    JcPiece p;
+    p.pos = w.seg_pos;
+    p.segment = w.segment; p.first_mcu = s.first_mcu; p.set = set; p.spare = 0;
+    const int to_next = split_mcus - s.first_mcu % split_mcus;
+    p.n_mcu = to_next < s.n_mcu ? to_next : s.n_mcu;
+    p.left = s.length;
+    p.st = zero;
+    w.rows[0] = p;
+    w.k = 1;
+  }
+  status[row] = jc_entropy_run<false>(stream + base + s.offset, s.length, zero, s.first_mcu, s.n_mcu, &ts, samp, mcus_x, mcus_y,
+                                      (int16_t*)nullptr, split_mcus, w);
+}
+
+// items[i] = (piece row, coefficient slot); waves[w] = (first item, count <= 64), the items of a wavefront sharing one
+// table set (trainclips.batch_tables).  Lane i decodes its piece into slot s's coefficient range, s in [slot_lo, slot_lo +
+// n_slots).  An item or a piece row that points outside any buffer, or whose set is not the wavefront's, counts as
+// JC_ERR_TABLE and touches nothing.  No status leaves the device per item: bit `code` of *err is set for every code met.
+__global__ __launch_bounds__(64) void jpeg_entropy_items_kernel(const uint8_t* __restrict__ stream, long stream_bytes,
+                                                                const JcPiece* __restrict__ pieces, int n_pieces,
+                                                                const int* __restrict__ items, int n_items,
+                                                                const int* __restrict__ waves, const JcTableSet* __restrict__ sets,
+                                                                int n_sets, int samp, int mcus_x, int mcus_y, int slot_lo, int n_slots,
+                                                                long frame_coefs, int16_t* __restrict__ coef,
+                                                                unsigned* __restrict__ err) {
+  __shared__ __attribute__((aligned(16))) JcTableSet ts;
+  const int lane = threadIdx.x;
+  int first = waves[2 * blockIdx.x], count = waves[2 * blockIdx.x + 1];
+  if (first < 0 || first >= n_items || count <= 0) {
+    if (lane == 0) atomicOr(err, 1u << JC_ERR_TABLE);
+    return;
+  }
+  count = count < 64 ? count : 64;
+  count = count < n_items - first ? count : n_items - first;
+  const int p0 = items[2 * first];
+  const int set = p0 >= 0 && p0 < n_pieces ? pieces[p0].set : -1;
+  if (set < 0 || set >= n_sets) {
+    if (lane == 0) atomicOr(err, 1u << JC_ERR_TABLE);
+    return;
+  }
+  const u32x4* src = reinterpret_cast<const u32x4*>(sets + set);
+  u32x4* dst = reinterpret_cast<u32x4*>(&ts);
+  for (int i = lane; i < JC_TABLE_SET_BYTES / 16; i += 64) dst[i] = src[i];
+  __syncthreads();
+  if (lane >= count) return;
+  const int pi = items[2 * (first + lane)];
+  const long f = (long)items[2 * (first + lane) + 1] - slot_lo;
+  int st = JC_ERR_TABLE;
+  if (pi >= 0 && pi < n_pieces && f >= 0 && f < n_slots) {
+    const JcPiece p = pieces[pi];
+    if (jc_piece_ok(p, stream_bytes, n_sets, mcus_x * mcus_y) && p.set == set) {
+      JcNoRecord rec;
+      st = jc_entropy_run<true>(stream + p.pos, p.left, p.st, p.first_mcu, p.n_mcu, &ts, samp, mcus_x, mcus_y,
+                                coef + f * frame_coefs, 1, rec);
+    }
+  }
+  if (st != JC_OK) atomicOr(err, 1u << st);
+}
+
+static int jpeg_resident_checks(const char* who, const void* stream, long stream_bytes, const void* waves, int n_waves,
+                                const void* table_sets, int n_sets, int W, int H, int sampling) {
+  TD_CHECK(stream && waves && table_sets, "%s: null pointer", who);
+  TD_CHECK(stream_bytes > 0 && n_waves > 0 && n_sets > 0, "%s: bad sizes", who);
+  TD_CHECK(W > 0 && H > 0 && W <= 65535 && H <= 65535, "%s: bad frame size %dx%d", who, H, W);
+  TD_CHECK(sampling >= JC_GREY && sampling <= JC_420, "%s: sampling %d (0 grey, 1 4:4:4, 2 4:2:2, 3 4:2:0)", who, sampling);
+  TD_CHECK((((uintptr_t)table_sets) & 15) == 0 && (((uintptr_t)waves) & 3) == 0,
+           "%s: table sets must be 16-byte aligned, the tables 4-byte", who);
+  return TDEED_OK;
+}
+
+extern "C" int tdeed_jpeg_entropy_index(const uint8_t* stream, long stream_bytes, long base, const int* segments, int n_segments,
+                                        const int* waves, int n_waves, const uint8_t* table_sets, int n_sets, int W, int H,
+                                        int sampling, int split_mcus, const int* piece_off, int seg_base, void* pieces,
+                                        int n_pieces, int* status, void* hip_stream) {
+  const int rc = jpeg_resident_checks("jpeg_entropy_index", stream, stream_bytes, waves, n_waves, table_sets, n_sets, W, H, sampling);
+  if (rc != TDEED_OK) return rc;
+  TD_CHECK(segments && piece_off && pieces && status, "jpeg_entropy_index: null pointer");
+  TD_CHECK(n_segments > 0 && n_pieces > 0 && seg_base >= 0 && base >= 0 && base <= stream_bytes, "jpeg_entropy_index: bad sizes");
+  TD_CHECK(split_mcus > 0, "jpeg_entropy_index: split_mcus %d", split_mcus);
+  TD_CHECK((((uintptr_t)segments | (uintptr_t)piece_off | (uintptr_t)status) & 3) == 0 && (((uintptr_t)pieces) & 7) == 0,
+           "jpeg_entropy_index: the tables must be 4-byte aligned, the piece table 8-byte");
+  const JcGeom g = jc_geom(W, H, sampling);
+  hipLaunchKernelGGL(jpeg_entropy_index_kernel, dim3(n_waves), dim3(64), 0, (hipStream_t)hip_stream, stream, stream_bytes, base,
+                     (const JcSegment*)segments, n_segments, waves, (const JcTableSet*)table_sets, n_sets, sampling, g.mcus_x,
+                     g.mcus_y, split_mcus, piece_off, seg_base, (JcPiece*)pieces, n_pieces, status);
+  TD_LAUNCH_CHECK("jpeg_entropy_index");
+  return TDEED_OK;
+}
+
+extern "C" int tdeed_jpeg_entropy_items(const uint8_t* stream, long stream_bytes, const void* pieces, int n_pieces,
+                                        const int* items, int n_items, const int* waves, int n_waves, const uint8_t* table_sets,
+                                        int n_sets, int W, int H, int sampling, int slot_lo, int n_slots, int16_t* coeff,
+                                        unsigned* err, void* hip_stream) {
+  const int rc = jpeg_resident_checks("jpeg_entropy_items", stream, stream_bytes, waves, n_waves, table_sets, n_sets, W, H, sampling);
+  if (rc != TDEED_OK) return rc;
+  TD_CHECK(pieces && items && coeff && err, "jpeg_entropy_items: null pointer");
+  TD_CHECK(n_pieces > 0 && n_items > 0 && slot_lo >= 0 && n_slots > 0, "jpeg_entropy_items: bad sizes");
+  TD_CHECK((((uintptr_t)items | (uintptr_t)err) & 3) == 0 && (((uintptr_t)pieces) & 7) == 0 && (((uintptr_t)coeff) & 15) == 0,
+           "jpeg_entropy_items: coefficients must be 16-byte aligned, the piece table 8-byte, the tables 4-byte");
+  const JcGeom g = jc_geom(W, H, sampling);
+  hipLaunchKernelGGL(jpeg_entropy_items_kernel, dim3(n_waves), dim3(64), 0, (hipStream_t)hip_stream, stream, stream_bytes,
+                     (const JcPiece*)pieces, n_pieces, items, n_items, waves, (const JcTableSet*)table_sets, n_sets, sampling,
+                     g.mcus_x, g.mcus_y, slot_lo, n_slots, (long)g.frame_blocks * 64, coeff, err);
+  TD_LAUNCH_CHECK("jpeg_entropy_items");
+  return TDEED_OK;
+}
+
+// Rows of a batch slot that no decode fills: fill[row] = -2 leaves the row alone, -1 zeroes it (a clip's padding), r >= 0
+// copies row r of the side buffer (frames kept decoded: another sampling, outside the decoder's subset, damaged).
+// blockIdx.y = row; a side row outside [0, side_rows) stores nothing.
+template <class V>
+__global__ __launch_bounds__(256) void jpeg_slot_fill_kernel(const V* __restrict__ side, long side_rows, long units,
+                                                             const int* __restrict__ fill, V* __restrict__ out) {
+  const int row = blockIdx.y;
+  const int r = fill[row];
+  if (r < -1 || r >= side_rows) return;
+  const V* src = side + (long)(r < 0 ? 0 : r) * units;
+  V* dst = out + (long)row * units;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < units; i += (long)gridDim.x * 256) dst[i] = r < 0 ? V{} : src[i];
+}
+
+extern "C" int tdeed_jpeg_slot_fill(const uint8_t* side, long side_rows, long frame_bytes, const int* fill, int n_rows,
+                                    uint8_t* out, void* hip_stream) {
+  TD_CHECK(fill && out && (side || side_rows == 0), "jpeg_slot_fill: null pointer");
+  TD_CHECK(side_rows >= 0 && frame_bytes > 0 && n_rows > 0 && n_rows <= 65535, "jpeg_slot_fill: bad sizes");
+  TD_CHECK((((uintptr_t)fill) & 3) == 0, "jpeg_slot_fill: fill must be 4-byte aligned");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const bool v16 = frame_bytes % 16 == 0 && (((uintptr_t)side | (uintptr_t)out) & 15) == 0;
+  const long units = v16 ? frame_bytes / 16 : frame_bytes;
+  const long gx = cdiv(units, 256 * 4);
+  const dim3 grid((unsigned)(gx < 64 ? gx : 64), n_rows);
+  if (v16)
+    hipLaunchKernelGGL(jpeg_slot_fill_kernel<u32x4>, grid, dim3(256), 0, st, (const u32x4*)side, side_rows, units, fill, (u32x4*)out);
+  else
+    hipLaunchKernelGGL(jpeg_slot_fill_kernel<uint8_t>, grid, dim3(256), 0, st, side, side_rows, units, fill, out);
+  TD_LAUNCH_CHECK("jpeg_slot_fill");
   return TDEED_OK;
 }
 

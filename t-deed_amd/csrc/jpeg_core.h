@@ -1,5 +1,6 @@
-// Baseline JPEG decode arithmetic shared by the device kernels (jpeg.hip) and the host check program
-// (tools/jpeg_host_check.cpp): bit reader, Huffman symbol decode, one segment's coefficient decode, the integer "islow"
+// Baseline JPEG decode arithmetic shared by the device kernels (jpeg.hip) and the host check programs
+// (tools/jpeg_host_check.cpp, tools/jpeg_split_check.cpp): bit reader, Huffman symbol decode, the coefficient decode of a
+// segment or of a piece of one (from a recorded decoder state), the integer "islow"
 // IDCT, libjpeg's "fancy" triangle up-sampling taps and the integer YCbCr -> RGB conversion.  Everything is integer
 // arithmetic and reproduces Pillow's Image.open(..).convert("RGB") (libjpeg-turbo) bit for bit on the supported subset
 // (tdeed_amd/jpegdev.py: parse).  No HIP types here: the file also compiles with a plain host C++ compiler.
@@ -14,6 +15,11 @@
 #define JC_HD static __host__ __device__ __forceinline__
 #else
 #define JC_HD static inline
+#endif
+#if defined(__HIPCC__)
+#define JC_HD_MEMBER __host__ __device__ __forceinline__
+#else
+#define JC_HD_MEMBER inline
 #endif
 #if defined(__clang__)
 #define JC_UNROLL _Pragma("unroll")
@@ -169,20 +175,68 @@ JC_HD bool jc_segment_ok(const JcSegment& s, long stream_bytes, int n_sets, int 
          s.first_mcu >= 0 && s.n_mcu > 0 && (long)s.first_mcu + s.n_mcu <= total_mcus;
 }
 
-// --------------------------------------------------------------------------------------------- one segment
-// Decodes the n_mcu MCUs from first_mcu of one frame into `coef` (the frame's zero-filled coefficient range, natural
-// order, un-dequantised).  One flat loop, one symbol per iteration: lanes of a wavefront that are in different blocks
-// still meet at the top of every iteration.  The caller has checked the row with jc_segment_ok.
-JC_HD int jc_entropy_segment(const uint8_t* seg, int len, int first_mcu, int n_mcu, const JcTableSet* ts, int samp, int mcus_x,
-                             int mcus_y, int16_t* coef) {
+// --------------------------------------------------------------------------------------------- decoder state, pieces
+// What the bit reader and the MCU loop carry across an MCU boundary: the offset of the next unread byte inside the
+// segment, the n valid bits of the buffer, pad and marker (jc_refill feeds zero bytes at the tail of a segment, so a
+// boundary inside the last four bytes already has pad > 0, and one behind a marker has marker set) and the three DC
+// predictors.  A decode that starts from a recorded state continues with the bits the whole-segment decode reads.
+struct JcState {
+  uint64_t bits;
+  int32_t byte_off, n, pad, marker;
+  int32_t pred[3];
+  int32_t spare;
+};
+
+// One row of the piece table: the MCUs [first_mcu, first_mcu + n_mcu) of segment `segment`, decodable on their own.
+// pos: position in the resident stream of the piece's next unread byte (the segment's start + st.byte_off); left: the
+// bytes from there to the end of the segment.  jpegdev.py mirrors the layout (PIECE).
+struct JcPiece {
+  int64_t pos;
+  int32_t segment, first_mcu, n_mcu, set, left, spare;
+  JcState st;
+};
+#define JC_PIECE_BYTES 72
+static_assert(sizeof(JcState) == 40 && sizeof(JcPiece) == JC_PIECE_BYTES && JC_PIECE_BYTES % 8 == 0,
+              "JcPiece layout (jpegdev.py reads it with numpy)");
+
+// false when a piece row cannot be decoded safely: byte range outside the stream, a foreign table set, MCUs outside the
+// frame, or a bit buffer state no decode leaves behind (0 <= pad <= n <= 63)
+JC_HD bool jc_piece_ok(const JcPiece& p, long stream_bytes, int n_sets, int total_mcus) {
+  return p.pos >= 0 && p.left >= 0 && p.pos <= stream_bytes && (long)p.left <= stream_bytes - p.pos && p.set >= 0 &&
+         p.set < n_sets && p.first_mcu >= 0 && p.n_mcu > 0 && (long)p.first_mcu + p.n_mcu <= total_mcus && p.st.n >= 0 &&
+         p.st.n <= 63 && p.st.pad >= 0 && p.st.pad <= p.st.n && p.st.byte_off >= 0;
+}
+
+// the split rule (jpegdev.split_points): MCU m of a segment starts a new piece when first_mcu < m and m % split_mcus == 0
+JC_HD int jc_piece_count(int first_mcu, int n_mcu, int split_mcus) {
+  return 1 + (first_mcu + n_mcu - 1) / split_mcus - first_mcu / split_mcus;
+}
+
+// Recorders of jc_entropy_run: `on` decides at compile time whether split points are looked at all.
+struct JcNoRecord {
+  static constexpr bool on = false;
+  JC_HD_MEMBER void operator()(int, const JcState&) const {}
+};
+
+// --------------------------------------------------------------------------------------------- MCUs of one segment
+// Decodes n_mcu MCUs of one frame, from MCU first_mcu on and from the decoder state st0, out of data[0, len) -- the
+// segment's bytes from st0's next unread byte on.  STORE: into `coef` (the frame's zero-filled coefficient range, natural
+// order, un-dequantised); otherwise nothing is stored.  Rec::on: rec(m, state) is called at every MCU m the run passes
+// with m % split_mcus == 0 (the state's byte_off counts from data).  One flat loop, one symbol per iteration: lanes of a
+// wavefront that are in different blocks still meet at the top of every iteration.  The caller has checked the row
+// (jc_segment_ok / jc_piece_ok).
+template <bool STORE, class Rec>
+JC_HD int jc_entropy_run(const uint8_t* data, int len, const JcState& st0, int first_mcu, int n_mcu, const JcTableSet* ts,
+                         int samp, int mcus_x, int mcus_y, int16_t* coef, int split_mcus, Rec& rec) {
   const int hs = (samp == JC_422 || samp == JC_420) ? 2 : 1, vs = samp == JC_420 ? 2 : 1;
   const int nY = samp == JC_GREY ? 1 : hs * vs, bpm = samp == JC_GREY ? 1 : nY + 2;
   const int bw0 = mcus_x * hs;
   JcBits b;
-  b.buf = 0; b.n = 0; b.pad = 0; b.marker = 0; b.p = seg; b.end = seg + len;
+  b.buf = st0.bits; b.n = st0.n; b.pad = st0.pad; b.marker = st0.marker; b.p = data; b.end = data + len;
   int my = first_mcu / mcus_x, mx = first_mcu - my * mcus_x;
   int mcu = 0, j = 0, k = 0, c = 0;
-  int pred0 = 0, pred1 = 0, pred2 = 0;
+  int pred0 = st0.pred[0], pred1 = st0.pred[1], pred2 = st0.pred[2];
+  int to_split = Rec::on ? split_mcus - first_mcu % split_mcus : 0;       // MCUs until the next split point
   long base = 0;
   for (;;) {
     jc_refill(b);
@@ -206,11 +260,11 @@ JC_HD int jc_entropy_segment(const uint8_t* seg, int len, int first_mcu, int n_m
         b.n -= sym;
       }
       int pred = c == 0 ? pred0 : c == 1 ? pred1 : pred2;
-      pred += diff;
+      pred = (int)((uint32_t)pred + (uint32_t)diff);            // wraps on a damaged stream or row instead of overflowing
       pred0 = c == 0 ? pred : pred0;
       pred1 = c == 1 ? pred : pred1;
       pred2 = c == 2 ? pred : pred2;
-      coef[base] = (int16_t)pred;
+      if (STORE) coef[base] = (int16_t)pred;
       k = 1;
     } else {
       const int r = sym >> 4, s = sym & 15;
@@ -220,7 +274,7 @@ JC_HD int jc_entropy_segment(const uint8_t* seg, int len, int first_mcu, int n_m
         if (s > 10) return JC_ERR_AC;
         const int v = jc_extend(jc_peek(b, s), s);
         b.n -= s;
-        coef[base + (ts->natural[k] & 63)] = (int16_t)v;
+        if (STORE) coef[base + (ts->natural[k] & 63)] = (int16_t)v;
         k += 1;
       } else if (r == 15) {
         k += 16;
@@ -239,9 +293,33 @@ JC_HD int jc_entropy_segment(const uint8_t* seg, int len, int first_mcu, int n_m
           mx = 0;
           ++my;
         }
+        if (Rec::on && --to_split == 0) {
+          to_split = split_mcus;
+          JcState st;
+          st.bits = b.n ? b.buf & (~(uint64_t)0 >> (64 - b.n)) : 0;
+          st.byte_off = (int32_t)(b.p - data); st.n = b.n; st.pad = b.pad; st.marker = b.marker;
+          st.pred[0] = pred0; st.pred[1] = pred1; st.pred[2] = pred2;
+          st.spare = 0;
+          rec(first_mcu + mcu, st);
+        }
       }
     }
   }
+}
+
+JC_HD JcState jc_zero_state() {
+  JcState st;
+  st.bits = 0; st.byte_off = 0; st.n = 0; st.pad = 0; st.marker = 0;
+  st.pred[0] = st.pred[1] = st.pred[2] = 0;
+  st.spare = 0;
+  return st;
+}
+
+// One whole segment from its first byte: the zero-state, no-recording instance.
+JC_HD int jc_entropy_segment(const uint8_t* seg, int len, int first_mcu, int n_mcu, const JcTableSet* ts, int samp, int mcus_x,
+                             int mcus_y, int16_t* coef) {
+  JcNoRecord rec;
+  return jc_entropy_run<true>(seg, len, jc_zero_state(), first_mcu, n_mcu, ts, samp, mcus_x, mcus_y, coef, 1, rec);
 }
 
 // --------------------------------------------------------------------------------------------- IDCT

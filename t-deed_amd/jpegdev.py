@@ -7,7 +7,9 @@ csrc/jpeg_core.h), and the kernels do the rest.  `pack_frames` is `pack` for the
 already parsed infos accepted), `ParseCache` keeps the parse results across epochs.  Supported files: baseline / extended-sequential Huffman (SOF0, SOF1),
 8-bit samples, greyscale or YCbCr with component ids 1, 2, 3, luma sampling 1x1, 2x1 or 2x2 with 1x1 chroma, one
 interleaved scan, optional restart intervals, no Adobe marker.  Everything else makes `parse` return None, and the
-caller decodes that frame with Pillow (feeder.load_video_device).
+caller decodes that frame with Pillow (feeder.load_video_device).  `split_points` / `piece_counts` / `PIECE` are the rule
+and the row layout by which a resident stream's segments are cut into pieces that decode on their own
+(trainclips.ResidentJpegClips).
 
 `decode_reference` is the arithmetic of libjpeg-turbo as Pillow uses it (Huffman decode, integer "islow" IDCT, "fancy"
 triangle up-sampling, integer YCbCr -> RGB), reproduced bit for bit; it exposes the intermediate stages.
@@ -359,6 +361,33 @@ def pack_frames(datas, infos=None, pinned=True):
         stream_np[off:off + ln] = arrs[f][src:src + ln]
     tsets = np.stack(set_rows) if set_rows else np.zeros((0, TABLE_SET_BYTES), np.uint8)
     return PackedJpegs(first.width, first.height, first.samp, n, stream, stream_np, seg, tsets, frame_set, fallback)
+
+
+# ------------------------------------------------------------------------------------------------- pieces of a segment
+# csrc/jpeg_core.h JcState / JcPiece: one row of the piece table of a resident stream
+_STATE = np.dtype([("bits", "<u8"), ("byte_off", "<i4"), ("n", "<i4"), ("pad", "<i4"), ("marker", "<i4"), ("pred", "<i4", 3),
+                   ("spare", "<i4")])
+PIECE = np.dtype([("pos", "<i8"), ("segment", "<i4"), ("first_mcu", "<i4"), ("n_mcu", "<i4"), ("set", "<i4"), ("left", "<i4"),
+                  ("spare", "<i4"), ("st", _STATE)])
+PIECE_BYTES = 72
+assert _STATE.itemsize == 40 and PIECE.itemsize == PIECE_BYTES
+
+
+def split_points(first_mcu, n_mcu, split_mcus):
+    """The MCUs at which a segment row (first_mcu, n_mcu) is cut into pieces: every m with first_mcu < m < first_mcu + n_mcu
+    and m % split_mcus == 0.  k split points make k + 1 pieces."""
+    if split_mcus < 1:
+        raise ValueError("split_mcus must be positive")
+    lo = (first_mcu // split_mcus + 1) * split_mcus
+    return list(range(lo, first_mcu + n_mcu, split_mcus))
+
+
+def piece_counts(segments, split_mcus):
+    """pieces per row of a segment table (int64 (n_segments,)) under `split_points`, as csrc/jpeg_core.h jc_piece_count"""
+    if split_mcus < 1:
+        raise ValueError("split_mcus must be positive")
+    first, n = segments[:, 1].astype(np.int64), segments[:, 2].astype(np.int64)
+    return 1 + (first + n - 1) // split_mcus - first // split_mcus
 
 
 class ParseCache:

@@ -1256,6 +1256,96 @@ def jpeg_pixels_rows(coeff, frame_set, table_sets, out, dst_row, frame_lo, n_fra
     return out
 
 
+PIECE_BYTES = 72          # csrc/jpeg_core.h JcPiece, jpegdev.PIECE
+
+
+def _chk_jpeg_resident(who, stream, table_sets, waves):
+    if waves.dim() != 2 or waves.shape[1] != 2 or waves.shape[0] < 1:
+        raise ValueError(f"{who}: waves (n, 2)")
+    if table_sets.dim() != 2 or table_sets.shape[1] != 4240 or table_sets.shape[0] < 1:
+        raise ValueError(f"{who}: table_sets (n_sets, 4240)")
+    if stream.dim() != 1 or stream.numel() < 1:
+        raise ValueError(f"{who}: stream must be a 1-d uint8 tensor")
+
+
+def jpeg_entropy_index(stream, base, segments, waves, table_sets, W, H, sampling, split_mcus, piece_off, seg_base, pieces,
+                       status):
+    """The index pass over the segments of one shard of a resident stream: nothing is decoded into coefficients, the decoder
+    state at every split point (jpegdev.split_points) is recorded.  stream uint8: the whole resident stream, the shard's
+    byte offsets count from `base`; segments int32 (n, 6), waves int32 (n_waves, 2) over them, piece_off int32 (n + 1,):
+    segment row i writes the rows piece_off[i] .. piece_off[i + 1] - 1 of pieces, uint8 (n_pieces, 72); seg_base: the
+    shard's first row in the numbering the piece rows carry; status int32 (>= n,): 0 or the error code per row."""
+    dev = stream.device
+    _chk_jpeg_tables("jpeg_entropy_index", dev, stream=(stream, torch.uint8), segments=(segments, torch.int32),
+                     waves=(waves, torch.int32), table_sets=(table_sets, torch.uint8), piece_off=(piece_off, torch.int32),
+                     pieces=(pieces, torch.uint8), status=(status, torch.int32))
+    if not stream.is_cuda:
+        raise TypeError("jpeg_entropy_index: the tensors must be on the device")
+    _chk_jpeg_resident("jpeg_entropy_index", stream, table_sets, waves)
+    if segments.dim() != 2 or segments.shape[1] != 6 or segments.shape[0] < 1:
+        raise ValueError("jpeg_entropy_index: segments (n, 6)")
+    n = int(segments.shape[0])
+    if piece_off.numel() != n + 1 or status.numel() < n:
+        raise ValueError(f"jpeg_entropy_index: {piece_off.numel()} piece offsets / {status.numel()} status entries for {n} segments")
+    if pieces.dim() != 2 or pieces.shape[1] != PIECE_BYTES or pieces.shape[0] < 1:
+        raise ValueError(f"jpeg_entropy_index: pieces (n_pieces, {PIECE_BYTES})")
+    if not 0 <= int(base) <= stream.numel() or int(split_mcus) < 1 or int(seg_base) < 0:
+        raise ValueError(f"jpeg_entropy_index: base {base} outside the stream of {stream.numel()} bytes, split_mcus {split_mcus} "
+                         f"or seg_base {seg_base}")
+    jpeg_frame_coeffs(W, H, sampling)
+    call("tdeed_jpeg_entropy_index", ptr(stream), stream.numel(), int(base), ptr(segments), n, ptr(waves), waves.shape[0],
+         ptr(table_sets), table_sets.shape[0], int(W), int(H), int(sampling), int(split_mcus), ptr(piece_off), int(seg_base),
+         ptr(pieces), pieces.shape[0], ptr(status), stream_ptr())
+    return pieces
+
+
+def jpeg_entropy_items(stream, pieces, items, waves, table_sets, W, H, sampling, slot_lo, n_slots, coeff, err):
+    """Decode the items listed by `waves` -- items int32 (n_items, 2) rows of (piece row, coefficient slot), waves int32
+    (n_waves, 2) rows of (first item, count <= 64), one table set per wave -- into coeff, int16 (>= n_slots *
+    jpeg_frame_coeffs) that the caller has zero-filled on this stream: slot s lands at (s - slot_lo) frames into it.  err:
+    int32 (1,) on the device, bit `code` of the word is set for every error code met; nothing else is reported."""
+    dev = coeff.device
+    _chk(coeff, "coeff", torch.int16)
+    _chk_jpeg_tables("jpeg_entropy_items", dev, stream=(stream, torch.uint8), pieces=(pieces, torch.uint8),
+                     items=(items, torch.int32), waves=(waves, torch.int32), table_sets=(table_sets, torch.uint8),
+                     err=(err, torch.int32))
+    _chk_jpeg_resident("jpeg_entropy_items", stream, table_sets, waves)
+    if items.dim() != 2 or items.shape[1] != 2 or items.shape[0] < 1:
+        raise ValueError("jpeg_entropy_items: items (n, 2)")
+    if pieces.dim() != 2 or pieces.shape[1] != PIECE_BYTES or pieces.shape[0] < 1:
+        raise ValueError(f"jpeg_entropy_items: pieces (n_pieces, {PIECE_BYTES})")
+    if err.numel() != 1 or int(slot_lo) < 0 or int(n_slots) < 1:
+        raise ValueError(f"jpeg_entropy_items: err holds {err.numel()} words, slots {slot_lo}..{int(slot_lo) + int(n_slots)}")
+    fc = jpeg_frame_coeffs(W, H, sampling)
+    if coeff.numel() < int(n_slots) * fc:
+        raise ValueError(f"jpeg_entropy_items: coeff holds {coeff.numel()} values, {n_slots} slots need {int(n_slots) * fc}")
+    call("tdeed_jpeg_entropy_items", ptr(stream), stream.numel(), ptr(pieces), pieces.shape[0], ptr(items), items.shape[0],
+         ptr(waves), waves.shape[0], ptr(table_sets), table_sets.shape[0], int(W), int(H), int(sampling), int(slot_lo),
+         int(n_slots), ptr(coeff), ptr(err), stream_ptr())
+    return coeff
+
+
+def jpeg_slot_fill(side, fill, out):
+    """The rows of a batch slot that no decode fills: out uint8 (..., 3, H, W) flattened to fill.numel() rows; fill int32 on
+    the device: -2 leaves the row as it is, -1 zeroes it, r >= 0 copies side[r] (side: uint8 (n, 3, H, W), or None when no
+    frame is kept decoded)."""
+    dev = out.device
+    _chk(out, "out", torch.uint8)
+    _chk_jpeg_tables("jpeg_slot_fill", dev, fill=(fill, torch.int32))
+    n = int(fill.numel())
+    if n < 1 or n > 65535 or out.numel() % n:
+        raise ValueError(f"jpeg_slot_fill: {n} rows for an output of {out.numel()} bytes")
+    fb = out.numel() // n
+    rows = 0
+    if side is not None:
+        _chk_jpeg_tables("jpeg_slot_fill", dev, side=(side, torch.uint8))
+        if side.numel() % fb:
+            raise ValueError(f"jpeg_slot_fill: side holds {side.numel()} bytes, a row has {fb}")
+        rows = side.numel() // fb
+    call("tdeed_jpeg_slot_fill", ptr(side) if rows else None, rows, fb, ptr(fill), n, ptr(out), stream_ptr())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- SGP contractions (sgp_gemm.hip)
 def sgp_gemm_ksteps(K):
     return int(_lib.load().tdeed_sgp_gemm_ksteps(K))

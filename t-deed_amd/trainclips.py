@@ -13,6 +13,10 @@ decoded ONCE, all videos stay on the device in one packed uint8 buffer, and a ba
 The host side restates what the reference computes and is pure numpy: `train_clip_table` (the clip list),
 `rasterise_labels` (label / displacement rows, the reference of the label kernel) and `ClipDraws` (the index stream of
 `__getitem__` under `random.seed(seed)` without workers).  `ResidentClips` is the loader `epoch()` consumes.
+
+`ResidentJpegClips` is the same loader over a set that stays on the device compressed: `load_resident_jpegs` packs the
+entropy streams of every frame once, and a batch decodes the frames it drew on the device (csrc/jpeg.hip), one lane per
+piece of a frame's scan; `batch_tables` is the host's share of a batch, pure numpy.
 """
 import random
 from types import SimpleNamespace
@@ -182,7 +186,76 @@ class _DeferredMix:
         return ops.train_clip_gather_mix(ld.video, self.tabs_a, self.tabs_b, lam.contiguous(), ld.clip_len, ld.stride)
 
 
-class ResidentClips:
+class _ClipLoader:
+    """What the resident loaders share: the clip table and its draws, the per-clip (first packed frame, base, video length,
+    video) rows, the ring bookkeeping of the batch slots and the label launches."""
+
+    def _init_clips(self, videos, lengths, classes, clip_len, stride, overlap, radi_displacement, mixup, dataset_len,
+                    batch_size, seed, pad_len, require_events, drop_last, device, depth):
+        name = type(self).__name__
+        self.table = train_clip_table(videos, classes, clip_len, stride, overlap, pad_len, require_events, radi_displacement)
+        n = len(self.table.clip_video)
+        if n == 0:
+            raise ValueError(f"{name}: no clips")
+        self.clip_len, self.stride, self.radius, self.mixup = int(clip_len), int(stride), int(radi_displacement), bool(mixup)
+        self.draws = ClipDraws(n, dataset_len, batch_size, mixup, seed, drop_last)
+        if batch_size * self.clip_len > 65535:
+            raise ValueError(f"{name}: {batch_size} clips of {clip_len} frames exceed the gather's 65535 frame slots")
+        self.device, self.depth = device, int(depth)
+        # per clip: first packed frame and length of its video
+        offs = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        cv = self.table.clip_video.astype(np.int64)
+        self._rows = np.stack([offs[cv], self.table.clip_base, np.asarray(lengths, np.int64)[cv], cv])       # (4, n)
+
+    def _init_ring(self):
+        self._copied = [None] * self.depth        # event: the H2D copy of the slot's pinned table has finished
+        self._consumed = [None] * self.depth      # event: the consumer is done with the slot's device buffers
+        self._out = [False] * self.depth          # handed to a consumer and not released yet
+        self._i = 0
+
+    def __len__(self):
+        return len(self.draws)
+
+    def reseed(self, seed):
+        """Start the draw stream anew from `seed` (the reference's workers reseed `random` per epoch, train_tdeed.py:126-127)."""
+        d = self.draws
+        self.draws = ClipDraws(d.n_clips, d.dataset_len, d.batch_size, d.mixup, seed, d.drop_last)
+
+    def release(self, j, stream=None):
+        """`feeder.done`: everything queued on `stream` (default: the current one) so far was the last use of slot j."""
+        import torch
+        ev = torch.cuda.Event()
+        ev.record(stream if stream is not None else torch.cuda.current_stream())
+        self._consumed[j] = ev
+        self._out[j] = False
+
+    def _next_slot(self):
+        """the ring entry of the next batch; the host waits only for the table copy of `depth` batches ago"""
+        j = self._i % self.depth
+        self._i += 1
+        if self._out[j]:
+            raise RuntimeError(f"{type(self).__name__}: the batch handed out {self.depth} batches ago was never released "
+                               "(feeder.done / feeder.prefetch); its buffers cannot be reused")
+        if self._copied[j] is not None:
+            self._copied[j].synchronize()                # a copy of `depth` batches ago: long finished
+        return j
+
+    def _label_launches(self, dev, lab, B, batch):
+        """the ops.clip_labels launches of one batch from its (4 * operands, B) device rows into the slot's label buffer"""
+        from . import ops
+        T, S, r = self.clip_len, self.stride, self.radius
+        k = 0
+        for op, sfx in enumerate(("", "2") if self.mixup else ("",)):
+            t4 = dev[4 * op:4 * op + 4]
+            label, labelD = ops.clip_labels(t4[3, :B], t4[1, :B], T, S, r, *self._ev, label=lab[k, :B],
+                                            labelD=lab[k + 1, :B] if r > 0 else None, displ=False)
+            batch["label" + sfx] = label
+            if r > 0:
+                batch["labelD" + sfx] = labelD
+            k += 2 if r > 0 else 1
+
+
+class ResidentClips(_ClipLoader):
     """The reference's training DataLoader over `ActionSpotDataset`, from videos that stay on the device.
 
     videos / classes / clip_len / stride / overlap / pad_len / require_events: `train_clip_table`.
@@ -233,19 +306,8 @@ class ResidentClips:
         if sum(lengths) * fb > max_resident_bytes:
             raise ValueError(f"ResidentClips: the videos need {sum(lengths) * fb} bytes on the device, more than "
                              f"max_resident_bytes={max_resident_bytes} (sharded epochs are not implemented)")
-        self.table = train_clip_table(videos, classes, clip_len, stride, overlap, pad_len, require_events, radi_displacement)
-        n = len(self.table.clip_video)
-        if n == 0:
-            raise ValueError("ResidentClips: no clips")
-        self.clip_len, self.stride, self.radius, self.mixup = int(clip_len), int(stride), int(radi_displacement), bool(mixup)
-        self.draws = ClipDraws(n, dataset_len, batch_size, mixup, seed, drop_last)
-        if batch_size * self.clip_len > 65535:
-            raise ValueError(f"ResidentClips: {batch_size} clips of {clip_len} frames exceed the gather's 65535 frame slots")
-        self.device, self.depth = device, int(depth)
-        # per clip: first packed frame and length of its video
-        offs = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
-        cv = self.table.clip_video.astype(np.int64)
-        self._rows = np.stack([offs[cv], self.table.clip_base, np.asarray(lengths, np.int64)[cv], cv])       # (4, n)
+        self._init_clips(videos, lengths, classes, clip_len, stride, overlap, radi_displacement, mixup, dataset_len, batch_size,
+                         seed, pad_len, require_events, drop_last, device, depth)
         self.stream = new_stream(device)
         self._copy_stream = new_stream(device, avoid=[self.stream])
         cur = torch.cuda.current_stream(device)
@@ -267,39 +329,14 @@ class ResidentClips:
                                                    for _ in range(self.depth)]
             nlab = nops * (2 if self.radius > 0 else 1)
             self._labels = [torch.empty((nlab, B, T), dtype=torch.int64, device=device) for _ in range(self.depth)]
-        self._copied = [None] * self.depth        # event: the H2D copy of the slot's pinned table has finished
-        self._consumed = [None] * self.depth      # event: the consumer is done with the slot's device buffers
-        self._out = [False] * self.depth          # handed to a consumer and not released yet
-        self._i = 0
-
-    def __len__(self):
-        return len(self.draws)
-
-    def reseed(self, seed):
-        """Start the draw stream anew from `seed` (the reference's workers reseed `random` per epoch, train_tdeed.py:126-127)."""
-        d = self.draws
-        self.draws = ClipDraws(d.n_clips, d.dataset_len, d.batch_size, d.mixup, seed, d.drop_last)
-
-    def release(self, j, stream=None):
-        """`feeder.done`: everything queued on `stream` (default: the current one) so far was the last use of slot j."""
-        import torch
-        ev = torch.cuda.Event()
-        ev.record(stream if stream is not None else torch.cuda.current_stream())
-        self._consumed[j] = ev
-        self._out[j] = False
+        self._init_ring()
 
     def __iter__(self):
         import torch
         from . import ops
-        T, S, r = self.clip_len, self.stride, self.radius
+        T, S = self.clip_len, self.stride
         for ia, ib in self.draws:
-            j = self._i % self.depth
-            self._i += 1
-            if self._out[j]:
-                raise RuntimeError(f"ResidentClips: the batch handed out {self.depth} batches ago was never released "
-                                   "(feeder.done / feeder.prefetch); its buffers cannot be reused")
-            if self._copied[j] is not None:
-                self._copied[j].synchronize()                # a copy of `depth` batches ago: long finished
+            j = self._next_slot()
             B = len(ia)
             host = self._host_np[j]
             host[0:4, :B] = self._rows[:, ia]
@@ -314,15 +351,7 @@ class ResidentClips:
                 ev.record(self.stream)
                 self._copied[j] = ev
                 batch = {}
-                k = 0
-                for op, sfx in enumerate(("", "2") if self.mixup else ("",)):
-                    t4 = dev[4 * op:4 * op + 4]
-                    label, labelD = ops.clip_labels(t4[3, :B], t4[1, :B], T, S, r, *self._ev, label=lab[k, :B],
-                                                    labelD=lab[k + 1, :B] if r > 0 else None, displ=False)
-                    batch["label" + sfx] = label
-                    if r > 0:
-                        batch["labelD" + sfx] = labelD
-                    k += 2 if r > 0 else 1
+                self._label_launches(dev, lab, B, batch)
                 tabs_a = (dev[0, :B], dev[1, :B], dev[2, :B])
                 if self.mixup:
                     batch["mix"] = _DeferredMix(self, tabs_a, (dev[4, :B], dev[5, :B], dev[6, :B]), B)
@@ -333,3 +362,474 @@ class ResidentClips:
             batch["_slot"] = (self, j, arrived)
             self._out[j] = True
             yield batch
+
+
+# ------------------------------------------------------------------------------------------------- resident JPEG streams
+class ResidentJpegs:
+    """The frames of a label list as packed entropy streams on the host (`load_resident_jpegs`).
+    shards: [namespace(packed=jpegdev.PackedJpegs, frames=int64 (n,) -- the set-wide number of every frame of the pack)];
+      the table-set column of every shard indexes `table_sets`, the one array of the whole set.
+    frame_set int32 (n_frames,): table set per frame, -1 = not decodable on the device (in `fallback`).
+    video_first / video_len: per video its first frame in the set-wide numbering and its length; names: every frame's file.
+    width / height / samp: geometry and sampling of the set's first supported frame (0 x 0 when there is none)."""
+
+    def __init__(self, shards, table_sets, frame_set, fallback, video_first, video_len, names, width, height, samp):
+        self.shards, self.table_sets, self.frame_set, self.fallback = shards, table_sets, frame_set, fallback
+        self.video_first, self.video_len, self.names = video_first, video_len, names
+        self.width, self.height, self.samp = width, height, samp
+
+    @property
+    def n_frames(self):
+        return len(self.names)
+
+    @property
+    def n_sets(self):
+        return int(self.table_sets.shape[0])
+
+    @property
+    def n_segments(self):
+        return sum(s.packed.n_segments for s in self.shards)
+
+    @property
+    def stream_bytes(self):
+        return sum(int(s.packed.stream_np.size) for s in self.shards)
+
+
+def load_resident_jpegs(frame_dir, dataset, videos, pool=None, cache=None, shard_bytes=1 << 30, pinned=True):
+    """Read every frame file of the label list ONCE (through `pool`'s threads when a DecodePool is given), parse it (with
+    `cache`, a jpegdev.ParseCache, when given) and pack the entropy segments with `jpegdev.pack_frames`, in shards of
+    consecutive frames whose stream stays under shard_bytes (a shard holds at least one frame; the default is below 2^31
+    because a segment row's byte offset is int32) -> ResidentJpegs.  Geometry and sampling are those of the set's first
+    supported frame: a supported frame of another geometry raises ValueError, one of another sampling takes the fallback,
+    as a file outside the decoder's subset does.  Missing files: as `load_resident_videos` -- num_frames must be the number
+    of frames that exist (ValueError), a hole in front of an existing frame raises FileNotFoundError."""
+    import os
+    from . import feeder, jpegdev
+    if not 0 < shard_bytes < 1 << 31:
+        raise ValueError("shard_bytes must be positive and below 2^31 (a segment row's byte offset is int32)")
+    names, video_first, video_len = [], [], []
+    for v in videos:
+        n = int(v["num_frames"])
+        path_fn = feeder.frame_locator(frame_dir, dataset, v["video"], v.get("_source_info"))[3]
+        if n < 1 or not os.path.exists(path_fn(n - 1)):
+            raise ValueError(f"video {v['video']}: num_frames={n}, but {path_fn(max(n, 1) - 1)} does not exist -- num_frames must "
+                             "be the number of frames that exist")
+        own = [path_fn(j) for j in range(n)]
+        for p in own:
+            if not os.path.exists(p):
+                raise FileNotFoundError(f"video {v['video']}: {p} is missing although later frames exist")
+        video_first.append(len(names))
+        video_len.append(n)
+        names += own
+    reader = pool.ex.map if pool is not None and hasattr(pool, "ex") else map
+    first = None
+    keys, set_rows = {}, []                         # tables_key -> set of the whole list
+    shards, fallback = [], []
+    frame_set = np.full(len(names), -1, np.int32)
+    cur, cur_bytes = [], 0                          # (frame, data, info | None) of the shard being filled
+
+    def flush():
+        nonlocal cur, cur_bytes
+        if not cur:
+            return
+        infos = [c[2] for c in cur]
+        packed = jpegdev.pack_frames([c[1] for c in cur], infos, pinned)
+        frames = np.asarray([c[0] for c in cur], np.int64)
+        local = []                                  # the shard's own sets, in pack_frames' order of first appearance
+        for info in infos:
+            if info is not None and info.tables_key not in local:
+                local.append(info.tables_key)
+        remap = np.zeros(max(len(local), 1), np.int32)
+        for i, key in enumerate(local):
+            if key not in keys:
+                keys[key] = len(set_rows)
+                set_rows.append(packed.table_sets[i])
+            remap[i] = keys[key]
+        if packed.n_segments:
+            packed.segments[:, 5] = remap[packed.segments[:, 5]]
+        on = packed.frame_set >= 0
+        packed.frame_set[on] = remap[packed.frame_set[on]]
+        frame_set[frames] = packed.frame_set
+        fallback.extend(int(frames[f]) for f in packed.fallback)
+        shards.append(SimpleNamespace(packed=packed, frames=frames))
+        cur, cur_bytes = [], 0
+
+    block = 256
+    for lo in range(0, len(names), block):
+        part = names[lo:lo + block]
+        for k, (data, size, mtime) in enumerate(reader(feeder._read_file_stat, part)):
+            info = cache.lookup(part[k], size, mtime, data) if cache is not None else jpegdev.parse(data)
+            if info is not None:
+                if first is None:
+                    first = info
+                if info.samp != first.samp:
+                    info = None                     # another sampling: kept decoded, as pack_frames would decide per pack
+                elif (info.width, info.height) != (first.width, first.height):
+                    raise ValueError(f"frame {part[k]}: {info.height}x{info.width} does not fit the set's "
+                                     f"{first.height}x{first.width}")
+            need = 0 if info is None else sum((int(ln) + jpegdev.GUARD + 3) & ~3 for ln in info.seg_len)
+            if cur and cur_bytes + need > shard_bytes:
+                flush()
+            cur.append((lo + k, data, info))
+            cur_bytes += need
+    flush()
+    table_sets = np.stack(set_rows) if set_rows else np.zeros((0, jpegdev.TABLE_SET_BYTES), np.uint8)
+    for s in shards:
+        s.packed.table_sets = table_sets
+    w, h, samp = (first.width, first.height, first.samp) if first is not None else (0, 0, 0)
+    return ResidentJpegs(shards, table_sets, frame_set, sorted(fallback), np.asarray(video_first, np.int64),
+                         np.asarray(video_len, np.int64), names, w, h, samp)
+
+
+def _cut_waves(keys):
+    """(first, count <= 64) rows over a sorted key column: no row spans two keys"""
+    n = keys.size
+    if n == 0:
+        return np.zeros((0, 2), np.int32)
+    brk = np.flatnonzero(np.diff(keys) != 0) + 1
+    out = []
+    for lo, hi in zip(np.concatenate([[0], brk]), np.concatenate([brk, [n]])):
+        for o in range(int(lo), int(hi), 64):
+            out.append((o, min(64, int(hi) - o)))
+    return np.asarray(out, np.int32).reshape(-1, 2)
+
+
+def batch_tables(rows, clip_len, stride, frame_set, side_row, piece_lo, piece_n, n_slots=None, clip_slot=None, chunk_slots=None):
+    """The tables of one batch of `ResidentJpegClips` (pure numpy; no file, no device).
+    rows: int64 (>= 3, n) -- per clip the first frame of its video in the set-wide numbering, the clip's base and the
+    video's length (`ResidentClips`' rows).  Slot clip_slot[k] + t (default k * clip_len + t) of the batch shows frame
+    first + base + t * stride of clip k, or zeros where base + t * stride falls outside the video (the window rule of
+    ops.train_clip_gather).  frame_set / side_row / piece_lo / piece_n: per frame of the set its table set (-1: not decoded
+    on the device), its row in the side buffer of decoded frames (-1: none), its first row in the piece table and its
+    number of pieces.  chunk_slots: slots per coefficient chunk (default: all in one).
+    -> namespace(n_slots,
+         slot_set int32 (n_slots,): table set of every slot the device decodes, -1 for the others (padding, side, unused);
+         fill int32 (n_slots,): -1 a padding slot (zeros), r >= 0 the side row to copy, -2 leave the slot alone;
+         items int32 (n_items, 2): (piece row, slot) of every piece of every device slot, ordered by chunk, then table set;
+         waves int32 (n_waves, 2): (first item, count <= 64), no wave spanning two sets or two chunks;
+         chunks [(slot_lo, slot_hi, wave_lo, wave_hi)]: the waves of every chunk that has any)."""
+    T = int(clip_len)
+    first, base, nfr = (np.asarray(rows[i], np.int64) for i in range(3))
+    n = first.size
+    at = np.arange(n, dtype=np.int64) * T if clip_slot is None else np.asarray(clip_slot, np.int64)
+    total = int(n_slots) if n_slots is not None else n * T
+    f = base[:, None] + np.arange(T, dtype=np.int64)[None, :] * int(stride)
+    real = ((f >= 0) & (f < nfr[:, None])).reshape(-1)
+    g = np.where(real, (first[:, None] + f).reshape(-1), 0)
+    slots = (at[:, None] + np.arange(T, dtype=np.int64)[None, :]).reshape(-1)
+    if n and (slots.min() < 0 or slots.max() >= total or np.unique(slots).size != slots.size):
+        raise ValueError("batch_tables: the clips' slots overlap or leave the batch")
+    side = np.where(real, side_row[g], -1)
+    sets = np.where(real & (side < 0), frame_set[g], -1)
+    if np.any(real & (side < 0) & (sets < 0)):
+        raise ValueError("batch_tables: a frame is neither decodable on the device nor in the side buffer")
+    slot_set = np.full(total, -1, np.int32)
+    fill = np.full(total, -2, np.int32)
+    slot_set[slots] = sets
+    fill[slots] = np.where(real, np.where(side >= 0, side, -2), -1)
+    dev = np.flatnonzero(sets >= 0)
+    cnt = piece_n[g[dev]].astype(np.int64)
+    n_items = int(cnt.sum())
+    it_slot = np.repeat(slots[dev], cnt)
+    it_piece = np.repeat(piece_lo[g[dev]].astype(np.int64), cnt) + (np.arange(n_items) - np.repeat(np.cumsum(cnt) - cnt, cnt))
+    it_set = np.repeat(sets[dev], cnt)
+    per = total if not chunk_slots else int(chunk_slots)
+    it_chunk = it_slot // max(per, 1)
+    order = np.lexsort((it_piece, it_set, it_chunk))
+    items = np.stack([it_piece[order], it_slot[order]], 1).astype(np.int32).reshape(-1, 2)
+    n_sets = int(frame_set.max()) + 1 if frame_set.size else 0
+    waves = _cut_waves(it_chunk[order] * max(n_sets, 1) + it_set[order])
+    chunks = []
+    if waves.shape[0]:
+        wchunk = it_chunk[order][waves[:, 0]]
+        for c in np.unique(wchunk):
+            w = np.flatnonzero(wchunk == c)
+            chunks.append((int(c) * per, min((int(c) + 1) * per, total), int(w[0]), int(w[-1]) + 1))
+    return SimpleNamespace(n_slots=total, slot_set=slot_set, fill=fill, items=items, waves=waves, chunks=chunks)
+
+
+class _SlotMix:
+    """Mixup of one batch of `ResidentJpegClips`: `mix(lam)` is ops_bwd.mix_frames on the batch's two decoded uint8 clips
+    (current stream, a fresh fp32 tensor).  Valid until the batch is released (`feeder.done`)."""
+
+    def __init__(self, a, b):
+        self.a, self.b = a, b
+
+    def __call__(self, lam):
+        from . import ops_bwd
+        return ops_bwd.mix_frames(self.a, self.b, lam.contiguous())
+
+
+class ResidentJpegClips(_ClipLoader):
+    """`ResidentClips` over a set that stays on the device COMPRESSED: the entropy streams of every frame are resident
+    (`load_resident_jpegs`), and a batch decodes the frames of the clips it drew with csrc/jpeg.hip.  Clip list, draws,
+    labels, batch dicts and the `_slot` hand-over are `ResidentClips`'; so are the keyword arguments, plus split_mcus (MCUs
+    per piece, default one MCU row: the index pass at construction records the decoder state at every such boundary, and
+    a batch decodes one lane per piece) and max_coeff_bytes (the coefficient buffer of a batch, chunked beyond it).
+
+    Construction uploads the shards' streams into one buffer and the tables in one copy, runs the index pass
+    (ops.jpeg_entropy_index, once per shard) and reads the per-segment statuses back -- its one host synchronisation.
+    Frames in a shard's fallback (outside the decoder's subset, another sampling) and frames the index pass flagged are
+    decoded once with `feeder.read_frame` and kept decoded in a side buffer; one of another size raises ValueError.
+    Resident bytes -- stream, segment and piece tables, table sets, side buffer -- above max_resident_bytes raise
+    ValueError before anything is uploaded, and again after the index pass if it added side frames.  `stats` reports them.
+
+    Per batch the host computes `batch_tables` (numpy over the batch's frame slots), which travel through the ring entry's
+    page-locked block in one copy; the loader's stream then zeroes the coefficients, runs ops.jpeg_entropy_items and
+    ops.jpeg_pixels_rows into the entry's uint8 slot, and ops.jpeg_slot_fill for padding and side frames.  With mixup the
+    slot holds both clips and `mix(lam)` is ops_bwd.mix_frames on them.  No host synchronisation per batch beyond
+    `ResidentClips`' table-reuse wait; at the end of each pass the device error word is read (one synchronisation) and a
+    non-zero word raises RuntimeError naming the pass."""
+
+    def __init__(self, videos, jpegs, classes, clip_len, stride=1, overlap=1, radi_displacement=0, mixup=False,
+                 dataset_len=1, batch_size=8, seed=None, pad_len=DEFAULT_PAD_LEN, require_events=False, drop_last=False,
+                 max_resident_bytes=16 << 30, device="cuda", depth=3, chunk_bytes=64 << 20, split_mcus=None,
+                 max_coeff_bytes=512 << 20):
+        import torch
+        from . import feeder, jpegdev, ops
+        from .streams import new_stream
+        if radi_displacement < 0:
+            raise ValueError("radi_displacement must not be negative")
+        if not videos or len(videos) != len(jpegs.video_len):
+            raise ValueError(f"ResidentJpegClips: {len(videos)} videos, {len(jpegs.video_len)} in the packed set")
+        for v, n in zip(videos, jpegs.video_len):
+            if int(v["num_frames"]) != int(n):
+                raise ValueError(f"ResidentJpegClips: video {v['video']} has {int(v['num_frames'])} frames, the packed set {int(n)}")
+        n_frames, names = jpegs.n_frames, jpegs.names
+        if jpegs.width:
+            W, H, samp = jpegs.width, jpegs.height, jpegs.samp
+        else:                                               # nothing for the device: the geometry comes from Pillow
+            fr0 = feeder.read_frame(names[0])
+            H, W, samp = int(fr0.shape[1]), int(fr0.shape[2]), 0
+        geom = jpegdev.geometry(W, H, samp)
+        split = int(split_mcus) if split_mcus is not None else geom.mcus_x
+        if split < 1:
+            raise ValueError("split_mcus must be positive")
+        fb = 3 * H * W
+        shards = [s for s in jpegs.shards]
+        seg_lo, piece_cnt, base, total = [], [], [], 0
+        n_seg = 0
+        for s in shards:
+            seg_lo.append(n_seg)
+            n_seg += s.packed.n_segments
+            piece_cnt.append(jpegdev.piece_counts(s.packed.segments, split) if s.packed.n_segments else np.zeros(0, np.int64))
+            base.append(total)
+            total += (int(s.packed.stream_np.size) + 15) & ~15 if s.packed.n_segments else 0
+        piece_off = np.concatenate([[0], np.cumsum(np.concatenate(piece_cnt))]) if n_seg else np.zeros(1, np.int64)
+        n_pieces = int(piece_off[-1])
+        if n_pieces >= 1 << 31:
+            raise ValueError(f"ResidentJpegClips: {n_pieces} pieces exceed the item table's 32-bit rows")
+        side = sorted(int(f) for f in jpegs.fallback)
+
+        def resident(n_side):
+            return total + n_seg * 4 * jpegdev.SEG_COLS + n_pieces * jpegdev.PIECE_BYTES + \
+                jpegs.n_sets * jpegdev.TABLE_SET_BYTES + n_side * fb
+
+        def check(n_side):
+            if resident(n_side) > max_resident_bytes:
+                raise ValueError(f"ResidentJpegClips: the set needs {resident(n_side)} bytes on the device ({total} of entropy "
+                                 f"streams, {n_side} frames kept decoded), more than max_resident_bytes={max_resident_bytes}")
+        check(len(side))
+        self._init_clips(videos, [int(n) for n in jpegs.video_len], classes, clip_len, stride, overlap, radi_displacement, mixup,
+                         dataset_len, batch_size, seed, pad_len, require_events, drop_last, device, depth)
+        self.shape, self.samp, self.split_mcus = (3, H, W), samp, split
+        dev = torch.device(device)
+        self.stream = new_stream(device)
+        self.stream.wait_stream(torch.cuda.current_stream(device))
+        flagged = []
+        with torch.cuda.stream(self.stream):
+            self._ev = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device)
+                             for a in (self.table.ev_off, self.table.ev_frame, self.table.ev_class))
+            self.pieces = self.table_sets = self.jstream = None
+            if n_seg:
+                # the streams, shard by shard, into one buffer; every table in one copy from a page-locked block
+                self.jstream = torch.zeros(total, dtype=torch.uint8, device=dev)
+                keep = []
+                for s, b in zip(shards, base):
+                    if not s.packed.n_segments:
+                        continue
+                    src = s.packed.stream if isinstance(s.packed.stream, torch.Tensor) else torch.from_numpy(s.packed.stream_np)
+                    for lo in range(0, src.numel(), int(chunk_bytes)):
+                        hi = min(lo + int(chunk_bytes), src.numel())
+                        self.jstream[b + lo:b + hi].copy_(src[lo:hi], non_blocking=True)
+                    keep.append(src)
+                segs = np.concatenate([s.packed.segments for s in shards if s.packed.n_segments])
+                waves = [s.packed.waves() for s in shards]
+                parts = [segs.reshape(-1).view(np.uint8), piece_off.astype(np.int32).view(np.uint8),
+                         jpegs.table_sets.reshape(-1)] + [np.ascontiguousarray(w).reshape(-1).view(np.uint8) for w in waves]
+                offs, size = [], 0
+                for a in parts:
+                    offs.append(size)
+                    size += (a.size + 15) & ~15
+                host = torch.zeros(size, dtype=torch.uint8).pin_memory()
+                hv = host.numpy()
+                for a, o in zip(parts, offs):
+                    hv[o:o + a.size] = a
+                meta = torch.empty(size, dtype=torch.uint8, device=dev)
+                meta.copy_(host, non_blocking=True)
+
+                def view(i, dtype, shape):
+                    return meta[offs[i]:offs[i] + parts[i].size].view(dtype).view(*shape)
+                d_segs = view(0, torch.int32, (n_seg, jpegdev.SEG_COLS))
+                d_off = view(1, torch.int32, (n_seg + 1,))
+                self.table_sets = view(2, torch.uint8, (jpegs.n_sets, jpegdev.TABLE_SET_BYTES))
+                self.pieces = torch.zeros((n_pieces, jpegdev.PIECE_BYTES), dtype=torch.uint8, device=dev)
+                status = torch.zeros(n_seg, dtype=torch.int32, device=dev)
+                for i, (s, b, s0) in enumerate(zip(shards, base, seg_lo)):
+                    n = s.packed.n_segments
+                    if n:
+                        ops.jpeg_entropy_index(self.jstream, b, d_segs[s0:s0 + n], view(3 + i, torch.int32, (waves[i].shape[0], 2)),
+                                               self.table_sets, W, H, samp, split, d_off[s0:s0 + n + 1], s0, self.pieces,
+                                               status[s0:s0 + n])
+                h_status = torch.empty(n_seg, dtype=torch.int32).pin_memory()
+                h_status.copy_(status, non_blocking=True)
+                self.stream.synchronize()                     # the one host synchronisation of construction
+                del keep, host
+                bad = h_status.numpy() != 0
+                for s, s0 in zip(shards, seg_lo):
+                    n = s.packed.n_segments
+                    if n and bad[s0:s0 + n].any():
+                        flagged += [int(f) for f in np.unique(s.frames[s.packed.segments[bad[s0:s0 + n], 0]])]
+                if flagged:
+                    side = sorted(set(side) | set(flagged))
+                    check(len(side))
+            # per frame of the set: table set, side row, piece rows
+            self._frame_set = jpegs.frame_set.copy()
+            self._side_row = np.full(n_frames, -1, np.int32)
+            self._side_row[side] = np.arange(len(side), dtype=np.int32)
+            self._frame_set[side] = -1
+            self._piece_lo = np.zeros(n_frames, np.int64)
+            self._piece_n = np.zeros(n_frames, np.int64)
+            for s, s0, cnt in zip(shards, seg_lo, piece_cnt):
+                n = s.packed.n_segments
+                if not n:
+                    continue
+                fr = s.frames[s.packed.segments[:, 0]]
+                lo = np.full(n_frames, np.iinfo(np.int64).max, np.int64)
+                np.minimum.at(lo, fr, piece_off[s0:s0 + n])
+                np.add.at(self._piece_n, fr, cnt)
+                seen = np.unique(fr)
+                self._piece_lo[seen] = lo[seen]
+            self.side = None
+            if side:
+                h_side = torch.empty((len(side), 3, H, W), dtype=torch.uint8).pin_memory()
+                for r, f in enumerate(side):
+                    fr = feeder.read_frame(names[f]) if not (f == 0 and not jpegs.width) else fr0
+                    if tuple(fr.shape) != (3, H, W):
+                        raise ValueError(f"frame {names[f]}: {tuple(fr.shape)} does not fit the set's {(3, H, W)}")
+                    h_side[r].copy_(fr)
+                self.side = torch.empty((len(side), 3, H, W), dtype=torch.uint8, device=dev)
+                self.side.copy_(h_side, non_blocking=True)
+                self._side_host = h_side
+            # the ring: per entry one page-locked block and its device twin (clip rows, then the batch tables), the uint8
+            # slot of both operands and the labels; one coefficient buffer, since every batch decodes on the one stream
+            B, T, nops = int(batch_size), self.clip_len, 2 if self.mixup else 1
+            self._cap = cap = nops * B * T
+            if cap > 65535:
+                raise ValueError(f"ResidentJpegClips: {nops} x {B} clips of {T} frames exceed the kernels' 65535 frame slots")
+            self._fc = fc = ops.jpeg_frame_coeffs(W, H, samp)
+            self._chunk = min(cap, max(1, int(max_coeff_bytes) // (2 * fc)))
+            max_pieces = int(self._piece_n.max()) if n_frames else 0
+            cap_items = max(cap * max_pieces, 1)
+            cap_waves = cap_items // 64 + max(jpegs.n_sets, 1) * -(-cap // self._chunk) + 1
+            sizes = [4 * nops * B * 8, cap * 4, cap * 4, cap_items * 8, cap_waves * 8]
+            self._offs = np.concatenate([[0], np.cumsum([(s + 15) & ~15 for s in sizes])]).astype(np.int64)
+            nbytes = int(self._offs[-1])
+            self._host = [torch.zeros(nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.depth)]
+            self._host_np = [h.numpy() for h in self._host]
+            self._dev = [torch.zeros(nbytes, dtype=torch.uint8, device=dev) for _ in range(self.depth)]
+            self._slots = [torch.empty((nops, B, T, 3, H, W), dtype=torch.uint8, device=dev) for _ in range(self.depth)]
+            nlab = nops * (2 if self.radius > 0 else 1)
+            self._labels = [torch.empty((nlab, B, T), dtype=torch.int64, device=dev) for _ in range(self.depth)]
+            self._coeff = torch.empty(self._chunk * fc, dtype=torch.int16, device=dev) if n_seg else None
+            self._ident = torch.arange(cap, dtype=torch.int32, device=dev)
+            self._err = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._err_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self._caps = (cap_items, cap_waves)
+        self._pass = 0
+        self.item_events = None                 # set to a list: (start, end) events around every jpeg_entropy_items launch
+        self._init_ring()
+        self.stats = dict(frames=n_frames, device_frames=n_frames - len(side), fallback_frames=len(side),
+                          index_flagged=sorted(flagged), segments=n_seg, pieces=n_pieces, shards=len(shards),
+                          table_sets=jpegs.n_sets, stream_bytes=total, resident_bytes=resident(len(side)),
+                          decoded_bytes=n_frames * fb)
+
+    def _views(self, block, B, np_side):
+        """(rows int64 (4 * operands, B), slot_set, fill, items (cap, 2), waves (cap, 2)) of a ring block"""
+        o = self._offs
+        nops = 2 if self.mixup else 1
+        cap_items, cap_waves = self._caps
+        if np_side:
+            part = lambda i, dt: block[o[i]:o[i + 1]].view(dt)                                   # noqa: E731
+            return (part(0, np.int64)[:4 * nops * B].reshape(4 * nops, B), part(1, np.int32)[:self._cap],
+                    part(2, np.int32)[:self._cap], part(3, np.int32)[:2 * cap_items].reshape(cap_items, 2),
+                    part(4, np.int32)[:2 * cap_waves].reshape(cap_waves, 2))
+        import torch
+        part = lambda i, dt: block[int(o[i]):int(o[i + 1])].view(dt)                              # noqa: E731
+        return (part(0, torch.int64)[:4 * nops * B].view(4 * nops, B), part(1, torch.int32)[:self._cap],
+                part(2, torch.int32)[:self._cap], part(3, torch.int32)[:2 * cap_items].view(cap_items, 2),
+                part(4, torch.int32)[:2 * cap_waves].view(cap_waves, 2))
+
+    def __iter__(self):
+        import torch
+        from . import ops
+        T, S = self.clip_len, self.stride
+        Bcap = self.draws.batch_size
+        _, H, W = self.shape
+        self._pass += 1
+        for ia, ib in self.draws:
+            j = self._next_slot()
+            B = len(ia)
+            h_rows, h_set, h_fill, h_items, h_waves = self._views(self._host_np[j], Bcap, True)
+            h_rows[0:4, :B] = self._rows[:, ia]
+            rows = self._rows[:, ia]
+            at = np.arange(B, dtype=np.int64) * T
+            if ib is not None:
+                h_rows[4:8, :B] = self._rows[:, ib]
+                rows = np.concatenate([rows, self._rows[:, ib]], 1)
+                at = np.concatenate([at, (Bcap + np.arange(B, dtype=np.int64)) * T])
+            tb = batch_tables(rows, T, S, self._frame_set, self._side_row, self._piece_lo, self._piece_n, n_slots=self._cap,
+                              clip_slot=at, chunk_slots=self._chunk)
+            h_set[:], h_fill[:] = tb.slot_set, tb.fill
+            h_items[:tb.items.shape[0]] = tb.items
+            h_waves[:tb.waves.shape[0]] = tb.waves
+            slot, lab = self._slots[j], self._labels[j]
+            with torch.cuda.stream(self.stream):
+                if self._consumed[j] is not None:
+                    self.stream.wait_event(self._consumed[j])   # do not overwrite buffers the consumer still reads
+                self._dev[j].copy_(self._host[j], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(self.stream)
+                self._copied[j] = ev
+                d_rows, d_set, d_fill, d_items, d_waves = self._views(self._dev[j], Bcap, False)
+                batch = {}
+                self._label_launches(d_rows, lab, B, batch)
+                for lo, hi, w_lo, w_hi in tb.chunks:
+                    self._coeff[:(hi - lo) * self._fc].zero_()
+                    if self.item_events is not None:
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record(self.stream)
+                    ops.jpeg_entropy_items(self.jstream, self.pieces, d_items[:tb.items.shape[0]], d_waves[w_lo:w_hi],
+                                           self.table_sets, W, H, self.samp, lo, hi - lo, self._coeff, self._err)
+                    if self.item_events is not None:
+                        e1.record(self.stream)
+                        self.item_events.append((e0, e1))
+                    ops.jpeg_pixels_rows(self._coeff, d_set, self.table_sets, slot, self._ident, lo, hi - lo, self.samp)
+                ops.jpeg_slot_fill(self.side, d_fill, slot)
+                if self.mixup:
+                    batch["mix"] = _SlotMix(slot[0, :B], slot[1, :B])
+                else:
+                    batch["frame"] = slot[0, :B]
+                arrived = torch.cuda.Event()
+                arrived.record(self.stream)
+            batch["_slot"] = (self, j, arrived)
+            self._out[j] = True
+            yield batch
+        with torch.cuda.stream(self.stream):
+            self._err_host.copy_(self._err, non_blocking=True)
+        self.stream.synchronize()                               # the one synchronisation of a pass
+        word = int(self._err_host[0])
+        if word:
+            codes = [c for c in range(1, 8) if word >> c & 1]
+            raise RuntimeError(f"ResidentJpegClips: pass {self._pass} met decode errors on the device (status codes {codes}); "
+                               "the resident streams or tables are damaged")

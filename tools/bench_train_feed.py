@@ -4,6 +4,8 @@
                                                                                                and written to profiles/train_feed.json
     python tools/bench_train_feed.py --decode-device [same options]      the JPEG decode on the device against the decode on the
                                                                          host (decode_device_main), profiles/train_feed_device_decode.json
+    python tools/bench_train_feed.py --resident-jpeg [same options]      clips decoded per batch from JPEG streams that stay on the
+                                                                         device (resident_jpeg_main), profiles/train_feed_resident_jpeg.json
 
 Synthetic JPEG videos (224 x 224, quality 90) are written to a temporary directory with a label file.  Measured:
   loader   clips/s of `trainclips.ResidentClips` alone (T = 100, batch 8), without mixup (the uint8 batch) and with it (labels
@@ -201,6 +203,135 @@ def decode_device_main(a):
     return 0
 
 
+def resident_jpeg_main(a):
+    """--resident-jpeg: `trainclips.ResidentJpegClips` (the entropy streams resident, every batch decoded on the device)
+    against `trainclips.ResidentClips` (every frame resident decoded) and `feeder.clip_batches` + ProcessDecodePool, on the
+    same noise-frame videos, in one run, the routes alternating: (a) the loader alone, plain clips, (b) a 200MF training
+    epoch with mixup fed by each.  Per route: clips/s with its spread over the rounds, resident bytes per frame, the time
+    of its construction, and for the new route the time of the per-piece entropy kernel per batch from device events.  One
+    JSON record, printed and written to profiles/train_feed_resident_jpeg.json.  No threshold: `faster` says for every pair
+    of routes whether the slowest round of one beat the fastest round of the other."""
+    from tdeed_amd import jpegdev
+    from tdeed_amd.model import TDEEDModel
+    from types import SimpleNamespace
+    T, r, bs = CFG["clip_len"], CFG["radi_displacement"], a.batch
+    root = tempfile.mkdtemp(prefix="tdeed_train_feed_")
+    out = dict(kind="train_feed_resident_jpeg", cfg=CFG, videos=a.videos, frames_per_video=a.frames, clips_per_epoch=a.clips,
+               batch_size=bs, decode_processes=a.procs, repeats=a.repeats, device=torch.cuda.get_device_name(0))
+    pool = None
+    try:
+        videos = write_videos(root, a.videos, a.frames)
+        n_frames = a.videos * a.frames
+        sizes = [os.path.getsize(os.path.join(root, v["video"], f"frame{i}.jpg")) for v in videos for i in range(a.frames)]
+        out["jpeg_bytes_per_frame"] = round(float(np.mean(sizes)), 1)
+        threads = feeder.DecodePool(a.procs)
+        common = dict(clip_len=T, radi_displacement=r, batch_size=bs, drop_last=True, device="cuda", dataset_len=a.clips, seed=1)
+
+        def build(mixup):
+            """both resident loaders, with the time each took from the files to a loader that is ready"""
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            jp = TC.ResidentJpegClips(videos, TC.load_resident_jpegs(root, DATASET, videos, pool=threads,
+                                                                     cache=jpegdev.ParseCache()), CLASSES, mixup=mixup, **common)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            rc = TC.ResidentClips(videos, TC.load_resident_videos(root, DATASET, videos, pool=threads), CLASSES, mixup=mixup,
+                                  **common)
+            torch.cuda.synchronize()
+            return jp, rc, round(t1 - t0, 3), round(time.perf_counter() - t1, 3)
+        jp, rc, t_jp, t_rc = build(False)
+        st = jp.stats
+        out["set"] = {k: st[k] for k in ("frames", "device_frames", "fallback_frames", "segments", "pieces", "shards", "table_sets",
+                                         "stream_bytes", "resident_bytes", "decoded_bytes")}
+        out["pieces_per_frame"] = round(st["pieces"] / max(st["device_frames"], 1), 2)
+        out["resident_bytes_per_frame"] = dict(resident_jpeg=round(st["resident_bytes"] / n_frames, 1),
+                                               resident_decoded=round(st["decoded_bytes"] / n_frames, 1), host_decoded=0)
+        out["frames_per_decoded_frame_budget"] = round(st["decoded_bytes"] / st["resident_bytes"], 2)
+        out["construction_s"] = dict(resident_jpeg=t_jp, resident_decoded=t_rc, host_decoded=0.0)
+        pool = feeder.ProcessDecodePool(a.procs)
+        n_epoch = a.clips // bs * bs
+
+        def drain(loader):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in feeder.prefetch(loader, "cuda"):
+                pass
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+
+        def reseeded(ld, seed):
+            ld.reseed(seed)
+            return ld
+
+        def faster(res):
+            names = list(res)
+            return {f"{x}_over_{y}": bool(res[x]["clips_per_s_min"] > res[y]["clips_per_s_max"]) for x in names for y in names if x != y}
+
+        def ratios(res):
+            return {f"resident_jpeg_over_{y}": round(res["resident_jpeg"]["clips_per_s"] / res[y]["clips_per_s"], 3)
+                    for y in res if y != "resident_jpeg"}
+
+        # ---- (a) the loader alone, plain clips; every round draws new clips, the same for every route
+        routes = dict(resident_jpeg=lambda seed: reseeded(jp, seed), resident_decoded=lambda seed: reseeded(rc, seed),
+                      host_decoded=lambda seed: decoded_loader(root, videos, pool, False, a.clips, bs, seed))
+        times = {k: [] for k in routes}
+        for rep in range(a.repeats + 1):
+            jp.item_events = [] if rep else None
+            for k, mk in routes.items():
+                t = drain(mk(10 + rep))
+                if rep:                                                        # the first round warms up
+                    times[k].append(t)
+            if rep:
+                ms = [e0.elapsed_time(e1) for e0, e1 in jp.item_events]
+                out.setdefault("item_kernel_ms_per_batch", []).append(round(float(np.sum(ms)) / max(len(jp), 1), 4))
+        jp.item_events = None
+        out["loader"] = {k: _rate(v, n_epoch) for k, v in times.items()}
+        out["loader"]["ratio"] = ratios({k: out["loader"][k] for k in routes})
+        out["loader"]["faster"] = faster({k: out["loader"][k] for k in routes})
+        del jp, rc
+
+        # ---- (b) a training epoch with mixup fed by each route
+        jp, rc, t_jp, t_rc = build(True)
+        out["construction_s_mixup"] = dict(resident_jpeg=t_jp, resident_decoded=t_rc, host_decoded=0.0)
+        threads.close()
+        m = TDEEDModel(device="cuda", args=SimpleNamespace(modality="rgb", temporal_arch="ed_sgp_mixer", pretrain=None, **CFG))
+        m.load({k: torch.from_numpy(v) for k, v in synth.make_state(state_layout.model_state_shapes(CFG), 0).items()})
+        opt, _ = m.get_optimizer({"lr": 1e-4})
+        routes = dict(resident_jpeg=lambda seed: reseeded(jp, seed), resident_decoded=lambda seed: reseeded(rc, seed),
+                      host_decoded=lambda seed: decoded_loader(root, videos, pool, True, a.clips, bs, seed))
+        times, losses = {k: [] for k in routes}, {}
+        for rep in range(a.repeats + 1):
+            for k, mk in routes.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                losses[k] = m.epoch(mk(2 + rep), optimizer=opt)
+                torch.cuda.synchronize()
+                if rep:
+                    times[k].append(time.perf_counter() - t0)
+        out["epoch"] = {k: dict(_rate(v, n_epoch), last_loss=round(float(losses[k]), 5)) for k, v in times.items()}
+        out["epoch"]["ratio"] = ratios({k: out["epoch"][k] for k in routes})
+        out["epoch"]["faster"] = faster({k: out["epoch"][k] for k in routes})
+        out["notes"] = [
+            "the JPEG files stay in the page cache on every route: decode is measured, not disk",
+            "loader: plain clips, drained through feeder.prefetch; the resident routes' construction (construction_s: reading, "
+            "parsing / decoding every file once, upload, index pass) is not in their rounds",
+            "item_kernel_ms_per_batch: per timed loader round, the summed event time of ops.jpeg_entropy_items over the round "
+            "divided by its batches",
+            "epoch: mixup as train_tdeed.py trains; the host route uploads 'frame2' by epoch()'s blocking copy",
+            "faster[x_over_y] is true only where x's slowest round beat y's fastest"]
+    finally:
+        if pool is not None:
+            pool.close()
+        shutil.rmtree(root, ignore_errors=True)
+    line = json.dumps(out)
+    print(line)
+    path = a.out if a.out else os.path.join(ROOT, "profiles", "train_feed_resident_jpeg.json")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as fh:
+        fh.write(line + "\n")
+    return 0
+
+
 def _rate(times, clips):
     t = np.asarray(times)
     return dict(clips_per_s=round(clips / float(np.median(t)), 1), clips_per_s_min=round(clips / float(t.max()), 1),
@@ -217,6 +348,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--decode-device", action="store_true",
                     help="measure feeder.device_clip_batches against the host-decoded feed instead (profiles/train_feed_device_decode.json)")
+    ap.add_argument("--resident-jpeg", action="store_true",
+                    help="measure trainclips.ResidentJpegClips against ResidentClips and the host-decoded feed instead "
+                         "(profiles/train_feed_resident_jpeg.json)")
     ap.add_argument("--read-threads", type=int, default=0,
                     help="--decode-device: threads that read the files (0: the feed's own thread; the files sit in the page cache, "
                          "where a read is too short to be worth a hand-over between threads)")
@@ -224,6 +358,8 @@ def main():
     a = ap.parse_args()
     if a.decode_device:
         return decode_device_main(a)
+    if a.resident_jpeg:
+        return resident_jpeg_main(a)
     a.out = a.out or os.path.join(ROOT, "profiles", "train_feed.json")
     from tdeed_amd.model import TDEEDModel
     from types import SimpleNamespace
