@@ -902,7 +902,15 @@ int tdeed_sgp_gemm_gelu_chsum(const void* A, int B, int T, int K, const void* Wp
  * tdeed_jpeg_pixels_rows: the same kernel body with a row table: pack frame f (frame_lo <= f < frame_lo + n_frames) goes to
  *   out + dst_row[f] * 3*H*W, out uint8 [out_rows][3][H][W] (the rows i*T + t of a (B,T,3,H,W) clip-batch slot); a frame
  *   with dst_row[f] < 0, dst_row[f] >= out_rows or a negative table set stores nothing.  dst_row int32, one entry per
- *   frame of the whole pack, on the device. */
+ *   frame of the whole pack, on the device.
+ * tdeed_jpeg_pixels_window: tdeed_jpeg_pixels_rows over the window [top, top + wh) x [left, left + ww) of the frames: out uint8
+ *   [out_rows][3][wh][ww].  Only the bands that hold window rows are launched and only the blocks under the window (and
+ *   under the chroma samples its up-sampling taps touch) are transformed: coefficients of other blocks are never read.  The
+ *   full window gives the bits of tdeed_jpeg_pixels_rows; an empty window or one that leaves the frame is an error.
+ * tdeed_jpeg_window_blocks: those block ranges as ten ints (band_lo, band_n, luma block columns lo / n, luma block rows
+ *   lo / hi, chroma block columns lo / n, MCU rows lo / hi with the 4:2:0 halo); 0, or -1 for a bad geometry or window.
+ * tdeed_jpeg_pixels_lds_bytes: the dynamic LDS bytes per workgroup that tdeed_jpeg_pixels / tdeed_jpeg_pixels_rows (windowed
+ *   0) or tdeed_jpeg_pixels_window (windowed 1) request for this geometry; -1 for a bad geometry or window. */
 long tdeed_jpeg_frame_coeffs(int W, int H, int sampling);
 int tdeed_jpeg_entropy(const uint8_t* stream, long stream_bytes, const int* segments, int n_segments, const int* waves,
                        int n_waves, const uint8_t* table_sets, int n_sets, int W, int H, int sampling, int frame_lo,
@@ -912,6 +920,11 @@ int tdeed_jpeg_pixels(const int16_t* coeff, const int* frame_table_set, const ui
 int tdeed_jpeg_pixels_rows(const int16_t* coeff, const int* frame_table_set, const uint8_t* table_sets, int n_sets,
                            uint8_t* out, long out_rows, const int* dst_row, int frame_lo, int n_frames, int H, int W,
                            int sampling, void* hip_stream);
+int tdeed_jpeg_pixels_window(const int16_t* coeff, const int* frame_table_set, const uint8_t* table_sets, int n_sets,
+                             uint8_t* out, long out_rows, const int* dst_row, int frame_lo, int n_frames, int H, int W,
+                             int sampling, int top, int left, int wh, int ww, void* hip_stream);
+int tdeed_jpeg_window_blocks(int W, int H, int sampling, int top, int left, int wh, int ww, int* ranges);
+long tdeed_jpeg_pixels_lds_bytes(int W, int H, int sampling, int windowed, int top, int left, int wh, int ww);
 
 /* ---- entropy streams that stay on the device (trainclips.ResidentJpegClips).  A piece is a run of MCUs of one segment
  * that decodes on its own from a recorded decoder state; the piece table has 72-byte rows (JcPiece, csrc/jpeg_core.h:

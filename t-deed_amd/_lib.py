@@ -208,6 +208,10 @@ _SIGS = {
     "tdeed_jpeg_entropy": ([P, c_long, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P], c_int),
     "tdeed_jpeg_pixels": ([P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P], c_int),
     "tdeed_jpeg_pixels_rows": ([P, P, P, c_int, P, c_long, P, c_int, c_int, c_int, c_int, c_int, P], c_int),
+    "tdeed_jpeg_pixels_window": ([P, P, P, c_int, P, c_long, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
+                                 c_int),
+    "tdeed_jpeg_window_blocks": ([c_int, c_int, c_int, c_int, c_int, c_int, c_int, P], c_int),
+    "tdeed_jpeg_pixels_lds_bytes": ([c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int], c_long),
     "tdeed_jpeg_entropy_index": ([P, c_long, c_long, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P,
                                   c_int, P, P], c_int),
     "tdeed_jpeg_entropy_items": ([P, c_long, P, c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P,

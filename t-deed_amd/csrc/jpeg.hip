@@ -279,54 +279,66 @@ extern "C" long tdeed_jpeg_frame_coeffs(int W, int H, int sampling) {
 // three 16-byte stores (V16) or guarded byte stores.
 // The frame lands in row dst_row[frame] of out when ROWS (tdeed_jpeg_pixels_rows: the frames of a clip batch go to rows
 // i * T + t of the batch slot), in row frame otherwise; a row outside [0, out_rows) stores nothing.
+// WIN (tdeed_jpeg_pixels_window): the same body over the window `win` of the frame (jc_window).  The grid holds the
+// window's bands only, phase 1 runs the blocks jc_window lists and no others -- the LDS planes are as wide as those block
+// columns, BandPlanes carries their first column -- and phase 2 covers the window's pixels, written as rows of a
+// (wh, ww) plane.  Without WIN the window is the frame, the block columns are the padded MCU grid's (bw0, mcus_x) and every
+// range below is the constant it was; jpeg_pixels_lds_bytes sizes the planes from the same columns.
 struct BandPlanes {
   const uint8_t* y;
   const uint8_t* cb;
   const uint8_t* cr;
   int ypitch, cpitch, y0, c0;      // luma row y0 / chroma row c0 is row 0 of the LDS plane
+  int yx0, cx0;                    // luma / chroma column that is column 0 of the LDS plane
   __device__ __forceinline__ int at(int c, int row, int col) const {
-    return c == 0 ? y[(row - y0) * ypitch + col] : (c == 1 ? cb : cr)[(row - c0) * cpitch + col];
+    return c == 0 ? y[(row - y0) * ypitch + col - yx0] : (c == 1 ? cb : cr)[(row - c0) * cpitch + col - cx0];
   }
 };
 
-template <int SAMP, bool V16, bool ROWS>
+template <int SAMP, bool V16, bool ROWS, bool WIN>
 __global__ __launch_bounds__(256) void jpeg_pixels_kernel(const int16_t* __restrict__ coef, const int* __restrict__ frame_set,
                                                           const JcTableSet* __restrict__ sets, int n_sets, int frame_lo,
                                                           int W, int H, int mcus_x, int mcus_y, uint8_t* __restrict__ out,
-                                                          const int* __restrict__ dst_row, long out_rows) {
+                                                          const int* __restrict__ dst_row, long out_rows, const JcWindow win) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   constexpr int HS = (SAMP == JC_422 || SAMP == JC_420) ? 2 : 1, VS = SAMP == JC_420 ? 2 : 1;
   constexpr int NC = SAMP == JC_GREY ? 0 : 2;                 // chroma planes
   constexpr int HALO = SAMP == JC_420 ? 1 : 0;
   constexpr int CROWS = 8 + 2 * HALO;
-  const int band = blockIdx.x, fl = blockIdx.y;
+  const int band = (WIN ? win.band_lo : 0) + blockIdx.x, fl = blockIdx.y;
   const int set = frame_set[frame_lo + fl];
   if (set < 0 || set >= n_sets) return;                        // a frame that is decoded on the host
   const long row = ROWS ? (long)dst_row[frame_lo + fl] : (long)frame_lo + fl;
   if (ROWS && (row < 0 || row >= out_rows)) return;            // a frame that no row of the slot takes
   TD_DEV_ASSERT(row >= 0 && (!ROWS || row < out_rows));
   const JcTableSet* ts = sets + set;
-  const int bw0 = mcus_x * HS, ypitch = bw0 * 8, cpitch = mcus_x * 8;
+  const int bw0 = mcus_x * HS;
+  const int ybx_lo = WIN ? win.ybx_lo : 0, ybx_n = WIN ? win.ybx_n : bw0;       // the block columns phase 1 runs
+  const int cbx_lo = WIN ? win.cbx_lo : 0, cbx_n = WIN ? win.cbx_n : mcus_x;
+  const int ypitch = ybx_n * 8, cpitch = cbx_n * 8;
   uint8_t* ly = lds;
   uint8_t* lc = lds + 8 * VS * ypitch;                         // [NC][CROWS][cpitch]
   const long luma_blocks = (long)bw0 * mcus_y * VS, chroma_blocks = (long)mcus_x * mcus_y;
   const int16_t* fc = coef + (long)fl * (luma_blocks + NC * chroma_blocks) * 64;
 
-  const int nY = VS * bw0, crows_b = 1 + 2 * HALO, nC = NC * crows_b * mcus_x;
+  const int nY = VS * ybx_n, crows_b = 1 + 2 * HALO, nC = NC * crows_b * cbx_n;
   for (int t = threadIdx.x; t < nY + nC; t += 256) {
     uint32_t rows[16];
     if (t < nY) {
-      const int v = t / bw0, bx = t - v * bw0;
-      jc_idct_block(fc + ((long)(band * VS + v) * bw0 + bx) * 64, ts->quant[ts->tq[0] & 3], rows);
+      const int v = t / ybx_n, bx = t - v * ybx_n;
+      if (WIN && (band * VS + v < win.ybr_lo || band * VS + v > win.ybr_hi)) continue;   // a block row outside the window
+      jc_idct_block(fc + ((long)(band * VS + v) * bw0 + ybx_lo + bx) * 64, ts->quant[ts->tq[0] & 3], rows);
 #pragma unroll
       for (int r = 0; r < 8; ++r)
         *reinterpret_cast<u32x2*>(ly + (v * 8 + r) * ypitch + bx * 8) = (u32x2){rows[2 * r], rows[2 * r + 1]};
     } else {
-      const int u = t - nY, per = crows_b * mcus_x;
-      const int c = u / per, w = u - c * per, rel = w / mcus_x, bx = w - rel * mcus_x;
+      const int u = t - nY, per = crows_b * cbx_n;
+      const int c = u / per, w = u - c * per, rel = w / cbx_n, bx = w - rel * cbx_n;
       const int by = band + rel - HALO;                        // rel 0 / 2 of 4:2:0: the band above / below
       if (by < 0 || by >= mcus_y) continue;
-      jc_idct_block(fc + (luma_blocks + c * chroma_blocks + (long)by * mcus_x + bx) * 64, ts->quant[ts->tq[1 + c] & 3], rows);
+      if (WIN && (by < win.mrow_lo || by > win.mrow_hi)) continue;                       // a halo row no window pixel taps
+      jc_idct_block(fc + (luma_blocks + c * chroma_blocks + (long)by * mcus_x + cbx_lo + bx) * 64, ts->quant[ts->tq[1 + c] & 3],
+                    rows);
       uint8_t* plane = lc + c * CROWS * cpitch + bx * 8;
       if (HALO && rel == 0) {
         *reinterpret_cast<u32x2*>(plane) = (u32x2){rows[14], rows[15]};
@@ -345,21 +357,24 @@ __global__ __launch_bounds__(256) void jpeg_pixels_kernel(const int16_t* __restr
   P.y = ly; P.cb = lc; P.cr = lc + CROWS * cpitch;
   P.ypitch = ypitch; P.cpitch = cpitch;
   P.y0 = band * 8 * VS; P.c0 = band * 8 - HALO;
+  P.yx0 = ybx_lo * 8; P.cx0 = cbx_lo * 8;
   const int cw = (W + HS - 1) / HS, ch = (H + VS - 1) / VS;
-  const int y_lo = band * 8 * VS, rows_here = H - y_lo < 8 * VS ? H - y_lo : 8 * VS;
-  const int chunks = (W + 15) / 16;
-  const long plane_px = (long)H * W;
+  const int top = WIN ? win.top : 0, left = WIN ? win.left : 0, wh = WIN ? win.wh : H, ww = WIN ? win.ww : W;
+  const int y_lo = band * 8 * VS > top ? band * 8 * VS : top;                            // the band's rows inside the window
+  const int y_end = (band + 1) * 8 * VS < top + wh ? (band + 1) * 8 * VS : top + wh;
+  const int rows_here = y_end - y_lo;
+  const int chunks = (ww + 15) / 16;
+  const long plane_px = (long)wh * ww;
   uint8_t* of = out + row * 3 * plane_px;
   for (int t = threadIdx.x; t < rows_here * chunks; t += 256) {
     const int ry = t / chunks, x0 = (t - ry * chunks) * 16, y = y_lo + ry;
     uint32_t pr[4] = {0, 0, 0, 0}, pg[4] = {0, 0, 0, 0}, pb[4] = {0, 0, 0, 0};
-    uint8_t* o = of + (long)y * W + x0;
+    uint8_t* o = of + (long)(y - top) * ww + x0;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int x = x0 + i;
-      if (V16 || x < W) {
+      if (V16 || x0 + i < ww) {
         int r, g, b;
-        jc_pixel<SAMP>(P, x, y, cw, ch, r, g, b);
+        jc_pixel<SAMP>(P, left + x0 + i, y, cw, ch, r, g, b);
         if (V16) {
           pr[i >> 2] |= (uint32_t)r << (8 * (i & 3));
           pg[i >> 2] |= (uint32_t)g << (8 * (i & 3));
@@ -379,24 +394,38 @@ __global__ __launch_bounds__(256) void jpeg_pixels_kernel(const int16_t* __restr
   }
 }
 
-// dst_row == nullptr: the identity-row instance (tdeed_jpeg_pixels)
+// Dynamic LDS of one workgroup: the planes as the kernel lays them out, 8 VS luma rows and per chroma plane 8 rows plus the
+// 4:2:0 halo rows, ypitch = 8 * (luma block columns), cpitch = 8 * (chroma block columns).  The columns are the kernel's:
+// the whole padded MCU grid (bw0 = mcus_x * HS, mcus_x) without a window, jc_window's with one.  For 2:1 chroma the padded
+// grid can be one luma block column wider than the frame (W % 16 in 1..8), which the full window's ceil(W / 8) is not.
+static long jpeg_pixels_lds_bytes(const JcGeom& g, const JcWindow* win) {
+  const int halo = g.samp == JC_420 ? 1 : 0, nc = g.samp == JC_GREY ? 0 : 2;
+  const int ybx_n = win ? win->ybx_n : g.bw[0], cbx_n = win ? win->cbx_n : g.mcus_x;
+  return 8L * g.vs * ybx_n * 8 + (long)nc * (8 + 2 * halo) * cbx_n * 8;
+}
+
+// dst_row == nullptr: the identity-row instance (tdeed_jpeg_pixels); win: the window of tdeed_jpeg_pixels_window, nullptr for
+// the whole frame.  out holds (h, w) planes, the window's size or the frame's.
 template <int SAMP>
 static int jpeg_pixels_launch(const int16_t* coef, const int* frame_set, const uint8_t* sets, int n_sets, uint8_t* out,
-                              const int* dst_row, long out_rows, int frame_lo, int n_frames, int H, int W, hipStream_t st) {
+                              const int* dst_row, long out_rows, int frame_lo, int n_frames, int H, int W, const JcWindow* win,
+                              hipStream_t st) {
   const JcGeom g = jc_geom(W, H, SAMP);
-  const int halo = SAMP == JC_420 ? 1 : 0, nc = SAMP == JC_GREY ? 0 : 2;
-  const long lds = 8L * g.vs * g.bw[0] * 8 + (long)nc * (8 + 2 * halo) * g.mcus_x * 8;
-  TD_CHECK(lds <= 64 * 1024, "jpeg_pixels: a band of a %d pixel wide frame needs %ld bytes of LDS (limit 65536)", W, lds);
+  const JcWindow w = win ? *win : jc_window(g, 0, 0, H, W);
+  const long lds = jpeg_pixels_lds_bytes(g, win);
+  TD_CHECK(lds <= 64 * 1024, "jpeg_pixels: a band of a %d pixel wide frame needs %ld bytes of LDS (limit 65536)", w.ww, lds);
   TD_CHECK(g.mcus_y <= 65535 && n_frames <= 65535, "jpeg_pixels: %d bands x %d frames exceed the grid", g.mcus_y, n_frames);
-  const bool v16 = W % 16 == 0 && (((uintptr_t)out) & 15) == 0;
-  const dim3 grid(g.mcus_y, n_frames);
-#define JPEG_PIXELS_GO(V16, ROWS)                                                                                              \
-  hipLaunchKernelGGL((jpeg_pixels_kernel<SAMP, V16, ROWS>), grid, dim3(256), lds, st, coef, frame_set, (const JcTableSet*)sets, \
-                     n_sets, frame_lo, W, H, g.mcus_x, g.mcus_y, out, dst_row, out_rows)
-  if (dst_row) {
-    if (v16) JPEG_PIXELS_GO(true, true); else JPEG_PIXELS_GO(false, true);
+  const bool v16 = w.ww % 16 == 0 && (((uintptr_t)out) & 15) == 0;
+  const dim3 grid(w.band_n, n_frames);
+#define JPEG_PIXELS_GO(V16, ROWS, WIN)                                                                                              \
+  hipLaunchKernelGGL((jpeg_pixels_kernel<SAMP, V16, ROWS, WIN>), grid, dim3(256), lds, st, coef, frame_set, (const JcTableSet*)sets, \
+                     n_sets, frame_lo, W, H, g.mcus_x, g.mcus_y, out, dst_row, out_rows, w)
+  if (win) {
+    if (v16) JPEG_PIXELS_GO(true, true, true); else JPEG_PIXELS_GO(false, true, true);
+  } else if (dst_row) {
+    if (v16) JPEG_PIXELS_GO(true, true, false); else JPEG_PIXELS_GO(false, true, false);
   } else {
-    if (v16) JPEG_PIXELS_GO(true, false); else JPEG_PIXELS_GO(false, false);
+    if (v16) JPEG_PIXELS_GO(true, false, false); else JPEG_PIXELS_GO(false, false, false);
   }
 #undef JPEG_PIXELS_GO
   TD_LAUNCH_CHECK("jpeg_pixels");
@@ -405,7 +434,7 @@ static int jpeg_pixels_launch(const int16_t* coef, const int* frame_set, const u
 
 static int jpeg_pixels_any(const int16_t* coeff, const int* frame_table_set, const uint8_t* table_sets, int n_sets, uint8_t* out,
                            const int* dst_row, long out_rows, int frame_lo, int n_frames, int H, int W, int sampling,
-                           void* hip_stream) {
+                           const JcWindow* win, void* hip_stream) {
   TD_CHECK(coeff && frame_table_set && table_sets && out, "jpeg_pixels: null pointer");
   TD_CHECK(n_sets > 0 && n_frames > 0 && frame_lo >= 0, "jpeg_pixels: bad sizes");
   TD_CHECK(W > 0 && H > 0 && W <= 65535 && H <= 65535, "jpeg_pixels: bad frame size %dx%d", H, W);
@@ -414,13 +443,17 @@ static int jpeg_pixels_any(const int16_t* coeff, const int* frame_table_set, con
   hipStream_t st = (hipStream_t)hip_stream;
   switch (sampling) {
     case JC_GREY:
-      return jpeg_pixels_launch<JC_GREY>(coeff, frame_table_set, table_sets, n_sets, out, dst_row, out_rows, frame_lo, n_frames, H, W, st);
+      return jpeg_pixels_launch<JC_GREY>(coeff, frame_table_set, table_sets, n_sets, out, dst_row, out_rows, frame_lo, n_frames, H, W,
+                                         win, st);
     case JC_444:
-      return jpeg_pixels_launch<JC_444>(coeff, frame_table_set, table_sets, n_sets, out, dst_row, out_rows, frame_lo, n_frames, H, W, st);
+      return jpeg_pixels_launch<JC_444>(coeff, frame_table_set, table_sets, n_sets, out, dst_row, out_rows, frame_lo, n_frames, H, W,
+                                         win, st);
     case JC_422:
-      return jpeg_pixels_launch<JC_422>(coeff, frame_table_set, table_sets, n_sets, out, dst_row, out_rows, frame_lo, n_frames, H, W, st);
+      return jpeg_pixels_launch<JC_422>(coeff, frame_table_set, table_sets, n_sets, out, dst_row, out_rows, frame_lo, n_frames, H, W,
+                                         win, st);
     case JC_420:
-      return jpeg_pixels_launch<JC_420>(coeff, frame_table_set, table_sets, n_sets, out, dst_row, out_rows, frame_lo, n_frames, H, W, st);
+      return jpeg_pixels_launch<JC_420>(coeff, frame_table_set, table_sets, n_sets, out, dst_row, out_rows, frame_lo, n_frames, H, W,
+                                         win, st);
   }
   TD_CHECK(false, "jpeg_pixels: sampling %d (0 grey, 1 4:4:4, 2 4:2:2, 3 4:2:0)", sampling);
   return TDEED_OK;
@@ -428,7 +461,8 @@ static int jpeg_pixels_any(const int16_t* coeff, const int* frame_table_set, con
 
 extern "C" int tdeed_jpeg_pixels(const int16_t* coeff, const int* frame_table_set, const uint8_t* table_sets, int n_sets,
                                  uint8_t* out, int frame_lo, int n_frames, int H, int W, int sampling, void* hip_stream) {
-  return jpeg_pixels_any(coeff, frame_table_set, table_sets, n_sets, out, nullptr, 0, frame_lo, n_frames, H, W, sampling, hip_stream);
+  return jpeg_pixels_any(coeff, frame_table_set, table_sets, n_sets, out, nullptr, 0, frame_lo, n_frames, H, W, sampling, nullptr,
+                         hip_stream);
 }
 
 extern "C" int tdeed_jpeg_pixels_rows(const int16_t* coeff, const int* frame_table_set, const uint8_t* table_sets, int n_sets,
@@ -437,5 +471,42 @@ extern "C" int tdeed_jpeg_pixels_rows(const int16_t* coeff, const int* frame_tab
   TD_CHECK(dst_row && (((uintptr_t)dst_row) & 3) == 0, "jpeg_pixels_rows: dst_row must be a 4-byte aligned device pointer");
   TD_CHECK(out_rows > 0, "jpeg_pixels_rows: out_rows %ld", out_rows);
   return jpeg_pixels_any(coeff, frame_table_set, table_sets, n_sets, out, dst_row, out_rows, frame_lo, n_frames, H, W, sampling,
+                         nullptr, hip_stream);
+}
+
+// tdeed_jpeg_pixels_rows over the window [top, top + wh) x [left, left + ww) of the H x W frames: out holds rows of (3, wh, ww)
+extern "C" int tdeed_jpeg_pixels_window(const int16_t* coeff, const int* frame_table_set, const uint8_t* table_sets, int n_sets,
+                                        uint8_t* out, long out_rows, const int* dst_row, int frame_lo, int n_frames, int H, int W,
+                                        int sampling, int top, int left, int wh, int ww, void* hip_stream) {
+  TD_CHECK(dst_row && (((uintptr_t)dst_row) & 3) == 0, "jpeg_pixels_window: dst_row must be a 4-byte aligned device pointer");
+  TD_CHECK(out_rows > 0, "jpeg_pixels_window: out_rows %ld", out_rows);
+  TD_CHECK(W > 0 && H > 0 && W <= 65535 && H <= 65535, "jpeg_pixels_window: bad frame size %dx%d", H, W);
+  TD_CHECK(sampling >= JC_GREY && sampling <= JC_420, "jpeg_pixels_window: sampling %d (0 grey, 1 4:4:4, 2 4:2:2, 3 4:2:0)", sampling);
+  TD_CHECK(top >= 0 && left >= 0 && wh > 0 && ww > 0 && wh <= H - top && ww <= W - left,
+           "jpeg_pixels_window: the window %dx%d at (%d, %d) is empty or leaves the %dx%d frame", wh, ww, top, left, H, W);
+  const JcWindow w = jc_window(jc_geom(W, H, sampling), top, left, wh, ww);
+  return jpeg_pixels_any(coeff, frame_table_set, table_sets, n_sets, out, dst_row, out_rows, frame_lo, n_frames, H, W, sampling, &w,
                          hip_stream);
+}
+
+// the dynamic LDS bytes the launchers request per workgroup: of tdeed_jpeg_pixels / tdeed_jpeg_pixels_rows when windowed == 0
+// (the window arguments are ignored), of tdeed_jpeg_pixels_window otherwise; -1 for a bad geometry or window
+extern "C" long tdeed_jpeg_pixels_lds_bytes(int W, int H, int sampling, int windowed, int top, int left, int wh, int ww) {
+  if (W <= 0 || H <= 0 || W > 65535 || H > 65535 || sampling < JC_GREY || sampling > JC_420) return -1;
+  const JcGeom g = jc_geom(W, H, sampling);
+  if (!windowed) return jpeg_pixels_lds_bytes(g, nullptr);
+  if (top < 0 || left < 0 || wh <= 0 || ww <= 0 || wh > H - top || ww > W - left) return -1;
+  const JcWindow w = jc_window(g, top, left, wh, ww);
+  return jpeg_pixels_lds_bytes(g, &w);
+}
+
+// the ranges of jc_window as ten ints (jpegdev.window_blocks is held against them): band_lo, band_n, ybx_lo, ybx_n, ybr_lo,
+// ybr_hi, cbx_lo, cbx_n, mrow_lo, mrow_hi; -1 for a bad geometry or window
+extern "C" int tdeed_jpeg_window_blocks(int W, int H, int sampling, int top, int left, int wh, int ww, int* ranges) {
+  if (!ranges || W <= 0 || H <= 0 || W > 65535 || H > 65535 || sampling < JC_GREY || sampling > JC_420) return -1;
+  if (top < 0 || left < 0 || wh <= 0 || ww <= 0 || wh > H - top || ww > W - left) return -1;
+  const JcWindow w = jc_window(jc_geom(W, H, sampling), top, left, wh, ww);
+  const int r[10] = {w.band_lo, w.band_n, w.ybx_lo, w.ybx_n, w.ybr_lo, w.ybr_hi, w.cbx_lo, w.cbx_n, w.mrow_lo, w.mrow_hi};
+  for (int i = 0; i < 10; ++i) ranges[i] = r[i];
+  return 0;
 }

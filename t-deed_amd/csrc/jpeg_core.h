@@ -100,6 +100,51 @@ JC_HD JcGeom jc_geom(int W, int H, int samp) {
   return g;
 }
 
+// What a pixel pass over the window [top, top + wh) x [left, left + ww) of a frame reads (jpegdev.window_blocks states the
+// same formulas): the bands (MCU rows) that hold window rows, the luma block columns and block rows under the window,
+// the chroma block columns of the samples jc_pixel's taps touch -- for 2:1 chroma sample x >> 1 and its clamped
+// neighbour, one to the left of an even x, one to the right of an odd x -- and the MCU rows whose coefficients are read:
+// the bands, plus for 4:2:0 the band above when the window starts on a band's first row and the band below when it ends
+// on a band's last row (the vertical taps' halo).  All ranges are inclusive lo / count or lo / hi.
+struct JcWindow {
+  int top, left, wh, ww;
+  int band_lo, band_n;          // bands band_lo .. band_lo + band_n - 1
+  int ybx_lo, ybx_n;            // luma block columns
+  int ybr_lo, ybr_hi;           // luma block rows
+  int cbx_lo, cbx_n;            // chroma block columns (0, 0 for greyscale)
+  int mrow_lo, mrow_hi;         // MCU rows read, halo included
+};
+
+// the caller has checked 0 <= top, 0 < wh, top + wh <= H and the same for the columns
+JC_HD JcWindow jc_window(const JcGeom& g, int top, int left, int wh, int ww) {
+  JcWindow w;
+  w.top = top; w.left = left; w.wh = wh; w.ww = ww;
+  const int x1 = left + ww - 1, y1 = top + wh - 1;
+  w.band_lo = top / (8 * g.vs);
+  w.band_n = y1 / (8 * g.vs) - w.band_lo + 1;
+  w.ybx_lo = left / 8;
+  w.ybx_n = x1 / 8 - w.ybx_lo + 1;
+  w.ybr_lo = top / 8;
+  w.ybr_hi = y1 / 8;
+  w.cbx_lo = w.cbx_n = 0;
+  if (g.ncomp == 3) {
+    int c_lo = left, c_hi = x1;
+    if (g.hs == 2) {
+      c_lo = (left & 1) ? left >> 1 : ((left >> 1) > 0 ? (left >> 1) - 1 : 0);
+      c_hi = (x1 & 1) ? ((x1 >> 1) + 1 < g.cw[1] ? (x1 >> 1) + 1 : g.cw[1] - 1) : x1 >> 1;
+    }
+    w.cbx_lo = c_lo / 8;
+    w.cbx_n = c_hi / 8 - w.cbx_lo + 1;
+  }
+  w.mrow_lo = w.band_lo;
+  w.mrow_hi = w.band_lo + w.band_n - 1;
+  if (g.vs == 2 && g.ncomp == 3) {
+    if (top % 16 == 0 && w.mrow_lo > 0) --w.mrow_lo;
+    if (y1 % 16 == 15 && (y1 >> 1) + 1 < g.ch[1]) ++w.mrow_hi;
+  }
+  return w;
+}
+
 // --------------------------------------------------------------------------------------------- bit reader
 // Right-aligned 64-bit buffer with n valid bits.  Past the end of the segment (or behind a marker) it is fed zero
 // bits, as libjpeg does; `pad` counts the zero bits at the tail, so n < pad after a symbol means it consumed some.

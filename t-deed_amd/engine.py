@@ -504,6 +504,12 @@ class SgpBuilder:
 TrunkGeometry = namedtuple("TrunkGeometry", "crop ch cw maps")
 
 
+def centre_window(H, W, ch, cw):
+    """(top, left, ch, cw) of the centre window of ch x cw pixels in an H x W frame: the crop rectangle of the first launch,
+    and of everything that has to cut the same pixels (evalutil.ResidentJpegVideos)"""
+    return (int(round((H - ch) / 2.0)), int(round((W - cw) / 2.0)), ch, cw)
+
+
 def trunk_geometry(blocks, crop, H, W):
     """Map sizes of the trunk over H x W frames.  Pure.  blocks: the block specs; crop: side of the centre crop (None or 0:
     none).  crop: the rectangle (top, left, ch, cw) the first launch reads (None: the whole frame), ch, cw: its size;
@@ -511,7 +517,7 @@ def trunk_geometry(blocks, crop, H, W):
     ch, cw, rect = H, W, None
     if crop is not None and crop > 0 and (crop != H or crop != W):
         ch = cw = crop
-        rect = (int(round((H - ch) / 2.0)), int(round((W - cw) / 2.0)), ch, cw)
+        rect = centre_window(H, W, ch, cw)
     h, w = (ch + 1) // 2, (cw + 1) // 2
     maps = [(h, w, blocks[0].cin)]
     for blk in blocks:

@@ -777,3 +777,173 @@ def map_videos(model, videos, classes, truth, suppress, tolerances=(0, 1, 2, 4),
         aps = {lab: [float(ap[i, t, classes[lab]]) for t in range(len(tols))] for lab in labels}
         out.append(([float(np.mean([aps[lab][t] for lab in aps])) for t in range(len(tols))], aps))
     return out
+
+
+# ----------------------------------------------------------------------------- validation videos from resident JPEG streams
+def _crop_window(crop, H, W):
+    """crop: None, an int side or (wh, ww) -> the centre window (top, left, wh, ww) by engine.centre_window -- the rectangle
+    `engine.trunk_geometry` gives the first launch -- or None when the window is the whole frame"""
+    from .engine import centre_window
+    if crop is None:
+        return None
+    wh, ww = (int(crop), int(crop)) if np.ndim(crop) == 0 else (int(crop[0]), int(crop[1]))
+    if wh < 1 or ww < 1:
+        raise ValueError(f"ResidentJpegVideos: crop {crop!r} must be positive")
+    if wh > H or ww > W:
+        raise ValueError(f"ResidentJpegVideos: the crop {wh}x{ww} is larger than the {H}x{W} frames")
+    if (wh, ww) == (H, W):
+        return None
+    return centre_window(H, W, wh, ww)
+
+
+class ResidentJpegVideos:
+    """The videos of a validation split resident on the device COMPRESSED, each decoded there when it is scored: what
+    `trainclips.ResidentJpegClips` is to training.  videos: the label list's dicts (video, num_frames, optionally fps);
+    jpegs: their `trainclips.load_resident_jpegs(..., stride=s)` pack, video i of which has ceil(num_frames / s) frames.
+    Construction is `ResidentJpegClips`' (`trainclips._ResidentStreams`): the shards' streams in one buffer, the tables in
+    one copy, the index pass once per shard, one host synchronisation, fallback and flagged frames decoded once with
+    `feeder.read_frame` into a side buffer; resident bytes over max_resident_bytes raise ValueError before anything is
+    uploaded.  split_mcus: MCUs per piece (default one MCU row); max_coeff_bytes: the coefficient buffer, a video beyond
+    it decodes in chunks of frames.
+
+    crop: None, an int side or (wh, ww): `frames` returns the centre window only (`engine.centre_window`, the rectangle the
+    first launch of a crop_dim model reads).  Then the pixel pass is ops.jpeg_pixels_window, the items leave out the pieces
+    whose MCU rows the window does not read (`trainclips.video_tables`), and the side buffer is kept cropped.
+
+    `frames(i)` is video i as a device uint8 (L_i, 3, h, w) tensor, the bits of `feeder.load_video`'s frames (cut to the
+    window); `sources()` is the `videos` argument of `stitch_videos`, `spot_videos`, `map_videos`: (name, length, fps,
+    callable) with fps from the video dicts.  `stats`: `ResidentJpegClips.stats`' fields plus frame_shape and
+    decoded_bytes_per_frame (of what `frames` returns).  `resident_bytes` and the budget count what construction leaves on the
+    device, as `ResidentJpegClips` counts it.  Not counted: the coefficient buffer (max_coeff_bytes bounds it) and the item
+    tables of the videos decoded so far, which are kept on the host and on the device for the next pass: 8 bytes per piece
+    plus 8 per frame, about 120 bytes per 224-row 4:2:0 frame against some 20 000 of stream.
+    Not offered: the frame ring (`stream_frames=True`) fed by this decode, and `reuse_frames` beyond what the consumers do
+    with any device tensor."""
+
+    UPLOAD_CHUNK_BYTES = 64 << 20        # the streams are uploaded in copies of this size (`ResidentJpegClips`' default)
+
+    def __init__(self, videos, jpegs, crop=None, split_mcus=None, max_resident_bytes=16 << 30, max_coeff_bytes=512 << 20,
+                 device="cuda"):
+        import threading
+        import torch
+        from . import jpegdev, ops
+        from .trainclips import _ResidentStreams
+        from . import streams
+        videos = list(videos)
+        stride = int(getattr(jpegs, "stride", 1))
+        if not videos or len(videos) != len(jpegs.video_len):
+            raise ValueError(f"ResidentJpegVideos: {len(videos)} videos, {len(jpegs.video_len)} in the packed set")
+        for v, n in zip(videos, jpegs.video_len):
+            if -(-int(v["num_frames"]) // stride) != int(n):
+                raise ValueError(f"ResidentJpegVideos: video {v['video']} has {int(v['num_frames'])} frames at stride {stride}, "
+                                 f"the packed set {int(n)}")
+        if int(max(jpegs.video_len)) > 65535:
+            raise ValueError(f"ResidentJpegVideos: a video of {int(max(jpegs.video_len))} frames exceeds the kernels' 65535 rows")
+        if int(max_coeff_bytes) < 1:
+            raise ValueError("ResidentJpegVideos: max_coeff_bytes must be positive")
+        if jpegs.width:
+            self.window = _crop_window(crop, jpegs.height, jpegs.width)      # argument errors before any file is touched
+            rs = _ResidentStreams("ResidentJpegVideos", jpegs, split_mcus, max_resident_bytes, self.window)
+        else:                                                   # the geometry comes from Pillow's decode of the first frame
+            rs = _ResidentStreams("ResidentJpegVideos", jpegs, split_mcus, 1 << 62, None)
+            self.window = _crop_window(crop, rs.H, rs.W)
+            rs.max_resident_bytes = max_resident_bytes
+            rs.set_window(self.window)                          # the budget, with side frames of the window's size
+        self._rs, self.samp, self.split_mcus = rs, rs.samp, rs.split
+        self.H, self.W = rs.H, rs.W
+        self.shape = rs.side_shape
+        self.names = [v["video"] for v in videos]
+        self.fps = [v.get("fps") for v in videos]
+        self.video_first = [int(x) for x in jpegs.video_first]
+        self.video_len = [int(x) for x in jpegs.video_len]
+        self._mcu_rows = jpegdev.window_blocks(rs.geom, *self.window).mcu_rows if self.window is not None else None
+        self.device = dev = torch.device(device)
+        self.stream = streams.new_stream(device)
+        self.stream.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(self.stream):
+            rs.upload(self.stream, dev, self.UPLOAD_CHUNK_BYTES)
+            self._fc = fc = ops.jpeg_frame_coeffs(rs.W, rs.H, rs.samp)
+            longest = max(self.video_len)
+            self._chunk = min(longest, 65535, max(1, int(max_coeff_bytes) // (2 * fc)))
+            self._coeff = torch.empty(self._chunk * fc, dtype=torch.int16, device=dev) if rs.n_seg else None
+            self._ident = torch.arange(longest, dtype=torch.int32, device=dev)
+            self._err = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._err_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        self.stream.synchronize()
+        self._lock = threading.Lock()
+        self._tabs = {}                                          # video -> (host tables, their device copies)
+        # internal, for tools/bench_video.py only: set to a list and `frames` appends (start, between, end) timing events
+        # around the entropy and the pixel launch of every chunk; None (the default) records nothing
+        self._kernel_events = None
+        self.stats = dict(rs.stats(), frame_shape=tuple(self.shape), decoded_bytes_per_frame=int(np.prod(self.shape)))
+
+    def __len__(self):
+        return len(self.names)
+
+    def video_tables(self, i):
+        """`trainclips.video_tables` of video i: what `frames(i)` launches with (host arrays)"""
+        from .trainclips import video_tables
+        rs = self._rs
+        return video_tables(self.video_first[i], self.video_len[i], rs.frame_set, rs.side_row, rs.piece_lo, rs.piece_n,
+                            chunk_slots=self._chunk, piece_mcu=rs.piece_mcu, mcus_x=rs.geom.mcus_x, mcu_rows=self._mcu_rows)
+
+    def frames(self, i, out=None):
+        """Video i decoded on the object's own stream: device uint8 (L_i, 3, h, w), into `out` when given.  Per coefficient
+        chunk: zero it, ops.jpeg_entropy_items, the pixel pass (ops.jpeg_pixels_rows, or ops.jpeg_pixels_window with crop);
+        then ops.jpeg_slot_fill for the side frames.  Waits for the stream and reads the device error word: non-zero raises
+        RuntimeError naming the video.  No file is read.  Calls from several threads take turns (one coefficient buffer)."""
+        import torch
+        from . import ops
+        i = int(i)
+        if not 0 <= i < len(self.names):
+            raise IndexError(f"ResidentJpegVideos: video {i} of {len(self.names)}")
+        rs, L = self._rs, self.video_len[i]
+        if out is None:
+            out = torch.empty((L,) + tuple(self.shape), dtype=torch.uint8, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self._ident.device
+              or not out.is_contiguous() or tuple(out.shape) != (L,) + tuple(self.shape)):
+            raise ValueError(f"ResidentJpegVideos: out must be a contiguous uint8 {(L,) + tuple(self.shape)} tensor on "
+                             f"{self._ident.device}")
+        with self._lock:
+            if i not in self._tabs:
+                tb = self.video_tables(i)
+                to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)     # noqa: E731
+                self._tabs[i] = (tb, to(tb.slot_set), to(tb.fill), to(tb.items), to(tb.waves))
+            tb, d_set, d_fill, d_items, d_waves = self._tabs[i]
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))     # `out` may be a block this stream just freed
+            with torch.cuda.stream(self.stream):
+                for lo, hi, w_lo, w_hi in tb.chunks:
+                    self._coeff[:(hi - lo) * self._fc].zero_()
+                    if self._kernel_events is not None:
+                        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                        ev[0].record(self.stream)
+                    ops.jpeg_entropy_items(rs.jstream, rs.pieces, d_items, d_waves[w_lo:w_hi], rs.table_sets, self.W, self.H,
+                                           self.samp, lo, hi - lo, self._coeff, self._err)
+                    if self._kernel_events is not None:
+                        ev[1].record(self.stream)
+                    if self.window is None:
+                        ops.jpeg_pixels_rows(self._coeff, d_set, rs.table_sets, out, self._ident, lo, hi - lo, self.samp)
+                    else:
+                        ops.jpeg_pixels_window(self._coeff, d_set, rs.table_sets, out, self._ident, lo, hi - lo, self.samp,
+                                               self.H, self.W, self.window[0], self.window[1])
+                    if self._kernel_events is not None:
+                        ev[2].record(self.stream)
+                        self._kernel_events.append(tuple(ev))
+                if bool((tb.fill >= 0).any()):
+                    ops.jpeg_slot_fill(rs.side, d_fill, out)
+                self._err_host.copy_(self._err, non_blocking=True)
+            self.stream.synchronize()
+            word = int(self._err_host[0])
+            if word:
+                with torch.cuda.stream(self.stream):
+                    self._err.zero_()
+                codes = [c for c in range(1, 8) if word >> c & 1]
+                raise RuntimeError(f"ResidentJpegVideos: video {self.names[i]} met decode errors on the device (status codes "
+                                   f"{codes}); the resident streams or tables are damaged")
+        return out
+
+    def sources(self):
+        """[(name, length, fps, callable)]: the `videos` argument of stitch_videos / spot_videos / map_videos and, callables
+        called, of predict_video_group; callable() is `frames(i)`"""
+        import functools
+        return [(self.names[i], self.video_len[i], self.fps[i], functools.partial(self.frames, i)) for i in range(len(self.names))]

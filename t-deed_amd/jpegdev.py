@@ -56,6 +56,42 @@ def geometry(width, height, samp):
                            frame_blocks=off)
 
 
+def window_blocks(geom, top, left, wh, ww):
+    """What a pixel pass over the window [top, top + wh) x [left, left + ww) of a frame reads, as csrc/jpeg_core.h jc_window
+    (the launcher of ops.jpeg_pixels_window uses the same formulas).  Pure.  Every range is half-open (lo, hi):
+    bands: the MCU rows that hold window rows (the grid); y_cols / y_rows: the luma block columns / block rows under the
+    window; c_cols: the chroma block columns of the samples the up-sampling taps touch -- for 2:1 chroma sample x >> 1 and
+    its clamped neighbour, x >> 1 - 1 for an even x, x >> 1 + 1 for an odd one -- None for greyscale; mcu_rows: the MCU
+    rows whose coefficients are read: the bands, for 4:2:0 one more above when the window starts on a band's first row
+    and one more below when it ends on a band's last row (the vertical taps' halo).  ranges: the ten ints of
+    ops.jpeg_window_blocks.  A window that is empty or leaves the frame raises ValueError."""
+    top, left, wh, ww = int(top), int(left), int(wh), int(ww)
+    if min(wh, ww) < 1 or top < 0 or left < 0 or top + wh > geom.height or left + ww > geom.width:
+        raise ValueError(f"window_blocks: the window {wh}x{ww} at ({top}, {left}) is empty or leaves the "
+                         f"{geom.height}x{geom.width} frame")
+    x1, y1 = left + ww - 1, top + wh - 1
+    bands = (top // (8 * geom.vs), y1 // (8 * geom.vs) + 1)
+    y_cols, y_rows = (left // 8, x1 // 8 + 1), (top // 8, y1 // 8 + 1)
+    c_cols = None
+    if geom.ncomp == 3:
+        c_lo, c_hi = left, x1
+        if geom.hs == 2:
+            c_lo = left >> 1 if left & 1 else max((left >> 1) - 1, 0)
+            c_hi = min((x1 >> 1) + 1, geom.cw[1] - 1) if x1 & 1 else x1 >> 1
+        c_cols = (c_lo // 8, c_hi // 8 + 1)
+    m_lo, m_hi = bands
+    if geom.vs == 2 and geom.ncomp == 3:
+        if top % 16 == 0 and m_lo > 0:
+            m_lo -= 1
+        if y1 % 16 == 15 and (y1 >> 1) + 1 < geom.ch[1]:
+            m_hi += 1
+    cc = c_cols or (0, 0)
+    ranges = [bands[0], bands[1] - bands[0], y_cols[0], y_cols[1] - y_cols[0], y_rows[0], y_rows[1] - 1, cc[0], cc[1] - cc[0],
+              m_lo, m_hi - 1]
+    return SimpleNamespace(top=top, left=left, wh=wh, ww=ww, bands=bands, y_cols=y_cols, y_rows=y_rows, c_cols=c_cols,
+                           mcu_rows=(m_lo, m_hi), ranges=ranges)
+
+
 def _be16(a, p):
     return (int(a[p]) << 8) | int(a[p + 1])
 
@@ -388,6 +424,17 @@ def piece_counts(segments, split_mcus):
         raise ValueError("split_mcus must be positive")
     first, n = segments[:, 1].astype(np.int64), segments[:, 2].astype(np.int64)
     return 1 + (first + n - 1) // split_mcus - first // split_mcus
+
+
+def piece_ranges(segments, split_mcus):
+    """(first MCU, MCU count) of every piece of a segment table under `split_points`, int64 (n_pieces, 2), in the piece
+    table's order: segment row by segment row, the pieces of a row in ascending MCU order (what the index pass records in
+    JcPiece.first_mcu / n_mcu, known on the host without it)."""
+    out = []
+    for m0, nm in np.asarray(segments)[:, 1:3].tolist():
+        cuts = [m0] + split_points(m0, nm, split_mcus) + [m0 + nm]
+        out += [(a, b - a) for a, b in zip(cuts[:-1], cuts[1:])]
+    return np.asarray(out, np.int64).reshape(-1, 2)
 
 
 class ParseCache:

@@ -1256,6 +1256,58 @@ def jpeg_pixels_rows(coeff, frame_set, table_sets, out, dst_row, frame_lo, n_fra
     return out
 
 
+def jpeg_pixels_window(coeff, frame_set, table_sets, out, dst_row, frame_lo, n_frames, sampling, H, W, top, left):
+    """jpeg_pixels_rows over a window of the H x W frames: out is a contiguous uint8 (...,3,wh,ww) buffer and row dst_row[f]
+    of it gets the pixels [top, top + wh) x [left, left + ww) of frame f.  Only the bands of the window are launched and
+    only the blocks under it are transformed (jpegdev.window_blocks): the coefficients of every other block are never
+    read.  The full window (0, 0, H, W) gives the bits of jpeg_pixels_rows.  A window that is empty or leaves the frame
+    raises ValueError."""
+    dev = out.device
+    _chk(out, "out", torch.uint8)
+    _chk(coeff, "coeff", torch.int16)
+    _chk_jpeg_tables("jpeg_pixels_window", dev, frame_set=(frame_set, torch.int32), table_sets=(table_sets, torch.uint8),
+                     dst_row=(dst_row, torch.int32))
+    if out.dim() < 4 or out.shape[-3] != 3:
+        raise ValueError("jpeg_pixels_window: out must be (...,3,wh,ww)")
+    wh, ww = int(out.shape[-2]), int(out.shape[-1])
+    H, W, top, left = int(H), int(W), int(top), int(left)
+    if min(wh, ww) < 1 or top < 0 or left < 0 or top + wh > H or left + ww > W:
+        raise ValueError(f"jpeg_pixels_window: the window {wh}x{ww} at ({top}, {left}) is empty or leaves the {H}x{W} frame")
+    rows = out.numel() // (3 * wh * ww)
+    if table_sets.dim() != 2 or table_sets.shape[1] != 4240 or table_sets.shape[0] < 1:
+        raise ValueError("jpeg_pixels_window: table_sets (n_sets, 4240)")
+    if rows < 1 or frame_lo < 0 or n_frames < 1 or min(frame_set.numel(), dst_row.numel()) < frame_lo + n_frames:
+        raise ValueError(f"jpeg_pixels_window: frames {frame_lo}..{frame_lo + n_frames} outside the {frame_set.numel()} of frame_set "
+                         f"/ {dst_row.numel()} of dst_row, or out has no row")
+    fc = jpeg_frame_coeffs(W, H, sampling)
+    if coeff.numel() < int(n_frames) * fc:
+        raise ValueError(f"jpeg_pixels_window: coeff holds {coeff.numel()} values, {n_frames} frames need {int(n_frames) * fc}")
+    call("tdeed_jpeg_pixels_window", ptr(coeff), ptr(frame_set), ptr(table_sets), table_sets.shape[0], ptr(out), rows, ptr(dst_row),
+         int(frame_lo), int(n_frames), H, W, int(sampling), top, left, wh, ww, stream_ptr())
+    return out
+
+
+def jpeg_window_blocks(W, H, sampling, top, left, wh, ww):
+    """the launcher's block ranges of a window (csrc/jpeg_core.h jc_window) as ten ints, in jpegdev.window_blocks' order:
+    band lo / n, luma block columns lo / n, luma block rows lo / hi, chroma block columns lo / n, MCU rows lo / hi"""
+    import ctypes
+    r = (ctypes.c_int * 10)()
+    if _lib.load().tdeed_jpeg_window_blocks(int(W), int(H), int(sampling), int(top), int(left), int(wh), int(ww), r) != 0:
+        raise ValueError(f"jpeg_window_blocks: bad geometry {H}x{W}, sampling {sampling} or window {wh}x{ww} at ({top}, {left})")
+    return list(r)
+
+
+def jpeg_pixels_lds_bytes(W, H, sampling, window=None):
+    """dynamic LDS bytes per workgroup that the pixel launchers request: jpeg_pixels / jpeg_pixels_rows without `window`,
+    jpeg_pixels_window with window = (top, left, wh, ww)"""
+    top, left, wh, ww = window if window is not None else (0, 0, 0, 0)
+    n = int(_lib.load().tdeed_jpeg_pixels_lds_bytes(int(W), int(H), int(sampling), int(window is not None), int(top), int(left),
+                                                    int(wh), int(ww)))
+    if n < 0:
+        raise ValueError(f"jpeg_pixels_lds_bytes: bad geometry {H}x{W}, sampling {sampling} or window {window}")
+    return n
+
+
 PIECE_BYTES = 72          # csrc/jpeg_core.h JcPiece, jpegdev.PIECE
 
 

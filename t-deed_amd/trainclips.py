@@ -371,9 +371,11 @@ class ResidentJpegs:
       the table-set column of every shard indexes `table_sets`, the one array of the whole set.
     frame_set int32 (n_frames,): table set per frame, -1 = not decodable on the device (in `fallback`).
     video_first / video_len: per video its first frame in the set-wide numbering and its length; names: every frame's file.
-    width / height / samp: geometry and sampling of the set's first supported frame (0 x 0 when there is none)."""
+    width / height / samp: geometry and sampling of the set's first supported frame (0 x 0 when there is none).
+    stride: the sampling of `load_resident_jpegs`: frame j of a video is its file j * stride."""
 
-    def __init__(self, shards, table_sets, frame_set, fallback, video_first, video_len, names, width, height, samp):
+    def __init__(self, shards, table_sets, frame_set, fallback, video_first, video_len, names, width, height, samp, stride=1):
+        self.stride = int(stride)
         self.shards, self.table_sets, self.frame_set, self.fallback = shards, table_sets, frame_set, fallback
         self.video_first, self.video_len, self.names = video_first, video_len, names
         self.width, self.height, self.samp = width, height, samp
@@ -395,18 +397,23 @@ class ResidentJpegs:
         return sum(int(s.packed.stream_np.size) for s in self.shards)
 
 
-def load_resident_jpegs(frame_dir, dataset, videos, pool=None, cache=None, shard_bytes=1 << 30, pinned=True):
+def load_resident_jpegs(frame_dir, dataset, videos, pool=None, cache=None, shard_bytes=1 << 30, pinned=True, stride=1):
     """Read every frame file of the label list ONCE (through `pool`'s threads when a DecodePool is given), parse it (with
     `cache`, a jpegdev.ParseCache, when given) and pack the entropy segments with `jpegdev.pack_frames`, in shards of
     consecutive frames whose stream stays under shard_bytes (a shard holds at least one frame; the default is below 2^31
     because a segment row's byte offset is int32) -> ResidentJpegs.  Geometry and sampling are those of the set's first
     supported frame: a supported frame of another geometry raises ValueError, one of another sampling takes the fallback,
     as a file outside the decoder's subset does.  Missing files: as `load_resident_videos` -- num_frames must be the number
-    of frames that exist (ValueError), a hole in front of an existing frame raises FileNotFoundError."""
+    of frames that exist (ValueError), a hole in front of an existing frame raises FileNotFoundError.
+    stride = s: only the files j * s of every video are read and packed (`feeder.load_video`'s sampling) and video_len is
+    ceil(num_frames / s); the set remembers s (`ResidentJpegs.stride`)."""
     import os
     from . import feeder, jpegdev
     if not 0 < shard_bytes < 1 << 31:
         raise ValueError("shard_bytes must be positive and below 2^31 (a segment row's byte offset is int32)")
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("load_resident_jpegs: stride must be positive")
     names, video_first, video_len = [], [], []
     for v in videos:
         n = int(v["num_frames"])
@@ -414,12 +421,12 @@ def load_resident_jpegs(frame_dir, dataset, videos, pool=None, cache=None, shard
         if n < 1 or not os.path.exists(path_fn(n - 1)):
             raise ValueError(f"video {v['video']}: num_frames={n}, but {path_fn(max(n, 1) - 1)} does not exist -- num_frames must "
                              "be the number of frames that exist")
-        own = [path_fn(j) for j in range(n)]
+        own = [path_fn(j) for j in range(0, n, stride)]
         for p in own:
             if not os.path.exists(p):
                 raise FileNotFoundError(f"video {v['video']}: {p} is missing although later frames exist")
         video_first.append(len(names))
-        video_len.append(n)
+        video_len.append(len(own))
         names += own
     reader = pool.ex.map if pool is not None and hasattr(pool, "ex") else map
     first = None
@@ -478,7 +485,7 @@ def load_resident_jpegs(frame_dir, dataset, videos, pool=None, cache=None, shard
         s.packed.table_sets = table_sets
     w, h, samp = (first.width, first.height, first.samp) if first is not None else (0, 0, 0)
     return ResidentJpegs(shards, table_sets, frame_set, sorted(fallback), np.asarray(video_first, np.int64),
-                         np.asarray(video_len, np.int64), names, w, h, samp)
+                         np.asarray(video_len, np.int64), names, w, h, samp, stride)
 
 
 def _cut_waves(keys):
@@ -494,14 +501,16 @@ def _cut_waves(keys):
     return np.asarray(out, np.int32).reshape(-1, 2)
 
 
-def batch_tables(rows, clip_len, stride, frame_set, side_row, piece_lo, piece_n, n_slots=None, clip_slot=None, chunk_slots=None):
+def batch_tables(rows, clip_len, stride, frame_set, side_row, piece_lo, piece_n, n_slots=None, clip_slot=None, chunk_slots=None,
+                 piece_keep=None):
     """The tables of one batch of `ResidentJpegClips` (pure numpy; no file, no device).
     rows: int64 (>= 3, n) -- per clip the first frame of its video in the set-wide numbering, the clip's base and the
     video's length (`ResidentClips`' rows).  Slot clip_slot[k] + t (default k * clip_len + t) of the batch shows frame
     first + base + t * stride of clip k, or zeros where base + t * stride falls outside the video (the window rule of
     ops.train_clip_gather).  frame_set / side_row / piece_lo / piece_n: per frame of the set its table set (-1: not decoded
     on the device), its row in the side buffer of decoded frames (-1: none), its first row in the piece table and its
-    number of pieces.  chunk_slots: slots per coefficient chunk (default: all in one).
+    number of pieces.  chunk_slots: slots per coefficient chunk (default: all in one).  piece_keep: bool per row of the
+    piece table, False leaves the piece out of the items (`video_tables`' MCU-row filter); default: every piece.
     -> namespace(n_slots,
          slot_set int32 (n_slots,): table set of every slot the device decodes, -1 for the others (padding, side, unused);
          fill int32 (n_slots,): -1 a padding slot (zeros), r >= 0 the side row to copy, -2 leave the slot alone;
@@ -533,6 +542,9 @@ def batch_tables(rows, clip_len, stride, frame_set, side_row, piece_lo, piece_n,
     it_slot = np.repeat(slots[dev], cnt)
     it_piece = np.repeat(piece_lo[g[dev]].astype(np.int64), cnt) + (np.arange(n_items) - np.repeat(np.cumsum(cnt) - cnt, cnt))
     it_set = np.repeat(sets[dev], cnt)
+    if piece_keep is not None:
+        on = np.asarray(piece_keep, bool)[it_piece]
+        it_slot, it_piece, it_set = it_slot[on], it_piece[on], it_set[on]
     per = total if not chunk_slots else int(chunk_slots)
     it_chunk = it_slot // max(per, 1)
     order = np.lexsort((it_piece, it_set, it_chunk))
@@ -546,6 +558,199 @@ def batch_tables(rows, clip_len, stride, frame_set, side_row, piece_lo, piece_n,
             w = np.flatnonzero(wchunk == c)
             chunks.append((int(c) * per, min((int(c) + 1) * per, total), int(w[0]), int(w[-1]) + 1))
     return SimpleNamespace(n_slots=total, slot_set=slot_set, fill=fill, items=items, waves=waves, chunks=chunks)
+
+
+def video_tables(first, length, frame_set, side_row, piece_lo, piece_n, chunk_slots=None, piece_mcu=None, mcus_x=None,
+                 mcu_rows=None):
+    """`batch_tables` for one whole video (pure numpy; no file, no device): the video is one "clip" of its own length at
+    stride 1 over the set's numbering, so slot t shows frame first + t and no slot is padding.  chunk_slots: frames per
+    coefficient chunk.  mcu_rows = (lo, hi): the MCU rows a windowed pixel pass reads (`jpegdev.window_blocks(...).mcu_rows`,
+    halo rows included); a piece whose MCUs -- piece_mcu int (n_pieces, 2) rows of (first MCU, MCU count), `jpegdev.
+    piece_ranges` -- lie wholly in other MCU rows (mcus_x MCUs each) is left out of the items.  -> batch_tables' namespace."""
+    keep = None
+    if mcu_rows is not None:
+        if piece_mcu is None or not mcus_x or int(mcus_x) < 1:
+            raise ValueError("video_tables: the MCU-row filter needs piece_mcu and mcus_x")
+        lo, hi = int(mcu_rows[0]), int(mcu_rows[1])
+        if not 0 <= lo < hi:
+            raise ValueError(f"video_tables: MCU rows {lo}..{hi}")
+        pm = np.asarray(piece_mcu, np.int64).reshape(-1, 2)
+        keep = ((pm[:, 0] + pm[:, 1] - 1) // int(mcus_x) >= lo) & (pm[:, 0] // int(mcus_x) < hi)
+    if int(length) < 1 or int(first) < 0:
+        raise ValueError(f"video_tables: {int(length)} frames from frame {int(first)}")
+    rows = np.asarray([[int(first)], [0], [int(length)]], np.int64)
+    return batch_tables(rows, int(length), 1, frame_set, side_row, piece_lo, piece_n, chunk_slots=chunk_slots, piece_keep=keep)
+
+
+class _ResidentStreams:
+    """What `ResidentJpegClips` and `evalutil.ResidentJpegVideos` share: a packed set (`load_resident_jpegs`) made resident.
+    The constructor is host arithmetic -- geometry, piece offsets, the resident bytes (stream, segment and piece tables,
+    table sets, side buffer) held against max_resident_bytes, a ValueError naming `who` before anything is uploaded.
+    `upload`, called inside the caller's stream context, copies the shards' streams into one buffer and the tables in one
+    copy, runs the index pass (ops.jpeg_entropy_index, once per shard), reads the per-segment statuses back -- the one host
+    synchronisation -- and decodes the fallback and the flagged frames once with `feeder.read_frame` into the side buffer
+    (the budget is checked again when the index pass added side frames).  window = (top, left, wh, ww), here or through
+    `set_window` before `upload`: the side buffer keeps that window of its frames only.  Afterwards: jstream, table_sets, pieces, side (device tensors or None),
+    frame_set / side_row / piece_lo / piece_n per frame of the set, piece_mcu per piece row, `stats()`."""
+
+    def __init__(self, who, jpegs, split_mcus, max_resident_bytes, window=None):
+        from . import feeder, jpegdev
+        self.who, self.jpegs, self.max_resident_bytes, self.window = who, jpegs, max_resident_bytes, window
+        self.fr0 = None
+        if jpegs.width:
+            W, H, samp = jpegs.width, jpegs.height, jpegs.samp
+        else:                                               # nothing for the device: the geometry comes from Pillow
+            self.fr0 = feeder.read_frame(jpegs.names[0])
+            H, W, samp = int(self.fr0.shape[1]), int(self.fr0.shape[2]), 0
+        self.H, self.W, self.samp = H, W, samp
+        self.geom = geom = jpegdev.geometry(W, H, samp)
+        self.split = split = int(split_mcus) if split_mcus is not None else geom.mcus_x
+        if split < 1:
+            raise ValueError("split_mcus must be positive")
+        self.side_shape, self.fb = (3, H, W), 3 * H * W
+        self.shards = shards = [s for s in jpegs.shards]
+        self.seg_lo, self.piece_cnt, self.base, total = [], [], [], 0
+        n_seg = 0
+        for s in shards:
+            self.seg_lo.append(n_seg)
+            n_seg += s.packed.n_segments
+            self.piece_cnt.append(jpegdev.piece_counts(s.packed.segments, split) if s.packed.n_segments else np.zeros(0, np.int64))
+            self.base.append(total)
+            total += (int(s.packed.stream_np.size) + 15) & ~15 if s.packed.n_segments else 0
+        self.n_seg, self.total = n_seg, total
+        self.piece_off = np.concatenate([[0], np.cumsum(np.concatenate(self.piece_cnt))]) if n_seg else np.zeros(1, np.int64)
+        self.n_pieces = int(self.piece_off[-1])
+        if self.n_pieces >= 1 << 31:
+            raise ValueError(f"{who}: {self.n_pieces} pieces exceed the item table's 32-bit rows")
+        self.side_frames = sorted(int(f) for f in jpegs.fallback)
+        self.flagged = []
+        self.pieces = self.table_sets = self.jstream = self.side = self.side_host = None
+        self.set_window(window)
+
+    def set_window(self, window):
+        """Before `upload`: keep the window (top, left, wh, ww) of the side frames only (None: whole frames), and hold the
+        resident bytes against the budget with side frames of that size."""
+        H, W = self.H, self.W
+        if window is not None:
+            top, left, wh, ww = (int(x) for x in window)
+            if min(wh, ww) < 1 or top < 0 or left < 0 or top + wh > H or left + ww > W:
+                raise ValueError(f"{self.who}: the window {wh}x{ww} at ({top}, {left}) is empty or leaves the {H}x{W} frames")
+            window = (top, left, wh, ww)
+        self.window = window
+        self.side_shape = (3, H, W) if window is None else (3, window[2], window[3])
+        self.fb = int(np.prod(self.side_shape))
+        self.check(len(self.side_frames))
+
+    def resident(self, n_side):
+        from . import jpegdev
+        return self.total + self.n_seg * 4 * jpegdev.SEG_COLS + self.n_pieces * jpegdev.PIECE_BYTES + \
+            self.jpegs.n_sets * jpegdev.TABLE_SET_BYTES + n_side * self.fb
+
+    def check(self, n_side):
+        if self.resident(n_side) > self.max_resident_bytes:
+            raise ValueError(f"{self.who}: the set needs {self.resident(n_side)} bytes on the device ({self.total} of entropy "
+                             f"streams, {n_side} frames kept decoded), more than max_resident_bytes={self.max_resident_bytes}")
+
+    def upload(self, stream, dev, chunk_bytes):
+        import torch
+        from . import feeder, jpegdev, ops
+        jpegs, shards, base, seg_lo, n_seg = self.jpegs, self.shards, self.base, self.seg_lo, self.n_seg
+        W, H, samp, split, piece_off, n_pieces = self.W, self.H, self.samp, self.split, self.piece_off, self.n_pieces
+        n_frames, names, side, flagged = jpegs.n_frames, jpegs.names, self.side_frames, []
+        if n_seg:
+            # the streams, shard by shard, into one buffer; every table in one copy from a page-locked block
+            self.jstream = torch.zeros(self.total, dtype=torch.uint8, device=dev)
+            keep = []
+            for s, b in zip(shards, base):
+                if not s.packed.n_segments:
+                    continue
+                src = s.packed.stream if isinstance(s.packed.stream, torch.Tensor) else torch.from_numpy(s.packed.stream_np)
+                for lo in range(0, src.numel(), int(chunk_bytes)):
+                    hi = min(lo + int(chunk_bytes), src.numel())
+                    self.jstream[b + lo:b + hi].copy_(src[lo:hi], non_blocking=True)
+                keep.append(src)
+            segs = np.concatenate([s.packed.segments for s in shards if s.packed.n_segments])
+            waves = [s.packed.waves() for s in shards]
+            parts = [segs.reshape(-1).view(np.uint8), piece_off.astype(np.int32).view(np.uint8),
+                     jpegs.table_sets.reshape(-1)] + [np.ascontiguousarray(w).reshape(-1).view(np.uint8) for w in waves]
+            offs, size = [], 0
+            for a in parts:
+                offs.append(size)
+                size += (a.size + 15) & ~15
+            host = torch.zeros(size, dtype=torch.uint8).pin_memory()
+            hv = host.numpy()
+            for a, o in zip(parts, offs):
+                hv[o:o + a.size] = a
+            meta = torch.empty(size, dtype=torch.uint8, device=dev)
+            meta.copy_(host, non_blocking=True)
+
+            def view(i, dtype, shape):
+                return meta[offs[i]:offs[i] + parts[i].size].view(dtype).view(*shape)
+            d_segs = view(0, torch.int32, (n_seg, jpegdev.SEG_COLS))
+            d_off = view(1, torch.int32, (n_seg + 1,))
+            self.table_sets = view(2, torch.uint8, (jpegs.n_sets, jpegdev.TABLE_SET_BYTES))
+            self.pieces = torch.zeros((n_pieces, jpegdev.PIECE_BYTES), dtype=torch.uint8, device=dev)
+            status = torch.zeros(n_seg, dtype=torch.int32, device=dev)
+            for i, (s, b, s0) in enumerate(zip(shards, base, seg_lo)):
+                n = s.packed.n_segments
+                if n:
+                    ops.jpeg_entropy_index(self.jstream, b, d_segs[s0:s0 + n], view(3 + i, torch.int32, (waves[i].shape[0], 2)),
+                                           self.table_sets, W, H, samp, split, d_off[s0:s0 + n + 1], s0, self.pieces,
+                                           status[s0:s0 + n])
+            h_status = torch.empty(n_seg, dtype=torch.int32).pin_memory()
+            h_status.copy_(status, non_blocking=True)
+            stream.synchronize()                          # the one host synchronisation of construction
+            del keep, host
+            bad = h_status.numpy() != 0
+            for s, s0 in zip(shards, seg_lo):
+                n = s.packed.n_segments
+                if n and bad[s0:s0 + n].any():
+                    flagged += [int(f) for f in np.unique(s.frames[s.packed.segments[bad[s0:s0 + n], 0]])]
+            if flagged:
+                side = sorted(set(side) | set(flagged))
+                self.check(len(side))
+        self.side_frames, self.flagged = side, flagged
+        # per frame of the set: table set, side row, piece rows; per piece row: its MCUs
+        self.frame_set = jpegs.frame_set.copy()
+        self.side_row = np.full(n_frames, -1, np.int32)
+        self.side_row[side] = np.arange(len(side), dtype=np.int32)
+        self.frame_set[side] = -1
+        self.piece_lo = np.zeros(n_frames, np.int64)
+        self.piece_n = np.zeros(n_frames, np.int64)
+        mcu = []
+        for s, s0, cnt in zip(shards, seg_lo, self.piece_cnt):
+            n = s.packed.n_segments
+            if not n:
+                continue
+            fr = s.frames[s.packed.segments[:, 0]]
+            lo = np.full(n_frames, np.iinfo(np.int64).max, np.int64)
+            np.minimum.at(lo, fr, piece_off[s0:s0 + n])
+            np.add.at(self.piece_n, fr, cnt)
+            seen = np.unique(fr)
+            self.piece_lo[seen] = lo[seen]
+            mcu.append(jpegdev.piece_ranges(s.packed.segments, split))
+        self.piece_mcu = np.concatenate(mcu) if mcu else np.zeros((0, 2), np.int64)
+        if side:
+            shape = self.side_shape
+            h_side = torch.empty((len(side),) + shape, dtype=torch.uint8).pin_memory()
+            for r, f in enumerate(side):
+                fr = feeder.read_frame(names[f]) if not (f == 0 and self.fr0 is not None) else self.fr0
+                if tuple(fr.shape) != (3, H, W):
+                    raise ValueError(f"frame {names[f]}: {tuple(fr.shape)} does not fit the set's {(3, H, W)}")
+                if self.window is not None:
+                    top, left, wh, ww = self.window
+                    fr = fr[:, top:top + wh, left:left + ww]
+                h_side[r].copy_(fr)
+            self.side = torch.empty((len(side),) + shape, dtype=torch.uint8, device=dev)
+            self.side.copy_(h_side, non_blocking=True)
+            self.side_host = h_side
+
+    def stats(self):
+        n_frames, n_side = self.jpegs.n_frames, len(self.side_frames)
+        return dict(frames=n_frames, device_frames=n_frames - n_side, fallback_frames=n_side,
+                    index_flagged=sorted(self.flagged), segments=self.n_seg, pieces=self.n_pieces, shards=len(self.shards),
+                    table_sets=self.jpegs.n_sets, stream_bytes=self.total, resident_bytes=self.resident(n_side),
+                    decoded_bytes=n_frames * 3 * self.H * self.W)
 
 
 class _SlotMix:
@@ -586,7 +791,7 @@ class ResidentJpegClips(_ClipLoader):
                  max_resident_bytes=16 << 30, device="cuda", depth=3, chunk_bytes=64 << 20, split_mcus=None,
                  max_coeff_bytes=512 << 20):
         import torch
-        from . import feeder, jpegdev, ops
+        from . import ops
         from .streams import new_stream
         if radi_displacement < 0:
             raise ValueError("radi_displacement must not be negative")
@@ -595,132 +800,21 @@ class ResidentJpegClips(_ClipLoader):
         for v, n in zip(videos, jpegs.video_len):
             if int(v["num_frames"]) != int(n):
                 raise ValueError(f"ResidentJpegClips: video {v['video']} has {int(v['num_frames'])} frames, the packed set {int(n)}")
-        n_frames, names = jpegs.n_frames, jpegs.names
-        if jpegs.width:
-            W, H, samp = jpegs.width, jpegs.height, jpegs.samp
-        else:                                               # nothing for the device: the geometry comes from Pillow
-            fr0 = feeder.read_frame(names[0])
-            H, W, samp = int(fr0.shape[1]), int(fr0.shape[2]), 0
-        geom = jpegdev.geometry(W, H, samp)
-        split = int(split_mcus) if split_mcus is not None else geom.mcus_x
-        if split < 1:
-            raise ValueError("split_mcus must be positive")
-        fb = 3 * H * W
-        shards = [s for s in jpegs.shards]
-        seg_lo, piece_cnt, base, total = [], [], [], 0
-        n_seg = 0
-        for s in shards:
-            seg_lo.append(n_seg)
-            n_seg += s.packed.n_segments
-            piece_cnt.append(jpegdev.piece_counts(s.packed.segments, split) if s.packed.n_segments else np.zeros(0, np.int64))
-            base.append(total)
-            total += (int(s.packed.stream_np.size) + 15) & ~15 if s.packed.n_segments else 0
-        piece_off = np.concatenate([[0], np.cumsum(np.concatenate(piece_cnt))]) if n_seg else np.zeros(1, np.int64)
-        n_pieces = int(piece_off[-1])
-        if n_pieces >= 1 << 31:
-            raise ValueError(f"ResidentJpegClips: {n_pieces} pieces exceed the item table's 32-bit rows")
-        side = sorted(int(f) for f in jpegs.fallback)
-
-        def resident(n_side):
-            return total + n_seg * 4 * jpegdev.SEG_COLS + n_pieces * jpegdev.PIECE_BYTES + \
-                jpegs.n_sets * jpegdev.TABLE_SET_BYTES + n_side * fb
-
-        def check(n_side):
-            if resident(n_side) > max_resident_bytes:
-                raise ValueError(f"ResidentJpegClips: the set needs {resident(n_side)} bytes on the device ({total} of entropy "
-                                 f"streams, {n_side} frames kept decoded), more than max_resident_bytes={max_resident_bytes}")
-        check(len(side))
+        rs = _ResidentStreams("ResidentJpegClips", jpegs, split_mcus, max_resident_bytes)
+        n_frames, n_seg, H, W, samp = jpegs.n_frames, rs.n_seg, rs.H, rs.W, rs.samp
         self._init_clips(videos, [int(n) for n in jpegs.video_len], classes, clip_len, stride, overlap, radi_displacement, mixup,
                          dataset_len, batch_size, seed, pad_len, require_events, drop_last, device, depth)
-        self.shape, self.samp, self.split_mcus = (3, H, W), samp, split
+        self.shape, self.samp, self.split_mcus = (3, H, W), samp, rs.split
         dev = torch.device(device)
         self.stream = new_stream(device)
         self.stream.wait_stream(torch.cuda.current_stream(device))
-        flagged = []
         with torch.cuda.stream(self.stream):
             self._ev = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device)
                              for a in (self.table.ev_off, self.table.ev_frame, self.table.ev_class))
-            self.pieces = self.table_sets = self.jstream = None
-            if n_seg:
-                # the streams, shard by shard, into one buffer; every table in one copy from a page-locked block
-                self.jstream = torch.zeros(total, dtype=torch.uint8, device=dev)
-                keep = []
-                for s, b in zip(shards, base):
-                    if not s.packed.n_segments:
-                        continue
-                    src = s.packed.stream if isinstance(s.packed.stream, torch.Tensor) else torch.from_numpy(s.packed.stream_np)
-                    for lo in range(0, src.numel(), int(chunk_bytes)):
-                        hi = min(lo + int(chunk_bytes), src.numel())
-                        self.jstream[b + lo:b + hi].copy_(src[lo:hi], non_blocking=True)
-                    keep.append(src)
-                segs = np.concatenate([s.packed.segments for s in shards if s.packed.n_segments])
-                waves = [s.packed.waves() for s in shards]
-                parts = [segs.reshape(-1).view(np.uint8), piece_off.astype(np.int32).view(np.uint8),
-                         jpegs.table_sets.reshape(-1)] + [np.ascontiguousarray(w).reshape(-1).view(np.uint8) for w in waves]
-                offs, size = [], 0
-                for a in parts:
-                    offs.append(size)
-                    size += (a.size + 15) & ~15
-                host = torch.zeros(size, dtype=torch.uint8).pin_memory()
-                hv = host.numpy()
-                for a, o in zip(parts, offs):
-                    hv[o:o + a.size] = a
-                meta = torch.empty(size, dtype=torch.uint8, device=dev)
-                meta.copy_(host, non_blocking=True)
-
-                def view(i, dtype, shape):
-                    return meta[offs[i]:offs[i] + parts[i].size].view(dtype).view(*shape)
-                d_segs = view(0, torch.int32, (n_seg, jpegdev.SEG_COLS))
-                d_off = view(1, torch.int32, (n_seg + 1,))
-                self.table_sets = view(2, torch.uint8, (jpegs.n_sets, jpegdev.TABLE_SET_BYTES))
-                self.pieces = torch.zeros((n_pieces, jpegdev.PIECE_BYTES), dtype=torch.uint8, device=dev)
-                status = torch.zeros(n_seg, dtype=torch.int32, device=dev)
-                for i, (s, b, s0) in enumerate(zip(shards, base, seg_lo)):
-                    n = s.packed.n_segments
-                    if n:
-                        ops.jpeg_entropy_index(self.jstream, b, d_segs[s0:s0 + n], view(3 + i, torch.int32, (waves[i].shape[0], 2)),
-                                               self.table_sets, W, H, samp, split, d_off[s0:s0 + n + 1], s0, self.pieces,
-                                               status[s0:s0 + n])
-                h_status = torch.empty(n_seg, dtype=torch.int32).pin_memory()
-                h_status.copy_(status, non_blocking=True)
-                self.stream.synchronize()                     # the one host synchronisation of construction
-                del keep, host
-                bad = h_status.numpy() != 0
-                for s, s0 in zip(shards, seg_lo):
-                    n = s.packed.n_segments
-                    if n and bad[s0:s0 + n].any():
-                        flagged += [int(f) for f in np.unique(s.frames[s.packed.segments[bad[s0:s0 + n], 0]])]
-                if flagged:
-                    side = sorted(set(side) | set(flagged))
-                    check(len(side))
-            # per frame of the set: table set, side row, piece rows
-            self._frame_set = jpegs.frame_set.copy()
-            self._side_row = np.full(n_frames, -1, np.int32)
-            self._side_row[side] = np.arange(len(side), dtype=np.int32)
-            self._frame_set[side] = -1
-            self._piece_lo = np.zeros(n_frames, np.int64)
-            self._piece_n = np.zeros(n_frames, np.int64)
-            for s, s0, cnt in zip(shards, seg_lo, piece_cnt):
-                n = s.packed.n_segments
-                if not n:
-                    continue
-                fr = s.frames[s.packed.segments[:, 0]]
-                lo = np.full(n_frames, np.iinfo(np.int64).max, np.int64)
-                np.minimum.at(lo, fr, piece_off[s0:s0 + n])
-                np.add.at(self._piece_n, fr, cnt)
-                seen = np.unique(fr)
-                self._piece_lo[seen] = lo[seen]
-            self.side = None
-            if side:
-                h_side = torch.empty((len(side), 3, H, W), dtype=torch.uint8).pin_memory()
-                for r, f in enumerate(side):
-                    fr = feeder.read_frame(names[f]) if not (f == 0 and not jpegs.width) else fr0
-                    if tuple(fr.shape) != (3, H, W):
-                        raise ValueError(f"frame {names[f]}: {tuple(fr.shape)} does not fit the set's {(3, H, W)}")
-                    h_side[r].copy_(fr)
-                self.side = torch.empty((len(side), 3, H, W), dtype=torch.uint8, device=dev)
-                self.side.copy_(h_side, non_blocking=True)
-                self._side_host = h_side
+            rs.upload(self.stream, dev, chunk_bytes)
+            self.pieces, self.table_sets, self.jstream, self.side = rs.pieces, rs.table_sets, rs.jstream, rs.side
+            self._frame_set, self._side_row, self._piece_lo, self._piece_n = rs.frame_set, rs.side_row, rs.piece_lo, rs.piece_n
+            self._side_host = rs.side_host
             # the ring: per entry one page-locked block and its device twin (clip rows, then the batch tables), the uint8
             # slot of both operands and the labels; one coefficient buffer, since every batch decodes on the one stream
             B, T, nops = int(batch_size), self.clip_len, 2 if self.mixup else 1
@@ -749,10 +843,7 @@ class ResidentJpegClips(_ClipLoader):
         self._pass = 0
         self.item_events = None                 # set to a list: (start, end) events around every jpeg_entropy_items launch
         self._init_ring()
-        self.stats = dict(frames=n_frames, device_frames=n_frames - len(side), fallback_frames=len(side),
-                          index_flagged=sorted(flagged), segments=n_seg, pieces=n_pieces, shards=len(shards),
-                          table_sets=jpegs.n_sets, stream_bytes=total, resident_bytes=resident(len(side)),
-                          decoded_bytes=n_frames * fb)
+        self.stats = rs.stats()
 
     def _views(self, block, B, np_side):
         """(rows int64 (4 * operands, B), slot_set, fill, items (cap, 2), waves (cap, 2)) of a ring block"""

@@ -19,6 +19,9 @@
     python tools/bench_video.py --ring [--frames 2030]                  predict_video resident against predict_video(
                                                                         stream_frames=True) at a quarter of the video's bytes,
                                                                         one JSON line, also written to profiles/video_ring.json
+    python tools/bench_video.py --resident-jpeg [--frames 2030]         validation mAP fed by host decode, by load_video_device,
+                                                                        by ResidentJpegVideos and by its crop=224, one JSON
+                                                                        line, also written to profiles/video_resident_jpeg.json
 
 Routes (RegNetY-200MF, T = 100, 224 x 224, bf16; 3/4 overlap like the evaluation datasets):
   A  the clip route: `evalutil.stitch_predictions` over host-resident PINNED uint8 clip batches of the video, at loader
@@ -742,6 +745,142 @@ def decode_device(a):
     return 0
 
 
+def resident_jpeg(a):
+    """A validation pass (`evalutil.map_videos`) over the tool's synthetic set -- `--map-videos` short videos of the diving
+    split plus one of `--frames` frames, 224 x 398 4:2:0 JPEG files, the model cropping the centre 224 x 224 -- fed four ways,
+    in one process, the routes alternating: (a) decode="host" with the tool's thread pool, (b) decode="device"
+    (`feeder.load_video_device`: files read, parsed, packed and uploaded every pass), (c) `evalutil.ResidentJpegVideos`, (d) the
+    same with crop=224 (windowed pixel pass, cropped frames).  A warm-up pass per route (reported as first_pass), then
+    `--repeats` timed passes (at least three), every pass listed.  Construction of (c) and (d) is timed apart.  Then the
+    entropy and the pixel kernel alone on the long video (HIP events), window against full, and the byte figures.  A route
+    is called faster than another only when it is faster in every timed pass; otherwise the ranges are given."""
+    import tempfile
+    from types import SimpleNamespace
+    from PIL import Image
+    from tdeed_amd.model import TDEEDModel
+    from tdeed_amd import trainclips as TC
+    FH, FW = 224, 398
+    repeats = max(int(a.repeats), 3)
+    m = TDEEDModel(device="cuda", args=SimpleNamespace(modality="rgb", temporal_arch="ed_sgp_mixer", pretrain=None, **CFG))
+    m.load({k: torch.from_numpy(v) for k, v in synth.make_state(state_layout.model_state_shapes(CFG), 0).items()})
+    K = CFG["num_classes"]
+    classes = {f"c{k}": k for k in range(1, K + 1)}
+    suppress = (("nms", 1, 0.10), ("snms", 3, 0.01))
+    tols = [0, 1, 2, 4]
+    lengths = group_lengths("diving")[:a.map_videos] + [a.frames]
+    n_frames = int(sum(lengths))
+    budget = 16 << 30
+    kw = dict(batch_size=8, group_videos=min(a.group_videos, 8))          # groups of 8: the next group decodes meanwhile
+    with tempfile.TemporaryDirectory() as tmp:
+        # 16 distinct pictures: a colour ramp, a wave and low noise, quality 90, 4:2:0
+        yy, xx = np.mgrid[0:FH, 0:FW].astype(np.float64)
+        pics = []
+        for k in range(16):
+            base = np.stack([30 + 180 * xx / (FW - 1), 40 + 170 * yy / (FH - 1), 128 + 90 * np.sin(0.11 * xx + k) * np.cos(0.07 * yy)], -1)
+            noise = synth.uint8_clip(700 + k, (FH, FW, 3)).astype(np.float64) / 10.0 - 12.75
+            pics.append(Image.fromarray(np.clip(base + noise, 0, 255).astype(np.uint8)))
+        videos, file_bytes = [], 0
+        for v, L in enumerate(lengths):
+            d = os.path.join(tmp, f"v{v:03d}")
+            os.makedirs(d)
+            for i in range(L):
+                pics[(i + 3 * v) % 16].save(os.path.join(d, f"frame{i}.jpg"), "JPEG", quality=90, subsampling=2)
+                file_bytes += os.path.getsize(os.path.join(d, f"frame{i}.jpg"))
+            videos.append(dict(video=f"v{v:03d}", num_frames=L, fps=25.0))
+        truth = [{"video": v["video"], "events": [{"label": f"c{1 + (f // 20) % K}", "frame": f} for f in range(7, v["num_frames"], 20)]}
+                 for v in videos]
+        tpool = feeder.DecodePool(a.threads)
+        try:
+            files = [(v["video"], v["num_frames"], v["fps"],
+                      dict(frame_dir=tmp, dataset="soccernetball", video_name=v["video"], num_frames=v["num_frames"], pool=tpool))
+                     for v in videos]
+            built, made = {}, {}
+            for key, crop in (("c_resident_jpeg", None), ("d_resident_jpeg_crop", 224)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                jpegs = TC.load_resident_jpegs(tmp, "soccernetball", videos, pool=tpool)
+                t1 = time.perf_counter()
+                made[key] = E.ResidentJpegVideos(videos, jpegs, crop=crop, max_resident_bytes=budget)
+                torch.cuda.synchronize()
+                built[key] = dict(read_parse_pack_ms=round((t1 - t0) * 1e3, 1), upload_index_ms=round((time.perf_counter() - t1) * 1e3, 1))
+                del jpegs
+            routes = dict(
+                a_decode_host=lambda: E.map_videos(m, files, classes, truth, suppress, tols, decode="host", **kw),
+                b_decode_device=lambda: E.map_videos(m, files, classes, truth, suppress, tols, decode="device", **kw),
+                c_resident_jpeg=lambda: E.map_videos(m, made["c_resident_jpeg"].sources(), classes, truth, suppress, tols, **kw),
+                d_resident_jpeg_crop=lambda: E.map_videos(m, made["d_resident_jpeg_crop"].sources(), classes, truth, suppress, tols, **kw))
+            res, first, syncs = {}, {}, {}
+            for k, fn in routes.items():                                    # warm-up: plans, graphs, table caches
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res[k] = fn()
+                torch.cuda.synchronize()
+                first[k] = round((time.perf_counter() - t0) * 1e3, 1)
+                syncs[k] = m.last_video_stats.get("host_syncs")
+            times = {k: [] for k in routes}
+            for _ in range(repeats):
+                for k, fn in routes.items():                                # alternating
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    times[k].append(time.perf_counter() - t0)
+            # the kernels alone, on the long video
+            kernels = {}
+            for key, rv in made.items():
+                rv._kernel_events = []
+                for _ in range(repeats + 1):
+                    rv.frames(len(lengths) - 1)
+                ev, rv._kernel_events = rv._kernel_events, None
+                per = len(ev) // (repeats + 1)
+                ent = [sum(e0.elapsed_time(e1) for e0, e1, _ in ev[i * per:(i + 1) * per]) for i in range(1, repeats + 1)]
+                pix = [sum(e1.elapsed_time(e2) for _, e1, e2 in ev[i * per:(i + 1) * per]) for i in range(1, repeats + 1)]
+                kernels[key] = dict(frames=lengths[-1], chunks=per, items=int(rv.video_tables(len(lengths) - 1).items.shape[0]),
+                                    entropy_items_ms=[round(x, 3) for x in ent], pixels_ms=[round(x, 3) for x in pix])
+            stats = {k: {f: (list(x) if isinstance(x, tuple) else x) for f, x in rv.stats.items() if f != "index_flagged"}
+                     for k, rv in made.items()}
+        finally:
+            tpool.close()
+    same = {k: bool(res[k] == res["a_decode_host"]) for k in routes}
+    rt = {}
+    for k, v in times.items():
+        tt = np.asarray(v) * 1e3
+        rt[k] = dict(first_pass_ms=first[k], passes_ms=[round(float(x), 1) for x in tt], ms_min=round(float(tt.min()), 1),
+                     ms_max=round(float(tt.max()), 1), ms_median=round(float(np.median(tt)), 1),
+                     frames_per_s_median=round(n_frames / float(np.median(tt)) * 1e3, 1), host_syncs_of_the_consumer=syncs[k])
+    verdicts = {}
+    for new, old in (("c_resident_jpeg", "a_decode_host"), ("c_resident_jpeg", "b_decode_device"),
+                     ("d_resident_jpeg_crop", "a_decode_host"), ("d_resident_jpeg_crop", "b_decode_device"),
+                     ("d_resident_jpeg_crop", "c_resident_jpeg")):
+        x, y = np.asarray(times[new]), np.asarray(times[old])
+        every = bool(np.all(x < y))
+        verdicts[f"{new}_vs_{old}"] = dict(
+            faster_in_every_timed_pass=every, ratio_of_medians_old_over_new=round(float(np.median(y) / np.median(x)), 3),
+            note=("faster in every timed pass" if every else "slower in every timed pass" if bool(np.all(x > y)) else
+                  "the ranges overlap or the order changes between passes: no claim"))
+    st_c, st_d = stats["c_resident_jpeg"], stats["d_resident_jpeg_crop"]
+    full_b, win_b = 3 * FH * FW, 3 * 224 * 224
+    comp = st_c["resident_bytes"] / st_c["frames"]
+    rec = dict(kind="video_resident_jpeg", device=torch.cuda.get_device_name(0), measured_on_gpu=True, cfg=CFG,
+               videos=len(lengths), frames=n_frames, longest_video=lengths[-1], frame="224x398 4:2:0 quality 90, 16 distinct pictures "
+               "(ramp + wave + low noise)", jpeg_file_bytes_per_frame=round(file_bytes / n_frames, 1), threads=tpool.threads,
+               group_videos=kw["group_videos"], batch_size=8, repeats=repeats, routes=rt, construction=built,
+               maps_equal_route_a=same, verdicts=verdicts, kernels_alone_long_video=kernels,
+               bytes_per_frame=dict(resident_compressed=round(comp, 1), decoded_full=full_b, decoded_window=win_b,
+                                    window_over_full=round(win_b / full_b, 4)),
+               frames_that_fit_max_resident_bytes=dict(max_resident_bytes=budget, decoded_full=budget // full_b,
+                                                       decoded_window=budget // win_b, compressed=int(budget // comp)),
+               stats=stats)
+    out = os.path.join(ROOT, "profiles", "video_resident_jpeg.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rec))
+    assert all(same.values()), f"the routes' mAP tables differ: {same}"
+    return 0
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=None, help="default 2030, with --spot 5625")
@@ -762,8 +901,10 @@ if __name__ == "__main__":
     ap.add_argument("--decode-device", action="store_true", help="JPEG decode: two host routes against load_video_device")
     ap.add_argument("--decode-frames", type=int, default=400)
     ap.add_argument("--threads", type=int, default=8)
+    ap.add_argument("--resident-jpeg", action="store_true",
+                    help="map_videos fed by host decode, device decode and ResidentJpegVideos (with and without crop)")
     a = ap.parse_args()
     if a.frames is None:
         a.frames = 5625 if a.spot else 2030
-    sys.exit(ring(a) if a.ring else map_bench(a) if a.map else decode_device(a) if a.decode_device else decode(a) if a.decode else gather_only(a) if a.gather_only else reuse(a) if a.reuse else group(a) if a.group
+    sys.exit(resident_jpeg(a) if a.resident_jpeg else ring(a) if a.ring else map_bench(a) if a.map else decode_device(a) if a.decode_device else decode(a) if a.decode else gather_only(a) if a.gather_only else reuse(a) if a.reuse else group(a) if a.group
              else spot(a) if a.spot else bench(a))
