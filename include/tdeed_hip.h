@@ -939,6 +939,10 @@ long tdeed_jpeg_pixels_lds_bytes(int W, int H, int sampling, int windowed, int t
  *   [n_waves][2] = (first item, count <= 64), the items of a wave of one table set.  Slots slot_lo .. slot_lo + n_slots - 1
  *   decode into coeff (zero-filled by the caller).  An item or row that points outside any buffer counts as status 7 and
  *   touches nothing; *err (uint32, on the device) gets bit `status` set for every non-zero status met.
+ * tdeed_jpeg_entropy_items_reloc: the same decode where a piece's bytes are a staged copy.  reloc holds n_reloc 24-byte
+ *   rows (JcReloc: int64 delta, lo, hi), indexed by the item's slot: the piece's bytes start at stream + pos - delta and
+ *   must lie wholly in [lo, hi) of the stream, lo >= 0, hi <= stream_bytes; a piece that does not, or a slot >= n_reloc,
+ *   counts as status 7 and touches nothing.  delta = 0 with the window (0, stream_bytes) is tdeed_jpeg_entropy_items.
  * tdeed_jpeg_slot_fill: rows of out uint8 [n_rows][frame_bytes] that no decode fills: fill[row] = -2 leaves the row, -1
  *   zeroes it, r >= 0 copies row r of side uint8 [side_rows][frame_bytes] (r >= side_rows stores nothing). */
 int tdeed_jpeg_entropy_index(const uint8_t* stream, long stream_bytes, long base, const int* segments, int n_segments,
@@ -948,6 +952,10 @@ int tdeed_jpeg_entropy_index(const uint8_t* stream, long stream_bytes, long base
 int tdeed_jpeg_entropy_items(const uint8_t* stream, long stream_bytes, const void* pieces, int n_pieces, const int* items,
                              int n_items, const int* waves, int n_waves, const uint8_t* table_sets, int n_sets, int W, int H,
                              int sampling, int slot_lo, int n_slots, int16_t* coeff, unsigned* err, void* hip_stream);
+int tdeed_jpeg_entropy_items_reloc(const uint8_t* stream, long stream_bytes, const void* pieces, int n_pieces,
+                                   const int* items, int n_items, const int* waves, int n_waves, const uint8_t* table_sets,
+                                   int n_sets, int W, int H, int sampling, int slot_lo, int n_slots, const void* reloc,
+                                   int n_reloc, int16_t* coeff, unsigned* err, void* hip_stream);
 int tdeed_jpeg_slot_fill(const uint8_t* side, long side_rows, long frame_bytes, const int* fill, int n_rows, uint8_t* out,
                          void* hip_stream);
 

@@ -216,6 +216,8 @@ _SIGS = {
                                   c_int, P, P], c_int),
     "tdeed_jpeg_entropy_items": ([P, c_long, P, c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P,
                                   P], c_int),
+    "tdeed_jpeg_entropy_items_reloc": ([P, c_long, P, c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P,
+                                        c_int, P, P, P], c_int),
     "tdeed_jpeg_slot_fill": ([P, c_long, c_long, P, c_int, P, P], c_int),
     "tdeed_comm_unique_id": ([P], c_int),
     "tdeed_comm_init": ([POINTER(c_void_p), P, c_int, c_int], c_int),

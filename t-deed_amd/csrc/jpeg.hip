@@ -145,13 +145,18 @@ __global__ __launch_bounds__(64) void jpeg_entropy_index_kernel(const uint8_t* _
 // table set (trainclips.batch_tables).  Lane i decodes its piece into slot s's coefficient range, s in [slot_lo, slot_lo +
 // n_slots).  An item or a piece row that points outside any buffer, or whose set is not the wavefront's, counts as
 // JC_ERR_TABLE and touches nothing.  No status leaves the device per item: bit `code` of *err is set for every code met.
+// RELOC (tdeed_jpeg_entropy_items_reloc): the same body, but a piece's bytes are a staged copy: reloc[s], s the item's
+// slot, s < n_reloc, says how far below JcPiece.pos they lie in `stream` and which window of it the slot may read
+// (jc_piece_reloc_ok); a piece that leaves its window, or a slot without a row, counts as JC_ERR_TABLE like the others.
+template <bool RELOC>
 __global__ __launch_bounds__(64) void jpeg_entropy_items_kernel(const uint8_t* __restrict__ stream, long stream_bytes,
                                                                 const JcPiece* __restrict__ pieces, int n_pieces,
                                                                 const int* __restrict__ items, int n_items,
                                                                 const int* __restrict__ waves, const JcTableSet* __restrict__ sets,
                                                                 int n_sets, int samp, int mcus_x, int mcus_y, int slot_lo, int n_slots,
                                                                 long frame_coefs, int16_t* __restrict__ coef,
-                                                                unsigned* __restrict__ err) {
+                                                                unsigned* __restrict__ err, const JcReloc* __restrict__ reloc,
+                                                                int n_reloc) {
   __shared__ __attribute__((aligned(16))) JcTableSet ts;
   const int lane = threadIdx.x;
   int first = waves[2 * blockIdx.x], count = waves[2 * blockIdx.x + 1];
@@ -173,13 +178,23 @@ __global__ __launch_bounds__(64) void jpeg_entropy_items_kernel(const uint8_t* _
   __syncthreads();
   if (lane >= count) return;
   const int pi = items[2 * (first + lane)];
-  const long f = (long)items[2 * (first + lane) + 1] - slot_lo;
+  const int slot = items[2 * (first + lane) + 1];
+  const long f = (long)slot - slot_lo;
   int st = JC_ERR_TABLE;
-  if (pi >= 0 && pi < n_pieces && f >= 0 && f < n_slots) {
+  if (pi >= 0 && pi < n_pieces && f >= 0 && f < n_slots && (!RELOC || slot < n_reloc)) {
     const JcPiece p = pieces[pi];
-    if (jc_piece_ok(p, stream_bytes, n_sets, mcus_x * mcus_y) && p.set == set) {
+    long at = p.pos;
+    bool ok;
+    if (RELOC) {
+      const JcReloc r = reloc[slot];
+      ok = jc_piece_reloc_ok(p, r, stream_bytes, n_sets, mcus_x * mcus_y);
+      at = p.pos - r.delta;
+    } else {
+      ok = jc_piece_ok(p, stream_bytes, n_sets, mcus_x * mcus_y);
+    }
+    if (ok && p.set == set) {
       JcNoRecord rec;
-      st = jc_entropy_run<true>(stream + p.pos, p.left, p.st, p.first_mcu, p.n_mcu, &ts, samp, mcus_x, mcus_y,
+      st = jc_entropy_run<true>(stream + at, p.left, p.st, p.first_mcu, p.n_mcu, &ts, samp, mcus_x, mcus_y,
                                 coef + f * frame_coefs, 1, rec);
     }
   }
@@ -227,10 +242,33 @@ extern "C" int tdeed_jpeg_entropy_items(const uint8_t* stream, long stream_bytes
   TD_CHECK((((uintptr_t)items | (uintptr_t)err) & 3) == 0 && (((uintptr_t)pieces) & 7) == 0 && (((uintptr_t)coeff) & 15) == 0,
            "jpeg_entropy_items: coefficients must be 16-byte aligned, the piece table 8-byte, the tables 4-byte");
   const JcGeom g = jc_geom(W, H, sampling);
-  hipLaunchKernelGGL(jpeg_entropy_items_kernel, dim3(n_waves), dim3(64), 0, (hipStream_t)hip_stream, stream, stream_bytes,
+  hipLaunchKernelGGL(jpeg_entropy_items_kernel<false>, dim3(n_waves), dim3(64), 0, (hipStream_t)hip_stream, stream, stream_bytes,
                      (const JcPiece*)pieces, n_pieces, items, n_items, waves, (const JcTableSet*)table_sets, n_sets, sampling,
-                     g.mcus_x, g.mcus_y, slot_lo, n_slots, (long)g.frame_blocks * 64, coeff, err);
+                     g.mcus_x, g.mcus_y, slot_lo, n_slots, (long)g.frame_blocks * 64, coeff, err, (const JcReloc*)nullptr, 0);
   TD_LAUNCH_CHECK("jpeg_entropy_items");
+  return TDEED_OK;
+}
+
+// tdeed_jpeg_entropy_items over staged copies: reloc holds n_reloc rows of (int64 delta, lo, hi), indexed by the item's slot
+extern "C" int tdeed_jpeg_entropy_items_reloc(const uint8_t* stream, long stream_bytes, const void* pieces, int n_pieces,
+                                              const int* items, int n_items, const int* waves, int n_waves,
+                                              const uint8_t* table_sets, int n_sets, int W, int H, int sampling, int slot_lo,
+                                              int n_slots, const void* reloc, int n_reloc, int16_t* coeff, unsigned* err,
+                                              void* hip_stream) {
+  const int rc =
+      jpeg_resident_checks("jpeg_entropy_items_reloc", stream, stream_bytes, waves, n_waves, table_sets, n_sets, W, H, sampling);
+  if (rc != TDEED_OK) return rc;
+  TD_CHECK(pieces && items && coeff && err && reloc, "jpeg_entropy_items_reloc: null pointer");
+  TD_CHECK(n_pieces > 0 && n_items > 0 && slot_lo >= 0 && n_slots > 0 && n_reloc > 0, "jpeg_entropy_items_reloc: bad sizes");
+  TD_CHECK((((uintptr_t)items | (uintptr_t)err) & 3) == 0 && (((uintptr_t)pieces | (uintptr_t)reloc) & 7) == 0 &&
+               (((uintptr_t)coeff) & 15) == 0,
+           "jpeg_entropy_items_reloc: coefficients must be 16-byte aligned, the piece and relocation tables 8-byte, the tables "
+           "4-byte");
+  const JcGeom g = jc_geom(W, H, sampling);
+  hipLaunchKernelGGL(jpeg_entropy_items_kernel<true>, dim3(n_waves), dim3(64), 0, (hipStream_t)hip_stream, stream, stream_bytes,
+                     (const JcPiece*)pieces, n_pieces, items, n_items, waves, (const JcTableSet*)table_sets, n_sets, sampling,
+                     g.mcus_x, g.mcus_y, slot_lo, n_slots, (long)g.frame_blocks * 64, coeff, err, (const JcReloc*)reloc, n_reloc);
+  TD_LAUNCH_CHECK("jpeg_entropy_items_reloc");
   return TDEED_OK;
 }
 

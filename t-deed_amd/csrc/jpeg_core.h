@@ -1,6 +1,6 @@
 // Baseline JPEG decode arithmetic shared by the device kernels (jpeg.hip) and the host check programs
-// (tools/jpeg_host_check.cpp, tools/jpeg_split_check.cpp): bit reader, Huffman symbol decode, the coefficient decode of a
-// segment or of a piece of one (from a recorded decoder state), the integer "islow"
+// (tools/jpeg_host_check.cpp, tools/jpeg_split_check.cpp, tools/jpeg_stage_check.cpp): bit reader, Huffman symbol decode,
+// the coefficient decode of a segment or of a piece of one (from a recorded decoder state), the integer "islow"
 // IDCT, libjpeg's "fancy" triangle up-sampling taps and the integer YCbCr -> RGB conversion.  Everything is integer
 // arithmetic and reproduces Pillow's Image.open(..).convert("RGB") (libjpeg-turbo) bit for bit on the supported subset
 // (tdeed_amd/jpegdev.py: parse).  No HIP types here: the file also compiles with a plain host C++ compiler.
@@ -250,6 +250,30 @@ JC_HD bool jc_piece_ok(const JcPiece& p, long stream_bytes, int n_sets, int tota
   return p.pos >= 0 && p.left >= 0 && p.pos <= stream_bytes && (long)p.left <= stream_bytes - p.pos && p.set >= 0 &&
          p.set < n_sets && p.first_mcu >= 0 && p.n_mcu > 0 && (long)p.first_mcu + p.n_mcu <= total_mcus && p.st.n >= 0 &&
          p.st.n <= 63 && p.st.pad >= 0 && p.st.pad <= p.st.n && p.st.byte_off >= 0;
+}
+
+// One row of the relocation table of a coefficient slot (trainclips.stage_batch): the pieces decoded into the slot have
+// their bytes at pos - delta of the device buffer -- a staged copy of a byte range of the set; delta = 0 where the stream
+// is resident at its own position -- and may read the window [lo, hi) of that buffer only.
+struct JcReloc {
+  int64_t delta, lo, hi;
+};
+#define JC_RELOC_BYTES 24
+static_assert(sizeof(JcReloc) == JC_RELOC_BYTES, "JcReloc layout (trainclips.py packs it with numpy)");
+
+// false when the piece's bytes [pos - delta, pos - delta + left) do not lie wholly inside the slot's window, or the window
+// not inside the buffer.  pos, lo and hi - left are not negative where they are subtracted, so nothing overflows whatever
+// the row holds: pos - delta >= lo  <=>  delta <= pos - lo, and pos - delta + left <= hi  <=>  delta >= pos - (hi - left).
+JC_HD bool jc_reloc_ok(const JcPiece& p, const JcReloc& r, long stream_bytes) {
+  return p.pos >= 0 && p.left >= 0 && r.lo >= 0 && r.lo <= r.hi && r.hi <= (int64_t)stream_bytes && r.hi - r.lo >= p.left &&
+         r.delta <= p.pos - r.lo && r.delta >= p.pos - (r.hi - p.left);
+}
+
+// jc_piece_ok of a relocated piece: the byte range is held against the slot's window (jc_reloc_ok), the rest as above
+JC_HD bool jc_piece_reloc_ok(const JcPiece& p, const JcReloc& r, long stream_bytes, int n_sets, int total_mcus) {
+  JcPiece q = p;
+  q.pos = 0;                                                   // the absolute range check passes: left <= stream_bytes below
+  return jc_reloc_ok(p, r, stream_bytes) && jc_piece_ok(q, stream_bytes, n_sets, total_mcus);
 }
 
 // the split rule (jpegdev.split_points): MCU m of a segment starts a new piece when first_mcu < m and m % split_mcus == 0

@@ -817,13 +817,21 @@ class ResidentJpegVideos:
     device, as `ResidentJpegClips` counts it.  Not counted: the coefficient buffer (max_coeff_bytes bounds it) and the item
     tables of the videos decoded so far, which are kept on the host and on the device for the next pass: 8 bytes per piece
     plus 8 per frame, about 120 bytes per 224-row 4:2:0 frame against some 20 000 of stream.
+    stream_videos=True: a set whose resident bytes exceed max_resident_bytes is accepted, as `ResidentJpegClips(
+    stream_clips=True)` accepts one: the tables and the streams of the first videos that fit stay resident, the other videos'
+    streams stay in the host shards of `jpegs`, and `frames(i)` of such a video copies its byte ranges into one staging
+    region on the object's stream before the relocating items entry decodes them -- chunk by chunk of the coefficient buffer,
+    whose frames are what the region holds, so a video longer than a chunk is staged in several copies.  A resident video
+    takes the path above untouched; the frames are the all-resident object's bit for bit.  The budget counts the region;
+    too small a budget raises ValueError naming the smallest that would do, a shard larger than the region one naming
+    `shard_bytes`.  `stats` gains resident_videos, streamed_videos, stage_bytes, host_stream_bytes.
     Not offered: the frame ring (`stream_frames=True`) fed by this decode, and `reuse_frames` beyond what the consumers do
     with any device tensor."""
 
     UPLOAD_CHUNK_BYTES = 64 << 20        # the streams are uploaded in copies of this size (`ResidentJpegClips`' default)
 
     def __init__(self, videos, jpegs, crop=None, split_mcus=None, max_resident_bytes=16 << 30, max_coeff_bytes=512 << 20,
-                 device="cuda"):
+                 device="cuda", stream_videos=False):
         import threading
         import torch
         from . import jpegdev, ops
@@ -843,9 +851,9 @@ class ResidentJpegVideos:
             raise ValueError("ResidentJpegVideos: max_coeff_bytes must be positive")
         if jpegs.width:
             self.window = _crop_window(crop, jpegs.height, jpegs.width)      # argument errors before any file is touched
-            rs = _ResidentStreams("ResidentJpegVideos", jpegs, split_mcus, max_resident_bytes, self.window)
+            rs = _ResidentStreams("ResidentJpegVideos", jpegs, split_mcus, max_resident_bytes, self.window, streamed=stream_videos)
         else:                                                   # the geometry comes from Pillow's decode of the first frame
-            rs = _ResidentStreams("ResidentJpegVideos", jpegs, split_mcus, 1 << 62, None)
+            rs = _ResidentStreams("ResidentJpegVideos", jpegs, split_mcus, 1 << 62, None, streamed=stream_videos)
             self.window = _crop_window(crop, rs.H, rs.W)
             rs.max_resident_bytes = max_resident_bytes
             rs.set_window(self.window)                          # the budget, with side frames of the window's size
@@ -857,6 +865,13 @@ class ResidentJpegVideos:
         self.video_first = [int(x) for x in jpegs.video_first]
         self.video_len = [int(x) for x in jpegs.video_len]
         self._mcu_rows = jpegdev.window_blocks(rs.geom, *self.window).mcu_rows if self.window is not None else None
+        self._plan = None
+        if stream_videos:
+            # a streamed video is staged in the frame chunks of the coefficient buffer: the plan's "clips" are those chunks
+            chunk = min(max(self.video_len), 65535, max(1, int(max_coeff_bytes) // (2 * ops.jpeg_frame_coeffs(rs.W, rs.H, rs.samp))))
+            rows = np.asarray([(f, lo, n, v) for v, (f, n) in enumerate(zip(self.video_first, self.video_len))
+                               for lo in range(0, n, chunk)], np.int64).T
+            self._plan = rs.plan_streaming(rows, chunk, 1, 1, 1, 1)
         self.device = dev = torch.device(device)
         self.stream = streams.new_stream(device)
         self.stream.wait_stream(torch.cuda.current_stream(device))
@@ -908,17 +923,29 @@ class ResidentJpegVideos:
             if i not in self._tabs:
                 tb = self.video_tables(i)
                 to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)     # noqa: E731
-                self._tabs[i] = (tb, to(tb.slot_set), to(tb.fill), to(tb.items), to(tb.waves))
-            tb, d_set, d_fill, d_items, d_waves = self._tabs[i]
+                copies, d_reloc = {}, None
+                if self._plan is not None:
+                    # per coefficient chunk its range copies into the one staging region; the relocation rows of the whole
+                    # video in one table (a resident video: no copies, delta 0 everywhere)
+                    from .trainclips import stage_batch
+                    reloc = np.zeros((L, 3), np.int64)
+                    for lo, hi, _, _ in tb.chunks:
+                        row = np.asarray([[self.video_first[i]], [lo], [L], [i]], np.int64)
+                        copies[lo], reloc[lo:hi] = stage_batch(self._plan, rs.ext, row, hi - lo, 1, self._plan.stage_lo)
+                    d_reloc = to(reloc)
+                self._tabs[i] = (tb, to(tb.slot_set), to(tb.fill), to(tb.items), to(tb.waves), copies, d_reloc)
+            tb, d_set, d_fill, d_items, d_waves, copies, d_reloc = self._tabs[i]
             self.stream.wait_stream(torch.cuda.current_stream(self.device))     # `out` may be a block this stream just freed
             with torch.cuda.stream(self.stream):
                 for lo, hi, w_lo, w_hi in tb.chunks:
                     self._coeff[:(hi - lo) * self._fc].zero_()
+                    for k, b_lo, b_hi, d in copies.get(lo, ()):      # a streamed video: behind the last chunk's items launch
+                        rs.jstream[d:d + b_hi - b_lo].copy_(rs.host_streams[k][b_lo:b_hi], non_blocking=True)
                     if self._kernel_events is not None:
                         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
                         ev[0].record(self.stream)
                     ops.jpeg_entropy_items(rs.jstream, rs.pieces, d_items, d_waves[w_lo:w_hi], rs.table_sets, self.W, self.H,
-                                           self.samp, lo, hi - lo, self._coeff, self._err)
+                                           self.samp, lo, hi - lo, self._coeff, self._err, reloc=d_reloc)
                     if self._kernel_events is not None:
                         ev[1].record(self.stream)
                     if self.window is None:

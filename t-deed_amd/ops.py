@@ -1351,11 +1351,17 @@ def jpeg_entropy_index(stream, base, segments, waves, table_sets, W, H, sampling
     return pieces
 
 
-def jpeg_entropy_items(stream, pieces, items, waves, table_sets, W, H, sampling, slot_lo, n_slots, coeff, err):
+RELOC_BYTES = 24          # csrc/jpeg_core.h JcReloc: int64 delta, lo, hi
+
+
+def jpeg_entropy_items(stream, pieces, items, waves, table_sets, W, H, sampling, slot_lo, n_slots, coeff, err, reloc=None):
     """Decode the items listed by `waves` -- items int32 (n_items, 2) rows of (piece row, coefficient slot), waves int32
     (n_waves, 2) rows of (first item, count <= 64), one table set per wave -- into coeff, int16 (>= n_slots *
     jpeg_frame_coeffs) that the caller has zero-filled on this stream: slot s lands at (s - slot_lo) frames into it.  err:
-    int32 (1,) on the device, bit `code` of the word is set for every error code met; nothing else is reported."""
+    int32 (1,) on the device, bit `code` of the word is set for every error code met; nothing else is reported.
+    reloc: None, or int64 (n, 3) on the device, row s = (delta, lo, hi) of slot s (trainclips.stage_batch): the bytes of a
+    piece of that slot are a staged copy at stream[pos - delta ...] and must lie in stream[lo:hi]; a piece that does not, or
+    a slot without a row, sets bit 7 of err and decodes nothing (tdeed_jpeg_entropy_items_reloc)."""
     dev = coeff.device
     _chk(coeff, "coeff", torch.int16)
     _chk_jpeg_tables("jpeg_entropy_items", dev, stream=(stream, torch.uint8), pieces=(pieces, torch.uint8),
@@ -1371,6 +1377,14 @@ def jpeg_entropy_items(stream, pieces, items, waves, table_sets, W, H, sampling,
     fc = jpeg_frame_coeffs(W, H, sampling)
     if coeff.numel() < int(n_slots) * fc:
         raise ValueError(f"jpeg_entropy_items: coeff holds {coeff.numel()} values, {n_slots} slots need {int(n_slots) * fc}")
+    if reloc is not None:
+        _chk_jpeg_tables("jpeg_entropy_items", dev, reloc=(reloc, torch.int64))
+        if reloc.dim() != 2 or reloc.shape[1] != 3 or reloc.shape[0] < 1:
+            raise ValueError("jpeg_entropy_items: reloc (n, 3) rows of (delta, lo, hi)")
+        call("tdeed_jpeg_entropy_items_reloc", ptr(stream), stream.numel(), ptr(pieces), pieces.shape[0], ptr(items),
+             items.shape[0], ptr(waves), waves.shape[0], ptr(table_sets), table_sets.shape[0], int(W), int(H), int(sampling),
+             int(slot_lo), int(n_slots), ptr(reloc), reloc.shape[0], ptr(coeff), ptr(err), stream_ptr())
+        return coeff
     call("tdeed_jpeg_entropy_items", ptr(stream), stream.numel(), ptr(pieces), pieces.shape[0], ptr(items), items.shape[0],
          ptr(waves), waves.shape[0], ptr(table_sets), table_sets.shape[0], int(W), int(H), int(sampling), int(slot_lo),
          int(n_slots), ptr(coeff), ptr(err), stream_ptr())

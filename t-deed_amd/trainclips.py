@@ -263,7 +263,8 @@ class ResidentClips(_ClipLoader):
     from a frame directory).  All videos are packed into one device buffer, uploaded once in `chunk_bytes` chunks on a copy
     stream; the event arrays travel once, too.  The whole set must fit `max_resident_bytes` (ValueError otherwise, before
     anything is uploaded): the default 16 GiB holds 114 130 frames of 3 x 224 x 224 (76 minutes at 25 fps).  Epochs over a
-    larger set, sharded over several resident subsets, are not implemented.
+    larger set, sharded over several resident subsets, are not implemented for decoded frames; a larger set of JPEG files
+    trains through `ResidentJpegClips(stream_clips=True)`, which keeps the streams that do not fit on the host.
     Iterating yields ceil(dataset_len / batch_size) batch dicts of device tensors (the floor with drop_last), the clips
     `ClipDraws(seed=seed)` draws: 'frame' uint8 (B,T,3,H,W), 'label' int64 (B,T) and, when radi_displacement > 0, 'labelD'.
     With mixup there is no 'frame': the batch carries 'label2' (/ 'labelD2') and 'mix', the deferred blend -- `mix(lam)`
@@ -582,6 +583,183 @@ def video_tables(first, length, frame_set, side_row, piece_lo, piece_n, chunk_sl
     return batch_tables(rows, int(length), 1, frame_set, side_row, piece_lo, piece_n, chunk_slots=chunk_slots, piece_keep=keep)
 
 
+# ------------------------------------------------------------------------------------------------- streamed sets: planning
+_NO_BYTE = np.iinfo(np.int64).max
+
+
+def _round16(x):
+    return (x + 15) & ~15
+
+
+def frame_extents(shards):
+    """Where every frame's entropy streams lie on the host.  shards: `ResidentJpegs.shards`.
+    -> namespace(shard int32 (n_frames,): the shard that lists the frame; lo / hi int64 (n_frames,): first byte and end byte
+    of the frame's segments in that shard's stream, the end including the zero GUARD behind the last segment (padded to the
+    segment alignment, as `jpegdev.pack_frames` lays it out) -- lo >= hi for a frame without segments (fallback);
+    shard_first int64 (n_shards + 1,): the shards' frame boundaries).  The frames of a shard are a consecutive run."""
+    from . import jpegdev
+    n = sum(len(s.frames) for s in shards)
+    shard = np.zeros(n, np.int32)
+    lo = np.full(n, _NO_BYTE, np.int64)
+    hi = np.zeros(n, np.int64)
+    first = [0]
+    for k, s in enumerate(shards):
+        fr = np.asarray(s.frames, np.int64)
+        if fr.size == 0 or fr[0] != first[-1] or np.any(np.diff(fr) != 1):
+            raise ValueError("frame_extents: the frames of the shards must be consecutive runs in set order")
+        first.append(first[-1] + fr.size)
+        shard[fr] = k
+        seg = s.packed.segments
+        if seg.shape[0]:
+            f = fr[seg[:, 0]]
+            off = seg[:, 3].astype(np.int64)
+            np.minimum.at(lo, f, off)
+            np.maximum.at(hi, f, off + ((seg[:, 4].astype(np.int64) + jpegdev.GUARD + 3) & ~3))
+    return SimpleNamespace(shard=shard, lo=lo, hi=hi, shard_first=np.asarray(first, np.int64))
+
+
+def _shard_first(ext):
+    if getattr(ext, "shard_first", None) is not None:
+        return np.asarray(ext.shard_first, np.int64)
+    sh = np.asarray(ext.shard, np.int64)
+    n_sh = int(sh.max()) + 1 if sh.size else 0
+    if sh.size and np.any(np.diff(sh) < 0):
+        raise ValueError("the shards must hold consecutive runs of frames")
+    return np.searchsorted(sh, np.arange(n_sh + 1)).astype(np.int64)
+
+
+def _clip_ranges(ext, rows, clip_len, stride):
+    """The byte ranges the clips `rows` need, one per clip and shard: every frame from the clip's first sampled frame that
+    exists to its last, the frames a stride skips included, so that a clip is one contiguous copy per shard.
+    -> (clip int64, shard int64, lo16 int64 -- the first byte rounded down to 16 --, hi int64), sorted by clip, then shard."""
+    first, base, nfr = (np.asarray(rows[i], np.int64) for i in range(3))
+    T, S = int(clip_len), int(stride)
+    a = base + np.where(base < 0, (-base + S - 1) // S, 0) * S                 # the first and the last sampled frame that exist
+    b = base + np.minimum(T - 1, (nfr - 1 - base) // S) * S
+    live = np.flatnonzero(a <= b)
+    g0, g1 = first[live] + a[live], first[live] + b[live]
+    sf = _shard_first(ext)
+    lo_pad = np.concatenate([np.asarray(ext.lo, np.int64), [_NO_BYTE]])
+    hi_pad = np.concatenate([np.asarray(ext.hi, np.int64), [0]])
+    shard = np.asarray(ext.shard, np.int64)
+    s0, s1 = shard[g0], shard[g1]
+    out = [np.zeros(0, np.int64)] * 4
+    for d in range(int((s1 - s0).max()) + 1 if live.size else 0):
+        k = np.flatnonzero(s0 + d <= s1)
+        s = s0[k] + d
+        idx = np.stack([np.maximum(g0[k], sf[s]), np.minimum(g1[k], sf[s + 1] - 1) + 1], 1).reshape(-1)
+        lo = np.minimum.reduceat(lo_pad, idx)[::2]
+        hi = np.maximum.reduceat(hi_pad, idx)[::2]
+        on = hi > lo
+        out = [np.concatenate([o, x[on]]) for o, x in zip(out, (live[k], s, lo & ~15, hi))]
+    order = np.lexsort((out[1], out[0]))
+    return tuple(o[order] for o in out)
+
+
+def stream_plan(ext, video_first, video_len, rows, clip_len, stride, operands, batch_size, depth, fixed_bytes,
+                max_resident_bytes, who="ResidentJpegClips"):
+    """Which videos of a set stay resident when the set is streamed (pure numpy; no file, no device).
+    ext: `frame_extents`; video_first / video_len: the videos' frames in the set-wide numbering, in set order; rows: int64
+    (4, n_clips) -- per clip the first frame of its video, its base, the video's length and the video (`_ClipLoader._rows`);
+    operands: clips per batch item (2 with mixup); fixed_bytes: what is resident whatever the plan -- segment and piece
+    tables, table sets, side buffer.
+    One staging region holds a batch: operands x batch_size x the largest sum of byte ranges (`_clip_ranges`, rounded out
+    to 16) that any clip of a streamed video needs.  First fixed_bytes and depth regions for the case that every video is
+    streamed are reserved; resident are then the first v whole videos, v as large as the rest of the budget allows -- so a
+    larger budget never keeps fewer videos resident.  Their streams take, per shard, the bytes from the shard's start to
+    the end of its last resident frame, rounded up to 16.  The regions are then as large as the clips of the videos v.. need
+    (none when every video is resident).  Counted against the budget: resident streams + fixed_bytes + depth regions.
+    -> namespace(resident_videos, resident_frames, shard_bytes int64 (n_shards,) -- resident bytes per shard --, shard_base
+       int64 (n_shards,) -- where a shard's position 0 lies in the numbering JcPiece.pos uses: its place in the device buffer
+       for a shard with resident bytes, a position behind the buffer for the others --, stream_bytes (the resident streams),
+       region_bytes, stage_lo (= stream_bytes: the first region's offset in the device buffer), buffer_bytes (= stream_bytes
+       + depth * region_bytes), resident_bytes, needs int64 (videos + 1,): the budget that keeps v = 0 .. all videos resident,
+       min_budget = needs[0]).
+    ValueError when not even v = 0 fits; the message names min_budget."""
+    vf, vl = np.asarray(video_first, np.int64), np.asarray(video_len, np.int64)
+    nv = vf.size
+    sf = _shard_first(ext)
+    n_sh, n_frames = sf.size - 1, int(sf[-1])
+    if nv == 0 or np.any(np.diff(vf) != vl[:-1]) or vf[0] != 0 or int(vf[-1] + vl[-1]) != n_frames:
+        raise ValueError(f"{who}: the videos must tile the set's {n_frames} frames in order")
+    depth, per_batch = int(depth), int(operands) * int(batch_size)
+    # resident bytes of shard k when the frames below F are resident: the running maximum of the frames' end bytes
+    hi = np.asarray(ext.hi, np.int64)
+    run = hi.copy()
+    for k in range(n_sh):
+        run[sf[k]:sf[k + 1]] = np.maximum.accumulate(hi[sf[k]:sf[k + 1]])
+
+    def shard_bytes(F):
+        return np.asarray([_round16(int(run[min(F, int(sf[k + 1])) - 1])) if F > sf[k] else 0 for k in range(n_sh)], np.int64)
+    # the largest clip of every video, and of the videos v.. (the streamed ones)
+    clip, _, lo16, hi_ = _clip_ranges(ext, rows, clip_len, stride)
+    need = np.zeros(np.asarray(rows[0]).size, np.int64)
+    np.add.at(need, clip, _round16(hi_) - lo16)
+    per_video = np.zeros(nv + 1, np.int64)
+    np.maximum.at(per_video, np.asarray(rows[3], np.int64), need)
+    region = np.maximum.accumulate(per_video[::-1])[::-1] * per_batch              # region[v]: videos v.. are streamed
+    ends = np.concatenate([vf, [n_frames]])
+    needs = np.asarray([int(shard_bytes(int(ends[v])).sum()) + int(fixed_bytes) + depth * int(region[0]) for v in range(nv + 1)],
+                       np.int64)
+    fits = np.flatnonzero(needs <= int(max_resident_bytes))
+    if fits.size == 0:
+        raise ValueError(f"{who}: with no video resident the set still needs {int(needs[0])} bytes on the device ({depth} staging "
+                         f"regions of {int(region[0])}, {int(fixed_bytes)} of tables and frames kept decoded), more than "
+                         f"max_resident_bytes={int(max_resident_bytes)}; the smallest max_resident_bytes that would do is "
+                         f"{int(needs[0])}")
+    v = int(fits[-1])
+    sb = shard_bytes(int(ends[v]))
+    stream_bytes, region_bytes = int(sb.sum()), int(region[v])
+    buffer_bytes = stream_bytes + depth * region_bytes
+    base = np.concatenate([[0], np.cumsum(sb)])[:-1]
+    full = np.asarray([_round16(int(run[sf[k + 1] - 1])) if sf[k + 1] > sf[k] else 0 for k in range(n_sh)], np.int64)
+    behind = _round16(buffer_bytes) + np.concatenate([[0], np.cumsum(full)])[:-1]
+    return SimpleNamespace(resident_videos=v, resident_frames=int(ends[v]), shard_bytes=sb,
+                           shard_base=np.where(sb > 0, base, behind).astype(np.int64), stream_bytes=stream_bytes,
+                           region_bytes=region_bytes, stage_lo=stream_bytes, buffer_bytes=buffer_bytes, depth=depth,
+                           resident_bytes=buffer_bytes + int(fixed_bytes), needs=needs, min_budget=int(needs[0]))
+
+
+def stage_batch(plan, ext, rows, clip_len, stride, region_off, n_slots=None, clip_slot=None):
+    """The copies and the relocation rows of one batch of a streamed set (pure numpy; no file, no device).
+    rows / clip_slot / n_slots: as `batch_tables` (rows with the video in row 3); region_off: where the batch's staging
+    region starts in the device buffer (plan.stage_lo + ring entry * plan.region_bytes).
+    -> (copies [(shard, host byte lo, host byte hi, device offset)]: one per clip of a streamed video and shard it touches,
+          packed into the region one behind the other, each at a 16-byte boundary and starting at a host byte that is a
+          multiple of 16;
+        reloc int64 (n_slots, 3): per slot (delta, window lo, window hi) -- csrc/jpeg_core.h JcReloc.  A slot that shows a
+          frame of a streamed video reads the copy that holds the frame: delta = plan.shard_base[shard] + host lo - device
+          offset (a multiple of 16), the window is the copy.  Every other slot -- padding, a resident video's -- gets delta
+          0 and the resident window [0, plan.stream_bytes).)
+    ValueError when the ranges exceed plan.region_bytes."""
+    T, S = int(clip_len), int(stride)
+    first, base, nfr, vid = (np.asarray(rows[i], np.int64) for i in range(4))
+    n = first.size
+    at = np.arange(n, dtype=np.int64) * T if clip_slot is None else np.asarray(clip_slot, np.int64)
+    total = int(n_slots) if n_slots is not None else n * T
+    reloc = np.zeros((total, 3), np.int64)
+    reloc[:, 2] = plan.stream_bytes
+    streamed = np.flatnonzero(vid >= plan.resident_videos)
+    copies = []
+    if streamed.size == 0:
+        return copies, reloc
+    clip, shard, lo16, hi = _clip_ranges(ext, [r[streamed] for r in (first, base, nfr)], T, S)
+    size = _round16(hi) - lo16
+    dev = int(region_off) + np.concatenate([[0], np.cumsum(size)])[:-1]
+    if int(size.sum()) > plan.region_bytes:
+        raise ValueError(f"stage_batch: the batch needs {int(size.sum())} bytes of staging, the region holds {plan.region_bytes}")
+    copies = [(int(s), int(l), int(h), int(d)) for s, l, h, d in zip(shard, lo16, hi, dev)]
+    fshard = np.asarray(ext.shard, np.int64)
+    for c, s, l, h, d in zip(clip, shard, lo16, hi, dev):
+        k = streamed[c]
+        f = base[k] + np.arange(T, dtype=np.int64) * S
+        real = (f >= 0) & (f < nfr[k])
+        g = np.where(real, first[k] + f, 0)
+        on = real & (fshard[g] == s) & (np.asarray(ext.hi)[g] > np.asarray(ext.lo)[g])
+        reloc[at[k] + np.flatnonzero(on)] = (int(plan.shard_base[s]) + int(l) - int(d), int(d), int(d) + int(h) - int(l))
+    return copies, reloc
+
+
 class _ResidentStreams:
     """What `ResidentJpegClips` and `evalutil.ResidentJpegVideos` share: a packed set (`load_resident_jpegs`) made resident.
     The constructor is host arithmetic -- geometry, piece offsets, the resident bytes (stream, segment and piece tables,
@@ -591,11 +769,21 @@ class _ResidentStreams:
     synchronisation -- and decodes the fallback and the flagged frames once with `feeder.read_frame` into the side buffer
     (the budget is checked again when the index pass added side frames).  window = (top, left, wh, ww), here or through
     `set_window` before `upload`: the side buffer keeps that window of its frames only.  Afterwards: jstream, table_sets, pieces, side (device tensors or None),
-    frame_set / side_row / piece_lo / piece_n per frame of the set, piece_mcu per piece row, `stats()`."""
+    frame_set / side_row / piece_lo / piece_n per frame of the set, piece_mcu per piece row, `stats()`.
+    streamed=True: the set may exceed the budget.  The constructor then checks nothing; the caller, who knows the clips, calls
+    `plan_streaming` before `upload` (`stream_plan` against the budget; ValueError before anything is uploaded).  `upload`
+    copies only the resident bytes of every shard (plan.shard_bytes) into jstream and leaves plan.depth staging regions
+    behind them in the same allocation.  The index pass still covers every shard: one with streamed frames is copied whole
+    into the staging memory, indexed there, its piece rows' positions moved to the shard's own numbering (plan.shard_base),
+    and the stream waited for before the next shard reuses the memory.  The shards stay alive on the host (`host_streams`,
+    one tensor per shard): the batches copy from them -- asynchronously when they are page-locked (`load_resident_jpegs`'
+    default), blocking the host when not (`pinned=False`).  `stats()` gains resident_videos, streamed_videos, stage_bytes and
+    host_stream_bytes, resident_bytes includes the staging, stream_bytes stays the whole set's."""
 
-    def __init__(self, who, jpegs, split_mcus, max_resident_bytes, window=None):
+    def __init__(self, who, jpegs, split_mcus, max_resident_bytes, window=None, streamed=False):
         from . import feeder, jpegdev
         self.who, self.jpegs, self.max_resident_bytes, self.window = who, jpegs, max_resident_bytes, window
+        self.streamed, self.plan, self.ext = bool(streamed), None, None
         self.fr0 = None
         if jpegs.width:
             W, H, samp = jpegs.width, jpegs.height, jpegs.samp
@@ -641,12 +829,41 @@ class _ResidentStreams:
         self.fb = int(np.prod(self.side_shape))
         self.check(len(self.side_frames))
 
-    def resident(self, n_side):
+    def fixed(self, n_side):
+        """the resident bytes besides the streams: segment and piece tables, table sets, side buffer"""
         from . import jpegdev
-        return self.total + self.n_seg * 4 * jpegdev.SEG_COLS + self.n_pieces * jpegdev.PIECE_BYTES + \
+        return self.n_seg * 4 * jpegdev.SEG_COLS + self.n_pieces * jpegdev.PIECE_BYTES + \
             self.jpegs.n_sets * jpegdev.TABLE_SET_BYTES + n_side * self.fb
 
+    def resident(self, n_side):
+        if self.plan is not None:
+            return self.plan.buffer_bytes + self.fixed(n_side)
+        return self.total + self.fixed(n_side)
+
+    def plan_streaming(self, rows, clip_len, stride, operands, batch_size, depth):
+        """Streamed sets, before `upload`: `stream_plan` over the clips `rows` against the budget (ValueError naming the
+        smallest budget that would do), and every shard that is not wholly resident held against the staging memory, through
+        which its index pass runs (ValueError naming `shard_bytes`)."""
+        self.ext = frame_extents(self.shards)
+        self.plan = plan = stream_plan(self.ext, self.jpegs.video_first, self.jpegs.video_len, rows, clip_len, stride, operands,
+                                       batch_size, depth, self.fixed(len(self.side_frames)), self.max_resident_bytes, self.who)
+        stage = plan.buffer_bytes - plan.stage_lo
+        for s, end in zip(self.shards, self.ext.shard_first[1:]):
+            size = _round16(int(s.packed.stream_np.size))
+            if s.packed.n_segments and end > plan.resident_frames and size > stage:
+                raise ValueError(f"{self.who}: a streamed shard of {size} bytes does not fit the {stage} bytes of staging memory "
+                                 "its index pass runs through; pass a smaller shard_bytes to load_resident_jpegs")
+        return plan
+
     def check(self, n_side):
+        if self.streamed:
+            # before the plan: nothing to hold (plan_streaming does); after the upload: the index pass added side frames, and
+            # a plan with fewer resident videos would need a new upload
+            if self.plan is not None and self.resident(n_side) > self.max_resident_bytes:
+                raise ValueError(f"{self.who}: the index pass left {n_side} frames to keep decoded, and with them the set needs "
+                                 f"{self.resident(n_side)} bytes on the device, more than max_resident_bytes="
+                                 f"{self.max_resident_bytes}")
+            return
         if self.resident(n_side) > self.max_resident_bytes:
             raise ValueError(f"{self.who}: the set needs {self.resident(n_side)} bytes on the device ({self.total} of entropy "
                              f"streams, {n_side} frames kept decoded), more than max_resident_bytes={self.max_resident_bytes}")
@@ -657,16 +874,25 @@ class _ResidentStreams:
         jpegs, shards, base, seg_lo, n_seg = self.jpegs, self.shards, self.base, self.seg_lo, self.n_seg
         W, H, samp, split, piece_off, n_pieces = self.W, self.H, self.samp, self.split, self.piece_off, self.n_pieces
         n_frames, names, side, flagged = jpegs.n_frames, jpegs.names, self.side_frames, []
+        plan = self.plan
+        if self.streamed and plan is None:
+            raise RuntimeError(f"{self.who}: a streamed set is planned (plan_streaming) before it is uploaded")
         if n_seg:
-            # the streams, shard by shard, into one buffer; every table in one copy from a page-locked block
-            self.jstream = torch.zeros(self.total, dtype=torch.uint8, device=dev)
+            # the streams, shard by shard, into one buffer; every table in one copy from a page-locked block.  Streamed: the
+            # resident bytes of every shard only (plan.shard_bytes), the staging regions behind them in the same allocation
+            self.jstream = torch.zeros(self.total if plan is None else max(plan.buffer_bytes, 16), dtype=torch.uint8, device=dev)
             keep = []
-            for s, b in zip(shards, base):
+            self.host_streams = []                          # per shard its stream as a host tensor (streamed sets copy from it)
+            for k, (s, b) in enumerate(zip(shards, base)):
+                src = s.packed.stream if isinstance(s.packed.stream, torch.Tensor) else torch.from_numpy(s.packed.stream_np)
+                self.host_streams.append(src)
                 if not s.packed.n_segments:
                     continue
-                src = s.packed.stream if isinstance(s.packed.stream, torch.Tensor) else torch.from_numpy(s.packed.stream_np)
-                for lo in range(0, src.numel(), int(chunk_bytes)):
-                    hi = min(lo + int(chunk_bytes), src.numel())
+                if plan is not None:
+                    b = base[k] = int(plan.shard_base[k])
+                end = src.numel() if plan is None else min(int(plan.shard_bytes[k]), src.numel())
+                for lo in range(0, end, int(chunk_bytes)):
+                    hi = min(lo + int(chunk_bytes), end)
                     self.jstream[b + lo:b + hi].copy_(src[lo:hi], non_blocking=True)
                 keep.append(src)
             segs = np.concatenate([s.packed.segments for s in shards if s.packed.n_segments])
@@ -693,10 +919,20 @@ class _ResidentStreams:
             status = torch.zeros(n_seg, dtype=torch.int32, device=dev)
             for i, (s, b, s0) in enumerate(zip(shards, base, seg_lo)):
                 n = s.packed.n_segments
-                if n:
-                    ops.jpeg_entropy_index(self.jstream, b, d_segs[s0:s0 + n], view(3 + i, torch.int32, (waves[i].shape[0], 2)),
-                                           self.table_sets, W, H, samp, split, d_off[s0:s0 + n + 1], s0, self.pieces,
-                                           status[s0:s0 + n])
+                if not n:
+                    continue
+                staged = plan is not None and int(self.ext.shard_first[i + 1]) > plan.resident_frames
+                if staged:
+                    # a shard with streamed frames: through the staging memory, then its rows' positions moved from there
+                    # to the shard's own base (plan.shard_base: 64-bit, behind the buffer for a shard without resident bytes)
+                    src, at = self.host_streams[i], plan.stage_lo
+                    self.jstream[at:at + src.numel()].copy_(src, non_blocking=True)
+                ops.jpeg_entropy_index(self.jstream, at if staged else b, d_segs[s0:s0 + n],
+                                       view(3 + i, torch.int32, (waves[i].shape[0], 2)), self.table_sets, W, H, samp, split,
+                                       d_off[s0:s0 + n + 1], s0, self.pieces, status[s0:s0 + n])
+                if staged:
+                    self.pieces.view(torch.int64)[int(piece_off[s0]):int(piece_off[s0 + n]), 0] += b - at
+                    stream.synchronize()                      # before the next shard reuses the staging memory
             h_status = torch.empty(n_seg, dtype=torch.int32).pin_memory()
             h_status.copy_(status, non_blocking=True)
             stream.synchronize()                          # the one host synchronisation of construction
@@ -747,10 +983,15 @@ class _ResidentStreams:
 
     def stats(self):
         n_frames, n_side = self.jpegs.n_frames, len(self.side_frames)
-        return dict(frames=n_frames, device_frames=n_frames - n_side, fallback_frames=n_side,
-                    index_flagged=sorted(self.flagged), segments=self.n_seg, pieces=self.n_pieces, shards=len(self.shards),
-                    table_sets=self.jpegs.n_sets, stream_bytes=self.total, resident_bytes=self.resident(n_side),
-                    decoded_bytes=n_frames * 3 * self.H * self.W)
+        st = dict(frames=n_frames, device_frames=n_frames - n_side, fallback_frames=n_side,
+                  index_flagged=sorted(self.flagged), segments=self.n_seg, pieces=self.n_pieces, shards=len(self.shards),
+                  table_sets=self.jpegs.n_sets, stream_bytes=self.total, resident_bytes=self.resident(n_side),
+                  decoded_bytes=n_frames * 3 * self.H * self.W)
+        if self.plan is not None:                               # streamed: stream_bytes stays the whole set's
+            nv = len(self.jpegs.video_len)
+            st.update(resident_videos=self.plan.resident_videos, streamed_videos=nv - self.plan.resident_videos,
+                      stage_bytes=self.plan.buffer_bytes - self.plan.stage_lo, host_stream_bytes=self.total - self.plan.stream_bytes)
+        return st
 
 
 class _SlotMix:
@@ -784,12 +1025,25 @@ class ResidentJpegClips(_ClipLoader):
     ops.jpeg_pixels_rows into the entry's uint8 slot, and ops.jpeg_slot_fill for padding and side frames.  With mixup the
     slot holds both clips and `mix(lam)` is ops_bwd.mix_frames on them.  No host synchronisation per batch beyond
     `ResidentClips`' table-reuse wait; at the end of each pass the device error word is read (one synchronisation) and a
-    non-zero word raises RuntimeError naming the pass."""
+    non-zero word raises RuntimeError naming the pass.
+
+    stream_clips=True: a set whose resident bytes exceed max_resident_bytes is accepted.  The tables of the whole set and the
+    streams of the first videos that fit stay resident (`stream_plan`: fixed bytes and `depth` staging regions are reserved
+    first; a budget too small for those raises ValueError naming the smallest that would do); the streams of the other videos
+    stay in the host shards of `jpegs`, which must outlive the loader's use (it keeps references).  Per batch `stage_batch`
+    gives one byte range per clip of a streamed video and shard; they are copied into the ring entry's staging region on a
+    copy stream, behind the event of the last items launch that read the region, the relocation rows travel with the other
+    tables, and the relocating items entry (ops.jpeg_entropy_items(..., reloc=...)) decodes from the copies -- no host
+    synchronisation added, the copies of a batch overlap the decode of the one before.  Everything a consumer sees is the
+    all-resident loader's bit for bit.  A shard with streamed frames must fit the staging memory (ValueError: pass a smaller
+    shard_bytes to `load_resident_jpegs`); pageable shards (`pinned=False`) work, their copies block the host.  `stats` gains
+    resident_videos, streamed_videos, stage_bytes, host_stream_bytes; `stage_log`, set to a list, collects the bytes copied
+    per batch.  Without the keyword nothing changes."""
 
     def __init__(self, videos, jpegs, classes, clip_len, stride=1, overlap=1, radi_displacement=0, mixup=False,
                  dataset_len=1, batch_size=8, seed=None, pad_len=DEFAULT_PAD_LEN, require_events=False, drop_last=False,
                  max_resident_bytes=16 << 30, device="cuda", depth=3, chunk_bytes=64 << 20, split_mcus=None,
-                 max_coeff_bytes=512 << 20):
+                 max_coeff_bytes=512 << 20, stream_clips=False):
         import torch
         from . import ops
         from .streams import new_stream
@@ -800,14 +1054,20 @@ class ResidentJpegClips(_ClipLoader):
         for v, n in zip(videos, jpegs.video_len):
             if int(v["num_frames"]) != int(n):
                 raise ValueError(f"ResidentJpegClips: video {v['video']} has {int(v['num_frames'])} frames, the packed set {int(n)}")
-        rs = _ResidentStreams("ResidentJpegClips", jpegs, split_mcus, max_resident_bytes)
+        rs = _ResidentStreams("ResidentJpegClips", jpegs, split_mcus, max_resident_bytes, streamed=stream_clips)
         n_frames, n_seg, H, W, samp = jpegs.n_frames, rs.n_seg, rs.H, rs.W, rs.samp
         self._init_clips(videos, [int(n) for n in jpegs.video_len], classes, clip_len, stride, overlap, radi_displacement, mixup,
                          dataset_len, batch_size, seed, pad_len, require_events, drop_last, device, depth)
         self.shape, self.samp, self.split_mcus = (3, H, W), samp, rs.split
+        self._plan = self._ext = self._copy_stream = None
+        if stream_clips:
+            self._plan = rs.plan_streaming(self._rows, self.clip_len, self.stride, 2 if self.mixup else 1, int(batch_size), self.depth)
+            self._ext = rs.ext
         dev = torch.device(device)
         self.stream = new_stream(device)
         self.stream.wait_stream(torch.cuda.current_stream(device))
+        if stream_clips:
+            self._copy_stream = new_stream(device, avoid=[self.stream])
         with torch.cuda.stream(self.stream):
             self._ev = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device)
                              for a in (self.table.ev_off, self.table.ev_frame, self.table.ev_class))
@@ -826,7 +1086,7 @@ class ResidentJpegClips(_ClipLoader):
             max_pieces = int(self._piece_n.max()) if n_frames else 0
             cap_items = max(cap * max_pieces, 1)
             cap_waves = cap_items // 64 + max(jpegs.n_sets, 1) * -(-cap // self._chunk) + 1
-            sizes = [4 * nops * B * 8, cap * 4, cap * 4, cap_items * 8, cap_waves * 8]
+            sizes = [4 * nops * B * 8, cap * 4, cap * 4, cap_items * 8, cap_waves * 8] + ([cap * 24] if stream_clips else [])
             self._offs = np.concatenate([[0], np.cumsum([(s + 15) & ~15 for s in sizes])]).astype(np.int64)
             nbytes = int(self._offs[-1])
             self._host = [torch.zeros(nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.depth)]
@@ -839,6 +1099,12 @@ class ResidentJpegClips(_ClipLoader):
             self._ident = torch.arange(cap, dtype=torch.int32, device=dev)
             self._err = torch.zeros(1, dtype=torch.int32, device=dev)
             self._err_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+            if stream_clips:
+                self._host_streams = rs.host_streams if n_seg else []
+                self._staged = [None] * self.depth        # event: the copies into the entry's staging region have finished
+                self._items_done = [None] * self.depth    # event: the last items launch that reads the entry's region
+                self._copy_stream.wait_stream(self.stream)
+        self.stage_log = None                   # set to a list: the byte count of every batch's range copies
         self._caps = (cap_items, cap_waves)
         self._pass = 0
         self.item_events = None                 # set to a list: (start, end) events around every jpeg_entropy_items launch
@@ -860,6 +1126,31 @@ class ResidentJpegClips(_ClipLoader):
         return (part(0, torch.int64)[:4 * nops * B].view(4 * nops, B), part(1, torch.int32)[:self._cap],
                 part(2, torch.int32)[:self._cap], part(3, torch.int32)[:2 * cap_items].view(cap_items, 2),
                 part(4, torch.int32)[:2 * cap_waves].view(cap_waves, 2))
+
+    def _stage(self, j, rows, at):
+        """Streamed sets: the relocation rows of the batch into entry j's page-locked block, and its range copies from the
+        host shards into the entry's staging region on the copy stream, behind the last items launch that read the region.
+        -> True when anything was copied (the loader's stream then waits for self._staged[j])."""
+        import torch
+        plan = self._plan
+        copies, reloc = stage_batch(plan, self._ext, rows, self.clip_len, self.stride, plan.stage_lo + j * plan.region_bytes,
+                                    n_slots=self._cap, clip_slot=at)
+        o = self._offs
+        self._host_np[j][o[5]:o[5] + self._cap * 24].view(np.int64).reshape(self._cap, 3)[:] = reloc
+        if self.stage_log is not None:
+            self.stage_log.append(sum(hi - lo for _, lo, hi, _ in copies))
+        if not copies:
+            return False
+        cs = self._copy_stream
+        if self._items_done[j] is not None:
+            cs.wait_event(self._items_done[j])
+        with torch.cuda.stream(cs):
+            for k, lo, hi, d in copies:
+                self.jstream[d:d + hi - lo].copy_(self._host_streams[k][lo:hi], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(cs)
+        self._staged[j] = ev
+        return True
 
     def __iter__(self):
         import torch
@@ -884,6 +1175,7 @@ class ResidentJpegClips(_ClipLoader):
             h_set[:], h_fill[:] = tb.slot_set, tb.fill
             h_items[:tb.items.shape[0]] = tb.items
             h_waves[:tb.waves.shape[0]] = tb.waves
+            staged = self._plan is not None and self._stage(j, rows, at)
             slot, lab = self._slots[j], self._labels[j]
             with torch.cuda.stream(self.stream):
                 if self._consumed[j] is not None:
@@ -895,17 +1187,27 @@ class ResidentJpegClips(_ClipLoader):
                 d_rows, d_set, d_fill, d_items, d_waves = self._views(self._dev[j], Bcap, False)
                 batch = {}
                 self._label_launches(d_rows, lab, B, batch)
+                d_reloc = None
+                if self._plan is not None:
+                    o = self._offs
+                    d_reloc = self._dev[j][int(o[5]):int(o[5]) + self._cap * 24].view(torch.int64).view(self._cap, 3)
+                    if staged:
+                        self.stream.wait_event(self._staged[j])
                 for lo, hi, w_lo, w_hi in tb.chunks:
                     self._coeff[:(hi - lo) * self._fc].zero_()
                     if self.item_events is not None:
                         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                         e0.record(self.stream)
                     ops.jpeg_entropy_items(self.jstream, self.pieces, d_items[:tb.items.shape[0]], d_waves[w_lo:w_hi],
-                                           self.table_sets, W, H, self.samp, lo, hi - lo, self._coeff, self._err)
+                                           self.table_sets, W, H, self.samp, lo, hi - lo, self._coeff, self._err, reloc=d_reloc)
                     if self.item_events is not None:
                         e1.record(self.stream)
                         self.item_events.append((e0, e1))
                     ops.jpeg_pixels_rows(self._coeff, d_set, self.table_sets, slot, self._ident, lo, hi - lo, self.samp)
+                if staged:
+                    done = torch.cuda.Event()
+                    done.record(self.stream)
+                    self._items_done[j] = done
                 ops.jpeg_slot_fill(self.side, d_fill, slot)
                 if self.mixup:
                     batch["mix"] = _SlotMix(slot[0, :B], slot[1, :B])

@@ -6,6 +6,9 @@
                                                                          host (decode_device_main), profiles/train_feed_device_decode.json
     python tools/bench_train_feed.py --resident-jpeg [same options]      clips decoded per batch from JPEG streams that stay on the
                                                                          device (resident_jpeg_main), profiles/train_feed_resident_jpeg.json
+    python tools/bench_train_feed.py --resident-jpeg --stream-clips 0.5 min [same options]
+                                                                         the same loader over a set larger than its budget
+                                                                         (streamed_jpeg_main), profiles/train_feed_streamed_jpeg.json
 
 Synthetic JPEG videos (224 x 224, quality 90) are written to a temporary directory with a label file.  Measured:
   loader   clips/s of `trainclips.ResidentClips` alone (T = 100, batch 8), without mixup (the uint8 batch) and with it (labels
@@ -332,6 +335,133 @@ def resident_jpeg_main(a):
     return 0
 
 
+def streamed_jpeg_main(a):
+    """--resident-jpeg --stream-clips F [F ...]: `trainclips.ResidentJpegClips(stream_clips=True)` at max_resident_bytes = F x
+    the all-resident bytes of the set ("min": `stream_plan`'s smallest budget, everything streamed; a fraction below it is
+    raised to it) against the all-resident loader (fraction 1.0, the keyword off) and `feeder.clip_batches` +
+    ProcessDecodePool, on the same noise-frame videos, in one run, the routes alternating: (a) the loader alone, plain clips,
+    (b) a 200MF training epoch with mixup fed by each.  Per setting: the budget, resident and streamed videos, staging and
+    host-only bytes, clips/s with its spread over the rounds, the bytes copied per batch and the time of the per-piece entropy
+    kernel per batch from device events.  One JSON record, printed and written to profiles/train_feed_streamed_jpeg.json.
+    No threshold: `faster` says for every pair of routes whether the slowest round of one beat the fastest round of the other."""
+    from tdeed_amd import jpegdev
+    from tdeed_amd.model import TDEEDModel
+    from types import SimpleNamespace
+    T, r, bs = CFG["clip_len"], CFG["radi_displacement"], a.batch
+    root = tempfile.mkdtemp(prefix="tdeed_train_feed_")
+    out = dict(kind="train_feed_streamed_jpeg", cfg=CFG, videos=a.videos, frames_per_video=a.frames, clips_per_epoch=a.clips,
+               batch_size=bs, decode_processes=a.procs, repeats=a.repeats, shard_bytes=a.shard_mib << 20,
+               device=torch.cuda.get_device_name(0), measured_on_gpu=True)
+    pool = None
+    try:
+        videos = write_videos(root, a.videos, a.frames)
+        threads = feeder.DecodePool(a.procs)
+        jpegs = TC.load_resident_jpegs(root, DATASET, videos, pool=threads, cache=jpegdev.ParseCache(), shard_bytes=a.shard_mib << 20)
+        threads.close()
+        common = dict(clip_len=T, radi_displacement=r, batch_size=bs, drop_last=True, device="cuda", dataset_len=a.clips, seed=1)
+        n_epoch = a.clips // bs * bs
+
+        def build(mixup):
+            """{route: loader}: the all-resident loader and one streamed loader per setting, with what each keeps where"""
+            made = dict(resident_all=TC.ResidentJpegClips(videos, jpegs, CLASSES, mixup=mixup, **common))
+            whole = made["resident_all"].stats["resident_bytes"]
+            low = TC.ResidentJpegClips(videos, jpegs, CLASSES, mixup=mixup, stream_clips=True, **common)._plan.min_budget
+            info = dict(resident_all=dict(budget_fraction=1.0, resident_bytes=whole))
+            for f in a.stream_clips:
+                want = low if f == "min" else int(float(f) * whole)
+                ld = TC.ResidentJpegClips(videos, jpegs, CLASSES, mixup=mixup, stream_clips=True, max_resident_bytes=max(want, low),
+                                          **common)
+                made[f"streamed_{f}"] = ld
+                info[f"streamed_{f}"] = dict(budget_fraction=f, asked_bytes=want, max_resident_bytes=max(want, low),
+                                             smallest_budget=low, raised_to_smallest=bool(want < low),
+                                             **{k: ld.stats[k] for k in ("resident_bytes", "resident_videos", "streamed_videos",
+                                                                         "stage_bytes", "host_stream_bytes", "stream_bytes")})
+            torch.cuda.synchronize()
+            return made, info
+
+        def drain(loader):
+            for _ in feeder.prefetch(loader, "cuda"):
+                pass
+
+        def reseeded(ld, seed):
+            ld.reseed(seed)
+            return ld
+
+        def faster(res):
+            names = list(res)
+            return {f"{x}_over_{y}": bool(res[x]["clips_per_s_min"] > res[y]["clips_per_s_max"]) for x in names for y in names if x != y}
+
+        def per_batch(made, res):
+            """the event time of the items kernel and the bytes copied, per batch, of the timed rounds of every resident route"""
+            for k, ld in made.items():
+                ms = [e0.elapsed_time(e1) for e0, e1 in ld.item_events]
+                res[k]["item_kernel_ms_per_batch"] = round(float(np.sum(ms)) / max(len(ld) * a.repeats, 1), 4)
+                res[k]["copied_bytes_per_batch"] = int(np.mean(ld.stage_log)) if ld.stage_log else 0
+                ld.item_events = ld.stage_log = None
+
+        def run(made, host, first_seed, step):
+            routes = {k: (lambda seed, ld=ld: reseeded(ld, seed)) for k, ld in made.items()}
+            routes["host_decoded"] = host
+            times, last = {k: [] for k in routes}, {}
+            for rep in range(a.repeats + 1):
+                if rep == 1:                                                   # the first round warms up
+                    for ld in made.values():
+                        ld.item_events, ld.stage_log = [], []
+                for k, mk in routes.items():                                   # alternating
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    last[k] = step(mk(first_seed + rep))
+                    torch.cuda.synchronize()
+                    if rep:
+                        times[k].append(time.perf_counter() - t0)
+            res = {k: dict(_rate(v, n_epoch), rounds_s=[round(x, 4) for x in v]) for k, v in times.items()}
+            per_batch(made, res)
+            return res, last
+
+        # ---- (a) the loader alone, plain clips; every round draws new clips, the same for every route
+        made, out["settings_plain"] = build(False)
+        st = made["resident_all"].stats
+        out["set"] = {k: st[k] for k in ("frames", "device_frames", "fallback_frames", "segments", "pieces", "shards", "table_sets",
+                                         "stream_bytes", "resident_bytes", "decoded_bytes")}
+        out["jpeg_stream_bytes_per_frame"] = round(st["stream_bytes"] / max(st["frames"], 1), 1)
+        pool = feeder.ProcessDecodePool(a.procs)
+        out["loader"], _ = run(made, lambda seed: decoded_loader(root, videos, pool, False, a.clips, bs, seed), 10,
+                               drain)
+        out["loader"]["faster"] = faster({k: v for k, v in out["loader"].items()})
+        del made
+
+        # ---- (b) a training epoch with mixup fed by each route
+        made, out["settings_mixup"] = build(True)
+        m = TDEEDModel(device="cuda", args=SimpleNamespace(modality="rgb", temporal_arch="ed_sgp_mixer", pretrain=None, **CFG))
+        m.load({k: torch.from_numpy(v) for k, v in synth.make_state(state_layout.model_state_shapes(CFG), 0).items()})
+        opt, _ = m.get_optimizer({"lr": 1e-4})
+        out["epoch"], losses = run(made, lambda seed: decoded_loader(root, videos, pool, True, a.clips, bs, seed), 2,
+                                   lambda ld: m.epoch(ld, optimizer=opt))
+        for k, v in losses.items():
+            out["epoch"][k]["last_loss"] = round(float(v), 5)
+        out["epoch"]["faster"] = faster({k: v for k, v in out["epoch"].items()})
+        out["notes"] = [
+            "the JPEG files stay in the page cache on the host route: decode is measured, not disk",
+            "resident_all is ResidentJpegClips without the keyword: every stream on the device, the absolute items entry",
+            "streamed_F: stream_clips=True with max_resident_bytes = F x resident_all's bytes, raised to the smallest budget the plan "
+            "allows where F asks for less (raised_to_smallest); streamed_min: that smallest budget, every video streamed",
+            "copied_bytes_per_batch: mean bytes of the range copies host -> staging region per batch of the timed rounds; "
+            "item_kernel_ms_per_batch: summed event time of the items launches of the timed rounds divided by their batches",
+            "construction (reading and parsing every file once, upload, index pass) is not in the rounds",
+            "faster[x_over_y] is true only where x's slowest round beat y's fastest"]
+    finally:
+        if pool is not None:
+            pool.close()
+        shutil.rmtree(root, ignore_errors=True)
+    line = json.dumps(out)
+    print(line)
+    path = a.out if a.out else os.path.join(ROOT, "profiles", "train_feed_streamed_jpeg.json")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as fh:
+        fh.write(line + "\n")
+    return 0
+
+
 def _rate(times, clips):
     t = np.asarray(times)
     return dict(clips_per_s=round(clips / float(np.median(t)), 1), clips_per_s_min=round(clips / float(t.max()), 1),
@@ -351,6 +481,11 @@ def main():
     ap.add_argument("--resident-jpeg", action="store_true",
                     help="measure trainclips.ResidentJpegClips against ResidentClips and the host-decoded feed instead "
                          "(profiles/train_feed_resident_jpeg.json)")
+    ap.add_argument("--stream-clips", nargs="+", default=None, metavar="BUDGET_FRACTION",
+                    help="with --resident-jpeg: measure ResidentJpegClips(stream_clips=True) at these fractions of the all-resident "
+                         "bytes ('min': the smallest budget) against the all-resident loader and the host-decoded feed "
+                         "(profiles/train_feed_streamed_jpeg.json)")
+    ap.add_argument("--shard-mib", type=int, default=16, help="--stream-clips: shard_bytes of load_resident_jpegs, in MiB")
     ap.add_argument("--read-threads", type=int, default=0,
                     help="--decode-device: threads that read the files (0: the feed's own thread; the files sit in the page cache, "
                          "where a read is too short to be worth a hand-over between threads)")
@@ -358,6 +493,8 @@ def main():
     a = ap.parse_args()
     if a.decode_device:
         return decode_device_main(a)
+    if a.resident_jpeg and a.stream_clips:
+        return streamed_jpeg_main(a)
     if a.resident_jpeg:
         return resident_jpeg_main(a)
     a.out = a.out or os.path.join(ROOT, "profiles", "train_feed.json")

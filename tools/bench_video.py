@@ -745,6 +745,135 @@ def decode_device(a):
     return 0
 
 
+def _write_jpeg_set(tmp, lengths, FH, FW, K):
+    """The synthetic validation set of the resident-JPEG modes: videos of `lengths` frames cycling 16 distinct pictures (a
+    colour ramp, a wave and low noise), quality 90, 4:2:0 -> (video dicts, truth lists, bytes of all files)"""
+    from PIL import Image
+    yy, xx = np.mgrid[0:FH, 0:FW].astype(np.float64)
+    pics = []
+    for k in range(16):
+        base = np.stack([30 + 180 * xx / (FW - 1), 40 + 170 * yy / (FH - 1), 128 + 90 * np.sin(0.11 * xx + k) * np.cos(0.07 * yy)], -1)
+        noise = synth.uint8_clip(700 + k, (FH, FW, 3)).astype(np.float64) / 10.0 - 12.75
+        pics.append(Image.fromarray(np.clip(base + noise, 0, 255).astype(np.uint8)))
+    videos, file_bytes = [], 0
+    for v, L in enumerate(lengths):
+        d = os.path.join(tmp, f"v{v:03d}")
+        os.makedirs(d)
+        for i in range(L):
+            pics[(i + 3 * v) % 16].save(os.path.join(d, f"frame{i}.jpg"), "JPEG", quality=90, subsampling=2)
+            file_bytes += os.path.getsize(os.path.join(d, f"frame{i}.jpg"))
+        videos.append(dict(video=f"v{v:03d}", num_frames=L, fps=25.0))
+    truth = [{"video": v["video"], "events": [{"label": f"c{1 + (f // 20) % K}", "frame": f} for f in range(7, v["num_frames"], 20)]}
+             for v in videos]
+    return videos, truth, file_bytes
+
+
+def streamed_jpeg(a):
+    """--resident-jpeg --stream-clips F [F ...]: the validation pass of `resident_jpeg` fed by `evalutil.ResidentJpegVideos(
+    stream_videos=True)` at max_resident_bytes = F x the all-resident bytes of the set ("min": the plan's smallest budget,
+    every video streamed; a fraction below it is raised to it), against the all-resident object (fraction 1.0, the keyword off)
+    and decode="host", in one process, the routes alternating: a warm-up pass per route, then `--repeats` timed passes (at
+    least three), every pass listed.  Per setting what stays where, and the entropy kernel alone on the long video.  A route is
+    called faster than another only when it is faster in every timed pass.  Written to profiles/video_streamed_jpeg.json."""
+    import tempfile
+    from types import SimpleNamespace
+    from tdeed_amd.model import TDEEDModel
+    from tdeed_amd import trainclips as TC
+    FH, FW = 224, 398
+    repeats = max(int(a.repeats), 3)
+    m = TDEEDModel(device="cuda", args=SimpleNamespace(modality="rgb", temporal_arch="ed_sgp_mixer", pretrain=None, **CFG))
+    m.load({k: torch.from_numpy(v) for k, v in synth.make_state(state_layout.model_state_shapes(CFG), 0).items()})
+    K = CFG["num_classes"]
+    classes = {f"c{k}": k for k in range(1, K + 1)}
+    suppress = (("nms", 1, 0.10), ("snms", 3, 0.01))
+    tols = [0, 1, 2, 4]
+    lengths = group_lengths("diving")[:a.map_videos] + [a.frames]
+    n_frames = int(sum(lengths))
+    kw = dict(batch_size=8, group_videos=min(a.group_videos, 8))
+    coeff = a.coeff_mib << 20
+    with tempfile.TemporaryDirectory() as tmp:
+        videos, truth, file_bytes = _write_jpeg_set(tmp, lengths, FH, FW, K)
+        tpool = feeder.DecodePool(a.threads)
+        try:
+            files = [(v["video"], v["num_frames"], v["fps"],
+                      dict(frame_dir=tmp, dataset="soccernetball", video_name=v["video"], num_frames=v["num_frames"], pool=tpool))
+                     for v in videos]
+            jpegs = TC.load_resident_jpegs(tmp, "soccernetball", videos, pool=tpool, shard_bytes=a.shard_mib << 20)
+            made = dict(resident_all=E.ResidentJpegVideos(videos, jpegs, max_coeff_bytes=coeff))
+            whole = made["resident_all"].stats["resident_bytes"]
+            low = E.ResidentJpegVideos(videos, jpegs, max_coeff_bytes=coeff, stream_videos=True)._plan.min_budget
+            settings = dict(resident_all=dict(budget_fraction=1.0, resident_bytes=whole))
+            for f in a.stream_clips:
+                want = low if f == "min" else int(float(f) * whole)
+                rv = E.ResidentJpegVideos(videos, jpegs, max_coeff_bytes=coeff, stream_videos=True, max_resident_bytes=max(want, low))
+                made[f"streamed_{f}"] = rv
+                settings[f"streamed_{f}"] = dict(budget_fraction=f, asked_bytes=want, max_resident_bytes=max(want, low),
+                                                 smallest_budget=low, raised_to_smallest=bool(want < low), chunk_frames=rv._chunk,
+                                                 **{k: rv.stats[k] for k in ("resident_bytes", "resident_videos", "streamed_videos",
+                                                                             "stage_bytes", "host_stream_bytes", "stream_bytes")})
+            routes = dict(a_decode_host=lambda: E.map_videos(m, files, classes, truth, suppress, tols, decode="host", **kw))
+            for k, rv in made.items():
+                routes[k] = lambda rv=rv: E.map_videos(m, rv.sources(), classes, truth, suppress, tols, **kw)
+            res, first = {}, {}
+            for k, fn in routes.items():                                    # warm-up: plans, graphs, table caches
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res[k] = fn()
+                torch.cuda.synchronize()
+                first[k] = round((time.perf_counter() - t0) * 1e3, 1)
+            times = {k: [] for k in routes}
+            for _ in range(repeats):
+                for k, fn in routes.items():                                # alternating
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    times[k].append(time.perf_counter() - t0)
+            kernels = {}
+            for key, rv in made.items():                                    # the entropy kernel alone, on the long video
+                rv._kernel_events = []
+                for _ in range(repeats + 1):
+                    rv.frames(len(lengths) - 1)
+                ev, rv._kernel_events = rv._kernel_events, None
+                per = len(ev) // (repeats + 1)
+                copies = rv._tabs[len(lengths) - 1][5]
+                kernels[key] = dict(frames=lengths[-1], chunks=per, copied_bytes=int(sum(hi - lo for c in copies.values() for _, lo, hi, _ in c)),
+                                    entropy_items_ms=[round(sum(e0.elapsed_time(e1) for e0, e1, _ in ev[i * per:(i + 1) * per]), 3)
+                                                      for i in range(1, repeats + 1)])
+        finally:
+            tpool.close()
+    same = {k: bool(res[k] == res["a_decode_host"]) for k in routes}
+    rt = {}
+    for k, v in times.items():
+        tt = np.asarray(v) * 1e3
+        rt[k] = dict(first_pass_ms=first[k], passes_ms=[round(float(x), 1) for x in tt], ms_min=round(float(tt.min()), 1),
+                     ms_max=round(float(tt.max()), 1), ms_median=round(float(np.median(tt)), 1),
+                     frames_per_s_median=round(n_frames / float(np.median(tt)) * 1e3, 1))
+    verdicts = {}
+    for new in made:
+        for old in routes:
+            if new != old and not (old in made and new == "resident_all"):
+                x, y = np.asarray(times[new]), np.asarray(times[old])
+                every = bool(np.all(x < y))
+                verdicts[f"{new}_vs_{old}"] = dict(
+                    faster_in_every_timed_pass=every, ratio_of_medians_old_over_new=round(float(np.median(y) / np.median(x)), 3),
+                    note=("faster in every timed pass" if every else "slower in every timed pass" if bool(np.all(x > y)) else
+                          "the ranges overlap or the order changes between passes: no claim"))
+    rec = dict(kind="video_streamed_jpeg", device=torch.cuda.get_device_name(0), measured_on_gpu=True, cfg=CFG, videos=len(lengths),
+               frames=n_frames, longest_video=lengths[-1], frame="224x398 4:2:0 quality 90, 16 distinct pictures (ramp + wave + low "
+               "noise)", jpeg_file_bytes_per_frame=round(file_bytes / n_frames, 1), threads=tpool.threads, group_videos=kw["group_videos"],
+               batch_size=8, repeats=repeats, max_coeff_bytes=coeff, shard_bytes=a.shard_mib << 20, settings=settings, routes=rt,
+               maps_equal_route_a=same, verdicts=verdicts, kernels_alone_long_video=kernels)
+    out = os.path.join(ROOT, "profiles", "video_streamed_jpeg.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rec))
+    assert all(same.values()), f"the routes' mAP tables differ: {same}"
+    return 0
+
+
 def resident_jpeg(a):
     """A validation pass (`evalutil.map_videos`) over the tool's synthetic set -- `--map-videos` short videos of the diving
     split plus one of `--frames` frames, 224 x 398 4:2:0 JPEG files, the model cropping the centre 224 x 224 -- fed four ways,
@@ -756,7 +885,6 @@ def resident_jpeg(a):
     is called faster than another only when it is faster in every timed pass; otherwise the ranges are given."""
     import tempfile
     from types import SimpleNamespace
-    from PIL import Image
     from tdeed_amd.model import TDEEDModel
     from tdeed_amd import trainclips as TC
     FH, FW = 224, 398
@@ -772,23 +900,7 @@ def resident_jpeg(a):
     budget = 16 << 30
     kw = dict(batch_size=8, group_videos=min(a.group_videos, 8))          # groups of 8: the next group decodes meanwhile
     with tempfile.TemporaryDirectory() as tmp:
-        # 16 distinct pictures: a colour ramp, a wave and low noise, quality 90, 4:2:0
-        yy, xx = np.mgrid[0:FH, 0:FW].astype(np.float64)
-        pics = []
-        for k in range(16):
-            base = np.stack([30 + 180 * xx / (FW - 1), 40 + 170 * yy / (FH - 1), 128 + 90 * np.sin(0.11 * xx + k) * np.cos(0.07 * yy)], -1)
-            noise = synth.uint8_clip(700 + k, (FH, FW, 3)).astype(np.float64) / 10.0 - 12.75
-            pics.append(Image.fromarray(np.clip(base + noise, 0, 255).astype(np.uint8)))
-        videos, file_bytes = [], 0
-        for v, L in enumerate(lengths):
-            d = os.path.join(tmp, f"v{v:03d}")
-            os.makedirs(d)
-            for i in range(L):
-                pics[(i + 3 * v) % 16].save(os.path.join(d, f"frame{i}.jpg"), "JPEG", quality=90, subsampling=2)
-                file_bytes += os.path.getsize(os.path.join(d, f"frame{i}.jpg"))
-            videos.append(dict(video=f"v{v:03d}", num_frames=L, fps=25.0))
-        truth = [{"video": v["video"], "events": [{"label": f"c{1 + (f // 20) % K}", "frame": f} for f in range(7, v["num_frames"], 20)]}
-                 for v in videos]
+        videos, truth, file_bytes = _write_jpeg_set(tmp, lengths, FH, FW, K)
         tpool = feeder.DecodePool(a.threads)
         try:
             files = [(v["video"], v["num_frames"], v["fps"],
@@ -903,8 +1015,13 @@ if __name__ == "__main__":
     ap.add_argument("--threads", type=int, default=8)
     ap.add_argument("--resident-jpeg", action="store_true",
                     help="map_videos fed by host decode, device decode and ResidentJpegVideos (with and without crop)")
+    ap.add_argument("--stream-clips", nargs="+", default=None, metavar="BUDGET_FRACTION",
+                    help="with --resident-jpeg: ResidentJpegVideos(stream_videos=True) at these fractions of the all-resident bytes "
+                         "('min': the smallest budget) against the all-resident object and host decode (profiles/video_streamed_jpeg.json)")
+    ap.add_argument("--shard-mib", type=int, default=4, help="--stream-clips: shard_bytes of load_resident_jpegs, in MiB")
+    ap.add_argument("--coeff-mib", type=int, default=128, help="--stream-clips: max_coeff_bytes, in MiB (its frame chunks are the staging region)")
     a = ap.parse_args()
     if a.frames is None:
         a.frames = 5625 if a.spot else 2030
-    sys.exit(resident_jpeg(a) if a.resident_jpeg else ring(a) if a.ring else map_bench(a) if a.map else decode_device(a) if a.decode_device else decode(a) if a.decode else gather_only(a) if a.gather_only else reuse(a) if a.reuse else group(a) if a.group
+    sys.exit(streamed_jpeg(a) if a.resident_jpeg and a.stream_clips else resident_jpeg(a) if a.resident_jpeg else ring(a) if a.ring else map_bench(a) if a.map else decode_device(a) if a.decode_device else decode(a) if a.decode else gather_only(a) if a.gather_only else reuse(a) if a.reuse else group(a) if a.group
              else spot(a) if a.spot else bench(a))
