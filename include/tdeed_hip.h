@@ -553,6 +553,12 @@ int tdeed_ap_rank(const double* ev_score, const int* ev_count, const int* vid_of
  * 16-byte aligned, a byte path otherwise.  B * T <= 65535. */
 int tdeed_train_clip_gather_u8(const uint8_t* frames, long total_frames, long frame_bytes, const long* first, const long* base,
                                const long* nframes, int B, int T, int stride, uint8_t* out, void* stream);
+/* The same with one stride per clip: strides DEVICE int32[B], out[b][t] = frames[first[b] + base[b] + t*strides[b]] under the
+ * same window rule, the same guards and the same two access widths (a joint batch mixes clips of sets sampled at different
+ * strides).  The entry cannot read the table: the caller refuses an entry <= 0 on the host; the kernel does not follow one
+ * (zero frames). */
+int tdeed_train_clip_gather_u8_ps(const uint8_t* frames, long total_frames, long frame_bytes, const long* first, const long* base,
+                                  const long* nframes, int B, int T, const int* strides, uint8_t* out, void* stream);
 /* Mixup of two such windows without their uint8 intermediates: out fp32 [B][T][frame_bytes] =
  * lam[b] * A[b][t] + (1 - lam[b]) * B[b][t], bit for bit what tdeed_mix_frames gives on the two batches
  * tdeed_train_clip_gather_u8 would write (a padded frame contributes 0).  4-byte loads / 16-byte stores when
@@ -560,6 +566,12 @@ int tdeed_train_clip_gather_u8(const uint8_t* frames, long total_frames, long fr
 int tdeed_train_clip_gather_mix_f32(const uint8_t* frames, long total_frames, long frame_bytes, const long* first_a,
                                     const long* base_a, const long* nframes_a, const long* first_b, const long* base_b,
                                     const long* nframes_b, const float* lam, int B, int T, int stride, float* out, void* stream);
+/* The same with one stride per clip, shared by its two operands: strides DEVICE int32[B]; bit for bit tdeed_mix_frames on the
+ * two batches tdeed_train_clip_gather_u8_ps would write.  The same 4-byte load / 16-byte store path and scalar path. */
+int tdeed_train_clip_gather_mix_f32_ps(const uint8_t* frames, long total_frames, long frame_bytes, const long* first_a,
+                                       const long* base_a, const long* nframes_a, const long* first_b, const long* base_b,
+                                       const long* nframes_b, const float* lam, int B, int T, const int* strides, float* out,
+                                       void* stream);
 /* Labels of n clips (dataset/frame.py:151-159, 226-233): clip_video / clip_base DEVICE int64[n] (video index, first original
  * frame), ev_off int32[nv+1] / ev_frame / ev_class int32[n_events] the videos' events in file order.  Per (clip, t) the
  * events of the clip's video are walked in order, idx = floor((ev_frame - base) / stride); the last one with
@@ -567,6 +579,10 @@ int tdeed_train_clip_gather_mix_f32(const uint8_t* frames, long total_frames, lo
  * int64 [n][T] (labelD may be NULL).  One thread per position, no atomics. */
 int tdeed_clip_labels(const long* clip_video, const long* clip_base, int n, int T, int stride, int r, const int* ev_off,
                       const int* ev_frame, const int* ev_class, int nv, int n_events, long* label, long* labelD, void* stream);
+/* The same with one stride per clip: strides DEVICE int32[n], idx = floor((ev_frame - base) / strides[clip]).  A clip whose
+ * entry is <= 0 gets 0 / 0 everywhere (the caller refuses such a table on the host). */
+int tdeed_clip_labels_ps(const long* clip_video, const long* clip_base, int n, int T, const int* strides, int r, const int* ev_off,
+                         const int* ev_frame, const int* ev_class, int nv, int n_events, long* label, long* labelD, void* stream);
 
 /* ---- backward of the SGP encoder-decoder (training path; sgp_bwd.hip) ------------------------------------------
  * Activations and activation gradients share the forward dtype; parameter gradients are fp32.  Every parameter

@@ -204,6 +204,9 @@ _SIGS = {
     "tdeed_train_clip_gather_u8": ([P, c_long, c_long, P, P, P, c_int, c_int, c_int, P, P], c_int),
     "tdeed_train_clip_gather_mix_f32": ([P, c_long, c_long, P, P, P, P, P, P, P, c_int, c_int, c_int, P, P], c_int),
     "tdeed_clip_labels": ([P, P, c_int, c_int, c_int, c_int, P, P, P, c_int, c_int, P, P, P], c_int),
+    "tdeed_train_clip_gather_u8_ps": ([P, c_long, c_long, P, P, P, c_int, c_int, P, P, P], c_int),
+    "tdeed_train_clip_gather_mix_f32_ps": ([P, c_long, c_long, P, P, P, P, P, P, P, c_int, c_int, P, P, P], c_int),
+    "tdeed_clip_labels_ps": ([P, P, c_int, c_int, P, c_int, P, P, P, c_int, c_int, P, P, P], c_int),
     "tdeed_jpeg_frame_coeffs": ([c_int, c_int, c_int], c_long),
     "tdeed_jpeg_entropy": ([P, c_long, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P], c_int),
     "tdeed_jpeg_pixels": ([P, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P], c_int),

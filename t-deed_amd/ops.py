@@ -1540,3 +1540,77 @@ def clip_labels(clip_video, clip_base, T, stride, r, ev_off, ev_frame, ev_class,
     call("tdeed_clip_labels", ptr(clip_video), ptr(clip_base), n, T, stride, r, ptr(ev_off), ptr(ev_frame) if ne else None,
          ptr(ev_class) if ne else None, ev_off.numel() - 1, ne, ptr(label), ptr(labelD), stream_ptr())
     return label, labelD
+
+
+# ---- the same three with one stride per clip (the ..._ps entries; trainclips.JointResidentClips)
+def _clip_strides(strides, n, dev, who):
+    """strides as the ..._ps entries take them: a contiguous int32 (n,) tensor on `dev`.  A host sequence / array is held
+    against the rule (every entry > 0, ValueError) and uploaded; a device tensor is the caller's own table, checked on the
+    host where it was built -- the kernels do not follow an entry <= 0."""
+    if not isinstance(strides, torch.Tensor) or not strides.is_cuda:
+        host = np.asarray(strides.numpy() if isinstance(strides, torch.Tensor) else strides)
+        if host.ndim != 1 or host.size != n or not np.issubdtype(host.dtype, np.integer):
+            raise ValueError(f"{who}: strides must be {n} integers, one per clip")
+        if host.size and int(host.min()) <= 0:
+            raise ValueError(f"{who}: every stride must be positive")
+        return torch.from_numpy(np.ascontiguousarray(host, np.int32)).to(dev)
+    if strides.dtype != torch.int32 or strides.dim() != 1 or strides.numel() != n or not strides.is_contiguous() \
+            or strides.device != dev:
+        raise ValueError(f"{who}: strides must be a contiguous int32 ({n},) tensor on the tables' device")
+    return strides
+
+
+def train_clip_gather_ps(frames_u8, first, base, nframes, T, strides, out):
+    """`train_clip_gather` with one stride per clip: out[b*T + t] = frames_u8[first[b] + base[b] + t*strides[b]] under the same
+    window rule.  strides: int32 (B,) on the device, or a host sequence (checked: every entry > 0)."""
+    B, L, fb = _chk_clip_tables(frames_u8, (first, base, nframes), "train_clip_gather_ps")
+    strides = _clip_strides(strides, B, frames_u8.device, "train_clip_gather_ps")
+    if out.dtype != torch.uint8 or not out.is_contiguous() or out.device != frames_u8.device:
+        raise TypeError("train_clip_gather_ps: out must be a contiguous uint8 tensor on the frames' device")
+    if out.numel() != B * T * fb:
+        raise ValueError(f"train_clip_gather_ps: out holds {out.numel()} bytes, {B} clips of {T} frames need {B * T * fb}")
+    call("tdeed_train_clip_gather_u8_ps", ptr(frames_u8), L, fb, ptr(first), ptr(base), ptr(nframes), B, T, ptr(strides),
+         ptr(out), stream_ptr())
+    return out
+
+
+def train_clip_gather_mix_ps(frames_u8, tabs_a, tabs_b, lam, T, strides, out=None):
+    """`train_clip_gather_mix` with one stride per clip, shared by the clip's two operands (strides as above)."""
+    if not isinstance(tabs_a, (tuple, list)) or not isinstance(tabs_b, (tuple, list)) or len(tabs_a) != 3 or len(tabs_b) != 3:
+        raise ValueError("train_clip_gather_mix_ps: (first, base, nframes) per operand")
+    B, L, fb = _chk_clip_tables(frames_u8, tuple(tabs_a) + tuple(tabs_b), "train_clip_gather_mix_ps")
+    strides = _clip_strides(strides, B, frames_u8.device, "train_clip_gather_mix_ps")
+    if lam.dtype != torch.float32 or lam.numel() != B or not lam.is_contiguous() or lam.device != frames_u8.device:
+        raise ValueError(f"train_clip_gather_mix_ps: lam must be a contiguous fp32 ({B},) tensor on the frames' device")
+    if out is None:
+        out = torch.empty((B, T) + tuple(frames_u8.shape[1:]), dtype=torch.float32, device=frames_u8.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * T * fb or out.device != frames_u8.device:
+        raise ValueError(f"train_clip_gather_mix_ps: out must be a contiguous fp32 tensor of {B * T * fb} elements")
+    call("tdeed_train_clip_gather_mix_f32_ps", ptr(frames_u8), L, fb, *(ptr(x) for x in tabs_a), *(ptr(x) for x in tabs_b),
+         ptr(lam), B, T, ptr(strides), ptr(out), stream_ptr())
+    return out
+
+
+def clip_labels_ps(clip_video, clip_base, T, strides, r, ev_off, ev_frame, ev_class, label=None, labelD=None, displ=True):
+    """`clip_labels` with one stride per clip: strides int32 (n,) on the device, or a host sequence (checked)."""
+    dev = clip_video.device
+    n = clip_video.numel()
+    for tab, dt, what in ((clip_video, torch.int64, "clip_video"), (clip_base, torch.int64, "clip_base"),
+                          (ev_off, torch.int32, "ev_off"), (ev_frame, torch.int32, "ev_frame"), (ev_class, torch.int32, "ev_class")):
+        if not isinstance(tab, torch.Tensor) or tab.dtype != dt or tab.dim() != 1 or not tab.is_contiguous() \
+                or not tab.is_cuda or tab.device != dev:
+            raise ValueError(f"clip_labels_ps: {what} must be a contiguous 1-d {dt} GPU tensor")
+    if clip_base.numel() != n or ev_class.numel() != ev_frame.numel() or ev_off.numel() < 2:
+        raise ValueError("clip_labels_ps: table lengths do not match")
+    strides = _clip_strides(strides, n, dev, "clip_labels_ps")
+    if label is None:
+        label = torch.empty((n, T), dtype=torch.int64, device=dev)
+    if labelD is None and displ:
+        labelD = torch.empty((n, T), dtype=torch.int64, device=dev)
+    for o in (label, labelD):
+        if o is not None and (o.dtype != torch.int64 or not o.is_contiguous() or o.numel() != n * T or o.device != dev):
+            raise ValueError(f"clip_labels_ps: outputs must be contiguous int64 ({n},{T}) tensors")
+    ne = ev_frame.numel()
+    call("tdeed_clip_labels_ps", ptr(clip_video), ptr(clip_base), n, T, ptr(strides), r, ptr(ev_off), ptr(ev_frame) if ne else None,
+         ptr(ev_class) if ne else None, ev_off.numel() - 1, ne, ptr(label), ptr(labelD), stream_ptr())
+    return label, labelD

@@ -17,6 +17,12 @@ The host side restates what the reference computes and is pure numpy: `train_cli
 `ResidentJpegClips` is the same loader over a set that stays on the device compressed: `load_resident_jpegs` packs the
 entropy streams of every frame once, and a batch decodes the frames it drew on the device (csrc/jpeg.hip), one lane per
 piece of a frame's scan; `batch_tables` is the host's share of a batch, pure numpy.
+
+`JointResidentClips` / `JointResidentJpegClips` are the two loaders over the reference's joint dataset
+(`ActionSpotDatasetJoint`, dataset/frame.py:640-663: two `ActionSpotDataset`s, a coin per item): `JointDraws` restates its
+draws, both parts live in the one packed buffer (`join_clip_tables`, `join_resident_jpegs`), every clip keeps the stride of its
+part and a batch is served by the per-clip-stride entries (ops.train_clip_gather_ps / train_clip_gather_mix_ps /
+clip_labels_ps); the batch dicts gain 'dataset'.
 """
 import random
 from types import SimpleNamespace
@@ -90,19 +96,21 @@ def rasterise_labels(table, clip_ids, clip_len, stride, radi_displacement):
     numerator is negative for events before the base); when -r <= idx < T + r every i in [max(0, idx-r), min(T, idx+r+1))
     gets label[i] = class, labelD[i] = i - idx.  Later events overwrite earlier ones.
     -> (label int64 (n,T), labelD int64 (n,T)).  A negative radius raises ValueError (the reference's branch for it reads
-    an attribute that does not exist)."""
+    an attribute that does not exist).  stride: one for all, or one per entry of clip_ids (a joined table's clips keep
+    the stride of their part)."""
     r = int(radi_displacement)
     if r < 0:
         raise ValueError("radi_displacement must not be negative")
     T = int(clip_len)
     ids = np.asarray(clip_ids, np.int64).reshape(-1)
+    strides = _strides_of(stride, len(ids), "rasterise_labels")
     label = np.zeros((len(ids), T), np.int64)
     labelD = np.zeros((len(ids), T), np.int64)
     for k, c in enumerate(ids):
         v = int(table.clip_video[c])
         base = int(table.clip_base[c])
         for e in range(int(table.ev_off[v]), int(table.ev_off[v + 1])):
-            idx = (int(table.ev_frame[e]) - base) // stride
+            idx = (int(table.ev_frame[e]) - base) // int(strides[k])
             if -r <= idx < T + r:
                 for i in range(max(0, idx - r), min(T, idx + r + 1)):
                     label[k, i] = int(table.ev_class[e])
@@ -142,6 +150,81 @@ class ClipDraws:
             yield np.asarray(a, np.int64), (np.asarray(b, np.int64) if self.mixup else None)
 
 
+class JointDraws:
+    """The draws of `ActionSpotDatasetJoint.__getitem__` (dataset/frame.py:651-660) over two `ActionSpotDataset`s, for a
+    DataLoader without workers after `random.seed(seed)`: per item one `random()` -- below 0.5 the item comes from part 1,
+    otherwise from part 2 --, then that part's `_get_one`: one `randint(0, n_k - 1)` on its clip count and, with mixup, a
+    second one on the same part (the partner never comes from the other part).  The pass has dataset_len items -- the sum of
+    the two parts' lengths (frame.py:662-663), given as that sum or as the pair --, cut into batches as `ClipDraws` does.
+    Iterating yields (part int64 (B,) of 1 / 2, idx int64 (B,), idx2 int64 (B,) | None) per batch; idx counts inside the
+    part.  A private `random.Random(seed)`, continued from pass to pass; `reseed(seed)` starts it anew."""
+
+    def __init__(self, n_clips, dataset_len, batch_size, mixup, seed, drop_last=False):
+        n_clips = tuple(int(n) for n in n_clips)
+        total = int(sum(dataset_len)) if isinstance(dataset_len, (tuple, list)) else int(dataset_len)
+        if len(n_clips) != 2:
+            raise ValueError("JointDraws: the reference joins two datasets")
+        if min(n_clips) <= 0 or total <= 0 or batch_size <= 0:
+            raise ValueError("n_clips, dataset_len and batch_size must be positive")
+        self.n_clips, self.dataset_len, self.batch_size = n_clips, total, int(batch_size)
+        self.mixup, self.drop_last = bool(mixup), bool(drop_last)
+        self._rng = random.Random(seed)
+
+    def __len__(self):
+        full, rest = divmod(self.dataset_len, self.batch_size)
+        return full + (1 if rest and not self.drop_last else 0)
+
+    def reseed(self, seed):
+        self._rng = random.Random(seed)
+
+    def __iter__(self):
+        left = self.dataset_len
+        for _ in range(len(self)):
+            B = min(self.batch_size, left)
+            left -= B
+            part, a, b = [], [], []
+            for _ in range(B):
+                k = 0 if self._rng.random() < 0.5 else 1
+                part.append(k + 1)
+                a.append(self._rng.randint(0, self.n_clips[k] - 1))
+                if self.mixup:
+                    b.append(self._rng.randint(0, self.n_clips[k] - 1))
+            yield np.asarray(part, np.int64), np.asarray(a, np.int64), (np.asarray(b, np.int64) if self.mixup else None)
+
+
+def join_clip_tables(tables):
+    """One clip table over several parts (`train_clip_table` per part, in order): the concatenation, with the video indices
+    and the event offsets of a part shifted by the videos and events of the parts in front.
+    -> namespace(train_clip_table's fields, clip_part int64 (n,) -- 1-based --, part_clips int64 (parts + 1,): the parts'
+    clip boundaries, part_videos int64 (parts + 1,): their video boundaries)."""
+    if not tables:
+        raise ValueError("join_clip_tables: no parts")
+    nv = np.concatenate([[0], np.cumsum([len(t.num_frames) for t in tables])]).astype(np.int64)
+    ne = np.concatenate([[0], np.cumsum([len(t.ev_frame) for t in tables])]).astype(np.int64)
+    nc = np.concatenate([[0], np.cumsum([len(t.clip_video) for t in tables])]).astype(np.int64)
+    return SimpleNamespace(
+        clip_video=np.concatenate([t.clip_video.astype(np.int64) + nv[k] for k, t in enumerate(tables)]).astype(np.int32),
+        clip_base=np.concatenate([t.clip_base for t in tables]).astype(np.int64),
+        ev_frame=np.concatenate([t.ev_frame for t in tables]).astype(np.int32),
+        ev_class=np.concatenate([t.ev_class for t in tables]).astype(np.int32),
+        ev_off=np.concatenate([[0]] + [t.ev_off[1:].astype(np.int64) + ne[k] for k, t in enumerate(tables)]).astype(np.int32),
+        num_frames=np.concatenate([t.num_frames for t in tables]).astype(np.int64),
+        clip_part=np.repeat(np.arange(1, len(tables) + 1, dtype=np.int64), np.diff(nc)), part_clips=nc, part_videos=nv)
+
+
+def _strides_of(stride, n, who):
+    """one stride per clip, int64 (n,), from a scalar or a per-clip sequence; ValueError unless every one is positive"""
+    s = np.asarray(stride)
+    if s.ndim == 0:
+        s = np.full(n, int(s))
+    s = s.astype(np.int64).reshape(-1)
+    if s.size != n:
+        raise ValueError(f"{who}: {s.size} strides for {n} clips")
+    if n and int(s.min()) <= 0:
+        raise ValueError(f"{who}: every stride must be positive")
+    return s
+
+
 def load_resident_videos(frame_dir, dataset, videos, pool=None, decode="host"):
     """The `frames` argument of `ResidentClips` from a frame directory: per video of the label list one uint8
     (num_frames,3,H,W) tensor (page-locked when a GPU runtime is there), every JPEG decoded once by
@@ -177,12 +260,14 @@ class _DeferredMix:
     allocation per batch on this path; `ops_bwd.mix_frames` allocates the same way).  `tabs_a` / `tabs_b`: the batch's
     (first, base, nframes) device tables.  Valid until the batch is released (`feeder.done`)."""
 
-    def __init__(self, loader, tabs_a, tabs_b, B):
-        self._loader, self.tabs_a, self.tabs_b, self.B = loader, tabs_a, tabs_b, B
+    def __init__(self, loader, tabs_a, tabs_b, B, strides=None):
+        self._loader, self.tabs_a, self.tabs_b, self.B, self.strides = loader, tabs_a, tabs_b, B, strides
 
     def __call__(self, lam):
         from . import ops
         ld = self._loader
+        if self.strides is not None:                # a joint batch: the device int32 (B,) stride of every clip
+            return ops.train_clip_gather_mix_ps(ld.video, self.tabs_a, self.tabs_b, lam.contiguous(), ld.clip_len, self.strides)
         return ops.train_clip_gather_mix(ld.video, self.tabs_a, self.tabs_b, lam.contiguous(), ld.clip_len, ld.stride)
 
 
@@ -192,13 +277,40 @@ class _ClipLoader:
 
     def _init_clips(self, videos, lengths, classes, clip_len, stride, overlap, radi_displacement, mixup, dataset_len,
                     batch_size, seed, pad_len, require_events, drop_last, device, depth):
+        part = dict(videos=videos, classes=classes, stride=stride, overlap=overlap, require_events=require_events,
+                    dataset_len=dataset_len)
+        self._init_parts([part], lengths, clip_len, radi_displacement, mixup, batch_size, seed, pad_len, drop_last, device, depth,
+                         joint=False)
+
+    def _init_parts(self, parts, lengths, clip_len, radi_displacement, mixup, batch_size, seed, pad_len, drop_last, device, depth,
+                    joint):
+        """parts: [dict(videos, classes, stride=1, overlap=1, require_events=False, dataset_len)], each with its own clip
+        list; lengths: the length of every video of every part, in order (they are packed in that order).  joint=False (one
+        part): the table, the rows and the draws of the single-set loaders, nothing else.  joint=True: the table is the
+        concatenation (`join_clip_tables`), the draws are `JointDraws`, and every clip keeps the stride and the number of
+        its part (`_clip_stride` int32, `table.clip_part`); a batch's device rows then end in one row of strides -- int32, in
+        the first half of the int64 row -- and one of part numbers, the batch's 'dataset'."""
         name = type(self).__name__
-        self.table = train_clip_table(videos, classes, clip_len, stride, overlap, pad_len, require_events, radi_displacement)
-        n = len(self.table.clip_video)
-        if n == 0:
-            raise ValueError(f"{name}: no clips")
-        self.clip_len, self.stride, self.radius, self.mixup = int(clip_len), int(stride), int(radi_displacement), bool(mixup)
-        self.draws = ClipDraws(n, dataset_len, batch_size, mixup, seed, drop_last)
+        tables = []
+        for k, p in enumerate(parts):
+            tables.append(train_clip_table(p["videos"], p["classes"], clip_len, p.get("stride", 1), p.get("overlap", 1), pad_len,
+                                           p.get("require_events", False), radi_displacement))
+            if len(tables[-1].clip_video) == 0:
+                raise ValueError(f"{name}: no clips" + (f" in part {k + 1}" if joint else ""))
+        self.clip_len, self.radius, self.mixup = int(clip_len), int(radi_displacement), bool(mixup)
+        self.joint = bool(joint)
+        self._nrows = (8 if self.mixup else 4) + (2 if joint else 0)
+        if joint:
+            self.tables, self.table = tables, join_clip_tables(tables)
+            self.stride, self.strides = None, tuple(int(p.get("stride", 1)) for p in parts)
+            counts = np.diff(self.table.part_clips)
+            self._clip_stride = _strides_of(np.repeat(np.asarray(self.strides, np.int64), counts), int(counts.sum()),
+                                            name).astype(np.int32)
+            self.draws = JointDraws(counts, [int(p["dataset_len"]) for p in parts], batch_size, mixup, seed, drop_last)
+        else:
+            self.table = tables[0]
+            self.stride = int(parts[0]["stride"])
+            self.draws = ClipDraws(len(self.table.clip_video), parts[0]["dataset_len"], batch_size, mixup, seed, drop_last)
         if batch_size * self.clip_len > 65535:
             raise ValueError(f"{name}: {batch_size} clips of {clip_len} frames exceed the gather's 65535 frame slots")
         self.device, self.depth = device, int(depth)
@@ -206,6 +318,26 @@ class _ClipLoader:
         offs = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
         cv = self.table.clip_video.astype(np.int64)
         self._rows = np.stack([offs[cv], self.table.clip_base, np.asarray(lengths, np.int64)[cv], cv])       # (4, n)
+
+    def _drawn(self, draw):
+        """(clip ids of the batch, the partners' | None, part numbers | None) of one item of `self.draws`"""
+        if not self.joint:
+            return draw[0], draw[1], None
+        part, ia, ib = draw
+        lo = self.table.part_clips[part - 1]
+        return lo + ia, (lo + ib if ib is not None else None), part
+
+    def _joint_rows(self, host_rows, ia, part):
+        """the stride and the part row of a joint batch into its page-locked (rows, B) int64 block"""
+        B, k = len(ia), self._nrows - 2
+        host_rows[k].view(np.int32)[:B] = self._clip_stride[ia]
+        host_rows[k + 1, :B] = part
+
+    def _joint_views(self, dev_rows, B):
+        """(strides int32 (B,), dataset int64 (B,)) of a joint batch's device rows"""
+        import torch
+        k = self._nrows - 2
+        return dev_rows[k].view(torch.int32)[:B], dev_rows[k + 1, :B]
 
     def _init_ring(self):
         self._copied = [None] * self.depth        # event: the H2D copy of the slot's pinned table has finished
@@ -219,7 +351,7 @@ class _ClipLoader:
     def reseed(self, seed):
         """Start the draw stream anew from `seed` (the reference's workers reseed `random` per epoch, train_tdeed.py:126-127)."""
         d = self.draws
-        self.draws = ClipDraws(d.n_clips, d.dataset_len, d.batch_size, d.mixup, seed, d.drop_last)
+        self.draws = type(d)(d.n_clips, d.dataset_len, d.batch_size, d.mixup, seed, d.drop_last)
 
     def release(self, j, stream=None):
         """`feeder.done`: everything queued on `stream` (default: the current one) so far was the last use of slot j."""
@@ -240,15 +372,19 @@ class _ClipLoader:
             self._copied[j].synchronize()                # a copy of `depth` batches ago: long finished
         return j
 
-    def _label_launches(self, dev, lab, B, batch):
-        """the ops.clip_labels launches of one batch from its (4 * operands, B) device rows into the slot's label buffer"""
+    def _label_launches(self, dev, lab, B, batch, strides=None):
+        """the ops.clip_labels launches of one batch from its (4 * operands, B) device rows into the slot's label buffer;
+        strides: a joint batch's device int32 (B,) strides, shared by a clip and its partner"""
         from . import ops
         T, S, r = self.clip_len, self.stride, self.radius
         k = 0
         for op, sfx in enumerate(("", "2") if self.mixup else ("",)):
             t4 = dev[4 * op:4 * op + 4]
-            label, labelD = ops.clip_labels(t4[3, :B], t4[1, :B], T, S, r, *self._ev, label=lab[k, :B],
-                                            labelD=lab[k + 1, :B] if r > 0 else None, displ=False)
+            out = dict(label=lab[k, :B], labelD=lab[k + 1, :B] if r > 0 else None, displ=False)
+            if strides is not None:
+                label, labelD = ops.clip_labels_ps(t4[3, :B], t4[1, :B], T, strides, r, *self._ev, **out)
+            else:
+                label, labelD = ops.clip_labels(t4[3, :B], t4[1, :B], T, S, r, *self._ev, **out)
             batch["label" + sfx] = label
             if r > 0:
                 batch["labelD" + sfx] = labelD
@@ -282,33 +418,45 @@ class ResidentClips(_ClipLoader):
     def __init__(self, videos, frames, classes, clip_len, stride=1, overlap=1, radi_displacement=0, mixup=False,
                  dataset_len=1, batch_size=8, seed=None, pad_len=DEFAULT_PAD_LEN, require_events=False, drop_last=False,
                  max_resident_bytes=16 << 30, device="cuda", depth=3, chunk_bytes=64 << 20):
+        part = dict(videos=videos, frames=frames, classes=classes, stride=stride, overlap=overlap, require_events=require_events,
+                    dataset_len=dataset_len)
+        self._build([part], False, clip_len, radi_displacement, mixup, batch_size, seed, pad_len, drop_last, max_resident_bytes,
+                    device, depth, chunk_bytes)
+
+    def _build(self, parts, joint, clip_len, radi_displacement, mixup, batch_size, seed, pad_len, drop_last, max_resident_bytes,
+               device, depth, chunk_bytes):
+        """The constructor over parts (`_ClipLoader._init_parts`; every part with its `frames`): the videos of all parts are
+        packed into the one buffer, in order."""
         import torch
         from . import feeder
         from .streams import new_stream
+        who = type(self).__name__
         if radi_displacement < 0:
             raise ValueError("radi_displacement must not be negative")
-        if len(frames) != len(videos) or not videos:
-            raise ValueError(f"ResidentClips: {len(videos)} videos, {len(frames)} frame tensors")
         srcs = []
-        for v, fr in zip(videos, frames):
-            if not isinstance(fr, torch.Tensor):
-                fr = torch.as_tensor(np.asarray(fr))
-            if fr.dtype != torch.uint8 or fr.dim() != 4:
-                raise TypeError("ResidentClips: frames must be uint8 (num_frames,3,H,W) tensors")
-            if fr.shape[0] != int(v["num_frames"]):
-                raise ValueError(f"ResidentClips: video {v['video']} has {int(v['num_frames'])} frames, its tensor {fr.shape[0]}")
-            srcs.append(fr)
+        for p in parts:
+            videos, frames = p["videos"], p["frames"]
+            if len(frames) != len(videos) or not videos:
+                raise ValueError(f"{who}: {len(videos)} videos, {len(frames)} frame tensors")
+            for v, fr in zip(videos, frames):
+                if not isinstance(fr, torch.Tensor):
+                    fr = torch.as_tensor(np.asarray(fr))
+                if fr.dtype != torch.uint8 or fr.dim() != 4:
+                    raise TypeError(f"{who}: frames must be uint8 (num_frames,3,H,W) tensors")
+                if fr.shape[0] != int(v["num_frames"]):
+                    raise ValueError(f"{who}: video {v['video']} has {int(v['num_frames'])} frames, its tensor {fr.shape[0]}")
+                srcs.append(fr)
         shape = tuple(srcs[0].shape[1:])
         if any(tuple(fr.shape[1:]) != shape for fr in srcs):
-            raise ValueError(f"ResidentClips: the videos share one frame geometry, got "
+            raise ValueError(f"{who}: the videos share one frame geometry, got "
                              f"{sorted({tuple(fr.shape[1:]) for fr in srcs})}")
         lengths = [int(fr.shape[0]) for fr in srcs]
         fb = int(np.prod(shape))
         if sum(lengths) * fb > max_resident_bytes:
-            raise ValueError(f"ResidentClips: the videos need {sum(lengths) * fb} bytes on the device, more than "
+            raise ValueError(f"{who}: the videos need {sum(lengths) * fb} bytes on the device, more than "
                              f"max_resident_bytes={max_resident_bytes} (sharded epochs are not implemented)")
-        self._init_clips(videos, lengths, classes, clip_len, stride, overlap, radi_displacement, mixup, dataset_len, batch_size,
-                         seed, pad_len, require_events, drop_last, device, depth)
+        self._init_parts(parts, lengths, clip_len, radi_displacement, mixup, batch_size, seed, pad_len, drop_last, device, depth,
+                         joint)
         self.stream = new_stream(device)
         self._copy_stream = new_stream(device, avoid=[self.stream])
         cur = torch.cuda.current_stream(device)
@@ -323,9 +471,9 @@ class ResidentClips(_ClipLoader):
             self.stream.wait_event(resident)
             self._ev = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device)
                              for a in (self.table.ev_off, self.table.ev_frame, self.table.ev_class))
-            self._host = [torch.zeros((4 * nops, B), dtype=torch.int64).pin_memory() for _ in range(self.depth)]
+            self._host = [torch.zeros((self._nrows, B), dtype=torch.int64).pin_memory() for _ in range(self.depth)]
             self._host_np = [h.numpy() for h in self._host]
-            self._dev = [torch.zeros((4 * nops, B), dtype=torch.int64, device=device) for _ in range(self.depth)]
+            self._dev = [torch.zeros((self._nrows, B), dtype=torch.int64, device=device) for _ in range(self.depth)]
             self._frame = None if self.mixup else [torch.empty((B, T) + shape, dtype=torch.uint8, device=device)
                                                    for _ in range(self.depth)]
             nlab = nops * (2 if self.radius > 0 else 1)
@@ -336,13 +484,16 @@ class ResidentClips(_ClipLoader):
         import torch
         from . import ops
         T, S = self.clip_len, self.stride
-        for ia, ib in self.draws:
+        for draw in self.draws:
+            ia, ib, part = self._drawn(draw)
             j = self._next_slot()
             B = len(ia)
             host = self._host_np[j]
             host[0:4, :B] = self._rows[:, ia]
             if ib is not None:
                 host[4:8, :B] = self._rows[:, ib]
+            if part is not None:
+                self._joint_rows(host, ia, part)
             dev, lab = self._dev[j], self._labels[j]
             with torch.cuda.stream(self.stream):
                 if self._consumed[j] is not None:
@@ -352,10 +503,15 @@ class ResidentClips(_ClipLoader):
                 ev.record(self.stream)
                 self._copied[j] = ev
                 batch = {}
-                self._label_launches(dev, lab, B, batch)
+                strides = None
+                if part is not None:
+                    strides, batch["dataset"] = self._joint_views(dev, B)
+                self._label_launches(dev, lab, B, batch, strides)
                 tabs_a = (dev[0, :B], dev[1, :B], dev[2, :B])
                 if self.mixup:
-                    batch["mix"] = _DeferredMix(self, tabs_a, (dev[4, :B], dev[5, :B], dev[6, :B]), B)
+                    batch["mix"] = _DeferredMix(self, tabs_a, (dev[4, :B], dev[5, :B], dev[6, :B]), B, strides)
+                elif strides is not None:
+                    batch["frame"] = ops.train_clip_gather_ps(self.video, *tabs_a, T, strides, self._frame[j][:B])
                 else:
                     batch["frame"] = ops.train_clip_gather(self.video, *tabs_a, T, S, self._frame[j][:B])
                 arrived = torch.cuda.Event()
@@ -363,6 +519,46 @@ class ResidentClips(_ClipLoader):
             batch["_slot"] = (self, j, arrived)
             self._out[j] = True
             yield batch
+
+
+def _two_parts(parts, frames_key, who):
+    """the `parts` argument of the joint loaders: two dicts, each with videos, classes, dataset_len and `frames_key`"""
+    parts = [dict(p) for p in parts]
+    if len(parts) != 2:
+        raise ValueError(f"{who}: the reference joins two datasets, got {len(parts)} parts")
+    for k, p in enumerate(parts):
+        missing = [key for key in ("videos", frames_key, "classes", "dataset_len") if key not in p]
+        if missing:
+            raise ValueError(f"{who}: part {k + 1} lacks {missing}")
+        p.setdefault("stride", 1)
+        p.setdefault("overlap", 1)
+        p.setdefault("require_events", False)
+        if int(p["stride"]) <= 0:
+            raise ValueError(f"{who}: part {k + 1}: stride must be positive")
+    return parts
+
+
+class JointResidentClips(ResidentClips):
+    """The reference's joint training DataLoader -- `ActionSpotDatasetJoint` over two `ActionSpotDataset`s, the `pretrain`
+    branch of `get_datasets` (dataset/datasets.py:60-94, dataset/frame.py:640-663) -- from videos that stay on the device.
+
+    parts: two dicts, [dict(videos=, frames=, classes=, stride=1, overlap=1, require_events=False, dataset_len=)]; the
+    first is the reference's dataset 1 (batch['dataset'] == 1), the second its dataset 2.  Each part has its own clip list
+    (`train_clip_table` with its stride / overlap / classes / require_events); clip_len, radi_displacement, mixup, pad_len
+    and the frame geometry are shared, as the reference collates the items of both into one tensor.  The other keyword
+    arguments are `ResidentClips`'.
+    Both parts live in the one packed buffer and one launch serves a whole batch: the gather, the gather-and-blend and the
+    label kernel take the batch's per-clip stride table (ops.train_clip_gather_ps / train_clip_gather_mix_ps /
+    clip_labels_ps).  The draws are `JointDraws(seed)`; a pass has dataset_len_1 + dataset_len_2 items.
+    Batches are `ResidentClips`' plus 'dataset', device int64 (B,) of 1 / 2.  The labels are each part's own class numbers
+    (`TDEEDModel.epoch()` shifts part 2's 'label' with `update_labels_2heads` and leaves 'label2' as it is, as the reference
+    does).  A validation loader is the same call with mixup=False."""
+
+    def __init__(self, parts, clip_len, radi_displacement=0, mixup=False, batch_size=8, seed=None, pad_len=DEFAULT_PAD_LEN,
+                 drop_last=False, max_resident_bytes=16 << 30, device="cuda", depth=3, chunk_bytes=64 << 20):
+        parts = _two_parts(parts, "frames", "JointResidentClips")
+        self._build(parts, True, clip_len, radi_displacement, mixup, batch_size, seed, pad_len, drop_last, max_resident_bytes,
+                    device, depth, chunk_bytes)
 
 
 # ------------------------------------------------------------------------------------------------- resident JPEG streams
@@ -489,6 +685,67 @@ def load_resident_jpegs(frame_dir, dataset, videos, pool=None, cache=None, shard
                          np.asarray(video_len, np.int64), names, w, h, samp, stride)
 
 
+def join_resident_jpegs(a, b):
+    """One packed set over two (`load_resident_jpegs` each), a's videos and frames in front of b's; pure host code.
+    The shards' streams are reused, not copied.  b's frame numbers are shifted by a's frames, and its table sets are
+    renumbered into the joined array: a set whose bytes a already has keeps a's number, the others follow a's (b's segment
+    tables and per-frame set columns are rewritten copies; a's shards are taken as they are, pointed at the joined array).
+    Geometry and sampling are those of the joined set's first supported frame.  Another width or height in the other
+    part raises ValueError.  With another chroma sampling, b's frames all take the existing route of a frame with
+    another sampling: they join the fallback, are decoded once on the host and stay decoded in the side buffer; their
+    shards are listed without segments.  The two sets must have been loaded with the same `stride`."""
+    from . import jpegdev
+    if a.stride != b.stride:
+        raise ValueError(f"join_resident_jpegs: the sets were loaded with strides {a.stride} and {b.stride}")
+    if a.width and b.width and (a.width, a.height) != (b.width, b.height):
+        raise ValueError(f"join_resident_jpegs: frames of {b.height}x{b.width} do not fit the set's {a.height}x{a.width}")
+    w, h, samp = (a.width, a.height, a.samp) if a.width else (b.width, b.height, b.samp)
+    other = bool(a.width and b.width and a.samp != b.samp)            # b: all through the side buffer
+    na = a.n_frames
+    rows = [r for r in a.table_sets]
+    seen = {r.tobytes(): i for i, r in enumerate(rows)}
+    remap = np.zeros(max(b.n_sets, 1), np.int32)
+    for i in range(0 if other else b.n_sets):
+        key = b.table_sets[i].tobytes()
+        if key not in seen:
+            seen[key] = len(rows)
+            rows.append(b.table_sets[i])
+        remap[i] = seen[key]
+    table_sets = np.stack(rows) if rows else np.zeros((0, jpegdev.TABLE_SET_BYTES), np.uint8)
+    shards = []
+    for s in a.shards:
+        s.packed.table_sets = table_sets                    # a's numbers are the joined array's first rows
+        shards.append(s)
+    for s in b.shards:
+        p = s.packed
+        n = len(s.frames)
+        if other:
+            none = np.zeros(jpegdev.GUARD, np.uint8)
+            packed = jpegdev.PackedJpegs(0, 0, 0, n, none, none, np.zeros((0, jpegdev.SEG_COLS), np.int32), table_sets,
+                                         np.full(n, -1, np.int32), list(range(n)))
+        else:
+            seg = p.segments.copy()
+            if seg.shape[0]:
+                seg[:, 5] = remap[seg[:, 5]]
+            fs = p.frame_set.copy()
+            fs[fs >= 0] = remap[fs[fs >= 0]]
+            packed = jpegdev.PackedJpegs(p.width, p.height, p.samp, p.n_frames, p.stream, p.stream_np, seg, table_sets, fs,
+                                         list(p.fallback))
+        shards.append(SimpleNamespace(packed=packed, frames=np.asarray(s.frames, np.int64) + na))
+    fs_b = np.asarray(b.frame_set, np.int32).copy()
+    if other:
+        fs_b[:] = -1
+        fall_b = list(range(b.n_frames))
+    else:
+        fs_b[fs_b >= 0] = remap[fs_b[fs_b >= 0]]
+        fall_b = [int(f) for f in b.fallback]
+    return ResidentJpegs(shards, table_sets, np.concatenate([np.asarray(a.frame_set, np.int32), fs_b]),
+                         sorted([int(f) for f in a.fallback] + [f + na for f in fall_b]),
+                         np.concatenate([np.asarray(a.video_first, np.int64), np.asarray(b.video_first, np.int64) + na]),
+                         np.concatenate([np.asarray(a.video_len, np.int64), np.asarray(b.video_len, np.int64)]),
+                         list(a.names) + list(b.names), w, h, samp, a.stride)
+
+
 def _cut_waves(keys):
     """(first, count <= 64) rows over a sorted key column: no row spans two keys"""
     n = keys.size
@@ -510,7 +767,8 @@ def batch_tables(rows, clip_len, stride, frame_set, side_row, piece_lo, piece_n,
     first + base + t * stride of clip k, or zeros where base + t * stride falls outside the video (the window rule of
     ops.train_clip_gather).  frame_set / side_row / piece_lo / piece_n: per frame of the set its table set (-1: not decoded
     on the device), its row in the side buffer of decoded frames (-1: none), its first row in the piece table and its
-    number of pieces.  chunk_slots: slots per coefficient chunk (default: all in one).  piece_keep: bool per row of the
+    number of pieces.  stride: one for all clips, or one per clip (a joint batch; with mixup the partners' follow the
+    clips', as the rows do).  chunk_slots: slots per coefficient chunk (default: all in one).  piece_keep: bool per row of the
     piece table, False leaves the piece out of the items (`video_tables`' MCU-row filter); default: every piece.
     -> namespace(n_slots,
          slot_set int32 (n_slots,): table set of every slot the device decodes, -1 for the others (padding, side, unused);
@@ -523,7 +781,7 @@ def batch_tables(rows, clip_len, stride, frame_set, side_row, piece_lo, piece_n,
     n = first.size
     at = np.arange(n, dtype=np.int64) * T if clip_slot is None else np.asarray(clip_slot, np.int64)
     total = int(n_slots) if n_slots is not None else n * T
-    f = base[:, None] + np.arange(T, dtype=np.int64)[None, :] * int(stride)
+    f = base[:, None] + np.arange(T, dtype=np.int64)[None, :] * _strides_of(stride, n, "batch_tables")[:, None]
     real = ((f >= 0) & (f < nfr[:, None])).reshape(-1)
     g = np.where(real, (first[:, None] + f).reshape(-1), 0)
     slots = (at[:, None] + np.arange(T, dtype=np.int64)[None, :]).reshape(-1)
@@ -630,10 +888,11 @@ def _shard_first(ext):
 
 def _clip_ranges(ext, rows, clip_len, stride):
     """The byte ranges the clips `rows` need, one per clip and shard: every frame from the clip's first sampled frame that
-    exists to its last, the frames a stride skips included, so that a clip is one contiguous copy per shard.
+    exists to its last, the frames a stride skips included, so that a clip is one contiguous copy per shard.  stride: one for
+    all clips, or one per clip.
     -> (clip int64, shard int64, lo16 int64 -- the first byte rounded down to 16 --, hi int64), sorted by clip, then shard."""
     first, base, nfr = (np.asarray(rows[i], np.int64) for i in range(3))
-    T, S = int(clip_len), int(stride)
+    T, S = int(clip_len), _strides_of(stride, first.size, "_clip_ranges")      # S: one stride per clip
     a = base + np.where(base < 0, (-base + S - 1) // S, 0) * S                 # the first and the last sampled frame that exist
     b = base + np.minimum(T - 1, (nfr - 1 - base) // S) * S
     live = np.flatnonzero(a <= b)
@@ -661,6 +920,7 @@ def stream_plan(ext, video_first, video_len, rows, clip_len, stride, operands, b
     """Which videos of a set stay resident when the set is streamed (pure numpy; no file, no device).
     ext: `frame_extents`; video_first / video_len: the videos' frames in the set-wide numbering, in set order; rows: int64
     (4, n_clips) -- per clip the first frame of its video, its base, the video's length and the video (`_ClipLoader._rows`);
+    stride: one for all clips, or one per clip (a joint set: `_ClipLoader._clip_stride`);
     operands: clips per batch item (2 with mixup); fixed_bytes: what is resident whatever the plan -- segment and piece
     tables, table sets, side buffer.
     One staging region holds a batch: operands x batch_size x the largest sum of byte ranges (`_clip_ranges`, rounded out
@@ -722,7 +982,7 @@ def stream_plan(ext, video_first, video_len, rows, clip_len, stride, operands, b
 
 def stage_batch(plan, ext, rows, clip_len, stride, region_off, n_slots=None, clip_slot=None):
     """The copies and the relocation rows of one batch of a streamed set (pure numpy; no file, no device).
-    rows / clip_slot / n_slots: as `batch_tables` (rows with the video in row 3); region_off: where the batch's staging
+    rows / clip_slot / n_slots / stride: as `batch_tables` (rows with the video in row 3); region_off: where the batch's staging
     region starts in the device buffer (plan.stage_lo + ring entry * plan.region_bytes).
     -> (copies [(shard, host byte lo, host byte hi, device offset)]: one per clip of a streamed video and shard it touches,
           packed into the region one behind the other, each at a 16-byte boundary and starting at a host byte that is a
@@ -732,9 +992,10 @@ def stage_batch(plan, ext, rows, clip_len, stride, region_off, n_slots=None, cli
           offset (a multiple of 16), the window is the copy.  Every other slot -- padding, a resident video's -- gets delta
           0 and the resident window [0, plan.stream_bytes).)
     ValueError when the ranges exceed plan.region_bytes."""
-    T, S = int(clip_len), int(stride)
+    T = int(clip_len)
     first, base, nfr, vid = (np.asarray(rows[i], np.int64) for i in range(4))
     n = first.size
+    S = _strides_of(stride, n, "stage_batch")                                  # one stride per clip
     at = np.arange(n, dtype=np.int64) * T if clip_slot is None else np.asarray(clip_slot, np.int64)
     total = int(n_slots) if n_slots is not None else n * T
     reloc = np.zeros((total, 3), np.int64)
@@ -743,7 +1004,7 @@ def stage_batch(plan, ext, rows, clip_len, stride, region_off, n_slots=None, cli
     copies = []
     if streamed.size == 0:
         return copies, reloc
-    clip, shard, lo16, hi = _clip_ranges(ext, [r[streamed] for r in (first, base, nfr)], T, S)
+    clip, shard, lo16, hi = _clip_ranges(ext, [r[streamed] for r in (first, base, nfr)], T, S[streamed])
     size = _round16(hi) - lo16
     dev = int(region_off) + np.concatenate([[0], np.cumsum(size)])[:-1]
     if int(size.sum()) > plan.region_bytes:
@@ -752,7 +1013,7 @@ def stage_batch(plan, ext, rows, clip_len, stride, region_off, n_slots=None, cli
     fshard = np.asarray(ext.shard, np.int64)
     for c, s, l, h, d in zip(clip, shard, lo16, hi, dev):
         k = streamed[c]
-        f = base[k] + np.arange(T, dtype=np.int64) * S
+        f = base[k] + np.arange(T, dtype=np.int64) * S[k]
         real = (f >= 0) & (f < nfr[k])
         g = np.where(real, first[k] + f, 0)
         on = real & (fshard[g] == s) & (np.asarray(ext.hi)[g] > np.asarray(ext.lo)[g])
@@ -1044,24 +1305,37 @@ class ResidentJpegClips(_ClipLoader):
                  dataset_len=1, batch_size=8, seed=None, pad_len=DEFAULT_PAD_LEN, require_events=False, drop_last=False,
                  max_resident_bytes=16 << 30, device="cuda", depth=3, chunk_bytes=64 << 20, split_mcus=None,
                  max_coeff_bytes=512 << 20, stream_clips=False):
+        part = dict(videos=videos, classes=classes, stride=stride, overlap=overlap, require_events=require_events,
+                    dataset_len=dataset_len)
+        self._build([part], False, jpegs, clip_len, radi_displacement, mixup, batch_size, seed, pad_len, drop_last,
+                    max_resident_bytes, device, depth, chunk_bytes, split_mcus, max_coeff_bytes, stream_clips)
+
+    def _build(self, parts, joint, jpegs, clip_len, radi_displacement, mixup, batch_size, seed, pad_len, drop_last,
+               max_resident_bytes, device, depth, chunk_bytes, split_mcus, max_coeff_bytes, stream_clips):
+        """The constructor over parts (`_ClipLoader._init_parts`); jpegs: the one packed set that holds the videos of all
+        parts, in order (`join_resident_jpegs`)."""
         import torch
         from . import ops
         from .streams import new_stream
+        who = type(self).__name__
         if radi_displacement < 0:
             raise ValueError("radi_displacement must not be negative")
-        if not videos or len(videos) != len(jpegs.video_len):
-            raise ValueError(f"ResidentJpegClips: {len(videos)} videos, {len(jpegs.video_len)} in the packed set")
+        videos = [v for p in parts for v in p["videos"]]
+        if not videos or any(not p["videos"] for p in parts) or len(videos) != len(jpegs.video_len):
+            raise ValueError(f"{who}: {len(videos)} videos, {len(jpegs.video_len)} in the packed set")
         for v, n in zip(videos, jpegs.video_len):
             if int(v["num_frames"]) != int(n):
-                raise ValueError(f"ResidentJpegClips: video {v['video']} has {int(v['num_frames'])} frames, the packed set {int(n)}")
-        rs = _ResidentStreams("ResidentJpegClips", jpegs, split_mcus, max_resident_bytes, streamed=stream_clips)
+                raise ValueError(f"{who}: video {v['video']} has {int(v['num_frames'])} frames, the packed set {int(n)}")
+        rs = _ResidentStreams(who, jpegs, split_mcus, max_resident_bytes, streamed=stream_clips)
         n_frames, n_seg, H, W, samp = jpegs.n_frames, rs.n_seg, rs.H, rs.W, rs.samp
-        self._init_clips(videos, [int(n) for n in jpegs.video_len], classes, clip_len, stride, overlap, radi_displacement, mixup,
-                         dataset_len, batch_size, seed, pad_len, require_events, drop_last, device, depth)
+        self._init_parts(parts, [int(n) for n in jpegs.video_len], clip_len, radi_displacement, mixup, batch_size, seed, pad_len,
+                         drop_last, device, depth, joint)
+        self._who = who
         self.shape, self.samp, self.split_mcus = (3, H, W), samp, rs.split
         self._plan = self._ext = self._copy_stream = None
         if stream_clips:
-            self._plan = rs.plan_streaming(self._rows, self.clip_len, self.stride, 2 if self.mixup else 1, int(batch_size), self.depth)
+            self._plan = rs.plan_streaming(self._rows, self.clip_len, self._clip_stride if joint else self.stride,
+                                           2 if self.mixup else 1, int(batch_size), self.depth)
             self._ext = rs.ext
         dev = torch.device(device)
         self.stream = new_stream(device)
@@ -1080,13 +1354,13 @@ class ResidentJpegClips(_ClipLoader):
             B, T, nops = int(batch_size), self.clip_len, 2 if self.mixup else 1
             self._cap = cap = nops * B * T
             if cap > 65535:
-                raise ValueError(f"ResidentJpegClips: {nops} x {B} clips of {T} frames exceed the kernels' 65535 frame slots")
+                raise ValueError(f"{who}: {nops} x {B} clips of {T} frames exceed the kernels' 65535 frame slots")
             self._fc = fc = ops.jpeg_frame_coeffs(W, H, samp)
             self._chunk = min(cap, max(1, int(max_coeff_bytes) // (2 * fc)))
             max_pieces = int(self._piece_n.max()) if n_frames else 0
             cap_items = max(cap * max_pieces, 1)
             cap_waves = cap_items // 64 + max(jpegs.n_sets, 1) * -(-cap // self._chunk) + 1
-            sizes = [4 * nops * B * 8, cap * 4, cap * 4, cap_items * 8, cap_waves * 8] + ([cap * 24] if stream_clips else [])
+            sizes = [self._nrows * B * 8, cap * 4, cap * 4, cap_items * 8, cap_waves * 8] + ([cap * 24] if stream_clips else [])
             self._offs = np.concatenate([[0], np.cumsum([(s + 15) & ~15 for s in sizes])]).astype(np.int64)
             nbytes = int(self._offs[-1])
             self._host = [torch.zeros(nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.depth)]
@@ -1112,28 +1386,29 @@ class ResidentJpegClips(_ClipLoader):
         self.stats = rs.stats()
 
     def _views(self, block, B, np_side):
-        """(rows int64 (4 * operands, B), slot_set, fill, items (cap, 2), waves (cap, 2)) of a ring block"""
+        """(rows int64 (4 * operands, B) -- two more for a joint loader --, slot_set, fill, items (cap, 2), waves (cap, 2)) of a
+        ring block"""
         o = self._offs
-        nops = 2 if self.mixup else 1
+        nr = self._nrows
         cap_items, cap_waves = self._caps
         if np_side:
             part = lambda i, dt: block[o[i]:o[i + 1]].view(dt)                                   # noqa: E731
-            return (part(0, np.int64)[:4 * nops * B].reshape(4 * nops, B), part(1, np.int32)[:self._cap],
+            return (part(0, np.int64)[:nr * B].reshape(nr, B), part(1, np.int32)[:self._cap],
                     part(2, np.int32)[:self._cap], part(3, np.int32)[:2 * cap_items].reshape(cap_items, 2),
                     part(4, np.int32)[:2 * cap_waves].reshape(cap_waves, 2))
         import torch
         part = lambda i, dt: block[int(o[i]):int(o[i + 1])].view(dt)                              # noqa: E731
-        return (part(0, torch.int64)[:4 * nops * B].view(4 * nops, B), part(1, torch.int32)[:self._cap],
+        return (part(0, torch.int64)[:nr * B].view(nr, B), part(1, torch.int32)[:self._cap],
                 part(2, torch.int32)[:self._cap], part(3, torch.int32)[:2 * cap_items].view(cap_items, 2),
                 part(4, torch.int32)[:2 * cap_waves].view(cap_waves, 2))
 
-    def _stage(self, j, rows, at):
+    def _stage(self, j, rows, at, strides):
         """Streamed sets: the relocation rows of the batch into entry j's page-locked block, and its range copies from the
         host shards into the entry's staging region on the copy stream, behind the last items launch that read the region.
         -> True when anything was copied (the loader's stream then waits for self._staged[j])."""
         import torch
         plan = self._plan
-        copies, reloc = stage_batch(plan, self._ext, rows, self.clip_len, self.stride, plan.stage_lo + j * plan.region_bytes,
+        copies, reloc = stage_batch(plan, self._ext, rows, self.clip_len, strides, plan.stage_lo + j * plan.region_bytes,
                                     n_slots=self._cap, clip_slot=at)
         o = self._offs
         self._host_np[j][o[5]:o[5] + self._cap * 24].view(np.int64).reshape(self._cap, 3)[:] = reloc
@@ -1159,23 +1434,29 @@ class ResidentJpegClips(_ClipLoader):
         Bcap = self.draws.batch_size
         _, H, W = self.shape
         self._pass += 1
-        for ia, ib in self.draws:
+        for draw in self.draws:
+            ia, ib, part = self._drawn(draw)
             j = self._next_slot()
             B = len(ia)
             h_rows, h_set, h_fill, h_items, h_waves = self._views(self._host_np[j], Bcap, True)
             h_rows[0:4, :B] = self._rows[:, ia]
             rows = self._rows[:, ia]
             at = np.arange(B, dtype=np.int64) * T
+            if part is not None:                                # a joint batch: every clip at the stride of its part
+                self._joint_rows(h_rows, ia, part)
+                S = self._clip_stride[ia]
             if ib is not None:
                 h_rows[4:8, :B] = self._rows[:, ib]
                 rows = np.concatenate([rows, self._rows[:, ib]], 1)
                 at = np.concatenate([at, (Bcap + np.arange(B, dtype=np.int64)) * T])
+                if part is not None:
+                    S = np.concatenate([S, S])                  # the partner comes from the same part
             tb = batch_tables(rows, T, S, self._frame_set, self._side_row, self._piece_lo, self._piece_n, n_slots=self._cap,
                               clip_slot=at, chunk_slots=self._chunk)
             h_set[:], h_fill[:] = tb.slot_set, tb.fill
             h_items[:tb.items.shape[0]] = tb.items
             h_waves[:tb.waves.shape[0]] = tb.waves
-            staged = self._plan is not None and self._stage(j, rows, at)
+            staged = self._plan is not None and self._stage(j, rows, at, S)
             slot, lab = self._slots[j], self._labels[j]
             with torch.cuda.stream(self.stream):
                 if self._consumed[j] is not None:
@@ -1186,7 +1467,10 @@ class ResidentJpegClips(_ClipLoader):
                 self._copied[j] = ev
                 d_rows, d_set, d_fill, d_items, d_waves = self._views(self._dev[j], Bcap, False)
                 batch = {}
-                self._label_launches(d_rows, lab, B, batch)
+                strides = None
+                if part is not None:
+                    strides, batch["dataset"] = self._joint_views(d_rows, B)
+                self._label_launches(d_rows, lab, B, batch, strides)
                 d_reloc = None
                 if self._plan is not None:
                     o = self._offs
@@ -1224,5 +1508,27 @@ class ResidentJpegClips(_ClipLoader):
         word = int(self._err_host[0])
         if word:
             codes = [c for c in range(1, 8) if word >> c & 1]
-            raise RuntimeError(f"ResidentJpegClips: pass {self._pass} met decode errors on the device (status codes {codes}); "
+            raise RuntimeError(f"{self._who}: pass {self._pass} met decode errors on the device (status codes {codes}); "
                                "the resident streams or tables are damaged")
+
+
+class JointResidentJpegClips(ResidentJpegClips):
+    """`JointResidentClips` over parts that stay on the device compressed: parts as there, with `jpegs`
+    (`load_resident_jpegs` of the part's videos) in place of `frames`.  The two packed sets are joined into one
+    (`join_resident_jpegs`: streams reused, table sets renumbered, a part 2 of another chroma sampling through the side
+    buffer, another width or height ValueError), so one items launch and one pixel pass decode the clips of both parts;
+    `batch_tables` -- and, with stream_clips=True, `stream_plan` / `stage_batch` -- take the batch's per-clip strides.  The
+    other keyword arguments are `ResidentJpegClips`'.  Everything a consumer sees equals `JointResidentClips` fed the decoded
+    frames, bit for bit."""
+
+    def __init__(self, parts, clip_len, radi_displacement=0, mixup=False, batch_size=8, seed=None, pad_len=DEFAULT_PAD_LEN,
+                 drop_last=False, max_resident_bytes=16 << 30, device="cuda", depth=3, chunk_bytes=64 << 20, split_mcus=None,
+                 max_coeff_bytes=512 << 20, stream_clips=False):
+        parts = _two_parts(parts, "jpegs", "JointResidentJpegClips")
+        for k, p in enumerate(parts):
+            if len(p["videos"]) != len(p["jpegs"].video_len):
+                raise ValueError(f"JointResidentJpegClips: part {k + 1} lists {len(p['videos'])} videos, its packed set "
+                                 f"{len(p['jpegs'].video_len)}")
+        jpegs = join_resident_jpegs(parts[0]["jpegs"], parts[1]["jpegs"])
+        self._build(parts, True, jpegs, clip_len, radi_displacement, mixup, batch_size, seed, pad_len, drop_last,
+                    max_resident_bytes, device, depth, chunk_bytes, split_mcus, max_coeff_bytes, stream_clips)

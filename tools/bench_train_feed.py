@@ -9,6 +9,9 @@
     python tools/bench_train_feed.py --resident-jpeg --stream-clips 0.5 min [same options]
                                                                          the same loader over a set larger than its budget
                                                                          (streamed_jpeg_main), profiles/train_feed_streamed_jpeg.json
+    python tools/bench_train_feed.py --joint [same options]              the joint loader over two parts against the single-set
+                                                                         loader over the same frames and the host-decoded joint
+                                                                         feed (joint_main), profiles/train_feed_joint.json
 
 Synthetic JPEG videos (224 x 224, quality 90) are written to a temporary directory with a label file.  Measured:
   loader   clips/s of `trainclips.ResidentClips` alone (T = 100, batch 8), without mixup (the uint8 batch) and with it (labels
@@ -462,6 +465,157 @@ def streamed_jpeg_main(a):
     return 0
 
 
+CLASSES2 = {"d": 1, "c": 2, "b": 3, "a": 4, "e": 5, "f": 6}          # the second part's own class list (and head)
+
+
+def joint_decoded_loader(root, parts, pool, mixup, batch_size, seed):
+    """The reference's joint route on `JointDraws`' draws: every drawn clip decoded from its JPEGs at the stride of its part
+    (`feeder.load_paths` -> `feeder.clip_batches`), two clips per item with mixup; labels from the host rule, 'dataset' per
+    item -- the batches `trainclips.JointResidentJpegClips` delivers."""
+    T, r = CFG["clip_len"], CFG["radi_displacement"]
+    tab = TC.join_clip_tables([TC.train_clip_table(p["videos"], p["classes"], T, p["stride"], p["overlap"]) for p in parts])
+    videos = [v for p in parts for v in p["videos"]]
+    per_clip = np.repeat([p["stride"] for p in parts], np.diff(tab.part_clips))
+    draws = [(part, tab.part_clips[part - 1] + ia, None if ib is None else tab.part_clips[part - 1] + ib)
+             for part, ia, ib in TC.JointDraws(np.diff(tab.part_clips), [p["dataset_len"] for p in parts], batch_size, mixup, seed,
+                                               drop_last=True)]
+
+    def descr(ids):
+        return [dict(paths=feeder.load_paths(root, DATASET, videos[int(tab.clip_video[c])]["video"], int(tab.clip_base[c]),
+                                             int(tab.clip_base[c]) + T * int(per_clip[c]), stride=int(per_clip[c])),
+                     stride=int(per_clip[c])) for c in ids]
+    streams = [feeder.clip_batches(descr(np.concatenate([d[1 + k] for d in draws])), batch_size, (3, H, W), T, pool=pool, depth=3 + k)
+               for k in range(2 if mixup else 1)]
+    for (part, ia, ib), *got in zip(draws, *streams):
+        lab, labD = TC.rasterise_labels(tab, ia, T, per_clip[ia], r)
+        b = dict(frame=got[0]["frame"], _src=got[0]["_src"], label=torch.from_numpy(lab), labelD=torch.from_numpy(labD),
+                 dataset=torch.from_numpy(part))
+        if mixup:
+            lab2, labD2 = TC.rasterise_labels(tab, ib, T, per_clip[ib], r)
+            b.update(frame2=got[1]["frame"], label2=torch.from_numpy(lab2), labelD2=torch.from_numpy(labD2))
+        yield b
+
+
+def joint_main(a):
+    """--joint: `trainclips.JointResidentJpegClips` over two parts of equal size (the first and the second half of the tool's
+    noise-frame videos, strides --joint-strides, two class lists) against (b) `trainclips.ResidentJpegClips` over the same
+    frames as ONE set at the first part's stride -- the single-set code, the yardstick for what the per-clip tables cost --
+    and (c) `feeder.clip_batches` + ProcessDecodePool producing the same joint batches; in one run, the routes alternating, a
+    warm-up round then --repeats timed ones: the loader alone (plain clips), then a 200MF two-head mixup epoch on (a) and
+    (c).  One JSON record, printed and written to profiles/train_feed_joint.json.  No threshold: `faster` says for every pair
+    of routes whether the slowest round of one beat the fastest round of the other."""
+    from tdeed_amd import jpegdev
+    from tdeed_amd.model import TDEEDModel
+    from types import SimpleNamespace
+    T, r, bs = CFG["clip_len"], CFG["radi_displacement"], a.batch
+    if a.videos < 2 or a.videos % 2:
+        raise SystemExit("--joint: --videos must be even, two parts of equal size")
+    root = tempfile.mkdtemp(prefix="tdeed_train_feed_")
+    out = dict(kind="train_feed_joint", cfg=CFG, videos=a.videos, frames_per_video=a.frames, clips_per_epoch=a.clips,
+               batch_size=bs, decode_processes=a.procs, repeats=a.repeats, strides=list(a.joint_strides),
+               device=torch.cuda.get_device_name(0), measured_on_gpu=True)
+    pool = None
+    try:
+        videos = write_videos(root, a.videos, a.frames)
+        half = a.videos // 2
+        threads = feeder.DecodePool(a.procs)
+        cache = jpegdev.ParseCache()
+        halves = [videos[:half], videos[half:]]
+        packs = [TC.load_resident_jpegs(root, DATASET, vs, pool=threads, cache=cache) for vs in halves]
+        whole = TC.load_resident_jpegs(root, DATASET, videos, pool=threads, cache=cache)
+        threads.close()
+        lens = [a.clips - a.clips // 2, a.clips // 2]
+        parts = [dict(videos=vs, classes=cl, stride=int(s), overlap=1, dataset_len=n)
+                 for vs, cl, s, n in zip(halves, (CLASSES, CLASSES2), a.joint_strides, lens)]
+        common = dict(clip_len=T, radi_displacement=r, batch_size=bs, drop_last=True, device="cuda", seed=1)
+        n_epoch = a.clips // bs * bs
+
+        def build(mixup):
+            joint = TC.JointResidentJpegClips([dict(p, jpegs=j) for p, j in zip(parts, packs)], mixup=mixup, **common)
+            single = TC.ResidentJpegClips(videos, whole, CLASSES, stride=int(a.joint_strides[0]), mixup=mixup, dataset_len=a.clips,
+                                          **common)
+            torch.cuda.synchronize()
+            return joint, single
+
+        def drain(loader):
+            for _ in feeder.prefetch(loader, "cuda"):
+                pass
+
+        def reseeded(ld, seed):
+            ld.reseed(seed)
+            return ld
+
+        def faster(res):
+            names = list(res)
+            return {f"{x}_over_{y}": bool(res[x]["clips_per_s_min"] > res[y]["clips_per_s_max"]) for x in names for y in names if x != y}
+
+        def run(routes, first_seed, step):
+            times, last = {k: [] for k in routes}, {}
+            for rep in range(a.repeats + 1):
+                for k, mk in routes.items():                                   # alternating; the first round warms up
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    last[k] = step(mk(first_seed + rep))
+                    torch.cuda.synchronize()
+                    if rep:
+                        times[k].append(time.perf_counter() - t0)
+            return {k: dict(_rate(v, n_epoch), rounds_s=[round(x, 4) for x in v]) for k, v in times.items()}, last
+
+        # ---- the loader alone, plain clips; every round draws new clips
+        joint, single = build(False)
+        out["set"] = dict(joint={k: joint.stats[k] for k in ("frames", "device_frames", "table_sets", "shards", "resident_bytes")},
+                          single={k: single.stats[k] for k in ("frames", "device_frames", "table_sets", "shards", "resident_bytes")})
+        pool = feeder.ProcessDecodePool(a.procs)
+        routes = dict(a_joint_resident_jpeg=lambda seed: reseeded(joint, seed),
+                      b_single_resident_jpeg=lambda seed: reseeded(single, seed),
+                      c_joint_host_decoded=lambda seed: joint_decoded_loader(root, parts, pool, False, bs, seed))
+        out["loader"], _ = run(routes, 10, drain)
+        res = {k: out["loader"][k] for k in routes}
+        out["loader"]["ratio"] = dict(a_over_b=round(res["a_joint_resident_jpeg"]["clips_per_s"] /
+                                                     res["b_single_resident_jpeg"]["clips_per_s"], 3),
+                                      a_over_c=round(res["a_joint_resident_jpeg"]["clips_per_s"] /
+                                                     res["c_joint_host_decoded"]["clips_per_s"], 3))
+        out["loader"]["faster"] = faster(res)
+        del joint, single
+
+        # ---- a two-head training epoch with mixup fed by (a) and by (c)
+        joint, single = build(True)
+        del single
+        m = TDEEDModel(device="cuda", args=SimpleNamespace(modality="rgb", temporal_arch="ed_sgp_mixer", pretrain=None, **CFG))
+        m.load({k: torch.from_numpy(v) for k, v in synth.make_state(state_layout.model_state_shapes(CFG), 0).items()})
+        heads = [len(CLASSES) + 1, len(CLASSES2) + 1]
+        m._model.update_pred_head(heads)
+        m._num_classes = sum(heads)                                             # train_tdeed.py:147-148
+        opt, _ = m.get_optimizer({"lr": 1e-4})
+        routes = dict(a_joint_resident_jpeg=lambda seed: reseeded(joint, seed),
+                      c_joint_host_decoded=lambda seed: joint_decoded_loader(root, parts, pool, True, bs, seed))
+        out["epoch"], losses = run(routes, 2, lambda ld: m.epoch(ld, optimizer=opt))
+        res = {k: out["epoch"][k] for k in routes}
+        for k, v in losses.items():
+            out["epoch"][k]["last_loss"] = round(float(v), 5)
+        out["epoch"]["ratio"] = dict(a_over_c=round(res["a_joint_resident_jpeg"]["clips_per_s"] /
+                                                    res["c_joint_host_decoded"]["clips_per_s"], 3))
+        out["epoch"]["faster"] = faster(res)
+        out["notes"] = [
+            "the JPEG files stay in the page cache on the host route: decode is measured, not disk",
+            "a: JointResidentJpegClips over two parts (half of the videos each); b: ResidentJpegClips over all of them as one set, "
+            "the single-set code with its scalar stride; c: clip_batches + decode processes on the joint draws",
+            "loader: plain clips, drained through feeder.prefetch; construction is not in the rounds",
+            "epoch: update_pred_head([5, 7]), mixup as train_tdeed.py trains; the host route uploads 'frame2' by epoch()'s blocking copy",
+            "faster[x_over_y] is true only where x's slowest round beat y's fastest"]
+    finally:
+        if pool is not None:
+            pool.close()
+        shutil.rmtree(root, ignore_errors=True)
+    line = json.dumps(out)
+    print(line)
+    path = a.out if a.out else os.path.join(ROOT, "profiles", "train_feed_joint.json")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as fh:
+        fh.write(line + "\n")
+    return 0
+
+
 def _rate(times, clips):
     t = np.asarray(times)
     return dict(clips_per_s=round(clips / float(np.median(t)), 1), clips_per_s_min=round(clips / float(t.max()), 1),
@@ -485,6 +639,10 @@ def main():
                     help="with --resident-jpeg: measure ResidentJpegClips(stream_clips=True) at these fractions of the all-resident "
                          "bytes ('min': the smallest budget) against the all-resident loader and the host-decoded feed "
                          "(profiles/train_feed_streamed_jpeg.json)")
+    ap.add_argument("--joint", action="store_true",
+                    help="measure trainclips.JointResidentJpegClips against ResidentJpegClips over the same frames and the "
+                         "host-decoded joint feed instead (profiles/train_feed_joint.json)")
+    ap.add_argument("--joint-strides", nargs=2, type=int, default=[1, 1], metavar="STRIDE", help="--joint: the two parts' strides")
     ap.add_argument("--shard-mib", type=int, default=16, help="--stream-clips: shard_bytes of load_resident_jpegs, in MiB")
     ap.add_argument("--read-threads", type=int, default=0,
                     help="--decode-device: threads that read the files (0: the feed's own thread; the files sit in the page cache, "
@@ -493,6 +651,8 @@ def main():
     a = ap.parse_args()
     if a.decode_device:
         return decode_device_main(a)
+    if a.joint:
+        return joint_main(a)
     if a.resident_jpeg and a.stream_clips:
         return streamed_jpeg_main(a)
     if a.resident_jpeg:

@@ -539,6 +539,126 @@ def train_clips(name="train_clips"):
     save(name, dict(kind="train_clips", classes=classes, videos=videos, names=names, n_items=n_items, cases=cases), **arrays)
 
 
+def train_clips_joint(name="train_clips_joint"):
+    """The reference's JOINT training dataset (dataset/frame.py:640-663 ActionSpotDatasetJoint over two ActionSpotDataset,
+    store_mode='store' -- the `pretrain` branch of get_datasets) on two temporary label files and frame directories of 8 x 8
+    JPEGs.  Two class lists, dataset names other than soccernet / soccernetball, the events with the hard cases of
+    `train_clips`.  Per case (the parts' stride / overlap pairs (1, 1 | 2, 0.5), (2, 0.9 | 2, 0.5) -- at clip_len 40, where
+    int((1 - 0.9) * 40) truncates to a step of 3 --, (12, 1 | 1, 1), and two without mixup): each part's clip list and, after
+    `random.seed(s)`, of the first 24 items the part, the clip index inside the part and the partner's -- the arguments and
+    results of the reference's own `random.randint` calls, recorded while it draws -- and the label / labelD / label2 /
+    labelD2 rows; for case 0 the `frame` / `frame2` arrays too.  The decoded frames of every video are stored as the
+    reference's reader returns them, so that a test can rebuild any clip.  Asserts per case that both parts occur and that
+    a recorded clip hangs over the end of its video."""
+    import random
+    import tempfile
+    from PIL import Image
+    import dataset.frame as rframe
+    ev = lambda *pairs: [dict(frame=f, label=l) for f, l in pairs]     # noqa: E731
+    parts = [
+        dict(dataset="fs_comp", classes={"dive": 1, "turn": 2, "land": 3}, videos=[
+            dict(video="v00003", num_frames=3, events=ev((1, "dive"))),
+            dict(video="v00007", num_frames=7, events=ev((3, "land"), (4, "dive"))),
+            dict(video="v00037", num_frames=37, events=ev((0, "dive"), (1, "turn"), (17, "land"), (19, "dive"), (35, "land"),
+                                                          (36, "turn"))),
+            dict(video="v00101", num_frames=101, events=ev((2, "turn"), (53, "land"), (50, "dive"), (99, "dive"), (100, "turn"))),
+        ]),
+        dict(dataset="fs_perf", classes={"jump": 1, "spin": 2, "step": 3, "fall": 4, "bow": 5}, videos=[
+            dict(video="w00006", num_frames=6, events=ev((0, "spin"), (5, "fall"))),
+            dict(video="w00020", num_frames=20, events=ev((9, "step"), (8, "jump"), (19, "bow"))),
+            dict(video="w00064", num_frames=64, events=ev((1, "fall"), (7, "jump"), (30, "spin"), (33, "step"), (31, "bow"),
+                                                          (62, "bow"), (63, "jump"))),
+        ]),
+    ]
+    settings = [  # (clip_len, (stride, overlap) of part 1, of part 2, radi_displacement, mixup, seed)
+        (8, (1, 1), (2, 0.5), 2, True, 41), (40, (2, 0.9), (2, 0.5), 2, True, 42), (8, (12, 1), (1, 1), 1, True, 43),
+        (8, (1, 1), (2, 0.5), 0, False, 44), (8, (3, 0.5), (2, 1), 2, False, 45),
+    ]
+    n_items = 24
+    arrays, cases = {}, []
+    with tempfile.TemporaryDirectory() as tmp:
+        for k, p in enumerate(parts):
+            fdir = os.path.join(tmp, f"frames{k}")
+            reader = rframe.FrameReader(fdir, "rgb", p["dataset"])
+            for vi, v in enumerate(p["videos"]):
+                d = os.path.join(fdir, v["video"])
+                os.makedirs(d)
+                for i in range(v["num_frames"]):
+                    Image.fromarray(synth.uint8_clip(900 + 1000 * k + 37 * vi + i, (8, 8, 3))).save(os.path.join(d, f"frame{i}.jpg"),
+                                                                                                     quality=90)
+                arrays[f"video__p{k}__{vi}"] = np.stack([reader.read_frame(os.path.join(d, f"frame{i}.jpg")).numpy()
+                                                         for i in range(v["num_frames"])]).astype(np.uint8)
+            p["label_file"] = os.path.join(tmp, f"train{k}.json")
+            with open(p["label_file"], "w") as fh:
+                json.dump(p["videos"], fh)
+        for ci, (clip_len, sp1, sp2, radi, mixup, seed) in enumerate(settings):
+            dsets = []
+            for k, (p, (stride, overlap)) in enumerate(zip(parts, (sp1, sp2))):
+                d = rframe.ActionSpotDataset(p["classes"], p["label_file"], os.path.join(tmp, f"frames{k}"),
+                                             os.path.join(tmp, f"store{ci}_{k}"), "store", "rgb", clip_len, n_items // 2, stride=stride,
+                                             overlap=overlap, radi_displacement=radi, mixup=mixup, dataset=p["dataset"])
+                kept_video, kept_base, n = [], [], 0
+                for vi, v in enumerate(p["videos"]):
+                    for base_idx in range(-d._pad_len * d._stride,
+                                          max(0, v["num_frames"] - 1 + (2 * d._pad_len - d._clip_len) * d._stride), d._overlap):
+                        paths = d._frame_reader.load_paths(v["video"], base_idx, base_idx + d._clip_len * d._stride, stride=d._stride)
+                        if paths[1] != -1:
+                            assert d._frame_paths[n] == paths, (ci, k, vi, base_idx)
+                            kept_video.append(vi)
+                            kept_base.append(base_idx)
+                            n += 1
+                assert n == len(d._frame_paths) == d._total_len
+                arrays[f"clip_video__{ci}__p{k}"] = np.array(kept_video, np.int32)
+                arrays[f"clip_base__{ci}__p{k}"] = np.array(kept_base, np.int64)
+                dsets.append(d)
+            joint = rframe.ActionSpotDatasetJoint(*dsets)
+            assert len(joint) == n_items
+            calls = []
+            real_randint = random.randint
+
+            def spy(a, b):
+                r = real_randint(a, b)
+                calls.append((a, b, r))
+                return r
+            random.seed(seed)
+            random.randint = spy
+            try:
+                items, drawn = [], []
+                for i in range(n_items):
+                    del calls[:]
+                    items.append(joint[i])
+                    drawn.append(list(calls))
+            finally:
+                random.randint = real_randint
+            part = np.array([it["dataset"] for it in items], np.int64)
+            assert set(part.tolist()) == {1, 2}, (ci, part)
+            for it, dr in zip(items, drawn):
+                assert len(dr) == (2 if mixup else 1) and all(a == 0 and b == dsets[it["dataset"] - 1]._total_len - 1 for a, b, _ in dr)
+            idx = np.array([dr[0][2] for dr in drawn], np.int64)
+            arrays[f"part__{ci}"], arrays[f"idx__{ci}"] = part, idx
+            if mixup:
+                arrays[f"idx2__{ci}"] = np.array([dr[1][2] for dr in drawn], np.int64)
+            over = 0
+            for pk, c in zip(part, idx):
+                k = int(pk) - 1
+                v = parts[k]["videos"][int(arrays[f"clip_video__{ci}__p{k}"][c])]
+                over += int(arrays[f"clip_base__{ci}__p{k}"][c]) + (clip_len - 1) * (sp1, sp2)[k][0] >= v["num_frames"]
+            assert over > 0, ci
+            keys = ["label"] + (["labelD"] if radi > 0 else []) + ((["label2"] + (["labelD2"] if radi > 0 else [])) if mixup else [])
+            for key in keys:
+                arrays[f"{key}__{ci}"] = np.stack([np.asarray(it[key]) for it in items]).astype(np.int64)
+            frame_keys = []
+            if ci == 0:
+                frame_keys = ["frame", "frame2"]
+                for key in frame_keys:
+                    arrays[f"{key}__{ci}"] = np.stack([it[key].numpy() for it in items]).astype(np.uint8)
+            cases.append(dict(clip_len=clip_len, strides=[sp1[0], sp2[0]], overlaps=[sp1[1], sp2[1]], radi_displacement=radi,
+                              mixup=mixup, seed=seed, pad_len=rframe.DEFAULT_PAD_LEN, dataset_len=[n_items // 2, n_items // 2],
+                              n_clips=[int(d._total_len) for d in dsets], keys=keys, frame_keys=frame_keys))
+    save(name, dict(kind="train_clips_joint", n_items=n_items, cases=cases,
+                    parts=[dict(dataset=p["dataset"], classes=p["classes"], videos=p["videos"]) for p in parts]), **arrays)
+
+
 # ----------------------------------------------------------------------------- training (VERDICT r4 item 3; SURVEY 8c)
 TRAIN_KEYS = [
     "_features.stem.conv.weight", "_features.stem.bn.weight", "_features.s1.b1.downsample.conv.weight",
@@ -737,6 +857,7 @@ CASES = {
     "train_step_tiny_rny002": lambda: train_step("train_step_tiny_rny002"),
     "train_epoch_tiny_rny002": lambda: train_epoch("train_epoch_tiny_rny002"),
     "train_clips": train_clips,
+    "train_clips_joint": train_clips_joint,
 }
 
 
