@@ -799,8 +799,8 @@ def _crop_window(crop, H, W):
 class ResidentJpegVideos:
     """The videos of a validation split resident on the device COMPRESSED, each decoded there when it is scored: what
     `trainclips.ResidentJpegClips` is to training.  videos: the label list's dicts (video, num_frames, optionally fps);
-    jpegs: their `trainclips.load_resident_jpegs(..., stride=s)` pack, video i of which has ceil(num_frames / s) frames.
-    Construction is `ResidentJpegClips`' (`trainclips._ResidentStreams`): the shards' streams in one buffer, the tables in
+    jpegs: their `jpegsets.load_resident_jpegs(..., stride=s)` pack, video i of which has ceil(num_frames / s) frames.
+    Construction is `ResidentJpegClips`' (`residentstreams.ResidentStreams`): the shards' streams in one buffer, the tables in
     one copy, the index pass once per shard, one host synchronisation, fallback and flagged frames decoded once with
     `feeder.read_frame` into a side buffer; resident bytes over max_resident_bytes raise ValueError before anything is
     uploaded.  split_mcus: MCUs per piece (default one MCU row); max_coeff_bytes: the coefficient buffer, a video beyond
@@ -808,7 +808,7 @@ class ResidentJpegVideos:
 
     crop: None, an int side or (wh, ww): `frames` returns the centre window only (`engine.centre_window`, the rectangle the
     first launch of a crop_dim model reads).  Then the pixel pass is ops.jpeg_pixels_window, the items leave out the pieces
-    whose MCU rows the window does not read (`trainclips.video_tables`), and the side buffer is kept cropped.
+    whose MCU rows the window does not read (`jpegsets.video_tables`), and the side buffer is kept cropped.
 
     `frames(i)` is video i as a device uint8 (L_i, 3, h, w) tensor, the bits of `feeder.load_video`'s frames (cut to the
     window); `sources()` is the `videos` argument of `stitch_videos`, `spot_videos`, `map_videos`: (name, length, fps,
@@ -834,9 +834,8 @@ class ResidentJpegVideos:
                  device="cuda", stream_videos=False):
         import threading
         import torch
-        from . import jpegdev, ops
-        from .trainclips import _ResidentStreams
-        from . import streams
+        from . import jpegdev, streams
+        from .residentstreams import ResidentStreams
         videos = list(videos)
         stride = int(getattr(jpegs, "stride", 1))
         if not videos or len(videos) != len(jpegs.video_len):
@@ -851,9 +850,9 @@ class ResidentJpegVideos:
             raise ValueError("ResidentJpegVideos: max_coeff_bytes must be positive")
         if jpegs.width:
             self.window = _crop_window(crop, jpegs.height, jpegs.width)      # argument errors before any file is touched
-            rs = _ResidentStreams("ResidentJpegVideos", jpegs, split_mcus, max_resident_bytes, self.window, streamed=stream_videos)
+            rs = ResidentStreams("ResidentJpegVideos", jpegs, split_mcus, max_resident_bytes, self.window, streamed=stream_videos)
         else:                                                   # the geometry comes from Pillow's decode of the first frame
-            rs = _ResidentStreams("ResidentJpegVideos", jpegs, split_mcus, 1 << 62, None, streamed=stream_videos)
+            rs = ResidentStreams("ResidentJpegVideos", jpegs, split_mcus, 1 << 62, None, streamed=stream_videos)
             self.window = _crop_window(crop, rs.H, rs.W)
             rs.max_resident_bytes = max_resident_bytes
             rs.set_window(self.window)                          # the budget, with side frames of the window's size
@@ -866,9 +865,10 @@ class ResidentJpegVideos:
         self.video_len = [int(x) for x in jpegs.video_len]
         self._mcu_rows = jpegdev.window_blocks(rs.geom, *self.window).mcu_rows if self.window is not None else None
         self._plan = None
+        longest = max(self.video_len)                           # at most 65535, checked above
         if stream_videos:
             # a streamed video is staged in the frame chunks of the coefficient buffer: the plan's "clips" are those chunks
-            chunk = min(max(self.video_len), 65535, max(1, int(max_coeff_bytes) // (2 * ops.jpeg_frame_coeffs(rs.W, rs.H, rs.samp))))
+            chunk = rs.chunk_frames(longest, max_coeff_bytes)
             rows = np.asarray([(f, lo, n, v) for v, (f, n) in enumerate(zip(self.video_first, self.video_len))
                                for lo in range(0, n, chunk)], np.int64).T
             self._plan = rs.plan_streaming(rows, chunk, 1, 1, 1, 1)
@@ -877,13 +877,8 @@ class ResidentJpegVideos:
         self.stream.wait_stream(torch.cuda.current_stream(device))
         with torch.cuda.stream(self.stream):
             rs.upload(self.stream, dev, self.UPLOAD_CHUNK_BYTES)
-            self._fc = fc = ops.jpeg_frame_coeffs(rs.W, rs.H, rs.samp)
-            longest = max(self.video_len)
-            self._chunk = min(longest, 65535, max(1, int(max_coeff_bytes) // (2 * fc)))
-            self._coeff = torch.empty(self._chunk * fc, dtype=torch.int16, device=dev) if rs.n_seg else None
-            self._ident = torch.arange(longest, dtype=torch.int32, device=dev)
-            self._err = torch.zeros(1, dtype=torch.int32, device=dev)
-            self._err_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+            rs.decode_buffers(dev, longest, max_coeff_bytes)
+            self._chunk = rs.chunk
         self.stream.synchronize()
         self._lock = threading.Lock()
         self._tabs = {}                                          # video -> (host tables, their device copies)
@@ -896,8 +891,8 @@ class ResidentJpegVideos:
         return len(self.names)
 
     def video_tables(self, i):
-        """`trainclips.video_tables` of video i: what `frames(i)` launches with (host arrays)"""
-        from .trainclips import video_tables
+        """`jpegsets.video_tables` of video i: what `frames(i)` launches with (host arrays)"""
+        from .jpegsets import video_tables
         rs = self._rs
         return video_tables(self.video_first[i], self.video_len[i], rs.frame_set, rs.side_row, rs.piece_lo, rs.piece_n,
                             chunk_slots=self._chunk, piece_mcu=rs.piece_mcu, mcus_x=rs.geom.mcus_x, mcu_rows=self._mcu_rows)
@@ -915,10 +910,10 @@ class ResidentJpegVideos:
         rs, L = self._rs, self.video_len[i]
         if out is None:
             out = torch.empty((L,) + tuple(self.shape), dtype=torch.uint8, device=self.device)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self._ident.device
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != rs.ident.device
               or not out.is_contiguous() or tuple(out.shape) != (L,) + tuple(self.shape)):
             raise ValueError(f"ResidentJpegVideos: out must be a contiguous uint8 {(L,) + tuple(self.shape)} tensor on "
-                             f"{self._ident.device}")
+                             f"{rs.ident.device}")
         with self._lock:
             if i not in self._tabs:
                 tb = self.video_tables(i)
@@ -927,7 +922,7 @@ class ResidentJpegVideos:
                 if self._plan is not None:
                     # per coefficient chunk its range copies into the one staging region; the relocation rows of the whole
                     # video in one table (a resident video: no copies, delta 0 everywhere)
-                    from .trainclips import stage_batch
+                    from .streamplan import stage_batch
                     reloc = np.zeros((L, 3), np.int64)
                     for lo, hi, _, _ in tb.chunks:
                         row = np.asarray([[self.video_first[i]], [lo], [L], [i]], np.int64)
@@ -936,37 +931,18 @@ class ResidentJpegVideos:
                 self._tabs[i] = (tb, to(tb.slot_set), to(tb.fill), to(tb.items), to(tb.waves), copies, d_reloc)
             tb, d_set, d_fill, d_items, d_waves, copies, d_reloc = self._tabs[i]
             self.stream.wait_stream(torch.cuda.current_stream(self.device))     # `out` may be a block this stream just freed
+
+            def stage(lo):                  # a streamed video: a chunk's range copies, behind the last chunk's items launch
+                for k, b_lo, b_hi, d in copies.get(lo, ()):
+                    rs.jstream[d:d + b_hi - b_lo].copy_(rs.host_streams[k][b_lo:b_hi], non_blocking=True)
+
             with torch.cuda.stream(self.stream):
-                for lo, hi, w_lo, w_hi in tb.chunks:
-                    self._coeff[:(hi - lo) * self._fc].zero_()
-                    for k, b_lo, b_hi, d in copies.get(lo, ()):      # a streamed video: behind the last chunk's items launch
-                        rs.jstream[d:d + b_hi - b_lo].copy_(rs.host_streams[k][b_lo:b_hi], non_blocking=True)
-                    if self._kernel_events is not None:
-                        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-                        ev[0].record(self.stream)
-                    ops.jpeg_entropy_items(rs.jstream, rs.pieces, d_items, d_waves[w_lo:w_hi], rs.table_sets, self.W, self.H,
-                                           self.samp, lo, hi - lo, self._coeff, self._err, reloc=d_reloc)
-                    if self._kernel_events is not None:
-                        ev[1].record(self.stream)
-                    if self.window is None:
-                        ops.jpeg_pixels_rows(self._coeff, d_set, rs.table_sets, out, self._ident, lo, hi - lo, self.samp)
-                    else:
-                        ops.jpeg_pixels_window(self._coeff, d_set, rs.table_sets, out, self._ident, lo, hi - lo, self.samp,
-                                               self.H, self.W, self.window[0], self.window[1])
-                    if self._kernel_events is not None:
-                        ev[2].record(self.stream)
-                        self._kernel_events.append(tuple(ev))
+                rs.decode(tb, d_items, d_waves, d_set, out, reloc=d_reloc, before_items=stage if copies else None,
+                          events=self._kernel_events)
                 if bool((tb.fill >= 0).any()):
                     ops.jpeg_slot_fill(rs.side, d_fill, out)
-                self._err_host.copy_(self._err, non_blocking=True)
-            self.stream.synchronize()
-            word = int(self._err_host[0])
-            if word:
-                with torch.cuda.stream(self.stream):
-                    self._err.zero_()
-                codes = [c for c in range(1, 8) if word >> c & 1]
-                raise RuntimeError(f"ResidentJpegVideos: video {self.names[i]} met decode errors on the device (status codes "
-                                   f"{codes}); the resident streams or tables are damaged")
+                rs.err_host.copy_(rs.err, non_blocking=True)
+            rs.raise_errors(self.stream, f"video {self.names[i]}", copy=False, reset=True)
         return out
 
     def sources(self):

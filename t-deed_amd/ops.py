@@ -1359,7 +1359,7 @@ def jpeg_entropy_items(stream, pieces, items, waves, table_sets, W, H, sampling,
     (n_waves, 2) rows of (first item, count <= 64), one table set per wave -- into coeff, int16 (>= n_slots *
     jpeg_frame_coeffs) that the caller has zero-filled on this stream: slot s lands at (s - slot_lo) frames into it.  err:
     int32 (1,) on the device, bit `code` of the word is set for every error code met; nothing else is reported.
-    reloc: None, or int64 (n, 3) on the device, row s = (delta, lo, hi) of slot s (trainclips.stage_batch): the bytes of a
+    reloc: None, or int64 (n, 3) on the device, row s = (delta, lo, hi) of slot s (streamplan.stage_batch): the bytes of a
     piece of that slot are a staged copy at stream[pos - delta ...] and must lie in stream[lo:hi]; a piece that does not, or
     a slot without a row, sets bit 7 of err and decodes nothing (tdeed_jpeg_entropy_items_reloc)."""
     dev = coeff.device
@@ -1468,7 +1468,7 @@ def sgp_gemm_gelu_chsum(A, Wp, bias, N, out, chs_out, form=None, out16=None):
     return out
 
 
-# ---- training clips drawn from resident videos (trainclips.hip; tables: trainclips.train_clip_table, int64 on the device)
+# ---- training clips drawn from resident videos (trainclips.hip; tables: cliptable.train_clip_table, int64 on the device)
 def _chk_clip_tables(frames_u8, tabs, who):
     if frames_u8.dtype != torch.uint8 or frames_u8.dim() < 2:
         raise TypeError(f"{who}: frames must be uint8 (L, ...)")
@@ -1484,41 +1484,67 @@ def _chk_clip_tables(frames_u8, tabs, who):
     return B, int(frames_u8.shape[0]), int(frames_u8[0].numel())
 
 
+def _clip_strides(strides, n, dev, who):
+    """The `stride` of the three clip ops -> (suffix of the C entry, its stride operand).  A scalar is one stride for all
+    clips: the scalar entry, ("", the scalar as given).  Anything else (a tensor, a sequence, an array) is one stride per clip
+    (trainclips.JointResidentClips): the ..._ps entry, "_ps" and a contiguous int32 (n,) tensor on `dev`.  A host sequence /
+    array is held against the rule (every entry > 0, ValueError) and uploaded; a device tensor is the caller's own table,
+    checked on the host where it was built -- the kernels do not follow an entry <= 0."""
+    if isinstance(strides, (int, float, np.generic)) or (isinstance(strides, np.ndarray) and strides.ndim == 0):
+        return "", strides
+    if not isinstance(strides, torch.Tensor) or not strides.is_cuda:
+        host = np.asarray(strides.numpy() if isinstance(strides, torch.Tensor) else strides)
+        if host.ndim != 1 or host.size != n or not np.issubdtype(host.dtype, np.integer):
+            raise ValueError(f"{who}: strides must be {n} integers, one per clip")
+        if host.size and int(host.min()) <= 0:
+            raise ValueError(f"{who}: every stride must be positive")
+        return "_ps", torch.from_numpy(np.ascontiguousarray(host, np.int32)).to(dev)
+    if strides.dtype != torch.int32 or strides.dim() != 1 or strides.numel() != n or not strides.is_contiguous() \
+            or strides.device != dev:
+        raise ValueError(f"{who}: strides must be a contiguous int32 ({n},) tensor on the tables' device")
+    return "_ps", strides
+
+
 def train_clip_gather(frames_u8, first, base, nframes, T, stride, out):
     """out[b*T + t] = frames_u8[first[b] + base[b] + t*stride] when 0 <= base[b] + t*stride < nframes[b], a zero frame
     otherwise.  frames_u8: the packed frames of all resident videos (sum L, ...); first / base / nframes: int64 (B,) on the
-    device (first packed frame and length of the clip's video, the clip's first original frame)."""
+    device (first packed frame and length of the clip's video, the clip's first original frame).  stride: an int, or one
+    per clip -- strides[b] in place of stride --: int32 (B,) on the device, or a host sequence (checked: every entry > 0)."""
     B, L, fb = _chk_clip_tables(frames_u8, (first, base, nframes), "train_clip_gather")
+    ps, stride = _clip_strides(stride, B, frames_u8.device, "train_clip_gather")
     if out.dtype != torch.uint8 or not out.is_contiguous() or out.device != frames_u8.device:
         raise TypeError("train_clip_gather: out must be a contiguous uint8 tensor on the frames' device")
     if out.numel() != B * T * fb:
         raise ValueError(f"train_clip_gather: out holds {out.numel()} bytes, {B} clips of {T} frames need {B * T * fb}")
-    call("tdeed_train_clip_gather_u8", ptr(frames_u8), L, fb, ptr(first), ptr(base), ptr(nframes), B, T, stride, ptr(out),
-         stream_ptr())
+    call("tdeed_train_clip_gather_u8" + ps, ptr(frames_u8), L, fb, ptr(first), ptr(base), ptr(nframes), B, T,
+         ptr(stride) if ps else stride, ptr(out), stream_ptr())
     return out
 
 
 def train_clip_gather_mix(frames_u8, tabs_a, tabs_b, lam, T, stride, out=None):
     """fp32 (B,T,...) = lam[b] * A[b] + (1 - lam[b]) * B[b] with A / B the windows train_clip_gather would write for the
     table triples tabs_a / tabs_b = (first, base, nframes): the bits of ops_bwd.mix_frames on those two batches, which are
-    never materialised.  lam: fp32 (B,) on the device."""
+    never materialised.  lam: fp32 (B,) on the device.  stride: as `train_clip_gather`; a clip's own stride is shared by its
+    two operands."""
     if not isinstance(tabs_a, (tuple, list)) or not isinstance(tabs_b, (tuple, list)) or len(tabs_a) != 3 or len(tabs_b) != 3:
         raise ValueError("train_clip_gather_mix: (first, base, nframes) per operand")
     B, L, fb = _chk_clip_tables(frames_u8, tuple(tabs_a) + tuple(tabs_b), "train_clip_gather_mix")
+    ps, stride = _clip_strides(stride, B, frames_u8.device, "train_clip_gather_mix")
     if lam.dtype != torch.float32 or lam.numel() != B or not lam.is_contiguous() or lam.device != frames_u8.device:
         raise ValueError(f"train_clip_gather_mix: lam must be a contiguous fp32 ({B},) tensor on the frames' device")
     if out is None:
         out = torch.empty((B, T) + tuple(frames_u8.shape[1:]), dtype=torch.float32, device=frames_u8.device)
     elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * T * fb or out.device != frames_u8.device:
         raise ValueError(f"train_clip_gather_mix: out must be a contiguous fp32 tensor of {B * T * fb} elements")
-    call("tdeed_train_clip_gather_mix_f32", ptr(frames_u8), L, fb, *(ptr(x) for x in tabs_a), *(ptr(x) for x in tabs_b),
-         ptr(lam), B, T, stride, ptr(out), stream_ptr())
+    call("tdeed_train_clip_gather_mix_f32" + ps, ptr(frames_u8), L, fb, *(ptr(x) for x in tabs_a), *(ptr(x) for x in tabs_b),
+         ptr(lam), B, T, ptr(stride) if ps else stride, ptr(out), stream_ptr())
     return out
 
 
 def clip_labels(clip_video, clip_base, T, stride, r, ev_off, ev_frame, ev_class, label=None, labelD=None, displ=True):
-    """Per-frame labels of n clips from their videos' event lists (trainclips.rasterise_labels on the device): clip_video /
-    clip_base int64 (n,), ev_off int32 (nv+1,), ev_frame / ev_class int32 (n_events,), all on the device.
+    """Per-frame labels of n clips from their videos' event lists (cliptable.rasterise_labels on the device): clip_video /
+    clip_base int64 (n,), ev_off int32 (nv+1,), ev_frame / ev_class int32 (n_events,), all on the device.  stride: as
+    `train_clip_gather`, an int or one per clip.
     -> (label int64 (n,T), labelD int64 (n,T) or None when displ is False)."""
     dev = clip_video.device
     n = clip_video.numel()
@@ -1529,6 +1555,7 @@ def clip_labels(clip_video, clip_base, T, stride, r, ev_off, ev_frame, ev_class,
             raise ValueError(f"clip_labels: {what} must be a contiguous 1-d {dt} GPU tensor")
     if clip_base.numel() != n or ev_class.numel() != ev_frame.numel() or ev_off.numel() < 2:
         raise ValueError("clip_labels: table lengths do not match")
+    ps, stride = _clip_strides(stride, n, dev, "clip_labels")
     if label is None:
         label = torch.empty((n, T), dtype=torch.int64, device=dev)
     if labelD is None and displ:
@@ -1537,80 +1564,6 @@ def clip_labels(clip_video, clip_base, T, stride, r, ev_off, ev_frame, ev_class,
         if o is not None and (o.dtype != torch.int64 or not o.is_contiguous() or o.numel() != n * T or o.device != dev):
             raise ValueError(f"clip_labels: outputs must be contiguous int64 ({n},{T}) tensors")
     ne = ev_frame.numel()
-    call("tdeed_clip_labels", ptr(clip_video), ptr(clip_base), n, T, stride, r, ptr(ev_off), ptr(ev_frame) if ne else None,
-         ptr(ev_class) if ne else None, ev_off.numel() - 1, ne, ptr(label), ptr(labelD), stream_ptr())
-    return label, labelD
-
-
-# ---- the same three with one stride per clip (the ..._ps entries; trainclips.JointResidentClips)
-def _clip_strides(strides, n, dev, who):
-    """strides as the ..._ps entries take them: a contiguous int32 (n,) tensor on `dev`.  A host sequence / array is held
-    against the rule (every entry > 0, ValueError) and uploaded; a device tensor is the caller's own table, checked on the
-    host where it was built -- the kernels do not follow an entry <= 0."""
-    if not isinstance(strides, torch.Tensor) or not strides.is_cuda:
-        host = np.asarray(strides.numpy() if isinstance(strides, torch.Tensor) else strides)
-        if host.ndim != 1 or host.size != n or not np.issubdtype(host.dtype, np.integer):
-            raise ValueError(f"{who}: strides must be {n} integers, one per clip")
-        if host.size and int(host.min()) <= 0:
-            raise ValueError(f"{who}: every stride must be positive")
-        return torch.from_numpy(np.ascontiguousarray(host, np.int32)).to(dev)
-    if strides.dtype != torch.int32 or strides.dim() != 1 or strides.numel() != n or not strides.is_contiguous() \
-            or strides.device != dev:
-        raise ValueError(f"{who}: strides must be a contiguous int32 ({n},) tensor on the tables' device")
-    return strides
-
-
-def train_clip_gather_ps(frames_u8, first, base, nframes, T, strides, out):
-    """`train_clip_gather` with one stride per clip: out[b*T + t] = frames_u8[first[b] + base[b] + t*strides[b]] under the same
-    window rule.  strides: int32 (B,) on the device, or a host sequence (checked: every entry > 0)."""
-    B, L, fb = _chk_clip_tables(frames_u8, (first, base, nframes), "train_clip_gather_ps")
-    strides = _clip_strides(strides, B, frames_u8.device, "train_clip_gather_ps")
-    if out.dtype != torch.uint8 or not out.is_contiguous() or out.device != frames_u8.device:
-        raise TypeError("train_clip_gather_ps: out must be a contiguous uint8 tensor on the frames' device")
-    if out.numel() != B * T * fb:
-        raise ValueError(f"train_clip_gather_ps: out holds {out.numel()} bytes, {B} clips of {T} frames need {B * T * fb}")
-    call("tdeed_train_clip_gather_u8_ps", ptr(frames_u8), L, fb, ptr(first), ptr(base), ptr(nframes), B, T, ptr(strides),
-         ptr(out), stream_ptr())
-    return out
-
-
-def train_clip_gather_mix_ps(frames_u8, tabs_a, tabs_b, lam, T, strides, out=None):
-    """`train_clip_gather_mix` with one stride per clip, shared by the clip's two operands (strides as above)."""
-    if not isinstance(tabs_a, (tuple, list)) or not isinstance(tabs_b, (tuple, list)) or len(tabs_a) != 3 or len(tabs_b) != 3:
-        raise ValueError("train_clip_gather_mix_ps: (first, base, nframes) per operand")
-    B, L, fb = _chk_clip_tables(frames_u8, tuple(tabs_a) + tuple(tabs_b), "train_clip_gather_mix_ps")
-    strides = _clip_strides(strides, B, frames_u8.device, "train_clip_gather_mix_ps")
-    if lam.dtype != torch.float32 or lam.numel() != B or not lam.is_contiguous() or lam.device != frames_u8.device:
-        raise ValueError(f"train_clip_gather_mix_ps: lam must be a contiguous fp32 ({B},) tensor on the frames' device")
-    if out is None:
-        out = torch.empty((B, T) + tuple(frames_u8.shape[1:]), dtype=torch.float32, device=frames_u8.device)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * T * fb or out.device != frames_u8.device:
-        raise ValueError(f"train_clip_gather_mix_ps: out must be a contiguous fp32 tensor of {B * T * fb} elements")
-    call("tdeed_train_clip_gather_mix_f32_ps", ptr(frames_u8), L, fb, *(ptr(x) for x in tabs_a), *(ptr(x) for x in tabs_b),
-         ptr(lam), B, T, ptr(strides), ptr(out), stream_ptr())
-    return out
-
-
-def clip_labels_ps(clip_video, clip_base, T, strides, r, ev_off, ev_frame, ev_class, label=None, labelD=None, displ=True):
-    """`clip_labels` with one stride per clip: strides int32 (n,) on the device, or a host sequence (checked)."""
-    dev = clip_video.device
-    n = clip_video.numel()
-    for tab, dt, what in ((clip_video, torch.int64, "clip_video"), (clip_base, torch.int64, "clip_base"),
-                          (ev_off, torch.int32, "ev_off"), (ev_frame, torch.int32, "ev_frame"), (ev_class, torch.int32, "ev_class")):
-        if not isinstance(tab, torch.Tensor) or tab.dtype != dt or tab.dim() != 1 or not tab.is_contiguous() \
-                or not tab.is_cuda or tab.device != dev:
-            raise ValueError(f"clip_labels_ps: {what} must be a contiguous 1-d {dt} GPU tensor")
-    if clip_base.numel() != n or ev_class.numel() != ev_frame.numel() or ev_off.numel() < 2:
-        raise ValueError("clip_labels_ps: table lengths do not match")
-    strides = _clip_strides(strides, n, dev, "clip_labels_ps")
-    if label is None:
-        label = torch.empty((n, T), dtype=torch.int64, device=dev)
-    if labelD is None and displ:
-        labelD = torch.empty((n, T), dtype=torch.int64, device=dev)
-    for o in (label, labelD):
-        if o is not None and (o.dtype != torch.int64 or not o.is_contiguous() or o.numel() != n * T or o.device != dev):
-            raise ValueError(f"clip_labels_ps: outputs must be contiguous int64 ({n},{T}) tensors")
-    ne = ev_frame.numel()
-    call("tdeed_clip_labels_ps", ptr(clip_video), ptr(clip_base), n, T, ptr(strides), r, ptr(ev_off), ptr(ev_frame) if ne else None,
-         ptr(ev_class) if ne else None, ev_off.numel() - 1, ne, ptr(label), ptr(labelD), stream_ptr())
+    call("tdeed_clip_labels" + ps, ptr(clip_video), ptr(clip_base), n, T, ptr(stride) if ps else stride, r, ptr(ev_off),
+         ptr(ev_frame) if ne else None, ptr(ev_class) if ne else None, ev_off.numel() - 1, ne, ptr(label), ptr(labelD), stream_ptr())
     return label, labelD

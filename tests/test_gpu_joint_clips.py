@@ -72,7 +72,7 @@ def test_gather_ps_equals_numpy_indexing(shape):
     first, base, nfr = _tables(CLIPS)
     want, pads = _host_gather(video.cpu(), first, base, nfr, STRIDES)
     out = torch.full((5, T) + shape, 9, dtype=torch.uint8, device=DEV)
-    ops.train_clip_gather_ps(video, _i64(first), _i64(base), _i64(nfr), T, _i32(STRIDES), out)
+    ops.train_clip_gather(video, _i64(first), _i64(base), _i64(nfr), T, _i32(STRIDES), out)
     torch.cuda.synchronize()
     assert torch.equal(out.cpu(), want)
     assert pads == int((want.flatten(2).max(dim=2).values == 0).sum()) and pads > 5
@@ -80,20 +80,20 @@ def test_gather_ps_equals_numpy_indexing(shape):
     assert want[2, 1:4].flatten(1).any(dim=1).all() and not want[2, 4:].any() and not want[2, 0].any()
     # a host sequence of strides is checked and uploaded
     out2 = torch.empty_like(out)
-    ops.train_clip_gather_ps(video, _i64(first), _i64(base), _i64(nfr), T, STRIDES, out2)
+    ops.train_clip_gather(video, _i64(first), _i64(base), _i64(nfr), T, STRIDES, out2)
     assert torch.equal(out2, out)
     # a row that points outside the packed buffer touches nothing it should not: zeros, and the neighbours stay right
     L = sum(LENGTHS)
     bad_first = first.copy()
     bad_first[[0, 3]] = [L + 7, -40]
     out.fill_(9)
-    ops.train_clip_gather_ps(video, _i64(bad_first), _i64(base), _i64(nfr), T, _i32(STRIDES), out)
+    ops.train_clip_gather(video, _i64(bad_first), _i64(base), _i64(nfr), T, _i32(STRIDES), out)
     torch.cuda.synchronize()
     assert not out[0].any() and not out[3].any() and torch.equal(out[[1, 2, 4]].cpu(), want[[1, 2, 4]])
     # behind the buffer's end by the window only: first inside, first + base + t * stride outside
     edge = (_i64([L - 2]), _i64([0]), _i64([30]))
     o1 = torch.full((1, T) + shape, 9, dtype=torch.uint8, device=DEV)
-    ops.train_clip_gather_ps(video, *edge, T, _i32([1]), o1)
+    ops.train_clip_gather(video, *edge, T, _i32([1]), o1)
     torch.cuda.synchronize()
     assert torch.equal(o1[0, :2], video[L - 2:]) and not o1[0, 2:].any()
 
@@ -105,19 +105,19 @@ def test_gather_mix_ps_equals_mix_frames_of_the_two_gathers(shape):
     tb = tuple(_i64(x) for x in _tables(PARTNERS))
     S = _i32(STRIDES)
     lam = torch.tensor([0.0, 1.0, 0.5, 0.123456, 1e-8], dtype=torch.float32, device=DEV)
-    a = ops.train_clip_gather_ps(video, *ta, T, S, torch.empty((5, T) + shape, dtype=torch.uint8, device=DEV))
-    b = ops.train_clip_gather_ps(video, *tb, T, S, torch.empty((5, T) + shape, dtype=torch.uint8, device=DEV))
+    a = ops.train_clip_gather(video, *ta, T, S, torch.empty((5, T) + shape, dtype=torch.uint8, device=DEV))
+    b = ops.train_clip_gather(video, *tb, T, S, torch.empty((5, T) + shape, dtype=torch.uint8, device=DEV))
     hb, _ = _host_gather(video.cpu(), *_tables(PARTNERS), STRIDES)
     assert torch.equal(b.cpu(), hb)
     want = ops_bwd.mix_frames(a, b, lam)
-    got = ops.train_clip_gather_mix_ps(video, ta, tb, lam, T, S)
+    got = ops.train_clip_gather_mix(video, ta, tb, lam, T, S)
     torch.cuda.synchronize()
     assert got.dtype == torch.float32 and got.shape == want.shape and torch.equal(got, want)
     pa, pb = a.flatten(2).max(dim=2).values == 0, b.flatten(2).max(dim=2).values == 0
     assert bool((pa & pb).any()) and bool((pa & ~pb).any()) and bool((~pa & pb).any()) and float(got.max()) > 1.0
     # one operand's row outside the buffer: that operand contributes zeros, nothing else changes
     bad = (_i64(_tables(PARTNERS)[0] + 10 ** 6), tb[1], tb[2])
-    got = ops.train_clip_gather_mix_ps(video, ta, bad, lam, T, S)
+    got = ops.train_clip_gather_mix(video, ta, bad, lam, T, S)
     torch.cuda.synchronize()
     assert torch.equal(got, ops_bwd.mix_frames(a, torch.zeros_like(b), lam))
 
@@ -134,7 +134,7 @@ def test_clip_labels_ps_equal_the_host_rule(r):
                    (np.arange(len(tab.clip_video)), np.repeat([12, 3], np.diff(tab.part_clips)))):
         want, wantD = TC.rasterise_labels(tab, ids, T, S, r)
         ev = [torch.from_numpy(x).to(DEV) for x in (tab.ev_off, tab.ev_frame, tab.ev_class)]
-        label, labelD = ops.clip_labels_ps(_i64(tab.clip_video[ids]), _i64(tab.clip_base[ids]), T, _i32(S), r, *ev)
+        label, labelD = ops.clip_labels(_i64(tab.clip_video[ids]), _i64(tab.clip_base[ids]), T, _i32(S), r, *ev)
         torch.cuda.synchronize()
         assert label.dtype == labelD.dtype == torch.int64
         assert torch.equal(label.cpu(), torch.from_numpy(want)) and torch.equal(labelD.cpu(), torch.from_numpy(wantD))
@@ -150,16 +150,16 @@ def test_ps_entries_with_equal_strides_are_their_scalar_twins_bit_for_bit(stride
         tb = tuple(_i64(x) for x in _tables(PARTNERS))
         S = _i32([stride] * 5)
         new = lambda: torch.empty((5, T) + shape, dtype=torch.uint8, device=DEV)      # noqa: E731
-        assert torch.equal(ops.train_clip_gather_ps(video, *ta, T, S, new()), ops.train_clip_gather(video, *ta, T, stride, new()))
+        assert torch.equal(ops.train_clip_gather(video, *ta, T, S, new()), ops.train_clip_gather(video, *ta, T, stride, new()))
         lam = torch.tensor([0.3, 0.9, 0.5, 0.0, 0.77], dtype=torch.float32, device=DEV)
-        assert torch.equal(ops.train_clip_gather_mix_ps(video, ta, tb, lam, T, S), ops.train_clip_gather_mix(video, ta, tb, lam, T, stride))
+        assert torch.equal(ops.train_clip_gather_mix(video, ta, tb, lam, T, S), ops.train_clip_gather_mix(video, ta, tb, lam, T, stride))
     meta, _ = JC.golden()
     case = dict(meta["cases"][0], strides=[stride, stride])
     _, tab = JC.joined_table(JC.parts_of(case, frames=False), T, 2)
     n = len(tab.clip_video)
     ev = [torch.from_numpy(x).to(DEV) for x in (tab.ev_off, tab.ev_frame, tab.ev_class)]
     cv, cb = _i64(tab.clip_video), _i64(tab.clip_base)
-    a, aD = ops.clip_labels_ps(cv, cb, T, _i32([stride] * n), 2, *ev)
+    a, aD = ops.clip_labels(cv, cb, T, _i32([stride] * n), 2, *ev)
     b, bD = ops.clip_labels(cv, cb, T, stride, 2, *ev)
     torch.cuda.synchronize()
     assert torch.equal(a, b) and torch.equal(aD, bD) and bool(a.any())
@@ -184,16 +184,16 @@ def test_ps_entry_points_check_their_arguments():
     tab = _i64([0, 0])
     out = torch.empty((2, T, 3, 5, 7), dtype=torch.uint8, device=DEV)
     with pytest.raises(ValueError, match="positive"):                       # refused on the host
-        ops.train_clip_gather_ps(video, tab, tab, tab, T, [1, 0], out)
+        ops.train_clip_gather(video, tab, tab, tab, T, [1, 0], out)
     with pytest.raises(ValueError, match="positive"):
-        ops.train_clip_gather_mix_ps(video, (tab,) * 3, (tab,) * 3, torch.ones(2, device=DEV), T, np.array([2, -1]))
+        ops.train_clip_gather_mix(video, (tab,) * 3, (tab,) * 3, torch.ones(2, device=DEV), T, np.array([2, -1]))
     with pytest.raises(ValueError):
-        ops.train_clip_gather_ps(video, tab, tab, tab, T, _i64([1, 1]), out)            # int64 on the device
+        ops.train_clip_gather(video, tab, tab, tab, T, _i64([1, 1]), out)            # int64 on the device
     with pytest.raises(ValueError):
-        ops.train_clip_gather_ps(video, tab, tab, tab, T, _i32([1]), out)
+        ops.train_clip_gather(video, tab, tab, tab, T, _i32([1]), out)
     ev = [_i32([0, 1]), _i32([3]), _i32([1])]
     with pytest.raises(ValueError, match="positive"):
-        ops.clip_labels_ps(tab, tab, T, [0, 1], 1, *ev)
+        ops.clip_labels(tab, tab, T, [0, 1], 1, *ev)
 
 
 # ----------------------------------------------------------------------------- 2. JointResidentClips against the fixture
@@ -229,7 +229,7 @@ def test_joint_resident_clips_equal_the_recorded_items_over_two_passes(ci):
                 S = got["mix"].strides
                 assert S.dtype == torch.int32 and S.cpu().tolist() == [case["strides"][p - 1] for p in w["dataset"].tolist()]
                 shape = tuple(w["frame"].shape[2:])
-                a, b = (ops.train_clip_gather_ps(loader.video, *tabs, Tc, S, torch.empty((B, Tc) + shape, dtype=torch.uint8, device=DEV))
+                a, b = (ops.train_clip_gather(loader.video, *tabs, Tc, S, torch.empty((B, Tc) + shape, dtype=torch.uint8, device=DEV))
                         for tabs in (got["mix"].tabs_a, got["mix"].tabs_b))
                 lam = torch.from_numpy(rs.beta(0.2, 0.2, B).astype(np.float32)).to(DEV)
                 assert torch.equal(got["mix"](lam), ops_bwd.mix_frames(w["frame"].to(DEV), w["frame2"].to(DEV), lam)), n

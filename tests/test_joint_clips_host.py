@@ -155,7 +155,8 @@ def test_a_single_part_loader_builds_the_tables_it_always_built(mixup):
     p = META["parts"][0]
     lengths = [v["num_frames"] for v in p["videos"]]
     ld = TC._ClipLoader()
-    ld._init_clips(p["videos"], lengths, p["classes"], 8, 2, 0.5, 2, mixup, 11, 4, 9, TC.DEFAULT_PAD_LEN, False, False, "cpu", 3)
+    part = dict(videos=p["videos"], classes=p["classes"], stride=2, overlap=0.5, require_events=False, dataset_len=11)
+    ld._init_parts([part], lengths, 8, 2, mixup, 4, 9, TC.DEFAULT_PAD_LEN, False, "cpu", 3, joint=False)
     tab = TC.train_clip_table(p["videos"], p["classes"], 8, 2, 0.5, TC.DEFAULT_PAD_LEN, False, 2)
     for key in ("clip_video", "clip_base", "ev_frame", "ev_class", "ev_off", "num_frames"):
         assert np.array_equal(getattr(ld.table, key), getattr(tab, key)) and getattr(ld.table, key).dtype == getattr(tab, key).dtype
