@@ -490,6 +490,11 @@ int tdeed_stitch_scores_seg(const float* clip_scores, int V, int n, int T, int K
  * with 0. */
 int tdeed_frame_events_seg(const float* mean, const int* seg_off, int nv, int L_total, int max_len, int K1, float hr_threshold,
                            int* pred, unsigned char* pred_u8, float* pred_score, int* first_frame, int* count, void* stream);
+/* The frame error and foreground-F1 counters of util/eval.py:34-84 over a packed track: pred = the first maximum of each row of
+ * mean fp32 [L_total][K1], true = labels uint8[L_total] (values < K1 <= 256).  stats int64 [2 + 3*K1] is ADDED to: frames,
+ * frames with pred != true, then (tp, fp, fn) for "any" (foreground against background) and for every class k >= 1 at
+ * 2 + 3*k.  Integer sums: the result does not depend on the order of accumulation. */
+int tdeed_frame_stats_seg(const float* mean, const unsigned char* labels, int L_total, int K1, long* stats, void* stream);
 /* bytes of workspace tdeed_nms_track_seg needs (0: max_len frames of suppression state fit the LDS of a workgroup) */
 long tdeed_nms_track_seg_workspace(int L_total, int max_len, int K1);
 /* threads of the suppression / compaction workgroups tdeed_nms_track_seg launches for this max_len */
@@ -542,6 +547,19 @@ int tdeed_ap_match_seg(const float* mean, const unsigned char* emitted, const do
 int tdeed_ap_rank(const double* ev_score, const int* ev_count, const int* vid_off, int NV, long LT_all, const int* gt_off, int G,
                   int K1, int n_entries, int n_tol, const int* hit_pos, const int* hit_count, const int* class_off, int* rank,
                   double* psorted, double* ap, int* nhits, void* stream);
+/* Exchange of the state between the ranks of a sharded pass.  ev_count / hit_count hold the sums over the ranks; sc_end int64
+ * [n_entries*(K1-1)*NV] and hc_end int64 [n_entries*n_tol*NV*K1] are their inclusive scans in the stores' own order, so segment
+ * s owns the elements end[s-1] .. end[s]-1 of a dense payload: scores double[n_scores], hits int32[n_hits] (the scans' last
+ * entries).  own int32[NV]: non-zero for the videos this rank matched.  pack copies the used part of the own segments out of
+ * ev_score / hit_pos (the buffers of tdeed_ap_rank) into the payloads, which the caller zeroes; unpack writes the segments of
+ * the videos that are NOT own from the payloads into the stores and leaves own segments and ev_frame alone.  One thread per
+ * payload element, a binary search in the scan; no atomics.  A payload may be NULL when it has no element. */
+int tdeed_ap_state_pack(const double* ev_score, const int* hit_pos, double* scores, int* hits, const long* sc_end,
+                        const long* hc_end, long n_scores, long n_hits, const int* own, const int* vid_off, const int* gt_off,
+                        int NV, int K1, int n_entries, int n_tol, long LT_all, int G, void* stream);
+int tdeed_ap_state_unpack(double* ev_score, int* hit_pos, const double* scores, const int* hits, const long* sc_end,
+                          const long* hc_end, long n_scores, long n_hits, const int* own, const int* vid_off, const int* gt_off,
+                          int NV, int K1, int n_entries, int n_tol, long LT_all, int G, void* stream);
 
 /* ---- training clips drawn from resident videos (trainclips.hip) -----------------------------------------------------
  * frames: uint8 [total_frames][frame_bytes], the frames of all resident videos packed one after the other.  The tables are

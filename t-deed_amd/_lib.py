@@ -201,6 +201,9 @@ _SIGS = {
     "tdeed_ap_match_seg": ([P, P, P, P, c_int, c_int, c_int, c_int, c_float, P, c_int, P, c_long, P, P, c_int, c_int, P, c_int, P, P,
                             P, P, P, P], c_int),
     "tdeed_ap_rank": ([P, P, P, c_int, c_long, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P], c_int),
+    "tdeed_ap_state_pack": ([P, P, P, P, P, P, c_long, c_long, P, P, P, c_int, c_int, c_int, c_int, c_long, c_int, P], c_int),
+    "tdeed_ap_state_unpack": ([P, P, P, P, P, P, c_long, c_long, P, P, P, c_int, c_int, c_int, c_int, c_long, c_int, P], c_int),
+    "tdeed_frame_stats_seg": ([P, P, c_int, c_int, P, P], c_int),
     "tdeed_train_clip_gather_u8": ([P, c_long, c_long, P, P, P, c_int, c_int, c_int, P, P], c_int),
     "tdeed_train_clip_gather_mix_f32": ([P, c_long, c_long, P, P, P, P, P, P, P, c_int, c_int, c_int, P, P], c_int),
     "tdeed_clip_labels": ([P, P, c_int, c_int, c_int, c_int, P, P, P, c_int, c_int, P, P, P], c_int),

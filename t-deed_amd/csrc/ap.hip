@@ -315,7 +315,103 @@ __global__ __launch_bounds__(AP_NT) void ap_rank_kernel(const double* __restrict
   }
 }
 
+// =========================================================================== exchange of the state between ranks
+// A validation pass sharded over ranks leaves every rank with the segments of its own videos.  After the counts have been
+// summed over the ranks (ev_count / hit_count are zero where a rank filled nothing), the used part of every segment has a
+// place in a dense payload: the exclusive scan of the counts in the store's own order -- (e, c, ord) for the scores, (e, t,
+// ord*K1+c) for the hits.  PACK copies the rank's own segments out of the stores into the (zero-filled) payloads, !PACK
+// writes the foreign segments of the summed payloads into the stores: one body, the copy turned round.
+//   One thread per payload element; it finds its segment by a binary search in the inclusive scan (sc_end / hc_end, int64, in
+// global memory: the E*(K1-1)*NV + E*T*NV*K1 entries do not fit LDS in general, but a wave's 64 consecutive elements walk the
+// same few cache lines of it).  The work is the payload, whatever the sizes of the segments: a workgroup per segment would
+// leave most workgroups empty (most (class, video) pairs of a tolerance have no hit) and a few with thousands of elements.
+// Empty segments are skipped by the search itself (their end equals their predecessor's).  The first blocks_s workgroups take
+// the score payload (8-byte elements), the others the hit payload (4-byte elements).  No atomics, no LDS, no scratch.
+template <bool PACK>
+__global__ __launch_bounds__(AP_NT) void ap_state_xchg_kernel(double* ev_score, int* hit_pos, double* pay_s, int* pay_h,
+                                                            const long* __restrict__ sc_end, const long* __restrict__ hc_end,
+                                                            long n_s, long n_h, long nseg_s, long nseg_h, int blocks_s,
+                                                            const int* __restrict__ own, const int* __restrict__ vid_off,
+                                                            const int* __restrict__ gt_off, int NV, int K1, long LT_all,
+                                                            long hit_stride) {
+  const bool scores = (int)blockIdx.x < blocks_s;
+  const long i = (long)(scores ? blockIdx.x : blockIdx.x - blocks_s) * AP_NT + threadIdx.x;
+  const long n = scores ? n_s : n_h;
+  if (i >= n) return;
+  const long* __restrict__ end = scores ? sc_end : hc_end;
+  long lo = 0, hi = scores ? nseg_s : nseg_h;                          // the first segment whose end lies beyond i
+  while (lo < hi) {
+    const long mid = (lo + hi) >> 1;
+    if (end[mid] <= i) lo = mid + 1; else hi = mid;
+  }
+  const long s = lo;
+  if (s >= (scores ? nseg_s : nseg_h)) return;                         // a payload longer than the scan says: not followed
+  const long k = i - (s > 0 ? end[s - 1] : 0);                         // position inside the segment
+  if (k < 0) return;
+  if (scores) {
+    const long row = s / NV;                                           // e * (K1-1) + c - 1
+    const int ord = (int)(s - row * NV);
+    const long g0 = vid_off[ord];
+    if (g0 < 0 || g0 + k >= (long)vid_off[ord + 1] || g0 + k >= LT_all) return;      // a count beyond the video's frames
+    const long j = row * LT_all + g0 + k;
+    if (PACK) {
+      if (own[ord]) pay_s[i] = ev_score[j];
+    } else {
+      if (!own[ord]) ev_score[j] = pay_s[i];
+    }
+  } else {
+    const long nk = (long)NV * K1;
+    const long row = s / nk;                                           // e * n_tol + t
+    const long oc = s - row * nk;                                      // ord * K1 + c
+    const int ord = (int)(oc / K1);
+    const long g0 = gt_off[oc];
+    if (g0 < 0 || g0 + k >= (long)gt_off[oc + 1] || g0 + k >= hit_stride) return;      // more hits than ground-truth frames
+    const long j = row * hit_stride + g0 + k;
+    if (PACK) {
+      if (own[ord]) pay_h[i] = hit_pos[j];
+    } else {
+      if (!own[ord]) hit_pos[j] = pay_h[i];
+    }
+  }
+}
+
+static int ap_state_xchg(bool pack, double* ev_score, int* hit_pos, double* pay_s, int* pay_h, const long* sc_end,
+                         const long* hc_end, long n_s, long n_h, const int* own, const int* vid_off, const int* gt_off, int NV,
+                         int K1, int n_entries, int n_tol, long LT_all, int G, void* stream) {
+  const char* who = pack ? "ap_state_pack" : "ap_state_unpack";
+  TD_CHECK(ev_score && hit_pos && sc_end && hc_end && own && vid_off && gt_off, "%s: null pointer", who);
+  TD_CHECK(NV > 0 && LT_all > 0 && LT_all < (1l << 31) && K1 > 1 && K1 <= 256 && G >= 0 && (long)NV * K1 < (1l << 31), "%s: bad sizes", who);
+  TD_CHECK(n_entries >= 1 && n_entries <= 65535 && n_tol >= 1 && n_tol <= AP_MAX_TOL, "%s: %d entries, %d tolerances", who,
+           n_entries, n_tol);
+  TD_CHECK(n_s >= 0 && n_h >= 0 && (n_s == 0 || pay_s) && (n_h == 0 || pay_h), "%s: payloads of %ld / %ld elements", who, n_s, n_h);
+  TD_CHECK(n_s <= (long)n_entries * (K1 - 1) * LT_all && n_h <= (long)n_entries * n_tol * (G > 0 ? G : 1),
+           "%s: payloads of %ld / %ld elements are larger than the stores", who, n_s, n_h);
+  const long bs = (n_s + AP_NT - 1) / AP_NT, bh = (n_h + AP_NT - 1) / AP_NT;
+  TD_CHECK(bs + bh < (1l << 31), "%s: %ld workgroups", who, bs + bh);
+  if (bs + bh == 0) return TDEED_OK;
+  const long nseg_s = (long)n_entries * (K1 - 1) * NV, nseg_h = (long)n_entries * n_tol * NV * K1;
+  auto kernel = pack ? ap_state_xchg_kernel<true> : ap_state_xchg_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(bs + bh)), dim3(AP_NT), 0, (hipStream_t)stream, ev_score, hit_pos, pay_s, pay_h, sc_end,
+                     hc_end, n_s, n_h, nseg_s, nseg_h, (int)bs, own, vid_off, gt_off, NV, K1, LT_all, (long)(G > 0 ? G : 1));
+  TD_LAUNCH_CHECK(who);
+  return TDEED_OK;
+}
+
 // =========================================================================== C entries
+extern "C" int tdeed_ap_state_pack(const double* ev_score, const int* hit_pos, double* scores, int* hits, const long* sc_end,
+                                   const long* hc_end, long n_scores, long n_hits, const int* own, const int* vid_off,
+                                   const int* gt_off, int NV, int K1, int n_entries, int n_tol, long LT_all, int G, void* stream) {
+  return ap_state_xchg(true, const_cast<double*>(ev_score), const_cast<int*>(hit_pos), scores, hits, sc_end, hc_end, n_scores,
+                       n_hits, own, vid_off, gt_off, NV, K1, n_entries, n_tol, LT_all, G, stream);
+}
+
+extern "C" int tdeed_ap_state_unpack(double* ev_score, int* hit_pos, const double* scores, const int* hits, const long* sc_end,
+                                     const long* hc_end, long n_scores, long n_hits, const int* own, const int* vid_off,
+                                     const int* gt_off, int NV, int K1, int n_entries, int n_tol, long LT_all, int G, void* stream) {
+  return ap_state_xchg(false, ev_score, hit_pos, const_cast<double*>(scores), const_cast<int*>(hits), sc_end, hc_end, n_scores,
+                       n_hits, own, vid_off, gt_off, NV, K1, n_entries, n_tol, LT_all, G, stream);
+}
+
 extern "C" int tdeed_ap_lds_frames(void) { return AP_LDS_FRAMES; }
 extern "C" int tdeed_ap_max_tolerances(void) { return AP_MAX_TOL; }
 extern "C" int tdeed_ap_max_truth(int n_tol) { return n_tol >= 1 && n_tol <= AP_MAX_TOL ? AP_GT_LDS_BYTES / (4 + n_tol) : 0; }

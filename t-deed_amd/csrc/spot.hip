@@ -64,6 +64,79 @@ extern "C" int tdeed_frame_events_seg(const float* mean, const int* seg_off, int
   return TDEED_OK;
 }
 
+// =========================================================================== frame error and foreground-F1 counters
+// The label-dependent counters of evalutil.frame_events(labels=...) (util/eval.py:34-84) over the packed track of a group:
+// per frame pred = frame_events_seg_kernel's arg-max (first maximum), true = the packed uint8 label.  stats int64
+// [2 + 3*K1] is added to: [0] frames, [1] frames with pred != true, then (tp, fp, fn) at 2 + 3*k for k = 0 ("any": foreground
+// against background) and every class k >= 1:
+//   any      tp: pred != 0 and true != 0    fp: pred != 0 and true == 0    fn: pred == 0 and true != 0
+//   class k  tp: pred == true == k          fp: pred == k != true          fn: true == k != pred
+// Integers, so any order of accumulation gives the same sums: int32 partials of a workgroup in LDS (the five frame-level
+// counters from wave ballots, at most two class counters per frame by LDS atomics), then one 64-bit vector atomic add per
+// counter the workgroup touched.  The grid is bounded (FS_MAX_BLOCKS workgroups stride over the frames), so a pass issues at
+// most FS_MAX_BLOCKS * (2 + 3*K1) global atomics whatever the length of the track.
+#define FS_NT 256
+#define FS_MAX_BLOCKS 256
+#define FS_MAX_COUNTERS (2 + 3 * 256)
+
+__global__ __launch_bounds__(FS_NT) void frame_stats_seg_kernel(const float* __restrict__ mean, const unsigned char* __restrict__ labels,
+                                                              int L_total, int K1, unsigned long long* __restrict__ stats) {
+  __shared__ int part[FS_MAX_COUNTERS];
+  const int nc = 2 + 3 * K1;
+  for (int j = threadIdx.x; j < nc; j += FS_NT) part[j] = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  // every wave runs the same number of rounds (the ballots need whole waves): frames past the end are masked out
+  for (long base = (long)blockIdx.x * FS_NT; base < L_total; base += (long)gridDim.x * FS_NT) {
+    const long f = base + threadIdx.x;
+    const bool in = f < L_total;
+    const float* row = mean + (in ? f : 0) * K1;
+    float best = row[0];
+    int p = 0;
+    for (int k = 1; k < K1; ++k) {
+      const float x = row[k];
+      if (x > best) { best = x; p = k; }
+    }
+    const int t = in ? (int)labels[f] : 0;
+    const bool ok = in && t < K1;                                      // a label outside the columns is not followed
+    const unsigned long long m_in = __ballot(ok);
+    const unsigned long long m_err = __ballot(ok && p != t);
+    const unsigned long long m_tp = __ballot(ok && p != 0 && t != 0);
+    const unsigned long long m_fp = __ballot(ok && p != 0 && t == 0);
+    const unsigned long long m_fn = __ballot(ok && p == 0 && t != 0);
+    if (lane == 0) {
+      if (m_in) atomicAdd(&part[0], __popcll(m_in));
+      if (m_err) atomicAdd(&part[1], __popcll(m_err));
+      if (m_tp) atomicAdd(&part[2], __popcll(m_tp));
+      if (m_fp) atomicAdd(&part[3], __popcll(m_fp));
+      if (m_fn) atomicAdd(&part[4], __popcll(m_fn));
+    }
+    if (ok) {
+      if (p == t) {
+        if (p != 0) atomicAdd(&part[2 + 3 * p], 1);
+      } else {
+        if (p != 0) atomicAdd(&part[2 + 3 * p + 1], 1);
+        if (t != 0) atomicAdd(&part[2 + 3 * t + 2], 1);
+      }
+    }
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < nc; j += FS_NT) {
+    const int x = part[j];
+    if (x != 0) atomicAdd(stats + j, (unsigned long long)x);
+  }
+}
+
+extern "C" int tdeed_frame_stats_seg(const float* mean, const unsigned char* labels, int L_total, int K1, long* stats, void* stream) {
+  TD_CHECK(mean && labels && stats, "frame_stats_seg: null pointer");
+  TD_CHECK(L_total > 0 && K1 > 1 && K1 <= 256, "frame_stats_seg: %d frames, %d columns (2 to 256: the labels are bytes)", L_total, K1);
+  const int blocks = cdiv(L_total, FS_NT) < FS_MAX_BLOCKS ? cdiv(L_total, FS_NT) : FS_MAX_BLOCKS;
+  hipLaunchKernelGGL(frame_stats_seg_kernel, dim3(blocks), dim3(FS_NT), 0, (hipStream_t)stream, mean, labels, L_total, K1,
+                     reinterpret_cast<unsigned long long*>(stats));
+  TD_LAUNCH_CHECK("frame_stats_seg");
+  return TDEED_OK;
+}
+
 // =========================================================================== suppression
 // rank of class c among the classes that have a candidate, by (first candidate frame, class): the position of its label in
 // the host's high-recall list (`_by_label`).  -1: no candidate.  K1 is small, every thread computes it from scalars.

@@ -726,9 +726,168 @@ def map_suppress_entries(suppress, who):
     return suppress
 
 
+# ----------------------------------------------------------------------------- the mAP pass sharded over ranks
+def shard_videos(lengths, world):
+    """Who scores what in a validation pass sharded over `world` ranks: lengths in ordinal order -> `world` lists of ordinals
+    (ascending), every ordinal in exactly one.  Longest video first (equal lengths: the lower ordinal) to the least-loaded
+    rank, load counted in frames (equal loads: the lower rank) -- pure arithmetic on the lengths, so every rank computes the
+    same table without communicating.  The loads then differ by at most the longest video.  A rank's list is empty when
+    there are fewer videos than ranks."""
+    world = int(world)
+    lengths = [int(x) for x in lengths]
+    if world < 1 or any(x < 0 for x in lengths):
+        raise ValueError(f"shard_videos: world {world} and lengths >= 0")
+    load, out = [0] * world, [[] for _ in range(world)]
+    for o in sorted(range(len(lengths)), key=lambda o: (-lengths[o], o)):
+        r = min(range(world), key=lambda r: (load[r], r))
+        out[r].append(o)
+        load[r] += lengths[o]
+    return [sorted(x) for x in out]
+
+
+def parse_shard(shard, who="map_videos"):
+    """shard: None -> None; "auto" -> (rank, world) of the initialised default process group ((0, 1) without one); (rank,
+    world) -> itself as ints.  ValueError for anything else."""
+    if shard is None:
+        return None
+    if isinstance(shard, str):
+        if shard != "auto":
+            raise ValueError(f"{who}: shard must be None, 'auto' or (rank, world), not {shard!r}")
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            return dist.get_rank(), dist.get_world_size()
+        return 0, 1
+    try:
+        rank, world = shard
+        ok = int(rank) == rank and int(world) == world and 0 <= int(rank) < int(world)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{who}: shard must be None, 'auto' or (rank, world) with 0 <= rank < world, not {shard!r}")
+    return int(rank), int(world)
+
+
+def _ap_segments(ev_count, hit_count, vid_off, gt_off, K1):
+    """the segments of the exchange in payload order: two lists of (ordinal, index of the segment's first element in its
+    flattened store row, row, count) -- scores (e, c, ord), hits (e, t, ord*K1+c)"""
+    ev_count, hit_count = np.asarray(ev_count), np.asarray(hit_count)
+    E, C, NV = ev_count.shape
+    T = hit_count.shape[1]
+    sc = [(o, int(vid_off[o]), e * C + c, int(ev_count[e, c, o])) for e in range(E) for c in range(C) for o in range(NV)]
+    hc = [(oc // K1, int(gt_off[oc]), e * T + t, int(hit_count[e, t, oc])) for e in range(E) for t in range(T) for oc in range(NV * K1)]
+    return sc, hc
+
+
+def ap_pack_ref(ev_score, ev_count, hit_pos, hit_count, vid_off, gt_off, K1, own_ords):
+    """numpy restatement of ops.ap_state_pack: the stores of one rank (ev_score (E,K1-1,LT) float64, hit_pos (E,T,G) int32)
+    with the counts already summed over the ranks -> (scores float64 (S,), hits int32 (Hh,)): the used part of every segment
+    of own_ords at the exclusive scan of the counts, zeros elsewhere."""
+    own = set(int(o) for o in own_ords)
+    sc, hc = _ap_segments(ev_count, hit_count, vid_off, gt_off, K1)
+    ev_score, hit_pos = np.asarray(ev_score), np.asarray(hit_pos)
+    out = []
+    for segs, store, dt in ((sc, ev_score.reshape(-1, ev_score.shape[-1]), np.float64), (hc, hit_pos.reshape(-1, hit_pos.shape[-1]), np.int32)):
+        pay = np.zeros(sum(s[3] for s in segs), dt)
+        at = 0
+        for o, first, row, n in segs:
+            if o in own:
+                pay[at:at + n] = store[row, first:first + n]
+            at += n
+        out.append(pay)
+    return out[0], out[1]
+
+
+def ap_unpack_ref(ev_score, ev_count, hit_pos, hit_count, vid_off, gt_off, K1, own_ords, scores, hits):
+    """numpy restatement of ops.ap_state_unpack: writes the segments of the videos NOT in own_ords from the summed payloads
+    into ev_score / hit_pos, in place; own segments are not written."""
+    own = set(int(o) for o in own_ords)
+    sc, hc = _ap_segments(ev_count, hit_count, vid_off, gt_off, K1)
+    for segs, store, pay in ((sc, ev_score.reshape(-1, ev_score.shape[-1]), scores), (hc, hit_pos.reshape(-1, hit_pos.shape[-1]), hits)):
+        at = 0
+        for o, first, row, n in segs:
+            if o not in own:
+                store[row, first:first + n] = pay[at:at + n]
+            at += n
+
+
+def frame_stats_ref(mean, labels, K1=None):
+    """numpy restatement of ops.frame_stats_seg on one track: int64 (2 + 3*K1,) -- frames, errors, then (tp, fp, fn) for "any"
+    and every class, by the counting rule of `frame_events(labels=...)`."""
+    mean, true = np.asarray(mean), np.asarray(labels).astype(np.int64)
+    K1 = mean.shape[1] if K1 is None else int(K1)
+    pred = mean.argmax(axis=1)
+    out = np.zeros(2 + 3 * K1, np.int64)
+    out[0], out[1] = true.shape[0], int((true != pred).sum())
+    p_fg, t_fg = pred != 0, true != 0
+    out[2:5] = int((p_fg & t_fg).sum()), int((p_fg & ~t_fg).sum()), int((~p_fg & t_fg).sum())
+    for k in range(1, K1):
+        out[2 + 3 * k:5 + 3 * k] = (int(((pred == k) & (true == k)).sum()), int(((pred == k) & (true != k)).sum()),
+                                    int(((true == k) & (pred != k)).sum()))
+    return out
+
+
+def frame_stats_dict(counters, classes):
+    """The counter tensor of ops.frame_stats_seg (int64 (2 + 3*K1,), on the host) -> the stats dict `frame_events` returns as
+    its third value: "err", "f1", "tp_fp_fn", keyed None ("any") and the class indices of `classes` (name -> index)."""
+    c = [int(x) for x in np.asarray(counters).reshape(-1)]
+    keys = [None] + sorted(classes.values())
+    if len(c) < 2 + 3 * (max(keys[1:], default=0) + 1):
+        raise ValueError(f"frame_stats_dict: {len(c)} counters for the classes {keys[1:]}")
+    trip = {k: tuple(c[2 + 3 * (k or 0):5 + 3 * (k or 0)]) for k in keys}
+
+    def f1(k):
+        tp, fp, fn = trip[k]
+        den = tp + 0.5 * fp + 0.5 * fn
+        return tp / (den if den != 0 else 1)
+    return {"err": c[1] / max(c[0], 1), "f1": {k: f1(k) for k in keys}, "tp_fp_fn": trip}
+
+
+def check_labels(labels, lengths, K1, who):
+    """labels: per video an (L,) integer array -> the uint8 arrays; ValueError when a length differs from the video's or a
+    value lies outside 0..K1-1"""
+    out = []
+    for i, (lab, L) in enumerate(zip(labels, lengths)):
+        a = np.asarray(lab)
+        if a.ndim != 1 or a.shape[0] != int(L) or a.dtype.kind not in "iu":
+            raise ValueError(f"{who}: the labels of video {i} must be {int(L)} integers, got {a.dtype} {a.shape}")
+        if a.size and (int(a.min()) < 0 or int(a.max()) > K1 - 1):
+            raise ValueError(f"{who}: the labels of video {i} must lie in 0..{K1 - 1}")
+        out.append(a.astype(np.uint8))
+    return out
+
+
+def merge_ap_state(state, own_ords, group=None, frame_stats=None):
+    """Makes the ops.ApState of every rank of a sharded pass the state of a one-rank pass, as far as ops.ap_rank reads it:
+    the three phases of ops.ap_state_counts / ap_state_pack / ap_state_unpack with torch.distributed sums in between
+    (tdeed_amd.dist.init sets the default group up; device tensors go to all_reduce as they are, like GradReducer's torch
+    backend: gloo in tests, RCCL in production).  own_ords: the ordinals this rank matched.  frame_stats: the counter
+    tensor of ops.frame_stats_seg, summed with the count tables.  Every rank must call it.  Without an initialised process
+    group, or with one rank, nothing happens.  -> dict(exchange_bytes: bytes of all tensors handed to collectives,
+    host_syncs: 1 for the payload sizes, 0 when nothing happened)."""
+    import torch.distributed as dist
+    from . import ops
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return dict(exchange_bytes=0, host_syncs=0)
+    nbytes = 0
+
+    def total(x):
+        nonlocal nbytes
+        if x.numel():
+            dist.all_reduce(x, op=dist.ReduceOp.SUM, group=group)
+            nbytes += x.numel() * x.element_size()
+    counts = ops.ap_state_counts(state, own_ords)
+    for x in counts + ([frame_stats] if frame_stats is not None else []):
+        total(x)
+    scores, hits = ops.ap_state_pack(state, own_ords, owners=counts[2])
+    total(scores)
+    total(hits)
+    ops.ap_state_unpack(state, own_ords, scores, hits)
+    return dict(exchange_bytes=nbytes, host_syncs=1)
+
+
 def map_videos(model, videos, classes, truth, suppress, tolerances=(0, 1, 2, 4), high_recall_score_threshold=0.01, augment=False,
                batch_size=8, overlap_len=None, decode_ahead=1, group_videos=1, max_resident_bytes=16 << 30, reuse_frames=False,
-               decode="host", stream_frames=False):
+               decode="host", stream_frames=False, labels=None, shard=None):
     """`spot_videos` + `mean_average_precisions` per suppress entry with the whole tail on the device: no event list reaches the
     host.  videos and the keyword arguments as in `spot_videos`; truth: the records `mean_average_precisions` takes; suppress:
     entries ("raw",) -- the unsuppressed high-recall list -- or (kind, window, threshold) with kind "nms" | "snms".
@@ -736,7 +895,17 @@ def map_videos(model, videos, classes, truth, suppress, tolerances=(0, 1, 2, 4),
     come from the device (csrc/ap.hip), the mean over the truth's labels is taken here, in sorted label order.  The video
     ordinal -- the index of a video's name in sorted order -- decides ties between videos, whatever order the groups arrive
     in.  The host synchronises once per group and once for the (entries, tolerances, K+1) table; model.last_video_stats:
-    the groups' totals plus groups, host_syncs and ap_d2h_bytes."""
+    the groups' totals plus groups, host_syncs, ap_d2h_bytes, videos_own (videos this rank scored) and exchange_bytes (bytes
+    handed to collectives; 0 without an exchange).
+    labels: {video: (L,) ints}, the ground-truth class of every frame.  Then the frame error / foreground-F1 counters are
+    taken on the device as well (one more launch per group, ops.frame_stats_seg; they come back with the AP table) and the
+    function returns (results, stats), stats being the dict `frame_events(labels=...)` returns as its third value.
+    shard: None -- this process scores every video, no collective; "auto" -- rank and world of the initialised default
+    process group; (rank, world).  The call still takes the list of ALL videos: names and lengths define the ordinals and the
+    state.  `shard_videos` decides who scores what; the source of a video that belongs to another rank may be None and is
+    never touched.  Groups are cut from the rank's own videos, after the last group the states are exchanged
+    (`merge_ap_state`), and the rank + AP launch runs on every rank: every rank returns the same result, bit for bit the
+    one-rank pass.  host_syncs <= own groups + 2."""
     from . import ops
     videos = list(videos)
     suppress = map_suppress_entries(suppress, "map_videos")
@@ -749,33 +918,67 @@ def map_videos(model, videos, classes, truth, suppress, tolerances=(0, 1, 2, 4),
     length = {v[0]: int(v[1]) for v in videos}
     K1 = len(classes) + 1
     table = truth_table(truth, ordinal, classes)
+    shard = parse_shard(shard)
+    own_ords = None
+    if shard is not None:
+        own_ords = shard_videos([length[v] for v in names], shard[1])[shard[0]]
+        own = set(own_ords)
+        videos = [v for v in videos if ordinal[v[0]] in own]
+        if shard[1] > 1:
+            import torch.distributed as dist
+            if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() != shard[1]:
+                raise ValueError(f"map_videos: shard {shard} needs an initialised process group of {shard[1]} ranks")
+    missing = [v[0] for v in videos if v[3] is None]
+    if missing:
+        raise ValueError(f"map_videos: the videos {missing} are this rank's own and have no frame source")
+    if labels is not None:
+        if K1 > 256:
+            raise ValueError(f"map_videos: {K1} score columns do not fit one-byte labels")
+        absent = [v[0] for v in videos if v[0] not in labels]
+        if absent:
+            raise ValueError(f"map_videos: no labels for the videos {absent}")
+        check_labels([labels[v[0]] for v in videos], [v[1] for v in videos], K1, "map_videos")
     videos = _with_loader(videos, decode)
     reuse = dict(reuse_frames=True) if reuse_frames else {}
     if stream_frames:
         reuse["stream_frames"] = True
     state = ops.ap_state([length[v] for v in names], table, K1, len(suppress), tols, device=model.device)
+    counters = None
+    if labels is not None:
+        import torch
+        counters = torch.zeros((ops.frame_stats_size(K1),), dtype=torch.int64, device=state.device)
     totals, groups = defaultdict(int), 0
-    for group in _decoded_groups(videos, group_videos, max_resident_bytes, decode_ahead, stream_frames):
+    for group in _decoded_groups(videos, group_videos, max_resident_bytes, decode_ahead, stream_frames) if videos else ():
+        with_labels = {} if labels is None else dict(labels=[labels[g[0]] for g in group], frame_stats=counters)
         model.map_video_group([g[3] for g in group], classes, state, [ordinal[g[0]] for g in group], suppress=suppress,
                               high_recall_score_threshold=high_recall_score_threshold, overlap_len=overlap_len,
-                              batch_size=batch_size, augment=augment, max_resident_bytes=max_resident_bytes, **reuse)
+                              batch_size=batch_size, augment=augment, max_resident_bytes=max_resident_bytes, **reuse, **with_labels)
         groups += 1
         for k, v in model.last_video_stats.items():
             if k in ("ring_frames", "ring_chunks", "resident_bytes"):       # (of the groups that streamed: the largest ring)
                 totals[k] = max(totals[k], v)
             elif k != "views":
                 totals[k] += v
-    ap, _ = model.map_finish(state)
+    merged = dict(exchange_bytes=0, host_syncs=0) if shard is None else merge_ap_state(state, own_ords, frame_stats=counters)
+    if counters is None:
+        ap, _ = model.map_finish(state)
+    else:
+        ap, _, counters = model.map_finish(state, frame_stats=counters)
     for k, v in model.last_video_stats.items():
         totals[k] += v
     totals["groups"] = groups
+    totals["host_syncs"] += merged["host_syncs"]
+    totals["exchange_bytes"] = merged["exchange_bytes"]
+    totals["videos_own"] = len(videos)
     model.last_video_stats = dict(totals)
     inv = {v: k for k, v in classes.items()}
-    labels = sorted(inv[c] for c in range(1, K1) if state.totals[c] > 0)
+    labelled = sorted(inv[c] for c in range(1, K1) if state.totals[c] > 0)
     out = []
     for i in range(len(suppress)):
-        aps = {lab: [float(ap[i, t, classes[lab]]) for t in range(len(tols))] for lab in labels}
+        aps = {lab: [float(ap[i, t, classes[lab]]) for t in range(len(tols))] for lab in labelled}
         out.append(([float(np.mean([aps[lab][t] for lab in aps])) for t in range(len(tols))], aps))
+    if labels is not None:
+        return out, frame_stats_dict(counters, classes)
     return out
 
 

@@ -564,14 +564,19 @@ class TDEEDModel:
 
     def map_video_group(self, frames_list, classes, state, ordinals, suppress=(("nms", 1, 0.01), ("snms", 3, 0.01)),
                         high_recall_score_threshold=0.01, clip_starts=None, overlap_len=None, pad_len=5, batch_size=8,
-                        augment=False, use_amp=True, max_resident_bytes=16 << 30, reuse_frames=False, stream_frames=False):
+                        augment=False, use_amp=True, max_resident_bytes=16 << 30, reuse_frames=False, stream_frames=False,
+                        labels=None, frame_stats=None):
         """spot_video_group's pipeline for a mAP pass (evalutil.map_videos): the group is scored as one packed job, then on the
         packed track one event launch, per entry of `suppress` its suppression launch (none for ("raw",), the unsuppressed
         high-recall list) and the segment + match launch (ops.ap_match_seg), which leaves the group's ordered predictions and
         hits in `state` (ops.ap_state, one per dataset, as many entries as `suppress`).  ordinals: per video its index among
         the dataset's sorted names.  Nothing is copied to the host -- no pred, no event list; the host synchronises once, so
         that the resident buffers outlive the stream work.  Returns state.  last_video_stats: the group's totals, host_syncs
-        1, ap_d2h_bytes 0."""
+        1, ap_d2h_bytes 0.
+        labels (per video of the group an (L,) integer array, the ground-truth class of every frame) and frame_stats (the int64
+        (2 + 3*(K+1),) device tensor of ops.frame_stats_seg) go together: one more launch on the packed track adds the
+        group's frame error / foreground-F1 counters to frame_stats.  A length that differs from the video's or a value
+        outside 0..K raises ValueError before any launch."""
         who = "map_video_group"
         from . import evalutil
         frames_list = list(frames_list)
@@ -589,6 +594,18 @@ class TDEEDModel:
         if len(ordinals) != len(frames_list) or len(set(ordinals)) != len(ordinals) \
                 or any(not 0 <= o < state.NV or state.lengths[o] != int(fr.shape[0]) for o, fr in zip(ordinals, frames_list)):
             raise ValueError(f"{who}: ordinals {ordinals} do not name {len(frames_list)} videos of the state's dataset by length")
+        h_labels = None
+        if (labels is None) != (frame_stats is None):
+            raise ValueError(f"{who}: labels and frame_stats go together")
+        if labels is not None:
+            labels = list(labels)
+            if len(labels) != len(frames_list):
+                raise ValueError(f"{who}: {len(labels)} label tracks for {len(frames_list)} videos")
+            packed = evalutil.check_labels(labels, [int(fr.shape[0]) for fr in frames_list], K1, who)
+            if not isinstance(frame_stats, torch.Tensor) or frame_stats.dtype != torch.int64 or not frame_stats.is_cuda \
+                    or tuple(frame_stats.shape) != (ops.frame_stats_size(K1),):
+                raise ValueError(f"{who}: frame_stats must be an int64 ({ops.frame_stats_size(K1)},) device tensor")
+            h_labels = torch.from_numpy(np.concatenate(packed)).pin_memory()
         _, _, mean, s0, stats, keep, g = self._packed_track(who, frames_list, clip_starts, overlap_len, pad_len, batch_size,
                                                             augment, use_amp, max_resident_bytes, want_mean=True,
                                                             reuse_frames=reuse_frames, stream_frames=stream_frames)
@@ -606,17 +623,23 @@ class TDEEDModel:
                     planes = ops.nms_track_seg(mean, g.seg_off_dev, g.max_len, e[1], e[2], e[0] == "snms", first, hr,
                                                planes=True)[5:]
                 ops.ap_match_seg(state, i, mean, g.seg_off_dev, ords, g.max_len, hr, planes=planes)
+            if h_labels is not None:
+                lab = torch.empty((mean.shape[0],), dtype=torch.uint8, device=mean.device)
+                lab.copy_(h_labels, non_blocking=True)
+                ops.frame_stats_seg(mean, lab, frame_stats)
             s0.synchronize()
-        del keep, h_ords
+        del keep, h_ords, h_labels
         stats["host_syncs"] = 1
         stats["ap_d2h_bytes"] = 0
         self.last_video_stats = stats
         return state
 
-    def map_finish(self, state):
+    def map_finish(self, state, frame_stats=None):
         """The end of a mAP pass: rank + AP over everything the groups left in `state` (ops.ap_rank), then the one copy of the
         pass: -> (ap float64 (entries, tolerances, K+1), hits int32 of that shape) numpy.  One host synchronisation;
-        last_video_stats: host_syncs 1 and ap_d2h_bytes, 12 bytes per (entry, tolerance, column) whatever the events."""
+        last_video_stats: host_syncs 1 and ap_d2h_bytes, 12 bytes per (entry, tolerance, column) whatever the events.
+        frame_stats: the counter tensor the groups accumulated (map_video_group(labels=...)); it rides in the same copy and
+        follows as a third entry (int64 numpy), 8 more bytes per counter in ap_d2h_bytes."""
         if not isinstance(state, ops.ApState):
             raise TypeError("map_finish: state must come from ops.ap_state")
         from .streams import new_stream
@@ -630,8 +653,14 @@ class TDEEDModel:
             h_n = torch.empty(nhits.shape, dtype=torch.int32).pin_memory()
             h_ap.copy_(ap, non_blocking=True)
             h_n.copy_(nhits, non_blocking=True)
+            if frame_stats is not None:
+                h_fs = torch.empty(frame_stats.shape, dtype=torch.int64).pin_memory()
+                h_fs.copy_(frame_stats, non_blocking=True)
             s0.synchronize()
         self.last_video_stats = dict(host_syncs=1, ap_d2h_bytes=ap.numel() * 12)
+        if frame_stats is not None:
+            self.last_video_stats["ap_d2h_bytes"] += frame_stats.numel() * 8
+            return h_ap.numpy().copy(), h_n.numpy().copy(), h_fs.numpy().copy()
         return h_ap.numpy().copy(), h_n.numpy().copy()
 
     frame_batch = 2                     # clips' worth of frames per launch of the per-frame pass (reuse_frames=True)

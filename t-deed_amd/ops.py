@@ -1150,6 +1150,124 @@ def ap_rank(state):
     return ap, nhits, rank
 
 
+# ---- a mAP pass sharded over ranks: every rank matches its own videos, then the states are exchanged (three phases, each
+# returning or taking the tensors that go through a sum over the ranks; evalutil.merge_ap_state is the glue)
+def _own_table(state, own_ords, who):
+    """own_ords -> (sorted tuple, int32 (NV,) device table: 1 for the ordinals this rank matched), cached on the state"""
+    if not isinstance(state, ApState):
+        raise TypeError(f"{who}: state must come from ap_state")
+    key = tuple(sorted(int(o) for o in own_ords))
+    if len(set(key)) != len(key) or any(not 0 <= o < state.NV for o in key):
+        raise ValueError(f"{who}: own ordinals {list(key)} must be distinct videos of the state's {state.NV}")
+    cached = getattr(state, "_own", None)
+    if cached is None or cached[0] != key:
+        tab = np.zeros(state.NV, np.int32)
+        tab[list(key)] = 1
+        state._own = (key, torch.from_numpy(tab).to(state.device))
+    return state._own
+
+
+def ap_state_counts(state, own_ords):
+    """Phase 1 of the exchange -> [state.ev_count, state.hit_count, owners]: the int32 tensors to be summed over the ranks IN
+    PLACE (a caller that sums elsewhere copies the sums back into them).  The two count tables are zero wherever this rank
+    matched nothing; owners int32 (NV,) is 1 for own_ords, so its sum must be 1 everywhere: ap_state_pack checks it."""
+    _, own = _own_table(state, own_ords, "ap_state_counts")
+    return [state.ev_count, state.hit_count, own.clone()]
+
+
+def ap_owner_errors(owners):
+    """The ordinals the summed ownership table names more than once / never, as the RuntimeError every rank raises before any
+    payload is built (None when every video was matched exactly once).  Host arithmetic only."""
+    owners = np.asarray(owners).reshape(-1)
+    twice = np.nonzero(owners > 1)[0].tolist()
+    never = np.nonzero(owners < 1)[0].tolist()
+    if not twice and not never:
+        return None
+    return RuntimeError(f"ap_state: the ranks do not partition the videos: ordinals scored twice {twice}, never {never}")
+
+
+def _ap_scans(state):
+    sc_end = torch.cumsum(state.ev_count.view(-1), 0, dtype=torch.int64)
+    hc_end = torch.cumsum(state.hit_count.view(-1), 0, dtype=torch.int64)
+    return sc_end, hc_end
+
+
+def ap_state_pack(state, own_ords, owners=None):
+    """Phase 2, once state.ev_count / state.hit_count hold the sums over the ranks -> (scores float64 (S,), hits int32 (Hh,)),
+    S = sum(ev_count), Hh = sum(hit_count): the dense payloads with this rank's own segments in place and zeros elsewhere, to
+    be summed over the ranks (every element is written by one rank, scores are not negative: x + 0.0 is exact).  Segment (e,
+    c, ord) of the scores starts at the exclusive scan of ev_count in the store's own order, segment (e, t, ord*K1+c) of the
+    hits at that of hit_count.  owners: the summed ownership table of ap_state_counts; it is read in the one host
+    synchronisation that sizes the payloads, and a video matched twice or never raises ap_owner_errors' RuntimeError before
+    a payload exists."""
+    key, own = _own_table(state, own_ords, "ap_state_pack")
+    dev = state.device
+    sc_end, hc_end = _ap_scans(state)
+    parts = [sc_end[-1:], hc_end[-1:]]
+    if owners is not None:
+        _chk_table(owners, state.NV, dev, "ap_state_pack", "owners")
+        parts.append(owners.to(torch.int64))
+    small = torch.cat(parts)
+    h_small = torch.empty(small.shape, dtype=torch.int64).pin_memory()
+    h_small.copy_(small, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    vals = h_small.numpy()
+    if owners is not None:
+        err = ap_owner_errors(vals[2:])
+        if err is not None:
+            raise err
+    S, Hh = int(vals[0]), int(vals[1])
+    scores = torch.zeros((S,), dtype=torch.float64, device=dev)
+    hits = torch.zeros((Hh,), dtype=torch.int32, device=dev)
+    call("tdeed_ap_state_pack", ptr(state.ev_score), ptr(state.hit_pos), ptr(scores) if S else None, ptr(hits) if Hh else None,
+         ptr(sc_end), ptr(hc_end), S, Hh, ptr(own), ptr(state.vid_off), ptr(state.gt_off), state.NV, state.K1, state.E, state.T,
+         state.LT, state.G, stream_ptr())
+    return scores, hits
+
+
+def ap_state_unpack(state, own_ords, scores, hits):
+    """Phase 3: writes the segments of the videos that are NOT in own_ords from the summed payloads into state.ev_score /
+    state.hit_pos; own segments are not written.  ev_frame of foreign videos is left as it is -- ap_rank does not read it, so
+    after the exchange the state answers ap_rank like a one-rank pass, but its ev_frame is only this rank's share."""
+    key, own = _own_table(state, own_ords, "ap_state_unpack")
+    dev = state.device
+    for x, dt, what in ((scores, torch.float64, "scores float64"), (hits, torch.int32, "hits int32")):
+        if not isinstance(x, torch.Tensor) or x.dtype != dt or x.dim() != 1 or not x.is_contiguous() or x.device != dev:
+            raise ValueError(f"ap_state_unpack: {what} must be a contiguous 1-d tensor on the state's device")
+    sc_end, hc_end = _ap_scans(state)
+    S, Hh = scores.numel(), hits.numel()
+    call("tdeed_ap_state_unpack", ptr(state.ev_score), ptr(state.hit_pos), ptr(scores) if S else None, ptr(hits) if Hh else None,
+         ptr(sc_end), ptr(hc_end), S, Hh, ptr(own), ptr(state.vid_off), ptr(state.gt_off), state.NV, state.K1, state.E, state.T,
+         state.LT, state.G, stream_ptr())
+
+
+def frame_stats_size(K1):
+    """entries of the frame counter tensor: frames, errors, then (tp, fp, fn) for "any" and every class"""
+    return 2 + 3 * int(K1)
+
+
+def frame_stats_seg(mean, labels_u8, stats=None):
+    """The frame error / foreground-F1 counters of evalutil.frame_events(labels=...) over a packed track: mean fp32 (sum L,K1),
+    labels_u8 uint8 (sum L,) the ground-truth class of every packed frame (K1 <= 256, values < K1), both on the device.  stats
+    int64 (2 + 3*K1,) is accumulated into (fresh zeros when None) and returned: [0] frames, [1] frames whose arg-max (first
+    maximum, np.argmax) differs from the label, then (tp, fp, fn) at 2 + 3*k for k = 0 ("any") and the classes k >= 1
+    (evalutil.frame_stats_dict turns it into frame_events' stats dict).  One asynchronous launch on the current stream."""
+    L, K1 = _chk_track(mean, "frame_stats_seg")
+    dev = mean.device
+    if K1 > 256:
+        raise ValueError(f"frame_stats_seg: {K1} columns do not fit one-byte labels")
+    if not isinstance(labels_u8, torch.Tensor) or labels_u8.dtype != torch.uint8 or tuple(labels_u8.shape) != (L,) \
+            or not labels_u8.is_contiguous() or labels_u8.device != dev:
+        raise ValueError(f"frame_stats_seg: labels must be a contiguous uint8 ({L},) tensor on the track's device")
+    if stats is None:
+        stats = torch.zeros((frame_stats_size(K1),), dtype=torch.int64, device=dev)
+    elif not isinstance(stats, torch.Tensor) or stats.dtype != torch.int64 or tuple(stats.shape) != (frame_stats_size(K1),) \
+            or not stats.is_contiguous() or stats.device != dev:
+        raise ValueError(f"frame_stats_seg: stats must be a contiguous int64 ({frame_stats_size(K1)},) tensor on the track's device")
+    call("tdeed_frame_stats_seg", ptr(mean), ptr(labels_u8), L, K1, ptr(stats), stream_ptr())
+    return stats
+
+
 def cast_bf16(src_f32):
     out = torch.empty(src_f32.shape, dtype=torch.bfloat16, device=src_f32.device)
     call("tdeed_cast_f32_to_bf16", ptr(src_f32), ptr(out), src_f32.numel(), stream_ptr())

@@ -14,6 +14,11 @@
     python tools/bench_video.py --map [--map-videos 24]                 validation mAP: spot_videos + mean_average_precisions
                                                                         against map_videos, one JSON line, also written to
                                                                         profiles/video_map.json
+    python tools/bench_video.py --map --ranks 2                         the validation pass sharded over ranks: child
+                                                                        processes of this script, each step under a time limit
+                                                                        (one rank with and without shard / labels, the exchange
+                                                                        alone, then 2 ranks sharing the GPU), one JSON line,
+                                                                        also written to profiles/video_map_sharded.json
     python tools/bench_video.py --reuse [--frames 2030]                 predict_video against predict_video(reuse_frames=
                                                                         True), one JSON line, also written to --out
     python tools/bench_video.py --ring [--frames 2030]                  predict_video resident against predict_video(
@@ -341,13 +346,9 @@ def group(a):
     return 0
 
 
-def map_bench(a):
-    """Two routes from the same synthetic videos and model to the mAP tables of a validation pass, alternating: (a)
-    `evalutil.spot_videos` + `mean_average_precisions` per suppress entry (event lists to the host, dicts, the Python walk),
-    (b) `evalutil.map_videos` (segment + match per group and one rank + AP launch on the device, one small table back).  Per
-    route: wall time over `--repeats` passes, host synchronisations and device-to-host bytes of one pass.  The two results
-    must agree within max(1, total) * 2^-52 per AP (summation order).  No speed-up is promised: route (a)'s time on the same
-    box in the same run is what route (b) is read against."""
+def _map_workload(a):
+    """the synthetic validation split of --map: the 200MF model, `--map-videos` videos of the diving split's lengths with
+    hashed frames, a ground-truth event every 20 frames, two suppress entries, five tolerances"""
     from tdeed_amd.model import TDEEDModel
     from types import SimpleNamespace
     m = TDEEDModel(device="cuda", args=SimpleNamespace(modality="rgb", temporal_arch="ed_sgp_mixer", pretrain=None, **CFG))
@@ -366,6 +367,17 @@ def map_bench(a):
     # a ground-truth event every 20 frames, the classes in turn
     truth = [{"video": f"v{i:03d}", "events": [{"label": f"c{1 + (f // 20) % K}", "frame": f} for f in range(7, L, 20)]}
              for i, L in enumerate(lengths)]
+    return m, classes, suppress, tols, lengths, off, vids, truth
+
+
+def map_bench(a):
+    """Two routes from the same synthetic videos and model to the mAP tables of a validation pass, alternating: (a)
+    `evalutil.spot_videos` + `mean_average_precisions` per suppress entry (event lists to the host, dicts, the Python walk),
+    (b) `evalutil.map_videos` (segment + match per group and one rank + AP launch on the device, one small table back).  Per
+    route: wall time over `--repeats` passes, host synchronisations and device-to-host bytes of one pass.  The two results
+    must agree within max(1, total) * 2^-52 per AP (summation order).  No speed-up is promised: route (a)'s time on the same
+    box in the same run is what route (b) is read against."""
+    m, classes, suppress, tols, lengths, off, vids, truth = _map_workload(a)
     totals = {lab: sum(1 for x in truth for e in x["events"] if e["label"] == lab) for lab in classes}
     seen = dict(syncs=0, d2h=0)
     real_sync, real_group = torch.cuda.Stream.synchronize, m.spot_video_group
@@ -498,6 +510,253 @@ def _map_tail(a, tols):
                 host_one_pass=host, host_total_s=round(sum(v for k, v in host.items() if k.endswith("_s")), 3),
                 device_ms_median=dev_ms, d2h_bytes_device=int(ap.size) * 8, maps_host=maps, max_abs_ap_diff=worst,
                 agree_within_bound=bool(ok))
+
+
+# ----------------------------------------------------------------------------- --map --ranks N: the pass sharded over ranks
+def _frame_labels(truth, lengths, classes):
+    """the truth records as per-frame labels: the class at every ground-truth frame, background elsewhere"""
+    out = {}
+    for x, L in zip(truth, lengths):
+        lab = np.zeros(L, np.int64)
+        for e in x["events"]:
+            lab[e["frame"]] = classes[e["label"]]
+        out[x["video"]] = lab
+    return out
+
+
+def _passes(routes, repeats):
+    """one warm-up pass of every route, then `repeats` timed passes with the routes alternating -> ({route: last result},
+    {route: [seconds]})"""
+    res = {k: fn() for k, fn in routes.items()}
+    times = {k: [] for k in routes}
+    for _ in range(repeats):
+        for k, fn in routes.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res[k] = fn()
+            torch.cuda.synchronize()
+            times[k].append(time.perf_counter() - t0)
+    return res, times
+
+
+def _ms(v):
+    tt = np.asarray(v) * 1e3
+    return dict(ms_median=round(float(np.median(tt)), 2), ms_min=round(float(tt.min()), 2), ms_max=round(float(tt.max()), 2))
+
+
+def _map_sharded_one(a):
+    """(a) one process, one rank: `map_videos` as it always ran against the same call with shard=(0, 1) and labels (one more
+    launch per group, the merge skipped); (b) the exchange alone on the noise tail.  One JSON line."""
+    m, classes, suppress, tols, lengths, off, vids, truth = _map_workload(a)
+    labels = _frame_labels(truth, lengths, classes)
+    kw = dict(batch_size=8, group_videos=a.group_videos)
+    stats = {}
+
+    def plain():
+        r = E.map_videos(m, vids, classes, truth, suppress, tols, **kw)
+        stats["plain"] = dict(m.last_video_stats)
+        return r
+
+    def sharded():
+        r = E.map_videos(m, vids, classes, truth, suppress, tols, labels=labels, shard=(0, 1), **kw)
+        stats["shard_0_1_labels"] = dict(m.last_video_stats)
+        return r
+    routes = dict(plain=plain) if a.shard_step == "plain" else dict(plain=plain, shard_0_1_labels=sharded)
+    res, times = _passes(routes, a.repeats)
+    rec = dict(device=torch.cuda.get_device_name(0), measured_on_gpu=True, lib_flavour=os.environ.get("TDEED_LIB_FLAVOUR", ""),
+               videos=len(lengths), frames=int(off[-1]), suppress=suppress, tolerances=tols,
+               routes={k: dict(_ms(v), host_syncs=stats[k]["host_syncs"], groups=stats[k]["groups"]) for k, v in times.items()},
+               maps=[r[0] for r in res["plain"]])
+    if a.shard_step == "one":
+        rec["equal"] = bool(res["shard_0_1_labels"][0] == res["plain"])
+        rec["frame_stats"] = dict(err=res["shard_0_1_labels"][1]["err"], f1_any=res["shard_0_1_labels"][1]["f1"][None])
+        if a.map_tail_videos:
+            rec["exchange_tail"] = _exchange_tail(a, tols)
+    print(json.dumps(rec))
+    return 0
+
+
+def _exchange_tail(a, tols):
+    """The exchange alone at the upper end: `_map_tail`'s noise tracks split over two pretend ranks by `shard_videos`, each
+    with a state of its own; timed: the sums a collective would take (torch adds standing in for it), pack, unpack on both
+    states -- next to the rank + AP launch of the same run."""
+    nv, L, K1, hr = a.map_tail_videos, 3000, 13, 0.01
+    rng = np.random.RandomState(1)
+    tracks = []
+    for _ in range(nv):
+        x = rng.rand(L, K1).astype(np.float32)
+        tracks.append(np.ascontiguousarray(x / x.sum(axis=1, keepdims=True), np.float32))
+    names = [f"t{i:03d}" for i in range(nv)]
+    classes = {f"c{k}": k for k in range(1, K1)}
+    truth = [{"video": v, "events": [{"label": f"c{1 + (f // 20) % (K1 - 1)}", "frame": f} for f in range(7, L, 20)]} for v in names]
+    entries = (("raw",), ("nms", 1, 0.10))
+    table = E.truth_table(truth, {v: i for i, v in enumerate(names)}, classes)
+    split = E.shard_videos([L] * nv, 2)
+
+    def filled(own):
+        state = ops.ap_state([L] * nv, table, K1, len(entries), tols, "cuda")
+        mean = torch.from_numpy(np.concatenate([tracks[o] for o in own])).cuda()
+        seg_off = torch.tensor(np.arange(len(own) + 1) * L, dtype=torch.int32, device="cuda")
+        ords = torch.tensor(own, dtype=torch.int32, device="cuda")
+        first = ops.frame_events_seg(mean, seg_off, L, hr)[2]
+        for i, e in enumerate(entries):
+            planes = None if e[0] == "raw" else ops.nms_track_seg(mean, seg_off, L, e[1], e[2], e[0] == "snms", first, hr,
+                                                                  planes=True)[5:]
+            ops.ap_match_seg(state, i, mean, seg_off, ords, L, hr, planes=planes)
+        return state
+    one = filled(list(range(nv)))
+    states = [filled(own) for own in split]
+    own_counts = [(s.ev_count.clone(), s.hit_count.clone()) for s in states]
+    nbytes = [0]
+
+    def exchange():
+        counts = [ops.ap_state_counts(s, own) for s, own in zip(states, split)]
+        sums = [counts[0][j] + counts[1][j] for j in range(3)]
+        for c in counts:
+            for j in range(3):
+                c[j].copy_(sums[j])
+        pays = [ops.ap_state_pack(s, own, owners=c[2]) for s, own, c in zip(states, split, counts)]
+        scores, hits = pays[0][0] + pays[1][0], pays[0][1] + pays[1][1]
+        for s, own in zip(states, split):
+            ops.ap_state_unpack(s, own, scores, hits)
+        nbytes[0] = sum(x.numel() * x.element_size() for x in sums + [scores, hits])
+    t_x, t_r = [], []
+    for i in range(a.repeats + 1):
+        for s, (ec, hc) in zip(states, own_counts):                     # every pass starts from the ranks' own counts
+            s.ev_count.copy_(ec)
+            s.hit_count.copy_(hc)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        exchange()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        ap = ops.ap_rank(states[0])[0]
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        if i:                                                           # the first pass is the warm-up
+            t_x.append(t1 - t0)
+            t_r.append(t2 - t1)
+    want = ops.ap_rank(one)[0]
+    same = bool(torch.equal(ap, want) and torch.equal(ops.ap_rank(states[1])[0], want))
+    return dict(videos=nv, frames_per_video=L, K1=K1, entries=entries, tolerances=tols, pretend_ranks=2,
+                events=int(one.ev_count.sum()), hits=int(one.hit_count.sum()), exchange_bytes=nbytes[0],
+                store_bytes_not_sent=int(one.ev_score.numel() * 12), exchange_both_ranks=_ms(t_x), ap_rank=_ms(t_r),
+                ap_equal_to_one_rank=same,
+                note="the sums between the phases are torch adds in one process, not a collective")
+
+
+def _map_sharded_rank(a):
+    """one rank of the sharded pass (RANK / WORLD_SIZE from the launching parent, gloo: the ranks share this box's GPU)"""
+    from tdeed_amd import dist as tdist
+    import torch.distributed as dist
+    torch.cuda.set_device(0)
+    rank, _, world = tdist.init(backend=os.environ.get("TDEED_DIST_BACKEND", "gloo"))
+    m, classes, suppress, tols, lengths, off, vids, truth = _map_workload(a)
+    labels = _frame_labels(truth, lengths, classes)
+    names = sorted(v[0] for v in vids)
+    ordinal = {v: i for i, v in enumerate(names)}
+    length = {v[0]: v[1] for v in vids}
+    own = set(E.shard_videos([length[v] for v in names], world)[rank])
+    vids = [v if ordinal[v[0]] in own else (v[0], v[1], v[2], None) for v in vids]        # foreign sources: None
+    stats = {}
+
+    def sharded():
+        dist.barrier()
+        r = E.map_videos(m, vids, classes, truth, suppress, tols, labels=labels, shard="auto", batch_size=8,
+                         group_videos=a.group_videos)
+        stats.update(m.last_video_stats)
+        return r
+    res, times = _passes(dict(sharded=sharded), a.repeats)
+    mine = torch.tensor([[stats["videos_own"], stats["frames"], stats["host_syncs"], stats["groups"], stats["exchange_bytes"]]],
+                        dtype=torch.int64)
+    every = [torch.zeros_like(mine) for _ in range(world)]
+    dist.all_gather(every, mine)
+    if rank == 0:
+        keys = ("videos_own", "frames", "host_syncs", "groups", "exchange_bytes")
+        print(json.dumps(dict(world=world, backend=dist.get_backend(), rank0_pass=_ms(times["sharded"]),
+                              ranks=[dict(zip(keys, x.view(-1).tolist())) for x in every], maps=[r[0] for r in res["sharded"][0]],
+                              frame_stats=dict(err=res["sharded"][1]["err"], f1_any=res["sharded"][1]["f1"][None]))))
+    dist.barrier()
+    dist.destroy_process_group()
+    return 0
+
+
+def map_sharded(a):
+    """`--map --ranks N`: profiles/video_map_sharded.json.  This process never touches the GPU; every step is a fresh child
+    process of this script under a time limit of its own, and the first bad exit status ends the run:
+      one     one rank: map_videos against map_videos(shard=(0, 1), labels=...), and the exchange alone on the noise tail
+      parent  (when csrc/libtdeed_hip_parent.so exists, tools/build_ab.py parent <rev> ap.hip spot.hip) map_videos on the
+              parent commit's kernels
+      ranks   N ranks that share the GPU over gloo, each scoring its share: evidence that the route runs, not a speed-up"""
+    if a.shard_step in ("one", "plain"):
+        return _map_sharded_one(a)
+    if a.shard_step == "ranks":
+        return _map_sharded_rank(a)
+    import socket
+    import subprocess
+    me = os.path.abspath(__file__)
+    base = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, me, "--map", "--ranks", str(a.ranks), "--repeats",
+            str(a.repeats), "--map-videos", str(a.map_videos), "--map-tail-videos", str(a.map_tail_videos), "--group-videos",
+            str(a.group_videos)]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+
+    def line(out):
+        got = [ln for ln in out.splitlines() if ln.startswith("{")]
+        return json.loads(got[-1]) if got else None
+
+    def step(name, extra_env=None):
+        r = subprocess.run(base + ["--shard-step", name], env=dict(env, **(extra_env or {})), cwd=ROOT, stdout=subprocess.PIPE, text=True)
+        if r.returncode != 0 or line(r.stdout) is None:
+            sys.stderr.write(f"bench_video --map --ranks: step {name} ended with status {r.returncode}\n")
+            sys.exit(r.returncode or 1)
+        return line(r.stdout)
+    rec = dict(kind="video_map_sharded", cfg=CFG, repeats=a.repeats, group_videos=a.group_videos, batch_size=8)
+    rec["one_rank"] = step("one")
+    if os.path.exists(os.path.join(ROOT, "t-deed_amd", "csrc", "libtdeed_hip_parent.so")):
+        rec["parent_commit_kernels"] = step("plain", dict(TDEED_LIB_FLAVOUR="parent"))
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    procs = []
+    for r in range(a.ranks):
+        renv = dict(env, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(a.ranks), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
+                    HSA_ENABLE_IPC_MODE_LEGACY="0")
+        procs.append(subprocess.Popen(base + ["--shard-step", "ranks"], env=renv, cwd=ROOT, text=True,
+                                      stdout=(subprocess.PIPE if r == 0 else subprocess.DEVNULL)))
+    out0 = []
+    import threading
+    rd = threading.Thread(target=lambda: out0.append(procs[0].stdout.read()), daemon=True)
+    rd.start()
+    while any(p.poll() is None for p in procs):                         # a rank that dies would leave the others waiting
+        if any(p.poll() not in (None, 0) for p in procs):
+            for p in procs:
+                if p.poll() is None:
+                    p.terminate()
+        time.sleep(0.2)
+    rd.join(timeout=10)
+    bad = [p.returncode for p in procs if p.returncode != 0]
+    if bad or line("".join(out0)) is None:
+        sys.stderr.write(f"bench_video --map --ranks: the ranks ended with {[p.returncode for p in procs]}\n")
+        sys.exit(bad[0] if bad else 1)
+    rec["ranks"] = line("".join(out0))
+    one = rec["one_rank"]["routes"]
+    ref = rec.get("parent_commit_kernels", rec["one_rank"])["routes"]["plain"]
+    rec["one_rank_cost"] = dict(
+        reference="map_videos on the parent commit's kernels" if "parent_commit_kernels" in rec else "map_videos, this commit",
+        reference_ms_median=ref["ms_median"], reference_spread_ms=round(ref["ms_max"] - ref["ms_min"], 2),
+        shard_0_1_labels_ms_median=one["shard_0_1_labels"]["ms_median"], plain_ms_median=one["plain"]["ms_median"],
+        within_reference_plus_spread=bool(one["shard_0_1_labels"]["ms_median"] <= ref["ms_median"] + (ref["ms_max"] - ref["ms_min"])))
+    rec["sharded_equals_one_rank"] = bool(rec["ranks"]["maps"] == rec["one_rank"]["maps"]
+                                          and rec["ranks"]["frame_stats"] == rec["one_rank"]["frame_stats"])
+    rec["note"] = (f"{a.ranks} ranks share ONE GPU here: their pass time shows that the route runs, no speed-up is claimed or "
+                   "expected; the 1 -> N curve has never been measured on multi-GPU hardware")
+    out = os.path.join(ROOT, "profiles", "video_map_sharded.json")
+    with open(out, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print(json.dumps(rec))
+    return 0 if rec["sharded_equals_one_rank"] and rec["one_rank"]["equal"] else 1
 
 
 def reuse(a):
@@ -1001,6 +1260,11 @@ if __name__ == "__main__":
     ap.add_argument("--map", action="store_true", help="spot_videos + mean_average_precisions against map_videos")
     ap.add_argument("--map-videos", type=int, default=24, help="--map: videos of the synthetic diving split")
     ap.add_argument("--map-tail-videos", type=int, default=40, help="--map: noise tracks of the tail-only measurement (0: skip it)")
+    ap.add_argument("--ranks", type=int, default=0,
+                    help="--map: the pass sharded over this many ranks, self-launched as child processes that share the GPU "
+                         "(profiles/video_map_sharded.json)")
+    ap.add_argument("--shard-step", default=None, choices=["one", "plain", "ranks"], help="--map --ranks: set by the launching parent")
+    ap.add_argument("--step-timeout", type=int, default=420, help="--map --ranks: seconds every child step may take")
     ap.add_argument("--reuse", action="store_true", help="predict_video against predict_video(reuse_frames=True)")
     ap.add_argument("--ring", action="store_true", help="predict_video resident against the frame ring (stream_frames=True)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "video_frame_reuse.json"), help="--reuse: where the JSON goes")
@@ -1023,5 +1287,5 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if a.frames is None:
         a.frames = 5625 if a.spot else 2030
-    sys.exit(streamed_jpeg(a) if a.resident_jpeg and a.stream_clips else resident_jpeg(a) if a.resident_jpeg else ring(a) if a.ring else map_bench(a) if a.map else decode_device(a) if a.decode_device else decode(a) if a.decode else gather_only(a) if a.gather_only else reuse(a) if a.reuse else group(a) if a.group
+    sys.exit(streamed_jpeg(a) if a.resident_jpeg and a.stream_clips else resident_jpeg(a) if a.resident_jpeg else ring(a) if a.ring else map_sharded(a) if a.map and a.ranks else map_bench(a) if a.map else decode_device(a) if a.decode_device else decode(a) if a.decode else gather_only(a) if a.gather_only else reuse(a) if a.reuse else group(a) if a.group
              else spot(a) if a.spot else bench(a))
