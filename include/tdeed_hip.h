@@ -420,6 +420,40 @@ int tdeed_adamw_step(float* param, const float* grad, float* exp_avg, float* exp
                      float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
                      void* stream);
 
+/* ---- guarded optimizer step (opt-in; see train.hip) -------------------------------------------------------------
+ * What the reference's GradScaler did for the optimizer (modules.py:390-404: scaler.step() leaves the optimizer and
+ * its step count untouched when a gradient holds an inf or a NaN) and clip_grad_norm_'s rule, with no host
+ * synchronisation and legal under stream capture.
+ *
+ * grad_guard: statistics of the flat fp32 gradient buffer, two launches.  Pass one sums g*g in binary64 (the square of an
+ *   fp32 value is exact there, and up to 2^31 of them cannot overflow, so the sum is finite exactly when every element
+ *   is: a buffer of FLT_MAX counts as finite) into one partial per workgroup in `ws`; pass two (one workgroup) folds the
+ *   partials in a fixed order and writes the record.  No atomics: the bits do not depend on which workgroup runs when.
+ *   `ws`: tdeed_grad_guard_ws_bytes(n) bytes (at most 4096 * 8), 8-byte aligned.  `guard`: the caller's record, 32 bytes,
+ *   16-byte aligned, zero before the first call:
+ *       offset  0  double  sumsq      this call's sum of squares of the raw buffer (before any grad_scale)
+ *       offset  8  int32   nonfinite  this call: 1 when the buffer holds an inf or a NaN, else 0
+ *       offset 12  int32   skipped    cumulative: pass two adds `nonfinite` to it when skip_nonfinite is set; nothing else
+ *                                     writes it
+ *       offset 16  16 bytes reserved, written as zero
+ * adamw_step_guarded: tdeed_adamw_step behind that record (the same update code).
+ *   skip_nonfinite != 0 and nonfinite != 0: the launch writes nothing (param, exp_avg, exp_avg_sq keep their bits).
+ *   max_grad_norm > 0: grad_scale is multiplied by min(1, max_grad_norm / (grad_scale * sqrt(sumsq) + 1e-6)), torch's
+ *     clip_grad_norm_ applied to the norm of the gradient AdamW sees (the mean over ranks and micro-batches); a coefficient
+ *     of 1 leaves grad_scale's bits alone; <= 0 means off.  With clipping on and skipping off a non-finite norm poisons
+ *     the update exactly as clip_grad_norm_(error_if_nonfinite=False) followed by step() does.
+ *   `step` stays the caller's count of ATTEMPTS (from 1).  While skipped == 0 the bias corrections are the host's, computed
+ *     as tdeed_adamw_step computes them: on finite gradients without clipping the launch is bit-identical to
+ *     tdeed_adamw_step.  Once skipped != 0 the effective step is step - skipped and the corrections come from the
+ *     device's powf, which may differ from glibc's by a few ulp.
+ *   The betas are fp32 here as in tdeed_adamw_step: beta2 = 0.999 arrives as float32(0.999) and 1 - beta2 is 9.99987e-04,
+ *     so exp_avg_sq sits a relative 1.29e-05 from an optimizer run at the decimal 0.999 (param does not show it). */
+long tdeed_grad_guard_ws_bytes(long n);
+int tdeed_grad_guard(const float* grad, long n, int skip_nonfinite, void* guard, void* ws, void* stream);
+int tdeed_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr,
+                             float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                             const void* guard, int skip_nonfinite, float max_grad_norm, void* stream);
+
 /* ---- post-proc (modules.py:406-426): softmax over the first K1 columns then scatter-max of
  * frame t onto clamp(t - rne(displ), 0, T-1).  scores fp32 [B][T][K1] (zero-initialised inside),
  * cls int64 [B][T] = argmax. */

@@ -155,10 +155,11 @@ extern "C" int tdeed_heads_bwd(const float* dout, const void* x, int rows, int C
 //   p *= 1 - lr*wd;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;
 //   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // grad_scale multiplies g first (1/world for the data-parallel mean, 1/loss-scale ...).  16-byte vectorised.
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                    float* __restrict__ m, float* __restrict__ v, long n, float lr,
-                                                    float b1, float b2, float eps, float wd, float bc1, float bc2s,
-                                                    float gscale) {
+// One body for the plain and the guarded kernel (adamw_kernel / adamw_guarded_kernel below).
+__device__ __forceinline__ void adamw_update(float* __restrict__ p, const float* __restrict__ g,
+                                             float* __restrict__ m, float* __restrict__ v, long n, float lr,
+                                             float b1, float b2, float eps, float wd, float bc1, float bc2s,
+                                             float gscale) {
   const long n4 = n >> 2;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
     f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
@@ -187,6 +188,19 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   }
 }
 
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                    float* __restrict__ m, float* __restrict__ v, long n, float lr,
+                                                    float b1, float b2, float eps, float wd, float bc1, float bc2s,
+                                                    float gscale) {
+  adamw_update(p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2s, gscale);
+}
+
+// grid of the flat-buffer kernels: one 16-byte chunk per thread and trip, at most 4096 workgroups of 256
+static int flat_grid(long n) {
+  const long n4 = n >> 2;
+  return (int)(n4 / 256 + 1 < 4096 ? n4 / 256 + 1 : 4096);
+}
+
 extern "C" int tdeed_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n,
                                 float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                                 float grad_scale, void* stream) {
@@ -196,11 +210,132 @@ extern "C" int tdeed_adamw_step(float* param, const float* grad, float* exp_avg,
            "adamw: buffers must be 16-byte aligned");
   const float bc1 = 1.0f - powf(beta1, (float)step);
   const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
-  const long n4 = n >> 2;
-  const int grid = (int)(n4 / 256 + 1 < 4096 ? n4 / 256 + 1 : 4096);
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, n,
-                     lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale);
+  hipLaunchKernelGGL(adamw_kernel, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
+                     n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale);
   TD_LAUNCH_CHECK("adamw");
+  return TDEED_OK;
+}
+
+// ------------------------------------------------------------------------------------------ guarded AdamW
+// What the reference's GradScaler did for the optimizer (modules.py:390-404: scaler.step() leaves the optimizer and its
+// step count alone when a gradient holds an inf or a NaN), plus clip_grad_norm_'s rule, without a host synchronisation.
+// The statistic both need is the sum of squares of the flat gradient buffer in binary64: the square of an fp32 value is
+// exact there and up to 2^31 of them cannot overflow, so the sum is finite exactly when every element is (a buffer of
+// FLT_MAX is finite).  Two launches, no atomics, fixed fold order: the bits do not depend on which workgroup runs when.
+struct GuardRecord {            // include/tdeed_hip.h: 32 bytes, owned by the caller
+  double sumsq;                 // this call, raw buffer (before grad_scale)
+  int nonfinite;                // this call, 0 | 1
+  int skipped;                  // cumulative: grad_guard_fold_kernel alone writes it
+  int reserved[4];
+};
+static_assert(sizeof(GuardRecord) == 32, "guard record layout");
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// 4 waves; thread 0's return value is the workgroup's sum (waves folded in index order)
+__device__ __forceinline__ double block_sum_f64(double v, double* scratch) {
+  v = wave_sum_f64(v);
+  if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3];
+}
+
+// pass one: part[blockIdx.x] = sum of g^2 over the chunks this workgroup walks (+ the scalar tail in workgroup 0)
+__global__ __launch_bounds__(256) void grad_guard_partial_kernel(const float* __restrict__ g, long n,
+                                                                 double* __restrict__ part) {
+  __shared__ double scratch[4];
+  const long n4 = n >> 2;
+  double acc = 0.0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc = fma((double)gv[e], (double)gv[e], acc);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const double t = (double)g[(n4 << 2) + threadIdx.x];
+    acc = fma(t, t, acc);
+  }
+  acc = block_sum_f64(acc, scratch);
+  if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+// pass two: one workgroup; thread t takes partials t, t + 256, ... in index order, then the same fixed fold
+__global__ __launch_bounds__(256) void grad_guard_fold_kernel(const double* __restrict__ part, int nparts,
+                                                              int skip_nonfinite, GuardRecord* __restrict__ rec) {
+  __shared__ double scratch[4];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += 256) acc += part[i];
+  acc = block_sum_f64(acc, scratch);
+  if (threadIdx.x == 0) {
+    const int bad = __builtin_isfinite(acc) ? 0 : 1;
+    const int skipped = rec->skipped + (skip_nonfinite ? bad : 0);
+    rec->sumsq = acc;
+    rec->nonfinite = bad;
+    rec->skipped = skipped;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) rec->reserved[e] = 0;
+  }
+}
+
+extern "C" long tdeed_grad_guard_ws_bytes(long n) { return n > 0 ? (long)flat_grid(n) * (long)sizeof(double) : 0; }
+
+extern "C" int tdeed_grad_guard(const float* grad, long n, int skip_nonfinite, void* guard, void* ws, void* stream) {
+  TD_CHECK(grad && guard && ws, "grad_guard: null pointer");
+  TD_CHECK(n > 0, "grad_guard: bad n");
+  TD_CHECK((((uintptr_t)grad | (uintptr_t)guard) & 15) == 0 && ((uintptr_t)ws & 7) == 0,
+           "grad_guard: grad and the record must be 16-byte aligned, the workspace 8-byte aligned");
+  const int grid = flat_grid(n);
+  hipLaunchKernelGGL(grad_guard_partial_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, grad, n, (double*)ws);
+  hipLaunchKernelGGL(grad_guard_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)ws, grid,
+                     skip_nonfinite, (GuardRecord*)guard);
+  TD_LAUNCH_CHECK("grad_guard");
+  return TDEED_OK;
+}
+
+// adamw_update behind the record (every thread reads it once; the addresses are uniform).  bc1 / bc2s are the host's, for
+// the host's count of attempts `step`: they are used as they are while nothing was skipped, so that on finite gradients
+// without clipping this launch writes the bits adamw_kernel writes.  After a skip the effective step is step - skipped and
+// the corrections come from the device's powf (a few ulp from glibc's).
+__global__ __launch_bounds__(256) void adamw_guarded_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                            float* __restrict__ m, float* __restrict__ v, long n, float lr,
+                                                            float b1, float b2, float eps, float wd, float bc1, float bc2s,
+                                                            float gscale, int step, const GuardRecord* __restrict__ rec,
+                                                            int skip_nonfinite, float max_norm) {
+  const double sumsq = rec->sumsq;
+  const int nonfinite = rec->nonfinite, skipped = rec->skipped;
+  if (skip_nonfinite && nonfinite) return;
+  if (max_norm > 0.0f) {
+    // clip_grad_norm_: coef = clamp(max_norm / (norm + 1e-6), max=1), the norm being that of the gradient AdamW sees.
+    // A NaN norm gives a NaN coefficient (torch's clamp keeps it), an infinite one 0: not special-cased.
+    const float norm = (float)((double)gscale * sqrt(sumsq));
+    const float q = max_norm / (norm + 1e-6f);
+    gscale *= q > 1.0f ? 1.0f : q;
+  }
+  if (skipped != 0) {
+    const float t = (float)(step - skipped);
+    bc1 = 1.0f - powf(b1, t);
+    bc2s = sqrtf(1.0f - powf(b2, t));
+  }
+  adamw_update(p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2s, gscale);
+}
+
+extern "C" int tdeed_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n,
+                                        float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                        float grad_scale, const void* guard, int skip_nonfinite, float max_grad_norm,
+                                        void* stream) {
+  TD_CHECK(param && grad && exp_avg && exp_avg_sq && guard, "adamw_guarded: null pointer");
+  TD_CHECK(n > 0 && step >= 1, "adamw_guarded: bad n/step");
+  TD_CHECK((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)guard) & 15) == 0,
+           "adamw_guarded: buffers and the record must be 16-byte aligned");
+  const float bc1 = 1.0f - powf(beta1, (float)step);
+  const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
+  hipLaunchKernelGGL(adamw_guarded_kernel, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+                     exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, step,
+                     (const GuardRecord*)guard, skip_nonfinite, max_grad_norm);
+  TD_LAUNCH_CHECK("adamw_guarded");
   return TDEED_OK;
 }
 

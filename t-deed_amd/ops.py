@@ -708,6 +708,41 @@ def adamw_step(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), e
     return param
 
 
+GUARD_WORDS = 8        # the guard record of tdeed_grad_guard as int32 words: [sumsq lo, hi, nonfinite, skipped, 4 reserved]
+
+
+def grad_guard_ws(n, device):
+    """The workspace tdeed_grad_guard wants for a flat buffer of n elements (one binary64 partial per workgroup)."""
+    return torch.empty(_lib.load().tdeed_grad_guard_ws_bytes(int(n)) // 8, dtype=torch.float64, device=device)
+
+
+def grad_guard(grad, guard, ws, skip_nonfinite=False):
+    """Statistics of the flat fp32 gradient buffer into the 32-byte record `guard` (int32 (8,), zero before the first call):
+    binary64 sum of squares, non-finite flag and, with skip_nonfinite, the cumulative count of skipped steps."""
+    _chk(grad, "grad_guard buffer", torch.float32)
+    _chk(guard, "guard record", torch.int32)
+    _chk(ws, "grad_guard workspace", torch.float64)
+    if guard.numel() != GUARD_WORDS or ws.numel() * 8 < _lib.load().tdeed_grad_guard_ws_bytes(grad.numel()):
+        raise ValueError("grad_guard: the record is 8 int32 words, the workspace grad_guard_ws(n) elements")
+    call("tdeed_grad_guard", ptr(grad), grad.numel(), int(bool(skip_nonfinite)), ptr(guard), ptr(ws), stream_ptr())
+    return guard
+
+
+def adamw_step_guarded(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01,
+                       grad_scale=1.0, guard=None, skip_nonfinite=False, max_grad_norm=None):
+    """adamw_step behind the record grad_guard wrote for `grad`: nothing is written when skip_nonfinite is set and the
+    gradient held an inf / NaN; max_grad_norm clips by the global norm (clip_grad_norm_'s rule); `step` counts attempts."""
+    for t_ in (param, grad, exp_avg, exp_avg_sq):
+        _chk(t_, "adamw buffer", torch.float32)
+    _chk(guard, "guard record", torch.int32)
+    if guard is None or guard.numel() != GUARD_WORDS:
+        raise ValueError("adamw_step_guarded: needs the record grad_guard wrote (8 int32 words)")
+    call("tdeed_adamw_step_guarded", ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), float(lr),
+         float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step), float(grad_scale), ptr(guard),
+         int(bool(skip_nonfinite)), 0.0 if max_grad_norm is None else float(max_grad_norm), stream_ptr())
+    return param
+
+
 def process_prediction(head_out, B, T, K1, displ_col, out=None):
     """out: optional contiguous fp32 (B,T,K1) tensor (e.g. a slice of a per-video score buffer) to write the scores into."""
     ld = head_out.shape[-1]

@@ -511,12 +511,19 @@ class TrainEngine:
 class HipAdamW(torch.optim.Optimizer):
     """What `TDEEDModel.get_optimizer` returns: a torch.optim.Optimizer whose single "parameter" is the flat fp32
     buffer and whose step() is the fused AdamW launch, so the reference's LR schedulers (LinearLR + CosineAnnealingLR
-    chained, train_tdeed.py:79-87) drive it unchanged through param_groups[0]['lr']."""
+    chained, train_tdeed.py:79-87) drive it unchanged through param_groups[0]['lr'].
+    skip_nonfinite / max_grad_norm (opt-in, `FusedAdamW.set_guard`): what the reference's GradScaler did for the optimizer
+    -- a step whose gradients hold an inf or a NaN changes nothing -- and clipping by the global norm.  Both sit in
+    param_groups[0] and are read at every step(), like lr.  An LR scheduler steps whether or not the update was skipped,
+    as in the reference."""
 
-    def __init__(self, engine: TrainEngine, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01):
+    def __init__(self, engine: TrainEngine, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, skip_nonfinite=False,
+                 max_grad_norm=None):
         self.engine = engine
         engine.opt.lr, engine.opt.betas, engine.opt.eps, engine.opt.wd = lr, betas, eps, weight_decay
-        super().__init__([engine.params.flat], dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        engine.opt.set_guard(skip_nonfinite, max_grad_norm)
+        super().__init__([engine.params.flat], dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                                    skip_nonfinite=skip_nonfinite, max_grad_norm=max_grad_norm))
 
     def zero_grad(self, set_to_none=False):
         self.engine.opt.zero_grad()
@@ -526,4 +533,23 @@ class HipAdamW(torch.optim.Optimizer):
         g = self.param_groups[0]
         o = self.engine.opt
         o.betas, o.eps, o.wd = g["betas"], g["eps"], g["weight_decay"]
+        if (g["skip_nonfinite"], g["max_grad_norm"]) != (o.skip_nonfinite, o.max_grad_norm):
+            o.set_guard(g["skip_nonfinite"], g["max_grad_norm"])
         self.engine.apply(lr=g["lr"], all_reduce=all_reduce)
+
+    def guard_stats(self):
+        """`FusedAdamW.guard_stats`: dict(skipped, last_nonfinite, last_norm); one device synchronisation."""
+        return self.engine.opt.guard_stats()
+
+    def state_dict(self):
+        """torch's state_dict (param_groups) with the fused optimizer's state next to it under "fused": exp_avg,
+        exp_avg_sq, t, skipped (`FusedAdamW.state_dict`)."""
+        sd = super().state_dict()
+        sd["fused"] = self.engine.opt.state_dict()
+        return sd
+
+    def load_state_dict(self, state_dict):
+        sd = dict(state_dict)
+        fused = sd.pop("fused")
+        super().load_state_dict(sd)
+        self.engine.opt.load_state_dict(fused)
