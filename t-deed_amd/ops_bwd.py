@@ -151,18 +151,19 @@ def sgp_branch_bwd(o, g, ks, up, dw, db, d_o=None, ldo=None, ldg=None, ld_do=Non
     return d_o, ddw, ddb
 
 
-def upsample_bwd(d_xu, T_lo, ld=None, B=None, T_hi=None, C=None):
+def upsample_bwd(d_xu, T_lo, ld=None, B=None, T_hi=None, C=None, out=None):
     if B is None:
         B, T_hi, C = d_xu.shape
-    out = torch.empty((B, T_lo, C), dtype=d_xu.dtype, device=d_xu.device)
+    if out is None:
+        out = torch.empty((B, T_lo, C), dtype=d_xu.dtype, device=d_xu.device)
     call("tdeed_upsample_bwd", ptr(d_xu), (C if ld is None else ld), B, T_hi, T_lo, C, ptr(out), dtype_code(d_xu.dtype),
          stream_ptr())
     return out
 
 
-def maxpool_bwd(x, dy):
+def maxpool_bwd(x, dy, out=None):
     B, T_in, C = x.shape
-    dx = torch.empty_like(x)
+    dx = torch.empty_like(x) if out is None else out
     call("tdeed_maxpool_bwd", ptr(x), ptr(dy), B, T_in, dy.shape[1], C, ptr(dx), dtype_code(x.dtype), stream_ptr())
     return dx
 

@@ -43,6 +43,34 @@ The SGP stage (sgp_fused.hip, sgp_tile.h, sgp_gemm.hip, sgp.hip) adds, with u = 
                          the output, inside the existing transcendental term 16 u (|x| + |f(x)|) >= 9.5e-7 |x|
                          (test_roundoff_sgp_host.py measures it, with both intrinsics pushed one ulp either way)
 
+The temporal stage's backward kernels (sgp_bwd.hip) add, all operands exact (a launch receives bf16 or fp32 tensors as they are):
+
+  normalisation backward two passes in fp32: m = s / n as above, then q = sum (x - m_k)^2 around the KERNEL's mean m_k.  Exactly
+                         sum (x - m_k)^2 = sum (x - m)^2 + n (m_k - m)^2, so the mean's error moves var by at most d_m^2; the
+                         rounding of the differences, squares, the sum and the division is (n + 4) 2^-23 var: no cancellation
+                         term of magnitude E[x^2] (moments()' one-pass d_var is an upper bound of this).  xhat = (x - m) rstd:
+                         d_xhat = rstd (d_m + u |x - m|) + |x - m| d_rstd + u |xhat|.  g = dy w (u |g|), s1 = mean g and
+                         s2 = mean g xhat carry the doubled summation bound over n terms, inner = g - s1 - xhat s2 the
+                         cancellation term 4 2^-23 (|g| + |s1| + |xhat s2|), dx = rstd inner:
+                         d_dx = rstd d_inner + |inner| d_rstd + u |dx|; `accumulate` adds the old value in fp32 (one more
+                         add) IN FRONT OF the one rounding of the store.  The parameter sums dw = sum dy xhat, db = sum dy are
+                         fp32 sums over `rows` terms in any order (per wave, per workgroup, reduce_partials):
+                         sum |dy| d_xhat + rows 2^-23 sum |dy xhat|
+  depthwise branch       the forward products again (dwconv, scale_shift, mean_T above), d psi = g (cw + ckw), d s = g psi by the
+                         product rule, the input gradient one fma chain over 3 + 2 ks + up terms (contraction rule), sums over
+                         T and over the clips by the summation rule.  The ReLU gate of phi is discontinuous: the bound holds
+                         for channels with |pre| > d_pre, `branch_bwd_ref` counts the others and the tests assert there are none
+  up-sampling backward   the transpose of the forward: a gather over T_hi with the weights 1 - l1, l1.  The fp32 position is off
+                         by at most T_hi 2^-23, which moves both weights by that much, and, where the position lies that close
+                         to a node, moves the contribution to the node on the other side of it
+  max-pool backward      the first maximum of a window takes its gradient (exact operands: exact ties); an input collects at
+                         most 3 windows: the summation rule
+  GELU backward          dy (cdf + x pdf): the transcendental term on |x|, |cdf| and |x pdf| (erff, expf), times |dy|
+  weight gradient        dW = dY^T X is the contraction rule with K = M rows, db an M-term sum, `accumulate` one more add.  At
+                         M >= 4096 the worst case (M + 4) 2^-23 sum |a| |b| is about 2 % of a typical element: no defect hides
+                         from BIT EQUALITY on exact operands instead (sgp_bwd_cases.exact_operand: every partial sum an fp32
+                         number, so the accumulation is exact in any order, on MFMA or VALU, through any number of slices)
+
 The first-order rule for rstd FAILS as var -> 0 (d_var / (var + eps) is no longer small, and with q/n >> var the cancellation
 term alone exceeds var): the bound is stated for rows and groups with var >= E[x^2] / 32, which `first_order` returns and the
 tests assert on every reference.
@@ -459,6 +487,202 @@ def cat_fc_ref(A, W, bias):
     """MODE 2 before its store: GELU(A W^T + b) in fp32 (B, T, N)"""
     B, T, K = A.shape
     return reshape(gelu(linear(rows(exact(A)), W, None, bias)), B, T, -1)
+
+
+# ----------------------------------------------------------------------------- the temporal stage's backward kernels
+def sum_over(v, dims, nterms=None):
+    """fp32 sum of v over dims, in any order: the summation rule with n = the number of terms"""
+    n = int(np.prod([v.ref.shape[i] for i in dims])) if nterms is None else nterms
+    return RB(v.ref.sum(dims), v.d.sum(dims) + n * 2.0 ** -23 * v.ref.abs().sum(dims))
+
+
+def two_pass_stats(x, dims, eps):
+    """mean, then the variance around the kernel's own mean (see the module docstring); statistics keep their dims"""
+    n = int(np.prod([x.ref.shape[i] for i in dims]))
+    a = x.ref.abs()
+    m = x.ref.sum(dims, keepdim=True) / n
+    d_m = (x.d.sum(dims, keepdim=True) + n * 2.0 ** -23 * a.sum(dims, keepdim=True)) / n + U_F32 * m.abs()
+    ex2 = (x.ref * x.ref).sum(dims, keepdim=True) / n
+    var = ((x.ref - m) ** 2).sum(dims, keepdim=True) / n
+    d_var = d_m * d_m + (n + 4) * 2.0 ** -23 * (var + d_m * d_m)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    return Stats(m, d_m, rstd, rstd * (d_var / (2 * (var + eps)) + 2 * U_F32), var, ex2), n
+
+
+def _norm_bwd(x, dy, w, dims, pdims, eps, base):
+    """x, dy exact, w broadcast to them; statistics over dims, parameter sums over pdims -> (dx, dw, db, Stats)"""
+    st, n = two_pass_stats(x, dims, eps)
+    xm = x.ref - st.m
+    xhat = RB(xm * st.rstd, st.rstd * (st.d_m + U_F32 * xm.abs()) + xm.abs() * st.d_rstd + st.d_m * st.d_rstd
+              + U_F32 * (xm * st.rstd).abs())
+    g = product(dy, RB(w, torch.zeros_like(w)))
+    def mean(v):                                                          # an n-term fp32 sum, one division
+        s_ = v.ref.sum(dims, keepdim=True) / n
+        return RB(s_, (v.d.sum(dims, keepdim=True) + n * 2.0 ** -23 * v.ref.abs().sum(dims, keepdim=True)) / n + U_F32 * s_.abs())
+
+    s1, s2 = mean(g), mean(product(g, xhat))
+    xs2 = product(xhat, s2)
+    inner = g.ref - s1.ref - xs2.ref
+    d_inner = g.d + s1.d + xs2.d + 4 * 2.0 ** -23 * (g.ref.abs() + s1.ref.abs() + xs2.ref.abs())
+    dx = inner * st.rstd
+    dx = RB(dx, st.rstd * d_inner + inner.abs() * st.d_rstd + d_inner * st.d_rstd + U_F32 * dx.abs())
+    if base is not None:
+        dx = total(dx, RB(f64(base).view(dx.ref.shape), torch.zeros_like(dx.ref)))
+    rows = int(np.prod([x.ref.shape[i] for i in pdims]))
+    p = dy.ref * xhat.ref
+    dw = RB(p.sum(pdims), (dy.ref.abs() * xhat.d).sum(pdims) + rows * 2.0 ** -23 * p.abs().sum(pdims))
+    db = RB(dy.ref.sum(pdims), rows * 2.0 ** -23 * dy.ref.abs().sum(pdims))
+    return dx, dw, db, st
+
+
+def layernorm_bwd_ref(x, dy, w, eps=1e-5, base=None):
+    """layernorm_bwd_kernel on x, dy (rows, C): -> (dx in fp32 before the store, dw (C), db (C)), Stats per row.
+    base: the old contents of dx under `accumulate` (added in fp32 in front of the store)"""
+    dx, dw, db, st = _norm_bwd(exact(x), exact(dy), f64(w).view(1, -1), (1,), (0,), eps, base)
+    return (dx, dw, db), Stats(*[v.reshape(-1) for v in st])
+
+
+def groupnorm_bwd_ref(x, dy, G, w, eps=1e-5, base=None):
+    """groupnorm_bwd_kernel on x, dy (B, T, C): the same algebra over a [T][C / G] slab; the per-channel parameter sums run
+    over T in the launch, then over B in reduce_partials"""
+    B, T, C = x.shape
+    v5 = lambda a: RB(a.ref.view(B, T, G, C // G), a.d.view(B, T, G, C // G))    # noqa: E731
+    dx, dw, db, st = _norm_bwd(v5(exact(x)), v5(exact(dy)), f64(w).view(1, 1, G, C // G), (1, 3), (0, 1), eps,
+                               None if base is None else f64(base).view(B, T, G, C // G))
+    return (reshape(dx, B, T, C), reshape(dw, C), reshape(db, C)), Stats(*[v.reshape(B, G) for v in st])
+
+
+def _corr_T(v, w):
+    """sum_k w[c][k] v[t + K // 2 - k] with zero padding: the transpose of dwconv's taps -> (ref, |w| d_v, |w| |v|)"""
+    w = f64(w).flip(-1)
+    C, K = w.shape
+    cv = lambda a, k: F.conv1d(a.transpose(1, 2), k.unsqueeze(1), padding=K // 2, groups=C).transpose(1, 2)   # noqa: E731
+    return cv(v.ref, w), cv(v.d, w.abs()), cv(v.ref.abs(), w.abs())
+
+
+def shifted(o, off):
+    """o[:, t + off] with zeros outside: (B, T, C) fp64"""
+    T = o.shape[1]
+    out = torch.zeros_like(o)
+    lo, hi = max(0, -off), min(T, T - off)
+    if lo < hi:
+        out[:, lo:hi] = o[:, lo + off:hi + off]
+    return out
+
+
+def branch_bwd_ref(o, g_conv, g_inst, g_id, ks, up, dw, db):
+    """branch_bwd_core in fp64 on exact o and gradients (B, T, C) -> (d_o in fp32 before the store, d_dw (C, 2 ks + up + 2),
+    d_db (5, C) in _dwpack's layout, parts, number of (clip, channel) pairs with |pre| <= d_pre: outside the bound's claim)"""
+    oe, gc, gi, gd = exact(o), exact(g_conv), exact(g_inst), exact(g_id)
+    B, T, C = oe.ref.shape
+    p = dw_split(dw, db, ks, up)
+    psi, s = dwconv(oe, *p["psi"]), total(dwconv(oe, *p["cw"]), dwconv(oe, *p["ckw"]))
+    dpsi, ds = product(gc, s), product(gc, psi)                               # zero outside [0, T): the LDS halo
+    fc = scale_shift(oe, *p["fc"])
+    mean = mean_T(oe)
+    pre = scale_shift(mean, *p["g"])
+    phi = relu(pre)
+    unsure = int((pre.ref.abs() <= pre.d).sum())
+    op = (pre.ref > 0).double()
+    bc = lambda v: RB(v.ref.unsqueeze(1), v.d.unsqueeze(1))                   # noqa: E731  (B, C) -> (B, 1, C)
+    dphi = sum_over(product(gi, fc), (1,))
+    dpre = RB(dphi.ref * op, dphi.d * op)
+    wf, wg = f64(p["fc"][0]), f64(p["g"][0])
+    dmean = RB(dpre.ref * wg / T, wg.abs() * dpre.d / T + 2 * U_F32 * (dpre.ref * wg / T).abs())
+    inst = product(gi, bc(product(RB(wf.expand(B, C), torch.zeros(B, C, dtype=torch.float64)), phi)))
+    lin, lin_d, lin_mag = [sum(v) for v in zip(_corr_T(dpsi, p["psi"][0]), _corr_T(ds, p["cw"][0]), _corr_T(ds, p["ckw"][0]))]
+    head_mag = gd.ref.abs() + inst.ref.abs() + dmean.ref.abs().unsqueeze(1)
+    d_o = RB(gd.ref + inst.ref + dmean.ref.unsqueeze(1) + lin,
+             inst.d + dmean.d.unsqueeze(1) + lin_d + (2 * ks + up + 3 + 4) * 2.0 ** -23 * (head_mag + lin_mag))
+    # weight gradients: one fma chain over T per (clip, tap, channel), then the clips in reduce_partials: B T terms
+    cols = []
+    for src, K, in ((dpsi, ks), (ds, ks), (ds, up)):
+        for k in range(K):
+            osh = shifted(oe.ref, k - K // 2)
+            cols.append(sum_over(RB(src.ref * osh, src.d * osh.abs()), (0, 1)))
+    s_go, s_g = sum_over(product(gi, oe), (1,)), sum_over(gi, (1,))
+    cols.append(sum_over(product(phi, s_go), (0,)))
+    cols.append(sum_over(product(dpre, mean), (0,)))
+    d_dw = RB(torch.stack([c_.ref for c_ in cols], 1), torch.stack([c_.d for c_ in cols], 1))
+    b_psi, b_s = sum_over(dpsi, (0, 1)), sum_over(ds, (0, 1))
+    rows5 = [b_psi, b_s, b_s, sum_over(product(phi, s_g), (0,)), sum_over(dpre, (0,))]
+    d_db = RB(torch.stack([r.ref for r in rows5]), torch.stack([r.d for r in rows5]))
+    parts = dict(identity=gd.ref, inst=inst.ref, gate=lin, dmean=dmean.ref, phi=phi, pre=pre, dpsi=dpsi, ds=ds)
+    return d_o, d_dw, d_db, parts, unsure
+
+
+def upsample_bwd_ref(d_xu, T_lo):
+    """upsample_bwd_kernel: d_xn[j] = sum_t wgt(t, j) d_xu[t] over (B, T_hi, C), one fma chain over the contributing t"""
+    g = f64(d_xu)
+    B, T_hi, C = g.shape
+    if T_hi == T_lo:
+        return exact(d_xu)
+    pos = torch.arange(T_hi, dtype=torch.float64) * ((T_lo - 1) / (T_hi - 1) if T_hi > 1 else 0.0)
+    i0 = pos.floor().long().clamp(max=T_lo - 1)
+    i1 = (i0 + 1).clamp(max=T_lo - 1)
+    l1 = pos - i0
+    dpos = T_hi * 2.0 ** -23
+    W = torch.zeros(T_hi, T_lo, dtype=torch.float64)                          # the weights
+    E = torch.zeros(T_hi, T_lo, dtype=torch.float64)                          # what the position error can move
+    tt = torch.arange(T_hi)
+    W[tt, i0] += 1.0 - l1
+    W[tt, i1] += l1
+    E[tt, i0] += dpos
+    E[tt, i1] += dpos
+    below = (l1 <= dpos) & (i0 > 0)                                           # the kernel may floor to i0 - 1
+    above = (1.0 - l1 <= dpos) & (i0 + 2 <= T_lo - 1)                         # or to i0 + 1, whose upper node is i0 + 2
+    E[tt[below], i0[below] - 1] += dpos
+    E[tt[above], i0[above] + 2] += dpos
+    E = E.clamp(max=dpos)
+    nterms = int((W != 0).sum(0).max()) + 2
+    ein = lambda M_, v: torch.einsum("tj,btc->bjc", M_, v)                     # noqa: E731
+    return RB(ein(W, g), ein(E, g.abs()) + (nterms + 6) * 2.0 ** -23 * ein(W, g.abs()))
+
+
+def maxpool_bwd_ref(x, dy):
+    """maxpool_bwd_kernel: the FIRST maximum of each window of x (B, T_in, C) takes that window's dy (B, T_out, C)"""
+    xx, g = f64(x), f64(dy)
+    B, T_in, C = xx.shape
+    ref, mag, cnt = torch.zeros_like(xx), torch.zeros_like(xx), torch.zeros_like(xx)
+    for i, (lo, hi) in enumerate(pool_windows(T_in, g.shape[1])):
+        at_max = xx[:, lo:hi] == xx[:, lo:hi].amax(1, keepdim=True)
+        first = at_max & at_max.double().cumsum(1).eq(1)                     # the first of equal maxima
+        ref[:, lo:hi] += first * g[:, i:i + 1]
+        mag[:, lo:hi] += first * g[:, i:i + 1].abs()
+        cnt[:, lo:hi] += first
+    assert int(cnt.max()) <= 3
+    return RB(ref, cnt * 2.0 ** -23 * mag)
+
+
+def gelu_bwd(x, dy):
+    """mode 1 of eltwise_kernel: dy (cdf + x pdf), cdf = 0.5 (1 + erff(x / sqrt 2)), pdf = expf(-x^2 / 2) / sqrt(2 pi)"""
+    xx, g = f64(x), f64(dy)
+    cdf = 0.5 * (1.0 + torch.erf(xx * 0.70710678118654752440))
+    xp = xx * 0.39894228040143267794 * torch.exp(-0.5 * xx * xx)
+    return RB(g * (cdf + xp), g.abs() * TRANSCENDENTAL * U_F32 * (xx.abs() + cdf.abs() + xp.abs()))
+
+
+def eltwise_ref(x, dy, mode):
+    """the four modes of eltwise_kernel in fp32 before the store: gelu, gelu backward, x + dy, x * dy (one fp32 operation)"""
+    if mode == 0:
+        return gelu(exact(x))
+    if mode == 1:
+        return gelu_bwd(x, dy)
+    v = f64(x) + f64(dy) if mode == 2 else f64(x) * f64(dy)
+    return RB(v, U_F32 * v.abs())
+
+
+def wgrad_ref(dY, X, X0=None, k0=0, base=None):
+    """tdeed_wgrad: dW[n][k] = sum_m dY[m][n] X[m][k], the columns k < k0 of X from X0; db[n] = sum_m dY[m][n].
+    base = (dW, db) old contents under `accumulate`.  -> (dW (N, K), db (N))"""
+    Y, Xe = f64(dY), f64(X).clone()
+    if X0 is not None:
+        Xe[:, :k0] = f64(X0)[:, :k0]
+    dW = affine(contraction(exact(Y.T), Xe.T))                               # (N, M) . (K, M)^T: K = M terms per element
+    db = sum_over(exact(Y), (0,))
+    if base is not None:
+        dW, db = total(dW, exact(base[0])), total(db, exact(base[1]))
+    return dW, db
 
 
 # ----------------------------------------------------------------------------- checks
