@@ -454,6 +454,25 @@ int tdeed_adamw_step_guarded(float* param, const float* grad, float* exp_avg, fl
                              float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
                              const void* guard, int skip_nonfinite, float max_grad_norm, void* stream);
 
+/* ---- AdamW over runs: parameter groups and frozen tensors (opt-in; see train.hip) ---------------------------------
+ * adamw_step_groups: the arguments of tdeed_adamw_step_guarded plus a device table of `nruns` (1 .. 16384) records that
+ *   cut [0, n) into runs, 16 bytes each, 16-byte aligned, written by the caller in plain host code and uploaded once:
+ *       offset  0  int32  end4      end of the run in 16-byte chunks (exclusive), ascending; the last run's is
+ *                                   ceil(n / 4), so the scalar tail (n & 3) belongs to the last run
+ *       offset  4  float  lr_scale  the run steps at lr * lr_scale (one fp32 product)
+ *       offset  8  float  wd        the run's weight decay; < 0: the launch's weight_decay
+ *       offset 12  int32  frozen    != 0: the run's param, grad, exp_avg, exp_avg_sq are neither loaded nor stored
+ *   Every run boundary is a multiple of 4 elements, so no 16-byte chunk is split.  guard == NULL selects the unguarded
+ *   form (skip_nonfinite / max_grad_norm are ignored); otherwise the record decides as in tdeed_adamw_step_guarded: a
+ *   skipped step writes nothing in any run, and the clipping coefficient is the one global coefficient.  With
+ *   lr_scale = 1, wd < 0 (or equal to weight_decay) and frozen = 0 in every run the launch is bit-identical to
+ *   tdeed_adamw_step / tdeed_adamw_step_guarded.  The table's content cannot move a memory access: n bounds the buffers
+ *   and nruns the table whatever the records hold. */
+int tdeed_adamw_step_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr,
+                            float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                            const void* guard, int skip_nonfinite, float max_grad_norm, const void* runs, int nruns,
+                            void* stream);
+
 /* ---- post-proc (modules.py:406-426): softmax over the first K1 columns then scatter-max of
  * frame t onto clamp(t - rne(displ), 0, T-1).  scores fp32 [B][T][K1] (zero-initialised inside),
  * cls int64 [B][T] = argmax. */

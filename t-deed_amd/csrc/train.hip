@@ -339,6 +339,130 @@ extern "C" int tdeed_adamw_step_guarded(float* param, const float* grad, float* 
   return TDEED_OK;
 }
 
+// ------------------------------------------------------------------------------------------ AdamW over runs
+// Parameter groups (optim.group_table): the flat buffer is a sequence of runs, each with its own lr scale and weight decay,
+// or frozen.  One record per run, written by the host once (FusedAdamW.set_groups); every run boundary is a multiple of 4
+// elements, so a 16-byte chunk lies in exactly one run.  The run ends are staged in LDS; a thread finds its chunk's run by
+// bisection from the run of its previous trip (neighbouring lanes read the same words: broadcasts), then the arithmetic is
+// adamw_update's (adamw_element below) with lr * lr_scale (one fp32 product) and the run's decay.  A frozen run loads and
+// stores nothing.  The table's content cannot move an access: i < n4 bounds the buffers, nruns the table.
+struct AdamwRun {               // include/tdeed_hip.h: 16 bytes
+  int end4;                     // end of the run in 16-byte chunks (exclusive); the last run's covers ceil(n / 4)
+  float lr_scale;
+  float wd;                     // < 0: the launch's weight_decay
+  int frozen;
+};
+static_assert(sizeof(AdamwRun) == 16, "run record layout");
+#define ADAMW_MAX_RUNS 16384    // 64 KiB of run ends in LDS
+
+// adamw_update's element arithmetic with the roundings spelled out.  Under -ffp-contract=fast the compiler chooses which
+// products of adamw_update fuse into an fma, and it chooses differently once lr and wd vary per thread.  Bit identity with
+// adamw_kernel / adamw_guarded_kernel therefore cannot be left to it: contraction is off in here and the fmas below are the
+// ones those two kernels compile to on gfx950 -- in the 16-byte loop (TAIL = false) decay = fma(-lr, wd, 1),
+// m = fma(1 - b1, gg, b1 m), v = fma(b2, v, gg ((1 - b2) gg)), p = fma(decay, p, -q); in the scalar tail (TAIL = true) v and
+// p are a product and a separate sum.  tests/test_gpu_param_groups.py holds every run to the plain launch bit for bit, so
+// a compiler that contracts adamw_update differently shows up there.
+template <bool TAIL>
+__device__ __forceinline__ void adamw_element(float& pv, float& mv, float& vv, float g, float lr, float b1, float b2,
+                                              float eps, float wd, float bc1, float bc2s, float gscale) {
+#pragma clang fp contract(off)
+  const float gg = g * gscale;
+  const float decay = __builtin_fmaf(-lr, wd, 1.0f);
+  mv = __builtin_fmaf(1.0f - b1, gg, b1 * mv);
+  const float g2 = gg * ((1.0f - b2) * gg);
+  vv = TAIL ? g2 + b2 * vv : __builtin_fmaf(b2, vv, g2);
+  const float q = ((lr / bc1) * mv) / (sqrtf(vv) / bc2s + eps);
+  pv = TAIL ? decay * pv - q : __builtin_fmaf(decay, pv, -q);
+}
+
+template <bool GUARDED>
+__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                           float* __restrict__ m, float* __restrict__ v, long n, float lr,
+                                                           float b1, float b2, float eps, float wd, float bc1, float bc2s,
+                                                           float gscale, int step, const GuardRecord* __restrict__ rec,
+                                                           int skip_nonfinite, float max_norm,
+                                                           const AdamwRun* __restrict__ runs, int nruns) {
+  extern __shared__ int run_end[];
+  if (GUARDED) {                // adamw_guarded_kernel's prologue; the early return is uniform over the grid
+    const double sumsq = rec->sumsq;
+    const int nonfinite = rec->nonfinite, skipped = rec->skipped;
+    if (skip_nonfinite && nonfinite) return;
+    if (max_norm > 0.0f) {
+      const float norm = (float)((double)gscale * sqrt(sumsq));
+      const float q = max_norm / (norm + 1e-6f);
+      gscale *= q > 1.0f ? 1.0f : q;
+    }
+    if (skipped != 0) {
+      const float t = (float)(step - skipped);
+      bc1 = 1.0f - powf(b1, t);
+      bc2s = sqrtf(1.0f - powf(b2, t));
+    }
+  }
+  for (int r = threadIdx.x; r < nruns; r += 256) run_end[r] = runs[r].end4;
+  __syncthreads();
+  const long n4 = n >> 2;
+  int r = 0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    if ((long)run_end[r] <= i) {                                 // first run in (r, nruns - 1] that ends behind chunk i
+      int lo = r + 1, hi = nruns - 1;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((long)run_end[mid] > i) hi = mid; else lo = mid + 1;
+      }
+      r = lo < nruns ? lo : nruns - 1;
+    }
+    const AdamwRun run = runs[r];
+    if (run.frozen) continue;
+    const float lr_s = lr * run.lr_scale, wd_s = run.wd < 0.0f ? wd : run.wd;
+    f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+    f32x4 mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float pe = pv[e], me = mv[e], ve = vv[e];
+      adamw_element<false>(pe, me, ve, gv[e], lr_s, b1, b2, eps, wd_s, bc1, bc2s, gscale);
+      pv[e] = pe; mv[e] = me; vv[e] = ve;
+    }
+    reinterpret_cast<f32x4*>(p)[i] = pv;
+    reinterpret_cast<f32x4*>(m)[i] = mv;
+    reinterpret_cast<f32x4*>(v)[i] = vv;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {                // the scalar tail belongs to the last run
+    const AdamwRun run = runs[nruns - 1];
+    if (run.frozen) return;
+    const float lr_s = lr * run.lr_scale, wd_s = run.wd < 0.0f ? wd : run.wd;
+    const long i = (n4 << 2) + threadIdx.x;
+    float pe = p[i], me = m[i], ve = v[i];
+    adamw_element<true>(pe, me, ve, g[i], lr_s, b1, b2, eps, wd_s, bc1, bc2s, gscale);
+    p[i] = pe; m[i] = me; v[i] = ve;
+  }
+}
+
+extern "C" int tdeed_adamw_step_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n,
+                                       float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                       float grad_scale, const void* guard, int skip_nonfinite, float max_grad_norm,
+                                       const void* runs, int nruns, void* stream) {
+  TD_CHECK(param && grad && exp_avg && exp_avg_sq && runs, "adamw_groups: null pointer");
+  TD_CHECK(n > 0 && step >= 1, "adamw_groups: bad n/step");
+  TD_CHECK((n >> 2) < 0x7fffffffL, "adamw_groups: the run table counts 16-byte chunks in 31 bits");
+  TD_CHECK(nruns >= 1 && nruns <= ADAMW_MAX_RUNS, "adamw_groups: 1 .. 16384 runs");
+  TD_CHECK((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)guard |
+             (uintptr_t)runs) & 15) == 0, "adamw_groups: buffers, the record and the run table must be 16-byte aligned");
+  const float bc1 = 1.0f - powf(beta1, (float)step);
+  const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
+  const size_t lds = (size_t)nruns * sizeof(int);
+  if (guard)
+    hipLaunchKernelGGL(adamw_groups_kernel<true>, dim3(flat_grid(n)), dim3(256), lds, (hipStream_t)stream, param, grad,
+                       exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, step,
+                       (const GuardRecord*)guard, skip_nonfinite, max_grad_norm, (const AdamwRun*)runs, nruns);
+  else
+    hipLaunchKernelGGL(adamw_groups_kernel<false>, dim3(flat_grid(n)), dim3(256), lds, (hipStream_t)stream, param, grad,
+                       exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, grad_scale, step,
+                       (const GuardRecord*)nullptr, 0, 0.0f, (const AdamwRun*)runs, nruns);
+  TD_LAUNCH_CHECK("adamw_groups");
+  return TDEED_OK;
+}
+
 // =========================================================================== joint-dataset (double head) loss
 // model.py:278-306: the class head is two heads side by side (K1a | K1b columns); clip i belongs to dataset ds[i] in
 // {1, 2} and is scored on its own slice only: loss = sum_i CE_i / B with CE_i = sum_t w[y] nll / sum_t w[y] over the

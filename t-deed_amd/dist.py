@@ -153,6 +153,7 @@ class GradReducer:
         self.capturable = backend == "rccl"
         self._works = []
         self._side = None
+        self.frozen = [False] * len(self.buckets)                # set_frozen(): buckets that are not reduced
         if backend == "torch" and flat.is_cuda:
             from .streams import new_stream
             self._side = new_stream(flat.device)
@@ -192,10 +193,18 @@ class GradReducer:
                     tail.wait()
         return [_Chain()]
 
+    def set_frozen(self, flags):
+        """flags[i]: every tensor of bucket i is frozen (TrainEngine.set_groups) -- nothing writes its range, it holds zeros
+        on every rank, and reduce_bucket(i) enqueues nothing.  Every rank must set the same flags."""
+        flags = [bool(f) for f in flags]
+        if len(flags) != len(self.buckets):
+            raise ValueError(f"set_frozen: {len(flags)} flags for {len(self.buckets)} buckets")
+        self.frozen = flags
+
     def reduce_bucket(self, i):
         lo, hi = self.buckets[i]
         view = self.flat[lo:hi]
-        if self.world == 1:
+        if self.world == 1 or self.frozen[i]:
             return
         pl = self.plan(i)
         self.launched.append((i, pl["collective"]))
@@ -216,6 +225,9 @@ class GradReducer:
                  rs_ag_tail_elems=[self.plan(i)["tail"] for i in range(len(self.buckets))],
                  shards_16B_aligned=[self.plan(i)["shard_aligned"] for i in range(len(self.buckets))],
                  capturable=self.capturable)
+        if any(self.frozen):
+            d["bucket_frozen"] = list(self.frozen)               # all tensors frozen: the bucket is not reduced
+            d["bucket_collectives"] = ["none (frozen)" if f else c for f, c in zip(self.frozen, d["bucket_collectives"])]
         if self._comm is not None:
             w, r = self._comm.info()
             d["rccl_ranks"], d["rccl_rank"] = w, r

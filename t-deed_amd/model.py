@@ -304,7 +304,10 @@ class TDEEDModel:
     def get_optimizer(self, opt_args):
         """modules.py:37-39: AdamW over all parameters (+ a GradScaler in the reference; bf16 needs none -> None).
         The returned optimizer is a torch.optim.Optimizer over the model's single flat parameter buffer whose step() is
-        the fused AdamW kernel, so torch LR schedulers work on it unchanged."""
+        the fused AdamW kernel, so torch LR schedulers work on it unchanged.
+        opt_args['groups'] (opt-in): a list of {'params': fnmatch patterns over the state_dict names, 'lr_scale',
+        'weight_decay', 'frozen'} -- per-tensor settings inside the one launch, and frozen tensors whose backward is not
+        run (trainer.HipAdamW, optim.check_groups)."""
         from .trainer import HipAdamW
         eng = self._model.train_engine()
         if eng.reducer is None:

@@ -743,6 +743,61 @@ def adamw_step_guarded(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0
     return param
 
 
+ADAMW_MAX_RUNS = 16384   # csrc/train.hip: the run ends of one table are staged in LDS
+
+
+def adamw_run_table(runs, n, device):
+    """The device table of tdeed_adamw_step_groups for a flat buffer of n elements: int32 (R, 4) holding, per run,
+    [end in 16-byte chunks, lr_scale bits, weight_decay bits, frozen].  runs: (end_element, lr_scale, weight_decay | None,
+    frozen) ascending and covering [0, n), as optim.group_table returns them; None stands for the launch's weight decay.
+    Every boundary but the last must be a multiple of 4 elements (a run never splits a 16-byte chunk)."""
+    import numpy as np
+    runs = list(runs)
+    if not 1 <= len(runs) <= ADAMW_MAX_RUNS:
+        raise ValueError(f"adamw_run_table: 1 .. {ADAMW_MAX_RUNS} runs, got {len(runs)}")
+    tab = np.zeros((len(runs), 4), dtype=np.int32)
+    prev = 0
+    for i, (end, scale, wd, frozen) in enumerate(runs):
+        end, scale = int(end), float(scale)
+        wd = -1.0 if wd is None else float(wd)
+        last = i == len(runs) - 1
+        if not prev < end <= n or (end % 4 and not last):
+            raise ValueError(f"adamw_run_table: run {i} ends at {end} (previous end {prev}, n {n}): ends ascend in "
+                             f"multiples of 4 elements")
+        if not (scale >= 0 and scale < float("inf")) or wd != wd or wd == float("inf") or (wd < 0 and wd != -1.0):
+            raise ValueError(f"adamw_run_table: run {i}: lr_scale {scale} / weight_decay {wd} must be finite and >= 0")
+        tab[i, 0] = (end + 3) // 4
+        tab[i, 1:3] = np.array([scale, wd], dtype=np.float32).view(np.int32)
+        tab[i, 3] = int(bool(frozen))
+        prev = end
+    if prev != n:
+        raise ValueError(f"adamw_run_table: the runs end at {prev}, the buffer at {n}")
+    return torch.from_numpy(tab).to(device)
+
+
+def adamw_step_groups(param, grad, exp_avg, exp_avg_sq, step, lr, run_table, betas=(0.9, 0.999), eps=1e-8,
+                      weight_decay=0.01, grad_scale=1.0, guard=None, skip_nonfinite=False, max_grad_norm=None):
+    """adamw_step over the runs of `run_table` (adamw_run_table): a run steps at lr * lr_scale with its own weight decay, a
+    frozen run is neither read nor written.  guard: the record grad_guard wrote for `grad` (adamw_step_guarded's
+    semantics over the whole buffer), or None for the unguarded form."""
+    for t_ in (param, grad, exp_avg, exp_avg_sq):
+        _chk(t_, "adamw buffer", torch.float32)
+        if t_.numel() != param.numel():
+            raise ValueError("adamw_step_groups: param, grad, exp_avg and exp_avg_sq must have one length")
+    _chk(run_table, "adamw run table", torch.int32)
+    if run_table.dim() != 2 or run_table.shape[1] != 4 or not 1 <= run_table.shape[0] <= ADAMW_MAX_RUNS:
+        raise ValueError("adamw_step_groups: the run table is int32 (R, 4) as adamw_run_table builds it")
+    if guard is not None:
+        _chk(guard, "guard record", torch.int32)
+        if guard.numel() != GUARD_WORDS:
+            raise ValueError("adamw_step_groups: the guard is the record grad_guard wrote (8 int32 words)")
+    call("tdeed_adamw_step_groups", ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), float(lr),
+         float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step), float(grad_scale), ptr(guard),
+         int(bool(skip_nonfinite)), 0.0 if max_grad_norm is None else float(max_grad_norm), ptr(run_table),
+         int(run_table.shape[0]), stream_ptr())
+    return param
+
+
 def process_prediction(head_out, B, T, K1, displ_col, out=None):
     """out: optional contiguous fp32 (B,T,K1) tensor (e.g. a slice of a per-video score buffer) to write the scores into."""
     ld = head_out.shape[-1]

@@ -24,6 +24,136 @@ def is_late_bucket_key(key):
     return key.startswith(("_temp_fine.", "_pred_"))
 
 
+# ------------------------------------------------------------------------------------------ parameter groups
+# get_optimizer({'groups': [...]}): each group is a dict with 'params' (fnmatch patterns over the state_dict names of
+# parameters) and any of 'lr_scale', 'weight_decay', 'frozen'.  For every tensor the first group that matches wins; an
+# unmatched tensor takes the optimizer's defaults.  Everything here is host arithmetic on names and offsets.
+GROUP_KEYS = ("params", "lr_scale", "weight_decay", "frozen")
+
+
+def check_groups(groups):
+    """-> the groups as a tuple of (patterns, lr_scale, weight_decay | None, frozen); ValueError on anything else."""
+    out = []
+    for gi, g in enumerate(groups):
+        if not isinstance(g, dict) or "params" not in g:
+            raise ValueError(f"group {gi}: a dict with 'params' expected, got {g!r}")
+        unknown = sorted(set(g) - set(GROUP_KEYS))
+        if unknown:
+            raise ValueError(f"group {gi} {g['params']!r}: unknown key(s) {unknown}; a group takes {GROUP_KEYS}")
+        pats = (g["params"],) if isinstance(g["params"], str) else tuple(g["params"])
+        if not pats or not all(isinstance(p, str) for p in pats):
+            raise ValueError(f"group {gi}: 'params' must be a tuple of fnmatch patterns, got {g['params']!r}")
+        scale, wd, frozen = g.get("lr_scale", 1.0), g.get("weight_decay"), g.get("frozen", False)
+        for name, val in (("lr_scale", scale), ("weight_decay", wd)):
+            if val is None and name == "weight_decay":
+                continue
+            if isinstance(val, bool) or not isinstance(val, (int, float)) or not math.isfinite(val) or val < 0:
+                raise ValueError(f"group {gi} {pats!r}: {name} must be a finite float >= 0, got {val!r}")
+        if not isinstance(frozen, bool):
+            raise ValueError(f"group {gi} {pats!r}: frozen must be a bool, got {frozen!r}")
+        out.append((pats, float(scale), None if wd is None else float(wd), frozen))
+    return tuple(out)
+
+
+def match_groups(keys, groups):
+    """-> {key: index of the first group one of whose patterns matches it} (unmatched keys are absent).  A group whose
+    patterns match no parameter name at all is a ValueError naming it: a typo must not pass as 'defaults'."""
+    return _match(keys, check_groups(groups))
+
+
+def _match(keys, groups_n):
+    import fnmatch
+    keys = list(keys)
+    owner = {}
+    for gi, (pats, *_rest) in enumerate(groups_n):
+        hit = [k for k in keys if any(fnmatch.fnmatchcase(k, p) for p in pats)]
+        if not hit:
+            raise ValueError(f"group {gi} {pats!r} matches no parameter")
+        for k in hit:
+            owner.setdefault(k, gi)
+    return owner
+
+
+def frozen_keys(keys, groups):
+    """The parameter names a frozen group owns (first match wins)."""
+    groups_n = check_groups(groups or ())
+    return frozenset(k for k, gi in _match(keys, groups_n).items() if groups_n[gi][3])
+
+
+def group_table(index, numel, groups, default_wd):
+    """Runs (end_element, lr_scale, weight_decay, frozen) covering [0, numel) of a flat buffer with `index` = name ->
+    (offset, size) (FlatParams.index / layout_only).  A tensor's padding belongs to the run in front of it (the padding
+    behind tensor i sits in tensor i's run); adjacent tensors with equal settings merge into one run.  default_wd: what an
+    unmatched tensor, or a group without 'weight_decay', decays with -- None stands for "the launch's" and is what
+    FusedAdamW uploads, so that param_groups[0]['weight_decay'] keeps working without a new table."""
+    groups_n = check_groups(groups or ())
+    owner = _match(index, groups_n)
+    order = sorted(index, key=lambda k: index[k][0])
+    runs = []
+    for i, k in enumerate(order):
+        off, n = index[k]
+        end = index[order[i + 1]][0] if i + 1 < len(order) else numel
+        assert off % 4 == 0 and end % 4 == 0 and off + n <= end, (k, off, n, end)   # FlatParams._layout guarantees it
+        if i == 0:
+            assert off == 0, (k, off)
+        gi = owner.get(k)
+        scale, wd, frozen = (1.0, None, False) if gi is None else groups_n[gi][1:]
+        cfg = (scale, default_wd if wd is None else wd, frozen)
+        if frozen:
+            cfg = (1.0, default_wd, True)                        # a frozen run's other settings do not matter: merge them
+        if runs and runs[-1][1:] == cfg:
+            runs[-1] = (end,) + cfg
+        else:
+            runs.append((end,) + cfg)
+    if not runs:
+        raise ValueError("group_table: no parameters")
+    return runs
+
+
+def groups_as_dicts(groups):
+    """The groups with every option spelled out, as plain dicts: what param_groups[0]['groups'] and state_dict() hold."""
+    out = []
+    for pats, scale, wd, frozen in check_groups(groups):
+        g = {"params": tuple(pats), "lr_scale": scale, "frozen": frozen}
+        if wd is not None:
+            g["weight_decay"] = wd
+        out.append(g)
+    return out
+
+
+def backward_stages(spec):
+    """The stages of the backward in the order it runs them: heads + temporal stack, avg-pool + temp_enc, the
+    bottlenecks last to first, the stem."""
+    return ["temporal", "temp_enc"] + [b.name for b in reversed(spec.blocks)] + ["stem"]
+
+
+def stage_of(key):
+    """The backward stage that produces the gradient of parameter `key`."""
+    if is_late_bucket_key(key):
+        return "temporal"
+    if key == "temp_enc":
+        return "temp_enc"
+    if key.startswith("_features.stem."):
+        return "stem"
+    if key.startswith("_features."):
+        return ".".join(key.split(".")[1:3])                     # "_features.s3.b2.conv1..." -> "s3.b2"
+    raise ValueError(f"no backward stage owns parameter {key!r}")
+
+
+def freeze_plan(spec, frozen, keys):
+    """Which backward stages run when the parameters `frozen` (names) of `keys` (all parameter names) are frozen: the
+    backward stops after the earliest stage of the model -- the last one it reaches -- that owns a trainable parameter.
+    Every stage in front of that point runs, frozen or not, because the gradient has to pass through it; a stage behind it
+    is not launched.  -> the list of stage names in backward order (empty when nothing is trainable)."""
+    stages = backward_stages(spec)
+    trainable = {stage_of(k) for k in keys if k not in frozen}
+    unknown = trainable - set(stages)
+    if unknown:
+        raise ValueError(f"parameters of unknown stages {sorted(unknown)}")
+    last = max((stages.index(s) for s in trainable), default=-1)
+    return stages[:last + 1]
+
+
 class FlatParams:
     @staticmethod
     def _layout(keys, sizes):
@@ -91,9 +221,26 @@ class FusedAdamW:
         self.guard_ws = None
         self.skip_nonfinite, self.max_grad_norm = False, None
         self._last_grad_scale = 1.0
+        self.groups, self.runs, self.run_table = None, None, None    # set_groups(): the grouped launch
+        self.frozen = frozenset()
 
     def zero_grad(self):
         self.p.grad.zero_()
+
+    def set_groups(self, groups):
+        """Parameter groups (opt-in; None or an empty list returns to the plain launch).  Builds the run table once and
+        uploads it; step() then takes tdeed_adamw_step_groups.  The gradient ranges of frozen tensors are zeroed here:
+        nothing writes them from now on, and a stale value from before the freeze must not reach the global norm."""
+        if not groups:
+            self.groups, self.runs, self.run_table, self.frozen = None, None, None, frozenset()
+            return
+        runs = group_table(self.p.index, self.p.numel, groups, None)
+        self.groups, self.runs = groups_as_dicts(groups), runs
+        self.frozen = frozen_keys(self.p.index, groups)
+        dev = self.p.flat.device
+        self.run_table = ops.adamw_run_table(runs, self.p.numel, dev) if dev.type == "cuda" else None
+        for k in self.frozen:
+            self.p.grad_view(k).zero_()
 
     def set_guard(self, skip_nonfinite=False, max_grad_norm=None):
         """Guard the update (opt-in).  skip_nonfinite: a step whose gradient buffer holds an inf or a NaN writes nothing
@@ -119,6 +266,16 @@ class FusedAdamW:
 
     def step(self, lr_factor=1.0, grad_scale=1.0):
         self.t += 1
+        if self.run_table is not None:
+            # frozen gradient ranges are zeros (set_groups; nothing writes them), so the statistics over the whole buffer
+            # are those of the trainable parameters and the one global clipping coefficient is clip_grad_norm_'s
+            if self.guard is not None and (self.skip_nonfinite or self.max_grad_norm is not None):
+                ops.grad_guard(self.p.grad, self.guard, self.guard_ws, self.skip_nonfinite)
+            self._last_grad_scale = grad_scale
+            ops.adamw_step_groups(self.p.flat, self.p.grad, self.exp_avg, self.exp_avg_sq, self.t, self.lr * lr_factor,
+                                  self.run_table, self.betas, self.eps, self.wd, grad_scale, self.guard,
+                                  self.skip_nonfinite, self.max_grad_norm)
+            return
         if self.guard is None:
             ops.adamw_step(self.p.flat, self.p.grad, self.exp_avg, self.exp_avg_sq, self.t, self.lr * lr_factor,
                            self.betas, self.eps, self.wd, grad_scale)
@@ -198,6 +355,36 @@ def guarded_adamw_ref(param, grad, state, lr, betas=(0.9, 0.999), eps=1e-8, weig
     bc2_sqrt = (1 - b2 ** step) ** 0.5
     denom = (v.sqrt() / bc2_sqrt).add_(eps)
     param.addcdiv_(m, denom, value=-(lr / bc1))
+    return dict(nonfinite=bad, norm=float(norm), coef=None if coef is None else float(coef))
+
+
+def grouped_adamw_ref(param, grad, state, runs, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, grad_scale=1.0,
+                      skip_nonfinite=False, max_grad_norm=None):
+    """Restatement on torch-CPU tensors of FusedAdamW.step() with parameter groups, for the tests: one attempt over the
+    `runs` of group_table (a weight_decay of None: `weight_decay`).  The decision to skip and the clipping coefficient are
+    those of the whole buffer (guarded_adamw_ref's rule); each run is then guarded_adamw_ref on its slice at
+    float32(lr) * float32(lr_scale) with the run's decay, and a frozen run is left untouched.
+    -> dict(nonfinite, norm, coef) of this attempt."""
+    import numpy as np
+    sumsq = float((grad.double() ** 2).sum())
+    bad = not math.isfinite(sumsq)
+    norm = torch.tensor(grad_scale * math.sqrt(sumsq) if sumsq == sumsq else float("nan"), dtype=torch.float64).float()
+    state["t"] += 1
+    if skip_nonfinite and bad:
+        state["skipped"] += 1
+        return dict(nonfinite=True, norm=float(norm), coef=None)
+    gscale, coef = torch.tensor(grad_scale, dtype=torch.float32), None
+    if max_grad_norm is not None:
+        coef = torch.clamp(torch.tensor(max_grad_norm, dtype=torch.float32) / (norm + 1e-6), max=1.0)
+        gscale = gscale * coef
+    lo = 0
+    for end, scale, wd, frozen in runs:
+        if not frozen:
+            sub = dict(exp_avg=state["exp_avg"][lo:end], exp_avg_sq=state["exp_avg_sq"][lo:end], t=state["t"] - 1,
+                       skipped=state["skipped"])
+            guarded_adamw_ref(param[lo:end], grad[lo:end], sub, float(np.float32(lr) * np.float32(scale)), betas, eps,
+                              weight_decay if wd is None else wd, grad_scale=float(gscale))
+        lo = end
     return dict(nonfinite=bad, norm=float(norm), coef=None if coef is None else float(coef))
 
 

@@ -49,6 +49,8 @@ class TrainEngine:
         self.zero32 = torch.zeros(32, device=device)
         self.sched_step = 0
         self.reducer = None                                      # dist.GradReducer of a data-parallel job (set_reducer)
+        self.frozen = frozenset()                                # set_groups(): names of the frozen parameters
+        self.stages = None                                       # ... and the backward stages that run (None: all)
         # kernel-layout weight copies through recorded index tables (TDEED_REPACK_GATHER=0: every module re-packs itself
         # with its own casts / transposes / gathers, ~350 small launches per step)
         import os
@@ -88,7 +90,40 @@ class TrainEngine:
             if td.is_available() and td.is_initialized() and td.get_world_size() > 1:
                 reducer = tdist.GradReducer(self.params.grad, self.grad_buckets(), device=torch.device(self.device))
         self.reducer = reducer
+        self._mark_frozen_buckets()
         return reducer
+
+    # ------------------------------------------------------------------ parameter groups, frozen tensors
+    def set_groups(self, groups):
+        """Parameter groups of the optimizer (`optim.check_groups`; None: none).  A frozen tensor keeps its bits: its
+        gradient is not written into the flat buffer (its range there stays zero) and not reduced, and the backward stops
+        after the earliest stage that still owns a trainable parameter (`optim.freeze_plan`).  The forward is untouched.
+        A captured step belongs to the freeze set it was captured under: the handle make_step() kept is dropped."""
+        from .optim import freeze_plan, frozen_keys
+        frozen = frozen_keys(self.params.index, groups)          # (checks the groups: nothing is changed on an error)
+        stages = freeze_plan(self.spec, frozen, self.params.index) if frozen else None
+        if stages is not None and not stages:
+            raise ValueError("the groups freeze every parameter: nothing left to train")
+        self.opt.set_groups(groups)
+        self.frozen, self.stages = frozen, stages
+        self.last_graph = None
+        self._mark_frozen_buckets()
+
+    def _mark_frozen_buckets(self):
+        """A gradient bucket whose tensors are all frozen is not reduced (its range is zeros on every rank)."""
+        if self.reducer is None or not hasattr(self.reducer, "set_frozen"):
+            return
+        idx = self.params.index
+        self.reducer.set_frozen([all(k in self.frozen for k, (o, n) in idx.items() if lo <= o < hi)
+                                 for lo, hi in self.reducer.buckets])
+
+    def _runs(self, stage):
+        return self.stages is None or stage in self.stages
+
+    def _trainable(self, grads):
+        """`grads` without the frozen tensors (their weight gradients were computed by launches that also produce what the
+        stages behind them need; they are dropped here, never written out)."""
+        return {k: g for k, g in grads.items() if k not in self.frozen} if self.frozen else grads
 
     # ------------------------------------------------------------------ forward + backward
     def _frame_flip(self, flip, Bn, T):
@@ -144,12 +179,15 @@ class TrainEngine:
         _lib.SCOPE = "temporal.bwd"
         d_feat = self.temporal.backward_heads(ctx.tctx, dhead, grads)
         grads.update(self.backward_trunk(ctx, d_feat))
-        return {k: B_.materialize(g) for k, g in grads.items()}
+        return {k: B_.materialize(g) for k, g in self._trainable(grads).items()}
 
     def backward_trunk(self, ctx, d_feat):
-        """Backward of avg-pool + positional encoding, the bottlenecks and the stem from d(loss)/d(features)."""
+        """Backward of avg-pool + positional encoding, the bottlenecks and the stem from d(loss)/d(features).  With frozen
+        tensors (set_groups) it ends after the last stage of `self.stages`; the stages behind are not launched."""
         sd = self.state
         grads = {}
+        if not self._runs("temp_enc"):
+            return grads
         dx, d_enc = B_.avgpool_posenc_bwd(d_feat, ctx.hw)
         grads["temp_enc"] = d_enc
         dx = dx.view(ctx.x_shape)
@@ -159,6 +197,8 @@ class TrainEngine:
         stem_sink = B_.GradSink(ctx.y0, ctx.z0, ctx.bn0[0]) if SINK else None
         for i in reversed(range(nb)):
             blk = self.blocks[i]
+            if not self._runs(blk.blk.name):
+                return grads
             _lib.SCOPE = blk.blk.name + ".bwd"
             if SINK:
                 # block i's input gradient is produced masked by the ReLU in front of it, with the column sums the BatchNorm
@@ -167,6 +207,8 @@ class TrainEngine:
                                   sink_out=(sinks[i - 1] if i > 0 else stem_sink))
             else:
                 dx = blk.backward(dx, grads)
+        if not self._runs("stem"):
+            return grads
         _lib.SCOPE = "stem.bwd"
         wbn = sd["_features.stem.bn.weight"]
         fr4 = ctx.fr.view(-1, *ctx.fr.shape[-3:])
@@ -219,11 +261,14 @@ class TrainEngine:
     def write_grads(self, grads, scale=1.0, first=True, partial=False, role=0):
         """Gradient write-out into the flat buffer (times `scale`; overwriting when `first`, adding otherwise:
         `acc_grad_iter` of the reference's step()): multi-tensor copies, a handful of launches instead of one per tensor."""
+        grads = self._trainable(grads)
         if not partial:
-            missing = set(self.params.index) - set(grads)
+            missing = set(self.params.index) - self.frozen - set(grads)
             if missing:
                 raise RuntimeError(f"no gradient produced for {sorted(missing)[:4]} ...")
         keys = list(grads)
+        if not keys and self.frozen:
+            return                                               # every tensor of this write-out is frozen
         srcs = [grads[k] for k in keys]                          # tensors (contiguous or column slices) or LazyFold partials
         for k, g in zip(keys, srcs):
             if g.numel() != self.params.index[k][1] or g.dtype != torch.float32:
@@ -271,7 +316,7 @@ class TrainEngine:
             g_b = self.backward_trunk(ctx, d_feat)
         finally:
             B_.LAZY_WGRAD = False
-        missing = set(self.params.index) - set(g_t) - set(g_b)
+        missing = set(self.params.index) - self.frozen - set(g_t) - set(g_b)
         if missing:
             raise RuntimeError(f"no gradient produced for {sorted(missing)[:4]} ...")
         self._check_bucket_keys(g_b, 1)
@@ -376,7 +421,7 @@ class TrainEngine:
                 g_b = self.backward_trunk(ctx, d_feat)
             finally:
                 B_.LAZY_WGRAD = False
-            missing = set(self.params.index) - done - set(g_b)
+            missing = set(self.params.index) - self.frozen - done - set(g_b)
             if missing:
                 raise RuntimeError(f"no gradient produced for {sorted(missing)[:4]} ...")
             self._check_bucket_keys(g_b, 1)
@@ -423,8 +468,11 @@ class TrainEngine:
             with torch.cuda.graph(ga, stream=side, capture_error_mode="thread_local"):
                 self.repack()
                 h.loss, ctx, d_feat, done = part_a()
-            with torch.cuda.graph(gb, pool=ga.pool(), stream=side, capture_error_mode="thread_local"):
-                part_b(ctx, d_feat, done)
+            if self._runs("temp_enc"):
+                with torch.cuda.graph(gb, pool=ga.pool(), stream=side, capture_error_mode="thread_local"):
+                    part_b(ctx, d_feat, done)
+            else:
+                gb = None                                        # everything behind the temporal stack is frozen
             h.keep_ctx = (ctx, d_feat)                           # activations of the first half that the second half reads
             h.graph, h.graph_b, h.mode, h.reduce_in_graph = ga, gb, "two", False
 
@@ -440,6 +488,7 @@ class TrainEngine:
                 capture_two()
         else:
             capture_two()
+        h.frozen = self.frozen                                   # the freeze set the backward was captured under
         h.keep = self._grad_tabs                                 # the gradient write-out tables the graph's copies read
         if eager_tabs is not None:
             self._grad_tabs = eager_tabs
@@ -452,6 +501,9 @@ class TrainEngine:
 
     def step_graph(self, h, frames, label, labelD=None, soft=None, drop_masks=None, lr=None, lr_factor=1.0, all_reduce=None):
         """One optimisation step through a captured graph: refresh the static inputs, replay, all-reduce (DP), AdamW."""
+        if getattr(h, "frozen", frozenset()) != self.frozen:
+            raise RuntimeError("this graph was captured under another set of frozen parameters: build_graph() again "
+                               "(make_step() does) after set_groups()")
         h.frames.copy_(frames, non_blocking=True)
         if h.label is not None:
             h.label.copy_(label, non_blocking=True)
@@ -468,7 +520,8 @@ class TrainEngine:
             # bucket 0 (temporal stack + heads) is complete: its all-reduce travels while the trunk backward replays
             if all_reduce is None:
                 self.reducer.reduce_bucket(0)
-            h.graph_b.replay()
+            if h.graph_b is not None:
+                h.graph_b.replay()
             if all_reduce is None:
                 self.reducer.reduce_bucket(1)
                 self.reducer.join()
@@ -496,7 +549,7 @@ class TrainEngine:
         if not use_graph:
             return lambda: self.step(frames, label, labelD, drop_masks=drop_masks, all_reduce=ar)
         hnd = getattr(self, "last_graph", None)
-        if hnd is None or getattr(hnd, "geom", None) != (B, H, W):
+        if hnd is None or getattr(hnd, "geom", None) != (B, H, W) or getattr(hnd, "frozen", frozenset()) != self.frozen:
             hnd = self.build_graph(B, H, W)
             hnd.geom = (B, H, W)
         self.last_graph = hnd                                    # (tests / the bench line read .mode)
@@ -515,18 +568,34 @@ class HipAdamW(torch.optim.Optimizer):
     skip_nonfinite / max_grad_norm (opt-in, `FusedAdamW.set_guard`): what the reference's GradScaler did for the optimizer
     -- a step whose gradients hold an inf or a NaN changes nothing -- and clipping by the global norm.  Both sit in
     param_groups[0] and are read at every step(), like lr.  An LR scheduler steps whether or not the update was skipped,
-    as in the reference."""
+    as in the reference.
+    groups (opt-in, `TrainEngine.set_groups`): per-tensor lr_scale / weight_decay / frozen by fnmatch patterns over the
+    state_dict names.  There is still ONE torch param group: param_groups[0]['lr'] is what the schedulers move and what
+    lr_scale multiplies at every step; the groups sit in param_groups[0]['groups'] and travel in state_dict().  Without the
+    keyword the key is absent and nothing else differs."""
 
     def __init__(self, engine: TrainEngine, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, skip_nonfinite=False,
-                 max_grad_norm=None):
+                 max_grad_norm=None, groups=None):
         self.engine = engine
         engine.opt.lr, engine.opt.betas, engine.opt.eps, engine.opt.wd = lr, betas, eps, weight_decay
         engine.opt.set_guard(skip_nonfinite, max_grad_norm)
-        super().__init__([engine.params.flat], dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                                    skip_nonfinite=skip_nonfinite, max_grad_norm=max_grad_norm))
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, skip_nonfinite=skip_nonfinite,
+                        max_grad_norm=max_grad_norm)
+        if groups:
+            engine.set_groups(groups)
+            defaults["groups"] = engine.opt.groups
+        super().__init__([engine.params.flat], defaults)
 
     def zero_grad(self, set_to_none=False):
         self.engine.opt.zero_grad()
+
+    def set_groups(self, groups):
+        """Replace the parameter groups between steps (e.g. to unfreeze gradually); None returns to the plain launch."""
+        self.engine.set_groups(groups)
+        if self.engine.opt.groups is None:
+            self.param_groups[0].pop("groups", None)
+        else:
+            self.param_groups[0]["groups"] = self.engine.opt.groups
 
     @torch.no_grad()
     def step(self, closure=None, all_reduce=None):
@@ -535,6 +604,8 @@ class HipAdamW(torch.optim.Optimizer):
         o.betas, o.eps, o.wd = g["betas"], g["eps"], g["weight_decay"]
         if (g["skip_nonfinite"], g["max_grad_norm"]) != (o.skip_nonfinite, o.max_grad_norm):
             o.set_guard(g["skip_nonfinite"], g["max_grad_norm"])
+        if g.get("groups") != o.groups:
+            self.engine.set_groups(g.get("groups"))              # param_groups[0]['groups'] was edited by hand
         self.engine.apply(lr=g["lr"], all_reduce=all_reduce)
 
     def guard_stats(self):
@@ -552,4 +623,6 @@ class HipAdamW(torch.optim.Optimizer):
         sd = dict(state_dict)
         fused = sd.pop("fused")
         super().load_state_dict(sd)
+        if self.param_groups[0].get("groups") != self.engine.opt.groups:
+            self.set_groups(self.param_groups[0].get("groups"))
         self.engine.opt.load_state_dict(fused)
