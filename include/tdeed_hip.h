@@ -54,6 +54,12 @@ int tdeed_stem_mfma_parts(int crop_h, int crop_w);
 int tdeed_stem_mfma_fwd(const void* frames, int frames_f32, int N, int H, int W, int crop_top, int crop_left, int crop_h,
                         int crop_w, int flip, const unsigned char* flip_mask, const void* wfrag, void* z, float* colpart,
                         void* stream);
+/* The eval instance of the same kernel body (a frozen, eval-mode stem inside the training step): the folded BatchNorm and
+ * the ReLU on the fp32 accumulator, out [N][Hs][Ws][32] bf16 = relu(scale[c] * conv + shift[c]) with ONE rounding; no column
+ * sums.  scale / shift: fp32 [32], 16-byte aligned.  Served geometries: tdeed_stem_mfma_parts(crop_h, crop_w) > 0. */
+int tdeed_stem_mfma_eval_fwd(const void* frames, int frames_f32, int N, int H, int W, int crop_top, int crop_left, int crop_h,
+                             int crop_w, int flip, const unsigned char* flip_mask, const void* wfrag, const float* scale,
+                             const float* shift, void* out, void* stream);
 
 /* ---- fused trunk front (bf16 only): pre-proc + stem + s1.b1.conv1 + s1.b1.conv2 (+SE squeeze) + s1.b1.downsample
  * uint8 frames [N][3][H][W] -> y2 [N][Ho][Wo][C1] (conv2 output), shortcut [N][Ho][Wo][C1], pooled fp32

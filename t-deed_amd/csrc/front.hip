@@ -1159,12 +1159,15 @@ struct StemP {
   const float* wf;                                  // [2][2][64][8] fp32 fragments (engine.stem_frags_on_device)
   bf16_t* z; float* colpart;                        // z [N][Hs][Ws][32]; colpart [N * nbands][2][32]
   int Hs, Ws, band, nbands;
+  const float* scale; const float* shift;           // EVAL: the folded BatchNorm, [32] each (z is then the activation map)
 };
 
-template <typename IN>
+// EVAL = false: the training stem -- raw conv output z (bf16) and the per-workgroup column sums of what it stored.
+// EVAL = true: the same patch, operands and MFMA loop with the folded eval-mode BatchNorm + ReLU applied to the fp32
+// accumulator (one rounding, into the activation map): no sums, no `red`, no colpart.
+template <typename IN, bool EVAL = false>
 __global__ __launch_bounds__(256) void stem_mfma_kernel(const StemP p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ float red[4][64];
   const long lid = xcd_logical_id(blockIdx.x, gridDim.x);
   int bnd, n;
   td_split(lid, p.nbands, n, bnd);
@@ -1198,6 +1201,14 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(const StemP p) {
   float s1[8], s2[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) s1[e] = s2[e] = 0.f;
+  f32x4 esc[2], esh[2];                                  // EVAL: the lane's eight constants, channels 4q + e and 16 + 4q + e
+  if constexpr (EVAL) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      esc[t] = *reinterpret_cast<const f32x4*>(p.scale + 16 * t + 4 * q);
+      esh[t] = *reinterpret_cast<const f32x4*>(p.shift + 16 * t + 4 * q);
+    }
+  }
   const int tiles_per_row = (p.Ws + 15) >> 4;
   const int ntiles = nrows * tiles_per_row;
   const IDiv dtpr(tiles_per_row);
@@ -1225,8 +1236,16 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(const StemP p) {
       }
     }
     bf16x4 o0, o1;
+    if constexpr (EVAL) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { o0[e] = (bf16_t)sa[0][e]; o1[e] = (bf16_t)sa[1][e]; }
+      for (int e = 0; e < 4; ++e) {
+        o0[e] = (bf16_t)fmaxf(fmaf(esc[0][e], sa[0][e], esh[0][e]), 0.f);
+        o1[e] = (bf16_t)fmaxf(fmaf(esc[1][e], sa[1][e], esh[1][e]), 0.f);
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { o0[e] = (bf16_t)sa[0][e]; o1[e] = (bf16_t)sa[1][e]; }
+    }
     if (cok) {
       bf16_t* zp = zf + ((long)(r0 + rq) * p.Ws + c) * 32 + 4 * q;
       *reinterpret_cast<bf16x4*>(zp) = o0;
@@ -1239,25 +1258,28 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(const StemP p) {
       }
     }
   }
-  // fold: the 16 pixel lanes of a k-slot group, then the 4 waves; channel of element e: 4q + e (e < 4), 16 + 4q + e - 4
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) {
-      s1[e] += __shfl_xor(s1[e], o, 64);
-      s2[e] += __shfl_xor(s2[e], o, 64);
-    }
-  }
-  if (px == 0) {
+  if constexpr (!EVAL) {
+    __shared__ float red[4][64];
+    // fold: the 16 pixel lanes of a k-slot group, then the 4 waves; channel of element e: 4q + e (e < 4), 16 + 4q + e - 4
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const int chn = (e < 4) ? (4 * q + e) : (16 + 4 * q + e - 4);
-      red[wv][chn] = s1[e];
-      red[wv][32 + chn] = s2[e];
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) {
+        s1[e] += __shfl_xor(s1[e], o, 64);
+        s2[e] += __shfl_xor(s2[e], o, 64);
+      }
     }
+    if (px == 0) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int chn = (e < 4) ? (4 * q + e) : (16 + 4 * q + e - 4);
+        red[wv][chn] = s1[e];
+        red[wv][32 + chn] = s2[e];
+      }
+    }
+    __syncthreads();
+    if (tid < 64) p.colpart[lid * 64 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
   }
-  __syncthreads();
-  if (tid < 64) p.colpart[lid * 64 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
 }
 
 static int stem_band(int cw, int Hs) {
@@ -1279,15 +1301,19 @@ extern "C" int tdeed_stem_mfma_parts(int crop_h, int crop_w) {
   return (Hs + band - 1) / band;
 }
 
-extern "C" int tdeed_stem_mfma_fwd(const void* frames, int frames_f32, int N, int H, int W, int crop_top, int crop_left,
-                                   int crop_h, int crop_w, int flip, const unsigned char* flip_mask, const void* wfrag,
-                                   void* z, float* colpart, void* stream) {
-  TD_CHECK(frames && wfrag && z && colpart, "stem_mfma: null pointer");
+// the launch of both instances; scale != nullptr: the eval instance (z is the activation map, no colpart)
+static int stem_mfma_launch(const void* frames, int frames_f32, int N, int H, int W, int crop_top, int crop_left, int crop_h,
+                            int crop_w, int flip, const unsigned char* flip_mask, const void* wfrag, void* z, float* colpart,
+                            const float* scale, const float* shift, void* stream) {
+  const bool ev = scale != nullptr;
+  TD_CHECK(frames && wfrag && z && (ev ? shift != nullptr : colpart != nullptr), "stem_mfma: null pointer");
+  TD_CHECK(!ev || ((((uintptr_t)scale | (uintptr_t)shift) & 15) == 0), "stem_mfma_eval: scale / shift must be 16-byte aligned");
   TD_CHECK(N > 0 && crop_h > 0 && crop_w > 0 && crop_top >= 0 && crop_left >= 0 && crop_top + crop_h <= H &&
                crop_left + crop_w <= W, "stem_mfma: bad geometry");
   StemP p;
   p.frames = frames; p.g.H = H; p.g.W = W; p.g.top = crop_top; p.g.left = crop_left; p.g.ch = crop_h; p.g.cw = crop_w;
   p.flip = flip; p.flip_mask = flip_mask; p.wf = (const float*)wfrag; p.z = (bf16_t*)z; p.colpart = colpart;
+  p.scale = scale; p.shift = shift;
   p.Hs = (crop_h + 1) / 2; p.Ws = (crop_w + 1) / 2;
   p.band = stem_band(crop_w, p.Hs);
   p.nbands = (p.Hs + p.band - 1) / p.band;
@@ -1301,13 +1327,39 @@ extern "C" int tdeed_stem_mfma_fwd(const void* frames, int frames_f32, int N, in
   if (!attr_set.get()) {
     hipError_t e = hipFuncSetAttribute((const void*)stem_mfma_kernel<uint8_t>, hipFuncAttributeMaxDynamicSharedMemorySize, FRONT_LDS_CAP);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)stem_mfma_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, FRONT_LDS_CAP);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)stem_mfma_kernel<uint8_t, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FRONT_LDS_CAP);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)stem_mfma_kernel<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, FRONT_LDS_CAP);
     if (e != hipSuccess) { tdeed_set_error("stem_mfma: hipFuncSetAttribute: %s", hipGetErrorString(e)); return TDEED_ERR_RUNTIME; }
     attr_set.set();
   }
-  if (frames_f32) hipLaunchKernelGGL(stem_mfma_kernel<float>, dim3((unsigned)grid), dim3(256), smem, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(stem_mfma_kernel<uint8_t>, dim3((unsigned)grid), dim3(256), smem, (hipStream_t)stream, p);
+  const dim3 gr((unsigned)grid), bl(256);
+  if (ev) {
+    if (frames_f32) hipLaunchKernelGGL((stem_mfma_kernel<float, true>), gr, bl, smem, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((stem_mfma_kernel<uint8_t, true>), gr, bl, smem, (hipStream_t)stream, p);
+  } else {
+    if (frames_f32) hipLaunchKernelGGL(stem_mfma_kernel<float>, gr, bl, smem, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(stem_mfma_kernel<uint8_t>, gr, bl, smem, (hipStream_t)stream, p);
+  }
   TD_LAUNCH_CHECK("stem_mfma");
   return TDEED_OK;
+}
+
+extern "C" int tdeed_stem_mfma_fwd(const void* frames, int frames_f32, int N, int H, int W, int crop_top, int crop_left,
+                                   int crop_h, int crop_w, int flip, const unsigned char* flip_mask, const void* wfrag,
+                                   void* z, float* colpart, void* stream) {
+  TD_CHECK(colpart, "stem_mfma: null pointer");
+  return stem_mfma_launch(frames, frames_f32, N, H, W, crop_top, crop_left, crop_h, crop_w, flip, flip_mask, wfrag, z, colpart,
+                          nullptr, nullptr, stream);
+}
+
+// The eval instance: out [N][Hs][Ws][32] bf16 = relu(scale[c] * conv + shift[c]), one rounding from the fp32 accumulator.
+// Same geometries as tdeed_stem_mfma_fwd (tdeed_stem_mfma_parts > 0).
+extern "C" int tdeed_stem_mfma_eval_fwd(const void* frames, int frames_f32, int N, int H, int W, int crop_top, int crop_left,
+                                        int crop_h, int crop_w, int flip, const unsigned char* flip_mask, const void* wfrag,
+                                        const float* scale, const float* shift, void* out, void* stream) {
+  TD_CHECK(scale && shift, "stem_mfma_eval: null pointer");
+  return stem_mfma_launch(frames, frames_f32, N, H, W, crop_top, crop_left, crop_h, crop_w, flip, flip_mask, wfrag, out, nullptr,
+                          scale, shift, stream);
 }
 
 // =============================================================================================

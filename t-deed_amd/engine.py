@@ -566,6 +566,9 @@ class TrunkBuilder:
         self.N = B * pw.clip_len
         self.frames = self.head_out = None
         self.front = None          # the _Front of a trunk whose first block sits in the fused front, until its conv3 is emitted
+        # fp32 fragments of the stem weight (packing.stem_frags_on_device): set by a caller that wants the un-fused bf16 stem
+        # on the MFMA kernel's eval instance (prefix.EvalPrefix); None: tdeed_stem_fwd
+        self.stem_wf = None
 
     # ------------------------------------------------------------------ bottlenecks
     def _se_conv3(self, bw, h2, w2, y2, pooled, gate, sc, out, out2=None, sc_from=None):
@@ -755,17 +758,26 @@ class TrunkBuilder:
         return x, h, w, x_kept
 
     # ------------------------------------------------------------------ the three stages
-    def trunk(self, H, W, crop, flip, frames_dtype=torch.uint8, stop=None, out_last=None):
+    def trunk(self, H, W, crop, flip, frames_dtype=torch.uint8, stop=None, out_last=None, rect=None, frames=None):
         """Stage 1: the fused front or the stem over self.frames (N,3,H,W), made here, and the blocks [0, stop) (None: all).
         crop: side of the centre crop (None: the caller's window as it is); flip: bool (all frames) or a uint8 device tensor
-        (N,) of per-frame flags (the augmented eval path); out_last: see _blocks.  Returns (x, h, w, x_kept) of its map."""
+        (N,) of per-frame flags (the augmented eval path); out_last: see _blocks.  rect: instead of `crop`, a LIST
+        [top, left, ch, cw] that the first launch reads at every run (the caller may move the window between runs, not resize
+        it); frames: the caller's input buffer instead of one made here.  Returns (x, h, w, x_kept) of its map."""
         Wt, pool, steps, N, dt, es = self.pw.W, self.pool, self.steps, self.N, self.act_dtype, _esz(self.act_dtype)
-        geo = trunk_geometry(self.pw.spec.blocks, crop, H, W)
-        rect, ch, cw, (Ho, Wo, c0) = geo.crop, geo.ch, geo.cw, geo.maps[0]
-        self.frames = frames = torch.empty((N, 3, H, W), dtype=frames_dtype, device=self.device)
+        if rect is not None:
+            geo = trunk_geometry(self.pw.spec.blocks, None, rect[2], rect[3])
+            win = lambda: tuple(rect)                                                                        # noqa: E731
+        else:
+            geo = trunk_geometry(self.pw.spec.blocks, crop, H, W)
+            win = lambda: geo.crop                                                                           # noqa: E731
+        ch, cw, (Ho, Wo, c0) = geo.ch, geo.cw, geo.maps[0]
+        if frames is None:
+            frames = torch.empty((N, 3, H, W), dtype=frames_dtype, device=self.device)
+        self.frames = frames
         blocks = list(Wt.blocks[:stop])
         if (Wt.front is not None and "_features.stem" not in self.taps and self.fuse_front and frames_dtype == torch.uint8
-                and not isinstance(flip, torch.Tensor) and ops.s1_front_parts(ch, cw, Wt.blocks[0].spec.cout) > 0):
+                and blocks and not isinstance(flip, torch.Tensor) and ops.s1_front_parts(ch, cw, Wt.blocks[0].spec.cout) > 0):
             bw = blocks.pop(0)
             blk, (h, w, _) = bw.spec, geo.maps[1]
             parts, M2 = ops.s1_front_parts(ch, cw, blk.cout), N * h * w
@@ -774,7 +786,7 @@ class TrunkBuilder:
             pooled = pool.take((N, parts, blk.cout), torch.float32)
             gate = pool.take((N, blk.cout), torch.float32)
             steps.append(Step("s1_front", "s1_front", lambda: ops.s1_front(
-                frames, Wt.front, rect, flip, y2=y2, shortcut=sc, pooled=pooled),
+                frames, Wt.front, win(), flip, y2=y2, shortcut=sc, pooled=pooled),
                               N * 3 * ch * cw + 2 * M2 * blk.cout * es,
                               2 * N * Ho * Wo * 32 * (27 + 2 * blk.cout) // 1 + 2 * M2 * blk.cout * blk.gw * 9))
             # the block's SE + conv3 follow in _blocks, where the form of the block behind decides how conv3 is launched
@@ -782,9 +794,17 @@ class TrunkBuilder:
             x, x_kept = None, True
         else:
             x, h, w = pool.take((N, Ho, Wo, c0), dt), Ho, Wo
-            steps.append(Step("stem", "stem", lambda: ops.stem(frames, Wt.stem_w, Wt.stem_scale, Wt.stem_shift, dt, rect, flip,
-                                                               out=x),
-                              N * 3 * ch * cw + N * Ho * Wo * 32 * es, 2 * N * Ho * Wo * 32 * 27))
+            if self.stem_wf is not None and dt == torch.bfloat16 and ops.stem_mfma_parts(ch, cw) > 0:
+                # the eval instance of the training stem's MFMA kernel (a frozen prefix inside the training step)
+                wf = self.stem_wf
+                steps.append(Step("stem", "stem_mfma", lambda: ops.stem_mfma_eval(frames, wf, Wt.stem_scale, Wt.stem_shift, win(),
+                                                                                flip, out=x),
+                                  N * 3 * ch * cw * (4 if frames_dtype == torch.float32 else 1) + N * Ho * Wo * 32 * es,
+                                  2 * N * Ho * Wo * 32 * 27))
+            else:
+                steps.append(Step("stem", "stem", lambda: ops.stem(frames, Wt.stem_w, Wt.stem_scale, Wt.stem_shift, dt, win(),
+                                                                   flip, out=x),
+                                  N * 3 * ch * cw + N * Ho * Wo * 32 * es, 2 * N * Ho * Wo * 32 * 27))
             x_kept = "_features.stem" in self.taps
             if x_kept:
                 self.keep["_features.stem"] = x

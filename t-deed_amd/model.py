@@ -117,6 +117,8 @@ class TDEEDModel:
             if self._train_engine is not None:
                 # the train engine keeps packed copies (bf16 casts, transposes, MFMA fragments) of the master weights
                 self._train_engine.repack()
+                # ... and, for a frozen eval-mode prefix, folded copies that no optimizer step refreshes
+                self._train_engine.reload_prefix()
 
         def load_timm_backbone(self, timm_state_dict):
             """Fill the trunk from a timm `regnety_002` / `regnety_008` state_dict (what `timm.create_model(...,
@@ -307,7 +309,10 @@ class TDEEDModel:
         the fused AdamW kernel, so torch LR schedulers work on it unchanged.
         opt_args['groups'] (opt-in): a list of {'params': fnmatch patterns over the state_dict names, 'lr_scale',
         'weight_decay', 'frozen'} -- per-tensor settings inside the one launch, and frozen tensors whose backward is not
-        run (trainer.HipAdamW, optim.check_groups)."""
+        run (trainer.HipAdamW, optim.check_groups).
+        opt_args['frozen_stats'] (opt-in): 'eval' runs the frozen prefix of the trunk -- the stem and the bottlenecks behind
+        it, as long as every parameter is frozen -- in eval mode on the inference kernels (TrainEngine.set_groups);
+        'batch' (default) leaves the forward as it is."""
         from .trainer import HipAdamW
         eng = self._model.train_engine()
         if eng.reducer is None:

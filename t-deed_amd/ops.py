@@ -73,6 +73,32 @@ def stem_mfma(frames, wfrag, crop=None, flip=False):
     return z, colpart
 
 
+def stem_mfma_eval(frames, wfrag, scale, shift, crop=None, flip=False, out=None):
+    """The eval instance of the MFMA stem (bf16): frames (N,3,H,W) uint8 or fp32 0..255 -> (N,Ho,Wo,32) bf16 activation map
+    relu(scale * conv + shift), the folded BatchNorm applied to the fp32 accumulator (one rounding).  scale, shift fp32 (32,).
+    crop / flip as `stem`; serves the geometries with stem_mfma_parts(ch, cw) > 0."""
+    _chk(frames, "frames", torch.float32 if frames.dtype == torch.float32 else torch.uint8)
+    _chk(wfrag, "wfrag", torch.float32)
+    _chk(scale, "scale", torch.float32)
+    _chk(shift, "shift", torch.float32)
+    if scale.numel() != 32 or shift.numel() != 32:
+        raise ValueError("stem_mfma_eval: scale and shift hold one value per stem channel (32)")
+    N, _, H, W = frames.shape
+    top, left, ch, cw = crop if crop is not None else (0, 0, H, W)
+    if stem_mfma_parts(ch, cw) <= 0:
+        raise RuntimeError(f"stem_mfma_eval: a {cw}-pixel row band does not fit LDS")
+    shape = (N, (ch + 1) // 2, (cw + 1) // 2, 32)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.bfloat16, device=frames.device)
+    _chk(out, "out", torch.bfloat16)
+    if tuple(out.shape) != shape:
+        raise ValueError(f"stem_mfma_eval: out {tuple(out.shape)}, expected {shape}")
+    fl, fmask = _flip_args(flip, N)
+    call("tdeed_stem_mfma_eval_fwd", ptr(frames), int(frames.dtype == torch.float32), N, H, W, top, left, ch, cw, fl, ptr(fmask),
+         ptr(wfrag), ptr(scale), ptr(shift), ptr(out), stream_ptr())
+    return out
+
+
 def s1_front_parts(ch, cw, C1):
     return _lib.load().tdeed_s1_front_parts(ch, cw, C1)
 

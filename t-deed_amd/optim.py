@@ -154,6 +154,48 @@ def freeze_plan(spec, frozen, keys):
     return stages[:last + 1]
 
 
+FROZEN_STATS = ("batch", "eval")
+
+
+def check_frozen_stats(frozen_stats):
+    """'batch' (frozen BatchNorms go on normalising with batch statistics and move their running statistics, the default) or
+    'eval' (the frozen prefix of the trunk runs in eval mode, `eval_prefix`); ValueError on anything else."""
+    if frozen_stats not in FROZEN_STATS:
+        raise ValueError(f"frozen_stats must be one of {FROZEN_STATS}, got {frozen_stats!r}")
+    return frozen_stats
+
+
+def forward_stages(spec):
+    """The stages of the trunk's forward in the order it runs them: the stem, then the bottlenecks."""
+    return ["stem"] + [b.name for b in spec.blocks]
+
+
+def eval_prefix(spec, frozen, keys):
+    """The eval prefix of the freeze set `frozen` (names) of `keys` (all parameter names): the longest run of forward stages
+    starting at the stem -- `stem`, then the bottlenecks in order -- in which every parameter is frozen.  -> the stage names
+    (empty when the stem still trains).  temp_enc and the temporal stack are never part of it; a frozen stage behind the
+    first trainable one is not either (the gradient passes through it: it keeps batch statistics)."""
+    trainable = {stage_of(k) for k in keys if k not in frozen}
+    out = []
+    for s in forward_stages(spec):
+        if s in trainable:
+            break
+        out.append(s)
+    return out
+
+
+def checked_eval_prefix(spec, frozen, keys, frozen_stats):
+    """eval_prefix under frozen_stats = 'eval' (ValueError when it is empty), () under 'batch'."""
+    if check_frozen_stats(frozen_stats) == "batch":
+        return ()
+    pre = tuple(eval_prefix(spec, frozen, keys))
+    if not pre:
+        raise ValueError("frozen_stats='eval' with an empty eval prefix: the stem still has a trainable parameter, so no "
+                         "stage of the trunk can run in eval mode (freeze '_features.stem.*' and the stages behind it, "
+                         "in order)")
+    return pre
+
+
 class FlatParams:
     @staticmethod
     def _layout(keys, sizes):

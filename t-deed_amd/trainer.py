@@ -51,6 +51,11 @@ class TrainEngine:
         self.reducer = None                                      # dist.GradReducer of a data-parallel job (set_reducer)
         self.frozen = frozenset()                                # set_groups(): names of the frozen parameters
         self.stages = None                                       # ... and the backward stages that run (None: all)
+        # set_groups(frozen_stats='eval'): the stages from the stem on that run in eval mode on the inference kernels
+        # (optim.eval_prefix), their launches (prefix.EvalPrefix) and the generation of its packed weights
+        self.frozen_stats, self.eval_prefix, self.prefix, self.prefix_gen = "batch", (), None, 0
+        self._nbt_inc = None                                     # step-counter increments with zeros at the prefix stages
+        self._static_frames = None                               # build_graph(): the captured step's frame buffer
         # kernel-layout weight copies through recorded index tables (TDEED_REPACK_GATHER=0: every module re-packs itself
         # with its own casts / transposes / gathers, ~350 small launches per step)
         import os
@@ -94,20 +99,51 @@ class TrainEngine:
         return reducer
 
     # ------------------------------------------------------------------ parameter groups, frozen tensors
-    def set_groups(self, groups):
+    def set_groups(self, groups, frozen_stats="batch"):
         """Parameter groups of the optimizer (`optim.check_groups`; None: none).  A frozen tensor keeps its bits: its
         gradient is not written into the flat buffer (its range there stays zero) and not reduced, and the backward stops
-        after the earliest stage that still owns a trainable parameter (`optim.freeze_plan`).  The forward is untouched.
-        A captured step belongs to the freeze set it was captured under: the handle make_step() kept is dropped."""
-        from .optim import freeze_plan, frozen_keys
+        after the earliest stage that still owns a trainable parameter (`optim.freeze_plan`).
+        frozen_stats 'batch' (default): the forward is untouched -- a frozen BatchNorm normalises with batch statistics and
+        moves its running statistics.  'eval': the eval prefix (`optim.eval_prefix`: the stem and the bottlenecks behind it,
+        in order, as long as every parameter is frozen; `self.eval_prefix`) runs as torch's .eval() + requires_grad_(False)
+        would: running statistics in the BatchNorms (2d and the gate-shift modules' 3d), buffers and step counters keep their
+        bits, nothing is kept for a backward; its launches are those of the inference engine (prefix.EvalPrefix).  A frozen
+        stage BEHIND the first trainable one keeps batch statistics (the gradient passes through it).  ValueError when the
+        prefix is empty.
+        A captured step belongs to the (freeze set, eval prefix) it was captured under: the handle make_step() kept is
+        dropped."""
+        from .optim import freeze_plan, frozen_keys, checked_eval_prefix
         frozen = frozen_keys(self.params.index, groups)          # (checks the groups: nothing is changed on an error)
         stages = freeze_plan(self.spec, frozen, self.params.index) if frozen else None
         if stages is not None and not stages:
             raise ValueError("the groups freeze every parameter: nothing left to train")
+        pre = checked_eval_prefix(self.spec, frozen, self.params.index, frozen_stats)
         self.opt.set_groups(groups)
         self.frozen, self.stages = frozen, stages
         self.last_graph = None
         self._mark_frozen_buckets()
+        changed = pre != self.eval_prefix
+        self.frozen_stats, self.eval_prefix = frozen_stats, pre
+        if changed or (pre and self.prefix is None):
+            self.reload_prefix()
+
+    def reload_prefix(self):
+        """(Re)build the eval prefix's packed weights from the state's tensors: when the prefix is set or changes, and after
+        load() / load_state_dict().  NOT part of repack(): an optimizer step leaves frozen tensors alone.  Graphs captured
+        over the old copies are stale from here on (step_graph raises, make_step rebuilds)."""
+        if not self.eval_prefix and self.prefix is None:
+            return                                               # no prefix before, none now: nothing to rebuild or invalidate
+        self.prefix_gen += 1
+        self.last_graph = None
+        if not self.eval_prefix:
+            self.prefix, self._nbt_inc = None, None
+            return
+        from .optim import stage_of
+        from .prefix import EvalPrefix
+        self.prefix = EvalPrefix(self.cfg, self.state, len(self.eval_prefix) - 1, self.dt, self.device)
+        nbt = [k for k in self.state if k.endswith("num_batches_tracked")]
+        inc = [0 if (k.startswith("_features.") and stage_of(k) in self.eval_prefix) else 1 for k in nbt]
+        self._nbt_inc = torch.tensor(inc or [1], dtype=torch.int64, device=self.device)
 
     def _mark_frozen_buckets(self):
         """A gradient bucket whose tensors are all frozen is not reduced (its range is zeros on every rank)."""
@@ -146,7 +182,15 @@ class TrainEngine:
         fl = self._frame_flip(flip, Bn, T)
         H_, W_ = fr.shape[-2:]
         chw = (crop[2], crop[3]) if crop is not None else (H_, W_)
-        if self.stem.wf is not None and STEM_MFMA and ops.stem_mfma_parts(*chw) > 0:
+        k0 = len(self.eval_prefix) - 1                          # blocks [0, k0) belong to the eval prefix (-1: none)
+        z0 = y0 = bn0 = pmap = None
+        if k0 >= 0:
+            # the frozen prefix in eval mode: block k0's input map from the inference kernels, on this stream.  The map is a
+            # buffer of the prefix's plan: (plan, run count) goes into the ctx so that the backward can tell a map that a
+            # later forward of the same geometry has overwritten
+            x = self.prefix.run(fr.contiguous(), crop, fl, static=frames_u8 is self._static_frames)
+            pmap = (x, self.prefix.last_plan, self.prefix.last_plan.runs)
+        elif self.stem.wf is not None and STEM_MFMA and ops.stem_mfma_parts(*chw) > 0:
             # bf16: conv on the MFMA pipe, BatchNorm statistics from its epilogue (no second pass over the 112^2 map)
             z0, cp = ops.stem_mfma(fr, self.stem.wf, crop=crop, flip=fl)
             cpf = cp.view(-1)
@@ -157,9 +201,12 @@ class TrainEngine:
             z0 = ops.stem(fr, sd["_features.stem.conv.weight"], self.one32, self.zero32, dt, crop=crop, flip=fl, relu=False)
             y0, bn0 = B_.bn_train(z0, sd["_features.stem.bn.weight"], sd["_features.stem.bn.bias"], BN_EPS, 0.1,
                                   sd["_features.stem.bn.running_mean"], sd["_features.stem.bn.running_var"], relu=True)
-        x = y0
+        if k0 < 0:
+            x = y0
         xs = None
         for i, blk in enumerate(self.blocks):
+            if i < k0:
+                continue
             _lib.SCOPE = blk.blk.name + ".fwd"
             nxt = self.blocks[i + 1] if i + 1 < len(self.blocks) else None
             x = blk.forward(x, xs=xs, next_fold=(nxt.blk.gsf_fold if nxt is not None and nxt.gs is not None else 0))
@@ -168,10 +215,11 @@ class TrainEngine:
         hw = x.shape[1] * x.shape[2]
         feat = ops.avgpool_posenc(x, Bn, T, sd["temp_enc"])
         head_out, tctx = self.temporal.forward_heads(feat, drop_masks)
-        self.params.nbt += 1                                     # BatchNorm step counters (nn.BatchNorm.num_batches_tracked)
+        # BatchNorm step counters (nn.BatchNorm.num_batches_tracked); those of the eval prefix keep their bits
+        self.params.nbt += 1 if self._nbt_inc is None else self._nbt_inc
         from types import SimpleNamespace
         return head_out, SimpleNamespace(fr=fr, crop=crop, flip=fl, z0=z0, y0=y0, bn0=bn0, x_shape=x.shape, hw=hw, tctx=tctx,
-                                         B=Bn, T=T)
+                                         B=Bn, T=T, pmap=pmap)
 
     def backward_train(self, ctx, dhead):
         """Backward of forward_train from d(loss)/d(head_out): returns grads dict name -> fp32 tensor."""
@@ -193,8 +241,29 @@ class TrainEngine:
         dx = dx.view(ctx.x_shape)
         from .trunk_train import ZMASK, SINK
         nb = len(self.blocks)
-        sinks = [blk.make_sink() for blk in self.blocks[:-1]] if SINK else []
-        stem_sink = B_.GradSink(ctx.y0, ctx.z0, ctx.bn0[0]) if SINK else None
+        k0 = len(self.eval_prefix) - 1
+        pmap = getattr(ctx, "pmap", None)
+        if (pmap is None) != (k0 < 0):
+            raise RuntimeError("the eval prefix changed between this forward and its backward")
+        if 0 <= k0 < nb and pmap[1].runs != pmap[2]:
+            # block k0 re-reads its input, and that map is the prefix plan's buffer, not an allocation of this forward
+            raise RuntimeError("another forward of the same geometry has overwritten the eval prefix's map since this one: "
+                               "with frozen_stats='eval', run each backward before the next forward")
+        # a block of the eval prefix has no train-mode forward and so no sink of its own
+        sinks = [(blk.make_sink() if i >= k0 else None) for i, blk in enumerate(self.blocks[:-1])] if SINK else []
+        stem_sink = B_.GradSink(ctx.y0, ctx.z0, ctx.bn0[0]) if (SINK and k0 < 0) else None
+        if SINK and 0 <= k0 < nb:
+            # The first block behind the prefix keeps the backward form it has under 'batch' (the fused launches that mask and
+            # sum for the stage in front): it fills a stand-in sink over its own input map -- the true ReLU mask, the map as
+            # "z" with mean 0 -- of the geometry of that stage's real sink.  Nobody reads the sums or the input gradient.
+            xk = pmap[0]
+            zero = torch.zeros(xk.shape[-1], dtype=torch.float32, device=xk.device)
+            ds = k0 > 0 and self.blocks[k0 - 1].blk.has_downsample
+            stand = B_.GradSink(xk, xk, zero, zd=(xk if ds else None), mean_d=(zero if ds else None))
+            if k0 > 0:
+                sinks[k0 - 1] = stand
+            else:
+                stem_sink = stand
         for i in reversed(range(nb)):
             blk = self.blocks[i]
             if not self._runs(blk.blk.name):
@@ -357,7 +426,19 @@ class TrainEngine:
         return loss
 
     # ------------------------------------------------------------------ the step as one HIP graph
-    def build_graph(self, B, H, W, frames_dtype=torch.uint8, with_labelD=None, soft=False, fg_weight=5.0):
+    def build_graph(self, *args, **kw):
+        """`_build_graph` with the engine's note of the static frame buffer cleared whatever happens, and the prefix plans
+        built over that buffer dropped when the capture fails (on success the handle owns them)."""
+        try:
+            return self._build_graph(*args, **kw)
+        except BaseException:
+            if self.prefix is not None:
+                self.prefix.take_static()
+            raise
+        finally:
+            self._static_frames = None
+
+    def _build_graph(self, B, H, W, frames_dtype=torch.uint8, with_labelD=None, soft=False, fg_weight=5.0):
         """Capture weight re-packing + train-mode forward + loss + backward + gradient write-out for one batch geometry
         into a HIP graph (the eager step is host-bound: ~1700 launches).  Inputs live in static buffers
         (`.frames/.label/.labelD/.soft/.masks` of the returned handle); the AdamW launch stays outside the graph because lr
@@ -380,6 +461,7 @@ class TrainEngine:
         C = self.spec.feat_dim
         h = SimpleNamespace(B=B)
         h.frames = torch.zeros((B, T, 3, H, W), dtype=frames_dtype, device=dev)
+        self._static_frames = h.frames                           # (the eval prefix reads it in place)
         h.label = None if soft else torch.zeros((B, T), dtype=torch.int64, device=dev)
         h.soft = torch.full((B, T, K1), 1.0 / K1, dtype=torch.float32, device=dev) if soft else None
         h.labelD = torch.zeros((B, T), dtype=torch.float32, device=dev) if with_labelD else None
@@ -489,6 +571,9 @@ class TrainEngine:
         else:
             capture_two()
         h.frozen = self.frozen                                   # the freeze set the backward was captured under
+        h.prefix = (self.eval_prefix, self.prefix_gen)           # ... and the eval prefix (with its packed weights) of the forward
+        # the prefix's launch list over h.frames and its buffers live as long as the handle
+        h.prefix_plans = self.prefix.take_static() if self.prefix is not None else None
         h.keep = self._grad_tabs                                 # the gradient write-out tables the graph's copies read
         if eager_tabs is not None:
             self._grad_tabs = eager_tabs
@@ -504,6 +589,9 @@ class TrainEngine:
         if getattr(h, "frozen", frozenset()) != self.frozen:
             raise RuntimeError("this graph was captured under another set of frozen parameters: build_graph() again "
                                "(make_step() does) after set_groups()")
+        if getattr(h, "prefix", ((), 0)) != (self.eval_prefix, self.prefix_gen):
+            raise RuntimeError("this graph was captured under another eval prefix (frozen_stats) or over packed weights that "
+                               "were rebuilt since: build_graph() again (make_step() does)")
         h.frames.copy_(frames, non_blocking=True)
         if h.label is not None:
             h.label.copy_(label, non_blocking=True)
@@ -549,7 +637,8 @@ class TrainEngine:
         if not use_graph:
             return lambda: self.step(frames, label, labelD, drop_masks=drop_masks, all_reduce=ar)
         hnd = getattr(self, "last_graph", None)
-        if hnd is None or getattr(hnd, "geom", None) != (B, H, W) or getattr(hnd, "frozen", frozenset()) != self.frozen:
+        if (hnd is None or getattr(hnd, "geom", None) != (B, H, W) or getattr(hnd, "frozen", frozenset()) != self.frozen
+                or getattr(hnd, "prefix", ((), 0)) != (self.eval_prefix, self.prefix_gen)):
             hnd = self.build_graph(B, H, W)
             hnd.geom = (B, H, W)
         self.last_graph = hnd                                    # (tests / the bench line read .mode)
@@ -572,30 +661,42 @@ class HipAdamW(torch.optim.Optimizer):
     groups (opt-in, `TrainEngine.set_groups`): per-tensor lr_scale / weight_decay / frozen by fnmatch patterns over the
     state_dict names.  There is still ONE torch param group: param_groups[0]['lr'] is what the schedulers move and what
     lr_scale multiplies at every step; the groups sit in param_groups[0]['groups'] and travel in state_dict().  Without the
-    keyword the key is absent and nothing else differs."""
+    keyword the key is absent and nothing else differs.
+    frozen_stats (opt-in, 'batch' | 'eval', `TrainEngine.set_groups`): 'eval' runs the frozen prefix of the trunk in eval mode.
+    A keyword of the optimizer, not a key of a group; it sits in param_groups[0]['frozen_stats'] only when it is 'eval' and
+    travels in state_dict() there."""
 
     def __init__(self, engine: TrainEngine, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, skip_nonfinite=False,
-                 max_grad_norm=None, groups=None):
+                 max_grad_norm=None, groups=None, frozen_stats="batch"):
         self.engine = engine
         engine.opt.lr, engine.opt.betas, engine.opt.eps, engine.opt.wd = lr, betas, eps, weight_decay
         engine.opt.set_guard(skip_nonfinite, max_grad_norm)
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, skip_nonfinite=skip_nonfinite,
                         max_grad_norm=max_grad_norm)
+        from .optim import check_frozen_stats
+        if check_frozen_stats(frozen_stats) == "eval" or groups:
+            engine.set_groups(groups, frozen_stats=frozen_stats)
         if groups:
-            engine.set_groups(groups)
             defaults["groups"] = engine.opt.groups
+        if frozen_stats == "eval":
+            defaults["frozen_stats"] = "eval"                    # (absent under the default, like 'groups')
         super().__init__([engine.params.flat], defaults)
 
     def zero_grad(self, set_to_none=False):
         self.engine.opt.zero_grad()
 
-    def set_groups(self, groups):
-        """Replace the parameter groups between steps (e.g. to unfreeze gradually); None returns to the plain launch."""
-        self.engine.set_groups(groups)
+    def set_groups(self, groups, frozen_stats="batch"):
+        """Replace the parameter groups between steps (e.g. to unfreeze gradually); None returns to the plain launch.
+        frozen_stats: 'batch' (default) or 'eval' (`TrainEngine.set_groups`); it sits in param_groups[0] only when 'eval'."""
+        self.engine.set_groups(groups, frozen_stats=frozen_stats)
         if self.engine.opt.groups is None:
             self.param_groups[0].pop("groups", None)
         else:
             self.param_groups[0]["groups"] = self.engine.opt.groups
+        if frozen_stats == "eval":
+            self.param_groups[0]["frozen_stats"] = "eval"
+        else:
+            self.param_groups[0].pop("frozen_stats", None)
 
     @torch.no_grad()
     def step(self, closure=None, all_reduce=None):
@@ -604,8 +705,9 @@ class HipAdamW(torch.optim.Optimizer):
         o.betas, o.eps, o.wd = g["betas"], g["eps"], g["weight_decay"]
         if (g["skip_nonfinite"], g["max_grad_norm"]) != (o.skip_nonfinite, o.max_grad_norm):
             o.set_guard(g["skip_nonfinite"], g["max_grad_norm"])
-        if g.get("groups") != o.groups:
-            self.engine.set_groups(g.get("groups"))              # param_groups[0]['groups'] was edited by hand
+        if g.get("groups") != o.groups or g.get("frozen_stats", "batch") != self.engine.frozen_stats:
+            # param_groups[0]['groups'] / ['frozen_stats'] was edited by hand
+            self.engine.set_groups(g.get("groups"), frozen_stats=g.get("frozen_stats", "batch"))
         self.engine.apply(lr=g["lr"], all_reduce=all_reduce)
 
     def guard_stats(self):
@@ -623,6 +725,7 @@ class HipAdamW(torch.optim.Optimizer):
         sd = dict(state_dict)
         fused = sd.pop("fused")
         super().load_state_dict(sd)
-        if self.param_groups[0].get("groups") != self.engine.opt.groups:
-            self.set_groups(self.param_groups[0].get("groups"))
+        g = self.param_groups[0]
+        if g.get("groups") != self.engine.opt.groups or g.get("frozen_stats", "batch") != self.engine.frozen_stats:
+            self.set_groups(g.get("groups"), frozen_stats=g.get("frozen_stats", "batch"))
         self.engine.opt.load_state_dict(fused)
