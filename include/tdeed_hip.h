@@ -479,6 +479,31 @@ int tdeed_adamw_step_groups(float* param, const float* grad, float* exp_avg, flo
                             const void* guard, int skip_nonfinite, float max_grad_norm, const void* runs, int nruns,
                             void* stream);
 
+/* ---- weight EMA inside the AdamW launch (opt-in; see train.hip) ----------------------------------------------------
+ * adamw_step_ema: the arguments of tdeed_adamw_step_groups plus the shadow `ema` (n floats, 16-byte aligned), updated
+ *   from the parameter the launch has just computed, while it is still in registers.  guard == NULL: the plain update;
+ *   runs == NULL: no groups (nruns is ignored).  Per APPLIED step, all fp32, no contraction, three roundings:
+ *       n_upd = (step - skipped) - ema_step0       (>= 1; skipped is the record's, 0 without a guard)
+ *       d_n   = ema_warmup ? min(ema_decay, (1 + n_upd) / (10 + n_upd)) : ema_decay     (correctly rounded quotient)
+ *       w     = 1 - d_n;   diff = p_new - e;   prod = w * diff;   e = e + prod
+ *   A skipped step leaves the shadow untouched; a frozen run neither loads nor stores its shadow slice.  param, exp_avg and
+ *   exp_avg_sq get the bits tdeed_adamw_step / _guarded / _groups would write.  0 < ema_decay < 1, ema_step0 >= 0,
+ *   step - ema_step0 >= 1.
+ * ema_tensors: the same update for tensors outside the flat buffer (BatchNorm running statistics).  `rows`: a device table
+ *   of `nrows` (1 .. 65535) 16-byte rows, 16-byte aligned, written by the caller in plain host code and uploaded once:
+ *       offset  0  const float*  src     the live tensor (4-byte aligned)
+ *       offset  8  int32         offset  first element of the row in `shadow`
+ *       offset 12  int32         count   elements
+ *   `host_rows`: the caller's host copy of the same table; every row is checked against shadow_n before the launch (and
+ *   bounded by it again on the device).  shadow[offset + i] is updated from src[i]; one workgroup per row; guard (may be
+ *   NULL), skip_nonfinite, step and ema_step0 as above, so a skipped step leaves the shadow untouched. */
+int tdeed_adamw_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr,
+                         float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                         const void* guard, int skip_nonfinite, float max_grad_norm, const void* runs, int nruns,
+                         float* ema, float ema_decay, int ema_warmup, int ema_step0, void* stream);
+int tdeed_ema_tensors(const void* rows, const void* host_rows, int nrows, float* shadow, long shadow_n, int step,
+                      const void* guard, int skip_nonfinite, float ema_decay, int ema_warmup, int ema_step0, void* stream);
+
 /* ---- post-proc (modules.py:406-426): softmax over the first K1 columns then scatter-max of
  * frame t onto clamp(t - rne(displ), 0, T-1).  scores fp32 [B][T][K1] (zero-initialised inside),
  * cls int64 [B][T] = argmax. */

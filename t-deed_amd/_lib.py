@@ -186,6 +186,9 @@ _SIGS = {
                                   c_float, P], c_int),
     "tdeed_adamw_step_groups": ([P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_float, c_int, c_float, P, c_int,
                                  c_float, P, c_int, P], c_int),
+    "tdeed_adamw_step_ema": ([P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_float, c_int, c_float, P, c_int,
+                              c_float, P, c_int, P, c_float, c_int, c_int, P], c_int),
+    "tdeed_ema_tensors": ([P, P, c_int, P, c_long, c_int, P, c_int, c_float, c_int, c_int, P], c_int),
     "tdeed_process_prediction": ([P, c_int, c_int, c_int, c_int, c_int, P, P, P], c_int),
     "tdeed_gather_cast": ([P, P, c_long, P, c_int, P], c_int),
     "tdeed_cast_f32_to_bf16": ([P, P, c_long, P], c_int),

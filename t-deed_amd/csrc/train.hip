@@ -463,6 +463,212 @@ extern "C" int tdeed_adamw_step_groups(float* param, const float* grad, float* e
   return TDEED_OK;
 }
 
+// ------------------------------------------------------------------------------------------ AdamW + weight EMA
+// An exponential moving average of the weights (the shadow `ema`, one more flat fp32 buffer), updated in the launch that
+// writes the new parameter: e += w (p_new - e) on the value still in registers, so the shadow costs one load and one store
+// per element and no second read of p.  All fp32, nothing fused, three roundings (diff, prod, sum).
+//   n   = (step - skipped) - ema_step0      applied updates since the shadow was switched on, this one included (>= 1)
+//   d_n = warmup ? min(d, (1 + n) / (10 + n)) : d;   w = 1 - d_n
+// The quotient is a binary64 division rounded to fp32: for operands below 2^24 that is the correctly rounded fp32 quotient
+// (53 >= 2 * 24 + 2 bits), whatever the flags make of an fp32 division.  optim.ema_ref restates this on the host.
+__device__ __forceinline__ float ema_weight(int n, float d, int warmup) {
+  if (n < 1) n = 1;                                             // (the entry checks step - ema_step0 >= 1)
+  float dn = d;
+  if (warmup) {
+    const float q = (float)((double)(1 + n) / (double)(10 + n));
+    dn = q < d ? q : d;
+  }
+  return 1.0f - dn;
+}
+
+// -ffp-contract=fast lets the backend fuse the product into the sum whatever a pragma says (it did: v_fmac_f32), so the
+// product passes through an empty asm statement: the compiler must materialise it, rounded, before the sum.
+__device__ __forceinline__ float ema_element(float e, float p_new, float w) {
+  const float diff = p_new - e;
+  float prod = w * diff;
+  asm("" : "+v"(prod));
+  return e + prod;
+}
+
+// adamw_groups_kernel's body (adamw_element; GROUPS = false is one neutral run: lr * 1 and the launch's decay, the bits of
+// adamw_kernel / adamw_guarded_kernel) with the shadow update behind it.  A skipped step returns before anything is read; a
+// frozen run neither loads nor stores its shadow slice (it equals the parameters from the moment EMA was switched on).
+template <bool GUARDED, bool GROUPS>
+__global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                        float* __restrict__ m, float* __restrict__ v,
+                                                        float* __restrict__ ema, long n, float lr, float b1, float b2,
+                                                        float eps, float wd, float bc1, float bc2s, float gscale, int step,
+                                                        const GuardRecord* __restrict__ rec, int skip_nonfinite,
+                                                        float max_norm, const AdamwRun* __restrict__ runs, int nruns,
+                                                        float ema_decay, int ema_warmup, int ema_step0) {
+  extern __shared__ int run_end[];
+  int skipped = 0;
+  if (GUARDED) {                // adamw_guarded_kernel's prologue; the early return is uniform over the grid
+    const double sumsq = rec->sumsq;
+    const int nonfinite = rec->nonfinite;
+    skipped = rec->skipped;
+    if (skip_nonfinite && nonfinite) return;
+    if (max_norm > 0.0f) {
+      const float norm = (float)((double)gscale * sqrt(sumsq));
+      const float q = max_norm / (norm + 1e-6f);
+      gscale *= q > 1.0f ? 1.0f : q;
+    }
+    if (skipped != 0) {
+      const float t = (float)(step - skipped);
+      bc1 = 1.0f - powf(b1, t);
+      bc2s = sqrtf(1.0f - powf(b2, t));
+    }
+  }
+  const float ew = ema_weight(step - skipped - ema_step0, ema_decay, ema_warmup);
+  if (GROUPS) {
+    for (int r = threadIdx.x; r < nruns; r += 256) run_end[r] = runs[r].end4;
+    __syncthreads();
+  }
+  const long n4 = n >> 2;
+  int r = 0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    float lr_s = lr, wd_s = wd;
+    if (GROUPS) {
+      if ((long)run_end[r] <= i) {                               // first run in (r, nruns - 1] that ends behind chunk i
+        int lo = r + 1, hi = nruns - 1;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if ((long)run_end[mid] > i) hi = mid; else lo = mid + 1;
+        }
+        r = lo < nruns ? lo : nruns - 1;
+      }
+      const AdamwRun run = runs[r];
+      if (run.frozen) continue;
+      lr_s = lr * run.lr_scale;
+      wd_s = run.wd < 0.0f ? wd : run.wd;
+    }
+    f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+    f32x4 mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
+    f32x4 ev = reinterpret_cast<f32x4*>(ema)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float pe = pv[e], me = mv[e], ve = vv[e];
+      adamw_element<false>(pe, me, ve, gv[e], lr_s, b1, b2, eps, wd_s, bc1, bc2s, gscale);
+      pv[e] = pe; mv[e] = me; vv[e] = ve;
+      ev[e] = ema_element(ev[e], pe, ew);
+    }
+    reinterpret_cast<f32x4*>(p)[i] = pv;
+    reinterpret_cast<f32x4*>(m)[i] = mv;
+    reinterpret_cast<f32x4*>(v)[i] = vv;
+    reinterpret_cast<f32x4*>(ema)[i] = ev;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {                // the scalar tail belongs to the last run
+    float lr_s = lr, wd_s = wd;
+    if (GROUPS) {
+      const AdamwRun run = runs[nruns - 1];
+      if (run.frozen) return;
+      lr_s = lr * run.lr_scale;
+      wd_s = run.wd < 0.0f ? wd : run.wd;
+    }
+    const long i = (n4 << 2) + threadIdx.x;
+    float pe = p[i], me = m[i], ve = v[i];
+    adamw_element<true>(pe, me, ve, g[i], lr_s, b1, b2, eps, wd_s, bc1, bc2s, gscale);
+    p[i] = pe; m[i] = me; v[i] = ve;
+    ema[i] = ema_element(ema[i], pe, ew);
+  }
+}
+
+template <bool GUARDED, bool GROUPS>
+static void launch_adamw_ema(int grid, size_t lds, hipStream_t stream, float* p, const float* g, float* m, float* v,
+                             float* ema, long n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2s,
+                             float gscale, int step, const GuardRecord* rec, int skip_nonfinite, float max_norm,
+                             const AdamwRun* runs, int nruns, float ema_decay, int ema_warmup, int ema_step0) {
+  hipLaunchKernelGGL((adamw_ema_kernel<GUARDED, GROUPS>), dim3(grid), dim3(256), lds, stream, p, g, m, v, ema, n, lr, b1, b2,
+                     eps, wd, bc1, bc2s, gscale, step, rec, skip_nonfinite, max_norm, runs, nruns, ema_decay, ema_warmup,
+                     ema_step0);
+}
+
+extern "C" int tdeed_adamw_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr,
+                                    float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
+                                    const void* guard, int skip_nonfinite, float max_grad_norm, const void* runs, int nruns,
+                                    float* ema, float ema_decay, int ema_warmup, int ema_step0, void* stream) {
+  TD_CHECK(param && grad && exp_avg && exp_avg_sq && ema, "adamw_ema: null pointer");
+  TD_CHECK(n > 0 && step >= 1, "adamw_ema: bad n/step");
+  TD_CHECK((n >> 2) < 0x7fffffffL, "adamw_ema: the run table counts 16-byte chunks in 31 bits");
+  TD_CHECK(!runs || (nruns >= 1 && nruns <= ADAMW_MAX_RUNS), "adamw_ema: 1 .. 16384 runs");
+  TD_CHECK((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)guard |
+             (uintptr_t)runs | (uintptr_t)ema) & 15) == 0,
+           "adamw_ema: buffers, the shadow, the record and the run table must be 16-byte aligned");
+  TD_CHECK(ema_decay > 0.0f && ema_decay < 1.0f, "adamw_ema: 0 < ema_decay < 1");
+  TD_CHECK(ema_step0 >= 0 && step - ema_step0 >= 1, "adamw_ema: ema_step0 >= 0 and step - ema_step0 >= 1");
+  const float bc1 = 1.0f - powf(beta1, (float)step);
+  const float bc2s = sqrtf(1.0f - powf(beta2, (float)step));
+  const size_t lds = runs ? (size_t)nruns * sizeof(int) : 0;
+  const int grid = flat_grid(n);
+  const GuardRecord* rec = (const GuardRecord*)guard;
+  if (!guard) { skip_nonfinite = 0; max_grad_norm = 0.0f; }
+  if (!runs) nruns = 0;
+#define TD_EMA_LAUNCH(G, R)                                                                                              \
+  launch_adamw_ema<G, R>(grid, lds, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq, ema, n, lr, beta1, beta2, eps, \
+                         weight_decay, bc1, bc2s, grad_scale, step, rec, skip_nonfinite, max_grad_norm,                  \
+                         (const AdamwRun*)runs, nruns, ema_decay, ema_warmup ? 1 : 0, ema_step0)
+  if (guard && runs) TD_EMA_LAUNCH(true, true);
+  else if (guard) TD_EMA_LAUNCH(true, false);
+  else if (runs) TD_EMA_LAUNCH(false, true);
+  else TD_EMA_LAUNCH(false, false);
+#undef TD_EMA_LAUNCH
+  TD_LAUNCH_CHECK("adamw_ema");
+  return TDEED_OK;
+}
+
+// The same average for tensors outside the flat buffer (the BatchNorm running statistics): a device table of 16-byte rows,
+// written by the host once and uploaded once; one workgroup per row, lanes stride over the row.  `host_rows` is the host's
+// copy of the table: the entry checks every row against the shadow's length before the launch, and the kernel bounds each
+// row by shadow_n again, so the table's content cannot move a store outside the shadow.
+struct EmaRow {                 // include/tdeed_hip.h: 16 bytes
+  const float* src;
+  int offset;                   // first element of the row in the shadow
+  int count;
+};
+static_assert(sizeof(EmaRow) == 16, "ema row layout");
+#define EMA_MAX_ROWS 65535
+
+__global__ __launch_bounds__(256) void ema_tensors_kernel(const EmaRow* __restrict__ rows, float* __restrict__ shadow,
+                                                          long shadow_n, int step, const GuardRecord* __restrict__ rec,
+                                                          int skip_nonfinite, float ema_decay, int ema_warmup,
+                                                          int ema_step0) {
+  int skipped = 0;
+  if (rec) {                    // uniform over the grid
+    skipped = rec->skipped;
+    if (skip_nonfinite && rec->nonfinite) return;
+  }
+  const float ew = ema_weight(step - skipped - ema_step0, ema_decay, ema_warmup);
+  const EmaRow row = rows[blockIdx.x];
+  if (row.offset < 0 || row.count < 0 || (long)row.offset + row.count > shadow_n) return;
+  float* __restrict__ dst = shadow + row.offset;
+  for (int i = threadIdx.x; i < row.count; i += 256) dst[i] = ema_element(dst[i], row.src[i], ew);
+}
+
+extern "C" int tdeed_ema_tensors(const void* rows, const void* host_rows, int nrows, float* shadow, long shadow_n, int step,
+                                 const void* guard, int skip_nonfinite, float ema_decay, int ema_warmup, int ema_step0,
+                                 void* stream) {
+  TD_CHECK(rows && host_rows && shadow, "ema_tensors: null pointer");
+  TD_CHECK(nrows >= 1 && nrows <= EMA_MAX_ROWS, "ema_tensors: 1 .. 65535 rows");
+  TD_CHECK(shadow_n > 0 && step >= 1, "ema_tensors: bad shadow length / step");
+  TD_CHECK((((uintptr_t)rows | (uintptr_t)guard) & 15) == 0 && ((uintptr_t)shadow & 3) == 0,
+           "ema_tensors: the table and the record must be 16-byte aligned, the shadow 4-byte aligned");
+  TD_CHECK(ema_decay > 0.0f && ema_decay < 1.0f, "ema_tensors: 0 < ema_decay < 1");
+  TD_CHECK(ema_step0 >= 0 && step - ema_step0 >= 1, "ema_tensors: ema_step0 >= 0 and step - ema_step0 >= 1");
+  const EmaRow* hr = (const EmaRow*)host_rows;
+  for (int r = 0; r < nrows; ++r) {
+    TD_CHECK(hr[r].src && ((uintptr_t)hr[r].src & 3) == 0, "ema_tensors: row %d: null or misaligned source", r);
+    TD_CHECK(hr[r].offset >= 0 && hr[r].count >= 1 && (long)hr[r].offset + hr[r].count <= shadow_n,
+             "ema_tensors: row %d (offset %d, count %d) overruns the shadow of %ld elements", r, hr[r].offset, hr[r].count,
+             shadow_n);
+  }
+  hipLaunchKernelGGL(ema_tensors_kernel, dim3(nrows), dim3(256), 0, (hipStream_t)stream, (const EmaRow*)rows, shadow,
+                     shadow_n, step, (const GuardRecord*)guard, guard ? skip_nonfinite : 0, ema_decay, ema_warmup ? 1 : 0,
+                     ema_step0);
+  TD_LAUNCH_CHECK("ema_tensors");
+  return TDEED_OK;
+}
+
 // =========================================================================== joint-dataset (double head) loss
 // model.py:278-306: the class head is two heads side by side (K1a | K1b columns); clip i belongs to dataset ds[i] in
 // {1, 2} and is scored on its own slice only: loss = sum_i CE_i / B with CE_i = sum_t w[y] nll / sum_t w[y] over the

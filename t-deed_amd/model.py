@@ -7,6 +7,7 @@ Same constructor arguments, attributes and method signatures as
 instead.  There is exactly one execution backend (the gfx950 kernels); without the
 built library or without a GPU every compute call raises.
 """
+import contextlib
 from types import SimpleNamespace
 
 import numpy as np
@@ -63,6 +64,8 @@ class TDEEDModel:
             self._train_engine = None               # trainer.TrainEngine over self._state (get_optimizer / first train-mode call)
             self._train_dtype = torch.bfloat16      # the reference trains under autocast; torch.float32 for parity runs
             self._train_ctx = None                  # activations of the last train-mode forward (for the backward)
+            self._averaged = False                  # inside TDEEDModel.averaged(): engine() serves the averaged weights
+            self._ema_engines = {}                  # act_dtype -> (FusedAdamW.ema_gen they were packed at, ForwardEngine)
             self.augment_fn = None                  # optional hook replacing the built-in train-time augmentation:
             #   augment_fn(frames (B,T,3,H,W) uint8|fp32 0..255 on the device, crop (top,left,h,w)|None) -> frames of the
             #   crop window (B,T,3,h,w), uint8 or fp32 0..255, on the device (flips included, if wanted)
@@ -164,11 +167,25 @@ class TDEEDModel:
 
         # ---- forward
         def engine(self, act_dtype):
+            if self._averaged:
+                return self._ema_engine(act_dtype)
             if act_dtype not in self._engines:
                 if not str(self._device).startswith("cuda"):
                     raise RuntimeError("tdeed_amd runs on the GPU only: construct TDEEDModel(device='cuda')")
                 self._engines[act_dtype] = ForwardEngine(self._cfg, self._state, act_dtype, self._device)
             return self._engines[act_dtype]
+
+        def _ema_engine(self, act_dtype):
+            """The inference engine over the averaged weights (TrainEngine.ema_state()), from a cache of its own: rebuilt only
+            when the shadows have moved (an applied or attempted step, set_ema, load_state_dict) since it was packed.  The
+            live engines, the packed training weights and every live tensor are not touched."""
+            te = self._train_engine
+            gen = te.opt.ema_gen
+            hit = self._ema_engines.get(act_dtype)
+            if hit is None or hit[0] != gen:
+                hit = (gen, ForwardEngine(self._cfg, te.ema_state(), act_dtype, self._device))
+                self._ema_engines[act_dtype] = hit
+            return hit[1]
 
         def train_engine(self):
             """The training engine over this model's state (created by get_optimizer(), or lazily by the first
@@ -278,6 +295,8 @@ class TDEEDModel:
             .train()/.eval() select BatchNorm statistics + dropout and `inference` selects the crop / augmentation branch.
             slot (eval only): which of the engine's independent buffer sets to use (two batches in flight on two streams)."""
             if self.training:
+                if self._averaged:
+                    raise RuntimeError("a train-mode forward inside averaged(): the averaged weights are for scoring only")
                 return self._forward_train(x, y, inference, augment_inference)
             if not inference:
                 return self._forward_eval_augmented(x, y, act_dtype)
@@ -312,7 +331,9 @@ class TDEEDModel:
         run (trainer.HipAdamW, optim.check_groups).
         opt_args['frozen_stats'] (opt-in): 'eval' runs the frozen prefix of the trunk -- the stem and the bottlenecks behind
         it, as long as every parameter is frozen -- in eval mode on the inference kernels (TrainEngine.set_groups);
-        'batch' (default) leaves the forward as it is."""
+        'batch' (default) leaves the forward as it is.
+        opt_args['ema_decay'] / ['ema_warmup'] (opt-in): an exponential moving average of the weights inside the AdamW launch
+        and of the BatchNorm running statistics behind it (TrainEngine.set_ema); averaged() / ema_state_dict() use it."""
         from .trainer import HipAdamW
         eng = self._model.train_engine()
         if eng.reducer is None:
@@ -328,6 +349,34 @@ class TDEEDModel:
         if self._model._train_engine is not None:
             raise RuntimeError("set _train_dtype before get_optimizer() / the first train-mode forward")
         self._model._train_dtype = dt
+
+    def ema_state_dict(self):
+        """The averaged model as a state_dict of clones: the optimizer's weight EMA, the averaged BatchNorm running statistics
+        and the live step counters, with the model's keys in the model's order -- loadable by load() and by the reference.
+        RuntimeError unless get_optimizer() was given 'ema_decay'."""
+        te = self._model._train_engine
+        if te is None or te.opt.ema is None:
+            raise RuntimeError("ema_state_dict(): the optimizer has no EMA (get_optimizer({'ema_decay': ...}))")
+        return {k: v.detach().clone() for k, v in te.ema_state().items()}
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """Context manager: inside it predict, predict_video / spot_video / *_group, evalutil.stitch_videos / spot_videos /
+        map_videos and epoch(optimizer=None) run on inference engines built from the averaged weights
+        (TrainEngine.ema_state()).  Those engines sit in a cache of their own and are rebuilt only when an optimizer step has
+        happened since they were packed; the live engines, the packed training weights and every live tensor keep their
+        bits.  epoch() with an optimizer, or a train-mode forward, inside the context is a RuntimeError, and so is
+        averaged() on a model whose optimizer has no EMA."""
+        te = self._model._train_engine
+        if te is None or te.opt.ema is None:
+            raise RuntimeError("averaged(): the optimizer has no EMA (get_optimizer({'ema_decay': ...}))")
+        if self._model._averaged:
+            raise RuntimeError("averaged() is already active")
+        self._model._averaged = True
+        try:
+            yield self
+        finally:
+            self._model._averaged = False
 
     def _get_params(self):
         return list(self._model.parameters())
@@ -884,6 +933,8 @@ class TDEEDModel:
               valMAP=False):
         """model.py:193-332: validation pass (optimizer None) or one training epoch (optimizer from get_optimizer)."""
         if optimizer is not None:
+            if self._model._averaged:
+                raise RuntimeError("epoch() with an optimizer inside averaged(): the averaged weights are for scoring only")
             return self._train_epoch(loader, optimizer, lr_scheduler, acc_grad_iter, fg_weight)
         self._model.eval()
         K1 = self._num_classes

@@ -824,6 +824,82 @@ def adamw_step_groups(param, grad, exp_avg, exp_avg_sq, step, lr, run_table, bet
     return param
 
 
+def adamw_step_ema(param, grad, exp_avg, exp_avg_sq, step, lr, ema, ema_decay, ema_warmup=False, ema_step0=0, run_table=None,
+                   betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, grad_scale=1.0, guard=None, skip_nonfinite=False,
+                   max_grad_norm=None):
+    """adamw_step / adamw_step_guarded (guard) / adamw_step_groups (run_table) with the shadow `ema` updated in the same
+    launch from the parameter it has just computed: e += (1 - d_n) (p_new - e), optim.ema_ref's arithmetic, at
+    n = (step - skipped) - ema_step0.  A skipped step and a frozen run leave the shadow untouched."""
+    for t_ in (param, grad, exp_avg, exp_avg_sq, ema):
+        _chk(t_, "adamw buffer", torch.float32)
+        if t_.numel() != param.numel():
+            raise ValueError("adamw_step_ema: param, grad, exp_avg, exp_avg_sq and ema must have one length")
+    nruns = 0
+    if run_table is not None:
+        _chk(run_table, "adamw run table", torch.int32)
+        if run_table.dim() != 2 or run_table.shape[1] != 4 or not 1 <= run_table.shape[0] <= ADAMW_MAX_RUNS:
+            raise ValueError("adamw_step_ema: the run table is int32 (R, 4) as adamw_run_table builds it")
+        nruns = int(run_table.shape[0])
+    if guard is not None:
+        _chk(guard, "guard record", torch.int32)
+        if guard.numel() != GUARD_WORDS:
+            raise ValueError("adamw_step_ema: the guard is the record grad_guard wrote (8 int32 words)")
+    call("tdeed_adamw_step_ema", ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), float(lr),
+         float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step), float(grad_scale), ptr(guard),
+         int(bool(skip_nonfinite)), 0.0 if max_grad_norm is None else float(max_grad_norm), ptr(run_table), nruns,
+         ptr(ema), float(ema_decay), int(bool(ema_warmup)), int(ema_step0), stream_ptr())
+    return param
+
+
+class EmaTensorTable:
+    """The row table of tdeed_ema_tensors: `.dev` int32 (R, 4) on the device, `.host` the same rows as numpy (what the
+    entry checks against the shadow's length), `.total` the shadow elements the rows cover, `.offsets` / `.counts` per row;
+    `.keep` holds the source tensors so that the pointers in the table stay valid."""
+
+    def __init__(self, dev, host, offsets, counts, keep):
+        self.dev, self.host, self.offsets, self.counts, self.keep = dev, host, offsets, counts, keep
+        self.total = max((o + c for o, c in zip(offsets, counts)), default=0)
+
+
+def ema_tensor_table(tensors, offsets=None):
+    """Row table for `ema_tensors`: one row {src pointer, offset, count} per tensor (fp32, contiguous, on one device; views
+    at 4-byte-aligned offsets of larger buffers are fine).  offsets: the first shadow element of each row; default: the
+    rows packed back to back in the order given.  Written on the host once, uploaded once."""
+    tensors = list(tensors)
+    if not tensors:
+        raise ValueError("ema_tensor_table: no tensors")
+    for t_ in tensors:
+        _chk(t_, "ema source", torch.float32)
+        if t_.numel() < 1 or t_.numel() >= 1 << 31:
+            raise ValueError("ema_tensor_table: a row holds 1 .. 2^31 - 1 elements")
+    counts = [int(t_.numel()) for t_ in tensors]
+    if offsets is None:
+        offsets = [int(x) for x in np.cumsum([0] + counts[:-1])]
+    offsets = [int(o) for o in offsets]
+    if len(offsets) != len(tensors) or any(o < 0 or o + c >= 1 << 31 for o, c in zip(offsets, counts)):
+        raise ValueError("ema_tensor_table: one offset >= 0 per tensor, offset + count below 2^31")
+    host = np.zeros((len(tensors), 4), dtype=np.int32)
+    host[:, :2] = np.array([t_.data_ptr() for t_ in tensors], dtype=np.uint64).view(np.int32).reshape(-1, 2)
+    host[:, 2] = offsets
+    host[:, 3] = counts
+    return EmaTensorTable(torch.from_numpy(host).to(tensors[0].device), host, offsets, counts, tensors)
+
+
+def ema_tensors(table, shadow, step, ema_decay, ema_warmup=False, ema_step0=0, guard=None, skip_nonfinite=False):
+    """shadow[offset + i] += (1 - d_n) (src[i] - shadow[offset + i]) for every row of `table` (ema_tensor_table) in one
+    launch, optim.ema_ref's arithmetic at n = (step - skipped) - ema_step0; with the record of grad_guard a skipped step
+    leaves the shadow untouched.  A row that does not lie inside `shadow` is refused."""
+    _chk(shadow, "ema shadow", torch.float32)
+    if guard is not None:
+        _chk(guard, "guard record", torch.int32)
+        if guard.numel() != GUARD_WORDS:
+            raise ValueError("ema_tensors: the guard is the record grad_guard wrote (8 int32 words)")
+    call("tdeed_ema_tensors", ptr(table.dev), table.host.ctypes.data, int(table.host.shape[0]), ptr(shadow),
+         shadow.numel(), int(step), ptr(guard), int(bool(skip_nonfinite)), float(ema_decay), int(bool(ema_warmup)),
+         int(ema_step0), stream_ptr())
+    return shadow
+
+
 def process_prediction(head_out, B, T, K1, displ_col, out=None):
     """out: optional contiguous fp32 (B,T,K1) tensor (e.g. a slice of a per-video score buffer) to write the scores into."""
     ld = head_out.shape[-1]

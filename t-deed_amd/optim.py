@@ -265,6 +265,11 @@ class FusedAdamW:
         self._last_grad_scale = 1.0
         self.groups, self.runs, self.run_table = None, None, None    # set_groups(): the grouped launch
         self.frozen = frozenset()
+        # set_ema(): the shadow of the flat buffer, updated inside the AdamW launch (tdeed_adamw_step_ema)
+        self.ema, self.ema_decay, self.ema_warmup, self.ema_step0 = None, None, False, 0
+        self.ema_gen = 0                # bumped whenever the shadow (or a statistics shadow behind ema_hook) may have changed
+        self.ema_hook = None            # callable(opt) issued right behind the EMA launch (TrainEngine: the BatchNorm statistics)
+        self.ema_stats_get = self.ema_stats_set = None   # the hook owner's statistics shadow, for state_dict()
 
     def zero_grad(self):
         self.p.grad.zero_()
@@ -300,6 +305,23 @@ class FusedAdamW:
         if self.guard is None and (self.skip_nonfinite or max_grad_norm is not None):
             self._alloc_guard()
 
+    def set_ema(self, decay, warmup=False):
+        """Exponential moving average of the weights (opt-in; None switches it off and drops the buffers).  The shadow
+        starts as a copy of the flat buffer now, and every APPLIED step from now on moves it inside the AdamW launch by
+        ema_ref's arithmetic at n = (t - skipped) - ema_step0.  ema_step0 = t - skipped is recorded here: one device
+        synchronisation when a guard record exists, none otherwise.  Calling it again while EMA is on only changes decay /
+        warmup (the shadow and ema_step0 stay)."""
+        if decay is None:
+            self.ema, self.ema_decay, self.ema_warmup, self.ema_step0 = None, None, False, 0
+            self.ema_gen += 1
+            return
+        decay, warmup = check_ema(decay, warmup)
+        if self.ema is None:
+            self.ema = self.p.flat.clone()
+            self.ema_step0 = self.t - self._record()[2]
+            self.ema_gen += 1
+        self.ema_decay, self.ema_warmup = decay, warmup
+
     def _alloc_guard(self):
         dev = self.p.flat.device
         self.guard = torch.zeros(ops.GUARD_WORDS, dtype=torch.int32, device=dev)
@@ -308,6 +330,18 @@ class FusedAdamW:
 
     def step(self, lr_factor=1.0, grad_scale=1.0):
         self.t += 1
+        if self.ema is not None:
+            # one launch for all three forms below (run table and record are optional), the shadow updated in it
+            if self.guard is not None and (self.skip_nonfinite or self.max_grad_norm is not None):
+                ops.grad_guard(self.p.grad, self.guard, self.guard_ws, self.skip_nonfinite)
+            self._last_grad_scale = grad_scale
+            ops.adamw_step_ema(self.p.flat, self.p.grad, self.exp_avg, self.exp_avg_sq, self.t, self.lr * lr_factor,
+                               self.ema, self.ema_decay, self.ema_warmup, self.ema_step0, self.run_table, self.betas,
+                               self.eps, self.wd, grad_scale, self.guard, self.skip_nonfinite, self.max_grad_norm)
+            if self.ema_hook is not None:
+                self.ema_hook(self)
+            self.ema_gen += 1
+            return
         if self.run_table is not None:
             # frozen gradient ranges are zeros (set_groups; nothing writes them), so the statistics over the whole buffer
             # are those of the trainable parameters and the one global clipping coefficient is clip_grad_norm_'s
@@ -351,8 +385,14 @@ class FusedAdamW:
     def state_dict(self):
         """exp_avg, exp_avg_sq (clones), t (attempts) and skipped (the device half of the step count; one synchronisation).
         The same dict is the `state` of guarded_adamw_ref."""
-        return dict(exp_avg=self.exp_avg.clone(), exp_avg_sq=self.exp_avg_sq.clone(), t=int(self.t),
-                    skipped=self._record()[2])
+        sd = dict(exp_avg=self.exp_avg.clone(), exp_avg_sq=self.exp_avg_sq.clone(), t=int(self.t),
+                  skipped=self._record()[2])
+        if self.ema is not None:
+            # with EMA on: the shadow, the statistics shadow of the hook's owner (None without one) and the three scalars
+            stats = self.ema_stats_get() if self.ema_stats_get is not None else None
+            sd.update(ema=self.ema.clone(), ema_stats=None if stats is None else stats.clone(),
+                      ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, ema_step0=int(self.ema_step0))
+        return sd
 
     def load_state_dict(self, sd):
         """Both counters come back as saved, so the resumed optimizer takes the bias-correction path (host values while
@@ -366,6 +406,86 @@ class FusedAdamW:
         if self.guard is not None:
             self.guard.zero_()
             self.guard[3] = skipped
+        if sd.get("ema") is not None:                            # (a state without the EMA keys loads as before)
+            self.set_ema(sd["ema_decay"], sd["ema_warmup"])
+            self.ema.copy_(sd["ema"])
+            self.ema_step0 = int(sd["ema_step0"])
+            if sd.get("ema_stats") is not None and self.ema_stats_set is not None:
+                self.ema_stats_set(sd["ema_stats"])
+            self.ema_gen += 1
+
+
+def check_ema(decay, warmup=False):
+    """-> (float decay, bool warmup); ValueError unless 0 < decay < 1 (a number) and warmup is a bool."""
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 < float(decay) < 1.0:
+        raise ValueError(f"ema_decay must be a float with 0 < decay < 1, got {decay!r}")
+    if not isinstance(warmup, bool):
+        raise ValueError(f"ema_warmup must be a bool, got {warmup!r}")
+    import numpy as np
+    if not 0.0 < float(np.float32(decay)) < 1.0:
+        raise ValueError(f"ema_decay must lie inside (0, 1) as a float32, got {decay!r}")
+    return float(decay), warmup
+
+
+def ema_decay_at(n, decay, warmup=False):
+    """d_n as a float32 tensor: float32(decay), or with warmup min(that, float32(1 + n) / float32(10 + n)) -- a correctly
+    rounded fp32 quotient.  n >= 1: the number of applied updates since EMA was switched on, counting this one."""
+    if n < 1:
+        raise ValueError(f"ema: n counts applied updates from 1, got {n}")
+    d = torch.tensor(decay, dtype=torch.float32)
+    if warmup:
+        d = torch.minimum(d, torch.tensor(1 + n, dtype=torch.float32) / torch.tensor(10 + n, dtype=torch.float32))
+    return d
+
+
+def ema_ref(shadow, param, n, decay, warmup=False):
+    """The EMA update of the fused launch restated on torch-CPU fp32 tensors, in place on `shadow`: w = 1 - d_n, then per
+    element diff = param - shadow, prod = w * diff, shadow += prod -- three roundings, nothing fused.  The device result
+    equals this bit for bit (tests/test_gpu_ema.py).  -> shadow."""
+    decay, warmup = check_ema(decay, warmup)
+    if shadow.dtype != torch.float32 or param.dtype != torch.float32 or shadow.is_cuda or param.is_cuda:
+        raise TypeError("ema_ref: float32 CPU tensors")
+    w = torch.tensor(1.0, dtype=torch.float32) - ema_decay_at(int(n), decay, warmup)
+    diff = param - shadow
+    prod = diff * w
+    shadow.add_(prod)
+    return shadow
+
+
+def is_ema_stat(key):
+    """The buffers the statistics shadow averages: BatchNorm running_mean / running_var (num_batches_tracked is not
+    averaged: the averaged model carries the live counters)."""
+    return key.rsplit(".", 1)[-1] in ("running_mean", "running_var")
+
+
+def ema_stat_layout(state):
+    """-> ({key: (offset, count)} for every running_mean / running_var of `state` in state-dict order, packed back to back;
+    total elements): the layout of the statistics shadow and of its row table."""
+    out, cur = {}, 0
+    for k, v in state.items():
+        if is_ema_stat(k):
+            n = int(v.numel())
+            out[k] = (cur, n)
+            cur += n
+    return out, cur
+
+
+def ema_state_map(state, index, shadow, stat_index, stat_shadow):
+    """The averaged model as an ordered mapping with the keys and the order of `state`: parameters as views of `shadow`
+    (the flat buffer's twin) through `index` (FlatParams.index), running statistics as views of `stat_shadow` through
+    `stat_index` (ema_stat_layout), everything else (the step counters) the live tensor.  Nothing is copied."""
+    from collections import OrderedDict
+    out = OrderedDict()
+    for k, v in state.items():
+        if k in index:
+            o, n = index[k]
+            out[k] = shadow[o:o + n].view(v.shape)
+        elif k in stat_index:
+            o, n = stat_index[k]
+            out[k] = stat_shadow[o:o + n].view(v.shape)
+        else:
+            out[k] = v
+    return out
 
 
 def guarded_adamw_ref(param, grad, state, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, grad_scale=1.0,

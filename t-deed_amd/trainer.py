@@ -56,6 +56,8 @@ class TrainEngine:
         self.frozen_stats, self.eval_prefix, self.prefix, self.prefix_gen = "batch", (), None, 0
         self._nbt_inc = None                                     # step-counter increments with zeros at the prefix stages
         self._static_frames = None                               # build_graph(): the captured step's frame buffer
+        # set_ema(): the shadow of the BatchNorm running statistics, its layout and its row table (ops.ema_tensor_table)
+        self.ema_stats, self.ema_stat_index, self._ema_rows = None, None, None
         # kernel-layout weight copies through recorded index tables (TDEED_REPACK_GATHER=0: every module re-packs itself
         # with its own casts / transposes / gathers, ~350 small launches per step)
         import os
@@ -97,6 +99,51 @@ class TrainEngine:
         self.reducer = reducer
         self._mark_frozen_buckets()
         return reducer
+
+    # ------------------------------------------------------------------ weight EMA
+    def set_ema(self, decay, warmup=False):
+        """Exponential moving average of the model (`FusedAdamW.set_ema`; None switches it off and drops the buffers).  The
+        parameters' shadow lives in the optimizer and moves inside the AdamW launch.  This engine owns the shadow of the
+        BatchNorm running statistics -- every running_mean / running_var of `self.state` in state-dict order, packed back to
+        back, a copy of the live values now -- and its row table, written and uploaded once; one `ops.ema_tensors` launch
+        right behind the AdamW launch moves it with the same n, decay and guard record, so a skipped step leaves both shadows
+        untouched.  num_batches_tracked is not averaged.
+        Data parallel: the ranks hold the same parameters and the same scalars (t, skipped, ema_step0, decay), so their
+        parameter shadows agree bit for bit without a collective; the statistics shadows are per rank, as the live running
+        statistics are.
+        A non-finite FORWARD still reaches the live running statistics, as in the reference, and from there the averaged ones
+        at the next applied step."""
+        from .optim import ema_stat_layout
+        self.opt.set_ema(decay, warmup)
+        if decay is None:
+            self.ema_stats, self.ema_stat_index, self._ema_rows = None, None, None
+            self.opt.ema_hook = self.opt.ema_stats_get = self.opt.ema_stats_set = None
+            return
+        if self.ema_stats is None:
+            index, total = ema_stat_layout(self.state)
+            srcs = [self.state[k].reshape(-1) for k in index]     # (views: the rows point at the live tensors)
+            if any(s.data_ptr() != self.state[k].data_ptr() for s, k in zip(srcs, index)):
+                raise RuntimeError("a running statistic of the state is not contiguous")
+            self._ema_rows = ops.ema_tensor_table(srcs, [o for o, _ in index.values()])
+            assert self._ema_rows.total == total
+            self.ema_stats = torch.cat([s.detach() for s in srcs])
+            self.ema_stat_index = index
+            self.opt.ema_hook = self._ema_stats_step
+            self.opt.ema_stats_get = lambda: self.ema_stats
+            self.opt.ema_stats_set = lambda v: self.ema_stats.copy_(v)
+
+    def _ema_stats_step(self, opt):
+        ops.ema_tensors(self._ema_rows, self.ema_stats, opt.t, opt.ema_decay, opt.ema_warmup, opt.ema_step0, opt.guard,
+                        opt.skip_nonfinite)
+
+    def ema_state(self):
+        """The averaged model: an ordered mapping with the model's own keys in the model's own order -- parameters as views
+        of the optimizer's shadow through `params.index`, running statistics as views of the statistics shadow, the step
+        counters live.  Views, not copies: `ForwardEngine(cfg, ema_state(), ...)` packs its own."""
+        from .optim import ema_state_map
+        if self.opt.ema is None:
+            raise RuntimeError("ema_state(): the optimizer has no EMA (get_optimizer({'ema_decay': ...}) / set_ema())")
+        return ema_state_map(self.state, self.params.index, self.opt.ema, self.ema_stat_index, self.ema_stats)
 
     # ------------------------------------------------------------------ parameter groups, frozen tensors
     def set_groups(self, groups, frozen_stats="batch"):
@@ -664,10 +711,14 @@ class HipAdamW(torch.optim.Optimizer):
     keyword the key is absent and nothing else differs.
     frozen_stats (opt-in, 'batch' | 'eval', `TrainEngine.set_groups`): 'eval' runs the frozen prefix of the trunk in eval mode.
     A keyword of the optimizer, not a key of a group; it sits in param_groups[0]['frozen_stats'] only when it is 'eval' and
-    travels in state_dict() there."""
+    travels in state_dict() there.
+    ema_decay / ema_warmup (opt-in, `TrainEngine.set_ema`): an exponential moving average of the weights, updated inside the
+    AdamW launch, and of the BatchNorm running statistics, one launch behind it; `TDEEDModel.averaged()` scores with it.  The
+    two keys sit in param_groups[0] only when given, are read at every step() and travel in state_dict(); the shadows
+    travel under "fused"."""
 
     def __init__(self, engine: TrainEngine, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, skip_nonfinite=False,
-                 max_grad_norm=None, groups=None, frozen_stats="batch"):
+                 max_grad_norm=None, groups=None, frozen_stats="batch", ema_decay=None, ema_warmup=False):
         self.engine = engine
         engine.opt.lr, engine.opt.betas, engine.opt.eps, engine.opt.wd = lr, betas, eps, weight_decay
         engine.opt.set_guard(skip_nonfinite, max_grad_norm)
@@ -680,6 +731,11 @@ class HipAdamW(torch.optim.Optimizer):
             defaults["groups"] = engine.opt.groups
         if frozen_stats == "eval":
             defaults["frozen_stats"] = "eval"                    # (absent under the default, like 'groups')
+        if ema_decay is not None:
+            engine.set_ema(ema_decay, ema_warmup)                # (ValueError on a bad pair: nothing was changed)
+            defaults["ema_decay"], defaults["ema_warmup"] = engine.opt.ema_decay, engine.opt.ema_warmup
+        elif ema_warmup is not False:
+            raise ValueError("ema_warmup without ema_decay")
         super().__init__([engine.params.flat], defaults)
 
     def zero_grad(self, set_to_none=False):
@@ -708,6 +764,8 @@ class HipAdamW(torch.optim.Optimizer):
         if g.get("groups") != o.groups or g.get("frozen_stats", "batch") != self.engine.frozen_stats:
             # param_groups[0]['groups'] / ['frozen_stats'] was edited by hand
             self.engine.set_groups(g.get("groups"), frozen_stats=g.get("frozen_stats", "batch"))
+        if (g.get("ema_decay"), g.get("ema_warmup", False)) != (o.ema_decay, o.ema_warmup):
+            self.engine.set_ema(g.get("ema_decay"), g.get("ema_warmup", False))
         self.engine.apply(lr=g["lr"], all_reduce=all_reduce)
 
     def guard_stats(self):
@@ -716,7 +774,7 @@ class HipAdamW(torch.optim.Optimizer):
 
     def state_dict(self):
         """torch's state_dict (param_groups) with the fused optimizer's state next to it under "fused": exp_avg,
-        exp_avg_sq, t, skipped (`FusedAdamW.state_dict`)."""
+        exp_avg_sq, t, skipped and, with EMA on, ema, ema_stats, ema_decay, ema_warmup, ema_step0 (`FusedAdamW.state_dict`)."""
         sd = super().state_dict()
         sd["fused"] = self.engine.opt.state_dict()
         return sd
@@ -728,4 +786,6 @@ class HipAdamW(torch.optim.Optimizer):
         g = self.param_groups[0]
         if g.get("groups") != self.engine.opt.groups or g.get("frozen_stats", "batch") != self.engine.frozen_stats:
             self.set_groups(g.get("groups"), frozen_stats=g.get("frozen_stats", "batch"))
+        if g.get("ema_decay") is not None or self.engine.opt.ema is not None:
+            self.engine.set_ema(g.get("ema_decay"), g.get("ema_warmup", False))   # (the shadows come back with `fused`)
         self.engine.opt.load_state_dict(fused)
