@@ -419,6 +419,17 @@ int tdeed_loss_bwd(const float* head_out, int rows, int ld, int K1, const int64_
 int tdeed_loss2(const float* head_out, int B, int T, int ld, int K1a, int K1b, const int64_t* dataset, const int64_t* hard,
                 const float* soft, const float* cls_w, int displ_col, const float* labelD, float grad_scale, float* out,
                 float* dhead, void* stream);
+/* distillation (opt-in): total = (1-alpha) CE + MSE + alpha KD + displ_weight KDdispl, value and gradient in one launch.
+ * CE / MSE are the terms of tdeed_loss_fwd / tdeed_loss_bwd (alpha = displ_weight = 0 gives their bits);
+ * KD = temperature^2 / rows * sum_r KL(softmax(t_r / temperature) || softmax(s_r / temperature)) with s = head_out[r][0..K1)
+ * and t = teacher[r][0..K1), read in place from the teacher's own head buffer (row stride ld_t, displacement column
+ * displ_col_t or <0); KDdispl = mean_r (d_s - d_t)^2 when both displacement columns exist, else 0 (displ_weight > 0 is
+ * then an argument error).  out5: total, ce, mse, kd, kd_displ.  dhead [rows][ld] may be NULL (value only).  Nothing is
+ * clamped: a non-finite teacher logit gives a non-finite kd and gradient row. */
+int tdeed_loss_kd(const float* head_out, int rows, int ld, int K1, const int64_t* hard, const float* soft,
+                  const float* cls_w, int displ_col, const float* labelD, const float* teacher, int ld_t, int displ_col_t,
+                  float alpha, float temperature, float displ_weight, float grad_scale, float* out5, float* dhead,
+                  void* stream);
 long tdeed_heads_bwd_workspace(int rows, int C, int n_out);
 int tdeed_heads_bwd(const float* dout, const void* x, int rows, int C, const float* w, int n_out, void* dx,
                     float* dw, float* db, void* workspace, int dtype, void* stream);

@@ -60,8 +60,138 @@ extern "C" int tdeed_loss_bwd(const float* head_out, int rows, int ld, int K1, c
   return TDEED_OK;
 }
 
+// ------------------------------------------------------------------------------------------ distillation loss
+// Value and gradient of  total = (1-a) CE + MSE + a KD + b KDdispl  in one launch (opt-in: TDEEDModel.distill_from).
+//   CE, MSE:  the terms of loss_kernel (misc.hip) / loss_bwd_kernel above, expression for expression, so that a = b = 0
+//             gives their bits
+//   KD      = tau^2 / rows * sum_r sum_k q_rk (log q_rk - log p_rk),  p = softmax(s_r / tau), q = softmax(t_r / tau);
+//             s = head[r][0..K1), t = teacher[r][0..K1) read in place from the teacher's head buffer (row stride ld_t)
+//   KDdispl = 1 / rows * sum_r (d_s - d_t)^2  when both heads have a displacement column, else 0
+//   dlogit[r][k] = (1-a) (the plain term) + a tau (p_rk - q_rk) gscale / rows
+//   ddispl[r]    = the plain term + 2 b (d_s - d_t) gscale / rows
+// Single block like the kernels it restates; every thread walks its rows in order and the block folds are fixed trees:
+// no atomics, the same bits at every launch.  Per row the two tempered softmaxes are reduced once (max, sum, log-sum) and
+// serve the value and the gradient.  Nothing is clamped: a non-finite teacher logit reaches KD and that row's gradient
+// (the guarded step's skip_nonfinite is what catches it).
+__global__ __launch_bounds__(256) void loss_kd_kernel(const float* __restrict__ head, int rows, int ld, int K1,
+                                                      const int64_t* __restrict__ hard, const float* __restrict__ soft,
+                                                      const float* __restrict__ cls_w, int displ_col,
+                                                      const float* __restrict__ labelD,
+                                                      const float* __restrict__ teacher, int ld_t, int displ_col_t,
+                                                      float alpha, float tau, float beta, float gscale,
+                                                      float* __restrict__ out, float* __restrict__ dhead) {
+  __shared__ float scratch[8];
+  float den = 0.f;
+  if (!soft)
+    for (int r = threadIdx.x; r < rows; r += 256) {
+      const int y = (int)hard[r];
+      den += cls_w[(y >= 0 && y < K1) ? y : 0];                  // out-of-range labels are never indexed
+    }
+  den = soft ? (float)rows : block_sum<4>(den, scratch);
+  const float inv = gscale / den;
+  const float oma = 1.0f - alpha;
+  const float it = 1.0f / tau;
+  const float gk = alpha * tau * gscale / (float)rows;
+  const float gd = 2.0f * beta * gscale / (float)rows;
+  const bool both_d = displ_col >= 0 && displ_col_t >= 0;
+  float num = 0.f, se = 0.f, bad = 0.f, kd = 0.f, kdd = 0.f;
+  for (int r = threadIdx.x; r < rows; r += 256) {
+    const float* lg = head + (long)r * ld;
+    const float* tg = teacher + (long)r * ld_t;
+    float m = lg[0], mt = tg[0];
+    for (int k = 1; k < K1; ++k) { m = fmaxf(m, lg[k]); mt = fmaxf(mt, tg[k]); }
+    float s = 0.f;
+    for (int k = 0; k < K1; ++k) s += expf(lg[k] - m);
+    const float lse = m + logf(s);
+    const float is = 1.0f / s;
+    // the tempered pair: x -> x / tau is monotone, so the row maxima carry over
+    const float ms = m * it;
+    mt *= it;
+    float ss = 0.f, st = 0.f;
+    for (int k = 0; k < K1; ++k) { ss += expf(lg[k] * it - ms); st += expf(tg[k] * it - mt); }
+    const float lss = ms + logf(ss), lst = mt + logf(st);
+    const float ips = 1.0f / ss, ipt = 1.0f / st;
+    if (soft) {
+      const float* p = soft + (long)r * K1;
+      float a = 0.f;
+      for (int k = 0; k < K1; ++k) a += cls_w[k] * p[k] * (lse - lg[k]);
+      num += a;
+    } else {
+      int yk = (int)hard[r];
+      if (yk < 0 || yk >= K1) { bad = 1.f; yk = 0; }
+      num += cls_w[yk] * (lse - lg[yk]);
+    }
+    float* dg = dhead ? dhead + (long)r * ld : nullptr;
+    if (dg) {
+      // the plain term first, in loss_bwd_kernel's own loops (its contractions decide the bits), then blended in place
+      for (int k = K1; k < ld; ++k) dg[k] = 0.f;
+      if (soft) {
+        const float* p = soft + (long)r * K1;
+        float wp = 0.f;
+        for (int k = 0; k < K1; ++k) wp += cls_w[k] * p[k];
+        for (int k = 0; k < K1; ++k) dg[k] = (expf(lg[k] - m) * is * wp - cls_w[k] * p[k]) * inv;
+      } else {
+        int y = (int)hard[r];
+        if (y < 0 || y >= K1) y = 0;
+        const float wy = cls_w[y];
+        for (int k = 0; k < K1; ++k) dg[k] = wy * (expf(lg[k] - m) * is - (k == y ? 1.f : 0.f)) * inv;
+      }
+    }
+    float a = 0.f;
+    for (int k = 0; k < K1; ++k) {
+      const float ps = expf(lg[k] * it - ms) * ips, qt = expf(tg[k] * it - mt) * ipt;
+      a += qt * ((tg[k] * it - lst) - (lg[k] * it - lss));
+      if (dg) dg[k] = oma * dg[k] + gk * (ps - qt);
+    }
+    kd += a;
+    float gdis = 0.f;
+    if (displ_col >= 0 && labelD) {
+      const float d = lg[displ_col] - labelD[r];
+      se += d * d;
+      gdis = 2.0f * (lg[displ_col] - labelD[r]) * gscale / (float)rows;
+    }
+    if (both_d) {
+      const float e = lg[displ_col] - tg[displ_col_t];
+      kdd += e * e;
+      gdis += gd * e;
+    }
+    if (dg && displ_col >= 0 && (labelD || both_d)) dg[displ_col] = gdis;
+  }
+  num = block_sum<4>(num, scratch);
+  se = block_sum<4>(se, scratch);
+  bad = block_sum<4>(bad, scratch);
+  kd = block_sum<4>(kd, scratch);
+  kdd = block_sum<4>(kdd, scratch);
+  if (threadIdx.x == 0) {
+    const float ce = bad > 0.f ? __builtin_nanf("") : (soft ? num / (float)rows : num / den);
+    const float mse = (displ_col >= 0 && labelD) ? se / (float)rows : 0.f;
+    const float kdv = tau * tau * kd / (float)rows;
+    const float kddv = both_d ? kdd / (float)rows : 0.f;
+    out[0] = oma * ce + mse + alpha * kdv + beta * kddv;
+    out[1] = ce;
+    out[2] = mse;
+    out[3] = kdv;
+    out[4] = kddv;
+  }
+}
+
+extern "C" int tdeed_loss_kd(const float* head_out, int rows, int ld, int K1, const int64_t* hard, const float* soft,
+                             const float* cls_w, int displ_col, const float* labelD, const float* teacher, int ld_t,
+                             int displ_col_t, float alpha, float temperature, float displ_weight, float grad_scale,
+                             float* out5, float* dhead, void* stream) {
+  TD_CHECK(head_out && cls_w && teacher && out5 && (hard || soft), "loss_kd: null pointer");
+  TD_CHECK(rows > 0 && K1 > 0 && K1 <= ld && displ_col < ld && K1 <= ld_t && displ_col_t < ld_t, "loss_kd: bad sizes");
+  TD_CHECK(alpha >= 0.f && alpha <= 1.f && temperature > 0.f && displ_weight >= 0.f, "loss_kd: bad alpha / temperature / weight");
+  TD_CHECK(displ_weight == 0.f || (displ_col >= 0 && displ_col_t >= 0), "loss_kd: displ_weight without both displacement columns");
+  hipLaunchKernelGGL(loss_kd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, head_out, rows, ld, K1, hard, soft,
+                     cls_w, displ_col, labelD, teacher, ld_t, displ_col_t, alpha, temperature, displ_weight, grad_scale,
+                     out5, dhead);
+  TD_LAUNCH_CHECK("loss_kd");
+  return TDEED_OK;
+}
+
 // ------------------------------------------------------------------------------------------ heads backward
-// out = x W^T + b  (x [rows][C] in T, W fp32 [n_out][C]):  dx = dout W (written in T),
+// out = x W^T + b (x [rows][C] in T, W fp32 [n_out][C]):  dx = dout W (written in T),
 // dW[o][c] = sum_r dout[r][o] x[r][c], db[o] = sum_r dout[r][o]   (fp32, deterministic two-stage reduction).
 template <typename T>
 __global__ __launch_bounds__(256) void heads_bwd_dx_kernel(const float* __restrict__ dout, int rows, int C,

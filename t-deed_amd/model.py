@@ -70,6 +70,8 @@ class TDEEDModel:
             #   augment_fn(frames (B,T,3,H,W) uint8|fp32 0..255 on the device, crop (top,left,h,w)|None) -> frames of the
             #   crop window (B,T,3,h,w), uint8 or fp32 0..255, on the device (flips included, if wanted)
             self.augment_generator = None           # torch.Generator for the augmentation draws (None: the global CPU one)
+            self._kd_wanted = False                 # a teacher is set (TDEEDModel.distill_from): train-mode forwards hand
+            self._kd_view = None                    # ... their view (crop-window frames, per-frame flip flags) over here
             self.dropout_mask_fn = None             # optional hook replaying a recorded dropout draw of the heads:
             #   dropout_mask_fn(B, T, C, n_heads) -> n_heads tensors (B,T,C) of 0 / 2 (class head(s) first, displacement last)
 
@@ -205,6 +207,48 @@ class TDEEDModel:
                 return {"im_feat": im_feat, "displ_feat": head[..., displ_col], "_head_out": head}, y
             return im_feat, y
 
+        def _draw_view(self, x):
+            """The draws of the training branch (model.py:110-129) on frames (B,T,3,H,W) on the device: one random crop window
+            for the whole batch, then augment_fn or the built-in per-clip augmentation and flips.
+            -> (frames, crop, flip_c): the frames after the augmentation (the crop window only once it has been applied),
+            the window (top, left, h, w) that is still to be cut out of them or None, and the per-clip flip flags (B,) uint8
+            on the CPU, None when no clip flips."""
+            B, T, _, H, W = x.shape
+            cd = self.croping
+            crop = None
+            if cd and (cd != H or cd != W):
+                # torchvision RandomCrop.get_params: torch.randint for the row, then for the column; ONE window for
+                # the whole batch (model.py:115 crops the 5-D tensor)
+                g = self.augment_generator
+                top = int(torch.randint(0, H - cd + 1, size=(1,), generator=g).item())
+                left = int(torch.randint(0, W - cd + 1, size=(1,), generator=g).item())
+                crop = (top, left, cd, cd)
+            flip_c = None
+            if self.augment_fn is not None:
+                x = self.augment_fn(x, crop)
+                crop = None
+                if x.dtype not in (torch.uint8, torch.float32) or not x.is_cuda:
+                    raise TypeError("augment_fn must return uint8 / float32 frames on the device")
+                x = x.contiguous()
+            else:
+                prm, flip_c = augment.draw_params(B, self.augment_generator)
+                if not augment.is_identity(prm):
+                    x = augment.apply(x, prm, crop)                 # fp32 0..255 frames of the crop window
+                    crop = None
+                if not bool(flip_c.any()):
+                    flip_c = None
+            return x, crop, flip_c
+
+        def _view_of(self, x, crop, flip_c):
+            """What `_draw_view` drew as an eval-mode forward takes it (ForwardEngine.forward_augmented): the crop-window
+            frames (B,T,3,h,w), contiguous, and the per-frame flip flags (B*T,) uint8 on the device or None."""
+            if crop is not None:
+                x = x[..., crop[0]:crop[0] + crop[2], crop[1]:crop[1] + crop[3]]
+            flip_frames = None
+            if flip_c is not None:
+                flip_frames = flip_c.to(self._device).to(torch.uint8).repeat_interleave(x.shape[1]).contiguous()
+            return x.contiguous(), flip_frames
+
         def _forward_train(self, x, y, inference, augment_inference):
             """model.py:105-149 under .train(): batch-statistics BatchNorm (running stats updated), dropout in the heads;
             `inference` only selects the crop / augmentation branch (model.py:110-129) like in the reference."""
@@ -219,25 +263,12 @@ class TDEEDModel:
             cd = self.croping
             crop, flip = None, False
             if not inference:
-                if cd and (cd != H or cd != W):
-                    # torchvision RandomCrop.get_params: torch.randint for the row, then for the column; ONE window for
-                    # the whole batch (model.py:115 crops the 5-D tensor)
-                    g = self.augment_generator
-                    top = int(torch.randint(0, H - cd + 1, size=(1,), generator=g).item())
-                    left = int(torch.randint(0, W - cd + 1, size=(1,), generator=g).item())
-                    crop = (top, left, cd, cd)
-                if self.augment_fn is not None:
-                    x = self.augment_fn(x, crop)
-                    crop = None
-                    if x.dtype not in (torch.uint8, torch.float32) or not x.is_cuda:
-                        raise TypeError("augment_fn must return uint8 / float32 frames on the device")
-                    x = x.contiguous()
-                else:
-                    prm, flip_c = augment.draw_params(B, self.augment_generator)
-                    if not augment.is_identity(prm):
-                        x = augment.apply(x, prm, crop)
-                        crop = None
-                    flip = flip_c.to(self._device) if bool(flip_c.any()) else False
+                x, crop, flip_c = self._draw_view(x)
+                if flip_c is not None:
+                    flip = flip_c.to(self._device)
+                if self._kd_wanted:
+                    # distillation (TDEEDModel.distill_from): the teacher gets exactly these pixels
+                    self._kd_view = self._view_of(x, crop, flip_c)
             else:
                 if cd and (cd != H or cd != W):
                     crop = (int(round((H - cd) / 2.0)), int(round((W - cd) / 2.0)), cd, cd)
@@ -264,29 +295,10 @@ class TDEEDModel:
             if x.dtype not in (torch.uint8, torch.float32):
                 x = x.float()
             x = x.to(self._device).contiguous()
-            B, T, _, H, W = x.shape
-            cd = self.croping
-            crop = None
-            if cd and (cd != H or cd != W):
-                g = self.augment_generator
-                top = int(torch.randint(0, H - cd + 1, size=(1,), generator=g).item())
-                left = int(torch.randint(0, W - cd + 1, size=(1,), generator=g).item())
-                crop = (top, left, cd, cd)
-            flip_frames = None
-            if self.augment_fn is not None:
-                x = self.augment_fn(x, crop)
-                if x.dtype not in (torch.uint8, torch.float32) or not x.is_cuda:
-                    raise TypeError("augment_fn must return uint8 / float32 frames on the device")
-            else:
-                prm, flip_c = augment.draw_params(B, self.augment_generator)
-                if not augment.is_identity(prm):
-                    x = augment.apply(x, prm, crop)                 # fp32 0..255 frames of the crop window
-                elif crop is not None:
-                    x = x[..., crop[0]:crop[0] + cd, crop[1]:crop[1] + cd]
-                if bool(flip_c.any()):
-                    flip_frames = flip_c.to(self._device).to(torch.uint8).repeat_interleave(T).contiguous()
+            B, T = x.shape[:2]
+            x, flip_frames = self._view_of(*self._draw_view(x))
             eng = self.engine(act_dtype)
-            head, _ = eng.forward_augmented(x.contiguous(), flip_frames)
+            head, _ = eng.forward_augmented(x, flip_frames)
             pw = eng.pw
             return self._pack_head(head, B, T, pw.n_cls, pw.displ_col, y)
 
@@ -320,6 +332,9 @@ class TDEEDModel:
         self._model.to(device)
         self._num_classes = args.num_classes + 1
         self._stream = None
+        self._kd = None                 # distill_from(): (teacher, teacher_dtype, settings)
+        self._kd_last = None            # the teacher's head buffer of the last distillation step (a reference, not a copy)
+        self.loss_parts = None          # after a training epoch with a teacher: means of ce / mse / kd / kd_displ
 
     # BaseRGBModel (modules.py:35-55)
     def get_optimizer(self, opt_args):
@@ -339,6 +354,60 @@ class TDEEDModel:
         if eng.reducer is None:
             eng.set_reducer("auto")          # data-parallel job (torch.distributed initialised, world > 1): bucketed all-reduce
         return HipAdamW(eng, **opt_args), None
+
+    def distill_from(self, teacher, alpha=0.5, temperature=2.0, displ_weight=0.0, teacher_dtype=torch.bfloat16):
+        """Train this model against `teacher`'s per-frame class distributions (opt-in; `distill_from(None)` clears it).
+        Every training batch of epoch() then runs the teacher in eval mode on exactly the frames this model saw -- the same
+        crop window, augmentation, flips and mixup blend, through `teacher._model.engine(teacher_dtype).forward_augmented`,
+        with whatever weights that engine serves (the averaged ones inside `teacher.averaged()`) -- and minimises
+            (1-alpha) ce + mse + alpha kd + displ_weight kd_displ,
+        kd = temperature^2 * KL(softmax(t / temperature) || softmax(s / temperature)) averaged over the B*T frames and
+        kd_displ = mean (d - d_teacher)^2 (ops.loss_kd: one launch for the value and the gradient).  epoch() still returns
+        the mean of the total; `loss_parts` holds the means of ce, mse, kd and kd_displ.  Validation epochs never run the
+        teacher, and the teacher takes no random draw.
+        The settings and the teacher are not part of state_dict(): a reloaded model distils only after another call.
+        ValueError: ranges (0 <= alpha <= 1, temperature > 0, displ_weight >= 0), the model as its own teacher, another
+        num_classes or clip_len, the joint-dataset double head on either model, displ_weight > 0 unless both models have a
+        displacement head; at the first batch, a teacher on another device.  Feature-map distillation is out of scope."""
+        if teacher is None:
+            self._kd, self._kd_last, self.loss_parts = None, None, None
+            self._model._kd_wanted, self._model._kd_view = False, None
+            return self
+        alpha, temperature, displ_weight = ops.check_kd(alpha, temperature, displ_weight)
+        if not isinstance(teacher, TDEEDModel):
+            raise TypeError("distill_from: the teacher is a TDEEDModel")
+        if teacher is self or teacher._model is self._model:
+            raise ValueError("distill_from: the model cannot be its own teacher")
+        if teacher_dtype not in (torch.bfloat16, torch.float32):
+            raise ValueError(f"distill_from: teacher_dtype {teacher_dtype} (bfloat16 or float32)")
+        ms, mt = self._model, teacher._model
+        if ms._double_head or mt._double_head:
+            raise ValueError("distill_from: the joint-dataset double head is not covered")
+        if teacher._num_classes != self._num_classes:
+            raise ValueError(f"distill_from: the teacher has {teacher._num_classes - 1} classes, the model {self._num_classes - 1}")
+        if mt._cfg["clip_len"] != ms._cfg["clip_len"]:
+            raise ValueError(f"distill_from: the teacher's clip_len {mt._cfg['clip_len']} != {ms._cfg['clip_len']}")
+        if displ_weight > 0.0 and not (ms._radi_displacement > 0 and mt._radi_displacement > 0):
+            raise ValueError("distill_from: displ_weight > 0 needs a displacement head on both models")
+        self._kd = (teacher, teacher_dtype, dict(alpha=alpha, temperature=temperature, displ_weight=displ_weight))
+        self._kd_last, self.loss_parts = None, None
+        ms._kd_wanted = True
+        return self
+
+    def _teacher_head(self):
+        """Run the teacher on the view of the train-mode forward that has just run, on the current stream -> (its head
+        buffer (B*T, ld_t) fp32, kd settings for TemporalTrain.loss_fwd_bwd)."""
+        teacher, dt, settings = self._kd
+        ms, mt = self._model, teacher._model
+        if ms._norm_device(mt._device) != ms._norm_device(ms._device):
+            raise ValueError(f"distill_from: the teacher is on {mt._device}, the model on {ms._device}")
+        view, flip_frames = ms._kd_view
+        ms._kd_view = None
+        teng = mt.engine(dt)
+        thead, _ = teng.forward_augmented(view, flip_frames)
+        thead = thead.view(view.shape[0] * view.shape[1], -1)
+        self._kd_last = thead
+        return thead, dict(settings, ld_t=thead.shape[1], displ_col_t=teng.pw.displ_col)
 
     @property
     def _train_dtype(self):
@@ -1004,6 +1073,8 @@ def _train_epoch_impl(self, loader, optimizer, lr_scheduler, acc_grad_iter, fg_w
     self._model.train()
     optimizer.zero_grad()
     total = torch.zeros((), dtype=torch.float32, device=self.device)
+    parts = None if self._kd is None else torch.zeros(5, dtype=torch.float32, device=self.device)
+    self.loss_parts = None
     n = 0
     cur = torch.cuda.current_stream()
     with self._ctx():
@@ -1043,10 +1114,13 @@ def _train_epoch_impl(self, loader, optimizer, lr_scheduler, acc_grad_iter, fg_w
             pred, _ = self._model(frame, y=label, inference=False)
             head = (pred["_head_out"] if isinstance(pred, dict) else pred).reshape(B * T, -1)
             scale = 1.0 / acc_grad_iter
+            # distillation: the teacher's eval-mode forward on the student's view, on this stream, before the loss
+            thead, kd = (None, None) if parts is None else self._teacher_head()
             loss, dhead = eng.temporal.loss_fwd_bwd(
                 head, B, T, None if label is None else label.reshape(-1).contiguous(),
                 labelD=None if labelD is None else labelD.reshape(-1).contiguous(),
-                soft=None if soft is None else soft.reshape(B * T, -1).contiguous(), fg_weight=fg_weight, dataset=dataset)
+                soft=None if soft is None else soft.reshape(B * T, -1).contiguous(), fg_weight=fg_weight, dataset=dataset,
+                teacher=thead, kd=kd)
             last = (batch_idx + 1) % acc_grad_iter == 0
             # data parallel (one process per GPU under torchrun): the bucket all-reduces of the step's last micro-batch are
             # enqueued from inside the backward; optimizer.step() waits for them on the device
@@ -1058,11 +1132,18 @@ def _train_epoch_impl(self, loader, optimizer, lr_scheduler, acc_grad_iter, fg_w
                 if lr_scheduler is not None:
                     lr_scheduler.step()
                 optimizer.zero_grad()
-            total += loss[0]
+            if parts is None:
+                total += loss[0]
+            else:
+                parts += loss
             n += 1
             feeder.done(batch)
         self._stream.synchronize()
     self._model._engines = {}                      # the inference engines hold packed copies of the old weights
+    if parts is not None:
+        p = [float(v) / max(n, 1) for v in parts.tolist()]           # the epoch's one host synchronisation
+        self.loss_parts = dict(ce=p[1], mse=p[2], kd=p[3], kd_displ=p[4])
+        return p[0]
     return float(total.item()) / max(n, 1)
 
 

@@ -691,6 +691,52 @@ def loss_bwd(head_out, K1, cls_w, hard=None, soft=None, displ_col=-1, labelD=Non
     return dhead
 
 
+def check_kd(alpha, temperature, displ_weight):
+    """Ranges of the distillation settings -> (alpha, temperature, displ_weight) as floats; ValueError outside them."""
+    alpha, temperature, displ_weight = float(alpha), float(temperature), float(displ_weight)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha must lie in [0, 1], got {alpha}")
+    if not (temperature > 0.0 and temperature < float("inf")):
+        raise ValueError(f"temperature must be positive and finite, got {temperature}")
+    if not (displ_weight >= 0.0 and displ_weight < float("inf")):
+        raise ValueError(f"displ_weight must be non-negative and finite, got {displ_weight}")
+    return alpha, temperature, displ_weight
+
+
+def loss_kd(head_out, K1, cls_w, teacher, hard=None, soft=None, displ_col=-1, labelD=None, teacher_displ_col=-1, alpha=0.5,
+            temperature=2.0, displ_weight=0.0, grad_scale=1.0, want_grad=True):
+    """Distillation loss, value and gradient in one launch -> (out5 [total, ce, mse, kd, kd_displ], dhead (rows, ld) | None).
+    total = (1-alpha) ce + mse + alpha kd + displ_weight kd_displ with ce / mse the terms of loss() and
+    kd = temperature^2 * KL(softmax(teacher / temperature) || softmax(logits / temperature)) averaged over the rows,
+    kd_displ = mean (d - d_teacher)^2.  teacher: the teacher's head buffer (rows, ld_t) fp32, read in place: its first K1
+    columns are the class logits, column teacher_displ_col (or -1) its displacement."""
+    alpha, temperature, displ_weight = check_kd(alpha, temperature, displ_weight)
+    if head_out.dim() != 2 or teacher.dim() != 2:
+        raise ValueError("loss_kd: head_out (rows, ld) and teacher (rows, ld_t)")
+    rows, ld = head_out.shape
+    ld_t = teacher.shape[1]
+    if teacher.shape[0] != rows:
+        raise ValueError(f"teacher: {teacher.shape[0]} rows for {rows} rows")
+    if not 0 < K1 <= min(ld, ld_t):
+        raise ValueError(f"loss_kd: {K1} classes in heads of {ld} and {ld_t} (teacher) columns")
+    if not (-1 <= displ_col < ld and -1 <= teacher_displ_col < ld_t):
+        raise ValueError(f"loss_kd: displacement columns {displ_col} / {teacher_displ_col} outside heads of {ld} / {ld_t} columns")
+    if displ_weight > 0.0 and (displ_col < 0 or teacher_displ_col < 0):
+        raise ValueError("loss_kd: displ_weight > 0 needs a displacement column in both heads")
+    if cls_w.numel() < K1:
+        raise ValueError(f"cls_w: {cls_w.numel()} weights for {K1} classes")
+    _chk_labels(head_out, hard, soft, labelD, K1)
+    _chk(cls_w, "cls_w", torch.float32)
+    _chk(teacher, "teacher", torch.float32)
+    if teacher.device != head_out.device:
+        raise ValueError(f"teacher on {teacher.device}, head_out on {head_out.device}")
+    out = torch.empty(5, dtype=torch.float32, device=head_out.device)
+    dhead = torch.empty_like(head_out) if want_grad else None
+    call("tdeed_loss_kd", ptr(head_out), rows, ld, K1, ptr(hard), ptr(soft), ptr(cls_w), displ_col, ptr(labelD), ptr(teacher),
+         ld_t, teacher_displ_col, alpha, temperature, displ_weight, float(grad_scale), ptr(out), ptr(dhead), stream_ptr())
+    return out, dhead
+
+
 def loss2(head_out, B, T, K1a, K1b, dataset, hard, cls_w, displ_col=-1, labelD=None, want_grad=False, grad_scale=1.0,
           soft=None):
     """Double-head (joint dataset) loss of model.py:278-306 -> (out[3], dhead | None).  hard: int64 labels over the

@@ -255,11 +255,17 @@ class TemporalStack:
         n_cls = sum(w_.shape[0] for w_ in ws) - (1 if self.radi > 0 else 0)
         return n_cls, (n_cls if self.radi > 0 else -1), double
 
-    def loss_fwd_bwd(self, head_out, Bn, T, label, labelD=None, soft=None, fg_weight=5.0, grad_scale=1.0, dataset=None):
-        """Loss of model.py:308-319 (double head: 278-306) and its gradient w.r.t. head_out."""
+    def loss_fwd_bwd(self, head_out, Bn, T, label, labelD=None, soft=None, fg_weight=5.0, grad_scale=1.0, dataset=None,
+                     teacher=None, kd=None):
+        """Loss of model.py:308-319 (double head: 278-306) and its gradient w.r.t. head_out.
+        teacher (opt-in): the teacher's head buffer (Bn*T, ld_t) fp32 with kd = dict(displ_col_t=, alpha=, temperature=,
+        displ_weight=): the one ops.loss_kd launch instead of the two plain ones, loss then has five entries
+        [total, ce, mse, kd, kd_displ]."""
         n_cls, dcol, double = self.head_layout()
         ld = labelD if self.radi > 0 else None
         dev = head_out.device
+        if teacher is not None and double:
+            raise ValueError("distillation does not cover the joint-dataset double head")
         if double:
             names = self._head_names()
             K1a, K1b = self.sd[names[0] + ".weight"].shape[0], self.sd[names[1] + ".weight"].shape[0]
@@ -278,6 +284,10 @@ class TemporalStack:
         if fg_weight not in self._cls_w:        # built once per weight: no host->device copy inside a captured step
             self._cls_w[fg_weight] = torch.tensor([1.0] + [float(fg_weight)] * (K1 - 1), dtype=torch.float32, device=dev)
         cls_w = self._cls_w[fg_weight]
+        if teacher is not None:
+            return ops.loss_kd(head_out, K1, cls_w, teacher, hard=label, soft=soft, displ_col=dcol, labelD=ld,
+                               teacher_displ_col=kd.get("displ_col_t", -1), alpha=kd["alpha"], temperature=kd["temperature"],
+                               displ_weight=kd["displ_weight"], grad_scale=grad_scale)
         loss = ops.loss(head_out, K1, cls_w, hard=label, soft=soft, displ_col=dcol, labelD=ld)
         dhead = ops.loss_bwd(head_out, K1, cls_w, hard=label, soft=soft, displ_col=dcol, labelD=ld, grad_scale=grad_scale)
         return loss, dhead
