@@ -67,6 +67,33 @@ __device__ __forceinline__ float bnk_row16_sum(float v) {
   return v;
 }
 
+// Piece i = tid, tid + BNK_THR, ... of a [pixels][n 16-byte chunks] image, walked by adds: one IDiv::divmod for the first
+// piece, then (pixel, chunk) step by (BNK_THR / n, BNK_THR % n) with one carry, and two byte offsets -- pixel * sa + (ck0 +
+// chunk) * 16 and the same with sb -- step with them.  A divmod per piece (float multiply, two conversions, a multiply-low,
+// two fix-ups) and a multiply per offset were a third of the vector instructions of the staging passes, which are bound by
+// issue, not by bytes.  Members a caller does not read cost nothing (the walk is inlined).
+struct BnkWalk {
+  int px, ck, oa, ob;
+  int n, stq, str, da0, da1, db0, db1;                   // wave-uniform: the steps without / with a carry into the next pixel
+  __device__ __forceinline__ BnkWalk(const IDiv& d, int i, int ck0, int sa, int sb) : n(d.d) {
+    d.divmod(i, px, ck);
+    stq = d.div(BNK_THR);
+    str = BNK_THR - stq * n;
+    oa = px * sa + (ck + ck0) * 16;
+    ob = px * sb + (ck + ck0) * 16;
+    da0 = stq * sa + str * 16; da1 = da0 + sa - n * 16;
+    db0 = stq * sb + str * 16; db1 = db0 + sb - n * 16;
+  }
+  __device__ __forceinline__ void step() {
+    ck += str;
+    const bool c = ck >= n;
+    ck -= c ? n : 0;
+    px += c ? stq + 1 : stq;
+    oa += c ? da1 : da0;
+    ob += c ? db1 : db0;
+  }
+};
+
 // FPW frames per workgroup, NPTM >= ceil(FPW * hw / 16) pixel tiles
 // TAPM: conv2's k-slot order (BneckP::w2_tap_major) as a compile-time constant -- as a run-time select the same addresses
 // cost the conv2 phase its whole gain (186 vs 175 stamp units: measured)
@@ -144,19 +171,22 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) wc1[ks] = p.w1f[((long)wv * KS + ks) * 64 + lane];
   }
+  // 1 / (pixels of a frame), for the fusion weights and the squeeze means: the IEEE division is a dozen vector instructions;
+  // made once, here, where the wave waits for its first requests anyway (opaque, or it is made again where it is used)
+  float inv_hw = 1.0f / (float)hw;
+  asm volatile("" : "+v"(inv_hw));
   BN_STAMP(0);
   // ---- P0: x (gate-shift columns spliced in) -> region A; pads, zero row
   {
     // the folded BatchNorm tables are requested FIRST and stored after the frames: behind the frames' LDS stores (where they
     // used to be read) they were a second, exposed memory round trip per workgroup
-    constexpr int NBV = (6 * 16 * ((KS * 32 + 15) / 16) + BNK_THR - 1) / BNK_THR;
-    float bv[NBV];
-#pragma unroll
-    for (int j = 0; j < NBV; ++j) {
-      const int i = tid + j * BNK_THR;
-      const int v = min(i / CP, 5), c = i - (i / CP) * CP;
-      const float* src = v == 0 ? p.s1 : v == 1 ? p.h1 : v == 2 ? p.s2 : v == 3 ? p.h2 : v == 4 ? p.s3 : p.h3;
-      bv[j] = src[min(c, C - 1)];
+    // thread = channel (CP <= 384 < BNK_THR), one request per table: six uniform bases and one shared offset -- as
+    // (table, channel) = divmod(tid + j * BNK_THR, CP) every request paid an integer division and a five-way pointer select
+    static_assert(KS * 32 <= BNK_THR, "one thread per channel of a BatchNorm table");
+    float bv[6];
+    {
+      const int c = min(tid, C - 1);
+      bv[0] = p.s1[c]; bv[1] = p.h1[c]; bv[2] = p.s2[c]; bv[3] = p.h2[c]; bv[4] = p.s3[c]; bv[5] = p.h3[c];
     }
     const int cpr = C >> 3;
     const bf16_t* gg = p.G ? p.G + (long)f0 * hw * p.Fp : nullptr;
@@ -174,8 +204,12 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
     u32x4 bxc[3], bxn[3], bxp[3];
     f32x2 bga[3];
     float bgn[3], bgp[3];
+    int bpx[3], bck[3];                                          // (pixel, chunk) of this thread's three pieces of the slice
     const int sfs = (FPW > 1 && tid >= gF) ? 1 : 0, sc_ = tid - sfs * gF;          // sums: thread = (frame slot, channel)
     const IDiv dgt(blend ? gT : 1);
+    // the time index of the workgroup's first frame in its clip, divided out once; its second frame's is the next, or 0
+    const int gt0 = f0 - dgt.div(f0) * gT, gt1 = gt0 + 1 < gT ? gt0 + 1 : 0;
+    auto gtime = [&](int fs) { return fs ? gt1 : gt0; };
     if (blend) {
       {
         const int f = f0 + min(sfs, nfr - 1);
@@ -192,14 +226,16 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
         cwv = *(ci < 18 ? p.gs.cw1 + ci : ci < 36 ? p.gs.cw2 + (ci - 18) : ci == 36 ? p.gs.cb1 : p.gs.cb2);
       }
       const IDiv dnpc(npc8);
+      BnkWalk wk(dnpc, tid, 0, RS, 0);
 #pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const int i = min(tid + j * BNK_THR, npix * npc8 - 1);
-        int px, ck;
-        dnpc.divmod(i, px, ck);
+      for (int j = 0; j < 3; ++j, wk.step()) {
+        // (a piece behind the last one requests from the last pixel and is never blended; a clamp, not a compare whose lane
+        //  mask would stay live in scalar registers until the blend below)
+        const int px = min(wk.px, npix - 1), ck = wk.ck;
+        bpx[j] = px; bck[j] = ck;
         const int fs = (FPW > 1 && px >= hw) ? 1 : 0, pix = px - fs * hw;
         const int f = f0 + fs;
-        const int t = f - dgt.div(f) * gT;
+        const int t = gtime(fs);
         const long fn = t < gT - 1 ? f + 1 : f, fpv = t > 0 ? f - 1 : f;
         const bf16_t* xs0 = p.gs.x + (long)pix * p.gs.ldx + ck * 8;
         const long fstride = (long)hw * p.gs.ldx;
@@ -216,27 +252,34 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
     }
     constexpr int NLD = 9;                                       // independent 16-byte loads in flight per thread: a workgroup's
     u32x4 v[NLD];                                                // 72 KB (7 x 7 x 368, two frames) in ONE round trip
+    // a piece's source and LDS offsets are walked by adds from the first piece's (one divmod per pass, none in x_store, which
+    // takes the LDS offset x_issue left); the source is the workgroup's uniform base + a 32-bit byte offset (its frames are
+    // contiguous: < 2^31 bytes, checked by the launcher)
+    int lofs[NLD];
+    const unsigned char* xgb = reinterpret_cast<const unsigned char*>(xg);
     auto x_issue = [&](int i0) {
+      BnkWalk wk(dcpr, i0, ck0, RS, C * 2);
 #pragma unroll
-      for (int b = 0; b < NLD; ++b) {
-        const int i = min(i0 + b * BNK_THR, total - 1);
-        int px, ck;
-        dcpr.divmod(i, px, ck);
-        const int k = (ck + ck0) * 8;
-        const bf16_t* src = (gg && k < p.Fp) ? gg + (long)px * p.Fp + k : xg + (long)px * C + k;
-        v[b] = *reinterpret_cast<const u32x4*>(src);
+      for (int b = 0; b < NLD; ++b, wk.step()) {
+        lofs[b] = wk.oa;
+        asm volatile("" : "+v"(lofs[b]));                        // (made here: left to x_store's time, the nine carries stay live as
+                                                                 //  lane masks in scalar register pairs across the blend, and spill)
+        if constexpr (BLEND) {
+          // (the offsets ascend with the piece index: a piece behind the last one requests the last one's bytes)
+          v[b] = *reinterpret_cast<const u32x4*>(xgb + (unsigned)min(wk.ob, npix * C * 2 - 16));
+        } else {
+          const int px = min(wk.px, npix - 1), k = (wk.ck + ck0) * 8;
+          const bf16_t* src = (gg && k < p.Fp) ? gg + (long)px * p.Fp + k : xg + (long)px * C + k;
+          v[b] = *reinterpret_cast<const u32x4*>(src);
+        }
       }
     };
     auto x_store = [&](int i0) {
 #pragma unroll
       for (int b = 0; b < NLD; ++b) {
-        const int i = i0 + b * BNK_THR;
-        if (i < total) {
-          int px, ck;
-          dcpr.divmod(i, px, ck);
-          ck += ck0;
-          TD_LDS_CHECK(px * RS + ck * 16, 16, FPW * hw * RS);
-          *reinterpret_cast<u32x4*>(At + px * RS + ck * 16) = v[b];
+        if (i0 + b * BNK_THR < total) {
+          TD_LDS_CHECK(lofs[b], 16, FPW * hw * RS);
+          *reinterpret_cast<u32x4*>(At + lofs[b]) = v[b];
         }
       }
     };
@@ -247,7 +290,7 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
       // sums (zeros outside the clip) and conv weights -> scratch; fusion weights of the workgroup's frames: the 3x3 conv over
       // the (channel, time) plane of the spatial means + sigmoid; then the blend of this thread's pieces into region A
       if (sfs < nfr && sc_ < gF) {
-        const int f = f0 + sfs, t = f - dgt.div(f) * gT;
+        const int t = gtime(sfs);
 #pragma unroll
         for (int row = 0; row < 10; ++row) {
           const int t2 = t + (row >= 5 ? row - 5 : row) - 2;
@@ -260,9 +303,8 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
       {
         const int fs = (FPW > 1 && tid >= p.Fp) ? 1 : 0, c = tid - fs * p.Fp;
         if (fs < nfr && c < p.Fp) {
-          const int t = (f0 + fs) - dgt.div(f0 + fs) * gT;
+          const int t = gtime(fs);
           const int rb = 1 + 12 * fs;
-          const float inv_hw = 1.0f / (float)hw;
           float wgt = 0.f;
           if (c < gF) {
             const int g = c >= gFh;
@@ -293,15 +335,13 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
         }
       }
       __syncthreads();
-      const IDiv dnpc(npc8);
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
         const int i = tid + j * BNK_THR;
         if (i < npix * npc8) {
-          int px, ck;
-          dnpc.divmod(i, px, ck);
+          const int px = bpx[j], ck = bck[j];
           const int fs = (FPW > 1 && px >= hw) ? 1 : 0;
-          const int t = (f0 + fs) - dgt.div(f0 + fs) * gT;
+          const int t = gtime(fs);
           const bool has_next = t < gT - 1, has_prev = t > 0;
           // a PAIR of channels per step (F / 2 is even: a pair never straddles the gate groups or the fold's end), packed fp32
           // math -- the blend is bound by instruction issue: ~12 operations per element as scalar code, 3 items per thread
@@ -344,18 +384,20 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
     // the pad bytes behind every row (they meet the zero weights of the k pad, but 0 * stale NaN = NaN), the zero row
     // (region B's pad bytes that the grouped conv reads are written by conv1 itself: the zeros of its overhang tile)
     const int padp = (RS - C * 2) >> 4;
+    const IDiv dpad(padp);                                       // (padp = 0 at C = 368: no trip)
     for (int i = tid; i < 2 * FPW * hw * padp; i += BNK_THR) {
-      const int r = i / padp, j = i - r * padp;
+      int r, j;
+      dpad.divmod(i, r, j);
+      TD_LDS_CHECK(r * RS + C * 2 + j * 16, 16, 2 * FPW * hw * RS);
       *reinterpret_cast<u32x4*>(smem + r * RS + C * 2 + j * 16) = (u32x4){0u, 0u, 0u, 0u};
     }
     for (int i = tid; i < (RS + 64) >> 4; i += BNK_THR) *reinterpret_cast<u32x4*>(Zr + i * 16) = (u32x4){0u, 0u, 0u, 0u};
     // the k pad of the last loaded row reads on into the next row (KS * 32 > C + pad / 2): region B's head, or the first
     // unused row of region A when the workgroup has fewer frames -- finite before anything has been written there
     if (tid < 4) *reinterpret_cast<u32x4*>(At + npix * RS + tid * 16) = (u32x4){0u, 0u, 0u, 0u};
+    if (tid < CP) {
 #pragma unroll
-    for (int j = 0; j < NBV; ++j) {
-      const int i = tid + j * BNK_THR;
-      if (i < 6 * CP) bnv[i] = (i - (i / CP) * CP) < C ? bv[j] : 0.f;      // channels >= C: exact zeros out of every epilogue
+      for (int j = 0; j < 6; ++j) bnv[j * CP + tid] = tid < C ? bv[j] : 0.f;     // channels >= C: exact zeros out of every epilogue
     }
   }
   __syncthreads();
@@ -367,11 +409,16 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
   int prow[NPTM], srowA[NPTM];
 #pragma unroll
   for (int pt = 0; pt < NPTM; ++pt) {
-    const int px = pt * 16 + pl;
-    prow[pt] = (px < npix ? px : 0) * RS;
-    srowA[pt] = px < npix ? px * RS : (int)(Tr - At);
+    const int px = pt * 16 + pl, r = pl * RS + pt * (16 * RS);       // (the row's offset steps by a uniform: one multiply per lane)
+    prow[pt] = px < npix ? r : 0;
+    srowA[pt] = px < npix ? r : (int)(Tr - At);
   }
   const int dAB = (int)(Bt - At);
+  // where a row of srowA stores in region B (conv1's and conv3's outputs), + a column offset, from region A's base: the row's
+  // offset + dAB, or the trash row again -- the trash row lies behind region B, so that is a minimum (an add3 and a min per
+  // store, not a compare, a select and two adds)
+  const int trashA = (int)(Tr - At);
+  auto rowB = [&](int srow, int col) { return min(srow + dAB + col, trashA + col); };
   // one 16-channel tile of a 1x1 conv: acc[pt] = sum_ks W[ks] . act[pixel tile pt][ks].  The pixel tiles go in two halves:
   // the LDS reads of one half are issued before the MFMAs of the other (sched_barrier pins that order), so a wave's reads
   // travel under its own MFMAs instead of in front of them
@@ -471,9 +518,9 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
       bf16x4 o;
 #pragma unroll
       for (int r = 0; r < 4; ++r) o[r] = (bf16_t)fmaxf(acc[pt][r] * sc[r] + sh[r], 0.f);
-      unsigned char* dst = At + srowA[pt];
-      TD_LDS_CHECK(((srowA[pt] < dAB ? dst + dAB : dst) + ch0 * 2) - smem, 8, (Tr + RS) - smem);
-      *reinterpret_cast<bf16x4*>((srowA[pt] < dAB ? dst + dAB : dst) + ch0 * 2) = o;
+      const int so = rowB(srowA[pt], ch0 * 2);
+      TD_LDS_CHECK((At - smem) + so, 8, (Tr + RS) - smem);
+      *reinterpret_cast<bf16x4*>(At + so) = o;
     }
   };
 
@@ -540,9 +587,9 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
         bf16x4 o;
 #pragma unroll
         for (int r = 0; r < 4; ++r) o[r] = (bf16_t)fmaxf(acc[pt][r] * sc[r] + sh[r], 0.f);
-        unsigned char* dst = At + srowA[pt];
-        TD_LDS_CHECK(((srowA[pt] < dAB ? dst + dAB : dst) + ch0 * 2) - smem, 8, (Tr + RS) - smem);
-        *reinterpret_cast<bf16x4*>((srowA[pt] < dAB ? dst + dAB : dst) + ch0 * 2) = o;
+        const int so = rowB(srowA[pt], ch0 * 2);
+        TD_LDS_CHECK((At - smem) + so, 8, (Tr + RS) - smem);
+        *reinterpret_cast<bf16x4*>(At + so) = o;
       }
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) wc[ks] = wn[ks];
@@ -557,11 +604,16 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
     const int NU = NT;
     // per (pixel tile, k-step): LDS offset of the tap pixel's 8 input channels in region B (k-slot s = 4 ks + q = half * 9 +
     // tap), or of the zero row -- the same for every 16-channel unit up to the unit's own 32-byte column offset
+    // The offsets count from the LDS base and carry this wave's column offset (wv * 32): unit U = wv + 8 ju then reads at
+    // toff + 256 ju, an immediate of the read -- not one address add per read.
+    // They are LDS addresses (not offsets from smem, whose address would be added again at every read).
     int toff[NPTM][5];
+    typedef __attribute__((address_space(3))) const unsigned char lds_cuc;
+    typedef __attribute__((address_space(3))) const bf16x8 lds_cfrag;
+    const int lds0 = (int)(unsigned)(__UINTPTR_TYPE__)(lds_cuc*)smem;
     {
-      const int zoff = (int)(Zr - Bt);
-      int dyv[5], dxv[5], doff[5];
-      bool sok[5];
+      const int zoff = lds0 + (int)(Zr - smem) + wv * 32;
+      int tsel[5], doff[5];
 #pragma unroll
       for (int ks = 0; ks < 5; ++ks) {                   // k-slot -> (tap, half): tap-major fragments (engine.pack_gconv_frags(tap_major))
         // the two k-slots of a ds_read_b128 lane group (q = 0 / 1: slots 4 ks, 4 ks + 1) are the two 16-byte halves of ONE tap
@@ -573,24 +625,39 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
         const int half = TAPM ? (sidx & 1) : (sidx >= 9 ? 1 : 0);
         const int tap = TAPM ? (sidx >> 1) : sidx - 9 * half;
         const int ty = (tap >= 3 ? 1 : 0) + (tap >= 6 ? 1 : 0);
-        dyv[ks] = ty - 1;
-        dxv[ks] = tap - 3 * ty - 1;
-        sok[ks] = sidx < 18;
-        doff[ks] = (dyv[ks] * p.w + dxv[ks]) * RS + half * 16;
+        tsel[ks] = sidx < 18 ? tap : 9;                  // bit 9 of a pixel's tap mask is never set: the k pad reads the zero row
+        doff[ks] = ((ty - 1) * p.w + (tap - 3 * ty - 1)) * RS + half * 16;
+        asm volatile("" : "+v"(doff[ks]));               // (opaque: or the multiply by RS is redone per (tile, k-step), as (px + d) * RS)
       }
-      const IDiv dhw(hw), dw(p.w);
+      // A lane's pixel steps by 16 from tile to tile: its column and its row (counted over the workgroup's stacked frames: a
+      // frame is h whole rows) are divided out for tile 0 and then walk by (16 / w, 16 % w) with one carry, and its LDS row by
+      // 16 RS -- not two divmods and a multiply per tile.
+      const IDiv dw(p.w);
+      int Y, ox;
+      dw.divmod(pl, Y, ox);
+      const int sq = __builtin_amdgcn_readfirstlane(dw.div(16)), sr = 16 - sq * p.w;
+      int rel = lds0 + (int)(Bt - smem) + wv * 32 + pl * RS;       // the LDS address of the pixel's row in region B (+ the wave's columns)
 #pragma unroll
       for (int pt = 0; pt < NPTM; ++pt) {
-        const int px = min(pt * 16 + pl, npix - 1);
-        int f, r, oy, ox;
-        dhw.divmod(px, f, r);
-        dw.divmod(r, oy, ox);
+        const int oy = (FPW > 1 && Y >= p.h) ? Y - p.h : Y;
+        // the pixel's nine taps that fall inside the map, bit 3 (dy + 1) + (dx + 1): made once per pixel tile; a k-step then
+        // extracts its tap's bit as an all-ones / zero mask (one v_bfe_i32) instead of two adds and two range compares.
+        // A row behind the last pixel (the one whose store offset is the trash row's: srowA is tested, not the pixel index
+        // again -- that compare would be shared with prow's and stay live as a lane mask per tile) has no tap inside: it
+        // reads the zero row.
+        const int cm = 7 & ~(ox == 0 ? 1 : 0) & ~(ox == p.w - 1 ? 4 : 0);
+        const int vm = srowA[pt] < dAB ? (oy > 0 ? cm : 0) | (cm << 3) | (oy < p.h - 1 ? cm << 6 : 0) : 0;
 #pragma unroll
         for (int ks = 0; ks < 5; ++ks) {
-          const bool ok = sok[ks] && (unsigned)(oy + dyv[ks]) < (unsigned)p.h && (unsigned)(ox + dxv[ks]) < (unsigned)p.w;
-          toff[pt][ks] = ok ? px * RS + doff[ks] : zoff;
-          TD_LDS_CHECK((Bt - smem) + toff[pt][ks] + (NT - 1) * 32, 16, lds_bytes);
+          const int m = __builtin_amdgcn_sbfe(vm, tsel[ks], 1);
+          toff[pt][ks] = ((rel + doff[ks]) & m) | (zoff & ~m);       // (one v_bfi_b32)
+          TD_LDS_CHECK(toff[pt][ks] - lds0 + (NT - 1 - wv) * 32, 16, lds_bytes);
         }
+        ox += sr;
+        const bool carry = ox >= p.w;
+        ox -= carry ? p.w : 0;
+        Y += carry ? sq + 1 : sq;
+        rel += 16 * RS;
       }
     }
     // the weights of ALL of this wave's units are requested up front (the first came with conv1): a unit is ~1.3 k cycles of
@@ -610,57 +677,84 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
       if (U >= NU) return;
       const int ch0 = U * 16 + 4 * q;
       const f32x4 sc = *reinterpret_cast<const f32x4*>(bnv + 2 * CP + ch0), sh = *reinterpret_cast<const f32x4*>(bnv + 3 * CP + ch0);
-      float psum[FPW][4];
+      f32x2 psum[FPW][2];
 #pragma unroll
-      for (int f = 0; f < FPW; ++f)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) psum[f][r] = 0.f;
+      for (int f = 0; f < FPW; ++f) psum[f][0] = psum[f][1] = (f32x2){0.f, 0.f};
       // k-step outer, pixel tile inner: NPTM independent accumulators (a tile-at-a-time loop is five dependent MFMAs)
       f32x4 acc[NPTM];
 #pragma unroll
       for (int pt = 0; pt < NPTM; ++pt) acc[pt] = (f32x4){0.f, 0.f, 0.f, 0.f};
       {
         bf16x8 yf[NPTM];
-        const unsigned char* bu = Bt + U * 32;
+        const int bu = ju * (BNK_NW * 32);               // a constant once the unit is inlined
 #pragma unroll
-        for (int pt = 0; pt < HA; ++pt) yf[pt] = *reinterpret_cast<const bf16x8*>(bu + toff[pt][0]);
+        for (int pt = 0; pt < HA; ++pt) yf[pt] = *(lds_cfrag*)(__UINTPTR_TYPE__)(unsigned)(toff[pt][0] + bu);
 #pragma unroll
         for (int ks = 0; ks < 5; ++ks) {
 #pragma unroll
-          for (int pt = HA; pt < NPTM; ++pt) yf[pt] = *reinterpret_cast<const bf16x8*>(bu + toff[pt][ks]);
+          for (int pt = HA; pt < NPTM; ++pt) yf[pt] = *(lds_cfrag*)(__UINTPTR_TYPE__)(unsigned)(toff[pt][ks] + bu);
 #pragma unroll
           for (int pt = 0; pt < HA; ++pt) acc[pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfu[ks], yf[pt], acc[pt], 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
           if (ks + 1 < 5) {
 #pragma unroll
-            for (int pt = 0; pt < HA; ++pt) yf[pt] = *reinterpret_cast<const bf16x8*>(bu + toff[pt][ks + 1]);
+            for (int pt = 0; pt < HA; ++pt) yf[pt] = *(lds_cfrag*)(__UINTPTR_TYPE__)(unsigned)(toff[pt][ks + 1] + bu);
           }
 #pragma unroll
           for (int pt = HA; pt < NPTM; ++pt) acc[pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfu[ks], yf[pt], acc[pt], 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
+      // BN + ReLU, rounded to bf16 in pairs (one v_cvt_pk per two channels) -> y2 rows; the packed words stay in registers:
+      // the squeeze sums below take the rounded values out of them by a shift / a mask
+      u32x2 ow[NPTM];
+      const int cw8 = wv * 32 + 8 * q;
 #pragma unroll
       for (int pt = 0; pt < NPTM; ++pt) {
-        const int px = pt * 16 + pl;
-        const bool pok = px < npix;
-        bf16x4 o;
+        float e[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) o[r] = (bf16_t)fmaxf(acc[pt][r] * sc[r] + sh[r], 0.f);
-        *reinterpret_cast<bf16x4*>(At + srowA[pt] + ch0 * 2) = o;
-        const bool second = FPW > 1 && px >= hw;
+        for (int r = 0; r < 4; ++r) e[r] = fmaxf(acc[pt][r] * sc[r] + sh[r], 0.f);
+        const bf16x2 o01 = {(bf16_t)e[0], (bf16_t)e[1]}, o23 = {(bf16_t)e[2], (bf16_t)e[3]};
+        ow[pt] = (u32x2){__builtin_bit_cast(unsigned, o01), __builtin_bit_cast(unsigned, o23)};
+        TD_LDS_CHECK(srowA[pt] + cw8 + ju * (BNK_NW * 32), 8, (Tr + RS) - smem);
+        *reinterpret_cast<u32x2*>((At + (srowA[pt] + cw8)) + ju * (BNK_NW * 32)) = ow[pt];
+      }
+      // Squeeze sums: lane pl adds the rounded values of its pixel of each tile, tiles in ascending order, per frame, from
+      // +0.f -- as ONE running sum `cur` per channel pair.  Which frame a tile belongs to is uniform (in pt) for every tile but
+      // the one that holds frame 1's first pixel (tile tm): there the lanes still in frame 0 add and bank their sum, the others
+      // bank theirs and restart from +0.f.  Every other tile is two packed adds with no select; a tile that reaches behind the
+      // last pixel first clears the words of those lanes.  The earlier form added +0.f into the other frame's sum, and into
+      // both for a row behind the last pixel, behind three selects per value: those adds are exact (the sums start at +0.f and
+      // +0.f + -0.f == +0.f, so no sum is ever -0.f and s + 0.f == s bit for bit), so leaving them out keeps the bits; what is
+      // kept is each lane's order of additions, the first one (+0.f + v) included.
+      const f32x2 z2 = {0.f, 0.f};
+      f32x2 cur[2] = {z2, z2};
+      [[maybe_unused]] const int tm = hw >> 4;
+      TD_DEV_ASSERT(FPW == 1 || tm < NPTM);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float v = pok ? (float)o[r] : 0.f;
-          if (FPW > 1) psum[FPW - 1][r] += second ? v : 0.f;
-          psum[0][r] += second ? 0.f : v;
+      for (int pt = 0; pt < NPTM; ++pt) {
+        unsigned w0 = ow[pt][0], w1 = ow[pt][1];
+        if (pt * 16 + 16 > npix) {                       // (uniform)
+          const unsigned m = srowA[pt] < dAB ? ~0u : 0u;   // (the lane's pixel exists; see the tap masks above)
+          w0 &= m; w1 &= m;
+        }
+        const f32x2 v01 = {__builtin_bit_cast(float, w0 << 16), __builtin_bit_cast(float, w0 & 0xffff0000u)};
+        const f32x2 v23 = {__builtin_bit_cast(float, w1 << 16), __builtin_bit_cast(float, w1 & 0xffff0000u)};
+        if (FPW > 1 && pt <= 4 && pt == tm) {            // (uniform; FPW > 1 is hw <= 64: tm <= 4)
+          const bool fr0 = pt * 16 + pl < hw;
+          const f32x2 t0 = (fr0 ? cur[0] : z2) + v01, t1 = (fr0 ? cur[1] : z2) + v23;
+          psum[0][0] = fr0 ? t0 : cur[0]; psum[0][1] = fr0 ? t1 : cur[1];
+          cur[0] = fr0 ? z2 : t0; cur[1] = fr0 ? z2 : t1;
+        } else {
+          cur[0] += v01; cur[1] += v23;
         }
       }
+      psum[FPW - 1][0] = cur[0]; psum[FPW - 1][1] = cur[1];
 #pragma unroll
       for (int f = 0; f < FPW; ++f)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float v = bnk_row16_sum(psum[f][r]);
+          const float v = bnk_row16_sum(psum[f][r >> 1][r & 1]);
           if (pl == 0 && ch0 + r < C) pooled[f * C + ch0 + r] = v;
         }
       BN_STAMP(9 + ju);
@@ -699,16 +793,16 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
   // ---- P3: SE excitation of the workgroup's frames on the MFMA pipe (scratch: the dead y1 region), y2 *= gate in place
   {
     SeP se = p.se;
-    se.pooled = pooled; se.n_parts = 1; se.inv_cnt = 1.0f / (float)hw; se.C = C; se.gate_out = nullptr;
+    se.pooled = pooled; se.n_parts = 1; se.inv_cnt = inv_hw; se.C = C; se.gate_out = nullptr;
     se_excite_lds<KS, 3, true, BNK_NW, true>(se, 0, nfr, nfr - 1, gtab, C, Bt, p.dbg ? p.dbg + (long)blockIdx.x * 16 + 12 : nullptr,
                                              &sew1);
     const int cpr = C >> 3;
     const IDiv dcpr(cpr);
-    for (int i = tid; i < npix * cpr; i += BNK_THR) {
-      int px, ck;
-      dcpr.divmod(i, px, ck);
-      const float* g = gtab + ((FPW > 1 && px >= hw) ? C : 0) + ck * 8;
-      bf16x8* ptr8 = reinterpret_cast<bf16x8*>(At + px * RS + ck * 16);
+    BnkWalk wk(dcpr, tid, 0, RS, 0);                       // ~9 trips per thread: the division per trip counted nine times
+    for (int i = tid; i < npix * cpr; i += BNK_THR, wk.step()) {
+      const float* g = gtab + ((FPW > 1 && wk.px >= hw) ? C : 0) + wk.ck * 8;
+      TD_LDS_CHECK(wk.oa, 16, FPW * hw * RS);
+      bf16x8* ptr8 = reinterpret_cast<bf16x8*>(At + wk.oa);
       bf16x8 v = *ptr8;
       const f32x4 g0 = *reinterpret_cast<const f32x4*>(g), g1 = *reinterpret_cast<const f32x4*>(g + 4);
 #pragma unroll
@@ -734,7 +828,7 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
   u32x4 wr[2];
   f32x4 bs[3][2], bh[3][2];
   int ipx[3], ick[3];
-  const IDiv dnch(qtail ? nch : 1), dw_(p.w), dhw_(hw);
+  const IDiv dnch(qtail ? nch : 1), dw_(p.w);
   auto q_request = [&]() {                                     // the fragments
     if (!qtail) return;
 #pragma unroll
@@ -755,14 +849,20 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
   };
   // ---- P4: conv3 on the gated y2, + residual x, ReLU -> output rows in region B
   // residual of one channel tile: 4 channels of this lane's pixel per pixel tile, L2-hot
+  // A load's address is the workgroup's uniform base + a 32-bit offset: this lane's offset in the first pixel tile (made once
+  // per wave) + the tile's channel offset (once per channel tile) + the pixel tile's uniform step, clamped to the last pixel's
+  // row -- an add and a min per load, where a select, a 64-bit multiply and a 64-bit add were.  No table of row offsets as
+  // prow is: at 7 x 7 x 368 the kernel has no seven registers left in this phase.  Rows behind the last pixel read the last
+  // row (they are never stored); lanes whose channels lie behind C (the last tile of C = 152) read the row's last four
+  // channels: their sums land in the row pad, which nothing reads.
+  const int plc = pl * (C * 2);
+  const unsigned char* xrb = reinterpret_cast<const unsigned char*>(xg);
   auto load_res = [&](int T, bf16x4 (&rres)[NPTM]) {
-    const int ch0 = T * 16 + 4 * q;
-    const bool cok = ch0 < C;
+    const int cofs = min(T * 16 + 4 * q, C - 4) * 2;
+    const int lo = plc + cofs, lim = (npix - 1) * (C * 2) + cofs;
 #pragma unroll
-    for (int pt = 0; pt < NPTM; ++pt) {
-      const int px = pt * 16 + pl;
-      rres[pt] = *reinterpret_cast<const bf16x4*>(xg + (long)((px < npix && cok) ? px : 0) * C + (cok ? ch0 : 0));
-    }
+    for (int pt = 0; pt < NPTM; ++pt)
+      rres[pt] = *reinterpret_cast<const bf16x4*>(xrb + (unsigned)min(lo + pt * 16 * (C * 2), lim));
   };
   auto epi3 = [&](int T, const f32x4 (&acc)[NPTM], const bf16x4 (&rres)[NPTM]) {
     const int ch0 = T * 16 + 4 * q;
@@ -772,8 +872,9 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
       bf16x4 o;
 #pragma unroll
       for (int r = 0; r < 4; ++r) o[r] = (bf16_t)fmaxf(acc[pt][r] * sc[r] + sh[r] + (float)rres[pt][r], 0.f);
-      unsigned char* dst = At + srowA[pt];
-      *reinterpret_cast<bf16x4*>((srowA[pt] < dAB ? dst + dAB : dst) + ch0 * 2) = o;
+      const int so = rowB(srowA[pt], ch0 * 2);
+      TD_LDS_CHECK((At - smem) + so, 8, (Tr + RS) - smem);
+      *reinterpret_cast<bf16x4*>(At + so) = o;
     }
   };
   if constexpr (TRIPLE) {
@@ -829,14 +930,9 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
         for (int ks = 0; ks < KS; ++ks) wn[ks] = p.w3f[((long)(T + BNK_NW) * KS + ks) * 64 + lane];
       }
       const int ch0 = T * 16 + 4 * q;
-      const bool cok = ch0 < C;
       const f32x4 sc = *reinterpret_cast<const f32x4*>(bnv + 4 * CP + ch0), sh = *reinterpret_cast<const f32x4*>(bnv + 5 * CP + ch0);
       bf16x4 rres[NPTM];                                 // residual: 4 channels of this lane's pixel, L2-hot
-#pragma unroll
-      for (int pt = 0; pt < NPTM; ++pt) {
-        const int px = pt * 16 + pl;
-        rres[pt] = *reinterpret_cast<const bf16x4*>(xg + (long)((px < npix && cok) ? px : 0) * C + (cok ? ch0 : 0));
-      }
+      load_res(T, rres);
       f32x4 acc[NPTM];
       contract(wc, At, acc);
 #pragma unroll
@@ -844,8 +940,9 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
         bf16x4 o;
 #pragma unroll
         for (int r = 0; r < 4; ++r) o[r] = (bf16_t)fmaxf(acc[pt][r] * sc[r] + sh[r] + (float)rres[pt][r], 0.f);
-        unsigned char* dst = At + srowA[pt];
-        *reinterpret_cast<bf16x4*>((srowA[pt] < dAB ? dst + dAB : dst) + ch0 * 2) = o;
+        const int so = rowB(srowA[pt], ch0 * 2);
+        TD_LDS_CHECK((At - smem) + so, 8, (Tr + RS) - smem);
+        *reinterpret_cast<bf16x4*>(At + so) = o;
       }
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) wc[ks] = wn[ks];
@@ -915,9 +1012,9 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
     {
       const IDiv d6(6);
       for (int i = tid; i < npix * 6; i += BNK_THR) {
-        int px, jg, fr, pix, py, pxx;
+        int px, jg, py, pxx;
         d6.divmod(i, px, jg);
-        dhw_.divmod(px, fr, pix);
+        const int pix = (FPW > 1 && px >= hw) ? px - hw : px;    // (a workgroup has at most two frames: no division by hw)
         dw_.divmod(pix, py, pxx);
         float sum = 0.f;
 #pragma unroll
@@ -937,6 +1034,8 @@ __global__ __launch_bounds__(BNK_THR, 1) void bneck_kernel(const BneckP p) {
     const int cpr = C >> 3;
     const IDiv dcpr(cpr);
     bf16_t* og = p.out + (long)f0 * hw * C;
+    // (a division per piece, not the BnkWalk of the other passes: walked, this phase measured 250-350 cycles LONGER at both
+    //  shipped shapes -- it is bound by the stores, and the walk's set-up stands in front of the first one)
     for (int i = tid; i < npix * cpr; i += BNK_THR) {
       int px, ck;
       dcpr.divmod(i, px, ck);
@@ -1006,6 +1105,8 @@ static int bneck_fill(BneckP& p, const void* x, int N, int h, int w, int C, cons
            "bneck: null pointer");
   TD_CHECK(N > 0 && tdeed_bneck_fits(h, w, C, R), "bneck: geometry h=%d w=%d C=%d R=%d unsupported", h, w, C, R);
   TD_CHECK(!out2 || (n2 % 8 == 0 && n2 > 0 && n2 <= C), "bneck: bad second output width %d", n2);
+  // the kernel addresses a workgroup's frames of x and out as a uniform base + a 32-bit byte offset
+  TD_CHECK((long long)bneck_fpw(h * w) * h * w * C * 2 < (1LL << 31), "bneck: a workgroup's frames exceed 2^31 bytes");
   p = BneckP{};
   p.x = (const bf16_t*)x;
   p.w1f = (const bf16x8*)w1f; p.s1 = s1; p.h1 = h1;

@@ -75,14 +75,19 @@ __device__ __forceinline__ void se_excite_lds(const SeP& se, long f_first, int n
   // ... and the biases of this lane's rows (a load behind the MFMAs would be one more exposed round trip per tile)
   constexpr int MAXT1 = (6 + NW - 1) / NW;               // R <= 96: at most 6 hidden tiles
   float b1v[MAXT1][4], b2v[MAXT2][4];
+  // (the index is clamped and >= 0: a 32-bit byte offset on the array's uniform base, not a sign extension and a 64-bit add
+  //  per element)
+  auto bias = [](const float* __restrict__ b, int i) {
+    return *reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(b) + (unsigned)i * 4u);
+  };
 #pragma unroll
   for (int j = 0; j < MAXT1; ++j)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) b1v[j][e] = se.b1[min((wv + j * NW) * 16 + 4 * q + e, R - 1)];
+    for (int e = 0; e < 4; ++e) b1v[j][e] = bias(se.b1, min((wv + j * NW) * 16 + 4 * q + e, R - 1));
 #pragma unroll
   for (int j = 0; j < MAXT2; ++j)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) b2v[j][e] = se.b2[min((wv + j * NW) * 16 + 4 * q + e, C - 1)];
+    for (int e = 0; e < 4; ++e) b2v[j][e] = bias(se.b2, min((wv + j * NW) * 16 + 4 * q + e, C - 1));
   // ---- squeeze sums -> means -> hi / lo (pad columns and unused frame columns are zero)
   const int c4n = KS1 * 8;
   for (int i = tid; i < 16 * c4n; i += NW * 64) {
