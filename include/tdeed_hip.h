@@ -430,6 +430,18 @@ int tdeed_loss_kd(const float* head_out, int rows, int ld, int K1, const int64_t
                   const float* cls_w, int displ_col, const float* labelD, const float* teacher, int ld_t, int displ_col_t,
                   float alpha, float temperature, float displ_weight, float grad_scale, float* out5, float* dhead,
                   void* stream);
+/* loss options (opt-in): label smoothing, a focal exponent and free per-class weights cls_w[K1] on the classification term,
+ * value and gradient in one launch; with teacher != NULL the distillation terms of tdeed_loss_kd on top, with teacher ==
+ * NULL kd = kd_displ = 0 and alpha / displ_weight must be 0 (ld_t, displ_col_t, temperature are then ignored).
+ * ce = sum_r sum_c w_c t'_c (1 - p_c)^focal_gamma (-log p_c) / den,  t' = (1 - label_smoothing) t + label_smoothing / K1
+ * (t: one-hot of the hard label or the soft row), den = sum_r w[y_r] (hard) or rows (soft); focal_gamma = 0 is
+ * F.cross_entropy(weight=, label_smoothing=).  label_smoothing = focal_gamma = 0 gives the bits of tdeed_loss_kd, without
+ * a teacher those of tdeed_loss_fwd + tdeed_loss_bwd.  out5: total, ce, mse, kd, kd_displ.  dhead may be NULL.
+ * Argument errors: label_smoothing outside [0, 1], focal_gamma negative or not finite, and those of tdeed_loss_kd. */
+int tdeed_loss_opt(const float* head_out, int rows, int ld, int K1, const int64_t* hard, const float* soft,
+                   const float* cls_w, int displ_col, const float* labelD, const float* teacher, int ld_t, int displ_col_t,
+                   float alpha, float temperature, float displ_weight, float label_smoothing, float focal_gamma,
+                   float grad_scale, float* out5, float* dhead, void* stream);
 long tdeed_heads_bwd_workspace(int rows, int C, int n_out);
 int tdeed_heads_bwd(const float* dout, const void* x, int rows, int C, const float* w, int n_out, void* dx,
                     float* dw, float* db, void* workspace, int dtype, void* stream);

@@ -179,6 +179,8 @@ _SIGS = {
     "tdeed_loss_bwd": ([P, c_int, c_int, c_int, P, P, P, c_int, P, c_float, P, P], c_int),
     "tdeed_loss_kd": ([P, c_int, c_int, c_int, P, P, P, c_int, P, P, c_int, c_int, c_float, c_float, c_float, c_float, P, P, P],
                       c_int),
+    "tdeed_loss_opt": ([P, c_int, c_int, c_int, P, P, P, c_int, P, P, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
+                        c_float, P, P, P], c_int),
     "tdeed_heads_bwd_workspace": ([c_int, c_int, c_int], c_long),
     "tdeed_heads_bwd": ([P, P, c_int, c_int, P, c_int, P, P, P, P, c_int, P], c_int),
     "tdeed_adamw_step": ([P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_float, c_int, c_float, P], c_int),

@@ -190,6 +190,185 @@ extern "C" int tdeed_loss_kd(const float* head_out, int rows, int ld, int K1, co
   return TDEED_OK;
 }
 
+// ------------------------------------------------------------------------------------------ loss options
+// Label smoothing eps, focal exponent gamma and free per-class weights w on the classification term, value and gradient in
+// one launch (opt-in: TDEEDModel.loss_options); with a teacher the distillation terms of loss_kd_kernel on top:
+//   total = (1-a) CE + MSE + a KD + b KDdispl,   MSE / KD / KDdispl and their gradients exactly loss_kd_kernel's.
+// Per row with logits s:  lse = m + log sum exp(s - m),  logp_c = s_c - lse  (never the log of a rounded probability),
+//   p_c = exp(logp_c),  q_c = 1 - p_c = -expm1(logp_c),  t'_c = (1-eps) t_c + eps / K1  (t: one-hot or the soft row),
+//   a_c = w_c t'_c,
+//   CE  = sum_r sum_c a_c q_c^gamma (-logp_c) / den,   den = sum_r w[y_r] (hard) or rows (soft): torch's rule
+//   g_c = -a_c q_c^gamma (gamma p_c rho_c + 1),  rho_c = -logp_c / q_c where q_c > 0, else 1 (its limit)
+//   dlogit_k = (g_k - p_k sum_c g_c) gscale / den
+// The rho form keeps a saturated row (p_y == 1 in fp32: logp = 0, q = 0) finite for every gamma: q^(gamma-1) never
+// appears.  Terms with a_c == 0 are skipped, at gamma == 0 powf is not called, nothing is clamped.  g_k waits in dhead
+// between the two class passes (written and read by the same thread).
+// eps == gamma == 0 takes loss_kernel's / loss_bwd_kernel's own loops on a uniform branch: their bits, and with a teacher
+// loss_kd_kernel's.  Single block, fixed fold order, no atomics.
+__global__ __launch_bounds__(256) void loss_opt_kernel(const float* __restrict__ head, int rows, int ld, int K1,
+                                                       const int64_t* __restrict__ hard, const float* __restrict__ soft,
+                                                       const float* __restrict__ cls_w, int displ_col,
+                                                       const float* __restrict__ labelD,
+                                                       const float* __restrict__ teacher, int ld_t, int displ_col_t,
+                                                       float alpha, float tau, float beta, float eps, float gamma,
+                                                       float gscale, float* __restrict__ out, float* __restrict__ dhead) {
+  __shared__ float scratch[8];
+  float den = 0.f;
+  if (!soft)
+    for (int r = threadIdx.x; r < rows; r += 256) {
+      const int y = (int)hard[r];
+      den += cls_w[(y >= 0 && y < K1) ? y : 0];                  // out-of-range labels are never indexed
+    }
+  den = soft ? (float)rows : block_sum<4>(den, scratch);
+  const float inv = gscale / den;
+  const float oma = 1.0f - alpha;
+  const float it = 1.0f / tau;
+  const float gk = alpha * tau * gscale / (float)rows;
+  const float gd = 2.0f * beta * gscale / (float)rows;
+  const bool kdon = teacher != nullptr;
+  const bool both_d = kdon && displ_col >= 0 && displ_col_t >= 0;
+  const bool neutral = eps == 0.f && gamma == 0.f;
+  const float ome = 1.0f - eps, eu = eps / (float)K1;
+  float num = 0.f, se = 0.f, bad = 0.f, kd = 0.f, kdd = 0.f;
+  for (int r = threadIdx.x; r < rows; r += 256) {
+    const float* lg = head + (long)r * ld;
+    float m = lg[0];
+    for (int k = 1; k < K1; ++k) m = fmaxf(m, lg[k]);
+    float s = 0.f;
+    for (int k = 0; k < K1; ++k) s += expf(lg[k] - m);
+    const float lse = m + logf(s);
+    const float is = 1.0f / s;
+    float* dg = dhead ? dhead + (long)r * ld : nullptr;
+    if (dg)
+      for (int k = K1; k < ld; ++k) dg[k] = 0.f;
+    if (neutral) {
+      if (soft) {
+        const float* p = soft + (long)r * K1;
+        float a = 0.f;
+        for (int k = 0; k < K1; ++k) a += cls_w[k] * p[k] * (lse - lg[k]);
+        num += a;
+      } else {
+        int yk = (int)hard[r];
+        if (yk < 0 || yk >= K1) { bad = 1.f; yk = 0; }
+        num += cls_w[yk] * (lse - lg[yk]);
+      }
+      if (dg) {
+        if (soft) {
+          const float* p = soft + (long)r * K1;
+          float wp = 0.f;
+          for (int k = 0; k < K1; ++k) wp += cls_w[k] * p[k];
+          for (int k = 0; k < K1; ++k) dg[k] = (expf(lg[k] - m) * is * wp - cls_w[k] * p[k]) * inv;
+        } else {
+          int y = (int)hard[r];
+          if (y < 0 || y >= K1) y = 0;
+          const float wy = cls_w[y];
+          for (int k = 0; k < K1; ++k) dg[k] = wy * (expf(lg[k] - m) * is - (k == y ? 1.f : 0.f)) * inv;
+        }
+      }
+    } else {
+      const float* p = soft ? soft + (long)r * K1 : nullptr;
+      int y = 0;
+      if (!soft) {
+        y = (int)hard[r];
+        if (y < 0 || y >= K1) { bad = 1.f; y = 0; }
+      }
+      float a = 0.f, gsum = 0.f;
+      for (int k = 0; k < K1; ++k) {
+        const float t = p ? p[k] : (k == y ? 1.f : 0.f);
+        const float ak = cls_w[k] * (ome * t + eu);
+        float g = 0.f;
+        if (ak != 0.f) {
+          const float logp = lg[k] - lse;
+          float f = ak, h = 1.f;                                   // a q^gamma,  gamma p rho + 1
+          if (gamma != 0.f) {
+            const float q = -expm1f(logp);
+            const float rho = q > 0.f ? -logp / q : 1.f;
+            f = ak * powf(q, gamma);
+            h = gamma * expf(logp) * rho + 1.f;
+          }
+          a -= f * logp;
+          g = -f * h;
+        }
+        gsum += g;
+        if (dg) dg[k] = g;
+      }
+      num += a;
+      if (dg)
+        for (int k = 0; k < K1; ++k) dg[k] = (dg[k] - expf(lg[k] - lse) * gsum) * inv;
+    }
+    if (kdon) {
+      const float* tg = teacher + (long)r * ld_t;
+      float mt = tg[0];
+      for (int k = 1; k < K1; ++k) mt = fmaxf(mt, tg[k]);
+      // the tempered pair: x -> x / tau is monotone, so the row maxima carry over
+      const float ms = m * it;
+      mt *= it;
+      float ss = 0.f, st = 0.f;
+      for (int k = 0; k < K1; ++k) { ss += expf(lg[k] * it - ms); st += expf(tg[k] * it - mt); }
+      const float lss = ms + logf(ss), lst = mt + logf(st);
+      const float ips = 1.0f / ss, ipt = 1.0f / st;
+      float a = 0.f;
+      for (int k = 0; k < K1; ++k) {
+        const float ps = expf(lg[k] * it - ms) * ips, qt = expf(tg[k] * it - mt) * ipt;
+        a += qt * ((tg[k] * it - lst) - (lg[k] * it - lss));
+        if (dg) dg[k] = oma * dg[k] + gk * (ps - qt);
+      }
+      kd += a;
+    }
+    float gdis = 0.f;
+    if (displ_col >= 0 && labelD) {
+      const float d = lg[displ_col] - labelD[r];
+      se += d * d;
+      gdis = 2.0f * (lg[displ_col] - labelD[r]) * gscale / (float)rows;
+    }
+    if (both_d) {
+      const float e = lg[displ_col] - teacher[(long)r * ld_t + displ_col_t];
+      kdd += e * e;
+      gdis += gd * e;
+    }
+    if (dg && displ_col >= 0 && (labelD || both_d)) dg[displ_col] = gdis;
+  }
+  num = block_sum<4>(num, scratch);
+  se = block_sum<4>(se, scratch);
+  bad = block_sum<4>(bad, scratch);
+  kd = block_sum<4>(kd, scratch);
+  kdd = block_sum<4>(kdd, scratch);
+  if (threadIdx.x == 0) {
+    const float ce = bad > 0.f ? __builtin_nanf("") : (soft ? num / (float)rows : num / den);
+    const float mse = (displ_col >= 0 && labelD) ? se / (float)rows : 0.f;
+    const float kdv = kdon ? tau * tau * kd / (float)rows : 0.f;
+    const float kddv = both_d ? kdd / (float)rows : 0.f;
+    out[0] = kdon ? oma * ce + mse + alpha * kdv + beta * kddv : ce + mse;
+    out[1] = ce;
+    out[2] = mse;
+    out[3] = kdv;
+    out[4] = kddv;
+  }
+}
+
+extern "C" int tdeed_loss_opt(const float* head_out, int rows, int ld, int K1, const int64_t* hard, const float* soft,
+                              const float* cls_w, int displ_col, const float* labelD, const float* teacher, int ld_t,
+                              int displ_col_t, float alpha, float temperature, float displ_weight, float label_smoothing,
+                              float focal_gamma, float grad_scale, float* out5, float* dhead, void* stream) {
+  TD_CHECK(head_out && cls_w && out5 && (hard || soft), "loss_opt: null pointer");
+  TD_CHECK(rows > 0 && K1 > 0 && K1 <= ld && displ_col < ld, "loss_opt: bad sizes");
+  TD_CHECK(label_smoothing >= 0.f && label_smoothing <= 1.f, "loss_opt: label_smoothing %g outside [0, 1]", (double)label_smoothing);
+  TD_CHECK(focal_gamma >= 0.f && focal_gamma <= 3.0e38f, "loss_opt: focal_gamma %g (non-negative and finite)", (double)focal_gamma);
+  if (teacher) {
+    TD_CHECK(K1 <= ld_t && displ_col_t < ld_t, "loss_opt: bad teacher sizes");
+    TD_CHECK(alpha >= 0.f && alpha <= 1.f && temperature > 0.f && displ_weight >= 0.f, "loss_opt: bad alpha / temperature / weight");
+    TD_CHECK(displ_weight == 0.f || (displ_col >= 0 && displ_col_t >= 0), "loss_opt: displ_weight without both displacement columns");
+  } else {
+    TD_CHECK(alpha == 0.f && displ_weight == 0.f, "loss_opt: alpha / displ_weight without a teacher");
+    temperature = 1.0f;
+  }
+  hipLaunchKernelGGL(loss_opt_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, head_out, rows, ld, K1, hard, soft,
+                     cls_w, displ_col, labelD, teacher, ld_t, displ_col_t, alpha, temperature, displ_weight,
+                     label_smoothing, focal_gamma, grad_scale, out5, dhead);
+  TD_LAUNCH_CHECK("loss_opt");
+  return TDEED_OK;
+}
+
 // ------------------------------------------------------------------------------------------ heads backward
 // out = x W^T + b (x [rows][C] in T, W fp32 [n_out][C]):  dx = dout W (written in T),
 // dW[o][c] = sum_r dout[r][o] x[r][c], db[o] = sum_r dout[r][o]   (fp32, deterministic two-stage reduction).

@@ -335,6 +335,7 @@ class TDEEDModel:
         self._kd = None                 # distill_from(): (teacher, teacher_dtype, settings)
         self._kd_last = None            # the teacher's head buffer of the last distillation step (a reference, not a copy)
         self.loss_parts = None          # after a training epoch with a teacher: means of ce / mse / kd / kd_displ
+        self._loss_opt = None           # loss_options(): dict(label_smoothing, focal_gamma, class_weights) or None
 
     # BaseRGBModel (modules.py:35-55)
     def get_optimizer(self, opt_args):
@@ -392,6 +393,31 @@ class TDEEDModel:
         self._kd = (teacher, teacher_dtype, dict(alpha=alpha, temperature=temperature, displ_weight=displ_weight))
         self._kd_last, self.loss_parts = None, None
         ms._kd_wanted = True
+        return self
+
+    def loss_options(self, label_smoothing=0.0, focal_gamma=0.0, class_weights=None):
+        """Options of the classification loss of the training epochs (opt-in; all-neutral arguments clear them):
+            ce = sum_r sum_c w_c t'_c (1 - p_c)^focal_gamma (-log p_c) / den,  t' = (1 - label_smoothing) t + label_smoothing / K1
+        with t the one-hot label (or the mixup soft label, so mixup composes with smoothing) and den = sum_r w[y_r] (hard
+        labels) or the number of frames (soft labels): focal_gamma = 0 is F.cross_entropy(weight=, label_smoothing=).
+        class_weights: one finite non-negative weight per class, background first; it replaces the [1, fg_weight, ...]
+        vector, so epoch()'s fg_weight is ignored in training epochs while it is set.  Value and gradient come from one
+        launch (ops.loss_opt), with the distillation terms of distill_from() on top when a teacher is set.  epoch() still
+        returns the mean of the total; `loss_parts` holds the means of ce and mse (and kd, kd_displ with a teacher).
+        Validation epochs keep the plain loss, so that validation losses stay comparable across runs.
+        The options are not part of state_dict().  ValueError: ranges (0 <= label_smoothing <= 1, focal_gamma >= 0 and
+        finite), a class_weights vector of another length or with a negative / non-finite entry, the joint-dataset double
+        head."""
+        eps, gamma, cw = ops.check_loss_options(label_smoothing, focal_gamma, class_weights, self._num_classes)
+        if eps == 0.0 and gamma == 0.0 and cw is None:
+            self._loss_opt = None
+            if self._kd is None:
+                self.loss_parts = None
+            return self
+        if self._model._double_head:
+            raise ValueError("loss_options: the joint-dataset double head is not covered")
+        self._loss_opt = dict(label_smoothing=eps, focal_gamma=gamma, class_weights=cw)
+        self.loss_parts = None
         return self
 
     def _teacher_head(self):
@@ -1073,7 +1099,10 @@ def _train_epoch_impl(self, loader, optimizer, lr_scheduler, acc_grad_iter, fg_w
     self._model.train()
     optimizer.zero_grad()
     total = torch.zeros((), dtype=torch.float32, device=self.device)
-    parts = None if self._kd is None else torch.zeros(5, dtype=torch.float32, device=self.device)
+    opts = self._loss_opt
+    if opts is not None and self._model._double_head:
+        raise ValueError("loss_options: the joint-dataset double head is not covered")
+    parts = None if self._kd is None and opts is None else torch.zeros(5, dtype=torch.float32, device=self.device)
     self.loss_parts = None
     n = 0
     cur = torch.cuda.current_stream()
@@ -1115,12 +1144,12 @@ def _train_epoch_impl(self, loader, optimizer, lr_scheduler, acc_grad_iter, fg_w
             head = (pred["_head_out"] if isinstance(pred, dict) else pred).reshape(B * T, -1)
             scale = 1.0 / acc_grad_iter
             # distillation: the teacher's eval-mode forward on the student's view, on this stream, before the loss
-            thead, kd = (None, None) if parts is None else self._teacher_head()
+            thead, kd = (None, None) if self._kd is None else self._teacher_head()
             loss, dhead = eng.temporal.loss_fwd_bwd(
                 head, B, T, None if label is None else label.reshape(-1).contiguous(),
                 labelD=None if labelD is None else labelD.reshape(-1).contiguous(),
                 soft=None if soft is None else soft.reshape(B * T, -1).contiguous(), fg_weight=fg_weight, dataset=dataset,
-                teacher=thead, kd=kd)
+                teacher=thead, kd=kd, loss=opts)
             last = (batch_idx + 1) % acc_grad_iter == 0
             # data parallel (one process per GPU under torchrun): the bucket all-reduces of the step's last micro-batch are
             # enqueued from inside the backward; optimizer.step() waits for them on the device
@@ -1142,7 +1171,7 @@ def _train_epoch_impl(self, loader, optimizer, lr_scheduler, acc_grad_iter, fg_w
     self._model._engines = {}                      # the inference engines hold packed copies of the old weights
     if parts is not None:
         p = [float(v) / max(n, 1) for v in parts.tolist()]           # the epoch's one host synchronisation
-        self.loss_parts = dict(ce=p[1], mse=p[2], kd=p[3], kd_displ=p[4])
+        self.loss_parts = dict(ce=p[1], mse=p[2], kd=p[3], kd_displ=p[4]) if self._kd is not None else dict(ce=p[1], mse=p[2])
         return p[0]
     return float(total.item()) / max(n, 1)
 

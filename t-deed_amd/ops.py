@@ -737,6 +737,75 @@ def loss_kd(head_out, K1, cls_w, teacher, hard=None, soft=None, displ_col=-1, la
     return out, dhead
 
 
+def check_loss_options(label_smoothing=0.0, focal_gamma=0.0, class_weights=None, K1=None):
+    """Ranges and shapes of the loss options -> (label_smoothing, focal_gamma as floats, class_weights as a tuple of K1
+    floats or None); ValueError with the offending value outside them: 0 <= label_smoothing <= 1, focal_gamma >= 0 and
+    finite, class_weights a vector of K1 finite non-negative numbers."""
+    eps, gamma = float(label_smoothing), float(focal_gamma)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"label_smoothing must lie in [0, 1], got {eps}")
+    if not (gamma >= 0.0 and gamma < float("inf")):
+        raise ValueError(f"focal_gamma must be non-negative and finite, got {gamma}")
+    if class_weights is not None:
+        w = torch.as_tensor(class_weights).detach().cpu().double()
+        if w.dim() != 1 or (K1 is not None and w.numel() != K1) or w.numel() == 0:
+            raise ValueError(f"class_weights must be a vector of {K1 if K1 is not None else 'K1'} weights, got shape "
+                             f"{tuple(w.shape)}")
+        if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+            raise ValueError(f"class_weights must be finite and non-negative, got {w.tolist()}")
+        class_weights = tuple(w.tolist())
+    return eps, gamma, class_weights
+
+
+def loss_opt(head_out, K1, cls_w, teacher=None, hard=None, soft=None, displ_col=-1, labelD=None, teacher_displ_col=-1,
+             alpha=0.0, temperature=1.0, displ_weight=0.0, label_smoothing=0.0, focal_gamma=0.0, grad_scale=1.0,
+             want_grad=True):
+    """The loss with its options, value and gradient in one launch -> (out5 [total, ce, mse, kd, kd_displ], dhead (rows, ld)
+    | None):  ce = sum_r sum_c w_c t'_c (1 - p_c)^focal_gamma (-log p_c) / den  with t' = (1 - label_smoothing) t +
+    label_smoothing / K1 (t the one-hot of the hard label or the soft row) and den = sum_r w[y_r] (hard) or rows (soft), so
+    focal_gamma = 0 is F.cross_entropy(weight=cls_w, label_smoothing=).  cls_w: K1 free per-class weights.  With a
+    teacher head (rows, ld_t) the distillation terms of loss_kd() on top (total = (1-alpha) ce + mse + alpha kd +
+    displ_weight kd_displ); without one kd = kd_displ = 0 and alpha / displ_weight must be 0.  Neutral options give the bits
+    of loss_kd(), without a teacher those of loss() + loss_bwd()."""
+    label_smoothing, focal_gamma, _ = check_loss_options(label_smoothing, focal_gamma)
+    if head_out.dim() != 2:
+        raise ValueError("loss_opt: head_out (rows, ld)")
+    rows, ld = head_out.shape
+    ld_t = 0
+    if teacher is None:
+        if float(alpha) != 0.0 or float(displ_weight) != 0.0:
+            raise ValueError(f"loss_opt: alpha {alpha} / displ_weight {displ_weight} without a teacher")
+        alpha, temperature, displ_weight, teacher_displ_col = 0.0, 1.0, 0.0, -1
+    else:
+        alpha, temperature, displ_weight = check_kd(alpha, temperature, displ_weight)
+        if teacher.dim() != 2 or teacher.shape[0] != rows:
+            raise ValueError(f"teacher: {tuple(teacher.shape)} for {rows} rows")
+        ld_t = teacher.shape[1]
+        if not 0 < K1 <= ld_t:
+            raise ValueError(f"loss_opt: {K1} classes in a teacher head of {ld_t} columns")
+        if not -1 <= teacher_displ_col < ld_t:
+            raise ValueError(f"loss_opt: displacement column {teacher_displ_col} outside a teacher head of {ld_t} columns")
+        if displ_weight > 0.0 and (displ_col < 0 or teacher_displ_col < 0):
+            raise ValueError("loss_opt: displ_weight > 0 needs a displacement column in both heads")
+        _chk(teacher, "teacher", torch.float32)
+        if teacher.device != head_out.device:
+            raise ValueError(f"teacher on {teacher.device}, head_out on {head_out.device}")
+    if not 0 < K1 <= ld:
+        raise ValueError(f"loss_opt: {K1} classes in a head of {ld} columns")
+    if not -1 <= displ_col < ld:
+        raise ValueError(f"loss_opt: displacement column {displ_col} outside a head of {ld} columns")
+    if cls_w.numel() < K1:
+        raise ValueError(f"cls_w: {cls_w.numel()} weights for {K1} classes")
+    _chk_labels(head_out, hard, soft, labelD, K1)
+    _chk(cls_w, "cls_w", torch.float32)
+    out = torch.empty(5, dtype=torch.float32, device=head_out.device)
+    dhead = torch.empty_like(head_out) if want_grad else None
+    call("tdeed_loss_opt", ptr(head_out), rows, ld, K1, ptr(hard), ptr(soft), ptr(cls_w), displ_col, ptr(labelD), ptr(teacher),
+         ld_t, teacher_displ_col, alpha, temperature, displ_weight, label_smoothing, focal_gamma, float(grad_scale), ptr(out),
+         ptr(dhead), stream_ptr())
+    return out, dhead
+
+
 def loss2(head_out, B, T, K1a, K1b, dataset, hard, cls_w, displ_col=-1, labelD=None, want_grad=False, grad_scale=1.0,
           soft=None):
     """Double-head (joint dataset) loss of model.py:278-306 -> (out[3], dhead | None).  hard: int64 labels over the

@@ -256,16 +256,21 @@ class TemporalStack:
         return n_cls, (n_cls if self.radi > 0 else -1), double
 
     def loss_fwd_bwd(self, head_out, Bn, T, label, labelD=None, soft=None, fg_weight=5.0, grad_scale=1.0, dataset=None,
-                     teacher=None, kd=None):
+                     teacher=None, kd=None, loss=None):
         """Loss of model.py:308-319 (double head: 278-306) and its gradient w.r.t. head_out.
         teacher (opt-in): the teacher's head buffer (Bn*T, ld_t) fp32 with kd = dict(displ_col_t=, alpha=, temperature=,
         displ_weight=): the one ops.loss_kd launch instead of the two plain ones, loss then has five entries
-        [total, ce, mse, kd, kd_displ]."""
+        [total, ce, mse, kd, kd_displ].
+        loss (opt-in): dict(label_smoothing=, focal_gamma=, class_weights=) -- the one ops.loss_opt launch instead (with or
+        without a teacher), five entries as well; class_weights (K1 finite non-negative numbers, or None) replaces the
+        [1, fg_weight, ...] vector and is uploaded once per vector, like it."""
         n_cls, dcol, double = self.head_layout()
         ld = labelD if self.radi > 0 else None
         dev = head_out.device
         if teacher is not None and double:
             raise ValueError("distillation does not cover the joint-dataset double head")
+        if loss is not None and double:
+            raise ValueError("the loss options do not cover the joint-dataset double head")
         if double:
             names = self._head_names()
             K1a, K1b = self.sd[names[0] + ".weight"].shape[0], self.sd[names[1] + ".weight"].shape[0]
@@ -284,6 +289,22 @@ class TemporalStack:
         if fg_weight not in self._cls_w:        # built once per weight: no host->device copy inside a captured step
             self._cls_w[fg_weight] = torch.tensor([1.0] + [float(fg_weight)] * (K1 - 1), dtype=torch.float32, device=dev)
         cls_w = self._cls_w[fg_weight]
+        if loss is not None:
+            cw = loss.get("class_weights")
+            if cw is not None:
+                # the canonical tuple (trainer.loss_settings) is its own key; checked and uploaded once per vector: no
+                # host->device copy inside a captured step
+                key = ("class_weights",) + (cw if isinstance(cw, tuple) else ops.check_loss_options(class_weights=cw, K1=K1)[2])
+                if key not in self._cls_w:
+                    vec = ops.check_loss_options(class_weights=key[1:], K1=K1)[2]
+                    self._cls_w[key] = torch.tensor(vec, dtype=torch.float32, device=dev)
+                cls_w = self._cls_w[key]
+            kd = kd if teacher is not None else {}
+            return ops.loss_opt(head_out, K1, cls_w, teacher, hard=label, soft=soft, displ_col=dcol, labelD=ld,
+                                teacher_displ_col=kd.get("displ_col_t", -1), alpha=kd.get("alpha", 0.0),
+                                temperature=kd.get("temperature", 1.0), displ_weight=kd.get("displ_weight", 0.0),
+                                label_smoothing=loss.get("label_smoothing", 0.0), focal_gamma=loss.get("focal_gamma", 0.0),
+                                grad_scale=grad_scale)
         if teacher is not None:
             return ops.loss_kd(head_out, K1, cls_w, teacher, hard=label, soft=soft, displ_col=dcol, labelD=ld,
                                teacher_displ_col=kd.get("displ_col_t", -1), alpha=kd["alpha"], temperature=kd["temperature"],

@@ -49,6 +49,20 @@ def kd_settings(kd, teacher=None):
     return dict(ld_t=int(ld_t), displ_col_t=int(kd.get("displ_col_t", -1)), alpha=alpha, temperature=tau, displ_weight=beta)
 
 
+def loss_settings(loss, K1=None):
+    """The loss options of a step in their canonical form -- dict(label_smoothing, focal_gamma as floats, class_weights as a
+    tuple of K1 floats or None), what a graph handle records and compares -- from the caller's dict (None: the plain
+    loss).  Ranges and shapes: ops.check_loss_options."""
+    if loss is None:
+        return None
+    unknown = set(loss) - {"label_smoothing", "focal_gamma", "class_weights"}
+    if unknown:
+        raise ValueError(f"loss: unknown settings {sorted(unknown)}")
+    eps, gamma, cw = ops.check_loss_options(loss.get("label_smoothing", 0.0), loss.get("focal_gamma", 0.0),
+                                            loss.get("class_weights"), K1)
+    return dict(label_smoothing=eps, focal_gamma=gamma, class_weights=cw)
+
+
 class TrainEngine:
     """state: name -> tensor (reference state_dict names; fp32 parameters, BN buffers).  The parameters are moved into one
     flat buffer (`FlatParams`), `state` afterwards holds views into it."""
@@ -418,7 +432,7 @@ class TrainEngine:
                       tables=self._grad_tabs, role=role)
 
     def accumulate(self, frames_u8, label, labelD=None, soft=None, crop=None, flip=False, drop_masks=None, scale=1.0,
-                   first=True, dataset=None, fg_weight=5.0, reduce=False, teacher=None, kd=None):
+                   first=True, dataset=None, fg_weight=5.0, reduce=False, teacher=None, kd=None, loss=None):
         """forward + backward of one (micro-)batch; its gradients (times `scale`) go into the flat gradient buffer.
         reduce (data parallel, last micro-batch of a step): each bucket's all-reduce is enqueued as soon as the backward has
         produced it -- the temporal stack + heads travel over xGMI while the trunk backward runs."""
@@ -427,7 +441,7 @@ class TrainEngine:
             head_out, ctx.B, ctx.T, None if label is None else label.reshape(-1).contiguous(),
             labelD=None if labelD is None else labelD.reshape(-1).float().contiguous(),
             soft=None if soft is None else soft.reshape(-1, soft.shape[-1]).contiguous(), fg_weight=fg_weight,
-            dataset=dataset, teacher=teacher, kd=kd)
+            dataset=dataset, teacher=teacher, kd=kd, loss=loss)
         self.backward_and_write(ctx, dhead, scale, first, reduce)
         return loss
 
@@ -486,14 +500,16 @@ class TrainEngine:
         self.repack()
 
     def step(self, frames_u8, label, labelD=None, soft=None, crop=None, flip=False, drop_masks=None, lr_factor=1.0,
-             all_reduce=None, teacher=None, kd=None):
+             all_reduce=None, teacher=None, kd=None, loss=None):
         """forward + backward + (data parallel: bucketed gradient all-reduce overlapped with the backward) + AdamW.
         all_reduce: the older blocking form, a callable(flat_grad) (dist.all_reduce_mean_).  Returns [total, ce, mse]
-        (with a teacher head and its kd settings, TemporalTrain.loss_fwd_bwd: [total, ce, mse, kd, kd_displ])."""
-        loss = self.accumulate(frames_u8, label, labelD, soft, crop, flip, drop_masks,
-                               reduce=self.reducer is not None and all_reduce is None, teacher=teacher, kd=kd)
+        (with a teacher head and its kd settings, or with loss options -- `loss`, see loss_settings --,
+        TemporalTrain.loss_fwd_bwd: [total, ce, mse, kd, kd_displ])."""
+        out = self.accumulate(frames_u8, label, labelD, soft, crop, flip, drop_masks,
+                              reduce=self.reducer is not None and all_reduce is None, teacher=teacher, kd=kd,
+                              loss=loss_settings(loss, self.cfg["num_classes"] + 1))
         self.apply(lr_factor=lr_factor, all_reduce=all_reduce)
-        return loss
+        return out
 
     # ------------------------------------------------------------------ the step as one HIP graph
     def build_graph(self, *args, **kw):
@@ -508,7 +524,8 @@ class TrainEngine:
         finally:
             self._static_frames = None
 
-    def _build_graph(self, B, H, W, frames_dtype=torch.uint8, with_labelD=None, soft=False, fg_weight=5.0, kd=None):
+    def _build_graph(self, B, H, W, frames_dtype=torch.uint8, with_labelD=None, soft=False, fg_weight=5.0, kd=None,
+                     loss=None):
         """Capture weight re-packing + train-mode forward + loss + backward + gradient write-out for one batch geometry
         into a HIP graph (the eager step is host-bound: ~1700 launches).  Inputs live in static buffers
         (`.frames/.label/.labelD/.soft/.masks` of the returned handle); the AdamW launch stays outside the graph because lr
@@ -517,6 +534,8 @@ class TrainEngine:
         kd (opt-in distillation): dict(ld_t=, displ_col_t=, alpha=, temperature=, displ_weight=) -- the handle gets a static
         teacher head buffer `.teacher` (B*T, ld_t) that the captured loss launch reads; the teacher's own forward stays
         outside the graph (it is the inference engine's business), step_graph() copies its head in.
+        loss (opt-in loss options): dict(label_smoothing=, focal_gamma=, class_weights=) -- the captured loss launch is
+        ops.loss_opt with these settings (the class weight vector is uploaded by the eager warm-up, not inside the graph).
         Data parallel (default, `mode == "two"`): the step is captured as TWO graphs -- [re-pack, forward, loss, temporal
         backward, bucket 0 write-out] and [trunk backward, bucket 1 write-out] -- and bucket 0's all-reduce is launched
         between the two replays on the communicator's own stream, so it travels while the trunk backward runs.  With
@@ -540,6 +559,7 @@ class TrainEngine:
         h.labelD = torch.zeros((B, T), dtype=torch.float32, device=dev) if with_labelD else None
         h.masks = [torch.ones((B, T, C), dtype=self.dt, device=dev) for _ in range(2 if radi > 0 else 1)]
         h.kd = kd_settings(kd)
+        h.loss_opt = loss_settings(loss, K1)
         h.teacher = None if h.kd is None else torch.zeros((B * T, h.kd["ld_t"]), dtype=torch.float32, device=dev)
         red = self.reducer
         # the gradient write-out launches read their record tables from pinned host memory at every replay: the graph gets
@@ -562,7 +582,7 @@ class TrainEngine:
                 head_out, ctx.B, ctx.T, None if h.label is None else h.label.reshape(-1),
                 labelD=None if h.labelD is None else h.labelD.reshape(-1),
                 soft=None if h.soft is None else h.soft.reshape(-1, h.soft.shape[-1]), fg_weight=fg_weight,
-                teacher=h.teacher, kd=h.kd)
+                teacher=h.teacher, kd=h.kd, loss=h.loss_opt)
             g_t = {}
             B_.LAZY_WGRAD = os.environ.get("TDEED_LAZY_WGRAD", "1") == "1"
             try:
@@ -587,7 +607,8 @@ class TrainEngine:
 
         def capture_one(in_graph):
             run = lambda: self.accumulate(h.frames, h.label, h.labelD, soft=h.soft, drop_masks=h.masks,      # noqa: E731
-                                          reduce=in_graph, fg_weight=fg_weight, teacher=h.teacher, kd=h.kd)
+                                          reduce=in_graph, fg_weight=fg_weight, teacher=h.teacher, kd=h.kd,
+                                          loss=h.loss_opt)
             # eager warm-up on a side stream (lazy kernel attributes / module loads must happen outside the capture); the
             # BatchNorm buffers it touches are restored afterwards
             side = new_stream()
@@ -661,14 +682,19 @@ class TrainEngine:
         return h
 
     def step_graph(self, h, frames, label, labelD=None, soft=None, drop_masks=None, lr=None, lr_factor=1.0, all_reduce=None,
-                   teacher=None, kd=None):
+                   teacher=None, kd=None, loss=None):
         """One optimisation step through a captured graph: refresh the static inputs, replay, all-reduce (DP), AdamW.
         teacher / kd: the teacher's head (B*T, ld_t) fp32 and the distillation settings of this call; they must be the
-        settings the handle was captured with (none for a handle built without kd)."""
+        settings the handle was captured with (none for a handle built without kd).  loss: the loss options of this call,
+        held to the handle's in the same way."""
         want = kd_settings(kd, teacher)
         if want != getattr(h, "kd", None):
             raise RuntimeError(f"this graph was captured under other distillation settings ({getattr(h, 'kd', None)}, the call "
                                f"has {want}): build_graph() again (make_step() does)")
+        want_loss = loss_settings(loss, self.cfg["num_classes"] + 1)
+        if want_loss != getattr(h, "loss_opt", None):
+            raise RuntimeError(f"this graph was captured under other loss options ({getattr(h, 'loss_opt', None)}, the call has "
+                               f"{want_loss}): build_graph() again (make_step() does)")
         if getattr(h, "frozen", frozenset()) != self.frozen:
             raise RuntimeError("this graph was captured under another set of frozen parameters: build_graph() again "
                                "(make_step() does) after set_groups()")
@@ -713,26 +739,31 @@ class TrainEngine:
         return h.loss
 
     def make_step(self, B, H, W, frames, label, labelD=None, drop_masks=None, use_graph=True, world=1, all_reduce=None,
-                  kd=None):
+                  kd=None, loss=None):
         """A zero-argument callable running one optimisation step on the given (static) batch: through the captured HIP graph
         or eagerly; for world > 1 the flat gradient buffer is all-reduced (RCCL) before AdamW.  all_reduce: a callable
         (flat_grad) replacing the bucketed reduction (the bench's "no communication" arm passes a no-op).
         kd (opt-in distillation): dict(teacher=the teacher's head tensor (B*T, ld_t) fp32 -- read at every call, so the
-        caller refreshes it in place --, displ_col_t=, alpha=, temperature=, displ_weight=)."""
+        caller refreshes it in place --, displ_col_t=, alpha=, temperature=, displ_weight=).
+        loss (opt-in loss options): dict(label_smoothing=, focal_gamma=, class_weights=)."""
         ar = all_reduce
+        los = loss_settings(loss, self.cfg["num_classes"] + 1)
         tch = None if kd is None else kd["teacher"]
         kds = kd_settings(kd, tch)
         if world > 1 and self.reducer is None:
             self.set_reducer("auto")
         if not use_graph:
-            return lambda: self.step(frames, label, labelD, drop_masks=drop_masks, all_reduce=ar, teacher=tch, kd=kds)
+            return lambda: self.step(frames, label, labelD, drop_masks=drop_masks, all_reduce=ar, teacher=tch, kd=kds,
+                                     loss=los)
         hnd = getattr(self, "last_graph", None)
         if (hnd is None or getattr(hnd, "geom", None) != (B, H, W) or getattr(hnd, "frozen", frozenset()) != self.frozen
-                or getattr(hnd, "prefix", ((), 0)) != (self.eval_prefix, self.prefix_gen) or getattr(hnd, "kd", None) != kds):
-            hnd = self.build_graph(B, H, W, kd=kds)
+                or getattr(hnd, "prefix", ((), 0)) != (self.eval_prefix, self.prefix_gen) or getattr(hnd, "kd", None) != kds
+                or getattr(hnd, "loss_opt", None) != los):
+            hnd = self.build_graph(B, H, W, kd=kds, loss=los)
             hnd.geom = (B, H, W)
         self.last_graph = hnd                                    # (tests / the bench line read .mode)
-        return lambda: self.step_graph(hnd, frames, label, labelD, drop_masks=drop_masks, all_reduce=ar, teacher=tch, kd=kds)
+        return lambda: self.step_graph(hnd, frames, label, labelD, drop_masks=drop_masks, all_reduce=ar, teacher=tch, kd=kds,
+                                       loss=los)
 
     def lr_factor(self, warmup_steps, cosine_steps):
         f = warmup_cosine_lr(self.sched_step, warmup_steps, cosine_steps)
