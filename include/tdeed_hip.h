@@ -589,6 +589,20 @@ int tdeed_rows_gather_seg(const void* maps, int rows, long row_bytes, int L_tota
 int tdeed_stitch_scores_seg(const float* clip_scores, int V, int n, int T, int K1, const int* starts, const int* seg_off,
                             const int* clip_off, int nv, int count_all, int L_total, float* track_sum, int* support,
                             float* mean_out, void* stream);
+/* tdeed_stitch_scores_seg for ONE video whose length is not known yet, one launch per batch of clips.  State between the
+ * launches: ring_sum fp32 [ring_rows][K1] and ring_sup int32 [ring_rows], frame p in row p % ring_rows, zero before the
+ * first launch.  clip_scores fp32 [V][B][T][K1]: the scores of this batch; starts: DEVICE int32[B], ascending, and ascending
+ * over the launches.  Host scalars: lo = rows final before this launch, final_hi = rows final after it (no later clip covers
+ * a frame below it), limit = frames that exist (frames at or beyond it are not touched).  One thread per frame p in [lo,
+ * min(limit, max(final_hi, starts[B-1] + T))) adds the batch's clips onto its ring row as tdeed_stitch_scores_seg does (same
+ * order, same support rule); for p < final_hi it writes out_sum[p - lo], out_sup[p - lo] and out_mean[p - lo] (or NULL) =
+ * sum / float(max(support, 1)) and zeroes the ring row.  Over the launches of a stream the rows carry the bits of one
+ * tdeed_stitch_scores_seg launch over the whole clip list.  The caller's duties: no clip of the batch covers a frame below lo,
+ * and the frames of one launch fit the ring (ring_rows >= T + (B - 1) * (stride of the clip grid)).  B = 0 is legal (clip_scores
+ * and starts may be NULL): it only writes out [lo, final_hi).  out_* may be NULL when final_hi == lo.  No atomics. */
+int tdeed_stitch_live(const float* clip_scores, int V, int B, int T, int K1, const int* starts, int count_all, int lo,
+                      int final_hi, int limit, int ring_rows, float* ring_sum, int* ring_sup, float* out_sum, int* out_sup,
+                      float* out_mean, void* stream);
 /* mean fp32 [L_total][K1] (tdeed_stitch_scores_seg's mean_out).  pred int32[L_total]: first maximum of each row (np.argmax),
  * pred_score fp32[L_total] that entry; pred_u8 (or NULL; K1 <= 256): pred in one byte per frame, the form in which it is
  * copied to the host.  Per video v and class c >= 1 the frames with mean[f][c] >= hr_threshold (fp32 comparison,

@@ -204,6 +204,7 @@ _SIGS = {
     "tdeed_rows_gather": ([P, c_int, c_long, c_int, c_int, P, c_int, c_int, P, P], c_int),
     "tdeed_rows_gather_seg": ([P, c_int, c_long, c_int, c_int, P, P, P, c_int, c_int, P, P], c_int),
     "tdeed_stitch_scores_seg": ([P, c_int, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, P, P, P, P], c_int),
+    "tdeed_stitch_live": ([P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P], c_int),
     "tdeed_frame_events_seg": ([P, P, c_int, c_int, c_int, c_int, c_float, P, P, P, P, P, P], c_int),
     "tdeed_nms_track_seg_workspace": ([c_int, c_int, c_int], c_long),
     "tdeed_nms_track_seg_threads": ([c_int], c_int),

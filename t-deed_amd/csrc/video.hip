@@ -243,3 +243,59 @@ extern "C" int tdeed_stitch_scores_seg(const float* clip_scores, int V, int n, i
   TD_LAUNCH_CHECK("stitch_scores_seg");
   return TDEED_OK;
 }
+
+// =========================================================================== live stitching
+// stitch_scores_seg for a stream whose length is not known yet: one launch per BATCH of clips, the partial sums carried
+// between launches in a ring -- ring_sum fp32 [R][K1], ring_sup int32 [R], frame p in row p % R.  One thread per frame p in
+// [lo, hi), hi = min(limit, max(final_hi, starts[B-1] + T)): the rows that become final with this launch and the rows the
+// batch touches.  The thread runs stitch_frame over the batch's clips on its ring row -- over the launches of a stream the
+// additions stitch_scores_seg_kernel performs over the whole clip list, in its order, each partial sum stored as the fp32
+// it is -- and, when p < final_hi (no later clip covers p), writes the row out at p - lo and zeroes the ring row for frame
+// p + R.  The caller's duties: clips ascending over the launches, no clip of this batch covers a frame below lo, and
+// hi - lo <= R (the rows of one launch are distinct).  No atomics, no LDS.
+__global__ __launch_bounds__(256) void stitch_live_kernel(const float* __restrict__ clip_scores, int V, int B, int T, int K1,
+                                                          const int* __restrict__ starts, int count_all, int lo, int final_hi,
+                                                          int limit, int R, float* __restrict__ ring_sum,
+                                                          int* __restrict__ ring_sup, float* __restrict__ out_sum,
+                                                          int* __restrict__ out_sup, float* __restrict__ out_mean) {
+  const long touch = B > 0 ? (long)starts[B - 1] + T : 0;     // one past the last frame the batch touches
+  long hi = touch > final_hi ? touch : final_hi;
+  hi = hi < limit ? hi : limit;
+  const long pl = (long)lo + (long)blockIdx.x * 256 + threadIdx.x;
+  if (pl >= hi) return;
+  TD_DEV_ASSERT(hi - lo <= R);
+  TD_DEV_ASSERT(B == 0 || lo == 0 || starts[0] >= lo);
+  const int p = (int)pl;
+  const unsigned row = (unsigned)p % (unsigned)R;
+  const bool fin = p < final_hi;
+  float* s = ring_sum + (long)row * K1;
+  int* sup = ring_sup + row;
+  const long o = (long)(p - lo);
+  stitch_frame(clip_scores, V, B, T, K1, starts, 0, B, count_all, p, s, sup, fin && out_mean ? out_mean + o * K1 : nullptr);
+  if (!fin) return;
+  for (int k = 0; k < K1; ++k) {
+    out_sum[o * K1 + k] = s[k];
+    s[k] = 0.f;
+  }
+  out_sup[o] = *sup;
+  *sup = 0;
+}
+
+extern "C" int tdeed_stitch_live(const float* clip_scores, int V, int B, int T, int K1, const int* starts, int count_all, int lo,
+                                 int final_hi, int limit, int ring_rows, float* ring_sum, int* ring_sup, float* out_sum,
+                                 int* out_sup, float* out_mean, void* stream) {
+  TD_CHECK(ring_sum && ring_sup, "stitch_live: null pointer");
+  TD_CHECK(V > 0 && B >= 0 && T > 0 && K1 > 0 && ring_rows > 0, "stitch_live: bad sizes");
+  TD_CHECK(B == 0 || (clip_scores && starts), "stitch_live: a batch of %d clips without scores or starts", B);
+  TD_CHECK(count_all == 0 || count_all == 1, "stitch_live: count_all must be 0 or 1");
+  TD_CHECK(0 <= lo && lo <= final_hi && final_hi <= limit, "stitch_live: rows [%d, %d) become final of %d frames", lo, final_hi,
+           limit);
+  TD_CHECK(final_hi - lo <= ring_rows, "stitch_live: %d rows become final, the ring holds %d", final_hi - lo, ring_rows);
+  TD_CHECK(final_hi == lo || (out_sum && out_sup), "stitch_live: rows become final and there is nowhere to write them");
+  const long rows = (long)limit - lo < ring_rows ? (long)limit - lo : ring_rows;      // no launch touches more
+  if (rows <= 0) return TDEED_OK;
+  hipLaunchKernelGGL(stitch_live_kernel, dim3((unsigned)cdiv(rows, 256)), dim3(256), 0, (hipStream_t)stream, clip_scores, V, B, T,
+                     K1, starts, count_all, lo, final_hi, limit, ring_rows, ring_sum, ring_sup, out_sum, out_sup, out_mean);
+  TD_LAUNCH_CHECK("stitch_live");
+  return TDEED_OK;
+}

@@ -568,6 +568,39 @@ class TDEEDModel:
         self._one_video_stats()
         return out[0]
 
+    def live_scorer(self, frame_shape, overlap_len=None, pad_len=5, batch_size=1, augment=False, use_amp=True, ring_frames=None):
+        """Score a video whose length is not known yet -- a camera, a feed, a file still being written: -> `live.LiveScorer`.
+        Frames are pushed as they arrive and the FINAL rows of predict_video's track come back.
+
+        The clip grid start_j = -pad_len + j * (clip_len - overlap_len) does not depend on the length, so a clip is scored
+        the moment its last frame has arrived, and a row is final once the next clip to be scored starts after it
+        (`liveplan`).  Batches of `batch_size` clips run only when full while the stream is open and close() cuts the rest
+        the same way: they are predict_video's batches, so for ANY split of a video into pushes the concatenated sums and
+        support equal predict_video(frames, overlap_len=, pad_len=, batch_size=, augment=, use_amp=) bit for bit, and the
+        mean equals ops.stitch_scores(..., mean=True)'s.  Custom clip starts are not offered: the closed-form grid is what
+        makes rows final.  frame_shape: (3,H,W) of the sampled frames.
+
+        push(frames): uint8 (m,3,H,W), m >= 1, a host tensor (pinned or pageable) or a device tensor; the caller's buffer is
+        free when push returns (host frames are staged into pinned memory of the scorer's own, `video_chunk_bytes` at a time,
+        and go up on the copy stream into a ring of `ring_frames` rows, frame p in row p % ring_frames; a row is overwritten
+        only behind the event of the last batch that read it).  Every complete batch runs as a batch of predict_video does
+        (ring gather, both views when augment, post-processing, alternating engine slots) and ops.stitch_live follows on
+        its stream: it adds the batch onto a score ring of liveplan.track_ring_rows(batch_size) rows and writes out the rows
+        that became final.  -> (first_row, sums (r,K+1) float32, support (r,) int32, mean (r,K+1) float32) numpy, rows
+        consecutive across calls, r may be 0.  A push that completes no batch does not synchronise the host, one that does
+        synchronises once, at its end; last_push_stats (host_syncs, batches, rows, frames_h2d_bytes) tells which.
+        close(): runs the remaining clips, their windows cut at the length, and returns all remaining rows; afterwards push
+        raises RuntimeError.  reset(): a new stream on the same buffers and graphs.  frames_pushed, rows_final,
+        latency_frames = clip_len - 1 + (batch_size - 1) * (clip_len - overlap_len): a frame's row comes back at most that
+        many frames after it.
+
+        Raises before any launch: TypeError / ValueError for a wrong dtype, rank or geometry, ValueError for ring_frames
+        below liveplan.frame_ring_rows (naming the minimum), and close() raises predict_video's ValueError for a stream
+        without frames or without clips.  Suppression is left to the caller (ops.nms_track on the complete track): no prefix
+        of its output is final."""
+        from .live import LiveScorer
+        return LiveScorer(self, frame_shape, overlap_len, pad_len, batch_size, augment, use_amp, ring_frames)
+
     def spot_video(self, frames, classes, suppress=(("nms", 1, 0.01), ("snms", 3, 0.01)), high_recall_score_threshold=0.01,
                    clip_starts=None, overlap_len=None, pad_len=5, batch_size=8, augment=False, use_amp=True,
                    max_resident_bytes=16 << 30, reuse_frames=False, stream_frames=False):

@@ -1255,6 +1255,50 @@ def stitch_scores_seg(clip_scores, starts_dev, seg_off, clip_off, L, count_all=N
     return track_sum, support, mean_out
 
 
+def stitch_live(ring_sum, ring_sup, clip_scores, starts_dev, count_all, lo, final_hi, limit, T=None, out=None):
+    """stitch_scores for a stream whose length is not known yet, one launch per batch (evalutil's twin: liveplan.live_stitch_ref,
+    the schedule: liveplan.LiveSchedule).  ring_sum fp32 (R,K1) / ring_sup int32 (R,): the state between launches, frame p in
+    row p % R, zero before the first launch.  clip_scores fp32 (V,B,T,K1): the scores of this batch, starts_dev int32 (B,)
+    ascending, on the device; both None for a launch that only emits rows (then T is needed).  lo / final_hi: rows final
+    before / after this launch, limit: frames that exist.  -> (sums (final_hi - lo, K1), support (final_hi - lo,) int32, mean
+    (final_hi - lo, K1)): the rows that became final, with the bits of stitch_scores over the whole clip list.  out: three
+    tensors of those shapes to write into instead of fresh ones."""
+    if not isinstance(ring_sum, torch.Tensor) or ring_sum.dtype != torch.float32 or ring_sum.dim() != 2 \
+            or not ring_sum.is_contiguous() or not ring_sum.is_cuda:
+        raise TypeError("stitch_live: ring_sum must be a contiguous float32 (R,K1) tensor on the device")
+    R, K1 = ring_sum.shape
+    dev = ring_sum.device
+    _chk_table(ring_sup, R, dev, "stitch_live", "ring_sup")
+    lo, final_hi, limit = int(lo), int(final_hi), int(limit)
+    if not 0 <= lo <= final_hi <= limit or final_hi - lo > R:
+        raise ValueError(f"stitch_live: rows [{lo}, {final_hi}) become final of {limit} frames in a ring of {R} rows")
+    if clip_scores is None:
+        if starts_dev is not None or T is None:
+            raise ValueError("stitch_live: a launch without scores has no starts and needs T")
+        V, B, T = 1, 0, int(T)
+    else:
+        if not isinstance(clip_scores, torch.Tensor) or clip_scores.dim() != 4 or clip_scores.dtype != torch.float32 \
+                or not clip_scores.is_contiguous() or clip_scores.device != dev:
+            raise TypeError("stitch_live: clip_scores must be a contiguous float32 (V,B,T,K1) tensor on the rings' device")
+        V, B, Ts, k1 = clip_scores.shape
+        if k1 != K1 or B < 1 or (T is not None and int(T) != Ts):
+            raise ValueError(f"stitch_live: scores {tuple(clip_scores.shape)} for rings of {K1} columns and T={T}")
+        T = Ts
+        _chk_table(starts_dev, B, dev, "stitch_live", "starts")
+    n = final_hi - lo
+    if out is None:
+        out = (torch.empty((n, K1), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev),
+               torch.empty((n, K1), dtype=torch.float32, device=dev))
+    sums, support, mean = out
+    for x, shape, dt in ((sums, (n, K1), torch.float32), (support, (n,), torch.int32), (mean, (n, K1), torch.float32)):
+        if not isinstance(x, torch.Tensor) or tuple(x.shape) != shape or x.dtype != dt or not x.is_contiguous() or x.device != dev:
+            raise ValueError(f"stitch_live: out must be contiguous (sums, support, mean) of {n} rows on the rings' device")
+    call("tdeed_stitch_live", ptr(clip_scores), V, B, T, K1, ptr(starts_dev), int(bool(count_all)), lo, final_hi, limit, R,
+         ptr(ring_sum), ptr(ring_sup), ptr(sums) if n else None, ptr(support) if n else None, ptr(mean) if n else None,
+         stream_ptr())
+    return sums, support, mean
+
+
 def frame_events_seg(mean, seg_off, max_len, hr_threshold=0.01, pred_u8=None, first_init=None):
     """frame_events per video of a packed track: mean fp32 (sum L,K1), seg_off int32 (nv+1,) on the device, max_len the
     longest video (a host number).  -> (pred (sum L,) int32, pred_score (sum L,) fp32, first_frame (nv,K1) int32 in
